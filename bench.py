@@ -22,11 +22,15 @@ HBM fraction of every rank ("roofline.per_rank").
 `python bench.py --gpus N` without a torchrun environment starts the N rank processes itself (a child
 `python -m torch.distributed.run` started BEFORE this process touches a GPU) and relays rank 0's JSON line.
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) including
+Prints ONE JSON line on rank 0 ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", ...) including
   "roofline":     trace-step algorithmic HBM bytes / its device time (HIP events on the launch stream)
+A plain run sets up, warms up, times --steps steps and prints that line, nothing more.  --full adds what takes runs of its own:
   "first_frame":  a fresh process's rt_ctx_create + scene build + rt_scene_upload + first rt_render ("first_frame_ms"), "alloc_bytes"
+  "value_host_inclusive": the same frame through rt_render to page-locked host memory
   "cpu_baseline": the CPU oracle in reference (stream) order, all host cores, bounded sample; built -O3 -march=native on
                   the box it is timed on when g++ is there (BASELINE.md's recipe), else the prebuilt -march=x86-64-v2 library
+  with N > 1 ranks: the config-2 leg under "also" and the rt_multi_render check under "in_library"
+--dump-outputs DIR writes what the last timed step computed (rank 0's framebuffer, its rays per depth) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -360,6 +364,30 @@ def init_ranks(dist, backend, device, rank, world, emit, timeout_s=None):
     done.set()
 
 
+# --dump-outputs stays under 64 MB: a frame of up to 4 M pixels (48 MB of f32 RGB; config 2 is 2.1 M) is written whole, a larger one
+# (config 3: 8.3 M pixels, 100 MB) as a seeded sample of 2 M pixels (24 MB) with their indices (16 MB)
+DUMP_WHOLE_PIXELS, DUMP_SAMPLE_PIXELS = 4_000_000, 2_000_000
+
+
+def dump_outputs(out_dir, frame, rays_per_depth):
+    """What the last timed step handed its caller, as float32 / float64 .npy files under out_dir:
+    framebuffer.npy [rows, nx, 3] (row 0 = bottom, as rt_render_device writes it), or for a frame of more than DUMP_WHOLE_PIXELS
+    pixels framebuffer_sample.npy [n, 3] at the flat pixel indices of framebuffer_sample_pixels.npy (the same every run);
+    rays_per_depth.npy: RtStats.rays_per_depth of that step (exact in float64)."""
+    import numpy as np
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    files = {"rays_per_depth": np.asarray(rays_per_depth, dtype=np.float64)}
+    n_pix = frame.shape[0] * frame.shape[1]
+    if n_pix <= DUMP_WHOLE_PIXELS:
+        files["framebuffer"] = frame
+    else:
+        pix = np.sort(np.random.default_rng(95).choice(n_pix, DUMP_SAMPLE_PIXELS, replace=False))
+        files["framebuffer_sample"] = frame.reshape(n_pix, 3)[pix]
+        files["framebuffer_sample_pixels"] = pix.astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def trace_roofline(trace_bytes, trace_s):
     achieved = trace_bytes / max(trace_s, 1e-12) / 1e9
     return round(achieved, 2), round(achieved / HBM_PEAK_GBPS, 5)
@@ -447,19 +475,28 @@ def main():
     ap.add_argument("--max-depth", type=int, default=50)
     ap.add_argument("--spp-slice", type=int, default=0)
     ap.add_argument("--band", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also the first-frame processes, the host-inclusive leg and the CPU baseline (one "
+                         "GPU), the config-2 leg and the in-library check (--gpus > 1); a plain run is set-up, warm-up and timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--timed-only", action="store_true",
-                    help="only the warm-up and the timed steps: no CPU baseline, no host-inclusive leg, no in-library check, no second "
-                         "workload (the runs that rocprofv3 counts: scripts/collect_traffic.py, collect_valu.py, the kernel statistics)")
+                    help="only the warm-up and the timed steps even with --full: no CPU baseline, no host-inclusive leg, no in-library "
+                         "check, no second workload (the runs that rocprofv3 counts: scripts/collect_traffic.py, collect_valu.py, the "
+                         "kernel statistics)")
     ap.add_argument("--in-library", action="store_true",
                     help="after the timed region, rank 0 also renders through rt_multi_render (one process, all --gpus devices, the RCCL "
-                         "gather inside the library) and reports bit-identity with rt_render; always on when --gpus > 1")
+                         "gather inside the library) and reports bit-identity with rt_render; always on with --full when --gpus > 1")
     ap.add_argument("--first-frame-child", action="store_true", help=argparse.SUPPRESS)  # (the fresh process of first_frame())
     ap.add_argument("--no-prepare", action="store_true", help=argparse.SUPPRESS)  # (first-frame child without the rt_prepare hint)
     ap.add_argument("--launcher-check", action="store_true",
                     help="rendezvous, world-size assertion and one framebuffer gather of a synthetic band buffer; no rendering "
                          "(the CPU test of the multi-rank launch path: RTOW_DIST_BACKEND=gloo, no GPU needed)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    extras = args.full and not args.timed_only  # the measurements beside the headline figure
 
     if args.first_frame_child:
         cfg = CONFIGS[args.config or 2]
@@ -484,11 +521,11 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # The reference renders ONE frame per process (main.rs:62-129) and its timer covers scene build + render (utils.rs:15-18):
-    # that frame is measured in a child process, twice — here, BEFORE this process has imported torch or touched the GPU (a
+    # with --full that frame is measured in a child process, twice — here, BEFORE this process has imported torch or touched the GPU (a
     # quiet device: nobody else holds or has just freed memory), and after the timed region while this process still holds its
     # own work buffers (a device with a tenant).  The second is `first_frame`, the first `first_frame_quiet_device`.
     ff_quiet = None
-    if world == 1 and not (args.timed_only or args.launcher_check):
+    if world == 1 and extras and not args.launcher_check:
         c0 = CONFIGS[args.config or 2]
         ff_quiet = first_frame(args.config or 2, args.nx or c0["nx"], args.ny or c0["ny"], args.spp or c0["spp"], args.max_depth)
 
@@ -553,6 +590,8 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the render path has no CPU fallback")
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)  # (before the run: an unwritable DIR fails here, not after the timed steps)
     device_index = local_rank % torch.cuda.device_count() if backend != "nccl" else local_rank
     torch.cuda.set_device(device_index)
     if world > 1:
@@ -588,8 +627,9 @@ def main():
         dist.all_reduce(c, op=op)
         return c
 
-    def run_workload(scene, w_nx, w_ny, w_spp_total, steps, warmup):
-        """warm-up, then exactly `steps` timed steps between fences; returns the aggregated measurements of all ranks"""
+    def run_workload(scene, w_nx, w_ny, w_spp_total, steps, warmup, keep_output=False):
+        """warm-up, then exactly `steps` timed steps between fences; returns the aggregated measurements of all ranks, the params
+        and (keep_output, on rank 0) the last step's frame in host memory, copied after the timed region"""
         params = rt.make_params(w_nx, w_ny, w_spp_total, max_depth=args.max_depth, seed=95, shard_band=args.band,
                                 shard_count=world, shard_id=rank, spp_slice=args.spp_slice)
         rows = renderer.shard_rows(params)
@@ -620,10 +660,12 @@ def main():
         t0 = time.perf_counter()
         stats = []
         for k in range(steps):
-            st, _ = step(True, k)  # reading the counters synchronises; the counters are part of the metric
+            st, full = step(True, k)  # reading the counters synchronises; the counters are part of the metric
             stats.append(st)
         fence()
         elapsed = time.perf_counter() - t0
+        output = full.cpu().numpy() if (keep_output and full is not None) else None  # (None on ranks other than 0)
+        del full
         gather_ms_local = 0.0
         if world > 1:
             gather_ms_local = sum((e if isinstance(e, float) else e[0].elapsed_time(e[1])) for e in ev) / max(steps, 1)
@@ -646,20 +688,24 @@ def main():
                  "bytes_algorithmic": s0.bytes_algorithmic, "seconds_device": s0.seconds_device,
                  "launches": sum(s.n_trace_launches for s in stats)}
         del local
-        return dict(elapsed_max=elapsed_max, rays_total=rays_total, gather_ms=gather_ms, per_rank=per_rank, rank0=rank0), params
+        return dict(elapsed_max=elapsed_max, rays_total=rays_total, gather_ms=gather_ms, per_rank=per_rank, rank0=rank0), params, \
+            (output, list(stats[-1].rays_per_depth))
 
     scene = rt.Scene.build(cfg["scene"], nx / ny)
     renderer.upload(scene)
-    meas, params = run_workload(scene, nx, ny, spp_total, args.steps, args.warmup)
+    meas, params, last = run_workload(scene, nx, ny, spp_total, args.steps, args.warmup, keep_output=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
+    del last
 
-    # With several GPUs and the default workload, the one-GPU headline frame rides along: config 2, weak scaling (every rank
+    # With several GPUs and the default workload (--full), the one-GPU headline frame rides along: config 2, weak scaling (every rank
     # 1080 / N rows x 256 N samples), two timed steps — the curve the round-3 lines were on
     also = None
-    if world > 1 and not args.config and not args.timed_only:
+    if world > 1 and not args.config and extras:
         c2 = CONFIGS[2]
         scene2 = rt.Scene.build(c2["scene"], c2["nx"] / c2["ny"])
         renderer.upload(scene2)
-        m2, _ = run_workload(scene2, c2["nx"], c2["ny"], c2["spp"] * world, 2, 1)
+        m2, _, _ = run_workload(scene2, c2["nx"], c2["ny"], c2["spp"] * world, 2, 1)
         also = (c2, m2)
         renderer.upload(scene)
 
@@ -667,7 +713,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     in_library = None
-    if rank == 0 and (args.in_library or world > 1) and not args.timed_only:
+    want_in_library = args.in_library or (world > 1 and args.full)
+    if rank == 0 and want_in_library and not args.timed_only:
         in_library = in_library_check(rt, scene, renderer, (nx, ny, spp_total, args.max_depth), world)
     if rank == 0:
         build_id = renderer.build_id
@@ -681,7 +728,7 @@ def main():
             out["also"]["roofline"] = {k: r2["roofline"][k] for k in ("achieved", "frac", "per_rank")}
             # weak scaling: every rank does the work of the one-GPU headline frame, whose committed line is the reference
             out["also"]["single_gpu_reference"] = single_gpu_reference(2, f"Mray/s (primary+secondary) at {c2['nx']}x{c2['ny']}/{c2['spp']}spp", build_id)
-        if world == 1 and not args.timed_only:
+        if world == 1 and extras:
             # the same frame handed to the HOST as the reference's output is (f32 frame + flipped RGB8 through rt_render into
             # page-locked memory of rt_host_alloc: the D2H copies included), never `value`: reported beside it
             renderer.render(scene.camera, params, want_rgb8=True, pinned=True)  # (the staging buffers' first touch)
@@ -691,16 +738,16 @@ def main():
                 _, _, sth = renderer.render(scene.camera, params, want_rgb8=True, pinned=True)
                 host_rays += sth.n_rays
             out["value_host_inclusive"] = round(host_rays / (time.perf_counter() - th0) / 1e6, 3)
-        if world == 1 and not args.timed_only:
+        if world == 1 and extras:
             # every number above is a warm, steady-state frame; the reference renders ONE frame per process (main.rs:62-129)
             ff = first_frame(config_id, nx, ny, spp_total, args.max_depth)
             out["first_frame"] = ff
             out["first_frame_quiet_device"] = ff_quiet
             out["first_frame_ms"] = ff.get("first_frame_ms")
             out["alloc_bytes"] = ff.get("alloc_bytes")
-        if args.in_library or world > 1:
+        if want_in_library:
             out["in_library"] = in_library
-        if world == 1 and not args.no_cpu_baseline and not args.timed_only:
+        if world == 1 and not args.no_cpu_baseline and extras:
             out["cpu_baseline"] = cpu_baseline(rt, scene, cfg["scene"], nx, ny, args.max_depth)
             out["speedup_vs_cpu_baseline"] = round(out["value"] / max(out["cpu_baseline"]["value"], 1e-9), 2)
         emit(out)

@@ -31,8 +31,8 @@ cp $out/traffic_config2.json $out/traffic_config4.json $out/traffic_config5.json
 fi
 if [[ $phase == *B* ]]; then
 prof=$(ls -d profiles/round* | sort -V | tail -1)
-step 300 $py bench.py --steps 20 --warmup 5 > $out/bench_config2.json 2> $out/bench_config2.err
-for c in 3 4 5; do step 300 $py bench.py --config $c --steps 3 --warmup 1 > $out/bench_config$c.json 2> $out/bench_config$c.err; done
+step 300 $py bench.py --full --steps 20 --warmup 5 > $out/bench_config2.json 2> $out/bench_config2.err
+for c in 3 4 5; do step 300 $py bench.py --full --config $c --steps 3 --warmup 1 > $out/bench_config$c.json 2> $out/bench_config$c.err; done
 for c in 2 4 5; do
   extra=""; [ $c != 2 ] && extra="--config $c"
   rm -rf $out/prof_tmp

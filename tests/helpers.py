@@ -12,6 +12,16 @@ def rmse_display(a, b):
     return float(np.sqrt(np.mean(d * d)))
 
 
+def hip_runtime():
+    """The HIP runtime the GPU library is bound to, as a ctypes library: its entry points are looked up through the library's own
+    handle.  ctypes.CDLL("libamdhip64.so") can name another copy (torch ships one), whose first call opens the GPU a second time in
+    the process and finds no device."""
+    import ctypes
+    from ray_tracing_in_one_weekend_amd import _ffi
+    _ffi.load_gpu_library()
+    return ctypes.CDLL(_ffi.GPU_LIB_PATH)
+
+
 def rays_on_scene(n, seed, center=(0.0, 0.5, 0.0), radius=12.0):
     """Unit-direction rays starting on a sphere around the scene pointing roughly inwards, plus
     rays starting just above the ground; keys are arbitrary."""

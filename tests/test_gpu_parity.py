@@ -14,7 +14,7 @@ import time
 import numpy as np
 import pytest
 
-from helpers import ctr_draw, display, path_keys, rays_on_scene, rmse_display
+from helpers import ctr_draw, display, hip_runtime, path_keys, rays_on_scene, rmse_display
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -900,7 +900,7 @@ def test_in_library_multi_gpu_entry_points(rt, renderer):
     reproduce rt_render bit for bit; (2) the assembly of an 8-GPU run goes through the same entry point
     (rt_deinterleave_bands) on 8 shards rendered one after the other into the layout the all_gather delivers."""
     import ctypes
-    hip = ctypes.CDLL("libamdhip64.so")  # the runtime the library itself is linked against (device buffers for part 2)
+    hip = hip_runtime()  # the runtime the library itself is linked against (device buffers for part 2)
     hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
     hip.hipMemset.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t]
     hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
@@ -1139,7 +1139,7 @@ def test_repeated_renders_reuploads_and_contexts(rt):
     """Buffers are reused across calls, scenes can be replaced, two contexts coexist, and nothing leaks."""
     import ctypes
 
-    hip = ctypes.CDLL("libamdhip64.so")  # the runtime the library itself is linked against
+    hip = hip_runtime()  # the runtime the library itself is linked against
 
     def free_bytes():
         f, tot = ctypes.c_size_t(), ctypes.c_size_t()
@@ -1194,7 +1194,7 @@ def _render_with_the_pool_grown(r, scene, p, limit_s=60.0):
 def _hip_memory():
     import ctypes
 
-    hip = ctypes.CDLL("libamdhip64.so")  # the runtime the library itself is linked against
+    hip = hip_runtime()  # the runtime the library itself is linked against
     hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
     hip.hipFree.argtypes = [ctypes.c_void_p]
 
@@ -2061,7 +2061,7 @@ def test_bench_two_ranks_render_and_gather(tmp_path):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["RTOW_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--nx", "960", "--ny", "540",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "1", "--warmup", "0", "--nx", "960", "--ny", "540",
                         "--spp", "16"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -2071,3 +2071,28 @@ def test_bench_two_ranks_render_and_gather(tmp_path):
     also = out["also"]
     assert also["workload"].startswith("config 2:") and also["scaling"] == "weak" and also["value"] > 0 and len(also["roofline"]["per_rank"]) == 2
     assert out["in_library"]["devices"] == 2  # (rt_multi_create over devices 0 and 1: fails on a one-GPU box, reported, never fatal)
+
+
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path, rt, renderer):
+    """A plain `python bench.py` is the headline line alone (nothing of --full), timed over exactly --steps steps; --dump-outputs
+    writes the last timed step's framebuffer, which is the frame rt_render makes of the same parameters bit for bit, and its rays
+    per depth."""
+    import json
+    import subprocess
+    import sys
+    nx, ny, spp = 320, 180, 8
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--nx", str(nx),
+                        "--ny", str(ny), "--spp", str(spp), "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["unit"] == "Mray/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert not {"first_frame", "first_frame_quiet_device", "value_host_inclusive", "cpu_baseline", "in_library", "also"} & set(out)
+    assert sorted(os.listdir(tmp_path / "out")) == ["framebuffer.npy", "rays_per_depth.npy"]
+    fb, rpd = np.load(tmp_path / "out" / "framebuffer.npy"), np.load(tmp_path / "out" / "rays_per_depth.npy")
+    assert fb.dtype == np.float32 and fb.shape == (ny, nx, 3) and rpd.dtype == np.float64
+    scene = rt.Scene.build("sphere_scene", nx / ny)
+    renderer.upload(scene)
+    img, _, st = renderer.render(scene.camera, rt.make_params(nx, ny, spp, max_depth=50, seed=95, shard_band=8))
+    assert np.array_equal(fb.view(np.uint32), img.view(np.uint32))
+    assert rpd.tolist() == [float(x) for x in st.rays_per_depth] and rpd.sum() == st.n_rays == out["config"]["rays_per_step_rank0"]
