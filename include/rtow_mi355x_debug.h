@@ -44,8 +44,14 @@ int rt_debug_render_parts(const RtCtx* ctx, char* buf, uint32_t cap);
  * options select between equivalent search structures, placements and orders so that tests can hold them against each
  * other, and so that measurements can vary one thing.  Same BITS with one stated exception: the closest-hit searches
  * (list walk, tree, grid, candidate lists) agree on every ray except those for which fp32 Sphere::hit (hitable.rs:75-91)
- * reports a root although the ray misses the sphere in exact arithmetic (cancellation at grazing incidence); a box or cell
- * test may cull such a false positive, the list walk cannot.  Measured: at most 8 of the 1.35e9 rays of config 2, each
+ * reports a root although the ray misses the sphere in exact arithmetic (cancellation at grazing incidence), and those for which
+ * fp32 reports a hit on a primitive below Translate / RotateY wrappers although the ray misses it under the exact ray map of its
+ * chain (hitable.rs:404-520 with the stored f32 offsets and sin / cos; the fp32 map rounds at the magnitude of every intermediate
+ * coordinate); a box or cell test may cull such a false positive, the list walk cannot.  Every culling bound holds the exact
+ * world region of its primitive widened by the rounding of that f32 map for rays that start among the primitives of the chain
+ * (rt_debug_world_bounds, error model in csrc/rt_api.hip).  A ray from farther out below a deep chain (1 per Translate plus 12 per
+ * RotateY summing to more than about 60) may meet two primitives at exact roots closer than the map can tell apart; which of the
+ * two a search reports is then a matter of rounding.  Measured: at most 8 of the 1.35e9 rays of config 2, each
  * proven a false positive in float64 by the tests.  Which of them the reference's own binary BvhNode would cull is unpinned.  0 is the library's own choice for every option.  Options marked
  * (upload) take effect at the next rt_scene_upload, the others at the next render. */
 enum RtDebugOption {
@@ -98,6 +104,23 @@ int rt_debug_scene_info(const RtCtx* ctx, RtSceneInfo* info);
  * cell lists; large[0..*n_large) = the spheres tested for every ray. */
 int rt_debug_grid_build(const RtFlatScene* scene, uint32_t cell_per_mille, uint32_t lds_budget, float grid[8], uint32_t dims[3],
                         uint32_t* cells, uint32_t* n_cells, uint16_t* refs, uint32_t* n_refs, uint32_t large[4], uint32_t* n_large);
+
+/* The world-space bounds rt_scene_upload culls with (host code only: no context, no GPU; the same function upload calls), for tests
+ * of the bounds of primitives below Translate / RotateY wrappers.  Arrays are caller-owned, any of them may be NULL; n_prims =
+ * n_spheres + n_rects (spheres first):
+ *   prim_box[6 * n_prims]         world box of every primitive after its wrapper chain, before the tree's pad (min xyz, max xyz);
+ *   prim_box_padded[6 * n_prims]  the box the tree builder stores for it;
+ *   world_sphere[4 * n_spheres]   centre and radius of every sphere in world space (a bare sphere: its own);
+ *   *n_entries                    in: capacity of the entry arrays, out: the number of world entries (primitives that are not a
+ *                                 medium boundary, then the media);
+ *   entry_id[*n_entries]          primitive i, or n_prims + medium m;
+ *   entry_box_padded[6 * ...]     the box the tree stores for the entry (a medium: around all of its boundary primitives);
+ *   entry_bs[4 * ...]             the bounding sphere k_primary_lists tests for it.
+ * Returns RT_ERR_INVALID for a scene rt_scene_upload would refuse for its geometry, wrappers or medium tags (a medium without
+ * boundary primitives included), or when *n_entries is too small (the
+ * needed count is then in *n_entries), else RT_OK. */
+int rt_debug_world_bounds(const RtFlatScene* scene, float* prim_box, float* prim_box_padded, float* world_sphere, uint32_t* n_entries,
+                          uint32_t* entry_id, float* entry_box_padded, float* entry_bs);
 
 #ifdef RT_PROFILE_LANES
 /* Diagnostic builds only (-DRT_PROFILE_LANES; absent from the product library): the lane-occupancy counters of

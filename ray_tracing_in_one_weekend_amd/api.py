@@ -202,6 +202,33 @@ def grid_build(scene, cell_per_mille=0, lds_budget=0):
             "dims": d, "cells": cells[:nc.value].reshape(d[2], d[1], d[0]), "refs": refs[:nr.value], "large": [int(large[k]) for k in range(nl.value)]}
 
 
+def world_bounds(scene):
+    """rt_debug_world_bounds (host code of the GPU library, no GPU): the world-space bounds rt_scene_upload culls with.
+    -> dict(prim_box f32 [n_prims, 2, 3] (before the tree's pad), prim_box_padded [n_prims, 2, 3], world_sphere [n_spheres, 4],
+    entry_id u32 [n_entries], entry_box_padded [n_entries, 2, 3], entry_bs [n_entries, 4]); primitives are the spheres, then the
+    rectangles; entries the primitives that are not a medium boundary, then the media (id n_prims + m)."""
+    lib = _ffi.load_gpu_library()
+    ptr = scene.flat_ptr if isinstance(scene, Scene) else C.pointer(scene)
+    fs = ptr.contents
+    n_prims = fs.n_spheres + fs.n_rects
+    cap = n_prims + fs.n_media
+    out = {"prim_box": np.zeros((max(n_prims, 1), 2, 3), np.float32), "prim_box_padded": np.zeros((max(n_prims, 1), 2, 3), np.float32),
+           "world_sphere": np.zeros((max(fs.n_spheres, 1), 4), np.float32), "entry_id": np.zeros(max(cap, 1), np.uint32),
+           "entry_box_padded": np.zeros((max(cap, 1), 2, 3), np.float32), "entry_bs": np.zeros((max(cap, 1), 4), np.float32)}
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    ne = C.c_uint32(cap)
+    rc = lib.rt_debug_world_bounds(ptr, fp(out["prim_box"]), fp(out["prim_box_padded"]), fp(out["world_sphere"]), C.byref(ne),
+                                   out["entry_id"].ctypes.data_as(C.POINTER(C.c_uint32)), fp(out["entry_box_padded"]), fp(out["entry_bs"]))
+    if rc != 0:
+        raise RtError(f"rt_debug_world_bounds failed ({rc})")
+    for k in ("prim_box", "prim_box_padded"):
+        out[k] = out[k][:n_prims]
+    out["world_sphere"] = out["world_sphere"][:fs.n_spheres]
+    for k in ("entry_id", "entry_box_padded", "entry_bs"):
+        out[k] = out[k][:ne.value]
+    return out
+
+
 def make_params(nx, ny, spp, max_depth=50, seed=95, shard_band=0, shard_count=1, shard_id=0, spp_slice=0, flags=0):
     p = RtParams()
     p.flags = flags

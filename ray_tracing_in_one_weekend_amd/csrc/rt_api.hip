@@ -451,6 +451,228 @@ int plan_slices(RtCtx* ctx, const RtParams* prm, uint64_t npix64, SlicePlan& pl)
     return RT_OK;
 }
 
+// World-space bounds the closest-hit search culls with, from a validated scene: rt_scene_upload builds the tree over `ent` and
+// k_primary_lists tests `ent_bs`; rt_debug_world_bounds hands the same arrays to the tests.
+struct WorldBounds {
+    std::vector<PrimBox> prim;        // per primitive (spheres, then rectangles), world space, before the tree's pad
+    std::vector<float4> world_sphere; // per sphere: world centre and radius of an instanced sphere (bare: its own)
+    std::vector<uint32_t> pxf, pmed;  // per primitive: innermost wrapper, medium
+    std::vector<PrimBox> ent;         // world entries: primitives that are not a medium boundary, then the media
+    std::vector<uint32_t> entry_ids;  // their ids (primitive i, or n_prims + medium m)
+    std::vector<float4> ent_bs;       // their bounding spheres
+};
+
+// f32 below / above a double
+float round_down(double x) {
+    float f = (float)x;
+    if ((double)f > x) f = std::nextafterf(f, -FLT_MAX);
+    return f;
+}
+float round_up(double x) {
+    float f = (float)x;
+    if ((double)f < x) f = std::nextafterf(f, FLT_MAX);
+    return f;
+}
+
+// Grows `box` (and `*ws`, a sphere's world sphere) to contain the region primitive i covers in world space under the exact ray map of
+// its chain.  The kernels map a world ray outermost wrapper first: Translate o -= q (hitable.rs:411), RotateY (x, z) -> (c x - s z,
+// s x + c z) (hitable.rs:483-492) with the STORED f32 s = sin, c = cos.  Those c, s lie off the unit circle (s2 = c^2 + s^2 = 1 +- 8e-8):
+// the exact inverse of a RotateY level is (x, z) -> (c x + s z, -s x + c z) / s2, and it scales x and z by 1 / sqrt(s2).  So an object
+// point goes to the world innermost wrapper first through these inverses, a rectangle's region is the hull of its four mapped corners,
+// and a sphere's the ellipsoid around its mapped centre with semi-axes r / S (x, z) and r (y), S = the product of sqrt(s2).
+// Error model: all of this runs in double.  A level rounds at most 6 times (s2: two; the rotation: two products, a sum, a quotient; a
+// Translate: one sum), each by 2^-53 of a value below 2 M, M = the largest magnitude any point takes on the way, and carries the error of
+// the levels inside it scaled by 1 / sqrt(s2) < 1 + 1e-7: n levels err by less than 16 n 2^-53 M, and S by 4 n 2^-53 of itself.  The
+// bound is widened by that and rounded outward to f32.
+// The kernels take the same map in f32, so the ray they test lies off the exact one, and the hit they report sits off the exact region
+// along the world ray: a box that held the exact region only would let the tree cull a primitive whose f32 root comes before the
+// box, behind the root of another primitive it already has (two hits a rounding apart, both real in exact arithmetic).  Error model
+// of the f32 map, for a ray whose origin at every level is no larger than M_l, the largest magnitude the primitive's own points take
+// at that level (a ray that starts among the primitives of the chain, or nearer the origin of each frame): a Translate rounds o - q
+// once, 2^-24 M_l per coordinate; a RotateY rounds two products and a sum of origin and of direction, 4 2^-24 M_l for the origin and
+// 4 2^-24 of the direction, which the root t carries over a distance below 2 M_l: 12 2^-24 M_l.  Later levels move these errors
+// without growing them (1 / sqrt(s2) < 1 + 1e-7), so the object-space hit lies within sqrt(3) 2^-24 sum_l c_l M_l of the primitive
+// (c = 1 per Translate, 12 per RotateY), and its world point within that over S.  The box is widened by this too.  A ray from
+// farther out errs in proportion to its distance; the tree's relative widening of the far plane (4e-6, rt_kernels.h) covers chains up
+// to sum c_l ~ 60 of it, and beyond, two real hits a rounding apart may come out in either order (rtow_mi355x_debug.h).
+void exact_world_region(const RtFlatScene* s, uint32_t i, PrimBox& box, float4* ws) {
+    const uint32_t x0 = i < s->n_spheres ? s->sph_xform[i] : s->rect_xform[i - s->n_spheres];
+    double pts[4][3];
+    int np = 1;
+    double r = 0.0;
+    if (i < s->n_spheres) {
+        pts[0][0] = s->sph_cx[i], pts[0][1] = s->sph_cy[i], pts[0][2] = s->sph_cz[i];
+        r = std::fabs((double)s->sph_r[i]);
+    } else {
+        const uint32_t j = i - s->n_spheres, ax = s->rect_axis[j];
+        const float* mn = s->rect_min + 3 * (size_t)j;
+        const float* mx = s->rect_max + 3 * (size_t)j;
+        const int ua = ax == 0 ? 1 : 0, va = ax == 2 ? 1 : 2;
+        np = 4;
+        for (int c = 0; c < 4; ++c) {
+            pts[c][ax] = mn[ax]; // the plane the hit test uses (hitable.rs:253)
+            pts[c][ua] = (c & 1) ? mx[ua] : mn[ua];
+            pts[c][va] = (c & 2) ? mx[va] : mn[va];
+        }
+    }
+    double mag = r, S = 1.0, f32_map = 0.0; // f32_map: sum_l c_l M_l
+    uint32_t n = 0;
+    for (int c = 0; c < np; ++c)
+        for (int k = 0; k < 3; ++k) mag = std::max(mag, std::fabs(pts[c][k]));
+    for (uint32_t x = x0; x != RT_NO_XFORM; x = s->xf_parent[x], ++n) {
+        const float* q = s->xf_param + 4 * (size_t)x;
+        const double sn = q[0], cs = q[1], s2 = cs * cs + sn * sn;
+        if (s->xf_type[x] == RT_XF_ROTATE_Y) S *= std::sqrt(s2);
+        double level_mag = r; // M_l: the points' magnitude on both sides of this level
+        for (int c = 0; c < np; ++c)
+            for (int k = 0; k < 3; ++k) level_mag = std::max(level_mag, std::fabs(pts[c][k]) + r);
+        for (int c = 0; c < np; ++c) {
+            double* p = pts[c];
+            if (s->xf_type[x] == RT_XF_TRANSLATE) {
+                for (int k = 0; k < 3; ++k) p[k] += (double)q[k];
+            } else {
+                const double px = p[0], pz = p[2];
+                p[0] = (cs * px + sn * pz) / s2, p[2] = (-sn * px + cs * pz) / s2;
+            }
+            for (int k = 0; k < 3; ++k) mag = std::max(mag, std::fabs(p[k])), level_mag = std::max(level_mag, std::fabs(p[k]) + r);
+        }
+        f32_map += (s->xf_type[x] == RT_XF_ROTATE_Y ? 12.0 : 1.0) * level_mag;
+    }
+    const double ulp = std::ldexp(1.0, -53);
+    const double half[3] = {r / S * (1.0 + 4.0 * n * ulp), r, r / S * (1.0 + 4.0 * n * ulp)}; // (0 for a rectangle)
+    const double e = 16.0 * (n + 1) * ulp * mag + 1.7321 * std::ldexp(f32_map, -24) / std::min(S, 1.0) * (1.0 + 1e-6);
+    for (int k = 0; k < 3; ++k) {
+        double lo = pts[0][k], hi = pts[0][k];
+        for (int c = 1; c < np; ++c) lo = std::min(lo, pts[c][k]), hi = std::max(hi, pts[c][k]);
+        box.mn[k] = std::min(box.mn[k], round_down(lo - half[k] - e));
+        box.mx[k] = std::max(box.mx[k], round_up(hi + half[k] + e));
+    }
+    if (ws) { // the world sphere keeps its centre and grows to hold the ellipsoid
+        const double dx = pts[0][0] - ws->x, dy = pts[0][1] - ws->y, dz = pts[0][2] - ws->z;
+        const double need = std::sqrt(dx * dx + dy * dy + dz * dz) + std::max(half[0], half[1]) + 2.0 * e;
+        if (need > (double)ws->w) ws->w = round_up(need);
+    }
+}
+
+void world_bounds(const RtFlatScene* s, WorldBounds& w) {
+    const uint32_t n_prims = s->n_spheres + s->n_rects;
+    w.prim.assign(n_prims, PrimBox{});
+    w.world_sphere.assign(s->n_spheres, make_float4(0.f, 0.f, 0.f, 0.f));
+    w.pxf.assign(n_prims, RT_NO_XFORM);
+    w.pmed.assign(n_prims, RT_NO_MEDIUM);
+    for (uint32_t i = 0; i < n_prims; ++i) {
+        const bool sph = i < s->n_spheres;
+        const uint32_t r = i - s->n_spheres;
+        w.pxf[i] = sph ? (s->sph_xform ? s->sph_xform[i] : RT_NO_XFORM) : (s->rect_xform ? s->rect_xform[r] : RT_NO_XFORM);
+        w.pmed[i] = sph ? (s->sph_medium ? s->sph_medium[i] : RT_NO_MEDIUM) : (s->rect_medium ? s->rect_medium[r] : RT_NO_MEDIUM);
+    }
+    for (uint32_t i = 0; i < s->n_spheres; ++i) {
+        const float c[3] = {s->sph_cx[i], s->sph_cy[i], s->sph_cz[i]};
+        const float r = std::fabs(s->sph_r[i]);
+        for (int k = 0; k < 3; ++k) w.prim[i].mn[k] = c[k] - r, w.prim[i].mx[k] = c[k] + r;
+        w.world_sphere[i] = make_float4(c[0], c[1], c[2], r);
+    }
+    for (uint32_t i = 0; i < s->n_rects; ++i) {
+        const uint32_t ax = s->rect_axis[i];
+        const float* mn = s->rect_min + 3 * (size_t)i;
+        const float* mx = s->rect_max + 3 * (size_t)i;
+        PrimBox& b = w.prim[s->n_spheres + i];
+        for (int k = 0; k < 3; ++k) b.mn[k] = std::min(mn[k], mx[k]), b.mx[k] = std::max(mn[k], mx[k]);
+        b.mn[ax] = mn[ax] - 0.0001f, b.mx[ax] = mn[ax] + 0.0001f; // the plane the hit test uses (hitable.rs:253)
+    }
+    // wrapped primitives: world-space bounds through the chain.  Two bounds, and the box is their hull:
+    //  * the float construction (corners through every wrapper from the inside out, as RotateY::new does at hitable.rs:455-473; the
+    //    centre of a sphere through the forward rotation) with its margins.  It is kept as a floor: on the scenes it was made for the
+    //    tree and the list walk agree bit for bit, and a smaller box would cull more fp32 false positives;
+    //  * the region the primitive covers under the chain's exact ray map (exact_world_region below).
+    // What the exact map misses and fp32 hits is a false positive of the wrapper transform: a box may cull it (rtow_mi355x_debug.h).
+    for (uint32_t i = 0; i < n_prims; ++i) {
+        const uint32_t x0 = w.pxf[i];
+        if (x0 == RT_NO_XFORM) continue;
+        if (i < s->n_spheres) {
+            // A sphere below Translate / RotateY wrappers is still a sphere: its world box is centre' +- r, not the
+            // box of the rotated box that RotateY::new computes (22 % wider per axis at 15 degrees, and the cloud of
+            // final_scene is 1 000 overlapping instanced spheres).  The exact test runs in object space on a ray
+            // whose transform rounds at the magnitude of the WORLD coordinates, so the box gets that slack.
+            double c[3] = {s->sph_cx[i], s->sph_cy[i], s->sph_cz[i]}, mag = std::fabs((double)s->sph_r[i]);
+            for (uint32_t x = x0; x != RT_NO_XFORM; x = s->xf_parent[x]) {
+                const float* q = s->xf_param + 4 * (size_t)x;
+                for (int k = 0; k < 3; ++k) mag = std::max(mag, std::fabs(c[k]));
+                if (s->xf_type[x] == RT_XF_TRANSLATE) {
+                    for (int k = 0; k < 3; ++k) c[k] += (double)q[k];
+                } else {
+                    const double sn = q[0], cs = q[1], cx = c[0], cz = c[2];
+                    c[0] = cs * cx + sn * cz, c[2] = -sn * cx + cs * cz;
+                }
+                for (int k = 0; k < 3; ++k) mag = std::max(mag, std::fabs(c[k]));
+            }
+            const double r = std::fabs((double)s->sph_r[i]), slack = 8e-6 * mag + 1e-30;
+            for (int k = 0; k < 3; ++k) w.prim[i].mn[k] = (float)(c[k] - r - slack), w.prim[i].mx[k] = (float)(c[k] + r + slack);
+            w.world_sphere[i] = make_float4((float)c[0], (float)c[1], (float)c[2], (float)(r + 2.0 * slack));
+            exact_world_region(s, i, w.prim[i], &w.world_sphere[i]);
+            continue;
+        }
+        PrimBox& b = w.prim[i];
+        for (uint32_t x = x0; x != RT_NO_XFORM; x = s->xf_parent[x]) {
+            const float* q = s->xf_param + 4 * (size_t)x;
+            if (s->xf_type[x] == RT_XF_TRANSLATE) {
+                for (int k = 0; k < 3; ++k) b.mn[k] += q[k], b.mx[k] += q[k];
+            } else {
+                const float sn = q[0], cs = q[1];
+                float mn[3] = {FLT_MAX, b.mn[1], FLT_MAX}, mx[3] = {-FLT_MAX, b.mx[1], -FLT_MAX};
+                for (int ci = 0; ci < 4; ++ci) {
+                    const float x0c = (ci & 1) ? b.mx[0] : b.mn[0], z0c = (ci & 2) ? b.mx[2] : b.mn[2];
+                    const float nx = cs * x0c + sn * z0c, nz = -sn * x0c + cs * z0c;
+                    mn[0] = std::min(mn[0], nx), mx[0] = std::max(mx[0], nx);
+                    mn[2] = std::min(mn[2], nz), mx[2] = std::max(mx[2], nz);
+                }
+                // the rotation itself rounds: widen by a few ulp of the coordinate magnitude
+                for (int k = 0; k < 3; k += 2) {
+                    const float e = 1e-6f * std::max(std::fabs(mn[k]), std::fabs(mx[k]));
+                    b.mn[k] = mn[k] - e, b.mx[k] = mx[k] + e;
+                }
+            }
+        }
+        exact_world_region(s, i, b, nullptr);
+    }
+    // world entries: the primitives that are not a medium boundary, then the media (the box around their boundaries)
+    w.ent.clear(), w.entry_ids.clear();
+    for (uint32_t i = 0; i < n_prims; ++i)
+        if (w.pmed[i] == RT_NO_MEDIUM) w.ent.push_back(w.prim[i]), w.entry_ids.push_back(i);
+    for (uint32_t m = 0; m < s->n_media; ++m) {
+        PrimBox mb;
+        for (int k = 0; k < 3; ++k) mb.mn[k] = FLT_MAX, mb.mx[k] = -FLT_MAX;
+        for (uint32_t i = 0; i < n_prims; ++i)
+            if (w.pmed[i] == m)
+                for (int k = 0; k < 3; ++k) mb.mn[k] = std::min(mb.mn[k], w.prim[i].mn[k]), mb.mx[k] = std::max(mb.mx[k], w.prim[i].mx[k]);
+        w.ent.push_back(mb);
+        w.entry_ids.push_back(n_prims + m);
+    }
+    // bounding spheres of the world entries (k_primary_lists): a sphere gets its world sphere, anything else the sphere
+    // around its world-space box
+    w.ent_bs.assign(w.ent.size(), make_float4(0.f, 0.f, 0.f, 0.f));
+    for (size_t e = 0; e < w.ent.size(); ++e) {
+        const uint32_t id = w.entry_ids[e];
+        if (id < s->n_spheres) {
+            w.ent_bs[e] = w.world_sphere[id];
+        } else {
+            const PrimBox& b = w.ent[e];
+            const double hx = 0.5 * ((double)b.mx[0] - b.mn[0]), hy = 0.5 * ((double)b.mx[1] - b.mn[1]), hz = 0.5 * ((double)b.mx[2] - b.mn[2]);
+            float4 bs = make_float4((float)(0.5 * ((double)b.mx[0] + b.mn[0])), (float)(0.5 * ((double)b.mx[1] + b.mn[1])),
+                                    (float)(0.5 * ((double)b.mx[2] + b.mn[2])), (float)(std::sqrt(hx * hx + hy * hy + hz * hz) * 1.0001));
+            // far from the origin the rounded centre moves by more than the 1e-4: the sphere holds the box's corners from where it is
+            double far2 = 0.0;
+            for (int c = 0; c < 8; ++c) {
+                const double dx = ((c & 1) ? b.mx[0] : b.mn[0]) - (double)bs.x, dy = ((c & 2) ? b.mx[1] : b.mn[1]) - (double)bs.y,
+                             dz = ((c & 4) ? b.mx[2] : b.mn[2]) - (double)bs.z;
+                far2 = std::max(far2, dx * dx + dy * dy + dz * dz);
+            }
+            if (std::sqrt(far2) > (double)bs.w) bs.w = round_up(std::sqrt(far2) * (1.0 + 1e-15));
+            w.ent_bs[e] = bs;
+        }
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -753,12 +975,6 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
     // rectangles: device geometry (k, u0, u1, v0), (v1, axis) with (u, v) the uv axes of hitable.rs:262-263 etc.
     const uint32_t n_prims = s->n_spheres + s->n_rects;
     std::vector<float4> rgeo((size_t)s->n_rects * 2);
-    std::vector<PrimBox> pboxes(n_prims);
-    for (uint32_t i = 0; i < s->n_spheres; ++i) {
-        const float c[3] = {geo[i].x, geo[i].y, geo[i].z};
-        const float r = std::fabs(geo[i].w);
-        for (int k = 0; k < 3; ++k) pboxes[i].mn[k] = c[k] - r, pboxes[i].mx[k] = c[k] + r;
-    }
     auto fbits = [](uint32_t u) {
         float f;
         std::memcpy(&f, &u, 4);
@@ -771,13 +987,9 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
         const int ua = ax == 0 ? 1 : 0, va = ax == 2 ? 1 : 2;
         rgeo[2 * (size_t)i] = make_float4(mn[ax], mn[ua], mx[ua], mn[va]);
         rgeo[2 * (size_t)i + 1] = make_float4(mx[va], fbits(ax), 0.0f, 0.0f);
-        PrimBox& b = pboxes[s->n_spheres + i];
-        for (int k = 0; k < 3; ++k) b.mn[k] = std::min(mn[k], mx[k]), b.mx[k] = std::max(mn[k], mx[k]);
-        b.mn[ax] = mn[ax] - 0.0001f, b.mx[ax] = mn[ax] + 0.0001f; // the plane the hit test uses (hitable.rs:253)
     }
-    // instance wrappers: per-primitive innermost wrapper, and world-space bounds through the chain (corners
-    // through every wrapper from the inside out, as RotateY::new does at hitable.rs:455-473)
-    std::vector<uint32_t> pxf(n_prims, RT_NO_XFORM);
+    // instance wrappers: the listed long chains; the per-primitive innermost wrapper and the world-space bounds come from
+    // world_bounds() below
     std::vector<float4> xparam(s->n_xforms);
     std::vector<uint2> xmeta(s->n_xforms);
     // xf_meta[x] = (type, parent).  A chain of more than RT_MAX_CHAIN wrappers is listed once more behind the table, outermost wrapper
@@ -809,73 +1021,23 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
         std::memcpy(&p0, &xparam[i].w, 4);
         for (uint32_t x = i; x != RT_NO_XFORM; x = s->xf_parent[x]) xmeta[p0 + --k] = make_uint2(x, xf_depth[i]);
     }
-    std::vector<float4> world_sphere(s->n_spheres); // instanced spheres: centre and radius in world space (culling only)
-    for (uint32_t i = 0; i < n_prims; ++i) {
-        const uint32_t x0 = i < s->n_spheres ? (s->sph_xform ? s->sph_xform[i] : RT_NO_XFORM)
-                                             : (s->rect_xform ? s->rect_xform[i - s->n_spheres] : RT_NO_XFORM);
-        pxf[i] = x0;
-        if (i < s->n_spheres && x0 != RT_NO_XFORM) {
-            // A sphere below Translate / RotateY wrappers is still a sphere: its world box is centre' +- r, not the
-            // box of the rotated box that RotateY::new computes (22 % wider per axis at 15 degrees, and the cloud of
-            // final_scene is 1 000 overlapping instanced spheres).  The exact test runs in object space on a ray
-            // whose transform rounds at the magnitude of the WORLD coordinates, so the box gets that slack.
-            double c[3] = {geo[i].x, geo[i].y, geo[i].z}, mag = std::fabs(geo[i].w);
-            for (uint32_t x = x0; x != RT_NO_XFORM; x = s->xf_parent[x]) {
-                const float* q = s->xf_param + 4 * (size_t)x;
-                for (int k = 0; k < 3; ++k) mag = std::max(mag, std::fabs(c[k]));
-                if (s->xf_type[x] == RT_XF_TRANSLATE) {
-                    for (int k = 0; k < 3; ++k) c[k] += (double)q[k];
-                } else {
-                    const double sn = q[0], cs = q[1], cx = c[0], cz = c[2];
-                    c[0] = cs * cx + sn * cz, c[2] = -sn * cx + cs * cz;
-                }
-                for (int k = 0; k < 3; ++k) mag = std::max(mag, std::fabs(c[k]));
-            }
-            const double r = std::fabs((double)geo[i].w), slack = 8e-6 * mag + 1e-30;
-            for (int k = 0; k < 3; ++k) pboxes[i].mn[k] = (float)(c[k] - r - slack), pboxes[i].mx[k] = (float)(c[k] + r + slack);
-            world_sphere[i] = make_float4((float)c[0], (float)c[1], (float)c[2], (float)(r + 2.0 * slack));
-            continue;
-        }
-        for (uint32_t x = x0; x != RT_NO_XFORM; x = s->xf_parent[x]) {
-            PrimBox& b = pboxes[i];
-            const float* q = s->xf_param + 4 * (size_t)x;
-            if (s->xf_type[x] == RT_XF_TRANSLATE) {
-                for (int k = 0; k < 3; ++k) b.mn[k] += q[k], b.mx[k] += q[k];
-            } else {
-                const float sn = q[0], cs = q[1];
-                float mn[3] = {FLT_MAX, b.mn[1], FLT_MAX}, mx[3] = {-FLT_MAX, b.mx[1], -FLT_MAX};
-                for (int ci = 0; ci < 4; ++ci) {
-                    const float x0c = (ci & 1) ? b.mx[0] : b.mn[0], z0c = (ci & 2) ? b.mx[2] : b.mn[2];
-                    const float nx = cs * x0c + sn * z0c, nz = -sn * x0c + cs * z0c;
-                    mn[0] = std::min(mn[0], nx), mx[0] = std::max(mx[0], nx);
-                    mn[2] = std::min(mn[2], nz), mx[2] = std::max(mx[2], nz);
-                }
-                // the rotation itself rounds: widen by a few ulp of the coordinate magnitude
-                for (int k = 0; k < 3; k += 2) {
-                    const float e = 1e-6f * std::max(std::fabs(mn[k]), std::fabs(mx[k]));
-                    b.mn[k] = mn[k] - e, b.mx[k] = mx[k] + e;
-                }
-            }
-        }
-    }
+    // world-space bounds of primitives and world entries (culling only; the same code answers rt_debug_world_bounds)
+    WorldBounds wb;
+    world_bounds(s, wb);
+    const std::vector<uint32_t>& pxf = wb.pxf;
+    const std::vector<uint32_t>& pmed = wb.pmed;
+    const std::vector<PrimBox>& eboxes = wb.ent;
+    const std::vector<uint32_t>& entry_ids = wb.entry_ids;
+    const std::vector<float4>& ent_bs = wb.ent_bs;
     // media: boundary primitive lists; world entries = primitives that are not a boundary, then the media
     const uint32_t n_entries = n_prims + s->n_media;
-    std::vector<uint32_t> pmed(n_prims, RT_NO_MEDIUM), med_prims;
+    std::vector<uint32_t> med_prims;
     std::vector<uint2> med_range(s->n_media);
     std::vector<float> med_nid(s->n_media);
     std::vector<uint2> med_xf(s->n_media, make_uint2(RT_NO_XFORM, RT_NO_XFORM)); // (.x: the chain all boundary primitives share, .y: the wrapper around the medium)
-    for (uint32_t i = 0; i < n_prims; ++i)
-        pmed[i] = i < s->n_spheres ? (s->sph_medium ? s->sph_medium[i] : RT_NO_MEDIUM)
-                                   : (s->rect_medium ? s->rect_medium[i - s->n_spheres] : RT_NO_MEDIUM);
-    std::vector<PrimBox> eboxes;
-    std::vector<uint32_t> entry_ids;
-    for (uint32_t i = 0; i < n_prims; ++i)
-        if (pmed[i] == RT_NO_MEDIUM) eboxes.push_back(pboxes[i]), entry_ids.push_back(i);
     for (uint32_t m = 0; m < s->n_media; ++m) {
         med_range[m] = make_uint2((uint32_t)med_prims.size(), 0u);
         med_nid[m] = s->med_neg_inv_density[m];
-        PrimBox mb;
-        for (int k = 0; k < 3; ++k) mb.mn[k] = FLT_MAX, mb.mx[k] = -FLT_MAX;
         for (uint32_t i = 0; i < n_prims; ++i)
             if (pmed[i] == m) {
                 // one wrapper chain for the whole boundary (a GBox under RotateY/Translate): medium_root moves the ray once
@@ -888,7 +1050,6 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
                 }
                 med_prims.push_back(i);
                 ++med_range[m].y;
-                for (int k = 0; k < 3; ++k) mb.mn[k] = std::min(mb.mn[k], pboxes[i].mn[k]), mb.mx[k] = std::max(mb.mx[k], pboxes[i].mx[k]);
             }
         if (med_range[m].y == 0) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: medium " + std::to_string(m) + " has no boundary primitives");
         if (s->med_xform) med_xf[m].y = s->med_xform[m];
@@ -901,24 +1062,6 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
             else if (med_xf[m].x != RT_MED_XF_MIXED && med_range[m].y == 1u && med_prims[med_range[m].x] < s->n_spheres) kind = RT_MED_KIND_SPHERE;
             if (ctx->opt[RT_OPT_MEDIUM_SEARCH] == 1u) kind = 0u; // test hook: the two searches as the reference makes them
             med_range[m].y |= kind << 24;
-        }
-        eboxes.push_back(mb);
-        entry_ids.push_back(n_prims + m);
-    }
-    // bounding spheres of the world entries (k_primary_lists): a bare sphere is its own, anything else gets the
-    // sphere around its (padded, world-space) box
-    std::vector<float4> ent_bs(eboxes.size());
-    for (size_t e = 0; e < eboxes.size(); ++e) {
-        const uint32_t id = entry_ids[e];
-        if (id < s->n_spheres && pxf[id] == RT_NO_XFORM) {
-            ent_bs[e] = make_float4(s->sph_cx[id], s->sph_cy[id], s->sph_cz[id], std::fabs(s->sph_r[id]));
-        } else if (id < s->n_spheres) {
-            ent_bs[e] = world_sphere[id];
-        } else {
-            const PrimBox& b = eboxes[e];
-            const double hx = 0.5 * ((double)b.mx[0] - b.mn[0]), hy = 0.5 * ((double)b.mx[1] - b.mn[1]), hz = 0.5 * ((double)b.mx[2] - b.mn[2]);
-            ent_bs[e] = make_float4((float)(0.5 * ((double)b.mx[0] + b.mn[0])), (float)(0.5 * ((double)b.mx[1] + b.mn[1])),
-                                    (float)(0.5 * ((double)b.mx[2] + b.mn[2])), (float)(std::sqrt(hx * hx + hy * hy + hz * hz) * 1.0001));
         }
     }
     HostBvh bvh;
@@ -1503,6 +1646,70 @@ int rt_debug_grid_build(const RtFlatScene* s, uint32_t cell_per_mille, uint32_t 
     std::copy(hg.refs.begin(), hg.refs.begin() + nr, refs);
     *n_large = hg.gp.n_always;
     for (uint32_t k = 0; k < hg.gp.n_always; ++k) large[k] = hg.gp.always[k];
+    return RT_OK;
+}
+
+int rt_debug_world_bounds(const RtFlatScene* s, float* prim_box, float* prim_box_padded, float* world_sphere, uint32_t* n_entries,
+                          uint32_t* entry_id, float* entry_box_padded, float* entry_bs) {
+    if (!s || !n_entries) return RT_ERR_INVALID;
+    const uint32_t n_prims = s->n_spheres + s->n_rects;
+    // what world_bounds() reads, checked as rt_scene_upload checks it
+    if (s->n_spheres && (!s->sph_cx || !s->sph_cy || !s->sph_cz || !s->sph_r)) return RT_ERR_INVALID;
+    if (s->n_rects && (!s->rect_axis || !s->rect_min || !s->rect_max)) return RT_ERR_INVALID;
+    if (s->n_xforms && (!s->xf_type || !s->xf_param || !s->xf_parent)) return RT_ERR_INVALID;
+    for (uint32_t i = 0; i < s->n_spheres; ++i)
+        if (!std::isfinite(s->sph_cx[i]) || !std::isfinite(s->sph_cy[i]) || !std::isfinite(s->sph_cz[i]) || !std::isfinite(s->sph_r[i])) return RT_ERR_INVALID;
+    for (uint32_t i = 0; i < s->n_rects; ++i) {
+        if (s->rect_axis[i] > RT_RECT_XY) return RT_ERR_INVALID;
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(s->rect_min[3 * (size_t)i + k]) || !std::isfinite(s->rect_max[3 * (size_t)i + k])) return RT_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < s->n_xforms; ++i) {
+        if (s->xf_type[i] > RT_XF_ROTATE_Y || (s->xf_parent[i] != RT_NO_XFORM && s->xf_parent[i] >= i)) return RT_ERR_INVALID;
+        for (int k = 0; k < 4; ++k)
+            if (!std::isfinite(s->xf_param[4 * (size_t)i + k])) return RT_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < n_prims; ++i) {
+        const bool sph = i < s->n_spheres;
+        const uint32_t* xf = sph ? s->sph_xform : s->rect_xform;
+        const uint32_t* md = sph ? s->sph_medium : s->rect_medium;
+        const uint32_t j = sph ? i : i - s->n_spheres;
+        if (xf && xf[j] != RT_NO_XFORM && xf[j] >= s->n_xforms) return RT_ERR_INVALID;
+        if (md && md[j] != RT_NO_MEDIUM && md[j] >= s->n_media) return RT_ERR_INVALID;
+    }
+    for (uint32_t m = 0; m < s->n_media; ++m) { // rt_scene_upload refuses a medium without boundary primitives
+        bool any = false;
+        for (uint32_t i = 0; i < n_prims && !any; ++i) {
+            const uint32_t* md = i < s->n_spheres ? s->sph_medium : s->rect_medium;
+            any = md && md[i < s->n_spheres ? i : i - s->n_spheres] == m;
+        }
+        if (!any) return RT_ERR_INVALID;
+    }
+    WorldBounds w;
+    world_bounds(s, w);
+    const uint32_t ne = (uint32_t)w.ent.size();
+    const bool fits = *n_entries >= ne;
+    *n_entries = ne;
+    if (!fits) return RT_ERR_INVALID;
+    auto put_box = [](float* dst, const PrimBox& b) {
+        for (int k = 0; k < 3; ++k) dst[k] = b.mn[k], dst[3 + k] = b.mx[k];
+    };
+    for (uint32_t i = 0; i < n_prims; ++i) {
+        if (prim_box) put_box(prim_box + 6 * (size_t)i, w.prim[i]);
+        if (prim_box_padded) put_box(prim_box_padded + 6 * (size_t)i, pad_prim_box(w.prim[i]));
+    }
+    for (uint32_t i = 0; i < s->n_spheres && world_sphere; ++i) {
+        const float4 v = w.world_sphere[i];
+        world_sphere[4 * (size_t)i] = v.x, world_sphere[4 * (size_t)i + 1] = v.y, world_sphere[4 * (size_t)i + 2] = v.z, world_sphere[4 * (size_t)i + 3] = v.w;
+    }
+    for (uint32_t e = 0; e < ne; ++e) {
+        if (entry_id) entry_id[e] = w.entry_ids[e];
+        if (entry_box_padded) put_box(entry_box_padded + 6 * (size_t)e, pad_prim_box(w.ent[e]));
+        if (entry_bs) {
+            const float4 v = w.ent_bs[e];
+            entry_bs[4 * (size_t)e] = v.x, entry_bs[4 * (size_t)e + 1] = v.y, entry_bs[4 * (size_t)e + 2] = v.z, entry_bs[4 * (size_t)e + 3] = v.w;
+        }
+    }
     return RT_OK;
 }
 

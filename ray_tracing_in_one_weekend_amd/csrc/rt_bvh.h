@@ -25,6 +25,20 @@ struct PrimBox {
     float mn[3], mx[3];
 };
 
+// the box the builder stores for a primitive: pad 2^-18 of the coordinate magnitude, >= 10x the fp32 error of the exact tests;
+// a NaN/inf primitive is never culled (also rt_debug_world_bounds)
+inline PrimBox pad_prim_box(const PrimBox& p) {
+    PrimBox b;
+    for (int k = 0; k < 3; ++k) {
+        const float mag = std::max(std::fabs(p.mn[k]), std::fabs(p.mx[k]));
+        const float pad = mag * 3.8146973e-06f + 1e-30f;
+        b.mn[k] = p.mn[k] - pad;
+        b.mx[k] = p.mx[k] + pad;
+        if (!(b.mn[k] <= b.mx[k])) b.mn[k] = -FLT_MAX, b.mx[k] = FLT_MAX;
+    }
+    return b;
+}
+
 struct HostBvh {
     std::vector<float4> a, b, c;
     std::vector<int4> d;
@@ -70,15 +84,10 @@ struct Builder {
         order.resize(prim.size());
         for (size_t i = 0; i < prim.size(); ++i) {
             order[i] = (uint32_t)i;
+            const PrimBox pb = pad_prim_box(prim[i]);
             for (int k = 0; k < 3; ++k) {
-                // pad: 2^-18 of the coordinate magnitude, >= 10x the fp32 error of the exact tests
-                const float mag = std::max(std::fabs(prim[i].mn[k]), std::fabs(prim[i].mx[k]));
-                const float pad = mag * 3.8146973e-06f + 1e-30f;
-                boxes[i].mn[k] = prim[i].mn[k] - pad;
-                boxes[i].mx[k] = prim[i].mx[k] + pad;
-                if (!(boxes[i].mn[k] <= boxes[i].mx[k])) { // NaN/inf primitive: never cull it
-                    boxes[i].mn[k] = -FLT_MAX, boxes[i].mx[k] = FLT_MAX;
-                }
+                boxes[i].mn[k] = pb.mn[k];
+                boxes[i].mx[k] = pb.mx[k];
                 cen[3 * i + (size_t)k] = 0.5f * prim[i].mn[k] + 0.5f * prim[i].mx[k];
             }
         }

@@ -617,7 +617,8 @@ __device__ __forceinline__ bool rect_root(float4 g0, float4 g1, V3 o, V3 d, floa
 // unrolled array.  The reference nests without limit (hitable.rs:404-520 hold an Arc<dyn Hitable>), so a deeper chain is listed once
 // more, outermost wrapper first, behind the wrapper table itself — entries xf_meta[p0 + k] = (wrapper, chain length) with p0 = the
 // bits of xf_param[x].w, 0 for a short chain (rt_scene_upload) — and walked by a loop: the same xform_ray / unwind steps in the same
-// order, so the same bits (tests: chains of up to 18 wrappers against the oracle).  NEST: kernels are compiled twice, and only
+// order, so the same bits (tests: chains of up to 18 wrappers against the oracle, RotateY chains of up to 256 through the list walk
+// and every culling search, tests/test_wrapped_culling.py).  NEST: kernels are compiled twice, and only
 // scenes that nest beyond what the registers hold (RtCtx::nest: a chain of more than RT_MAX_CHAIN, more media than the per-lane
 // mask has bits, wrappers AROUND a medium) run the instantiation with the loops — the others run the code they always ran.
 #define RT_NO_XFORM_DEV 0xFFFFFFFFu

@@ -14,7 +14,7 @@ import time
 import numpy as np
 import pytest
 
-from helpers import ctr_draw, display, hip_runtime, path_keys, rays_on_scene, rmse_display
+from helpers import ctr_draw, display, hip_runtime, path_keys, primary_rays as _primary_rays, rays_on_scene, rmse_display
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -554,28 +554,6 @@ def test_c_host_through_the_headers(rt, renderer, tmp_path):
         assert f"{st.n_rays} rays" in r.stdout
         with Image.open(png) as im:
             assert np.array_equal(np.asarray(im.convert("RGB")), rgb8)
-
-
-def _primary_rays(scene, p, pix_i, pix_j, samp):
-    """main.rs:89-94 + camera.rs:40-46 for the given (pixel, sample) pairs in numpy float32, every operation rounded once
-    (glam order: dot = (xx + yy) + zz, normalize = v * (1 / len)) — the very rays the renderer and the oracle trace."""
-    f = np.float32
-    keys = path_keys(int(p.seed), pix_j.astype(np.uint64) * p.nx + pix_i.astype(np.uint64), samp.astype(np.uint64))
-    k0, k1 = keys[:, 0].astype(np.uint64), keys[:, 1].astype(np.uint64)
-
-    def draw(ctr):
-        return ((ctr_draw(k0, k1, ctr) >> 8).astype(np.float32) * f(1.0 / 16777216.0)).astype(f)
-    u = ((pix_i.astype(f) + draw(0)) / f(p.nx)).astype(f)
-    v = ((pix_j.astype(f) + draw(1)) / f(p.ny)).astype(f)
-    cam = scene.camera
-    org, H, V, llc = (np.array(list(x), dtype=f) for x in (cam.origin, cam.horizontal, cam.vertical, cam.lower_left_corner))
-    dirs = np.empty((len(u), 3), dtype=f)
-    for k in range(3):
-        dirs[:, k] = (((llc[k] + (u * H[k]).astype(f)).astype(f) + (v * V[k]).astype(f)).astype(f) - org[k]).astype(f)
-    len2 = (((dirs[:, 0] * dirs[:, 0]).astype(f) + (dirs[:, 1] * dirs[:, 1]).astype(f)).astype(f) + (dirs[:, 2] * dirs[:, 2]).astype(f)).astype(f)
-    inv = (f(1.0) / np.sqrt(len2).astype(f)).astype(f)
-    dirs = (dirs * inv[:, None]).astype(f)
-    return np.tile(org, (len(u), 1)).astype(f), dirs, keys
 
 
 def _texel_edge_distance(scene, hit, o, d, t):
