@@ -69,11 +69,18 @@ int rth_hitable_bbox(RthScene* s, uint32_t hitable, float out[6]);
 int rth_set_sky(RthScene* s, uint32_t sky, const char* env_path);
 int rth_set_camera(RthScene* s, const float lookfrom[3], const float lookat[3], const float vup[3], float vfov,
                    float aspect_ratio);
+/* The book's thin-lens camera, Camera::new(lookfrom, lookat, vup, vfov, aspect_ratio, aperture, focus_dist) (chapter 13): the
+ * RtCamera is rth_set_camera's bit for bit; rth_scene_lens gives {aperture / 2, focus_dist} for rt_set_lens.  aperture >= 0,
+ * focus_dist > 0, both finite. */
+int rth_set_camera_lens(RthScene* s, const float lookfrom[3], const float lookat[3], const float vup[3], float vfov,
+                        float aspect_ratio, float aperture, float focus_dist);
 /* Wraps everything added so far in a BvhNode like build_bvh (demo_scene.rs:223-227) and flattens. */
 int rth_scene_finish(RthScene* s, int use_bvh);
 
 const RtFlatScene* rth_scene_flat(const RthScene* s);
 int rth_scene_camera(const RthScene* s, RtCamera* out);
+/* The lens of the finished scene's camera: {0, 1} for a pinhole one. */
+int rth_scene_lens(const RthScene* s, RtLens* out);
 const char* rth_scene_sphere_name(const RthScene* s, uint32_t index);
 void rth_scene_free(RthScene* s);
 

@@ -328,6 +328,21 @@ typedef void (*RtProgressFn)(void* user, uint32_t spp_done, uint32_t spp_total, 
                              uint32_t rows);
 int rt_set_progress(RtCtx* ctx, RtProgressFn fn, void* user);
 
+/*
+ * Thin lens: defocus blur.  The book's Camera::new(lookfrom, lookat, vup, vfov, aspect, aperture, focus_dist) (Ray Tracing in One
+ * Weekend, chapter 13; the reference's camera.rs has no lens) with lens_radius = aperture / 2.  The RtCamera stays camera.rs's
+ * unit-focal-length camera; the lens is applied on top of it.  A primary ray leaves origin + rx LU + ry LV, (rx, ry) drawn in the unit
+ * disc, towards origin + focus_dist * (llc + u H + v V - origin), with LU = lens_radius H / |H| and LV = lens_radius V / |V|: the plane
+ * of focus lies at focus_dist along -w, as the book's does.  DESIGN.md "Thin lens".
+ */
+typedef struct RtLens {
+    float lens_radius, focus_dist;
+} RtLens;
+/* The lens of every following rt_render / rt_render_device of `ctx` (per context, like rt_set_progress; rt_scene_upload leaves it).
+ * NULL or lens_radius 0: the pinhole camera, bit for bit.  RT_ERR_INVALID, and the previous lens stays, unless both values are finite,
+ * lens_radius >= 0 and, where lens_radius > 0, focus_dist > 0. */
+int rt_set_lens(RtCtx* ctx, const RtLens* lens);
+
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the
  * world shared read-only (main.rs:72-108); here the scene is replicated on every device, device r renders the image
@@ -357,6 +372,8 @@ int rt_multi_scene_upload(RtMulti* m, const RtFlatScene* scene);
  * either may be NULL.  `stats` sums the counters of the devices and takes the maximum of their times. */
 int rt_multi_render(RtMulti* m, const RtCamera* cam, const RtParams* params, float* out_rgb_f32, uint8_t* out_rgb8,
                     RtStats* stats);
+/* rt_set_lens on every device (all or none: the values are checked by the first). */
+int rt_multi_set_lens(RtMulti* m, const RtLens* lens);
 /* The de-interleave step on its own: `d_gathered` is a DEVICE buffer of n_shards band buffers, each
  * max_r rt_shard_rows(ny, band, n_shards, r) rows of nx*3 floats (what the gather delivers); writes the frame in
  * image row order to d_out_rgb_f32 [ny*nx*3] and / or the quantised, flipped image to d_out_rgb8 (device pointers,

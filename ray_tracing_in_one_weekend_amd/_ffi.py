@@ -68,6 +68,11 @@ class RtCamera(C.Structure):
                 ("lower_left_corner", C.c_float * 3)]
 
 
+class RtLens(C.Structure):
+    """rt_set_lens: the book's thin lens, lens_radius = aperture / 2; lens_radius 0 = the pinhole."""
+    _fields_ = [("lens_radius", C.c_float), ("focus_dist", C.c_float)]
+
+
 class RtParams(C.Structure):
     _fields_ = [("nx", C.c_uint32), ("ny", C.c_uint32), ("spp", C.c_uint32), ("max_depth", C.c_int32),
                 ("seed", C.c_uint64), ("shard_band", C.c_uint32), ("shard_count", C.c_uint32),
@@ -124,11 +129,12 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_shard_rows", "rt_shard_row_to_image_row", "rt_prepare", "rt_render", "rt_render_device", "rt_debug_bounce", "rt_debug_arithmetic",
                "rt_get_depth_timings", "rt_set_progress", "rt_host_alloc", "rt_host_free", "rt_debug_set_option", "rt_debug_get_option",
                "rt_debug_scene_info", "rt_debug_grid_build", "rt_debug_world_bounds", "rt_debug_render_parts", "rt_multi_create", "rt_multi_create_ex", "rt_multi_destroy", "rt_multi_device_count",
-               "rt_multi_last_error", "rt_multi_scene_upload", "rt_multi_render", "rt_deinterleave_bands"]
+               "rt_multi_last_error", "rt_multi_scene_upload", "rt_multi_render", "rt_deinterleave_bands", "rt_set_lens", "rt_multi_set_lens"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
                 "rth_sphere", "rth_rect", "rth_gbox", "rth_translate", "rth_rotate_y", "rth_constant_medium", "rth_hitable_bbox", "rth_set_sky", "rth_set_camera", "rth_scene_finish", "rth_scene_flat",
-                "rth_scene_camera", "rth_scene_sphere_name", "rth_scene_free", "rth_png_write", "rth_output_file_name"]
+                "rth_scene_camera", "rth_scene_sphere_name", "rth_scene_free", "rth_png_write", "rth_output_file_name",
+                "rth_set_camera_lens", "rth_scene_lens"]
 
 _gpu_lib = None
 _host_lib = None
@@ -180,6 +186,10 @@ def load_gpu_library():
     lib.rt_debug_arithmetic.restype = C.c_int
     lib.rt_set_progress.argtypes = [vp, RtProgressFn, vp]
     lib.rt_set_progress.restype = C.c_int
+    lib.rt_set_lens.argtypes = [vp, C.POINTER(RtLens)]
+    lib.rt_set_lens.restype = C.c_int
+    lib.rt_multi_set_lens.argtypes = [vp, C.POINTER(RtLens)]
+    lib.rt_multi_set_lens.restype = C.c_int
     lib.rt_host_alloc.argtypes = [C.c_size_t]
     lib.rt_host_alloc.restype = vp
     lib.rt_host_free.argtypes = [vp]
@@ -270,6 +280,10 @@ def load_host_library():
     lib.rth_scene_flat.restype = C.POINTER(RtFlatScene)
     lib.rth_scene_camera.argtypes = [vp, C.POINTER(RtCamera)]
     lib.rth_scene_camera.restype = C.c_int
+    lib.rth_set_camera_lens.argtypes = [vp, f3, f3, f3, C.c_float, C.c_float, C.c_float, C.c_float]
+    lib.rth_set_camera_lens.restype = C.c_int
+    lib.rth_scene_lens.argtypes = [vp, C.POINTER(RtLens)]
+    lib.rth_scene_lens.restype = C.c_int
     lib.rth_scene_sphere_name.argtypes = [vp, C.c_uint32]
     lib.rth_scene_sphere_name.restype = C.c_char_p
     lib.rth_scene_free.argtypes = [vp]

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import RtBounceIO, RtCamera, RtFlatScene, RtParams, RtStats
+from ._ffi import RtBounceIO, RtCamera, RtFlatScene, RtLens, RtParams, RtStats
 
 
 class RtError(RuntimeError):
@@ -18,6 +18,15 @@ class RtError(RuntimeError):
 
 def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def _lens_ptr(lens):
+    """None -> NULL (the pinhole); an RtLens or a (lens_radius, focus_dist) pair -> a pointer to an RtLens"""
+    if lens is None:
+        return None
+    if not isinstance(lens, RtLens):
+        lens = RtLens(*[float(x) for x in lens])
+    return C.byref(lens)
 
 
 class Scene:
@@ -99,9 +108,15 @@ class Scene:
         if self._lib.rth_set_sky(self._h, sky, env_path.encode() if env_path else None) != 0:
             raise RtError(self._lib.rth_last_error().decode())
 
-    def set_camera(self, lookfrom, lookat, vup, vfov, aspect_ratio):
-        if self._lib.rth_set_camera(self._h, _f3(lookfrom), _f3(lookat), _f3(vup), C.c_float(vfov),
-                                    C.c_float(aspect_ratio)) != 0:
+    def set_camera(self, lookfrom, lookat, vup, vfov, aspect_ratio, aperture=0.0, focus_dist=1.0):
+        """Camera::new (camera.rs:14-39); with an aperture, the book's thin-lens camera (chapter 13): the same RtCamera, and
+        Scene.lens = (aperture / 2, focus_dist) for Renderer.set_lens."""
+        if aperture == 0.0 and focus_dist == 1.0:
+            rc = self._lib.rth_set_camera(self._h, _f3(lookfrom), _f3(lookat), _f3(vup), C.c_float(vfov), C.c_float(aspect_ratio))
+        else:
+            rc = self._lib.rth_set_camera_lens(self._h, _f3(lookfrom), _f3(lookat), _f3(vup), C.c_float(vfov), C.c_float(aspect_ratio),
+                                               C.c_float(aperture), C.c_float(focus_dist))
+        if rc != 0:
             raise RtError(self._lib.rth_last_error().decode())
 
     def finish(self, use_bvh=True):
@@ -130,6 +145,14 @@ class Scene:
         if self._lib.rth_scene_camera(self._h, C.byref(cam)) != 0:
             raise RtError("scene not finished")
         return cam
+
+    @property
+    def lens(self):
+        """RtLens of the camera (rth_scene_lens): (0, 1) for a pinhole one.  Renderer.upload does not apply it: pass it to set_lens."""
+        lens = RtLens()
+        if self._lib.rth_scene_lens(self._h, C.byref(lens)) != 0:
+            raise RtError("scene not finished")
+        return lens
 
     def sphere_name(self, i):
         return self._lib.rth_scene_sphere_name(self._h, i).decode()
@@ -348,6 +371,14 @@ class Renderer:
         if rc != 0:
             self._raise("rt_set_progress", rc)
 
+    def set_lens(self, lens):
+        """rt_set_lens: the thin lens of the following renders — an RtLens, a (lens_radius, focus_dist) pair or Scene.lens;
+        lens_radius = aperture / 2 of the book's Camera::new.  None or lens_radius 0: the pinhole.  Per context, and like the
+        camera it is passed, not taken from the uploaded scene."""
+        rc = self._lib.rt_set_lens(self._ctx, _lens_ptr(lens))
+        if rc != 0:
+            self._raise("rt_set_lens", rc)
+
     def render_device(self, camera, params, device_ptr, stream=None, want_stats=True):
         """Renders into HBM at `device_ptr` (e.g. torch_tensor.data_ptr()); nothing crosses PCIe."""
         stats = RtStats()
@@ -360,7 +391,8 @@ class Renderer:
 
     def render_parts(self):
         """rt_debug_render_parts: host-side timeline of the last render as {label: ms} in call order (allocations one by one, the
-        hardware-queue probe = first kernel launch, candidate lists + the in-frame synchronisation, enqueue, wait)."""
+        hardware-queue probe = first kernel launch, candidate lists + the in-frame synchronisation, enqueue, wait), plus counters:
+        "primary_lists_overflow" = pixels whose candidate list overflowed (-1: no lists, or a general scene)."""
         import json
         buf = C.create_string_buffer(4096)
         n = self._lib.rt_debug_render_parts(self._ctx, buf, len(buf))
@@ -499,6 +531,12 @@ class MultiRenderer:
         rc = self._lib.rt_multi_scene_upload(self._m, ptr)
         if rc != 0:
             self._raise("rt_multi_scene_upload", rc)
+
+    def set_lens(self, lens):
+        """rt_multi_set_lens: Renderer.set_lens on every device."""
+        rc = self._lib.rt_multi_set_lens(self._m, _lens_ptr(lens))
+        if rc != 0:
+            self._raise("rt_multi_set_lens", rc)
 
     def render(self, camera, params, want_rgb8=False):
         """Returns (f32 image [ny, nx, 3] (row 0 = bottom), rgb8 or None, RtStats summed over the devices)."""

@@ -81,6 +81,8 @@ struct RtCtx {
     // Page-locked word for the one host decision inside a frame: how many pixels have more primary-ray candidates than a list
     // holds (k_primary_lists counts them; render_impl reads the count back 0.1 ms into the frame).
     uint32_t* h_overflow = nullptr;
+    long long last_overflow = -1; // that count for the last frame (rt_debug_render_parts); -1: it made no lists or did not read it
+    RtLens lens{0.0f, 1.0f};      // rt_set_lens (lens_radius 0: the pinhole)
     // progressive preview (rt_set_progress): called from rt_render after every slice
     RtProgressFn progress_fn = nullptr;
     void* progress_user = nullptr;
@@ -272,6 +274,7 @@ struct StepBuffers {
     float* rad;
     unsigned long long* totals;
     const GenParams* gpd;
+    bool lens = false; // depth 0 through the thin lens (the LENS instantiations)
 };
 bool scene_is_general(const RtCtx* ctx) { return ctx->general_kernels; }
 bool grid_enabled(const RtCtx* ctx) { return ctx->use_grid && ctx->opt[RT_OPT_GRID] != 1u && !scene_is_general(ctx); }
@@ -286,8 +289,14 @@ void launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32
         return;
     }
 #define RT_LAUNCH_ISECT_X(G, R, N, T, X)                                                                               \
-    hipLaunchKernelGGL((k_intersect<RT_BVH_BLOCK, G, R, N, T, X>), dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg, ctx->ds, \
-                       b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd)
+    do {                                                                                                                \
+        if (G && b.lens)                                                                                                \
+            hipLaunchKernelGGL((k_intersect<RT_BVH_BLOCK, G, R, N, T, X, G>), dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg, \
+                               ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);                                      \
+        else                                                                                                            \
+            hipLaunchKernelGGL((k_intersect<RT_BVH_BLOCK, G, R, N, T, X>), dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg,  \
+                               ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);                                      \
+    } while (0)
 #define RT_LAUNCH_ISECT(G, R, N, T) RT_LAUNCH_ISECT_X(G, R, N, T, false)
     // general scenes: tables in LDS or not; and (ctx->nest) the instantiation whose wrapper chains and media masks are loops
 #define RT_LAUNCH_ISECT_G(G, N)                       \
@@ -320,8 +329,15 @@ void launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32
     // sphere geometry for the closest hit inside k_shade<GEN>
     const uint32_t n_fused = (gen && fused_lists) ? ctx->ds.n_spheres : 0u;
     const size_t shade_lds = shade_lds_bytes(ctx->ds.n_prims + ctx->ds.n_media, perlin_lds ? ctx->ds.n_perlin : 0u, n_fused, !gen && sp.sort);
-#define RT_LAUNCH_SHADE(P, G, R, X) \
-    hipLaunchKernelGGL((k_shade<P, G, R, X>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, b.cout, b.rad, sp, b.totals, b.gpd)
+#define RT_LAUNCH_SHADE(P, G, R, X)                                                                                                      \
+    do {                                                                                                                                  \
+        if (G && b.lens)                                                                                                                  \
+            hipLaunchKernelGGL((k_shade<P, G, R, X, G>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, b.cout, \
+                               b.rad, sp, b.totals, b.gpd);                                                                               \
+        else                                                                                                                              \
+            hipLaunchKernelGGL((k_shade<P, G, R, X>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, b.cout,    \
+                               b.rad, sp, b.totals, b.gpd);                                                                               \
+    } while (0)
 #define RT_LAUNCH_SHADE_R(P, G)        \
     do {                               \
         if (rects && ctx->nest) RT_LAUNCH_SHADE(P, G, true, true); \
@@ -743,6 +759,16 @@ int rt_ctx_create(int device_id, RtCtx** out_ctx) {
 #define RT_SHADE_VARIANTS(P, G) reinterpret_cast<const void*>(&k_shade<P, G, false>), reinterpret_cast<const void*>(&k_shade<P, G, true>), reinterpret_cast<const void*>(&k_shade<P, G, true, true>)
             RT_SHADE_VARIANTS(true, true), RT_SHADE_VARIANTS(true, false), RT_SHADE_VARIANTS(false, true), RT_SHADE_VARIANTS(false, false),
 #undef RT_SHADE_VARIANTS
+            // the depth-0 instantiations of the thin lens (rt_set_lens): every GEN one launch_intersect / launch_shade can pick
+#define RT_ISECT_LENS(R, N, T, X) reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, true, R, N, T, X, true>)
+            RT_ISECT_LENS(false, true, false, false), RT_ISECT_LENS(true, true, false, false), RT_ISECT_LENS(true, true, true, false),
+            RT_ISECT_LENS(true, false, false, false), RT_ISECT_LENS(true, false, true, false), RT_ISECT_LENS(true, true, false, true),
+            RT_ISECT_LENS(true, true, true, true),    RT_ISECT_LENS(true, false, false, true), RT_ISECT_LENS(true, false, true, true),
+#undef RT_ISECT_LENS
+#define RT_SHADE_LENS(P) reinterpret_cast<const void*>(&k_shade<P, true, false, false, true>), reinterpret_cast<const void*>(&k_shade<P, true, true, false, true>), \
+                         reinterpret_cast<const void*>(&k_shade<P, true, true, true, true>)
+            RT_SHADE_LENS(true), RT_SHADE_LENS(false),
+#undef RT_SHADE_LENS
         };
         for (const void* fn : variants)
             if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_limit)) != hipSuccess)
@@ -1217,6 +1243,38 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
     return RT_OK;
 }
 
+// The lens of a frame in the kernels' terms (rt_kernels.h GenLens).  LU and LV in double, rounded once.  The two terms of the candidate
+// lists' bound (k_primary_lists) are rounded up:
+//   grow >= |o - origin|.  |rx LU + ry LV|^2 <= (rx^2 + ry^2) (max(|LU|^2, |LV|^2) + |LU.LV|), and rx^2 + ry^2 <= 1 + 2^-22 for a pair the
+//     fp32 test accepts; plus the roundings of rx LU_k + ry LV_k (three, of operands up to |LU_k| + |LV_k|) and of origin + off.
+//   sin_tilt >= grow / (focus_dist h), h = the distance from origin to the image plane (every dir = llc + u H + v V - origin is at
+//     least that long).  Above 1/2 the pixels get no list (sin_tilt 1 makes the cone unusable).
+static GenLens host_gen_lens(const RtCamera* cam, const RtLens& lens) {
+    GenLens g{};
+    const double R = lens.lens_radius;
+    double H[3], V[3], O[3], L[3];
+    for (int k = 0; k < 3; ++k) H[k] = cam->horizontal[k], V[k] = cam->vertical[k], O[k] = cam->origin[k], L[k] = cam->lower_left_corner[k];
+    const double hn = std::sqrt((H[0] * H[0] + H[1] * H[1]) + H[2] * H[2]), vn = std::sqrt((V[0] * V[0] + V[1] * V[1]) + V[2] * V[2]);
+    for (int k = 0; k < 3; ++k) g.lu[k] = (float)(R * H[k] / hn), g.lv[k] = (float)(R * V[k] / vn);
+    g.focus_dist = lens.focus_dist;
+    double lu2 = 0.0, lv2 = 0.0, luv = 0.0, mu = 0.0, mv = 0.0, mo = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        const double a = g.lu[k], b = g.lv[k];
+        lu2 += a * a, lv2 += b * b, luv += a * b;
+        mu = std::max(mu, std::fabs(a)), mv = std::max(mv, std::fabs(b)), mo = std::max(mo, std::fabs(O[k]));
+    }
+    const double ulp = 1.0 / 16777216.0;
+    const double off = std::sqrt((1.0 + 1.0 / 4194304.0) * (std::max(lu2, lv2) + std::fabs(luv)));
+    const double grow = (off + 1.7321 * (3.0 * ulp * (mu + mv) + ulp * (mo + off))) * (1.0 + 1e-6);
+    const double n[3] = {H[1] * V[2] - H[2] * V[1], H[2] * V[0] - H[0] * V[2], H[0] * V[1] - H[1] * V[0]};
+    const double h = std::fabs((L[0] - O[0]) * n[0] + (L[1] - O[1]) * n[1] + (L[2] - O[2]) * n[2]) / std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    double st = grow / ((double)lens.focus_dist * h) * (1.0 + 1e-6);
+    if (!(st <= 0.5)) st = 1.0; // (also NaN: a degenerate camera)
+    g.grow = std::nextafter((float)grow, INFINITY);
+    g.sin_tilt = std::nextafter((float)st, INFINITY);
+    return g;
+}
+
 static int check_params(RtCtx* ctx, const RtCamera* cam, const RtParams* p) {
     if (!ctx) return RT_ERR_INVALID;
     if (!ctx->has_scene) return fail(ctx, RT_ERR_STATE, "render: no scene uploaded");
@@ -1242,6 +1300,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     hipStream_t st = stream_v ? (hipStream_t)stream_v : ctx->stream;
     const auto wall0 = std::chrono::steady_clock::now();
     ctx->parts_begin();
+    ctx->last_overflow = -1;
 
     const uint32_t nx = prm->nx, ny = prm->ny, spp = prm->spp;
     const uint32_t band = prm->shard_band ? prm->shard_band : 1u;
@@ -1272,8 +1331,8 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     if ((rc = ensure(ctx, ctx->counts, counts_bytes))) return rc;
     const size_t totals_bytes = (size_t)(n_depths + 2) * sizeof(unsigned long long);
     if ((rc = ensure(ctx, ctx->totals, totals_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams)))) return rc;
-    if (want_lists && (rc = ensure(ctx, ctx->lists, ((size_t)npix + 1u) * sizeof(uint4)))) return rc; // + the overflow counter behind the lists
+    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + sizeof(GenLens)))) return rc; // (the lens behind the params: gen_lens_of)
+    if (want_lists &&(rc = ensure(ctx, ctx->lists, ((size_t)npix + 1u) * sizeof(uint4)))) return rc; // + the overflow counter behind the lists
     GenParams* gpd = (GenParams*)ctx->genp.p;
     float* acc = (float*)ctx->acc.p;
     uint32_t* counts = (uint32_t*)ctx->counts.p;
@@ -1305,6 +1364,8 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     gp.seed_lo = (uint32_t)prm->seed, gp.seed_hi = (uint32_t)(prm->seed >> 32);
     gp.lists = nullptr;
     gp.n_overflow = nullptr;
+    const bool lens = ctx->lens.lens_radius > 0.0f; // depth 0 through the thin lens: the LENS instantiations
+    const GenLens glens = lens ? host_gen_lens(cam, ctx->lens) : GenLens{};
     bool no_overflow = false; // every pixel of this frame has a candidate list (read back from k_primary_lists below)
     {   // udiv_inv: reciprocals that keep the float quotient at or below the true one
         auto inv = [](uint32_t d) { return (float)((1.0 / (double)d) * (1.0 - 1.0 / 4194304.0)); };
@@ -1325,8 +1386,11 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
         uint32_t* n_overflow = (uint32_t*)((uint4*)ctx->lists.p + npix);
         gp.n_overflow = n_overflow;
         RT_HIP(ctx, hipMemsetAsync(n_overflow, 0, sizeof(uint4), st));
-        hipLaunchKernelGGL(k_primary_lists, dim3((npix + 255u) / 256u), dim3(256), (size_t)ctx->ds.n_entries * sizeof(float4) + 4u * RT_LIST_WAVE_CAP * 2u, st,
-                           ctx->ds, gp, (uint4*)ctx->lists.p, n_overflow);
+        const size_t lists_lds = (size_t)ctx->ds.n_entries * sizeof(float4) + 4u * RT_LIST_WAVE_CAP * 2u;
+        if (lens)
+            hipLaunchKernelGGL(k_primary_lists<true>, dim3((npix + 255u) / 256u), dim3(256), lists_lds, st, ctx->ds, gp, (uint4*)ctx->lists.p, n_overflow, glens);
+        else
+            hipLaunchKernelGGL(k_primary_lists<false>, dim3((npix + 255u) / 256u), dim3(256), lists_lds, st, ctx->ds, gp, (uint4*)ctx->lists.p, n_overflow, glens);
         // The one host decision of a frame: with no overflowing list (every headline configuration) depth 0 of a sphere-only scene
         // needs no closest-hit launch at all — k_shade<GEN> finds every hit from the lists.  An empty launch is not free: each of
         // its workgroups waits for 66 KB of LDS behind the other chain's shading waves and holds its own chain's shading back
@@ -1337,6 +1401,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
             RT_HIP(ctx, hipMemcpyAsync(ctx->h_overflow, n_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             RT_HIP(ctx, hipStreamSynchronize(st));
             no_overflow = *ctx->h_overflow == 0u;
+            ctx->last_overflow = *ctx->h_overflow;
         }
         ctx->mark("primary_lists_and_in_frame_sync");
     }
@@ -1418,8 +1483,10 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
         gp.s0 = s0;
         gp.n_rays = npix * sc;
         RT_HIP(ctx, hipMemsetAsync(counts, 0, counts_bytes, st));
-        hipLaunchKernelGGL(k_init_counts, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, gpd);
-        if (!fuse_gen) hipLaunchKernelGGL(k_gen_primary, dim3((gp.n_rays + 255u) / 256u), dim3(256), 0, st, gp, Q[0]);
+        if (lens) hipLaunchKernelGGL(k_init_counts<true>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, gpd, glens);
+        else hipLaunchKernelGGL(k_init_counts<false>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, gpd, glens);
+        if (!fuse_gen && lens) hipLaunchKernelGGL(k_gen_primary<true>, dim3((gp.n_rays + 255u) / 256u), dim3(256), 0, st, gp, Q[0], glens);
+        else if (!fuse_gen) hipLaunchKernelGGL(k_gen_primary<false>, dim3((gp.n_rays + 255u) / 256u), dim3(256), 0, st, gp, Q[0], glens);
         RT_HIP(ctx, hipEventRecord(ctx->events[2 * sl], st));
         if (n_groups > 1u) {
             RT_HIP(ctx, hipEventRecord(ctx->ev_fork, st));
@@ -1442,7 +1509,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
             const bool gen = fuse_gen && depth == 0;
             ip.depth = depth;
             ip.q0 = q0, ip.q1 = q1;
-            const StepBuffers sb{qi, qo, qhit, cin, cout, rad, totals, gpd};
+            const StepBuffers sb{qi, qo, qhit, cin, cout, rad, totals, gpd, lens};
             // depth 0 of a sphere-only scene whose pixels all have a candidate list: k_shade<GEN> finds every closest hit itself
             const bool no_primary_trace = gen && !rects && gp.lists != nullptr && no_overflow;
             if (!no_primary_trace) launch_intersect(ctx, sg, use_bvh, gen, isect_grid_g, sb, ip);
@@ -1603,6 +1670,10 @@ int rt_debug_render_parts(const RtCtx* ctx, char* buf, uint32_t cap) {
     }
     std::snprintf(num, sizeof(num), "%s\"pool_mapped_mb\": %zu", ctx->parts.empty() ? "" : ", ", ctx->pool.mapped.load() >> 20);
     js += num;
+    // pixels whose primary-ray candidate list overflowed in the last frame (-1: it made no lists, or a general scene that does not read
+    // the count back)
+    std::snprintf(num, sizeof(num), ", \"primary_lists_overflow\": %lld", ctx->last_overflow);
+    js += num;
     std::snprintf(num, sizeof(num), ", \"pool_chunks_grown\": %u", ctx->pool.n_grown.load());
     js += num;
     std::snprintf(num, sizeof(num), ", \"pool_slowest_chunk_ms\": %.3f", ctx->pool.slowest_chunk_ms.load());
@@ -1743,6 +1814,19 @@ int rt_set_progress(RtCtx* ctx, RtProgressFn fn, void* user) {
     return RT_OK;
 }
 
+int rt_set_lens(RtCtx* ctx, const RtLens* lens) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!lens) {
+        ctx->lens = RtLens{0.0f, 1.0f};
+        return RT_OK;
+    }
+    const float r = lens->lens_radius, f = lens->focus_dist;
+    if (!std::isfinite(r) || !std::isfinite(f) || r < 0.0f || (r > 0.0f && !(f > 0.0f)))
+        return fail(ctx, RT_ERR_INVALID, "rt_set_lens: lens_radius and focus_dist must be finite, lens_radius >= 0, and focus_dist > 0 for a lens");
+    ctx->lens = *lens;
+    return RT_OK;
+}
+
 int rt_get_depth_timings(RtCtx* ctx, uint32_t max_n, float* isect_ms, float* shade_ms, uint64_t* rays) {
     if (!ctx) return RT_ERR_INVALID;
     RT_HIP(ctx, hipSetDevice(ctx->device));
@@ -1792,7 +1876,7 @@ static int debug_bounce_production(RtCtx* ctx, const RtBounceIO* io) {
     gp.nq = nq, gp.cap = cap;
     gp.inv_npix = gp.inv_nx = (float)((1.0 / (double)n) * (1.0 - 1.0 / 4194304.0));
     gp.inv_band = (float)(1.0 - 1.0 / 4194304.0);
-    hipLaunchKernelGGL(k_init_counts, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, (GenParams*)ctx->genp.p);
+    hipLaunchKernelGGL(k_init_counts<false>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, (GenParams*)ctx->genp.p, GenLens{});
     hipLaunchKernelGGL(k_debug_fill, dim3((n + 255u) / 256u), dim3(256), 0, st, gp, Q[0], d_o, d_d);
     const bool use_bvh = ctx->use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
     const StepBuffers sb{Q[0], Q[1], wv.qhit, counts, counts + nq, wv.rad,

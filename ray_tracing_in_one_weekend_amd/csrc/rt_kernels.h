@@ -76,6 +76,17 @@ struct GenParams {
     uint32_t tiles_per_row, tile_pixels;
     float inv_tpr;
 };
+// Thin lens of a frame (rt_set_lens), read by the LENS instantiations only.  The depth-0 kernels find it right behind the
+// slice's GenParams in HBM (gen_lens_of); the kernels that take GenParams by value get it as an argument of its own.  The
+// pinhole kernels keep their code and registers.
+struct GenLens {
+    float lu[3], lv[3]; // lens_radius * H / |H|, lens_radius * V / |V| (host: double, rounded once)
+    float focus_dist;
+    // k_primary_lists only (host: double, rounded up; DESIGN.md "Thin lens"):
+    float grow;     // >= |o - origin| of every sample, the rounding of o = origin + off included
+    float sin_tilt; // >= grow / (focus_dist * h), h = distance from origin to the image plane
+};
+__device__ __forceinline__ const GenLens& gen_lens_of(const GenParams* gpd) { return *reinterpret_cast<const GenLens*>(gpd + 1); }
 
 // x / d for the slot arithmetic of gen_primary / path_key_of_slot (quotients below 2^21): a float product that never exceeds the true quotient
 // (inv = (1/d)(1 - 2^-22) absorbs the roundings of the conversion and of the product) and two correction steps.
@@ -129,8 +140,13 @@ __device__ __forceinline__ void path_key_of_slot(const GenParams& gp, uint32_t s
 
 // Primary ray of path `idx` of the slice (main.rs:86-94 + camera.rs:40-46).
 // idx = s_local * npix + pixel_local, so consecutive idx are consecutive pixels of a row.
-__device__ __forceinline__ void gen_primary(const GenParams& gp, uint32_t idx, V3& o, V3& d, uint32_t& k0, uint32_t& k1,
-                                            uint32_t& pl) {
+// LENS: the book's thin-lens camera (rt_set_lens).  The eye point is drawn on the lens disc by random_in_unit_disk from counter 2
+// on (counters 2..255 are unused at depth 0, DESIGN.md "RNG"), and the ray aims at origin + focus_dist * dir, the point of the plane
+// of focus the pinhole ray reaches.  The pinhole instantiation does not read `gl`.
+#define RT_LENS_TRIPS 126u // counters 2..253; after the last trip the lens centre (probability 0.215^126)
+template <bool LENS>
+__device__ __forceinline__ void gen_primary(const GenParams& gp, const GenLens& gl, uint32_t idx, V3& o, V3& d, uint32_t& k0,
+                                            uint32_t& k1, uint32_t& pl) {
     uint32_t i;
     const uint32_t s_local = udiv_inv(idx, gp.npix, gp.inv_npix, pl); // pl = local pixel
     uint32_t lj;
@@ -149,12 +165,29 @@ __device__ __forceinline__ void gen_primary(const GenParams& gp, uint32_t idx, V
     const V3 Vv = v3(gp.cam_vertical[0], gp.cam_vertical[1], gp.cam_vertical[2]);
     const V3 llc = v3(gp.cam_llc[0], gp.cam_llc[1], gp.cam_llc[2]);
     o = origin;
-    d = normalize(llc + u * H + v * Vv - origin);
+    if (!LENS) {
+        d = normalize(llc + u * H + v * Vv - origin);
+    } else {
+        const V3 dir = llc + u * H + v * Vv - origin;
+        float rx = 0.0f, ry = 0.0f;
+        for (uint32_t t = 0; t < RT_LENS_TRIPS; ++t) { // while p.length_squared() >= 1.0
+            const float x = rng.next_pm1(), y = rng.next_pm1();
+            if (x * x + y * y < 1.0f) {
+                rx = x, ry = y;
+                break;
+            }
+        }
+        const V3 off = rx * v3(gl.lu[0], gl.lu[1], gl.lu[2]) + ry * v3(gl.lv[0], gl.lv[1], gl.lv[2]);
+        o = origin + off;
+        d = normalize(gl.focus_dist * dir - off);
+    }
     k0 = rng.k0, k1 = rng.k1;
 }
-__device__ __forceinline__ void gen_primary(const GenParams& gp, uint32_t idx, V3& o, V3& d, uint32_t& k0, uint32_t& k1) {
+template <bool LENS>
+__device__ __forceinline__ void gen_primary(const GenParams& gp, const GenLens& gl, uint32_t idx, V3& o, V3& d, uint32_t& k0,
+                                            uint32_t& k1) {
     uint32_t pl;
-    gen_primary(gp, idx, o, d, k0, k1, pl);
+    gen_primary<LENS>(gp, gl, idx, o, d, k0, k1, pl);
 }
 
 // Depth-0 queue geometry: chunks of 256 consecutive paths are dealt round-robin to the queue
@@ -165,11 +198,13 @@ __device__ __forceinline__ uint32_t primary_idx_of(uint32_t nq, uint32_t shard, 
 }
 // Number of primary rays of each shard (closed form of the mapping above).
 // Also parks the slice's GenParams in HBM for the depth-0 kernels (they read them through a
-// pointer: 24 dwords of kernel arguments would push k_intersect past 80 SGPRs and cost a wave).
+// pointer: 24 dwords of kernel arguments would push k_intersect past 80 SGPRs and cost a wave), and the lens behind them (LENS).
+template <bool LENS>
 __global__ __launch_bounds__(256) void k_init_counts(GenParams gp, uint32_t* __restrict__ counts,
-                                                     GenParams* __restrict__ gp_dev) {
+                                                     GenParams* __restrict__ gp_dev, GenLens gl) {
     const uint32_t sq = blockIdx.x * 256u + threadIdx.x;
     if (sq == 0) *gp_dev = gp;
+    if (LENS && sq == 0) *reinterpret_cast<GenLens*>(gp_dev + 1) = gl; // (gen_lens_of)
     if (sq >= gp.nq) return;
     const uint32_t nchunks = (gp.n_rays + 255u) / 256u;
     const uint32_t nc = sq < nchunks ? (nchunks - sq + gp.nq - 1u) / gp.nq : 0u;
@@ -181,12 +216,13 @@ __global__ __launch_bounds__(256) void k_init_counts(GenParams gp, uint32_t* __r
 // Materialises the primary rays in the queue.  Only the list-walk fallback uses it: on the BVH
 // path k_intersect and k_shade regenerate the ray of depth 0 from its queue position instead
 // (80 instructions twice per path against 48 B written + 80 B read back from HBM).
-__global__ __launch_bounds__(256) void k_gen_primary(GenParams gp, Queue q) {
+template <bool LENS>
+__global__ __launch_bounds__(256) void k_gen_primary(GenParams gp, Queue q, GenLens gl) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= gp.n_rays) return;
     V3 o, d;
     uint32_t k0, k1;
-    gen_primary(gp, idx, o, d, k0, k1);
+    gen_primary<LENS>(gp, gl, idx, o, d, k0, k1);
     const uint32_t chunk = idx >> 8;
     const uint32_t sq = chunk % gp.nq;
     const size_t pos = (size_t)sq * gp.cap + (size_t)(chunk / gp.nq) * 256u + (idx & 255u);
@@ -207,12 +243,15 @@ __global__ __launch_bounds__(256) void k_gen_primary(GenParams gp, Queue q) {
 #define RT_LIST_OVERFLOW 0xFFFFu
 #define RT_LIST_WAVE_CAP 512u // survivors of the wave-level cull kept per wave (more: the lanes scan all entries)
 // cone (axis, half-angle alpha given as sin/cos) against a bounding sphere seen from `origin`
-__device__ __forceinline__ bool cone_touches_sphere(V3 origin, V3 axis, float sa, float ca, float4 bs) {
+// LENS: the eye is anywhere within `grow` of `origin`, and the sphere grows by as much (k_primary_lists)
+template <bool LENS>
+__device__ __forceinline__ bool cone_touches_sphere(V3 origin, V3 axis, float sa, float ca, float4 bs, float grow) {
     const V3 c = v3(bs.x, bs.y, bs.z) - origin;
     // (the last term: `c` is a difference of fp32 coordinates, good to half an ulp of the larger one per component — nothing next to
     // the 0.1 % for a scene around the origin, the whole margin for a small sphere 1e5 units away from it)
     const float big = fmaxf(fmaxf(fmaxf(fabsf(bs.x), fabsf(bs.y)), fabsf(bs.z)), fmaxf(fmaxf(fabsf(origin.x), fabsf(origin.y)), fabsf(origin.z)));
-    const float r = bs.w * 1.001f + 1e-6f + big * (1.0f / 2097152.0f);
+    float r = bs.w * 1.001f + 1e-6f + big * (1.0f / 2097152.0f);
+    if (LENS) r += grow;
     const float dist2 = length_squared(c);
     if (!(dist2 > r * r * 1.0001f)) return true; // the eye is inside or on the bounding sphere (or NaN)
     const float dist = sqrtf(dist2);
@@ -226,7 +265,9 @@ __device__ __forceinline__ bool cone_touches_sphere(V3 origin, V3 axis, float sa
     if (c_theta > 0.0f && c_sum > 0.0f) return length(cross(c, axis)) <= s_sum * dist * 1.0001f + 1e-6f * dist;
     return c_theta >= c_sum * dist - 1e-5f * dist;
 }
-__global__ __launch_bounds__(256) void k_primary_lists(DevScene sc, GenParams gp, uint4* __restrict__ lists, uint32_t* __restrict__ n_overflow) {
+template <bool LENS>
+__global__ __launch_bounds__(256) void k_primary_lists(DevScene sc, GenParams gp, uint4* __restrict__ lists, uint32_t* __restrict__ n_overflow,
+                                                       GenLens gl) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float4* s_bs = reinterpret_cast<float4*>(smem);
     unsigned short* s_keep = reinterpret_cast<unsigned short*>(s_bs + sc.n_entries) + (threadIdx.x >> 6) * RT_LIST_WAVE_CAP;
@@ -263,7 +304,14 @@ __global__ __launch_bounds__(256) void k_primary_lists(DevScene sc, GenParams gp
     const float S = fmaxf(fmaxf(fabsf(llc.x) + fabsf(H.x) + fabsf(Vv.x) + fabsf(origin.x), fabsf(llc.y) + fabsf(H.y) + fabsf(Vv.y) + fabsf(origin.y)),
                           fabsf(llc.z) + fabsf(H.z) + fabsf(Vv.z) + fabsf(origin.z));
     const float rounding = 2.0f * 1.7321f * (S * (4.0f / 8388608.0f)) / (length(dc) * (1.0f - smax));
-    const float alpha = asinf(fminf(smax, 1.0f)) * 1.02f + 1e-4f + rounding;
+    float alpha = asinf(fminf(smax, 1.0f)) * 1.02f + 1e-4f + rounding;
+    // Thin lens (DESIGN.md "Thin lens"): a sample's ray runs from o, |o - origin| <= grow, to P = origin + focus_dist * dir on the
+    // plane of focus, and dir lies in the cone above.  Its direction P - o is off P - origin by at most asin(grow / |P - origin|) <=
+    // asin(sin_tilt), so every point o + t (P - o) lies within grow of the ray origin + t (P - o) of the widened cone: the cone opens by
+    // the tilt and every bounding sphere grows by `grow` (cone_touches_sphere<true>).  focus_dist * dir - off and origin + off are two
+    // more roundings of operands up to focus_dist * S + grow: another 2 x `rounding` for tilts below 30 degrees (the host gives up the
+    // lists above: sin_tilt 1).
+    if (LENS) alpha += asinf(fminf(gl.sin_tilt, 1.0f)) * 1.02f + 2.0f * rounding;
     const bool unusable = !(alpha < 1.5f); // (or NaN) no cone to speak of: the pixel's rays use the tree
     const float ca = cosf(alpha), sa = sinf(alpha);
 
@@ -290,7 +338,7 @@ __global__ __launch_bounds__(256) void k_primary_lists(DevScene sc, GenParams gp
     if (!wide) {
         for (uint32_t e0 = 0; e0 < sc.n_entries; e0 += 64u) {
             const uint32_t e = e0 + lane;
-            const bool keep = e < sc.n_entries && cone_touches_sphere(origin, waxis, wsa, wca, s_bs[e]);
+            const bool keep = e < sc.n_entries && cone_touches_sphere<LENS>(origin, waxis, wsa, wca, s_bs[e], gl.grow);
             const unsigned long long m = __ballot(keep);
             const uint32_t cnt = (uint32_t)__popcll(m);
             if (n_keep + cnt > RT_LIST_WAVE_CAP) {
@@ -309,7 +357,7 @@ __global__ __launch_bounds__(256) void k_primary_lists(DevScene sc, GenParams gp
     const uint32_t n_scan = scan_all ? sc.n_entries : n_keep;
     for (uint32_t t0 = 0; t0 < n_scan; ++t0) {
         const uint32_t e = scan_all ? t0 : (uint32_t)s_keep[t0];
-        if (cone_touches_sphere(origin, axis, sa, ca, s_bs[e])) {
+        if (cone_touches_sphere<LENS>(origin, axis, sa, ca, s_bs[e], gl.grow)) {
 #pragma unroll
             for (uint32_t t = 0; t < RT_LIST_MAX; ++t)
                 if (n == t) ids[t] = sc.ent_leaf[e];
@@ -861,8 +909,8 @@ struct IntersectParams {
 // __launch_bounds__ argument = waves per SIMD on AMD; 16 B of scratch in the cold path) so that two
 // 1024-thread workgroups (8 waves per SIMD) share a CU and hide each other's dependent node fetches
 // — measured +15 % on cornell_box and +20 % on final_scene against 7 waves = one workgroup.
-// GEN (depth 0): the ray is regenerated from its queue position instead of being loaded.
-template <int BLOCK, bool GEN, bool RECTS, bool LDS_NODES, bool GLDS, bool NEST = false>
+// GEN (depth 0): the ray is regenerated from its queue position instead of being loaded; LENS (with GEN): through the thin lens.
+template <int BLOCK, bool GEN, bool RECTS, bool LDS_NODES, bool GLDS, bool NEST = false, bool LENS = false>
 __global__ __launch_bounds__(BLOCK, 8) void k_intersect(DevScene sc, const float4* __restrict__ qa,
                                                      const float4* __restrict__ qb,
                                                      float2* __restrict__ qh, const uint32_t* __restrict__ in_counts,
@@ -939,7 +987,7 @@ __global__ __launch_bounds__(BLOCK, 8) void k_intersect(DevScene sc, const float
                 if (!skip) {
                 if (GEN) {
                     uint32_t k0, k1, pl;
-                    gen_primary(*gpd, primary_idx_of(ip.nq, shard, off), o, d, k0, k1, pl);
+                    gen_primary<LENS>(*gpd, gen_lens_of(gpd), primary_idx_of(ip.nq, shard, off), o, d, k0, k1, pl);
                     if (RECTS) mc.k0 = k0, mc.k1 = k1;
                     if (gpd->lists) list = gpd->lists[pl];
                 } else {
@@ -1123,7 +1171,7 @@ __host__ __device__ inline size_t shade_lds_bytes(uint32_t n_entries, uint32_t n
     b += (size_t)n_fused_spheres * 16u;
     return (b + 15u) & ~(size_t)15u;
 }
-template <bool PERLIN_LDS, bool GEN, bool RECTS, bool NEST = false> // NEST (general scenes only): rt_device.h, wrapper chains and media as loops
+template <bool PERLIN_LDS, bool GEN, bool RECTS, bool NEST = false, bool LENS = false> // NEST (general scenes only): rt_device.h, wrapper chains and media as loops; LENS (with GEN): the thin lens
 #ifndef RT_GEN_WAVES
 #define RT_GEN_WAVES 4 // waves per SIMD the depth-0 instantiations are compiled for (98 VGPR: 5 fit).  Round 2: 4 / 5 / 6 no difference.
                        // Round 3 (cheaper draws): alone on the chip, 6 (80 VGPR, 8 B of scratch) is 2.4-2.7 % faster at depth 0 on the
@@ -1317,7 +1365,7 @@ __global__ __launch_bounds__(256, GEN ? RT_GEN_WAVES : RT_SORTED_WAVES) void k_s
                 if (GEN) { // depth 0: T = 1, slot = path index, ray regenerated (bitwise the one k_intersect would trace)
                     uint32_t pl;
                     slot = primary_idx_of(tp.nq, q, base + j);
-                    gen_primary(*gpd, slot, o, d, k0, k1, pl);
+                    gen_primary<LENS>(*gpd, gen_lens_of(gpd), slot, o, d, k0, k1, pl);
                     T = splat(1.0f);
                     uint4 list = make_uint4(RT_LIST_OVERFLOW, 0u, 0u, 0u);
                     if (fused) list = gpd->lists[pl];

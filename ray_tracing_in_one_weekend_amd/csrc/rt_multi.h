@@ -184,6 +184,15 @@ int rt_multi_scene_upload(RtMulti* m, const RtFlatScene* scene) {
     return RT_OK;
 }
 
+int rt_multi_set_lens(RtMulti* m, const RtLens* lens) {
+    if (!m) return RT_ERR_INVALID;
+    for (size_t i = 0; i < m->ctx.size(); ++i) { // (the first context refuses what all would: then none has changed)
+        const int rc = rt_set_lens(m->ctx[i], lens);
+        if (rc) return multi_fail(m, rc, std::string("device ") + std::to_string(m->devices[i]) + ": " + rt_last_error(m->ctx[i]));
+    }
+    return RT_OK;
+}
+
 int rt_deinterleave_bands(RtCtx* ctx, const void* d_gathered, uint32_t nx, uint32_t ny, uint32_t band, uint32_t n_shards,
                           void* d_out_rgb_f32, void* d_out_rgb8, void* stream) {
     if (!ctx) return RT_ERR_INVALID;

@@ -13,6 +13,7 @@ struct RthScene {
     bool has_camera = false;
     Camera camera;
     RtCamera rt_camera{};
+    RtLens rt_lens{0.0f, 1.0f};
     bool finished = false;
     FlatSceneBuilder builder;
     RtFlatScene flat{};
@@ -54,6 +55,7 @@ int finish(RthScene* s, bool use_bvh) {
     flatten_world(world, s->builder);
     s->flat = s->builder.view();
     s->rt_camera = s->camera.flatten();
+    s->rt_lens = s->camera.lens();
     s->finished = true;
     return RT_OK;
 }
@@ -257,6 +259,17 @@ int rth_set_camera(RthScene* s, const float lookfrom[3], const float lookat[3], 
     });
 }
 
+int rth_set_camera_lens(RthScene* s, const float lookfrom[3], const float lookat[3], const float vup[3], float vfov,
+                        float aspect_ratio, float aperture, float focus_dist) {
+    return guarded([&] {
+        if (!std::isfinite(aperture) || !std::isfinite(focus_dist) || aperture < 0.0f || !(focus_dist > 0.0f))
+            throw std::runtime_error("rth_set_camera_lens: aperture must be finite and >= 0, focus_dist finite and > 0");
+        s->camera = Camera::new_lens(v(lookfrom), v(lookat), v(vup), vfov, aspect_ratio, aperture, focus_dist);
+        s->has_camera = true;
+        return RT_OK;
+    });
+}
+
 int rth_scene_finish(RthScene* s, int use_bvh) {
     return guarded([&] { return finish(s, use_bvh != 0); });
 }
@@ -266,6 +279,12 @@ const RtFlatScene* rth_scene_flat(const RthScene* s) { return (s && s->finished)
 int rth_scene_camera(const RthScene* s, RtCamera* out) {
     if (!s || !out || !s->finished) return RT_ERR_INVALID;
     *out = s->rt_camera;
+    return RT_OK;
+}
+
+int rth_scene_lens(const RthScene* s, RtLens* out) {
+    if (!s || !out || !s->finished) return RT_ERR_INVALID;
+    *out = s->rt_lens;
     return RT_OK;
 }
 

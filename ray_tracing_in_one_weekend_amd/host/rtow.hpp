@@ -740,6 +740,14 @@ class Camera {
         c.lower_left_corner = c.origin - c.horizontal / 2.0f - c.vertical / 2.0f - w;
         return c;
     }
+    // The book's thin-lens camera (Camera::new(.., aperture, focus_dist), chapter 13; camera.rs has no lens): the flattened RtCamera is
+    // new_'s bit for bit, the lens goes beside it (lens(), rt_set_lens).
+    static Camera new_lens(Vec3A lookfrom, Vec3A lookat, Vec3A vup, float vfov, float aspect_ratio, float aperture, float focus_dist) {
+        Camera c = new_(lookfrom, lookat, vup, vfov, aspect_ratio);
+        c.lens_radius = aperture / 2.0f;
+        c.focus_dist = focus_dist;
+        return c;
+    }
     // the accessor the private fields need (SURVEY.md §8(b) "Obstacle to flattening")
     RtCamera flatten() const {
         RtCamera r;
@@ -748,9 +756,11 @@ class Camera {
         for (int k = 0; k < 4; ++k) dst[k][0] = src[k]->x, dst[k][1] = src[k]->y, dst[k][2] = src[k]->z;
         return r;
     }
+    RtLens lens() const { return RtLens{lens_radius, focus_dist}; }
 
   private:
     Vec3A origin, horizontal, vertical, lower_left_corner;
+    float lens_radius = 0.0f, focus_dist = 1.0f; // new_: a pinhole
 };
 
 // Flattens a world + the global sky state into `b`.

@@ -29,6 +29,9 @@ def main(argv=None):
     ap.add_argument("--preview-every", type=int, default=0, metavar="SPP",
                     help="save a partial image every SPP samples (main.rs:114-123 saves every 10 columns)")
     ap.add_argument("--out", default=None, help="default: the reference's <local time>.png (main.rs:110-112)")
+    ap.add_argument("--aperture", type=float, default=0.0,
+                    help="thin-lens aperture of the book's Camera::new (chapter 13; the cover: 0.1); 0 = pinhole")
+    ap.add_argument("--focus-dist", type=float, default=10.0, help="distance of the plane of focus (with --aperture)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     ny = a.ny
@@ -40,6 +43,8 @@ def main(argv=None):
     scene = Scene.build(a.scene, aspect)
     rend = Renderer(a.device)
     rend.upload(scene)
+    if a.aperture:
+        rend.set_lens((a.aperture / 2.0, a.focus_dist))
     flags = _ffi.FLAG_RUSSIAN_ROULETTE if a.russian_roulette else 0
     params = make_params(a.nx, ny, a.spp, max_depth=a.max_depth, seed=a.seed, spp_slice=a.preview_every, flags=flags)
     if a.preview_every:
