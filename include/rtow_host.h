@@ -53,6 +53,10 @@ uint32_t rth_tex_image(RthScene* s, const char* path);
  * p = the scalar fields in the order documented at RtMatType. */
 uint32_t rth_material(RthScene* s, uint32_t type, uint32_t tex0, uint32_t tex1, const float color[3], const float p[4]);
 uint32_t rth_sphere(RthScene* s, const float c[3], float r, uint32_t material, const char* name);
+/* "The Next Week" chapter 1, MovingSphere::new(center0, center1, radius, material): the centre moves linearly from c0 (time 0) to c1
+ * (time 1).  Flattens to the sphere at c0 plus an entry of rth_scene_motion; only at the top level of the world (not below
+ * rth_translate / rth_rotate_y, not as a medium boundary: rth_scene_finish fails). */
+uint32_t rth_moving_sphere(RthScene* s, const float c0[3], const float c1[3], float r, uint32_t material, const char* name);
 /* hitable.rs:244-362 XYRect/XZRect/YZRect { min, max, mat } (axis = RtRectAxis) and hitable.rs:364-383 GBox::new */
 uint32_t rth_rect(RthScene* s, uint32_t axis, const float mn[3], const float mx[3], uint32_t material);
 uint32_t rth_gbox(RthScene* s, const float mn[3], const float mx[3], uint32_t material);
@@ -74,6 +78,8 @@ int rth_set_camera(RthScene* s, const float lookfrom[3], const float lookat[3], 
  * focus_dist > 0, both finite. */
 int rth_set_camera_lens(RthScene* s, const float lookfrom[3], const float lookat[3], const float vup[3], float vfov,
                         float aspect_ratio, float aperture, float focus_dist);
+/* The camera's shutter, after rth_set_camera / rth_set_camera_lens: 0 <= shutter_open <= shutter_close <= 1 (default 0, 1). */
+int rth_set_camera_shutter(RthScene* s, float shutter_open, float shutter_close);
 /* Wraps everything added so far in a BvhNode like build_bvh (demo_scene.rs:223-227) and flattens. */
 int rth_scene_finish(RthScene* s, int use_bvh);
 
@@ -81,6 +87,9 @@ const RtFlatScene* rth_scene_flat(const RthScene* s);
 int rth_scene_camera(const RthScene* s, RtCamera* out);
 /* The lens of the finished scene's camera: {0, 1} for a pinhole one. */
 int rth_scene_lens(const RthScene* s, RtLens* out);
+/* The motion of the finished scene for rt_set_motion: its moving spheres (pointers into the scene, valid until rth_scene_free) and the
+ * camera's shutter; n_moving 0 for a static scene. */
+int rth_scene_motion(const RthScene* s, RtMotion* out);
 const char* rth_scene_sphere_name(const RthScene* s, uint32_t index);
 void rth_scene_free(RthScene* s);
 

@@ -343,6 +343,25 @@ typedef struct RtLens {
  * lens_radius >= 0 and, where lens_radius > 0, focus_dist > 0. */
 int rt_set_lens(RtCtx* ctx, const RtLens* lens);
 
+/* Motion blur ("The Next Week", chapter 1): spheres whose centre moves linearly while the shutter is open, every path carrying a time.
+ * Sphere `sphere[k]` of the uploaded scene has its RtFlatScene centre c0 at time 0 and center1[3 k ..] at time 1; radius, material and
+ * name stay.  A path's time is tm = shutter_open + u * (shutter_close - shutter_open), u the f32 draw of counter 254 of the path's key
+ * (one time for all its segments); the sphere is then hit at c(tm) = c0 + tm * (c1 - c0), every operation rounded to f32 (c1 - c0
+ * once, at this call), exactly as a static sphere at c(tm) would be.  DESIGN.md "Moving spheres".
+ * Only bare spheres move: one below a Translate / RotateY wrapper or bounding a medium is RT_ERR_UNSUPPORTED. */
+typedef struct RtMotion {
+    uint32_t n_moving;
+    const uint32_t* sphere;   /* [n_moving] sphere indices of the uploaded scene, strictly increasing */
+    const float* center1;     /* [3*n_moving] centre at time 1 */
+    float shutter_open, shutter_close; /* 0 <= shutter_open <= shutter_close <= 1 */
+} RtMotion;
+/* The motion of every following render of `ctx`, after rt_scene_upload (RT_ERR_STATE before); rt_scene_upload clears it (the indices
+ * belong to a scene).  NULL or n_moving 0: the static renderer, bit for bit.  n_moving > 0 selects the motion kernels even when no
+ * sphere is displaced, and rebuilds what bounds the listed spheres (tree leaves, grid cells, candidate-list spheres) over the region
+ * they sweep.  RT_ERR_INVALID (indices unsorted, repeated or out of range, non-finite center1, a shutter outside
+ * 0 <= open <= close <= 1) or RT_ERR_UNSUPPORTED: the previous motion stays.  The arrays are copied. */
+int rt_set_motion(RtCtx* ctx, const RtMotion* motion);
+
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the
  * world shared read-only (main.rs:72-108); here the scene is replicated on every device, device r renders the image
@@ -374,6 +393,9 @@ int rt_multi_render(RtMulti* m, const RtCamera* cam, const RtParams* params, flo
                     RtStats* stats);
 /* rt_set_lens on every device (all or none: the values are checked by the first). */
 int rt_multi_set_lens(RtMulti* m, const RtLens* lens);
+/* rt_set_motion on every device.  An invalid motion is refused by the first device and none has changed; a device-side failure
+ * (RT_ERR_NOMEM, RT_ERR_DEVICE) on a later device leaves every device with NO motion (the static renderer), not the previous one. */
+int rt_multi_set_motion(RtMulti* m, const RtMotion* motion);
 /* The de-interleave step on its own: `d_gathered` is a DEVICE buffer of n_shards band buffers, each
  * max_r rt_shard_rows(ny, band, n_shards, r) rows of nx*3 floats (what the gather delivers); writes the frame in
  * image row order to d_out_rgb_f32 [ny*nx*3] and / or the quantised, flipped image to d_out_rgb8 (device pointers,

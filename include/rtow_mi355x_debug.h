@@ -122,6 +122,18 @@ int rt_debug_grid_build(const RtFlatScene* scene, uint32_t cell_per_mille, uint3
 int rt_debug_world_bounds(const RtFlatScene* scene, float* prim_box, float* prim_box_padded, float* world_sphere, uint32_t* n_entries,
                           uint32_t* entry_id, float* entry_box_padded, float* entry_bs);
 
+/* The bounds rt_set_motion built for the uploaded scene with its motion (RT_ERR_STATE when none is set), for tests of their
+ * conservativeness.  Arrays are caller-owned:
+ *   entry_box_padded[6 * n]  the box the tree stores for every world entry (a moving sphere: around the region it sweeps);
+ *   entry_sphere[4 * n]      the bounding sphere k_primary_lists tests for it;
+ *   entry_id[n]              primitive i, or n_prims + medium m;          entry_cap = capacity of these three, *n_entries = n;
+ *   grid[0..2] = min corner, grid[3..5] = cell edges, dims = cells per axis (all 0: the scene with its motion has no grid);
+ *   cell_begin[n_moving + 1], cell_id[*n_cell_ids]: the cells (x fastest) that list moving sphere k are cell_id[cell_begin[k] ..
+ *   cell_begin[k + 1]); a single entry 0xFFFFFFFF: the sphere is "large" and tested for every ray.  cell_cap = capacity of cell_id.
+ * Returns RT_ERR_INVALID when a buffer is missing or too small (the needed counts are then in *n_entries / *n_cell_ids). */
+int rt_debug_motion_bounds(const RtCtx* ctx, float* entry_box_padded, float* entry_sphere, uint32_t* entry_id, uint32_t entry_cap, uint32_t* n_entries,
+                           float grid[6], uint32_t dims[3], uint32_t* cell_begin, uint32_t* cell_id, uint32_t cell_cap, uint32_t* n_cell_ids);
+
 #ifdef RT_PROFILE_LANES
 /* Diagnostic builds only (-DRT_PROFILE_LANES; absent from the product library): the lane-occupancy counters of
  * csrc/rt_kernels.h, optionally reset after reading. */

@@ -73,6 +73,13 @@ class RtLens(C.Structure):
     _fields_ = [("lens_radius", C.c_float), ("focus_dist", C.c_float)]
 
 
+class RtMotion(C.Structure):
+    """rt_set_motion: sphere `sphere[k]` moves linearly from its RtFlatScene centre (time 0) to center1[3 k ..] (time 1); a path's
+    time lies in [shutter_open, shutter_close]."""
+    _fields_ = [("n_moving", C.c_uint32), ("sphere", C.POINTER(C.c_uint32)), ("center1", C.POINTER(C.c_float)),
+                ("shutter_open", C.c_float), ("shutter_close", C.c_float)]
+
+
 class RtParams(C.Structure):
     _fields_ = [("nx", C.c_uint32), ("ny", C.c_uint32), ("spp", C.c_uint32), ("max_depth", C.c_int32),
                 ("seed", C.c_uint64), ("shard_band", C.c_uint32), ("shard_count", C.c_uint32),
@@ -129,12 +136,14 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_shard_rows", "rt_shard_row_to_image_row", "rt_prepare", "rt_render", "rt_render_device", "rt_debug_bounce", "rt_debug_arithmetic",
                "rt_get_depth_timings", "rt_set_progress", "rt_host_alloc", "rt_host_free", "rt_debug_set_option", "rt_debug_get_option",
                "rt_debug_scene_info", "rt_debug_grid_build", "rt_debug_world_bounds", "rt_debug_render_parts", "rt_multi_create", "rt_multi_create_ex", "rt_multi_destroy", "rt_multi_device_count",
-               "rt_multi_last_error", "rt_multi_scene_upload", "rt_multi_render", "rt_deinterleave_bands", "rt_set_lens", "rt_multi_set_lens"]
+               "rt_multi_last_error", "rt_multi_scene_upload", "rt_multi_render", "rt_deinterleave_bands", "rt_set_lens", "rt_multi_set_lens",
+               "rt_set_motion", "rt_multi_set_motion", "rt_debug_motion_bounds"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
                 "rth_sphere", "rth_rect", "rth_gbox", "rth_translate", "rth_rotate_y", "rth_constant_medium", "rth_hitable_bbox", "rth_set_sky", "rth_set_camera", "rth_scene_finish", "rth_scene_flat",
                 "rth_scene_camera", "rth_scene_sphere_name", "rth_scene_free", "rth_png_write", "rth_output_file_name",
-                "rth_set_camera_lens", "rth_scene_lens"]
+                "rth_set_camera_lens", "rth_scene_lens",
+                "rth_moving_sphere", "rth_set_camera_shutter", "rth_scene_motion"]
 
 _gpu_lib = None
 _host_lib = None
@@ -190,6 +199,13 @@ def load_gpu_library():
     lib.rt_set_lens.restype = C.c_int
     lib.rt_multi_set_lens.argtypes = [vp, C.POINTER(RtLens)]
     lib.rt_multi_set_lens.restype = C.c_int
+    lib.rt_set_motion.argtypes = [vp, C.POINTER(RtMotion)]
+    lib.rt_set_motion.restype = C.c_int
+    lib.rt_multi_set_motion.argtypes = [vp, C.POINTER(RtMotion)]
+    lib.rt_multi_set_motion.restype = C.c_int
+    lib.rt_debug_motion_bounds.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.c_float * 6, C.c_uint32 * 3, vp, vp, C.c_uint32,
+                                           C.POINTER(C.c_uint32)]
+    lib.rt_debug_motion_bounds.restype = C.c_int
     lib.rt_host_alloc.argtypes = [C.c_size_t]
     lib.rt_host_alloc.restype = vp
     lib.rt_host_free.argtypes = [vp]
@@ -284,6 +300,12 @@ def load_host_library():
     lib.rth_set_camera_lens.restype = C.c_int
     lib.rth_scene_lens.argtypes = [vp, C.POINTER(RtLens)]
     lib.rth_scene_lens.restype = C.c_int
+    lib.rth_moving_sphere.argtypes = [vp, f3, f3, C.c_float, C.c_uint32, C.c_char_p]
+    lib.rth_moving_sphere.restype = C.c_uint32
+    lib.rth_set_camera_shutter.argtypes = [vp, C.c_float, C.c_float]
+    lib.rth_set_camera_shutter.restype = C.c_int
+    lib.rth_scene_motion.argtypes = [vp, C.POINTER(RtMotion)]
+    lib.rth_scene_motion.restype = C.c_int
     lib.rth_scene_sphere_name.argtypes = [vp, C.c_uint32]
     lib.rth_scene_sphere_name.restype = C.c_char_p
     lib.rth_scene_free.argtypes = [vp]

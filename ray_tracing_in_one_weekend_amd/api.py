@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import RtBounceIO, RtCamera, RtFlatScene, RtLens, RtParams, RtStats
+from ._ffi import RtBounceIO, RtCamera, RtFlatScene, RtLens, RtMotion, RtParams, RtStats
 
 
 class RtError(RuntimeError):
@@ -27,6 +27,26 @@ def _lens_ptr(lens):
     if not isinstance(lens, RtLens):
         lens = RtLens(*[float(x) for x in lens])
     return C.byref(lens)
+
+
+def make_motion(spheres, center1, shutter=(0.0, 1.0)):
+    """An RtMotion (with its arrays kept alive on it) from sphere indices, their centres at time 1 [n, 3] and the shutter interval."""
+    idx = np.ascontiguousarray(spheres, dtype=np.uint32).ravel()
+    c1 = np.ascontiguousarray(center1, dtype=np.float32).reshape(-1)
+    if c1.size != 3 * idx.size:
+        raise RtError("make_motion: center1 must hold three floats per listed sphere")
+    m = RtMotion(idx.size, idx.ctypes.data_as(C.POINTER(C.c_uint32)), c1.ctypes.data_as(C.POINTER(C.c_float)), float(shutter[0]), float(shutter[1]))
+    m._keep = (idx, c1)
+    return m
+
+
+def _motion_ptr(motion):
+    """None -> NULL (the static renderer); an RtMotion (Scene.motion, make_motion) -> a pointer to it"""
+    if motion is None:
+        return None
+    if not isinstance(motion, RtMotion):
+        motion = make_motion(*motion)
+    return C.byref(motion)
 
 
 class Scene:
@@ -81,6 +101,10 @@ class Scene:
     def sphere(self, c, r, material, name=""):
         return self._check(self._lib.rth_sphere(self._h, _f3(c), C.c_float(r), material, name.encode()))
 
+    def moving_sphere(self, c0, c1, r, material, name=""):
+        """A sphere whose centre moves linearly from c0 (time 0) to c1 (time 1): motion blur.  Only at the top level of the world."""
+        return self._check(self._lib.rth_moving_sphere(self._h, _f3(c0), _f3(c1), C.c_float(r), material, name.encode()))
+
     def rect(self, axis, mn, mx, material):
         return self._check(self._lib.rth_rect(self._h, axis, _f3(mn), _f3(mx), material))
 
@@ -108,15 +132,18 @@ class Scene:
         if self._lib.rth_set_sky(self._h, sky, env_path.encode() if env_path else None) != 0:
             raise RtError(self._lib.rth_last_error().decode())
 
-    def set_camera(self, lookfrom, lookat, vup, vfov, aspect_ratio, aperture=0.0, focus_dist=1.0):
+    def set_camera(self, lookfrom, lookat, vup, vfov, aspect_ratio, aperture=0.0, focus_dist=1.0, shutter=(0.0, 1.0)):
         """Camera::new (camera.rs:14-39); with an aperture, the book's thin-lens camera (chapter 13): the same RtCamera, and
-        Scene.lens = (aperture / 2, focus_dist) for Renderer.set_lens."""
+        Scene.lens = (aperture / 2, focus_dist) for Renderer.set_lens.  shutter = (open, close) within [0, 1]: the interval the
+        times of Scene.motion are drawn from."""
         if aperture == 0.0 and focus_dist == 1.0:
             rc = self._lib.rth_set_camera(self._h, _f3(lookfrom), _f3(lookat), _f3(vup), C.c_float(vfov), C.c_float(aspect_ratio))
         else:
             rc = self._lib.rth_set_camera_lens(self._h, _f3(lookfrom), _f3(lookat), _f3(vup), C.c_float(vfov), C.c_float(aspect_ratio),
                                                C.c_float(aperture), C.c_float(focus_dist))
         if rc != 0:
+            raise RtError(self._lib.rth_last_error().decode())
+        if tuple(shutter) != (0.0, 1.0) and self._lib.rth_set_camera_shutter(self._h, C.c_float(shutter[0]), C.c_float(shutter[1])) != 0:
             raise RtError(self._lib.rth_last_error().decode())
 
     def finish(self, use_bvh=True):
@@ -153,6 +180,16 @@ class Scene:
         if self._lib.rth_scene_lens(self._h, C.byref(lens)) != 0:
             raise RtError("scene not finished")
         return lens
+
+    @property
+    def motion(self):
+        """RtMotion of the scene (rth_scene_motion): its moving spheres and the camera's shutter; n_moving 0 for a static scene.  It
+        points into the scene.  Renderer.upload does not apply it: pass it to set_motion."""
+        m = RtMotion()
+        if self._lib.rth_scene_motion(self._h, C.byref(m)) != 0:
+            raise RtError("scene not finished")
+        m._keep = self
+        return m
 
     def sphere_name(self, i):
         return self._lib.rth_scene_sphere_name(self._h, i).decode()
@@ -379,6 +416,37 @@ class Renderer:
         if rc != 0:
             self._raise("rt_set_lens", rc)
 
+    def set_motion(self, motion):
+        """rt_set_motion: the moving spheres of the following renders — Scene.motion, make_motion(..) or a (spheres, center1[, shutter])
+        tuple; None: the static renderer.  After upload(); upload() clears it."""
+        if motion is not None and not isinstance(motion, RtMotion):
+            motion = make_motion(*motion)
+        rc = self._lib.rt_set_motion(self._ctx, _motion_ptr(motion))
+        if rc != 0:
+            self._raise("rt_set_motion", rc)
+        self._n_moving = motion.n_moving if motion is not None else 0  # (motion_bounds sizes its cell table by it)
+
+    def motion_bounds(self):
+        """rt_debug_motion_bounds as a dict: the bounds set_motion built (padded entry boxes, candidate-list spheres, entry ids, the
+        grid and the cells that list each moving sphere; a cell list [0xFFFFFFFF] = tested for every ray)."""
+        n, nc = C.c_uint32(0), C.c_uint32(0)
+        grid, dims = (C.c_float * 6)(), (C.c_uint32 * 3)()
+        # the sizing call: RT_ERR_INVALID ("a buffer is missing", the counts are filled in) is its expected answer
+        rc = self._lib.rt_debug_motion_bounds(self._ctx, None, None, None, 0, C.byref(n), grid, dims, None, None, 0, C.byref(nc))
+        if rc not in (0, -1):
+            self._raise("rt_debug_motion_bounds", rc)
+        boxes = np.zeros((n.value, 6), np.float32)
+        bs = np.zeros((n.value, 4), np.float32)
+        ids = np.zeros(n.value, np.uint32)
+        cells = np.zeros(max(nc.value, 1), np.uint32)
+        begin = np.zeros(getattr(self, "_n_moving", 0) + 1, np.uint32)  # the call writes n_moving + 1 entries
+        rc = self._lib.rt_debug_motion_bounds(self._ctx, boxes.ctypes.data, bs.ctypes.data, ids.ctypes.data, n.value, C.byref(n), grid, dims,
+                                              begin.ctypes.data, cells.ctypes.data, cells.size, C.byref(nc))
+        if rc != 0:
+            self._raise("rt_debug_motion_bounds", rc)
+        return {"entry_box_padded": boxes, "entry_sphere": bs, "entry_id": ids, "grid_min": np.array(grid[0:3], np.float32),
+                "grid_cell": np.array(grid[3:6], np.float32), "grid_dims": tuple(dims), "cell_begin": begin, "cell_id": cells[:nc.value]}
+
     def render_device(self, camera, params, device_ptr, stream=None, want_stats=True):
         """Renders into HBM at `device_ptr` (e.g. torch_tensor.data_ptr()); nothing crosses PCIe."""
         stats = RtStats()
@@ -537,6 +605,12 @@ class MultiRenderer:
         rc = self._lib.rt_multi_set_lens(self._m, _lens_ptr(lens))
         if rc != 0:
             self._raise("rt_multi_set_lens", rc)
+
+    def set_motion(self, motion):
+        """rt_multi_set_motion: Renderer.set_motion on every device."""
+        rc = self._lib.rt_multi_set_motion(self._m, _motion_ptr(motion))
+        if rc != 0:
+            self._raise("rt_multi_set_motion", rc)
 
     def render(self, camera, params, want_rgb8=False):
         """Returns (f32 image [ny, nx, 3] (row 0 = bottom), rgb8 or None, RtStats summed over the devices)."""

@@ -83,6 +83,33 @@ struct RtCtx {
     uint32_t* h_overflow = nullptr;
     long long last_overflow = -1; // that count for the last frame (rt_debug_render_parts); -1: it made no lists or did not read it
     RtLens lens{0.0f, 1.0f};      // rt_set_lens (lens_radius 0: the pinhole)
+    // rt_set_motion.  The search state above (ds, tree placement, grid) is the ACTIVE one; `static_search` is what rt_scene_upload
+    // built, `keep` what rt_set_motion needs of the scene on the host to bound the moved spheres again.  Clearing the motion puts
+    // static_search back: the static renderer, its arrays, kernels and bits.
+    struct Search {
+        DevScene ds{};
+        bool use_bvh = false, bvh_in_lds = false, general_lds = false, use_grid = false;
+        size_t isect_lds = 0, grid_lds = 0;
+        GridParams grid{};
+    } static_search;
+    struct Keep {
+        std::vector<float4> geo;         // spheres (c0, r)
+        std::vector<PrimBox> eboxes;     // world entries, unpadded
+        std::vector<uint32_t> entry_ids;
+        std::vector<float4> ent_bs;
+        std::vector<uint8_t> bare;       // per sphere: no wrapper, not a medium boundary
+        uint32_t bvh_depth = 0;
+    } keep;
+    bool motion = false;           // the MOTION instantiations (n_moving > 0)
+    GenMotion gmotion{};           // (sph_dc in motion_region)
+    size_t motion_lds = 0;         // 16 B per sphere beside the geometry where it is staged in LDS
+    DevBuf motion_region;          // the arrays rt_set_motion uploads: displacements, tree, bounding spheres, grid
+    struct MotionDebug {           // rt_debug_motion_bounds
+        std::vector<uint32_t> sphere;
+        std::vector<PrimBox> eboxes; // unpadded (pad_prim_box is applied on the way out, as the builder does)
+        std::vector<float4> ent_bs;
+        HostGrid grid;
+    } motion_dbg;
     // progressive preview (rt_set_progress): called from rt_render after every slice
     RtProgressFn progress_fn = nullptr;
     void* progress_user = nullptr;
@@ -275,6 +302,7 @@ struct StepBuffers {
     unsigned long long* totals;
     const GenParams* gpd;
     bool lens = false; // depth 0 through the thin lens (the LENS instantiations)
+    bool motion = false; // moving spheres (the MOTION instantiations)
 };
 bool scene_is_general(const RtCtx* ctx) { return ctx->general_kernels; }
 bool grid_enabled(const RtCtx* ctx) { return ctx->use_grid && ctx->opt[RT_OPT_GRID] != 1u && !scene_is_general(ctx); }
@@ -284,13 +312,21 @@ bool scene_perlin_lds(const RtCtx* ctx) { return ctx->ds.n_perlin > 0 && ctx->ds
 void launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32_t grid, const StepBuffers& b, const IntersectParams& ip) {
     const bool rects = scene_is_general(ctx);
     if (use_bvh && !gen && grid_enabled(ctx)) { // sphere-only scene, depth >= 1: the grid walk (rt_grid.h), same hit records
-        if (ctx->grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid<true>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->grid_lds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
+        const size_t mlds = ctx->grid_lds + ctx->motion_lds;
+        if (b.motion && ctx->grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid_motion<true>, dim3(grid), dim3(RT_BVH_BLOCK), mlds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        else if (b.motion) hipLaunchKernelGGL(k_intersect_grid_motion<false>, dim3(grid), dim3(RT_BVH_BLOCK), mlds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        else if (ctx->grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid<true>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->grid_lds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
         else hipLaunchKernelGGL(k_intersect_grid<false>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->grid_lds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
         return;
     }
+#define RT_LAUNCH_ISECT_M(G, R, N, T, X, L)                                                                                      \
+    hipLaunchKernelGGL((k_intersect<RT_BVH_BLOCK, G, R, N, T, X, L, true>), dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg, ctx->ds, \
+                       b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd)
 #define RT_LAUNCH_ISECT_X(G, R, N, T, X)                                                                               \
     do {                                                                                                                \
-        if (G && b.lens)                                                                                                \
+        if (b.motion && G && b.lens) RT_LAUNCH_ISECT_M(G, R, N, T, X, G);                                               \
+        else if (b.motion) RT_LAUNCH_ISECT_M(G, R, N, T, X, false);                                                     \
+        else if (G && b.lens)                                                                                                \
             hipLaunchKernelGGL((k_intersect<RT_BVH_BLOCK, G, R, N, T, X, G>), dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg, \
                                ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);                                      \
         else                                                                                                            \
@@ -317,9 +353,11 @@ void launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32
 #undef RT_LAUNCH_ISECT_G
 #undef RT_LAUNCH_ISECT
 #undef RT_LAUNCH_ISECT_X
+#undef RT_LAUNCH_ISECT_M
     else {
         const size_t list_lds = (size_t)std::min<uint32_t>(std::max<uint32_t>(ctx->ds.n_spheres, 1u), RT_SPHERE_TILE) * sizeof(float4);
-        hipLaunchKernelGGL(k_intersect_list, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        if (b.motion) hipLaunchKernelGGL(k_intersect_list_motion, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        else hipLaunchKernelGGL(k_intersect_list, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
     }
 }
 
@@ -327,11 +365,16 @@ void launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32
 void launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32_t n_shards, const StepBuffers& b, const ShadeParams& sp) {
     const bool rects = scene_is_general(ctx), perlin_lds = scene_perlin_lds(ctx);
     // sphere geometry for the closest hit inside k_shade<GEN>
-    const uint32_t n_fused = (gen && fused_lists) ? ctx->ds.n_spheres : 0u;
+    const uint32_t n_fused = (gen && fused_lists) ? ctx->ds.n_spheres * (b.motion ? 2u : 1u) : 0u; // (MOTION: the displacements behind the geometry)
     const size_t shade_lds = shade_lds_bytes(ctx->ds.n_prims + ctx->ds.n_media, perlin_lds ? ctx->ds.n_perlin : 0u, n_fused, !gen && sp.sort);
+#define RT_LAUNCH_SHADE_M(P, G, R, X, L)                                                                                                       \
+    hipLaunchKernelGGL((k_shade<P, G, R, X, L, true>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, b.cout, b.rad, \
+                       sp, b.totals, b.gpd)
 #define RT_LAUNCH_SHADE(P, G, R, X)                                                                                                      \
     do {                                                                                                                                  \
-        if (G && b.lens)                                                                                                                  \
+        if (b.motion && G && b.lens) RT_LAUNCH_SHADE_M(P, G, R, X, G);                                                                    \
+        else if (b.motion) RT_LAUNCH_SHADE_M(P, G, R, X, false);                                                                          \
+        else if (G && b.lens)                                                                                                                  \
             hipLaunchKernelGGL((k_shade<P, G, R, X, G>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, b.cout, \
                                b.rad, sp, b.totals, b.gpd);                                                                               \
         else                                                                                                                              \
@@ -350,6 +393,7 @@ void launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32
     else RT_LAUNCH_SHADE_R(false, false);
 #undef RT_LAUNCH_SHADE_R
 #undef RT_LAUNCH_SHADE
+#undef RT_LAUNCH_SHADE_M
 }
 
 // Where the work buffers of a slice lie in the pool: two ray queues of n_queue rays (a / b records interleaved when RT_QSTRIDE is
@@ -689,6 +733,63 @@ void world_bounds(const RtFlatScene* s, WorldBounds& w) {
     }
 }
 
+// Where the closest-hit search of the scene in ctx->ds runs: tree in LDS or through L2, wrapper tables in LDS, a grid or none.
+// rt_scene_upload calls it for the static scene, rt_set_motion again for the scene with its moved spheres: `dc` (else NULL) = their
+// displacements, which take 16 B per sphere of LDS beside the geometry wherever the geometry is staged (k_intersect with the tree in
+// LDS, k_intersect_grid) — counted in every budget below, so a scene that no longer fits two workgroups per CU with them falls back
+// exactly as a larger scene does (tree through L2, no grid).  The grid's arrays go through upload() into the current region.
+int configure_search(RtCtx* ctx, uint32_t bvh_depth, const std::vector<float4>& geo, const std::vector<float4>* dc) {
+    const DevScene& ds = ctx->ds;
+    const uint32_t n_entries = ds.n_prims + ds.n_media;
+    const size_t extra = dc ? (size_t)ds.n_spheres * sizeof(float4) : 0u;
+    // k_intersect keeps nodes + geometry + one u16 stack column per lane in LDS when that fits 160 KB;
+    // larger trees are traversed out of HBM/L2 with only the stacks in LDS; the list walk is the last resort
+    const bool bvh_ok = ds.n_prims > 0 && ds.n_bvh4_nodes > 0 && ds.n_bvh4_nodes < 32768 && n_entries <= 32768 &&
+                        bvh_depth <= RT_BVH_MAX_DEPTH;
+    const bool force_hbm = ctx->opt[RT_OPT_TREE_PLACEMENT] == 1u; // test hook: traverse out of HBM even when LDS would fit
+    // General scenes (wrappers, rectangles, media): the tree goes to LDS only when TWO workgroups per CU still fit.  Their
+    // traversal is bound by dependent loads, and 8 waves per SIMD reading the tree through L2 beat 4 waves reading it from
+    // LDS: a final_scene-like scene of 600-1 300 primitives runs 16-19 % faster with its tree in L2 and two workgroups than
+    // with tree AND wrapper tables in LDS and one (profiles/round3/final_like.txt) — which is also why final_scene's tree was
+    // not squeezed into LDS with quantised boxes: 1 150 nodes x 48 B + 56 KB of stacks leave room for one workgroup only.
+    // Sphere-only scenes keep their faster LDS-only kernel (sorted slab planes) even at one workgroup per CU.
+    const bool general = ds.n_rects > 0 || ds.n_xforms > 0 || ds.n_media > 0 || ctx->opt[RT_OPT_GENERAL_KERNELS] == 1u;
+    ctx->general_kernels = general;
+    const size_t lds_budget = general ? ctx->lds_limit / 2 : ctx->lds_limit;
+    ctx->bvh_in_lds = bvh_ok && bvh_lds_bytes(ds, RT_BVH_BLOCK, true) + extra <= lds_budget && !force_hbm;
+    ctx->isect_lds = bvh_lds_bytes(ds, RT_BVH_BLOCK, ctx->bvh_in_lds);
+    ctx->motion_lds = ctx->bvh_in_lds ? extra : 0u; // (a tree in HBM reads the displacements there too)
+    ctx->use_bvh = bvh_ok && ctx->isect_lds + ctx->motion_lds <= ctx->lds_limit;
+    // general scenes: wrapper / medium tables behind the tree carve, when two workgroups per CU still fit
+    ctx->general_lds = false;
+    if (ctx->use_bvh && (ds.n_xforms || ds.n_media) && ctx->isect_lds + general_lds_bytes(ds) + ctx->motion_lds <= ctx->lds_limit / 2 &&
+        ctx->opt[RT_OPT_GENERAL_LDS] != 1u) {
+        ctx->isect_lds += general_lds_bytes(ds);
+        ctx->general_lds = true;
+    }
+    // Sphere-only scenes: a uniform grid over the spheres for the rays of depth >= 1 (rt_grid.h), when the scene suits one and
+    // two workgroups per CU still fit.  The tree stays: depth 0 (candidate-list overflow), the single-kernel test hook and
+    // RT_OPT_GRID = 1 use it, and the tests hold the two searches against each other bit for bit.
+    ctx->use_grid = false;
+    if (ctx->use_bvh && ctx->bvh_in_lds && !general && ctx->opt[RT_OPT_GRID] != 1u) {
+        HostGrid hg;
+        const size_t half_lds = ctx->lds_limit / 2; // (no room at all beside the displacements: budget 0, no grid)
+        build_sphere_grid(geo, half_lds > extra ? half_lds - extra : 0u, (double)ctx->opt[RT_OPT_GRID_CELL] * 1e-3, hg, dc);
+        if (hg.ok) {
+            int rc;
+            if ((rc = upload(ctx, hg.cells, &hg.gp.cells)) || (rc = upload(ctx, hg.refs, &hg.gp.refs))) return rc;
+            hg.gp.sph_geo = ds.sph_geo;
+            ctx->grid = hg.gp;
+            ctx->grid_lds = grid_lds_bytes(hg.gp.n_spheres, hg.gp.n_cells, hg.gp.n_refs);
+            ctx->use_grid = true;
+            if (dc) ctx->motion_dbg.grid = hg;
+        }
+    }
+    ctx->isect_lds += ctx->use_bvh ? ctx->motion_lds : 0u;
+    if (!ctx->use_bvh) ctx->motion_lds = 0u;
+    return RT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -769,6 +870,24 @@ int rt_ctx_create(int device_id, RtCtx** out_ctx) {
                          reinterpret_cast<const void*>(&k_shade<P, true, true, true, true>)
             RT_SHADE_LENS(true), RT_SHADE_LENS(false),
 #undef RT_SHADE_LENS
+            // the instantiations of moving spheres (rt_set_motion): every one launch_intersect / launch_shade can pick
+#define RT_ISECT_MOTION(R, N, T, X)                                                                     \
+    reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, false, R, N, T, X, false, true>),          \
+        reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, true, R, N, T, X, false, true>),       \
+        reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, true, R, N, T, X, true, true>)
+            RT_ISECT_MOTION(false, true, false, false), RT_ISECT_MOTION(true, true, false, false), RT_ISECT_MOTION(true, true, true, false),
+            RT_ISECT_MOTION(true, false, false, false), RT_ISECT_MOTION(true, false, true, false), RT_ISECT_MOTION(true, true, false, true),
+            RT_ISECT_MOTION(true, true, true, true),    RT_ISECT_MOTION(true, false, false, true), RT_ISECT_MOTION(true, false, true, true),
+#undef RT_ISECT_MOTION
+#define RT_SHADE_MOTION(P, R, X)                                                                                                           \
+    reinterpret_cast<const void*>(&k_shade<P, false, R, X, false, true>), reinterpret_cast<const void*>(&k_shade<P, true, R, X, false, true>), \
+        reinterpret_cast<const void*>(&k_shade<P, true, R, X, true, true>)
+            RT_SHADE_MOTION(true, false, false), RT_SHADE_MOTION(true, true, false), RT_SHADE_MOTION(true, true, true),
+            RT_SHADE_MOTION(false, false, false), RT_SHADE_MOTION(false, true, false), RT_SHADE_MOTION(false, true, true),
+#undef RT_SHADE_MOTION
+            reinterpret_cast<const void*>(&k_intersect_grid_motion<true>), reinterpret_cast<const void*>(&k_intersect_grid_motion<false>),
+            reinterpret_cast<const void*>(&k_debug_bounce_motion<RT_BVH_BLOCK, true, true>),
+            reinterpret_cast<const void*>(&k_debug_bounce_motion<RT_BVH_BLOCK, true, false>),
         };
         for (const void* fn : variants)
             if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_limit)) != hipSuccess)
@@ -1198,48 +1317,18 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
     if (!all_u8) ds.texels8 = nullptr; // (upload() hands out a 16 B allocation even for an empty pool)
     ctx->ds = ds;
     ctx->has_scene = true;
-    // k_intersect keeps nodes + geometry + one u16 stack column per lane in LDS when that fits 160 KB;
-    // larger trees are traversed out of HBM/L2 with only the stacks in LDS; the list walk is the last resort
-    const bool bvh_ok = ds.n_prims > 0 && ds.n_bvh4_nodes > 0 && ds.n_bvh4_nodes < 32768 && n_entries <= 32768 &&
-                        bvh.depth <= RT_BVH_MAX_DEPTH;
-    const bool force_hbm = ctx->opt[RT_OPT_TREE_PLACEMENT] == 1u; // test hook: traverse out of HBM even when LDS would fit
-    // General scenes (wrappers, rectangles, media): the tree goes to LDS only when TWO workgroups per CU still fit.  Their
-    // traversal is bound by dependent loads, and 8 waves per SIMD reading the tree through L2 beat 4 waves reading it from
-    // LDS: a final_scene-like scene of 600-1 300 primitives runs 16-19 % faster with its tree in L2 and two workgroups than
-    // with tree AND wrapper tables in LDS and one (profiles/round3/final_like.txt) — which is also why final_scene's tree was
-    // not squeezed into LDS with quantised boxes: 1 150 nodes x 48 B + 56 KB of stacks leave room for one workgroup only.
-    // Sphere-only scenes keep their faster LDS-only kernel (sorted slab planes) even at one workgroup per CU.
-    const bool general = ds.n_rects > 0 || ds.n_xforms > 0 || ds.n_media > 0 || ctx->opt[RT_OPT_GENERAL_KERNELS] == 1u;
-    ctx->general_kernels = general;
-    const size_t lds_budget = general ? ctx->lds_limit / 2 : ctx->lds_limit;
-    ctx->bvh_in_lds = bvh_ok && bvh_lds_bytes(ds, RT_BVH_BLOCK, true) <= lds_budget && !force_hbm;
-    ctx->isect_lds = bvh_lds_bytes(ds, RT_BVH_BLOCK, ctx->bvh_in_lds);
-    ctx->use_bvh = bvh_ok && ctx->isect_lds <= ctx->lds_limit;
-    // general scenes: wrapper / medium tables behind the tree carve, when two workgroups per CU still fit
-    ctx->general_lds = false;
-    if (ctx->use_bvh && (ds.n_xforms || ds.n_media) && ctx->isect_lds + general_lds_bytes(ds) <= ctx->lds_limit / 2 &&
-        ctx->opt[RT_OPT_GENERAL_LDS] != 1u) {
-        ctx->isect_lds += general_lds_bytes(ds);
-        ctx->general_lds = true;
+    {   // what rt_set_motion needs to bound moved spheres again, and the state it puts back when the motion is cleared
+        ctx->keep.geo = geo, ctx->keep.eboxes = eboxes, ctx->keep.entry_ids = entry_ids, ctx->keep.ent_bs = ent_bs;
+        ctx->keep.bare.assign(s->n_spheres, 0);
+        for (uint32_t i = 0; i < s->n_spheres; ++i) ctx->keep.bare[i] = pxf[i] == RT_NO_XFORM && pmed[i] == RT_NO_MEDIUM;
+        ctx->keep.bvh_depth = bvh.depth;
+        ctx->motion = false, ctx->motion_lds = 0, ctx->gmotion = GenMotion{}, ctx->motion_dbg = RtCtx::MotionDebug{};
     }
-    // Sphere-only scenes: a uniform grid over the spheres for the rays of depth >= 1 (rt_grid.h), when the scene suits one and
-    // two workgroups per CU still fit.  The tree stays: depth 0 (candidate-list overflow), the single-kernel test hook and
-    // RT_OPT_GRID = 1 use it, and the tests hold the two searches against each other bit for bit.
-    ctx->use_grid = false;
-    if (ctx->use_bvh && ctx->bvh_in_lds && !general && ctx->opt[RT_OPT_GRID] != 1u) {
-        HostGrid hg;
-        build_sphere_grid(geo, ctx->lds_limit / 2, (double)ctx->opt[RT_OPT_GRID_CELL] * 1e-3, hg);
-        if (hg.ok) {
-            if ((rc = upload(ctx, hg.cells, &hg.gp.cells)) || (rc = upload(ctx, hg.refs, &hg.gp.refs))) {
-                free_scene(ctx);
-                return rc;
-            }
-            hg.gp.sph_geo = ds.sph_geo;
-            ctx->grid = hg.gp;
-            ctx->grid_lds = grid_lds_bytes(hg.gp.n_spheres, hg.gp.n_cells, hg.gp.n_refs);
-            ctx->use_grid = true;
-        }
+    if ((rc = configure_search(ctx, bvh.depth, geo, nullptr))) {
+        free_scene(ctx);
+        return rc;
     }
+    ctx->static_search = RtCtx::Search{ctx->ds, ctx->use_bvh, ctx->bvh_in_lds, ctx->general_lds, ctx->use_grid, ctx->isect_lds, ctx->grid_lds, ctx->grid};
     return RT_OK;
 }
 
@@ -1331,7 +1420,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     if ((rc = ensure(ctx, ctx->counts, counts_bytes))) return rc;
     const size_t totals_bytes = (size_t)(n_depths + 2) * sizeof(unsigned long long);
     if ((rc = ensure(ctx, ctx->totals, totals_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + sizeof(GenLens)))) return rc; // (the lens behind the params: gen_lens_of)
+    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_MOTION_OFFSET + sizeof(GenMotion)))) return rc; // (the lens and the motion behind the params: gen_lens_of, gen_motion_of)
     if (want_lists &&(rc = ensure(ctx, ctx->lists, ((size_t)npix + 1u) * sizeof(uint4)))) return rc; // + the overflow counter behind the lists
     GenParams* gpd = (GenParams*)ctx->genp.p;
     float* acc = (float*)ctx->acc.p;
@@ -1483,6 +1572,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
         gp.s0 = s0;
         gp.n_rays = npix * sc;
         RT_HIP(ctx, hipMemsetAsync(counts, 0, counts_bytes, st));
+        if (ctx->motion) hipLaunchKernelGGL(k_set_motion, dim3(1), dim3(64), 0, st, gpd, ctx->gmotion);
         if (lens) hipLaunchKernelGGL(k_init_counts<true>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, gpd, glens);
         else hipLaunchKernelGGL(k_init_counts<false>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, gpd, glens);
         if (!fuse_gen && lens) hipLaunchKernelGGL(k_gen_primary<true>, dim3((gp.n_rays + 255u) / 256u), dim3(256), 0, st, gp, Q[0], glens);
@@ -1509,7 +1599,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
             const bool gen = fuse_gen && depth == 0;
             ip.depth = depth;
             ip.q0 = q0, ip.q1 = q1;
-            const StepBuffers sb{qi, qo, qhit, cin, cout, rad, totals, gpd, lens};
+            const StepBuffers sb{qi, qo, qhit, cin, cout, rad, totals, gpd, lens, ctx->motion};
             // depth 0 of a sphere-only scene whose pixels all have a candidate list: k_shade<GEN> finds every closest hit itself
             const bool no_primary_trace = gen && !rects && gp.lists != nullptr && no_overflow;
             if (!no_primary_trace) launch_intersect(ctx, sg, use_bvh, gen, isect_grid_g, sb, ip);
@@ -1827,6 +1917,196 @@ int rt_set_lens(RtCtx* ctx, const RtLens* lens) {
     return RT_OK;
 }
 
+static void restore_static_search(RtCtx* ctx) {
+    const RtCtx::Search& st = ctx->static_search;
+    ctx->ds = st.ds, ctx->use_bvh = st.use_bvh, ctx->bvh_in_lds = st.bvh_in_lds, ctx->general_lds = st.general_lds, ctx->use_grid = st.use_grid;
+    ctx->isect_lds = st.isect_lds, ctx->grid_lds = st.grid_lds, ctx->grid = st.grid;
+    ctx->motion = false, ctx->motion_lds = 0, ctx->gmotion = GenMotion{}, ctx->motion_dbg = RtCtx::MotionDebug{};
+}
+
+// Moving spheres.  Everything that bounds a listed sphere is built again over the region it sweeps; the static arrays stay where they
+// are (clearing the motion only switches back to them).  The kernels form c(tm) = fl(c0 + fl(tm dc)), dc = fl(c1 - c0), tm in [0, 1]:
+// the exact point c0 + tm dc lies on the segment from c0 to e1 = c0 + dc (e1 in double: it need not be the caller's c1 to the last
+// bit), and the two roundings move a coordinate by at most half an ulp of |dc| and half an ulp of the larger of |c0|, |e1| — together
+// below `slack` = 2^-22 of the coordinate magnitude (2 ulp).  The bounds take the union of the two end positions (exact for linear
+// motion) and add that slack for the moved spheres, so none of the existing pads (2^-18 of the magnitude around a tree leaf, which
+// is there for the slab arithmetic; the list cone's 0.1 % + 2^-21 of the magnitude) is asked to cover it:
+//   tree leaf  = [min(c0, e1) - r - slack, max(c0, e1) + r + slack], then pad_prim_box as for every leaf;
+//   ent_bs     = centre (c0 + e1) / 2, radius r + |e1 - c0| / 2 + the distance the rounded centre moved + sqrt(3) slack, rounded up;
+//   grid       = build_sphere_grid's swept boxes (its own argument for the roundings, rt_grid.h).
+int rt_set_motion(RtCtx* ctx, const RtMotion* motion) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!ctx->has_scene) return fail(ctx, RT_ERR_STATE, "rt_set_motion: no scene uploaded");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!motion || motion->n_moving == 0) {
+        if (motion && (!std::isfinite(motion->shutter_open) || !std::isfinite(motion->shutter_close) || motion->shutter_open < 0.0f ||
+                       motion->shutter_close > 1.0f || motion->shutter_open > motion->shutter_close))
+            return fail(ctx, RT_ERR_INVALID, "rt_set_motion: the shutter must satisfy 0 <= shutter_open <= shutter_close <= 1");
+        if (ctx->motion) {
+            RT_HIP(ctx, hipDeviceSynchronize());
+            restore_static_search(ctx);
+        }
+        return RT_OK;
+    }
+    const uint32_t n_sph = ctx->static_search.ds.n_spheres, nm = motion->n_moving;
+    if (!motion->sphere || !motion->center1) return fail(ctx, RT_ERR_INVALID, "rt_set_motion: NULL array");
+    if (!std::isfinite(motion->shutter_open) || !std::isfinite(motion->shutter_close) || motion->shutter_open < 0.0f ||
+        motion->shutter_close > 1.0f || motion->shutter_open > motion->shutter_close)
+        return fail(ctx, RT_ERR_INVALID, "rt_set_motion: the shutter must satisfy 0 <= shutter_open <= shutter_close <= 1");
+    const RtCtx::Keep& kp = ctx->keep;
+    for (uint32_t k = 0; k < nm; ++k) {
+        const uint32_t i = motion->sphere[k];
+        if (i >= n_sph) return fail(ctx, RT_ERR_INVALID, "rt_set_motion: sphere index " + std::to_string(i) + " out of range");
+        if (k > 0 && i <= motion->sphere[k - 1]) return fail(ctx, RT_ERR_INVALID, "rt_set_motion: sphere indices must be strictly increasing");
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(motion->center1[3 * (size_t)k + c])) return fail(ctx, RT_ERR_INVALID, "rt_set_motion: non-finite center1 of sphere " + std::to_string(i));
+        if (!kp.bare[i])
+            return fail(ctx, RT_ERR_UNSUPPORTED, "rt_set_motion: sphere " + std::to_string(i) + " lies below a Translate / RotateY wrapper or bounds a medium: only bare spheres move");
+    }
+    // ---- displacements and swept bounds (host)
+    std::vector<float4> dc(std::max<uint32_t>(n_sph, 1u), make_float4(0.f, 0.f, 0.f, 0.f));
+    std::vector<PrimBox> eboxes = kp.eboxes;
+    std::vector<float4> ent_bs = kp.ent_bs;
+    std::vector<uint32_t> entry_of(n_sph, 0xFFFFFFFFu);
+    for (size_t e = 0; e < kp.entry_ids.size(); ++e)
+        if (kp.entry_ids[e] < n_sph) entry_of[kp.entry_ids[e]] = (uint32_t)e;
+    for (uint32_t k = 0; k < nm; ++k) {
+        const uint32_t i = motion->sphere[k];
+        const float4 g = kp.geo[i];
+        const float c0[3] = {g.x, g.y, g.z};
+        float d[3];
+        for (int c = 0; c < 3; ++c) d[c] = motion->center1[3 * (size_t)k + c] - c0[c]; // fl(c1 - c0), once
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(d[c])) return fail(ctx, RT_ERR_INVALID, "rt_set_motion: the displacement of sphere " + std::to_string(i) + " overflows");
+        dc[i] = make_float4(d[0], d[1], d[2], 1.0f);
+        const uint32_t e = entry_of[i]; // (a bare sphere is a world entry)
+        const double r = std::fabs((double)g.w);
+        double mid[3], half2 = 0.0, slack_max = 0.0;
+        for (int c = 0; c < 3; ++c) {
+            const double a = c0[c], b = (double)c0[c] + (double)d[c];
+            const double slack = std::ldexp(std::max(std::fabs(a), std::fabs(b)), -22) + 1e-37;
+            slack_max = std::max(slack_max, slack);
+            eboxes[e].mn[c] = round_down(std::min(a, b) - r - slack);
+            eboxes[e].mx[c] = round_up(std::max(a, b) + r + slack);
+            mid[c] = 0.5 * (a + b);
+            half2 += 0.25 * (b - a) * (b - a);
+        }
+        float4 bs = make_float4((float)mid[0], (float)mid[1], (float)mid[2], 0.0f);
+        const double mx = mid[0] - bs.x, my = mid[1] - bs.y, mz = mid[2] - bs.z;
+        bs.w = round_up((r + std::sqrt(half2) + std::sqrt(mx * mx + my * my + mz * mz) + 1.7321 * slack_max) * (1.0 + 1e-12));
+        ent_bs[e] = bs;
+    }
+    HostBvh bvh;
+    build_prim_bvh(eboxes, RT_BVH_MAX_DEPTH, bvh);
+    for (auto& dd : bvh.d) { // leaf ids: index into eboxes -> world entry id
+        if (dd.x < 0 && dd.x != INT_MIN) dd.x = ~(int)kp.entry_ids[(size_t)~dd.x];
+        if (dd.y < 0 && dd.y != INT_MIN) dd.y = ~(int)kp.entry_ids[(size_t)~dd.y];
+    }
+    HostBvh4 bvh4;
+    collapse_bvh4(bvh, bvh4);
+    // ---- device: nothing may still read the motion arrays of the call before
+    RT_HIP(ctx, hipDeviceSynchronize());
+    restore_static_search(ctx);
+    DevScene ds = ctx->static_search.ds;
+    ds.n_bvh4_nodes = (uint32_t)bvh4.id.size();
+    ds.bvh4_depth = bvh4.depth;
+    {
+        double ext2 = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            float lo = FLT_MAX, hi = -FLT_MAX;
+            for (const PrimBox& b : eboxes) lo = std::min(lo, b.mn[k]), hi = std::max(hi, b.mx[k]);
+            if (hi > lo) ext2 += ((double)hi - lo) * ((double)hi - lo);
+        }
+        ds.bvh_exact_eps = (float)(std::sqrt(ext2) / 1024.0);
+    }
+    const float4* d_dc = nullptr;
+    auto upload_all = [&]() -> int {
+        int rc;
+        if ((rc = upload(ctx, dc, &d_dc)) || (rc = upload(ctx, ent_bs, &ds.ent_bs)) || (rc = upload(ctx, bvh4.id, &ds.bvh4_id)) ||
+            (rc = upload(ctx, bvh4.p[0], &ds.bvh4_p[0])) || (rc = upload(ctx, bvh4.p[1], &ds.bvh4_p[1])) ||
+            (rc = upload(ctx, bvh4.p[2], &ds.bvh4_p[2])) || (rc = upload(ctx, bvh4.p[3], &ds.bvh4_p[3])) ||
+            (rc = upload(ctx, bvh4.p[4], &ds.bvh4_p[4])) || (rc = upload(ctx, bvh4.p[5], &ds.bvh4_p[5]))) return rc;
+        return RT_OK;
+    };
+    // upload() carves the scene region: for this call the motion region stands in for it (measured first, + room for the grid's arrays)
+    const DevBuf scene_region = ctx->scene_region;
+    const size_t scene_used = ctx->scene_used;
+    ctx->scene_measuring = true, ctx->scene_measure = 0;
+    (void)upload_all();
+    ctx->scene_measuring = false;
+    int rc = ensure(ctx, ctx->motion_region, ctx->scene_measure + (1u << 20));
+    if (!rc) {
+        ctx->scene_region = ctx->motion_region, ctx->scene_used = 0;
+        rc = upload_all();
+        if (!rc) {
+            ctx->ds = ds;
+            ctx->motion_dbg.sphere.assign(motion->sphere, motion->sphere + nm);
+            rc = configure_search(ctx, bvh.depth, kp.geo, &dc);
+        }
+        ctx->scene_region = scene_region, ctx->scene_used = scene_used;
+    }
+    if (rc) { // (a device error: the static renderer)
+        const std::string err = ctx->err;
+        restore_static_search(ctx);
+        ctx->err = err;
+        return rc;
+    }
+    ctx->motion_dbg.eboxes = eboxes, ctx->motion_dbg.ent_bs = ent_bs;
+    ctx->gmotion = GenMotion{d_dc, motion->shutter_open, motion->shutter_close - motion->shutter_open};
+    ctx->motion = true;
+    return RT_OK;
+}
+
+int rt_debug_motion_bounds(const RtCtx* ctx, float* entry_box_padded, float* entry_sphere, uint32_t* entry_ids, uint32_t entry_cap, uint32_t* n_entries,
+                           float grid[6], uint32_t dims[3], uint32_t* cell_begin, uint32_t* cell_ids, uint32_t cell_cap, uint32_t* n_cell_ids) {
+    if (!ctx || !n_entries || !n_cell_ids || !grid || !dims) return RT_ERR_INVALID;
+    if (!ctx->has_scene || !ctx->motion) return RT_ERR_STATE;
+    const RtCtx::MotionDebug& md = ctx->motion_dbg;
+    *n_entries = (uint32_t)md.eboxes.size();
+    *n_cell_ids = 0;
+    for (int k = 0; k < 3; ++k) dims[k] = 0u, grid[k] = grid[3 + k] = 0.0f;
+    const bool fits = entry_cap >= *n_entries && entry_box_padded && entry_sphere && entry_ids;
+    if (fits)
+        for (uint32_t e = 0; e < *n_entries; ++e) {
+            const PrimBox pb = pad_prim_box(md.eboxes[e]);
+            for (int k = 0; k < 3; ++k) entry_box_padded[6 * (size_t)e + k] = pb.mn[k], entry_box_padded[6 * (size_t)e + 3 + k] = pb.mx[k];
+            const float4 b = md.ent_bs[e];
+            entry_sphere[4 * (size_t)e] = b.x, entry_sphere[4 * (size_t)e + 1] = b.y, entry_sphere[4 * (size_t)e + 2] = b.z, entry_sphere[4 * (size_t)e + 3] = b.w;
+            entry_ids[e] = ctx->keep.entry_ids[e];
+        }
+    bool cells_fit = true;
+    if (ctx->use_grid && md.grid.ok) {
+        const GridParams& g = md.grid.gp;
+        dims[0] = g.nx, dims[1] = g.ny, dims[2] = g.nz;
+        for (int k = 0; k < 3; ++k) grid[k] = g.g0[k], grid[3 + k] = g.cs[k];
+        uint32_t n = 0;
+        for (size_t k = 0; k < md.sphere.size(); ++k) {
+            if (cell_begin) cell_begin[k] = n;
+            const uint32_t sph = md.sphere[k];
+            bool always = false;
+            for (uint32_t a = 0; a < g.n_always; ++a) always = always || g.always[a] == sph;
+            if (always) { // tested for every ray: one entry 0xFFFFFFFF
+                if (cell_ids && n < cell_cap) cell_ids[n] = 0xFFFFFFFFu;
+                ++n;
+                continue;
+            }
+            for (uint32_t c = 0; c < g.n_cells; ++c) {
+                const uint32_t rec = md.grid.cells[c];
+                for (uint32_t t = 0; t < (rec & RT_GRID_CNT_MASK); ++t)
+                    if (md.grid.refs[(rec >> RT_GRID_CNT_BITS) + t] == sph) {
+                        if (cell_ids && n < cell_cap) cell_ids[n] = c;
+                        ++n;
+                        break;
+                    }
+            }
+        }
+        if (cell_begin) cell_begin[md.sphere.size()] = n;
+        *n_cell_ids = n;
+        cells_fit = cell_begin && cell_ids && n <= cell_cap;
+    }
+    return fits && cells_fit ? RT_OK : RT_ERR_INVALID;
+}
+
 int rt_get_depth_timings(RtCtx* ctx, uint32_t max_n, float* isect_ms, float* shade_ms, uint64_t* rays) {
     if (!ctx) return RT_ERR_INVALID;
     RT_HIP(ctx, hipSetDevice(ctx->device));
@@ -1853,7 +2133,7 @@ static int debug_bounce_production(RtCtx* ctx, const RtBounceIO* io) {
     int rc;
     if ((rc = ensure(ctx, ctx->counts, (size_t)2 * nq * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(ctx, ctx->totals, 4 * sizeof(unsigned long long)))) return rc;
-    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams)))) return rc;
+    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_MOTION_OFFSET + sizeof(GenMotion)))) return rc;
     if ((rc = ensure(ctx, ctx->dbg, (size_t)n * 6 * sizeof(float)))) return rc;
     const WorkLayout wl = work_layout((size_t)nq * cap, n);
     const size_t wbase = work_base(ctx);
@@ -1877,10 +2157,11 @@ static int debug_bounce_production(RtCtx* ctx, const RtBounceIO* io) {
     gp.inv_npix = gp.inv_nx = (float)((1.0 / (double)n) * (1.0 - 1.0 / 4194304.0));
     gp.inv_band = (float)(1.0 - 1.0 / 4194304.0);
     hipLaunchKernelGGL(k_init_counts<false>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, (GenParams*)ctx->genp.p, GenLens{});
+    if (ctx->motion) hipLaunchKernelGGL(k_set_motion, dim3(1), dim3(64), 0, st, (GenParams*)ctx->genp.p, ctx->gmotion); // (the time of slot i: its slot key)
     hipLaunchKernelGGL(k_debug_fill, dim3((n + 255u) / 256u), dim3(256), 0, st, gp, Q[0], d_o, d_d);
     const bool use_bvh = ctx->use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
     const StepBuffers sb{Q[0], Q[1], wv.qhit, counts, counts + nq, wv.rad,
-                         (unsigned long long*)ctx->totals.p, (const GenParams*)ctx->genp.p};
+                         (unsigned long long*)ctx->totals.p, (const GenParams*)ctx->genp.p, false, ctx->motion};
     const IntersectParams ip{nq, cap, (int)io->depth, 0u, nq};
     launch_intersect(ctx, st, use_bvh, false, qg.isect_grid, sb, ip);
     const ShadeParams sp{nq, cap, (int)io->depth, 0x7FFFFFFF, 1u, 0u, 0u};
@@ -1958,23 +2239,27 @@ int rt_debug_bounce(RtCtx* ctx, const RtBounceIO* io) {
     RT_HIP(ctx, hipMemcpyAsync(base + off_d, io->in_d, 3 * n * 4, hipMemcpyHostToDevice, st));
     RT_HIP(ctx, hipMemcpyAsync(base + off_key, io->in_key, 2 * n * 4, hipMemcpyHostToDevice, st));
     const bool use_bvh = ctx->use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
+#define RT_DEBUG_BOUNCE(B, U, L, LDS)                                                                                                      \
+    do {                                                                                                                                   \
+        if (ctx->motion)                                                                                                                   \
+            hipLaunchKernelGGL((k_debug_bounce_motion<B, U, L>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n, \
+                               (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
+                               base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive),   \
+                               ctx->gmotion);                                                                                              \
+        else                                                                                                                               \
+            hipLaunchKernelGGL((k_debug_bounce<B, U, L>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n,       \
+                               (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
+                               base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive));  \
+    } while (0)
     if (use_bvh && !ctx->bvh_in_lds) {
-        hipLaunchKernelGGL((k_debug_bounce<RT_BVH_BLOCK, true, false>), dim3((unsigned)((n + RT_BVH_BLOCK - 1) / RT_BVH_BLOCK)),
-                           dim3(RT_BVH_BLOCK), ctx->isect_lds, st, ctx->ds, (uint32_t)n, (int)io->depth, base + off_o, base + off_d,
-                           (const uint32_t*)(base + off_key), (int*)(base + off_hit), base + off_t, base + off_rad, base + off_att,
-                           base + off_so, base + off_sd, (uint8_t*)(base + off_alive));
+        RT_DEBUG_BOUNCE(RT_BVH_BLOCK, true, false, ctx->isect_lds);
     } else if (use_bvh) {
-        hipLaunchKernelGGL((k_debug_bounce<RT_BVH_BLOCK, true, true>), dim3((unsigned)((n + RT_BVH_BLOCK - 1) / RT_BVH_BLOCK)),
-                           dim3(RT_BVH_BLOCK), ctx->isect_lds, st, ctx->ds, (uint32_t)n, (int)io->depth, base + off_o, base + off_d,
-                           (const uint32_t*)(base + off_key), (int*)(base + off_hit), base + off_t, base + off_rad, base + off_att,
-                           base + off_so, base + off_sd, (uint8_t*)(base + off_alive));
+        RT_DEBUG_BOUNCE(RT_BVH_BLOCK, true, true, ctx->isect_lds);
     } else {
         const size_t lds_bytes = (size_t)std::min<uint32_t>(std::max<uint32_t>(ctx->ds.n_spheres, 1u), RT_SPHERE_TILE) * sizeof(float4);
-        hipLaunchKernelGGL((k_debug_bounce<256, false, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds_bytes, st, ctx->ds,
-                           (uint32_t)n, (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key),
-                           (int*)(base + off_hit), base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd,
-                           (uint8_t*)(base + off_alive));
+        RT_DEBUG_BOUNCE(256, false, true, lds_bytes);
     }
+#undef RT_DEBUG_BOUNCE
     RT_HIP(ctx, hipGetLastError());
     RT_HIP(ctx, hipMemcpyAsync(io->out_hit, base + off_hit, n * 4, hipMemcpyDeviceToHost, st));
     RT_HIP(ctx, hipMemcpyAsync(io->out_t, base + off_t, n * 4, hipMemcpyDeviceToHost, st));

@@ -545,6 +545,19 @@ __device__ __forceinline__ V3 world_to_local_with_rot(V3 norm, V3 tang0, V3 v, f
     return v3(dot(v, tang), dot(v, bitang), dot(v, norm));
 }
 
+// Motion blur (rt_set_motion): a sphere whose centre moves linearly while the shutter is open.  `dc` = (c1 - c0, listed ? 1 : 0), one per
+// sphere beside the geometry (zero for a sphere the motion table does not list); c(tm) = fl(c0 + fl(tm * dc)) per component, two
+// roundings (-ffp-contract=off), then Sphere::hit on (c(tm), r) unchanged: a moving sphere at time tm is bit for bit a static one at
+// c(tm).  An unlisted sphere keeps its centre untouched (also a -0.0 component, which c0 + 0 would turn into +0.0).
+__device__ __forceinline__ float4 sphere_at(float4 g, float4 dc, float tm) {
+    if (dc.w != 0.0f) {
+        g.x = g.x + tm * dc.x;
+        g.y = g.y + tm * dc.y;
+        g.z = g.z + tm * dc.z;
+    }
+    return g;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Closest hit against one sphere (hitable.rs:75-91).  Returns the accepted root in `t_hit`.
 // The caller keeps (t, index) only; the HitRecord fields (hitable.rs:93-99) are derived
@@ -694,9 +707,11 @@ struct Bounce {
 struct NoPrefetch {
     __device__ __forceinline__ void operator()() const {}
 };
-template <bool RECTS, class AfterLoads = NoPrefetch, bool NEST = false>
+// MOTION: the hit sphere's centre is c(tm) (sphere_at; `sph_dc` = the per-sphere displacements, `tm` = the path's time).
+template <bool RECTS, class AfterLoads = NoPrefetch, bool NEST = false, bool MOTION = false>
 __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro, V3 rd, int hit, float t, Rng& rng,
-                               uint32_t& n_fetch, AfterLoads after_record_loads = AfterLoads()) {
+                               uint32_t& n_fetch, AfterLoads after_record_loads = AfterLoads(), const float4* sph_dc = nullptr,
+                               float tm = 0.0f) {
     Bounce out;
     out.radiance = splat(0.0f);
     out.attenuation = splat(1.0f);
@@ -705,8 +720,12 @@ __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro
     out.alive = false;
     // (the record of entry 0 for a miss: every lane of the wave issues the same loads before the prefetch)
     const float4* rec = sc.sph_rec + 5u * (uint32_t)(hit < 0 ? 0 : hit);
-    const float4 g = rec[0], r1 = rec[1], r2 = rec[2];
+    float4 g = rec[0];
+    const float4 r1 = rec[1], r2 = rec[2];
+    float4 dcv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (MOTION && hit >= 0 && (uint32_t)hit < sc.n_spheres) dcv = sph_dc[hit];
     after_record_loads();
+    if (MOTION) g = sphere_at(g, dcv, tm);
     if (hit < 0) {
         out.radiance = sky_value(sc, rd, n_fetch); // main.rs:58
         return out;

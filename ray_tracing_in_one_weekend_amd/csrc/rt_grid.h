@@ -90,10 +90,18 @@ struct HostGrid {
 // many spheres, more than RT_GRID_MAX_ALWAYS large ones at every cell size tried, a grid that does not fit `lds_budget`
 // next to the sphere list, or one whose cells are so small against the coordinates that the fp32 walk could not be
 // trusted (pad below 2^-20 of the largest coordinate).  cell_factor: cell edge in median sphere diameters, 0 = the default.
-inline void build_sphere_grid(const std::vector<float4>& sph, size_t lds_budget, double cell_factor, HostGrid& out) {
+// `dc` (rt_set_motion; NULL: no motion): per sphere (c1 - c0, listed).  A listed sphere is bounded by its SWEPT box — the union of its
+// boxes at tm = 0 and tm = 1, exact for linear motion — in the "large" rule (a fast mover is tested for every ray exactly as a big sphere
+// is), in the grid's extent and in the cells that list it (every cell the swept box + pad reaches; no corner pruning).  The kernel's
+// c(tm) = fl(c0 + fl(tm dc)) lies within 2 ulp of a coordinate off that segment: `pad * 2^20 >= 2 maxabs` below makes one ulp at most
+// pad / 16, so the two roundings take pad / 8 of the pad, next to the pad / 8 the walk itself uses (header: 2^-10 cells against 2^-7).
+inline void build_sphere_grid(const std::vector<float4>& sph, size_t lds_budget, double cell_factor, HostGrid& out,
+                              const std::vector<float4>* dc = nullptr) {
     out = HostGrid{};
     const uint32_t n = (uint32_t)sph.size();
     if (n < 16u || n > RT_GRID_MAX_SPHERES) return;
+    auto moves = [&](uint32_t i) { return dc && (*dc)[i].w != 0.0f; };
+    auto disp = [&](uint32_t i, int k) { return !moves(i) ? 0.0 : (double)(k == 0 ? (*dc)[i].x : (k == 1 ? (*dc)[i].y : (*dc)[i].z)); };
     std::vector<double> diam(n);
     for (uint32_t i = 0; i < n; ++i) diam[i] = 2.0 * std::fabs((double)sph[i].w);
     std::vector<double> sorted(diam);
@@ -105,14 +113,21 @@ inline void build_sphere_grid(const std::vector<float4>& sph, size_t lds_budget,
         const double pad = cs_d / 128.0; // (the cells come out between 2/3 and 4/3 of cs_d; the bound below uses the real ones)
         std::vector<uint32_t> always, small;
         for (uint32_t i = 0; i < n; ++i) {
-            const double k = std::floor((diam[i] + 2.0 * pad) / cs_d) + 2.0;
-            (k * k * k > RT_GRID_BIG_CELLS ? always : small).push_back(i);
+            double cells = 1.0;
+            if (!moves(i)) {
+                const double k = std::floor((diam[i] + 2.0 * pad) / cs_d) + 2.0;
+                cells = k * k * k;
+            } else {
+                for (int k = 0; k < 3; ++k) cells *= std::floor((diam[i] + std::fabs(disp(i, k)) + 2.0 * pad) / cs_d) + 2.0;
+            }
+            (cells > RT_GRID_BIG_CELLS ? always : small).push_back(i);
         }
         if (always.size() > RT_GRID_MAX_ALWAYS || small.size() < 8u) continue;
         double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, maxabs = 0.0;
         for (uint32_t i : small) {
             const double c[3] = {sph[i].x, sph[i].y, sph[i].z}, r = 0.5 * diam[i];
-            for (int k = 0; k < 3; ++k) lo[k] = std::min(lo[k], c[k] - r - 2.0 * pad), hi[k] = std::max(hi[k], c[k] + r + 2.0 * pad);
+            for (int k = 0; k < 3; ++k)
+                lo[k] = std::min(lo[k], c[k] + std::min(disp(i, k), 0.0) - r - 2.0 * pad), hi[k] = std::max(hi[k], c[k] + std::max(disp(i, k), 0.0) + r + 2.0 * pad);
         }
         GridParams g{};
         uint64_t total = 1;
@@ -145,11 +160,13 @@ inline void build_sphere_grid(const std::vector<float4>& sph, size_t lds_budget,
         // cell lists: count, prefix, fill (cells in x-fastest order; spheres in index order within a cell)
         auto cell_range = [&](uint32_t i, int k, uint32_t& a, uint32_t& b) {
             const double c = k == 0 ? sph[i].x : (k == 1 ? sph[i].y : sph[i].z), r = 0.5 * diam[i] + pad;
-            const double fa = std::floor((c - r - (double)g.g0[k]) / (double)g.cs[k]), fb = std::floor((c + r - (double)g.g0[k]) / (double)g.cs[k]);
+            const double fa = std::floor((c + std::min(disp(i, k), 0.0) - r - (double)g.g0[k]) / (double)g.cs[k]),
+                         fb = std::floor((c + std::max(disp(i, k), 0.0) + r - (double)g.g0[k]) / (double)g.cs[k]);
             a = (uint32_t)std::min<double>(std::max(fa, 0.0), dims[k] - 1.0);
             b = (uint32_t)std::min<double>(std::max(fb, 0.0), dims[k] - 1.0);
         };
         auto reaches = [&](uint32_t i, uint32_t x, uint32_t y, uint32_t z) { // sphere grown by pad against the cell box
+            if (moves(i)) return true; // (a mover: every cell of its swept box)
             const double c[3] = {sph[i].x, sph[i].y, sph[i].z}, r = 0.5 * diam[i] + pad;
             const uint32_t q[3] = {x, y, z};
             double d2 = 0.0;
@@ -240,10 +257,14 @@ __device__ __forceinline__ float min_raw(float a, float b) {
     asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-template <bool ONE_LAYER>
-__global__ __launch_bounds__(RT_BVH_BLOCK, 8) void k_intersect_grid(GridParams G, const float4* __restrict__ qa,
-                                                                      const float4* __restrict__ qb, float2* __restrict__ qh,
-                                                                      const uint32_t* __restrict__ in_counts, IntersectParams ip) {
+// MOTION (k_intersect_grid_motion): the spheres' displacements are staged behind the static carve (16 B per sphere more; the host
+// builds the grid with that much less budget, so two workgroups per CU still fit — a scene whose grid no longer does gets none and
+// its secondary rays walk the tree).  The ray's time is recomputed from its slot once, when the lane takes the ray.
+template <bool ONE_LAYER, bool MOTION>
+__device__ __forceinline__ void intersect_grid_body(const GridParams& G, const float4* __restrict__ qa,
+                                                    const float4* __restrict__ qb, float2* __restrict__ qh,
+                                                    const uint32_t* __restrict__ in_counts, const IntersectParams& ip,
+                                                    const GenParams* __restrict__ gpd) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr uint32_t BLOCK = RT_BVH_BLOCK;
     uint32_t pre[RT_ISECT_MAX_SHARDS + 1];
@@ -263,6 +284,10 @@ __global__ __launch_bounds__(RT_BVH_BLOCK, 8) void k_intersect_grid(GridParams G
     unsigned short* s_refs = reinterpret_cast<unsigned short*>(s_cells + G.n_cells);
     uint32_t* s_work = reinterpret_cast<uint32_t*>(smem + grid_lds_bytes(G.n_spheres, G.n_cells, G.n_refs) - 16u);
     for (uint32_t i = threadIdx.x; i < G.n_spheres; i += BLOCK) s_geo[i] = G.sph_geo[i];
+    float4* s_dc = reinterpret_cast<float4*>(smem + grid_lds_bytes(G.n_spheres, G.n_cells, G.n_refs));
+    if (MOTION)
+        for (uint32_t i = threadIdx.x; i < G.n_spheres; i += BLOCK) s_dc[i] = gen_motion_of(gpd).sph_dc[i];
+    float tm = 0.0f; // MOTION: this lane's ray's time
     for (uint32_t i = threadIdx.x; i < G.n_cells; i += BLOCK) s_cells[i] = G.cells[i];
     {
         const uint32_t* src = reinterpret_cast<const uint32_t*>(G.refs);
@@ -286,7 +311,7 @@ __global__ __launch_bounds__(RT_BVH_BLOCK, 8) void k_intersect_grid(GridParams G
     size_t pos = 0;
     auto test_sphere = [&](uint32_t s) {
         float th;
-        if (sphere_root(s_geo[s], o, d, rcp_a, 1e-3f, RT_FLT_MAX, th) && (th < tbest || (th == tbest && (int)s > hit))) {
+        if (sphere_root(MOTION ? sphere_at(s_geo[s], s_dc[s], tm) : s_geo[s], o, d, rcp_a, 1e-3f, RT_FLT_MAX, th) && (th < tbest || (th == tbest && (int)s > hit))) {
             tbest = th;
             hit = (int)s;
         }
@@ -349,6 +374,11 @@ __global__ __launch_bounds__(RT_BVH_BLOCK, 8) void k_intersect_grid(GridParams G
                 o = v3(ra.x, ra.y, ra.z);
                 d = v3(rb.x, rb.y, rb.z);
                 rcp_a = shared_rcp(length_squared(d));
+                if (MOTION) {
+                    uint32_t k0, k1;
+                    path_key_of_slot(*gpd, __float_as_uint(ra.w), k0, k1);
+                    tm = path_time(gen_motion_of(gpd), k0, k1);
+                }
                 tbest = RT_FLT_MAX;
                 hit = -1;
                 has = true;
@@ -432,6 +462,19 @@ __global__ __launch_bounds__(RT_BVH_BLOCK, 8) void k_intersect_grid(GridParams G
             test_sphere(s);
         }
     }
+}
+template <bool ONE_LAYER>
+__global__ __launch_bounds__(RT_BVH_BLOCK, 8) void k_intersect_grid(GridParams G, const float4* __restrict__ qa,
+                                                                      const float4* __restrict__ qb, float2* __restrict__ qh,
+                                                                      const uint32_t* __restrict__ in_counts, IntersectParams ip) {
+    intersect_grid_body<ONE_LAYER, false>(G, qa, qb, qh, in_counts, ip, nullptr);
+}
+template <bool ONE_LAYER>
+__global__ __launch_bounds__(RT_BVH_BLOCK, 8) void k_intersect_grid_motion(GridParams G, const float4* __restrict__ qa,
+                                                                             const float4* __restrict__ qb, float2* __restrict__ qh,
+                                                                             const uint32_t* __restrict__ in_counts, IntersectParams ip,
+                                                                             const GenParams* __restrict__ gpd) {
+    intersect_grid_body<ONE_LAYER, true>(G, qa, qb, qh, in_counts, ip, gpd);
 }
 
 } // namespace rt

@@ -87,6 +87,24 @@ struct GenLens {
     float sin_tilt; // >= grow / (focus_dist * h), h = distance from origin to the image plane
 };
 __device__ __forceinline__ const GenLens& gen_lens_of(const GenParams* gpd) { return *reinterpret_cast<const GenLens*>(gpd + 1); }
+// Motion blur of a frame (rt_set_motion), read by the MOTION instantiations only; it lies behind the lens (k_set_motion puts it there), so
+// the static kernels keep their arguments, code and registers.  The time of a path is DERIVED, not stored: tm = open + u * span with u
+// the draw of counter 254 of the path's key (unused by every other draw of depth 0, DESIGN.md "RNG"), one time for all its segments.
+// Past depth 0 the key comes from the slot in the ray record (path_key_of_slot), so the 40 B record does not grow.
+struct GenMotion {
+    const float4* sph_dc; // [n_spheres] (c1 - c0, listed ? 1 : 0): sphere_at (rt_device.h)
+    float open, span;     // shutter_open, fl(shutter_close - shutter_open)
+};
+#define RT_MOTION_OFFSET 40u // behind the 36 B of GenLens, 8-aligned
+static_assert(sizeof(GenLens) <= RT_MOTION_OFFSET && sizeof(GenParams) % 8u == 0u, "GenMotion behind GenLens");
+__device__ __forceinline__ const GenMotion& gen_motion_of(const GenParams* gpd) {
+    return *reinterpret_cast<const GenMotion*>(reinterpret_cast<const char*>(gpd + 1) + RT_MOTION_OFFSET);
+}
+#define RT_TIME_COUNTER 254u
+__device__ __forceinline__ float path_time(const GenMotion& gm, uint32_t k0, uint32_t k1) {
+    Rng rng(k0, k1, RT_TIME_COUNTER);
+    return gm.open + rng.next() * gm.span;
+}
 
 // x / d for the slot arithmetic of gen_primary / path_key_of_slot (quotients below 2^21): a float product that never exceeds the true quotient
 // (inv = (1/d)(1 - 2^-22) absorbs the roundings of the conversion and of the product) and two correction steps.
@@ -211,6 +229,11 @@ __global__ __launch_bounds__(256) void k_init_counts(GenParams gp, uint32_t* __r
     uint32_t cnt = nc * 256u;
     if (nc && ((nchunks - 1u) % gp.nq) == sq) cnt -= nchunks * 256u - gp.n_rays;
     counts[sq] = cnt;
+}
+
+// Parks the frame's motion behind the GenParams and the lens (gen_motion_of); launched in front of the depth-0 kernels when motion is set.
+__global__ void k_set_motion(GenParams* __restrict__ gp_dev, GenMotion gm) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<GenMotion*>(reinterpret_cast<char*>(gp_dev + 1) + RT_MOTION_OFFSET) = gm;
 }
 
 // Materialises the primary rays in the queue.  Only the list-walk fallback uses it: on the BVH
@@ -376,11 +399,12 @@ __global__ __launch_bounds__(256) void k_primary_lists(DevScene sc, GenParams gp
 
 // Closest hit over a tile of the list, HitableList::hit order and acceptance rule
 // (hitable.rs:117-132: t_max shrinks to the closest so far; a root equal to t_max is accepted).
+template <bool MOTION = false>
 __device__ __forceinline__ void closest_hit_tile(const float4* s_geo, uint32_t n, uint32_t base, V3 o, V3 d, float a,
-                                                 float& tbest, int& hit) {
+                                                 float& tbest, int& hit, const float4* dc = nullptr, float tm = 0.0f) {
     for (uint32_t s = 0; s < n; ++s) {
         float th;
-        if (sphere_root(s_geo[s], o, d, a, 1e-3f, tbest, th)) {
+        if (sphere_root(MOTION ? sphere_at(s_geo[s], dc[base + s], tm) : s_geo[s], o, d, a, 1e-3f, tbest, th)) {
             tbest = th;
             hit = (int)(base + s);
         }
@@ -399,12 +423,12 @@ __device__ __forceinline__ uint32_t medium_counter(uint32_t base, uint32_t m) {
 }
 // Candidate root of one geometric primitive through its wrapper chain (general scenes), geometry from `geo`
 // (spheres, then 2 float4 per rectangle; LDS in k_intersect, HBM in the list walk).
-template <bool NEST, class Tables>
+template <bool NEST, bool MOTION = false, class Tables>
 __device__ __forceinline__ bool prim_root(const Tables& sc, const float4* geo, uint32_t s, V3 o, V3 d, float t_min,
-                                          float t_max, float& th) {
+                                          float t_max, float& th, const float4* dc = nullptr, float tm = 0.0f) {
     const uint32_t xf = sc.prim_xform[s];
     if (xf != RT_NO_XFORM_DEV) ray_to_object<NEST>(sc, xf, o, d);
-    if (s < sc.n_spheres) return sphere_root(geo[s], o, d, length_squared(d), t_min, t_max, th);
+    if (s < sc.n_spheres) return sphere_root(MOTION ? sphere_at(geo[s], dc[s], tm) : geo[s], o, d, length_squared(d), t_min, t_max, th);
     const uint32_t gi = sc.n_spheres + 2u * (s - sc.n_spheres);
     return rect_root(geo[gi], geo[gi + 1u], o, d, t_min, t_max, th);
 }
@@ -414,9 +438,9 @@ struct ChainCache {
     uint32_t xf; // RT_NO_XFORM_DEV = empty
     V3 o, d;
 };
-template <bool NEST, class Tables>
+template <bool NEST, bool MOTION = false, class Tables>
 __device__ __forceinline__ bool prim_root_cached(const Tables& sc, const float4* geo, uint32_t s, V3 o, V3 d, float t_min,
-                                                 float t_max, ChainCache& cc, float& th) {
+                                                 float t_max, ChainCache& cc, float& th, const float4* dc = nullptr, float tm = 0.0f) {
     const uint32_t xf = sc.prim_xform[s];
     if (xf != RT_NO_XFORM_DEV) {
         if (xf != cc.xf) {
@@ -426,7 +450,7 @@ __device__ __forceinline__ bool prim_root_cached(const Tables& sc, const float4*
         }
         o = cc.o, d = cc.d;
     }
-    if (s < sc.n_spheres) return sphere_root(geo[s], o, d, length_squared(d), t_min, t_max, th);
+    if (s < sc.n_spheres) return sphere_root(MOTION ? sphere_at(geo[s], dc[s], tm) : geo[s], o, d, length_squared(d), t_min, t_max, th);
     const uint32_t gi = sc.n_spheres + 2u * (s - sc.n_spheres);
     return rect_root(geo[gi], geo[gi + 1u], o, d, t_min, t_max, th);
 }
@@ -608,14 +632,16 @@ __device__ __forceinline__ void closest_hit_rects(const DevScene& sc, V3 o, V3 d
     }
 }
 // List walk over spheres of a scene with wrappers (read from HBM; the LDS tile loop assumes none).
-__device__ __forceinline__ void closest_hit_spheres_general(const DevScene& sc, V3 o, V3 d, float& tbest, int& hit) {
+template <bool MOTION = false>
+__device__ __forceinline__ void closest_hit_spheres_general(const DevScene& sc, V3 o, V3 d, float& tbest, int& hit, const float4* dc = nullptr,
+                                                            float tm = 0.0f) {
     for (uint32_t s = 0; s < sc.n_spheres; ++s) {
         float th;
         if (sc.prim_medium[s] != RT_NO_XFORM_DEV) continue;
         V3 po = o, pd = d;
         const uint32_t xf = sc.prim_xform[s];
         if (xf != RT_NO_XFORM_DEV) ray_to_object<true>(sc, xf, po, pd);
-        if (sphere_root(sc.sph_geo[s], po, pd, length_squared(pd), 1e-3f, tbest, th)) {
+        if (sphere_root(MOTION ? sphere_at(sc.sph_geo[s], dc[s], tm) : sc.sph_geo[s], po, pd, length_squared(pd), 1e-3f, tbest, th)) {
             tbest = th;
             hit = (int)s;
         }
@@ -684,6 +710,7 @@ struct BvhLds {
     uint32_t n_spheres;
     GenTables gt;          // wrapper / medium tables of general scenes (HBM, or LDS with GLDS)
     unsigned short* stack; // this lane's column: stack[level * BLOCK]
+    const float4* dc;      // MOTION: the spheres' displacements (LDS when the geometry is, behind everything else of the carve)
 };
 
 // LDS_NODES = false: the tree and the primitive geometry stay in HBM (scenes whose tree does not fit the
@@ -726,14 +753,14 @@ __device__ __forceinline__ BvhLds stage_bvh(const DevScene& sc, char* smem) {
 
 // Exact test of world entry `s` (a BVH leaf or an entry of a primary-ray candidate list) and the order-independent
 // accept.  Sphere-only scenes: Sphere::hit roots (hitable.rs:75-91).
-template <bool RECTS, bool NEST = RECTS>
+template <bool RECTS, bool NEST = RECTS, bool MOTION = false>
 __device__ __forceinline__ void leaf_test(const BvhLds& L, int s, V3 o, V3 d, float a, uint32_t& pend, float& tbest,
-                                          int& hit, ChainCache* cc = nullptr) {
+                                          int& hit, ChainCache* cc = nullptr, float tm = 0.0f) {
     float th;
     // candidate root of this primitive (independent of tbest), then the order-independent accept
     bool ok;
     if (!RECTS) {
-        ok = sphere_root(L.geo[s], o, d, a, 1e-3f, RT_FLT_MAX, th);
+        ok = sphere_root(MOTION ? sphere_at(L.geo[s], L.dc[s], tm) : L.geo[s], o, d, a, 1e-3f, RT_FLT_MAX, th);
     } else {
         // general scene: a primitive that may sit below Translate / RotateY wrappers (t is unchanged by
         // them), or a medium.  A medium costs two searches over its boundary, ~12x a rectangle; tested
@@ -744,8 +771,8 @@ __device__ __forceinline__ void leaf_test(const BvhLds& L, int s, V3 o, V3 d, fl
             pend |= 1u << (NEST ? min((uint32_t)s - L.gt.n_prims, 31u) : (uint32_t)s - L.gt.n_prims); // NEST, bit 31: "one of the media from 31 on" (media_step)
             ok = false;
         } else {
-            ok = cc ? prim_root_cached<NEST>(L.gt, L.geo, (uint32_t)s, o, d, 1e-3f, RT_FLT_MAX, *cc, th)
-                    : prim_root<NEST>(L.gt, L.geo, (uint32_t)s, o, d, 1e-3f, RT_FLT_MAX, th);
+            ok = cc ? prim_root_cached<NEST, MOTION>(L.gt, L.geo, (uint32_t)s, o, d, 1e-3f, RT_FLT_MAX, *cc, th, L.dc, tm)
+                    : prim_root<NEST, MOTION>(L.gt, L.geo, (uint32_t)s, o, d, 1e-3f, RT_FLT_MAX, th, L.dc, tm);
         }
     }
     if (ok && (th < tbest || (th == tbest && s > hit))) {
@@ -792,10 +819,10 @@ struct SlabPlanes {
 // (24 of the ~120 vector instructions of a node step) go away.  Only the fma form relies on it — `exact` rays (inv
 // infinite or NaN among them, see k_intersect) still order the two distances with min / max, which does not care which
 // array a value came from.
-template <int BLOCK, bool RECTS, bool SORTED = false, bool NEST = RECTS>
+template <int BLOCK, bool RECTS, bool SORTED = false, bool NEST = RECTS, bool MOTION = false>
 __device__ __forceinline__ bool bvh_step(const BvhLds& L, V3 o, V3 d, float ix, float iy, float iz, float nox, float noy,
                                          float noz, float eps, bool exact, float a, uint32_t& pend, int& cur, int& sp,
-                                         float& tbest, int& hit, const SlabPlanes* sp6 = nullptr) {
+                                         float& tbest, int& hit, const SlabPlanes* sp6 = nullptr, float tm = 0.0f) {
     { // leaves never reach the stack (they are tested inside the node step below): cur is always a node
         RT_LANE_STAT(2, true);
         const float4 mnx = SORTED ? sp6->nx[cur] : L.pl[0][cur], mny = SORTED ? sp6->ny[cur] : L.pl[1][cur],
@@ -862,7 +889,7 @@ __device__ __forceinline__ bool bvh_step(const BvhLds& L, V3 o, V3 d, float ix, 
             const int s = (int)(lq0 & 0xFFFFu) - 1;
             lq0 = (lq0 >> 16) | (lq1 << 16);
             lq1 >>= 16;
-            leaf_test<RECTS, NEST>(L, s, o, d, a, pend, tbest, hit, RECTS ? &cc : nullptr);
+            leaf_test<RECTS, NEST, MOTION>(L, s, o, d, a, pend, tbest, hit, RECTS ? &cc : nullptr, tm);
         }
         if (best != (int)0x80000000) {
             cur = best;
@@ -910,7 +937,8 @@ struct IntersectParams {
 // 1024-thread workgroups (8 waves per SIMD) share a CU and hide each other's dependent node fetches
 // — measured +15 % on cornell_box and +20 % on final_scene against 7 waves = one workgroup.
 // GEN (depth 0): the ray is regenerated from its queue position instead of being loaded; LENS (with GEN): through the thin lens.
-template <int BLOCK, bool GEN, bool RECTS, bool LDS_NODES, bool GLDS, bool NEST = false, bool LENS = false>
+// MOTION: moving spheres (rt_set_motion).  The time of the lane's ray is formed once, when the lane takes the ray.
+template <int BLOCK, bool GEN, bool RECTS, bool LDS_NODES, bool GLDS, bool NEST = false, bool LENS = false, bool MOTION = false>
 __global__ __launch_bounds__(BLOCK, 8) void k_intersect(DevScene sc, const float4* __restrict__ qa,
                                                      const float4* __restrict__ qb,
                                                      float2* __restrict__ qh, const uint32_t* __restrict__ in_counts,
@@ -932,6 +960,16 @@ __global__ __launch_bounds__(BLOCK, 8) void k_intersect(DevScene sc, const float
     if (GEN && !RECTS && gpd->lists && *gpd->n_overflow == 0u) return; // every pixel has a list: k_shade<GEN> finds all closest hits of depth 0
     BvhLds L = stage_bvh<BLOCK, LDS_NODES>(sc, smem);
     if (GLDS) L.gt = stage_general<BLOCK>(sc, smem + bvh_lds_bytes(sc, BLOCK, LDS_NODES));
+    L.dc = nullptr;
+    if (MOTION) {
+        L.dc = gen_motion_of(gpd).sph_dc;
+        if (LDS_NODES) { // beside the geometry in LDS: behind the carve of the static kernel (and the general tables)
+            float4* sdc = reinterpret_cast<float4*>(smem + bvh_lds_bytes(sc, BLOCK, LDS_NODES) + (GLDS ? general_lds_bytes(sc) : 0u));
+            for (uint32_t i = threadIdx.x; i < sc.n_spheres; i += BLOCK) sdc[i] = L.dc[i];
+            L.dc = sdc;
+        }
+    }
+    float tm = 0.0f; // MOTION: this lane's ray's time
     uint32_t* s_work = reinterpret_cast<uint32_t*>(smem + bvh_lds_bytes(sc, BLOCK, LDS_NODES) - 16u);
     if (threadIdx.x == 0) *s_work = 0u;
     __syncthreads();
@@ -989,11 +1027,18 @@ __global__ __launch_bounds__(BLOCK, 8) void k_intersect(DevScene sc, const float
                     uint32_t k0, k1, pl;
                     gen_primary<LENS>(*gpd, gen_lens_of(gpd), primary_idx_of(ip.nq, shard, off), o, d, k0, k1, pl);
                     if (RECTS) mc.k0 = k0, mc.k1 = k1;
+                    if (MOTION) tm = path_time(gen_motion_of(gpd), k0, k1);
                     if (gpd->lists) list = gpd->lists[pl];
                 } else {
                     const float4 ra = qa[RT_QSTRIDE * pos], rb = qb[RT_QSTRIDE * pos];
                     o = v3(ra.x, ra.y, ra.z);
                     d = v3(rb.x, rb.y, rb.z);
+                    if (MOTION) { // (the key of the slot: the free-path draw of a medium uses it too)
+                        uint32_t k0, k1;
+                        path_key_of_slot(*gpd, __float_as_uint(ra.w), k0, k1);
+                        tm = path_time(gen_motion_of(gpd), k0, k1);
+                        if (RECTS) mc.k0 = k0, mc.k1 = k1;
+                    } else
                     if (RECTS && sc.n_media) path_key_of_slot(*gpd, __float_as_uint(ra.w), mc.k0, mc.k1); // the free-path draw
                 }
                 // Slab constants (culling only, never reference arithmetic): v_rcp_f32, 1 ulp, instead of the IEEE division's
@@ -1022,13 +1067,13 @@ __global__ __launch_bounds__(BLOCK, 8) void k_intersect(DevScene sc, const float
                 if (GEN && has && (list.x & 0xFFFFu) != RT_LIST_OVERFLOW) {
                     // primary ray of a pixel with a candidate list (k_primary_lists): the listed entries instead of the tree
                     const uint32_t n_list = list.x & 0xFFFFu;
-                    if (n_list > 0u) leaf_test<RECTS, NEST>(L, (int)(list.x >> 16), o, d, a, pend, tbest, hit);
-                    if (n_list > 1u) leaf_test<RECTS, NEST>(L, (int)(list.y & 0xFFFFu), o, d, a, pend, tbest, hit);
-                    if (n_list > 2u) leaf_test<RECTS, NEST>(L, (int)(list.y >> 16), o, d, a, pend, tbest, hit);
-                    if (n_list > 3u) leaf_test<RECTS, NEST>(L, (int)(list.z & 0xFFFFu), o, d, a, pend, tbest, hit);
-                    if (n_list > 4u) leaf_test<RECTS, NEST>(L, (int)(list.z >> 16), o, d, a, pend, tbest, hit);
-                    if (n_list > 5u) leaf_test<RECTS, NEST>(L, (int)(list.w & 0xFFFFu), o, d, a, pend, tbest, hit);
-                    if (n_list > 6u) leaf_test<RECTS, NEST>(L, (int)(list.w >> 16), o, d, a, pend, tbest, hit);
+                    if (n_list > 0u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.x >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 1u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.y & 0xFFFFu), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 2u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.y >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 3u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.z & 0xFFFFu), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 4u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.z >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 5u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.w & 0xFFFFu), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 6u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.w >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
                     if (RECTS && pend) {
                         trav = false; // its media are tested in the media phase below
                     } else {
@@ -1054,7 +1099,7 @@ __global__ __launch_bounds__(BLOCK, 8) void k_intersect(DevScene sc, const float
                 continue;
             }
         }
-        if (has && trav && bvh_step<BLOCK, RECTS, SORTED, NEST>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit, &planes)) {
+        if (has && trav && bvh_step<BLOCK, RECTS, SORTED, NEST, MOTION>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit, &planes, tm)) {
             if (RECTS && pend) {
                 trav = false;
             } else {
@@ -1109,6 +1154,61 @@ __global__ __launch_bounds__(256) void k_intersect_list(DevScene sc, const float
         }
         MediumCtx mc{0u, 0u, depth_counter_base(ip.depth)};
         if (active && sc.n_media) path_key_of_slot(*gpd, __float_as_uint(qa[RT_QSTRIDE * (qbase + i)].w), mc.k0, mc.k1);
+        closest_hit_rects(sc, o, d, mc, tbest, hit);
+        if (active) qh[qbase + i] = make_float2(tbest, __int_as_float(hit));
+    }
+}
+
+// k_intersect_list with moving spheres (rt_set_motion), a kernel of its own beside the static one, whose code stays as it was.  The
+// displacements are read from HBM beside the LDS tile — this walk is the test path (RT_FLAG_BRUTE_FORCE) and the last resort, not a hot
+// one.  The ray's time comes from its slot key, which a medium's free-path draw uses too.
+__global__ __launch_bounds__(256) void k_intersect_list_motion(DevScene sc, const float4* __restrict__ qa,
+                                                    const float4* __restrict__ qb,
+                                                    float2* __restrict__ qh, const uint32_t* __restrict__ in_counts,
+                                                    IntersectParams ip, const GenParams* __restrict__ gpd) {
+    constexpr bool MOTION = true;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float4* s_geo = reinterpret_cast<float4*>(smem);
+    const uint32_t q = ip.q0 + blockIdx.x;
+    const uint32_t count = in_counts[q];
+    if (count == 0) return;
+    const uint32_t n_sph = sc.n_spheres;
+    const bool single_tile = n_sph <= RT_SPHERE_TILE;
+    if (single_tile) {
+        for (uint32_t i = threadIdx.x; i < n_sph; i += 256u) s_geo[i] = sc.sph_geo[i];
+        __syncthreads();
+    }
+    const size_t qbase = (size_t)q * ip.cap;
+    for (uint32_t base = 0; base < count; base += 256u) {
+        const uint32_t i = base + threadIdx.x;
+        const bool active = i < count;
+        V3 o = splat(0.0f), d = v3(0.f, 0.f, 1.f);
+        if (active) {
+            const float4 ra = qa[RT_QSTRIDE * (qbase + i)], rb = qb[RT_QSTRIDE * (qbase + i)];
+            o = v3(ra.x, ra.y, ra.z);
+            d = v3(rb.x, rb.y, rb.z);
+        }
+        float tbest = RT_FLT_MAX;
+        int hit = -1;
+        const float a = length_squared(d);
+        MediumCtx mc{0u, 0u, depth_counter_base(ip.depth)};
+        if (MOTION && active) path_key_of_slot(*gpd, __float_as_uint(qa[RT_QSTRIDE * (qbase + i)].w), mc.k0, mc.k1);
+        const float4* dc = MOTION ? gen_motion_of(gpd).sph_dc : nullptr;
+        const float tm = MOTION ? path_time(gen_motion_of(gpd), mc.k0, mc.k1) : 0.0f;
+        if (sc.n_xforms || sc.n_media) {
+            closest_hit_spheres_general<MOTION>(sc, o, d, tbest, hit, dc, tm);
+        } else if (single_tile) {
+            closest_hit_tile<MOTION>(s_geo, n_sph, 0u, o, d, a, tbest, hit, dc, tm);
+        } else {
+            for (uint32_t t0 = 0; t0 < n_sph; t0 += RT_SPHERE_TILE) {
+                const uint32_t n = min(RT_SPHERE_TILE, n_sph - t0);
+                __syncthreads();
+                for (uint32_t k = threadIdx.x; k < n; k += 256u) s_geo[k] = sc.sph_geo[t0 + k];
+                __syncthreads();
+                closest_hit_tile<MOTION>(s_geo, n, t0, o, d, a, tbest, hit, dc, tm);
+            }
+        }
+        if (!MOTION && active && sc.n_media) path_key_of_slot(*gpd, __float_as_uint(qa[RT_QSTRIDE * (qbase + i)].w), mc.k0, mc.k1);
         closest_hit_rects(sc, o, d, mc, tbest, hit);
         if (active) qh[qbase + i] = make_float2(tbest, __int_as_float(hit));
     }
@@ -1171,7 +1271,7 @@ __host__ __device__ inline size_t shade_lds_bytes(uint32_t n_entries, uint32_t n
     b += (size_t)n_fused_spheres * 16u;
     return (b + 15u) & ~(size_t)15u;
 }
-template <bool PERLIN_LDS, bool GEN, bool RECTS, bool NEST = false, bool LENS = false> // NEST (general scenes only): rt_device.h, wrapper chains and media as loops; LENS (with GEN): the thin lens
+template <bool PERLIN_LDS, bool GEN, bool RECTS, bool NEST = false, bool LENS = false, bool MOTION = false> // MOTION: moving spheres (rt_set_motion) — the time comes from the path key a hit that scatters needs anyway; the all-miss segments stay free of it.  NEST (general scenes only): rt_device.h, wrapper chains and media as loops; LENS (with GEN): the thin lens
 #ifndef RT_GEN_WAVES
 #define RT_GEN_WAVES 4 // waves per SIMD the depth-0 instantiations are compiled for (98 VGPR: 5 fit).  Round 2: 4 / 5 / 6 no difference.
                        // Round 3 (cheaper draws): alone on the chip, 6 (80 VGPR, 8 B of scratch) is 2.4-2.7 % faster at depth 0 on the
@@ -1226,7 +1326,10 @@ __global__ __launch_bounds__(256, GEN ? RT_GEN_WAVES : RT_SORTED_WAVES) void k_s
     if (fused) {
         float4* g = reinterpret_cast<float4*>(smem + lds_off);
         for (uint32_t i = threadIdx.x; i < sc.n_spheres; i += 256u) g[i] = sc.sph_geo[i];
+        if (MOTION) // the displacements behind the geometry (the host doubles n_fused_spheres of shade_lds_bytes)
+            for (uint32_t i = threadIdx.x; i < sc.n_spheres; i += 256u) g[sc.n_spheres + i] = gen_motion_of(gpd).sph_dc[i];
     }
+    const float4* s_dc = s_geo + sc.n_spheres;
     if (threadIdx.x == 0) *s_out = 0u;
     __syncthreads();
     uint32_t n_fetch = 0, n_bad = 0;
@@ -1359,6 +1462,7 @@ __global__ __launch_bounds__(256, GEN ? RT_GEN_WAVES : RT_SORTED_WAVES) void k_s
             V3 T = splat(0.0f);
             float rr_threshold = 0.0f;
             uint32_t slot = 0, k0 = 0, k1 = 0;
+            float tm = 0.0f;
             if (j < n_here) {
                 float2 h = hA;
                 V3 o, d;
@@ -1366,6 +1470,7 @@ __global__ __launch_bounds__(256, GEN ? RT_GEN_WAVES : RT_SORTED_WAVES) void k_s
                     uint32_t pl;
                     slot = primary_idx_of(tp.nq, q, base + j);
                     gen_primary<LENS>(*gpd, gen_lens_of(gpd), slot, o, d, k0, k1, pl);
+                    if (MOTION) tm = path_time(gen_motion_of(gpd), k0, k1);
                     T = splat(1.0f);
                     uint4 list = make_uint4(RT_LIST_OVERFLOW, 0u, 0u, 0u);
                     if (fused) list = gpd->lists[pl];
@@ -1383,7 +1488,7 @@ __global__ __launch_bounds__(256, GEN ? RT_GEN_WAVES : RT_SORTED_WAVES) void k_s
                             float th;
                             const int s = (int)ids[t];
                             if (t < n_list) RT_LANE_STAT(12, true); // (profiling builds: trips of the list test and lanes in them)
-                            if (t < n_list && sphere_root(s_geo[s], o, d, ra, 1e-3f, RT_FLT_MAX, th) &&
+                            if (t < n_list && sphere_root(MOTION ? sphere_at(s_geo[s], s_dc[s], tm) : s_geo[s], o, d, ra, 1e-3f, RT_FLT_MAX, th) &&
                                 (th < tbest || (th == tbest && s > hit))) {
                                 tbest = th;
                                 hit = s;
@@ -1398,6 +1503,7 @@ __global__ __launch_bounds__(256, GEN ? RT_GEN_WAVES : RT_SORTED_WAVES) void k_s
                     T = v3(rbA.w, rcA.x, rcA.y);
                     slot = __float_as_uint(raA.w);
                     path_key_of_slot(*gpd, slot, k0, k1);
+                    if (MOTION) tm = path_time(gen_motion_of(gpd), k0, k1);
                 }
                 V3 Lr = splat(0.0f);
                 if (!near_one(d)) { // main.rs:39 assert!: the reference panics; the path is dropped
@@ -1407,7 +1513,8 @@ __global__ __launch_bounds__(256, GEN ? RT_GEN_WAVES : RT_SORTED_WAVES) void k_s
                     if (__float_as_int(h.y) >= (int)(sc.n_prims + sc.n_media)) __builtin_trap();
 #endif
                     Rng rng{k0, k1, depth_counter_base(tp.depth)};
-                    bo = shade<RECTS, decltype(prefetch), NEST>(sc, pt, o, d, __float_as_int(h.y), h.x, rng, n_fetch, prefetch);
+                    bo = shade<RECTS, decltype(prefetch), NEST, MOTION>(sc, pt, o, d, __float_as_int(h.y), h.x, rng, n_fetch, prefetch,
+                                                                        MOTION ? gen_motion_of(gpd).sph_dc : nullptr, tm);
                     if (bo.alive && tp.russian_roulette) { // main.rs:49-53
                         const float rr = rng.next();
                         rr_threshold = fmaxf(bo.attenuation.x, fmaxf(bo.attenuation.y, bo.attenuation.z)); // max_element
@@ -1603,6 +1710,76 @@ __global__ __launch_bounds__(BLOCK) void k_debug_bounce(DevScene sc, uint32_t n,
     uint32_t n_fetch = 0;
     Rng rng{in_key[2 * i], in_key[2 * i + 1], depth_counter_base(depth)};
     Bounce bo = shade<true, NoPrefetch, true>(sc, PerlinTables{sc.perlin_vec, sc.perlin_perm2}, o, d, hit, tbest, rng, n_fetch);
+    out_hit[i] = hit;
+    out_t[i] = hit >= 0 ? tbest : 0.0f;
+    out_rad[3 * i] = bo.radiance.x, out_rad[3 * i + 1] = bo.radiance.y, out_rad[3 * i + 2] = bo.radiance.z;
+    out_att[3 * i] = bo.attenuation.x, out_att[3 * i + 1] = bo.attenuation.y, out_att[3 * i + 2] = bo.attenuation.z;
+    out_o[3 * i] = bo.o.x, out_o[3 * i + 1] = bo.o.y, out_o[3 * i + 2] = bo.o.z;
+    out_d[3 * i] = bo.d.x, out_d[3 * i + 1] = bo.d.y, out_d[3 * i + 2] = bo.d.z;
+    out_alive[i] = bo.alive ? 1 : 0;
+}
+
+// k_debug_bounce with moving spheres (rt_set_motion): the ray's time comes from counter 254 of in_key; the displacements are read from
+// HBM.  A kernel of its own beside the static one, whose code stays as it was.
+template <int BLOCK, bool USE_BVH, bool LDS_NODES>
+__global__ __launch_bounds__(BLOCK) void k_debug_bounce_motion(DevScene sc, uint32_t n, int depth, const float* __restrict__ in_o,
+                                                  const float* __restrict__ in_d, const uint32_t* __restrict__ in_key,
+                                                  int* __restrict__ out_hit, float* __restrict__ out_t,
+                                                  float* __restrict__ out_rad, float* __restrict__ out_att,
+                                                  float* __restrict__ out_o, float* __restrict__ out_d,
+                                                  uint8_t* __restrict__ out_alive, GenMotion gm) {
+    constexpr bool MOTION = true;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    const bool active = i < n;
+    const float tm = MOTION && active ? path_time(gm, in_key[2 * i], in_key[2 * i + 1]) : 0.0f;
+    V3 o = splat(0.0f), d = v3(0.f, 0.f, 1.f);
+    if (active) {
+        o = v3(in_o[3 * i], in_o[3 * i + 1], in_o[3 * i + 2]);
+        d = v3(in_d[3 * i], in_d[3 * i + 1], in_d[3 * i + 2]);
+    }
+    float tbest = RT_FLT_MAX;
+    int hit = -1;
+    const float a = length_squared(d);
+    if (USE_BVH) {
+        BvhLds L = stage_bvh<BLOCK, LDS_NODES>(sc, smem);
+        L.dc = gm.sph_dc;
+        __syncthreads();
+        if (active && sc.n_prims) {
+            const float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
+            const float nox = -(o.x * ix), noy = -(o.y * iy), noz = -(o.z * iz);
+            float eps = 2.4e-7f * fmaxf(fmaxf(fabsf(nox), fabsf(noy)), fabsf(noz));
+            const bool exact = !(eps <= sc.bvh_exact_eps);
+            if (exact) eps = 0.0f;
+            int cur = 0, sp = 0;
+            const MediumCtx mc{active ? in_key[2 * i] : 0u, active ? in_key[2 * i + 1] : 0u, depth_counter_base(depth)};
+            uint32_t pend = 0u;
+            while (!bvh_step<BLOCK, true, false, true, MOTION>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit, nullptr, tm)) {
+            }
+            while (pend && !media_step<true>(L, o, d, mc, sc.n_media, pend, tbest, hit)) {
+            }
+        }
+    } else {
+        float4* s_geo = reinterpret_cast<float4*>(smem);
+        if (sc.n_xforms || sc.n_media) {
+            closest_hit_spheres_general<MOTION>(sc, o, d, tbest, hit, gm.sph_dc, tm);
+        } else {
+            for (uint32_t t0 = 0; t0 < sc.n_spheres; t0 += RT_SPHERE_TILE) {
+                const uint32_t nn = min(RT_SPHERE_TILE, sc.n_spheres - t0);
+                __syncthreads();
+                for (uint32_t k = threadIdx.x; k < nn; k += BLOCK) s_geo[k] = sc.sph_geo[t0 + k];
+                __syncthreads();
+                closest_hit_tile<MOTION>(s_geo, nn, t0, o, d, a, tbest, hit, gm.sph_dc, tm);
+            }
+        }
+        const MediumCtx mc{active ? in_key[2 * i] : 0u, active ? in_key[2 * i + 1] : 0u, depth_counter_base(depth)};
+        closest_hit_rects(sc, o, d, mc, tbest, hit);
+    }
+    if (!active) return;
+    uint32_t n_fetch = 0;
+    Rng rng{in_key[2 * i], in_key[2 * i + 1], depth_counter_base(depth)};
+    Bounce bo = shade<true, NoPrefetch, true, MOTION>(sc, PerlinTables{sc.perlin_vec, sc.perlin_perm2}, o, d, hit, tbest, rng, n_fetch, NoPrefetch(),
+                                                      gm.sph_dc, tm);
     out_hit[i] = hit;
     out_t[i] = hit >= 0 ? tbest : 0.0f;
     out_rad[3 * i] = bo.radiance.x, out_rad[3 * i + 1] = bo.radiance.y, out_rad[3 * i + 2] = bo.radiance.z;

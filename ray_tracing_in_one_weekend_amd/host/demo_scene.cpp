@@ -96,6 +96,57 @@ std::pair<HitableList, Camera> sphere_scene(float aspect_ratio) {
     return build_bvh(world, cam); // :85
 }
 
+// The cover of "The Next Week": sphere_scene's layout and draw order, the small DIFFUSE spheres moving upwards by dy in [0, 0.5) while the
+// shutter is open (c1 = c0 + (0, dy, 0)).  dy comes from a stream of its own, so every sphere stands where sphere_scene puts it.
+std::pair<HitableList, Camera> moving_sphere_scene(float aspect_ratio) {
+    SKY_COLOR_set(SkyFn::sky_color); // :38
+    auto perlin = PerlinTex::new_(4.0f);                   // :41 (first consumer of the thread RNG)
+    auto earth_map = ImageTex::new_("res/earthmap.jpg");   // :42
+    auto material_ground = std::make_shared<Diffuse>(perlin);
+    auto material_1 = std::make_shared<Emission>(earth_map);
+    auto material_2 = std::make_shared<Dielectric>(1.5f);
+    auto material_3 = std::make_shared<Metal>(vec3a(0.8f, 0.6f, 0.2f), 0.0f);
+    HitableList world = {
+        std::make_shared<Sphere>(vec3a(1.0f, -1000.0f, -1.0f), 1000.0f, material_ground, "Ground"),
+        std::make_shared<Sphere>(vec3a(0.0f, 1.0f, 3.0f), 1.0f, material_1, "Sphere_1"),
+        std::make_shared<Sphere>(vec3a(-4.0f, 1.0f, 0.0f), 1.0f, material_2, "Sphere_2"),
+        std::make_shared<Sphere>(vec3a(4.0f, 1.0f, 0.0f), 1.0f, material_3, "Sphere_3"),
+    };
+    SmallRng rng = SmallRng::seed_from_u64(95); // :56
+    SmallRng rng_dy = SmallRng::seed_from_u64(96);
+    for (int a = -11; a <= 11; ++a) {
+        for (int b = -11; b <= 11; ++b) {
+            float choose_mat = rng.gen_f32();
+            float cx = (float)a + 0.9f * rng.gen_f32();
+            float cz = (float)b + 0.9f * rng.gen_f32();
+            Vec3A center = vec3a(cx, 0.2f, cz);
+            MaterialPtr mat;
+            bool moves = false;
+            float dy = 0.0f;
+            if (choose_mat < 0.8f) {
+                float ax = rng.gen_f32(), ay = rng.gen_f32(), az = rng.gen_f32();
+                float bx = rng.gen_f32(), by = rng.gen_f32(), bz = rng.gen_f32();
+                Vec3A col = vec3a(ax, ay, az) * vec3a(bx, by, bz);
+                mat = std::make_shared<Diffuse>(std::make_shared<ConstantTex>(col));
+                moves = true;
+                dy = 0.5f * rng_dy.gen_f32(); // gen_range(0.0..0.5)
+            } else if (choose_mat < 0.95f) {
+                float ax = rng.gen_f32(), ay = rng.gen_f32(), az = rng.gen_f32();
+                Vec3A albedo = vec3a(ax, ay, az) * 0.5f + 0.5f;
+                float fuzz = rng.gen_f32();
+                mat = std::make_shared<Metal>(albedo, fuzz);
+            } else {
+                mat = material_2;
+            }
+            const std::string name = "Sphere " + std::to_string(a) + ", " + std::to_string(b);
+            if (moves) world.push_back(std::make_shared<MovingSphere>(center, center + vec3a(0.0f, dy, 0.0f), 0.2f, mat, name));
+            else world.push_back(std::make_shared<Sphere>(center, 0.2f, mat, name));
+        }
+    }
+    Camera cam = Camera::new_(vec3a(13.0f, 2.0f, 3.0f), vec3a(0.0f, 0.0f, 0.0f), vec3a(0.0f, 1.0f, 0.0f), 20.0f, aspect_ratio);
+    return build_bvh(world, cam); // :85
+}
+
 // demo_scene.rs:229-244 — two Lambert spheres, gradient sky, no BVH.
 std::pair<HitableList, Camera> test_sphere(float aspect_ratio) {
     SKY_COLOR_set(SkyFn::sky_color);

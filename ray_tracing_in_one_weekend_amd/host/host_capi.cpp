@@ -83,6 +83,7 @@ int rth_scene_build(const char* name, float aspect_ratio, RthScene** out) {
         std::string n(name);
         SceneFn fn = nullptr;
         if (n == "sphere_scene") fn = sphere_scene;
+        else if (n == "moving_sphere_scene") fn = moving_sphere_scene;
         else if (n == "test_sphere") fn = test_sphere;
         else if (n == "simple_light_scene") fn = simple_light_scene;
         else if (n == "cornell_box") fn = cornell_box;
@@ -169,6 +170,14 @@ uint32_t rth_sphere(RthScene* s, const float c[3], float r, uint32_t material, c
     return guarded_handle([&]() -> uint32_t {
         if (material >= s->materials.size()) throw std::runtime_error("rth_sphere: bad material handle");
         s->world.push_back(std::make_shared<Sphere>(v(c), r, s->materials[material], name ? name : ""));
+        return (uint32_t)s->world.size() - 1;
+    });
+}
+
+uint32_t rth_moving_sphere(RthScene* s, const float c0[3], const float c1[3], float r, uint32_t material, const char* name) {
+    return guarded_handle([&]() -> uint32_t {
+        if (material >= s->materials.size()) throw std::runtime_error("rth_moving_sphere: bad material handle");
+        s->world.push_back(std::make_shared<MovingSphere>(v(c0), v(c1), r, s->materials[material], name ? name : ""));
         return (uint32_t)s->world.size() - 1;
     });
 }
@@ -270,6 +279,16 @@ int rth_set_camera_lens(RthScene* s, const float lookfrom[3], const float lookat
     });
 }
 
+int rth_set_camera_shutter(RthScene* s, float shutter_open, float shutter_close) {
+    return guarded([&] {
+        if (!s->has_camera) throw std::runtime_error("rth_set_camera_shutter: set the camera first");
+        if (!std::isfinite(shutter_open) || !std::isfinite(shutter_close) || shutter_open < 0.0f || shutter_close > 1.0f || shutter_open > shutter_close)
+            throw std::runtime_error("rth_set_camera_shutter: 0 <= shutter_open <= shutter_close <= 1");
+        s->camera.shutter_open = shutter_open, s->camera.shutter_close = shutter_close;
+        return RT_OK;
+    });
+}
+
 int rth_scene_finish(RthScene* s, int use_bvh) {
     return guarded([&] { return finish(s, use_bvh != 0); });
 }
@@ -285,6 +304,15 @@ int rth_scene_camera(const RthScene* s, RtCamera* out) {
 int rth_scene_lens(const RthScene* s, RtLens* out) {
     if (!s || !out || !s->finished) return RT_ERR_INVALID;
     *out = s->rt_lens;
+    return RT_OK;
+}
+
+int rth_scene_motion(const RthScene* s, RtMotion* out) {
+    if (!s || !out || !s->finished) return RT_ERR_INVALID;
+    out->n_moving = (uint32_t)s->builder.motion_sphere.size();
+    out->sphere = s->builder.motion_sphere.data();
+    out->center1 = s->builder.motion_c1.data();
+    out->shutter_open = s->camera.shutter_open, out->shutter_close = s->camera.shutter_close;
     return RT_OK;
 }
 

@@ -166,6 +166,14 @@ class FlatSceneBuilder {
         sph_xform.push_back(cur_xform);
         sph_medium.push_back(cur_medium);
     }
+    // a MovingSphere: the sphere at its centre of time 0, and an entry of the motion table (rt_set_motion) with its centre of time 1
+    void push_moving_sphere(Vec3A c0, Vec3A c1, float r, uint32_t mat, const std::string& name) {
+        if (cur_xform != RT_NO_XFORM || cur_medium != RT_NO_MEDIUM)
+            throw std::runtime_error("flatten: a MovingSphere below a wrapper or as a medium boundary (only bare spheres move)");
+        motion_sphere.push_back((uint32_t)sph_cx.size());
+        push3(motion_c1, c1);
+        push_sphere(c0, r, mat, name);
+    }
     // hitable.rs:523-533 ConstantMedium: primitives pushed until end_medium() bound medium `m`
     uint32_t begin_medium(float neg_inv_density, uint32_t mat) {
         if (cur_medium != RT_NO_MEDIUM) throw std::runtime_error("flatten: a ConstantMedium inside a ConstantMedium boundary");
@@ -219,6 +227,8 @@ class FlatSceneBuilder {
     }
 
     std::vector<float> sph_cx, sph_cy, sph_cz, sph_r;
+    std::vector<uint32_t> motion_sphere; // motion table: sphere indices (increasing: spheres are pushed in order) and centres at time 1
+    std::vector<float> motion_c1;
     std::vector<uint32_t> sph_mat;
     std::vector<std::string> sph_name;
     std::vector<uint8_t> rect_axis;
@@ -497,6 +507,22 @@ struct Sphere : Hitable { // hitable.rs:57-62
     std::string memo() const override { return name; }
 };
 
+// "The Next Week" chapter 1: a sphere whose centre moves linearly from center0 (time 0) to center1 (time 1).  Flattens to the
+// sphere at center0 plus a motion-table entry; its box is the union of the boxes at both ends.
+struct MovingSphere : Hitable {
+    Vec3A c0, c1;
+    float r;
+    MaterialPtr mat;
+    std::string name;
+    MovingSphere(Vec3A c0_, Vec3A c1_, float r_, MaterialPtr m, std::string n) : c0(c0_), c1(c1_), r(r_), mat(std::move(m)), name(std::move(n)) {}
+    void flatten(FlatSceneBuilder& b) const override { b.push_moving_sphere(c0, c1, r, b.intern_material(mat.get()), name); }
+    bool bbox(AABB& aabb) const override {
+        aabb = AABB{c0 + (-r), c0 + r}.surround(AABB{c1 + (-r), c1 + r});
+        return true;
+    }
+    std::string memo() const override { return name; }
+};
+
 // hitable.rs:244-362 — axis-aligned rectangles.  The plane coordinate is min[axis] (max[axis] is ignored by hit()).
 #define RTOW_RECT(Name, AXIS, MEMO)                                                                      \
     struct Name : Hitable {                                                                              \
@@ -757,6 +783,8 @@ class Camera {
         return r;
     }
     RtLens lens() const { return RtLens{lens_radius, focus_dist}; }
+    // the shutter interval of motion blur, 0 <= open <= close <= 1 (default: the whole of [0, 1])
+    float shutter_open = 0.0f, shutter_close = 1.0f;
 
   private:
     Vec3A origin, horizontal, vertical, lower_left_corner;
@@ -781,6 +809,7 @@ inline void flatten_world(const HitableList& world, FlatSceneBuilder& b) {
 // ---- demo_scene.rs ---------------------------------------------------------------------------------------------
 using SceneFn = std::pair<HitableList, Camera> (*)(float aspect_ratio);
 std::pair<HitableList, Camera> sphere_scene(float aspect_ratio); // demo_scene.rs:37-86  "random-spheres"
+std::pair<HitableList, Camera> moving_sphere_scene(float aspect_ratio); // sphere_scene with its small diffuse spheres bouncing ("The Next Week" cover)
 std::pair<HitableList, Camera> test_sphere(float aspect_ratio);  // demo_scene.rs:229-244
 std::pair<HitableList, Camera> simple_light_scene(float aspect_ratio); // demo_scene.rs:88-110 (spheres + XYRect light)
 std::pair<HitableList, Camera> cornell_box(float aspect_ratio);        // demo_scene.rs:112-148 (walls + two smoke boxes)

@@ -13,7 +13,7 @@ import time
 from . import Renderer, Scene, make_params, output_file_name, register_default_images, save_png
 from . import _ffi
 
-SCENES = ("test_sphere", "sphere_scene", "simple_light_scene", "cornell_box", "final_scene", "earth_env_scene",
+SCENES = ("test_sphere", "sphere_scene", "moving_sphere_scene", "simple_light_scene", "cornell_box", "final_scene", "earth_env_scene",
           "pbr_sweep_scene")
 
 
@@ -32,6 +32,8 @@ def main(argv=None):
     ap.add_argument("--aperture", type=float, default=0.0,
                     help="thin-lens aperture of the book's Camera::new (chapter 13; the cover: 0.1); 0 = pinhole")
     ap.add_argument("--focus-dist", type=float, default=10.0, help="distance of the plane of focus (with --aperture)")
+    ap.add_argument("--shutter", type=float, nargs=2, default=None, metavar=("OPEN", "CLOSE"),
+                    help="shutter interval within [0, 1] for a scene with moving spheres (default: the scene camera's, [0, 1])")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     ny = a.ny
@@ -45,6 +47,11 @@ def main(argv=None):
     rend.upload(scene)
     if a.aperture:
         rend.set_lens((a.aperture / 2.0, a.focus_dist))
+    motion = scene.motion  # a scene's moving spheres are applied by themselves
+    if motion.n_moving:
+        if a.shutter:
+            motion.shutter_open, motion.shutter_close = a.shutter
+        rend.set_motion(motion)
     flags = _ffi.FLAG_RUSSIAN_ROULETTE if a.russian_roulette else 0
     params = make_params(a.nx, ny, a.spp, max_depth=a.max_depth, seed=a.seed, spp_slice=a.preview_every, flags=flags)
     if a.preview_every:
