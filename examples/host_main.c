@@ -113,6 +113,18 @@ int main(int argc, char** argv) {
         goto done;
     }
 
+    { /* the scene's quads and triangles ("quads_scene", "mesh_scene"): they are attached to the uploaded scene */
+        RtQuads quads;
+        if (rth_scene_quads(scene, &quads) != 0) {
+            fail("rth_scene_quads", rth_last_error());
+            goto done;
+        }
+        if (quads.n && rt_set_quads(ctx, &quads) != 0) {
+            fail("rt_set_quads", rt_last_error(ctx));
+            goto done;
+        }
+    }
+
     /* main.rs:76 ImageBuffer::new(nx, ny) — in page-locked memory, so that the frame arrives at PCIe rate */
     n = (size_t)nx * ny * 3u;
     frame = (float*)rt_host_alloc(n * sizeof(float));

@@ -38,7 +38,7 @@ int rth_register_image(const char* path, uint32_t w, uint32_t h, const float* rg
 /* Re-seeds the thread-local RNG (lib.rs:8; default 1995) that PerlinTex::new draws from. */
 void rth_rng_reseed(uint64_t seed);
 
-/* Runs a named scene function: "sphere_scene", "test_sphere", "simple_light_scene",
+/* Runs a named scene function: "sphere_scene", "moving_sphere_scene", "quads_scene", "mesh_scene", "test_sphere", "simple_light_scene",
  * "cornell_box", "final_scene", "earth_env_scene", "pbr_sweep_scene"; flattens world + sky + camera.  The thread RNG is reset to its
  * fresh-process state (seed 1995) first, so repeated builds give identical Perlin tables. */
 int rth_scene_build(const char* name, float aspect_ratio, RthScene** out);
@@ -57,6 +57,11 @@ uint32_t rth_sphere(RthScene* s, const float c[3], float r, uint32_t material, c
  * (time 1).  Flattens to the sphere at c0 plus an entry of rth_scene_motion; only at the top level of the world (not below
  * rth_translate / rth_rotate_y, not as a medium boundary: rth_scene_finish fails). */
 uint32_t rth_moving_sphere(RthScene* s, const float c0[3], const float c1[3], float r, uint32_t material, const char* name);
+/* "The Next Week" chapter 6: the quad Q + a u + b v (0 <= a, b <= 1) and the triangle with the corners a, b, c, stored as Q = a,
+ * u = b - a, v = c - a (each rounded to f32 once).  They flatten to entries of rth_scene_quads, in the order the world lists them; only
+ * at the top level of the world (not below rth_translate / rth_rotate_y, not as a medium boundary: rth_scene_finish fails). */
+uint32_t rth_quad(RthScene* s, const float Q[3], const float u[3], const float v[3], uint32_t material);
+uint32_t rth_triangle(RthScene* s, const float a[3], const float b[3], const float c[3], uint32_t material);
 /* hitable.rs:244-362 XYRect/XZRect/YZRect { min, max, mat } (axis = RtRectAxis) and hitable.rs:364-383 GBox::new */
 uint32_t rth_rect(RthScene* s, uint32_t axis, const float mn[3], const float mx[3], uint32_t material);
 uint32_t rth_gbox(RthScene* s, const float mn[3], const float mx[3], uint32_t material);
@@ -90,6 +95,9 @@ int rth_scene_lens(const RthScene* s, RtLens* out);
 /* The motion of the finished scene for rt_set_motion: its moving spheres (pointers into the scene, valid until rth_scene_free) and the
  * camera's shutter; n_moving 0 for a static scene. */
 int rth_scene_motion(const RthScene* s, RtMotion* out);
+/* The planar primitives of the finished scene for rt_set_quads (pointers into the scene, valid until rth_scene_free); n 0 for a scene
+ * without any. */
+int rth_scene_quads(const RthScene* s, RtQuads* out);
 const char* rth_scene_sphere_name(const RthScene* s, uint32_t index);
 void rth_scene_free(RthScene* s);
 

@@ -362,6 +362,48 @@ typedef struct RtMotion {
  * 0 <= open <= close <= 1) or RT_ERR_UNSUPPORTED: the previous motion stays.  The arrays are copied. */
 int rt_set_motion(RtCtx* ctx, const RtMotion* motion);
 
+/* Planar primitives ("The Next Week", chapter 6): quadrilaterals (parallelograms) Q + a u + b v, 0 <= a, b <= 1, in any orientation, and
+ * triangles with the corners Q, Q + u, Q + v (a, b >= 0, a + b <= 1), attached to the uploaded scene.  Planar primitive i is primitive
+ * n_spheres + n_rects + n_media + i: it comes after everything of the world list, no existing index moves, and it takes part in the
+ * winner rule t < best || (t == best && idx > best_idx).  The primitives are bare (no wrapper, no medium boundary); transform the
+ * vertices yourself.  The hit test is the book's quad::hit, every operation one IEEE f32 operation:
+ *   at rt_set_quads, once, in this order:  n = cross(u, v);  normal = n / sqrt(dot(n, n)) (three divisions);  D = dot(normal, Q);
+ *     w = n / dot(n, n) (three divisions);  dot(a, b) = (ax bx + ay by) + az bz,  cross(a, b) = (ay bz - az by, az bx - ax bz, ax by - ay bx)
+ *   per ray:  denom = dot(normal, d), a miss where |denom| < 1e-8;  t = (D - dot(normal, o)) / denom, rejected when NaN, t < t_min or
+ *     t > t_max;  P = o + d t;  p = P - Q;  alpha = dot(w, cross(p, v));  beta = dot(w, cross(u, p));  quad: 0 <= alpha <= 1 &&
+ *     0 <= beta <= 1;  triangle: alpha >= 0 && beta >= 0 && alpha + beta <= 1.
+ * The record is p = P, t, uv = (alpha, beta) (what an image texture reads) and set_face_normal(r, normal).  A planar primitive carries
+ * no tangent, as a rectangle carries none: DisneyMetal on one is RT_ERR_UNSUPPORTED.  As the book's, the test is NOT watertight across
+ * an edge two primitives share: in f32 a ray through the edge may be accepted by both, or by neither.
+ * Conditioning: RT_ERR_INVALID unless |n|^2 >= RT_PLANAR_MIN_SIN2 |u|^2 |v|^2 (evaluated in double; sin of the angle between u and v
+ * at least 2^-10, 0.056 degrees) — the limit the culling bound is derived for.  A tree leaf is the box of the 3 or 4 corners grown by
+ *   slack = 2^-24 (64 L / sin(u, v) + 16 (M + RT_PLANAR_REACH W)),  L = max(|u|, |v|), M = the largest corner coordinate magnitude,
+ *   W = the largest coordinate magnitude of the scene's bounds and of all corners of the set,
+ * which covers what the f32 test can accept outside the exact figure for every ray whose origin coordinates stay within
+ * RT_PLANAR_REACH W (DESIGN.md "Planar primitives").  Scattered rays start on the scene; the camera is checked: rt_render of a context
+ * that holds a set returns RT_ERR_UNSUPPORTED when |origin_k| + lens_radius exceeds RT_PLANAR_REACH W on any axis.
+ * Moving spheres and planar primitives do not combine yet: rt_set_motion on a context that holds planar primitives, and rt_set_quads
+ * on one that holds a motion, are RT_ERR_UNSUPPORTED and the previous state stays.  rt_set_lens combines freely. */
+enum RtPlanarKind { RT_PLANAR_QUAD = 0, RT_PLANAR_TRIANGLE = 1 };
+#define RT_PLANAR_MIN_SIN2 9.5367431640625e-07 /* 2^-20 */
+#define RT_PLANAR_REACH 16.0
+typedef struct RtQuads {
+    uint32_t n;
+    const float* q;        /* [3n] corner Q */
+    const float* u;        /* [3n] edge vectors: the quad is Q + a u + b v, 0 <= a,b <= 1; */
+    const float* v;        /* [3n] the triangle has the corners Q, Q+u, Q+v (a,b >= 0, a+b <= 1) */
+    const uint8_t* kind;   /* [n] RtPlanarKind */
+    const uint32_t* mat;   /* [n] index into the material table of the uploaded scene */
+} RtQuads;
+/* The planar primitives of every following render of `ctx`, after rt_scene_upload (RT_ERR_STATE before); rt_scene_upload clears them.
+ * NULL or n 0: the renderer without planar primitives, bit for bit, with the upload's search structures back.  A set selects the
+ * general kernels in their planar instantiations (no sphere grid, no candidate lists) and builds the tree over the scene's entries
+ * and the set.  RT_ERR_INVALID (a non-finite component, a kind outside the enum, a material index out of range, a degenerate or
+ * ill-conditioned u, v, more entries than the tree indexes) or RT_ERR_UNSUPPORTED: the previous set stays.  A device-side failure
+ * (RT_ERR_NOMEM, RT_ERR_DEVICE) while a set replaces another leaves the context WITHOUT planar primitives, not with the previous set.
+ * The arrays are copied. */
+int rt_set_quads(RtCtx* ctx, const RtQuads* quads);
+
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the
  * world shared read-only (main.rs:72-108); here the scene is replicated on every device, device r renders the image
@@ -396,6 +438,9 @@ int rt_multi_set_lens(RtMulti* m, const RtLens* lens);
 /* rt_set_motion on every device.  An invalid motion is refused by the first device and none has changed; a device-side failure
  * (RT_ERR_NOMEM, RT_ERR_DEVICE) on a later device leaves every device with NO motion (the static renderer), not the previous one. */
 int rt_multi_set_motion(RtMulti* m, const RtMotion* motion);
+/* rt_set_quads on every device, all or none as rt_multi_set_motion: a refusal comes from the first device and none has changed; a
+ * device-side failure on a later device leaves every device WITHOUT planar primitives. */
+int rt_multi_set_quads(RtMulti* m, const RtQuads* quads);
 /* The de-interleave step on its own: `d_gathered` is a DEVICE buffer of n_shards band buffers, each
  * max_r rt_shard_rows(ny, band, n_shards, r) rows of nx*3 floats (what the gather delivers); writes the frame in
  * image row order to d_out_rgb_f32 [ny*nx*3] and / or the quantised, flipped image to d_out_rgb8 (device pointers,

@@ -96,6 +96,15 @@ typedef struct RtSceneInfo {
 } RtSceneInfo;
 int rt_debug_scene_info(const RtCtx* ctx, RtSceneInfo* info);
 
+/* The planar primitives of `ctx` (rt_set_quads): how many there are and where the kernels read their plane data — 0: through L2 (the
+ * only placement so far, DESIGN.md "Planar primitives"), 1: staged in LDS.  Either pointer may be NULL. */
+int rt_debug_planar_info(const RtCtx* ctx, uint32_t* n_planar, uint32_t* plane_data_in_lds);
+/* The culling bounds rt_set_quads gives the primitives of `quads` (host code only: no context, no GPU; the same function rt_set_quads
+ * calls), for tests of their derivation.  `world_mag` = the largest coordinate magnitude of the scene's bounds the set is attached to
+ * (0: the set alone); the set's own corners are added to it.  box[6 n] = the box of the corners grown by slack[i] (min xyz, max xyz),
+ * before the tree's own pad; slack[n] as rtow_mi355x.h states it.  RT_ERR_INVALID where rt_set_quads would refuse the geometry. */
+int rt_debug_planar_bounds(const RtQuads* quads, float world_mag, float* box, float* slack);
+
 /* The uniform grid rt_scene_upload would build over the spheres of `scene` (host code only: no context, no GPU), for tests of
  * its construction.  cell_per_mille as RT_OPT_GRID_CELL (0 = default), lds_budget in bytes (0 = 80 KiB, two workgroups per CU).
  * Returns RT_ERR_UNSUPPORTED when the scene gets no grid, RT_ERR_INVALID when a buffer is too small (the needed sizes are

@@ -13,6 +13,7 @@ GPU_LIB_PATH = os.environ.get("RTOW_GPU_LIB") or os.path.join(_PKG_DIR, "librtow
 HOST_LIB_PATH = os.path.join(_PKG_DIR, "librtow_host.so")
 
 RT_NO_TEX = 0xFFFFFFFF
+ERR_INVALID, ERR_DEVICE, ERR_NOMEM, ERR_UNSUPPORTED, ERR_STATE = 1, 2, 3, 4, 5  # magnitudes of the negative RT_ERR_* codes
 FLAG_BRUTE_FORCE = 1
 FLAG_RUSSIAN_ROULETTE = 2
 FLAG_TIME_DEPTHS = 4
@@ -80,6 +81,18 @@ class RtMotion(C.Structure):
                 ("shutter_open", C.c_float), ("shutter_close", C.c_float)]
 
 
+class RtQuads(C.Structure):
+    """rt_set_quads: planar primitive i is the quad Q + a u + b v (kind 0) or the triangle Q, Q + u, Q + v (kind 1) with material
+    mat[i] of the uploaded scene; it is primitive n_spheres + n_rects + n_media + i."""
+    _fields_ = [("n", C.c_uint32), ("q", C.POINTER(C.c_float)), ("u", C.POINTER(C.c_float)), ("v", C.POINTER(C.c_float)),
+                ("kind", C.POINTER(C.c_uint8)), ("mat", C.POINTER(C.c_uint32))]
+
+
+PLANAR_QUAD, PLANAR_TRIANGLE = 0, 1
+PLANAR_MIN_SIN2 = 2.0 ** -20
+PLANAR_REACH = 16.0
+
+
 class RtParams(C.Structure):
     _fields_ = [("nx", C.c_uint32), ("ny", C.c_uint32), ("spp", C.c_uint32), ("max_depth", C.c_int32),
                 ("seed", C.c_uint64), ("shard_band", C.c_uint32), ("shard_count", C.c_uint32),
@@ -137,13 +150,15 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_get_depth_timings", "rt_set_progress", "rt_host_alloc", "rt_host_free", "rt_debug_set_option", "rt_debug_get_option",
                "rt_debug_scene_info", "rt_debug_grid_build", "rt_debug_world_bounds", "rt_debug_render_parts", "rt_multi_create", "rt_multi_create_ex", "rt_multi_destroy", "rt_multi_device_count",
                "rt_multi_last_error", "rt_multi_scene_upload", "rt_multi_render", "rt_deinterleave_bands", "rt_set_lens", "rt_multi_set_lens",
-               "rt_set_motion", "rt_multi_set_motion", "rt_debug_motion_bounds"]
+               "rt_set_motion", "rt_multi_set_motion", "rt_debug_motion_bounds",
+               "rt_set_quads", "rt_multi_set_quads", "rt_debug_planar_info", "rt_debug_planar_bounds"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
                 "rth_sphere", "rth_rect", "rth_gbox", "rth_translate", "rth_rotate_y", "rth_constant_medium", "rth_hitable_bbox", "rth_set_sky", "rth_set_camera", "rth_scene_finish", "rth_scene_flat",
                 "rth_scene_camera", "rth_scene_sphere_name", "rth_scene_free", "rth_png_write", "rth_output_file_name",
                 "rth_set_camera_lens", "rth_scene_lens",
-                "rth_moving_sphere", "rth_set_camera_shutter", "rth_scene_motion"]
+                "rth_moving_sphere", "rth_set_camera_shutter", "rth_scene_motion",
+                "rth_quad", "rth_triangle", "rth_scene_quads"]
 
 _gpu_lib = None
 _host_lib = None
@@ -206,6 +221,14 @@ def load_gpu_library():
     lib.rt_debug_motion_bounds.argtypes = [vp, vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.c_float * 6, C.c_uint32 * 3, vp, vp, C.c_uint32,
                                            C.POINTER(C.c_uint32)]
     lib.rt_debug_motion_bounds.restype = C.c_int
+    lib.rt_set_quads.argtypes = [vp, C.POINTER(RtQuads)]
+    lib.rt_set_quads.restype = C.c_int
+    lib.rt_multi_set_quads.argtypes = [vp, C.POINTER(RtQuads)]
+    lib.rt_multi_set_quads.restype = C.c_int
+    lib.rt_debug_planar_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.rt_debug_planar_info.restype = C.c_int
+    lib.rt_debug_planar_bounds.argtypes = [C.POINTER(RtQuads), C.c_float, vp, vp]
+    lib.rt_debug_planar_bounds.restype = C.c_int
     lib.rt_host_alloc.argtypes = [C.c_size_t]
     lib.rt_host_alloc.restype = vp
     lib.rt_host_free.argtypes = [vp]
@@ -306,6 +329,12 @@ def load_host_library():
     lib.rth_set_camera_shutter.restype = C.c_int
     lib.rth_scene_motion.argtypes = [vp, C.POINTER(RtMotion)]
     lib.rth_scene_motion.restype = C.c_int
+    lib.rth_quad.argtypes = [vp, f3, f3, f3, C.c_uint32]
+    lib.rth_quad.restype = C.c_uint32
+    lib.rth_triangle.argtypes = [vp, f3, f3, f3, C.c_uint32]
+    lib.rth_triangle.restype = C.c_uint32
+    lib.rth_scene_quads.argtypes = [vp, C.POINTER(RtQuads)]
+    lib.rth_scene_quads.restype = C.c_int
     lib.rth_scene_sphere_name.argtypes = [vp, C.c_uint32]
     lib.rth_scene_sphere_name.restype = C.c_char_p
     lib.rth_scene_free.argtypes = [vp]

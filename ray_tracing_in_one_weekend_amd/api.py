@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import RtBounceIO, RtCamera, RtFlatScene, RtLens, RtMotion, RtParams, RtStats
+from ._ffi import RtBounceIO, RtCamera, RtFlatScene, RtLens, RtMotion, RtParams, RtQuads, RtStats
 
 
 class RtError(RuntimeError):
@@ -47,6 +47,47 @@ def _motion_ptr(motion):
     if not isinstance(motion, RtMotion):
         motion = make_motion(*motion)
     return C.byref(motion)
+
+
+def make_quads(q, u, v, kind, mat):
+    """An RtQuads (with its arrays kept alive on it) from corners Q [n, 3], edge vectors u, v [n, 3], kinds [n] (0 quad, 1 triangle) and
+    material indices [n] of the uploaded scene."""
+    qa = np.ascontiguousarray(q, dtype=np.float32).reshape(-1)
+    ua = np.ascontiguousarray(u, dtype=np.float32).reshape(-1)
+    va = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+    ka = np.ascontiguousarray(kind, dtype=np.uint8).ravel()
+    ma = np.ascontiguousarray(mat, dtype=np.uint32).ravel()
+    n = ka.size
+    if not (qa.size == ua.size == va.size == 3 * n and ma.size == n):
+        raise RtError("make_quads: q, u, v must hold three floats and kind, mat one entry per primitive")
+    fp = C.POINTER(C.c_float)
+    s = RtQuads(n, qa.ctypes.data_as(fp), ua.ctypes.data_as(fp), va.ctypes.data_as(fp), ka.ctypes.data_as(C.POINTER(C.c_uint8)),
+                ma.ctypes.data_as(C.POINTER(C.c_uint32)))
+    s._keep = (qa, ua, va, ka, ma)
+    return s
+
+
+def _quads_ptr(quads):
+    """None -> NULL (no planar primitives); an RtQuads (Scene.quads, make_quads) -> a pointer to it"""
+    if quads is None:
+        return None
+    if not isinstance(quads, RtQuads):
+        quads = make_quads(*quads)
+    return C.byref(quads)
+
+
+def planar_bounds(quads, world_mag=0.0):
+    """rt_debug_planar_bounds (host code, no GPU): (box [n, 6], slack [n]) — the leaf box of every primitive before the tree's pad and
+    the slack it was grown by."""
+    lib = _ffi.load_gpu_library()
+    if not isinstance(quads, RtQuads):
+        quads = make_quads(*quads)
+    box = np.zeros((quads.n, 6), np.float32)
+    slack = np.zeros(quads.n, np.float32)
+    rc = lib.rt_debug_planar_bounds(C.byref(quads), C.c_float(world_mag), box.ctypes.data, slack.ctypes.data)
+    if rc != 0:
+        raise RtError("rt_debug_planar_bounds", rc)
+    return box, slack
 
 
 class Scene:
@@ -104,6 +145,15 @@ class Scene:
     def moving_sphere(self, c0, c1, r, material, name=""):
         """A sphere whose centre moves linearly from c0 (time 0) to c1 (time 1): motion blur.  Only at the top level of the world."""
         return self._check(self._lib.rth_moving_sphere(self._h, _f3(c0), _f3(c1), C.c_float(r), material, name.encode()))
+
+    def quad(self, q, u, v, material):
+        """The parallelogram Q + a u + b v, 0 <= a, b <= 1 ("The Next Week" ch. 6).  Only at the top level of the world; it becomes an entry
+        of Scene.quads."""
+        return self._check(self._lib.rth_quad(self._h, _f3(q), _f3(u), _f3(v), material))
+
+    def triangle(self, a, b, c, material):
+        """The triangle with the corners a, b, c, stored as Q = a, u = b - a, v = c - a.  Only at the top level of the world."""
+        return self._check(self._lib.rth_triangle(self._h, _f3(a), _f3(b), _f3(c), material))
 
     def rect(self, axis, mn, mx, material):
         return self._check(self._lib.rth_rect(self._h, axis, _f3(mn), _f3(mx), material))
@@ -190,6 +240,16 @@ class Scene:
             raise RtError("scene not finished")
         m._keep = self
         return m
+
+    @property
+    def quads(self):
+        """RtQuads of the scene (rth_scene_quads): its planar primitives; n 0 for a scene without any.  It points into the scene.
+        Renderer.upload does not apply it: pass it to set_quads."""
+        s = RtQuads()
+        if self._lib.rth_scene_quads(self._h, C.byref(s)) != 0:
+            raise RtError("scene not finished")
+        s._keep = self
+        return s
 
     def sphere_name(self, i):
         return self._lib.rth_scene_sphere_name(self._h, i).decode()
@@ -352,7 +412,13 @@ class Renderer:
         rc = self._lib.rt_debug_scene_info(self._ctx, C.byref(info))
         if rc != 0:
             self._raise("rt_debug_scene_info", rc)
-        return info.as_dict()
+        d = info.as_dict()
+        n, lds = C.c_uint32(0), C.c_uint32(0)
+        rc = self._lib.rt_debug_planar_info(self._ctx, C.byref(n), C.byref(lds))
+        if rc != 0:
+            self._raise("rt_debug_planar_info", rc)
+        d["n_planar"], d["plane_data_in_lds"] = n.value, lds.value  # (rt_set_quads: the count, and LDS or L2 for the plane data)
+        return d
 
     def shard_rows(self, params):
         return self._lib.rt_shard_rows(params.ny, params.shard_band or 1, params.shard_count, params.shard_id)
@@ -425,6 +491,13 @@ class Renderer:
         if rc != 0:
             self._raise("rt_set_motion", rc)
         self._n_moving = motion.n_moving if motion is not None else 0  # (motion_bounds sizes its cell table by it)
+
+    def set_quads(self, quads):
+        """rt_set_quads: the planar primitives (quads, triangles) of the following renders — Scene.quads, make_quads(..) or a
+        (q, u, v, kind, mat) tuple; None: none.  After upload(); upload() clears them.  Not together with set_motion."""
+        rc = self._lib.rt_set_quads(self._ctx, _quads_ptr(quads))
+        if rc != 0:
+            self._raise("rt_set_quads", rc)
 
     def motion_bounds(self):
         """rt_debug_motion_bounds as a dict: the bounds set_motion built (padded entry boxes, candidate-list spheres, entry ids, the
@@ -611,6 +684,12 @@ class MultiRenderer:
         rc = self._lib.rt_multi_set_motion(self._m, _motion_ptr(motion))
         if rc != 0:
             self._raise("rt_multi_set_motion", rc)
+
+    def set_quads(self, quads):
+        """rt_multi_set_quads: Renderer.set_quads on every device."""
+        rc = self._lib.rt_multi_set_quads(self._m, _quads_ptr(quads))
+        if rc != 0:
+            self._raise("rt_multi_set_quads", rc)
 
     def render(self, camera, params, want_rgb8=False):
         """Returns (f32 image [ny, nx, 3] (row 0 = bottom), rgb8 or None, RtStats summed over the devices)."""

@@ -91,6 +91,7 @@ struct RtCtx {
         bool use_bvh = false, bvh_in_lds = false, general_lds = false, use_grid = false;
         size_t isect_lds = 0, grid_lds = 0;
         GridParams grid{};
+        bool general_kernels = false;
     } static_search;
     struct Keep {
         std::vector<float4> geo;         // spheres (c0, r)
@@ -99,7 +100,20 @@ struct RtCtx {
         std::vector<float4> ent_bs;
         std::vector<uint8_t> bare;       // per sphere: no wrapper, not a medium boundary
         uint32_t bvh_depth = 0;
+        // rt_set_quads: what the records and sort keys of planar primitives are made of, and the static ones they are appended to
+        std::vector<MatRec> mats;
+        std::vector<TexRec> texs;
+        std::vector<float4> srec;        // 5 per world entry
+        std::vector<uint8_t> raw_class;  // per world entry, before the ranking of the classes present
+        uint32_t sky_type = 0;
+        double world_mag = 0.0;          // largest coordinate magnitude of the world entries' bounds
     } keep;
+    // rt_set_quads.  As with the motion, the active search state is rebuilt over the scene's entries AND the set, in a region of its
+    // own; clearing the set puts static_search back.
+    bool planar = false;           // the PLANAR instantiations (n > 0)
+    GenPlanar gplanar{};           // (pq in quads_region)
+    double planar_reach = 0.0;     // RT_PLANAR_REACH W of the set: the leaf slack holds for ray origins within it (render_impl checks the camera)
+    DevBuf quads_region;
     bool motion = false;           // the MOTION instantiations (n_moving > 0)
     GenMotion gmotion{};           // (sph_dc in motion_region)
     size_t motion_lds = 0;         // 16 B per sphere beside the geometry where it is staged in LDS
@@ -303,6 +317,7 @@ struct StepBuffers {
     const GenParams* gpd;
     bool lens = false; // depth 0 through the thin lens (the LENS instantiations)
     bool motion = false; // moving spheres (the MOTION instantiations)
+    bool planar = false; // planar primitives (the PLANAR instantiations)
 };
 bool scene_is_general(const RtCtx* ctx) { return ctx->general_kernels; }
 bool grid_enabled(const RtCtx* ctx) { return ctx->use_grid && ctx->opt[RT_OPT_GRID] != 1u && !scene_is_general(ctx); }
@@ -317,6 +332,34 @@ void launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32
         else if (b.motion) hipLaunchKernelGGL(k_intersect_grid_motion<false>, dim3(grid), dim3(RT_BVH_BLOCK), mlds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
         else if (ctx->grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid<true>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->grid_lds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
         else hipLaunchKernelGGL(k_intersect_grid<false>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->grid_lds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
+        return;
+    }
+    if (b.planar && use_bvh) {
+        // planar primitives (rt_set_quads): the general kernel in its NEST form (loops over wrapper chains and media: the same bits
+        // for a scene that needs none), so one instantiation per tree placement, table placement and depth-0 form
+#define RT_LAUNCH_ISECT_P(G, N, T, L)                                                                                                     \
+    hipLaunchKernelGGL((k_intersect<RT_BVH_BLOCK, G, true, N, T, true, L, false, true>), dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg, \
+                       ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd)
+#define RT_LAUNCH_ISECT_PT(G, N, L)                          \
+    do {                                                     \
+        if (ctx->general_lds) RT_LAUNCH_ISECT_P(G, N, true, L); \
+        else RT_LAUNCH_ISECT_P(G, N, false, L);              \
+    } while (0)
+#define RT_LAUNCH_ISECT_PN(G, L)                             \
+    do {                                                     \
+        if (ctx->bvh_in_lds) RT_LAUNCH_ISECT_PT(G, true, L); \
+        else RT_LAUNCH_ISECT_PT(G, false, L);                \
+    } while (0)
+        if (gen && b.lens) RT_LAUNCH_ISECT_PN(true, true);
+        else if (gen) RT_LAUNCH_ISECT_PN(true, false);
+        else RT_LAUNCH_ISECT_PN(false, false);
+#undef RT_LAUNCH_ISECT_PN
+#undef RT_LAUNCH_ISECT_PT
+#undef RT_LAUNCH_ISECT_P
+        return;
+    }
+    if (b.planar) {
+        hipLaunchKernelGGL(k_intersect_list_planar, dim3(ip.q1 - ip.q0), dim3(256), 0, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
         return;
     }
 #define RT_LAUNCH_ISECT_M(G, R, N, T, X, L)                                                                                      \
@@ -366,7 +409,23 @@ void launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32
     const bool rects = scene_is_general(ctx), perlin_lds = scene_perlin_lds(ctx);
     // sphere geometry for the closest hit inside k_shade<GEN>
     const uint32_t n_fused = (gen && fused_lists) ? ctx->ds.n_spheres * (b.motion ? 2u : 1u) : 0u; // (MOTION: the displacements behind the geometry)
-    const size_t shade_lds = shade_lds_bytes(ctx->ds.n_prims + ctx->ds.n_media, perlin_lds ? ctx->ds.n_perlin : 0u, n_fused, !gen && sp.sort);
+    const size_t shade_lds = shade_lds_bytes(ctx->ds.n_prims + ctx->ds.n_media + (b.planar ? ctx->gplanar.n : 0u), perlin_lds ? ctx->ds.n_perlin : 0u, n_fused, !gen && sp.sort);
+    if (b.planar) { // (general, NEST: launch_intersect)
+#define RT_LAUNCH_SHADE_P(P, G, L)                                                                                                          \
+    hipLaunchKernelGGL((k_shade<P, G, true, true, L, false, true>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, \
+                       b.cout, b.rad, sp, b.totals, b.gpd)
+#define RT_LAUNCH_SHADE_PP(G, L)                   \
+    do {                                           \
+        if (perlin_lds) RT_LAUNCH_SHADE_P(true, G, L); \
+        else RT_LAUNCH_SHADE_P(false, G, L);       \
+    } while (0)
+        if (gen && b.lens) RT_LAUNCH_SHADE_PP(true, true);
+        else if (gen) RT_LAUNCH_SHADE_PP(true, false);
+        else RT_LAUNCH_SHADE_PP(false, false);
+#undef RT_LAUNCH_SHADE_PP
+#undef RT_LAUNCH_SHADE_P
+        return;
+    }
 #define RT_LAUNCH_SHADE_M(P, G, R, X, L)                                                                                                       \
     hipLaunchKernelGGL((k_shade<P, G, R, X, L, true>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, b.cout, b.rad, \
                        sp, b.totals, b.gpd)
@@ -740,11 +799,11 @@ void world_bounds(const RtFlatScene* s, WorldBounds& w) {
 // exactly as a larger scene does (tree through L2, no grid).  The grid's arrays go through upload() into the current region.
 int configure_search(RtCtx* ctx, uint32_t bvh_depth, const std::vector<float4>& geo, const std::vector<float4>* dc) {
     const DevScene& ds = ctx->ds;
-    const uint32_t n_entries = ds.n_prims + ds.n_media;
+    const uint32_t n_entries = ds.n_prims + ds.n_media + ctx->gplanar.n; // (rt_set_quads: the planar primitives behind the media)
     const size_t extra = dc ? (size_t)ds.n_spheres * sizeof(float4) : 0u;
     // k_intersect keeps nodes + geometry + one u16 stack column per lane in LDS when that fits 160 KB;
     // larger trees are traversed out of HBM/L2 with only the stacks in LDS; the list walk is the last resort
-    const bool bvh_ok = ds.n_prims > 0 && ds.n_bvh4_nodes > 0 && ds.n_bvh4_nodes < 32768 && n_entries <= 32768 &&
+    const bool bvh_ok = (ds.n_prims > 0 || ctx->gplanar.n > 0) && ds.n_bvh4_nodes > 0 && ds.n_bvh4_nodes < 32768 && n_entries <= 32768 &&
                         bvh_depth <= RT_BVH_MAX_DEPTH;
     const bool force_hbm = ctx->opt[RT_OPT_TREE_PLACEMENT] == 1u; // test hook: traverse out of HBM even when LDS would fit
     // General scenes (wrappers, rectangles, media): the tree goes to LDS only when TWO workgroups per CU still fit.  Their
@@ -753,7 +812,7 @@ int configure_search(RtCtx* ctx, uint32_t bvh_depth, const std::vector<float4>& 
     // with tree AND wrapper tables in LDS and one (profiles/round3/final_like.txt) — which is also why final_scene's tree was
     // not squeezed into LDS with quantised boxes: 1 150 nodes x 48 B + 56 KB of stacks leave room for one workgroup only.
     // Sphere-only scenes keep their faster LDS-only kernel (sorted slab planes) even at one workgroup per CU.
-    const bool general = ds.n_rects > 0 || ds.n_xforms > 0 || ds.n_media > 0 || ctx->opt[RT_OPT_GENERAL_KERNELS] == 1u;
+    const bool general = ds.n_rects > 0 || ds.n_xforms > 0 || ds.n_media > 0 || ctx->gplanar.n > 0 || ctx->opt[RT_OPT_GENERAL_KERNELS] == 1u;
     ctx->general_kernels = general;
     const size_t lds_budget = general ? ctx->lds_limit / 2 : ctx->lds_limit;
     ctx->bvh_in_lds = bvh_ok && bvh_lds_bytes(ds, RT_BVH_BLOCK, true) + extra <= lds_budget && !force_hbm;
@@ -888,6 +947,21 @@ int rt_ctx_create(int device_id, RtCtx** out_ctx) {
             reinterpret_cast<const void*>(&k_intersect_grid_motion<true>), reinterpret_cast<const void*>(&k_intersect_grid_motion<false>),
             reinterpret_cast<const void*>(&k_debug_bounce_motion<RT_BVH_BLOCK, true, true>),
             reinterpret_cast<const void*>(&k_debug_bounce_motion<RT_BVH_BLOCK, true, false>),
+            // the instantiations of planar primitives (rt_set_quads): every one launch_intersect / launch_shade can pick
+#define RT_ISECT_PLANAR(N, T)                                                                                   \
+    reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, false, true, N, T, true, false, false, true>),     \
+        reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, true, true, N, T, true, false, false, true>),  \
+        reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, true, true, N, T, true, true, false, true>)
+            RT_ISECT_PLANAR(true, true), RT_ISECT_PLANAR(true, false), RT_ISECT_PLANAR(false, true), RT_ISECT_PLANAR(false, false),
+#undef RT_ISECT_PLANAR
+#define RT_SHADE_PLANAR(P)                                                                   \
+    reinterpret_cast<const void*>(&k_shade<P, false, true, true, false, false, true>),       \
+        reinterpret_cast<const void*>(&k_shade<P, true, true, true, false, false, true>),    \
+        reinterpret_cast<const void*>(&k_shade<P, true, true, true, true, false, true>)
+            RT_SHADE_PLANAR(true), RT_SHADE_PLANAR(false),
+#undef RT_SHADE_PLANAR
+            reinterpret_cast<const void*>(&k_debug_bounce_planar<RT_BVH_BLOCK, true, true>),
+            reinterpret_cast<const void*>(&k_debug_bounce_planar<RT_BVH_BLOCK, true, false>),
         };
         for (const void* fn : variants)
             if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_limit)) != hipSuccess)
@@ -917,6 +991,7 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->acc), free_buf(ctx->counts), free_buf(ctx->totals);
     free_buf(ctx->out_f32), free_buf(ctx->out_u8), free_buf(ctx->dbg), free_buf(ctx->genp);
     free_buf(ctx->preview_u8), free_buf(ctx->lists);
+    free_buf(ctx->motion_region), free_buf(ctx->quads_region);
     for (auto ev : ctx->events) (void)hipEventDestroy(ev);
     for (auto ev : ctx->depth_events) (void)hipEventDestroy(ev);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
@@ -1247,6 +1322,7 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
     for (int pass = 0; pass < 2; ++pass)
         for (uint32_t c = 0; c < RT_NCLASS; ++c)
             if (class_present[c] && class_is_light(c, s->sky_type) == (pass == 0)) class_key[c] = n_keys++;
+    const std::vector<uint8_t> raw_class = sclass; // (rt_set_quads ranks the classes again with those of its primitives)
     for (uint32_t i = 0; i < n_entries; ++i) sclass[i] = (uint8_t)class_key[sclass[i]];
 
     HostBvh4 bvh4;
@@ -1322,13 +1398,20 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
         ctx->keep.bare.assign(s->n_spheres, 0);
         for (uint32_t i = 0; i < s->n_spheres; ++i) ctx->keep.bare[i] = pxf[i] == RT_NO_XFORM && pmed[i] == RT_NO_MEDIUM;
         ctx->keep.bvh_depth = bvh.depth;
+        ctx->keep.mats = mats, ctx->keep.texs = texs, ctx->keep.srec = srec, ctx->keep.raw_class = raw_class, ctx->keep.sky_type = s->sky_type;
+        ctx->keep.world_mag = 0.0;
+        for (const PrimBox& b : eboxes)
+            for (int k = 0; k < 3; ++k)
+                if (std::isfinite(b.mn[k]) && std::isfinite(b.mx[k])) ctx->keep.world_mag = std::max(ctx->keep.world_mag, (double)std::max(std::fabs(b.mn[k]), std::fabs(b.mx[k])));
+        ctx->planar = false, ctx->gplanar = GenPlanar{};
         ctx->motion = false, ctx->motion_lds = 0, ctx->gmotion = GenMotion{}, ctx->motion_dbg = RtCtx::MotionDebug{};
     }
     if ((rc = configure_search(ctx, bvh.depth, geo, nullptr))) {
         free_scene(ctx);
         return rc;
     }
-    ctx->static_search = RtCtx::Search{ctx->ds, ctx->use_bvh, ctx->bvh_in_lds, ctx->general_lds, ctx->use_grid, ctx->isect_lds, ctx->grid_lds, ctx->grid};
+    ctx->static_search = RtCtx::Search{ctx->ds, ctx->use_bvh, ctx->bvh_in_lds, ctx->general_lds, ctx->use_grid, ctx->isect_lds, ctx->grid_lds, ctx->grid,
+                                       ctx->general_kernels};
     return RT_OK;
 }
 
@@ -1385,6 +1468,13 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
                        void* stream_v, RtStats* stats, float* h_out_f32 = nullptr, uint8_t* h_out_u8 = nullptr) {
     int rc = check_params(ctx, cam, prm);
     if (rc) return rc;
+    if (ctx->planar) { // the leaf slack of the set is derived for ray origins within RT_PLANAR_REACH W: the eye (and its lens) must lie there
+        const double lens_r = ctx->lens.lens_radius > 0.0f ? (double)ctx->lens.lens_radius : 0.0;
+        for (int k = 0; k < 3; ++k)
+            if (!(std::fabs((double)cam->origin[k]) + lens_r <= ctx->planar_reach))
+                return fail(ctx, RT_ERR_UNSUPPORTED, "render: the camera lies outside RT_PLANAR_REACH x W = " + std::to_string(ctx->planar_reach) +
+                                                         " of the scene with its planar primitives (rtow_mi355x.h): the culling bound of rt_set_quads does not cover it");
+    }
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream_v ? (hipStream_t)stream_v : ctx->stream;
     const auto wall0 = std::chrono::steady_clock::now();
@@ -1411,7 +1501,8 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     // 46.7 -> 41.9 ms, pbr_sweep_scene 41.2 -> 39.3, test_sphere 15.5 -> 14.8, cornell_box unchanged (its walls'
     // bounding spheres cover every pixel: overflow); final_scene (3 408 entries, most pixels overflow) would pay
     // 3 ms for nothing, hence the cap.
-    const bool want_lists = use_bvh && fuse_gen && spp >= 4 && ctx->ds.n_entries > 0 && ctx->ds.n_entries <= 2048 && ctx->opt[RT_OPT_PRIMARY_LISTS] != 1u;
+    const bool want_lists = use_bvh && fuse_gen && spp >= 4 && ctx->ds.n_entries > 0 && ctx->ds.n_entries <= 2048 && ctx->opt[RT_OPT_PRIMARY_LISTS] != 1u &&
+                            !ctx->planar; // (the lists know the static entries only)
 
     // the small persistent buffers first (they lie at the bottom of the pool); the work buffers of the slices start above them
     ctx->pool.chunk_delay_us.store(ctx->opt[RT_OPT_POOL_CHUNK_DELAY_US]);
@@ -1420,7 +1511,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     if ((rc = ensure(ctx, ctx->counts, counts_bytes))) return rc;
     const size_t totals_bytes = (size_t)(n_depths + 2) * sizeof(unsigned long long);
     if ((rc = ensure(ctx, ctx->totals, totals_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_MOTION_OFFSET + sizeof(GenMotion)))) return rc; // (the lens and the motion behind the params: gen_lens_of, gen_motion_of)
+    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_PLANAR_OFFSET + sizeof(GenPlanar)))) return rc; // (the lens, the motion and the planar set behind the params: gen_lens_of, gen_motion_of, gen_planar_of)
     if (want_lists &&(rc = ensure(ctx, ctx->lists, ((size_t)npix + 1u) * sizeof(uint4)))) return rc; // + the overflow counter behind the lists
     GenParams* gpd = (GenParams*)ctx->genp.p;
     float* acc = (float*)ctx->acc.p;
@@ -1573,6 +1664,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
         gp.n_rays = npix * sc;
         RT_HIP(ctx, hipMemsetAsync(counts, 0, counts_bytes, st));
         if (ctx->motion) hipLaunchKernelGGL(k_set_motion, dim3(1), dim3(64), 0, st, gpd, ctx->gmotion);
+        if (ctx->planar) hipLaunchKernelGGL(k_set_planar, dim3(1), dim3(64), 0, st, gpd, ctx->gplanar);
         if (lens) hipLaunchKernelGGL(k_init_counts<true>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, gpd, glens);
         else hipLaunchKernelGGL(k_init_counts<false>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, gpd, glens);
         if (!fuse_gen && lens) hipLaunchKernelGGL(k_gen_primary<true>, dim3((gp.n_rays + 255u) / 256u), dim3(256), 0, st, gp, Q[0], glens);
@@ -1599,7 +1691,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
             const bool gen = fuse_gen && depth == 0;
             ip.depth = depth;
             ip.q0 = q0, ip.q1 = q1;
-            const StepBuffers sb{qi, qo, qhit, cin, cout, rad, totals, gpd, lens, ctx->motion};
+            const StepBuffers sb{qi, qo, qhit, cin, cout, rad, totals, gpd, lens, ctx->motion, ctx->planar};
             // depth 0 of a sphere-only scene whose pixels all have a candidate list: k_shade<GEN> finds every closest hit itself
             const bool no_primary_trace = gen && !rects && gp.lists != nullptr && no_overflow;
             if (!no_primary_trace) launch_intersect(ctx, sg, use_bvh, gen, isect_grid_g, sb, ip);
@@ -1920,7 +2012,8 @@ int rt_set_lens(RtCtx* ctx, const RtLens* lens) {
 static void restore_static_search(RtCtx* ctx) {
     const RtCtx::Search& st = ctx->static_search;
     ctx->ds = st.ds, ctx->use_bvh = st.use_bvh, ctx->bvh_in_lds = st.bvh_in_lds, ctx->general_lds = st.general_lds, ctx->use_grid = st.use_grid;
-    ctx->isect_lds = st.isect_lds, ctx->grid_lds = st.grid_lds, ctx->grid = st.grid;
+    ctx->isect_lds = st.isect_lds, ctx->grid_lds = st.grid_lds, ctx->grid = st.grid, ctx->general_kernels = st.general_kernels;
+    ctx->planar = false, ctx->gplanar = GenPlanar{};
     ctx->motion = false, ctx->motion_lds = 0, ctx->gmotion = GenMotion{}, ctx->motion_dbg = RtCtx::MotionDebug{};
 }
 
@@ -1948,6 +2041,7 @@ int rt_set_motion(RtCtx* ctx, const RtMotion* motion) {
         }
         return RT_OK;
     }
+    if (ctx->planar) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_set_motion: the context holds planar primitives (rt_set_quads); the two do not combine yet");
     const uint32_t n_sph = ctx->static_search.ds.n_spheres, nm = motion->n_moving;
     if (!motion->sphere || !motion->center1) return fail(ctx, RT_ERR_INVALID, "rt_set_motion: NULL array");
     if (!std::isfinite(motion->shutter_open) || !std::isfinite(motion->shutter_close) || motion->shutter_open < 0.0f ||
@@ -2107,6 +2201,226 @@ int rt_debug_motion_bounds(const RtCtx* ctx, float* entry_box_padded, float* ent
     return fits && cells_fit ? RT_OK : RT_ERR_INVALID;
 }
 
+// ---- planar primitives (rt_set_quads) --------------------------------------------------------------------------------------------
+// The set-up of rtow_mi355x.h in f32 (this file is built with -ffp-contract=off: one rounding per operation), the box of every
+// primitive's corners and its slack.  DESIGN.md "Planar primitives" derives the slack; in short, for a ray whose origin coordinates
+// stay within RT_PLANAR_REACH W and a primitive with s = sin(u, v) >= 2^-10:
+//   - the plane the kernels test is the f32 (normal, D): tilted against the exact one by <= 3.5 eps / s, i.e. off by <= 7 eps L / s over the figure;
+//   - alpha, beta carry <= 9 eps |p| / (|u| s) of rounding and 3.5 eps / s of scale (w), i.e. <= 22 eps L / s in space for |p| <= 2 L;
+//   - P = fl(o + fl(d t)) and the two dot products of t move the accepted point by <= 16 eps (M + reach) (3 + 2 x 3 sqrt(3) roundings).
+// eps = 2^-24.  The constants are rounded up to 64 and 16; the slack is added in double, rounded outwards, BEFORE pad_prim_box.
+struct PlanarHost {
+    std::vector<float4> pq;     // 5 per primitive (planar_root)
+    std::vector<PrimBox> boxes; // corners + slack
+    std::vector<float> slack;
+    double world_mag = 0.0;     // W: the scene's and the set's largest coordinate magnitude
+};
+static int planar_setup(const RtQuads* q, double world_mag, PlanarHost& out, std::string& err) {
+    const uint32_t n = q->n;
+    if (!q->q || !q->u || !q->v || !q->kind || !q->mat) return err = "NULL array", RT_ERR_INVALID;
+    double W = world_mag;
+    for (size_t k = 0; k < 3 * (size_t)n; ++k) {
+        if (!std::isfinite(q->q[k]) || !std::isfinite(q->u[k]) || !std::isfinite(q->v[k])) return err = "primitive " + std::to_string(k / 3) + " has a component that is not finite", RT_ERR_INVALID;
+        const double a = q->q[k], b = q->u[k], c = q->v[k];
+        W = std::max(W, std::max(std::max(std::fabs(a), std::fabs(a + b)), std::max(std::fabs(a + c), std::fabs(a + b + c))));
+    }
+    out.world_mag = W;
+    out.pq.assign(5 * (size_t)n, make_float4(0.f, 0.f, 0.f, 0.f));
+    out.boxes.resize(n), out.slack.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (q->kind[i] > RT_PLANAR_TRIANGLE) return err = "primitive " + std::to_string(i) + " has a kind outside RtPlanarKind", RT_ERR_INVALID;
+        const float* Q = q->q + 3 * (size_t)i;
+        const float* u = q->u + 3 * (size_t)i;
+        const float* v = q->v + 3 * (size_t)i;
+        {   // conditioning, in double: |n|^2 >= 2^-20 |u|^2 |v|^2
+            const double ud[3] = {u[0], u[1], u[2]}, vd[3] = {v[0], v[1], v[2]};
+            const double nd[3] = {ud[1] * vd[2] - ud[2] * vd[1], ud[2] * vd[0] - ud[0] * vd[2], ud[0] * vd[1] - ud[1] * vd[0]};
+            const double n2 = nd[0] * nd[0] + nd[1] * nd[1] + nd[2] * nd[2], u2 = ud[0] * ud[0] + ud[1] * ud[1] + ud[2] * ud[2], v2 = vd[0] * vd[0] + vd[1] * vd[1] + vd[2] * vd[2];
+            if (!(u2 > 0.0 && v2 > 0.0 && n2 >= RT_PLANAR_MIN_SIN2 * u2 * v2)) return err = "primitive " + std::to_string(i) + " is degenerate or ill-conditioned (|u x v|^2 < 2^-20 |u|^2 |v|^2)", RT_ERR_INVALID;
+            const double L = std::sqrt(std::max(u2, v2)), sn = std::sqrt(n2 / (u2 * v2));
+            double M = 0.0, lo[3], hi[3];
+            for (int k = 0; k < 3; ++k) {
+                const double c0 = Q[k], c1 = c0 + ud[k], c2 = c0 + vd[k], c3 = c0 + ud[k] + vd[k];
+                lo[k] = std::min(std::min(c0, c1), c2), hi[k] = std::max(std::max(c0, c1), c2);
+                if (q->kind[i] == RT_PLANAR_QUAD) lo[k] = std::min(lo[k], c3), hi[k] = std::max(hi[k], c3);
+                M = std::max(M, std::max(std::max(std::fabs(c0), std::fabs(c1)), std::max(std::fabs(c2), std::fabs(c3))));
+            }
+            const double slack = std::ldexp(64.0 * L / sn + 16.0 * (M + RT_PLANAR_REACH * W), -24) * (1.0 + 1e-9) + 1e-37;
+            out.slack[i] = round_up(slack);
+            for (int k = 0; k < 3; ++k) out.boxes[i].mn[k] = round_down(lo[k] - slack), out.boxes[i].mx[k] = round_up(hi[k] + slack);
+        }
+        // f32, in the order of the header
+        const float nx = u[1] * v[2] - u[2] * v[1], ny = u[2] * v[0] - u[0] * v[2], nz = u[0] * v[1] - u[1] * v[0];
+        const float nn = (nx * nx + ny * ny) + nz * nz;
+        const float len = std::sqrt(nn);
+        const float ux = nx / len, uy = ny / len, uz = nz / len;
+        const float D = (ux * Q[0] + uy * Q[1]) + uz * Q[2];
+        const float wx = nx / nn, wy = ny / nn, wz = nz / nn;
+        if (!std::isfinite(ux) || !std::isfinite(uy) || !std::isfinite(uz) || !std::isfinite(D) || !std::isfinite(wx) || !std::isfinite(wy) || !std::isfinite(wz) || !(nn > 0.0f))
+            return err = "primitive " + std::to_string(i) + ": the f32 plane set-up overflows or underflows", RT_ERR_INVALID;
+        uint32_t kb = q->kind[i];
+        float kf;
+        std::memcpy(&kf, &kb, 4);
+        out.pq[5 * (size_t)i + 0] = make_float4(ux, uy, uz, D);
+        out.pq[5 * (size_t)i + 1] = make_float4(Q[0], Q[1], Q[2], kf);
+        out.pq[5 * (size_t)i + 2] = make_float4(u[0], u[1], u[2], 0.0f);
+        out.pq[5 * (size_t)i + 3] = make_float4(v[0], v[1], v[2], 0.0f);
+        out.pq[5 * (size_t)i + 4] = make_float4(wx, wy, wz, 0.0f);
+    }
+    return RT_OK;
+}
+
+int rt_debug_planar_bounds(const RtQuads* quads, float world_mag, float* box, float* slack) {
+    if (!quads || !(world_mag >= 0.0f) || !std::isfinite(world_mag)) return RT_ERR_INVALID;
+    PlanarHost ph;
+    std::string err;
+    const int rc = planar_setup(quads, world_mag, ph, err);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < quads->n; ++i) {
+        if (box)
+            for (int k = 0; k < 3; ++k) box[6 * (size_t)i + k] = ph.boxes[i].mn[k], box[6 * (size_t)i + 3 + k] = ph.boxes[i].mx[k];
+        if (slack) slack[i] = ph.slack[i];
+    }
+    return RT_OK;
+}
+
+int rt_debug_planar_info(const RtCtx* ctx, uint32_t* n_planar, uint32_t* plane_data_in_lds) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!ctx->has_scene) return RT_ERR_STATE;
+    if (n_planar) *n_planar = ctx->planar ? ctx->gplanar.n : 0u;
+    if (plane_data_in_lds) *plane_data_in_lds = 0u;
+    return RT_OK;
+}
+
+int rt_set_quads(RtCtx* ctx, const RtQuads* quads) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!ctx->has_scene) return fail(ctx, RT_ERR_STATE, "rt_set_quads: no scene uploaded");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!quads || quads->n == 0) {
+        if (ctx->planar) {
+            RT_HIP(ctx, hipDeviceSynchronize());
+            restore_static_search(ctx);
+        }
+        return RT_OK;
+    }
+    if (ctx->motion) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_set_quads: the context holds a motion (rt_set_motion); the two do not combine yet");
+    const RtCtx::Keep& kp = ctx->keep;
+    const DevScene& sds = ctx->static_search.ds;
+    const uint32_t n = quads->n, base = sds.n_prims + sds.n_media;
+    if ((uint64_t)base + n > 32768u) return fail(ctx, RT_ERR_INVALID, "rt_set_quads: more than 32768 world entries with the set");
+    PlanarHost ph;
+    {
+        std::string err;
+        const int rc = planar_setup(quads, kp.world_mag, ph, err);
+        if (rc) return fail(ctx, rc, "rt_set_quads: " + err);
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        if (quads->mat[i] >= kp.mats.size()) return fail(ctx, RT_ERR_INVALID, "rt_set_quads: primitive " + std::to_string(i) + " has material index out of range");
+        if (kp.mats[quads->mat[i]].type == RT_MAT_DISNEY_METAL)
+            return fail(ctx, RT_ERR_UNSUPPORTED, "rt_set_quads: DisneyMetal on a planar primitive reads a tangent it does not carry");
+    }
+    // ---- records and sort keys: the static ones, then the set's; the classes present are ranked again (rt_scene_upload)
+    auto fbits = [](uint32_t u) {
+        float f;
+        std::memcpy(&f, &u, 4);
+        return f;
+    };
+    std::vector<float4> srec((size_t)(base + n) * 5, make_float4(0.f, 0.f, 0.f, 0.f));
+    std::copy(kp.srec.begin(), kp.srec.begin() + 5 * (size_t)base, srec.begin());
+    std::vector<uint8_t> sclass(kp.raw_class);
+    sclass.resize((size_t)base + n);
+    const uint32_t n_tex = (uint32_t)kp.texs.size();
+    for (uint32_t i = 0; i < n; ++i) {
+        const MatRec& m = kp.mats[quads->mat[i]];
+        const bool has_t0 = mat_needs_tex0(m.type) && m.tex0 < n_tex;
+        const uint32_t tt = has_t0 ? kp.texs[m.tex0].type : 0u;
+        sclass[base + i] = (uint8_t)(1u + m.type * 4u + tt);
+        const size_t r = 5 * (size_t)(base + i);
+        srec[r + 1] = make_float4(fbits(m.type), fbits(tt), fbits(has_t0 ? kp.texs[m.tex0].aux : 0u), fbits(m.tex1));
+        srec[r + 2] = has_t0 ? make_float4(kp.texs[m.tex0].c0r, kp.texs[m.tex0].c0g, kp.texs[m.tex0].c0b, m.p0) : make_float4(m.cr, m.cg, m.cb, m.p0);
+        srec[r + 3] = make_float4(m.p1, m.p2, has_t0 ? kp.texs[m.tex0].scale : 0.0f, fbits(m.tex0));
+    }
+    bool class_present[RT_NCLASS] = {};
+    class_present[0] = true;
+    for (uint8_t c : sclass) class_present[c] = true;
+    uint32_t class_key[RT_NCLASS] = {}, n_keys = 0;
+    for (int pass = 0; pass < 2; ++pass)
+        for (uint32_t c = 0; c < RT_NCLASS; ++c)
+            if (class_present[c] && class_is_light(c, kp.sky_type) == (pass == 0)) class_key[c] = n_keys++;
+    for (uint8_t& c : sclass) c = (uint8_t)class_key[c];
+    // ---- the tree over the scene's entries and the set
+    std::vector<PrimBox> eboxes = kp.eboxes;
+    std::vector<uint32_t> entry_ids = kp.entry_ids;
+    for (uint32_t i = 0; i < n; ++i) eboxes.push_back(ph.boxes[i]), entry_ids.push_back(base + i);
+    HostBvh bvh;
+    build_prim_bvh(eboxes, RT_BVH_MAX_DEPTH, bvh);
+    for (auto& dd : bvh.d) {
+        if (dd.x < 0 && dd.x != INT_MIN) dd.x = ~(int)entry_ids[(size_t)~dd.x];
+        if (dd.y < 0 && dd.y != INT_MIN) dd.y = ~(int)entry_ids[(size_t)~dd.y];
+    }
+    HostBvh4 bvh4;
+    collapse_bvh4(bvh, bvh4);
+    if (bvh4.id.size() >= 32768u || bvh.depth > RT_BVH_MAX_DEPTH) return fail(ctx, RT_ERR_INVALID, "rt_set_quads: the tree over the set has more nodes or levels than the kernels index");
+    // ---- device: nothing may still read the arrays of the set before
+    RT_HIP(ctx, hipDeviceSynchronize());
+    DevScene ds = ctx->static_search.ds;
+    ds.n_bvh4_nodes = (uint32_t)bvh4.id.size();
+    ds.bvh4_depth = bvh4.depth;
+    ds.n_entries = (uint32_t)eboxes.size();
+    ds.key_miss = class_key[0];
+    {
+        double ext2 = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            float lo = FLT_MAX, hi = -FLT_MAX;
+            for (const PrimBox& b : eboxes) lo = std::min(lo, b.mn[k]), hi = std::max(hi, b.mx[k]);
+            if (hi > lo) ext2 += ((double)hi - lo) * ((double)hi - lo);
+        }
+        ds.bvh_exact_eps = (float)(std::sqrt(ext2) / 1024.0);
+    }
+    const float4* d_pq = nullptr;
+    auto upload_all = [&]() -> int {
+        int rc;
+        if ((rc = upload(ctx, ph.pq, &d_pq)) || (rc = upload(ctx, srec, &ds.sph_rec)) || (rc = upload(ctx, sclass, &ds.sph_class)) ||
+            (rc = upload(ctx, bvh4.id, &ds.bvh4_id)) || (rc = upload(ctx, bvh4.p[0], &ds.bvh4_p[0])) || (rc = upload(ctx, bvh4.p[1], &ds.bvh4_p[1])) ||
+            (rc = upload(ctx, bvh4.p[2], &ds.bvh4_p[2])) || (rc = upload(ctx, bvh4.p[3], &ds.bvh4_p[3])) ||
+            (rc = upload(ctx, bvh4.p[4], &ds.bvh4_p[4])) || (rc = upload(ctx, bvh4.p[5], &ds.bvh4_p[5]))) return rc;
+        return RT_OK;
+    };
+    // upload() carves the scene region: for this call the quads region stands in for it (measured first), as in rt_set_motion.  A set
+    // that replaces another is written to the other's region after the synchronize above, while the context still names the old arrays:
+    // on a device error it goes back to the static renderer, not to the previous set.
+    const bool had_set = ctx->planar;
+    const DevBuf scene_region = ctx->scene_region;
+    const size_t scene_used = ctx->scene_used;
+    ctx->scene_measuring = true, ctx->scene_measure = 0;
+    (void)upload_all();
+    ctx->scene_measuring = false;
+    int rc = ensure(ctx, ctx->quads_region, ctx->scene_measure + (1u << 20));
+    if (!rc) {
+        ctx->scene_region = ctx->quads_region, ctx->scene_used = 0;
+        rc = upload_all();
+        ctx->scene_region = scene_region, ctx->scene_used = scene_used;
+    }
+    if (rc) {
+        const std::string err = ctx->err;
+        if (had_set) restore_static_search(ctx);
+        ctx->err = err;
+        return rc;
+    }
+    restore_static_search(ctx);
+    ctx->ds = ds;
+    ctx->gplanar = GenPlanar{d_pq, base, n};
+    ctx->planar = true;
+    ctx->planar_reach = RT_PLANAR_REACH * ph.world_mag;
+    if ((rc = configure_search(ctx, bvh.depth, kp.geo, nullptr))) { // (no grid for a general scene: nothing is uploaded here)
+        const std::string err = ctx->err;
+        restore_static_search(ctx);
+        ctx->err = err;
+        return rc;
+    }
+    return RT_OK;
+}
+
 int rt_get_depth_timings(RtCtx* ctx, uint32_t max_n, float* isect_ms, float* shade_ms, uint64_t* rays) {
     if (!ctx) return RT_ERR_INVALID;
     RT_HIP(ctx, hipSetDevice(ctx->device));
@@ -2133,7 +2447,7 @@ static int debug_bounce_production(RtCtx* ctx, const RtBounceIO* io) {
     int rc;
     if ((rc = ensure(ctx, ctx->counts, (size_t)2 * nq * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(ctx, ctx->totals, 4 * sizeof(unsigned long long)))) return rc;
-    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_MOTION_OFFSET + sizeof(GenMotion)))) return rc;
+    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_PLANAR_OFFSET + sizeof(GenPlanar)))) return rc;
     if ((rc = ensure(ctx, ctx->dbg, (size_t)n * 6 * sizeof(float)))) return rc;
     const WorkLayout wl = work_layout((size_t)nq * cap, n);
     const size_t wbase = work_base(ctx);
@@ -2158,10 +2472,11 @@ static int debug_bounce_production(RtCtx* ctx, const RtBounceIO* io) {
     gp.inv_band = (float)(1.0 - 1.0 / 4194304.0);
     hipLaunchKernelGGL(k_init_counts<false>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, (GenParams*)ctx->genp.p, GenLens{});
     if (ctx->motion) hipLaunchKernelGGL(k_set_motion, dim3(1), dim3(64), 0, st, (GenParams*)ctx->genp.p, ctx->gmotion); // (the time of slot i: its slot key)
+    if (ctx->planar) hipLaunchKernelGGL(k_set_planar, dim3(1), dim3(64), 0, st, (GenParams*)ctx->genp.p, ctx->gplanar);
     hipLaunchKernelGGL(k_debug_fill, dim3((n + 255u) / 256u), dim3(256), 0, st, gp, Q[0], d_o, d_d);
     const bool use_bvh = ctx->use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
     const StepBuffers sb{Q[0], Q[1], wv.qhit, counts, counts + nq, wv.rad,
-                         (unsigned long long*)ctx->totals.p, (const GenParams*)ctx->genp.p, false, ctx->motion};
+                         (unsigned long long*)ctx->totals.p, (const GenParams*)ctx->genp.p, false, ctx->motion, ctx->planar};
     const IntersectParams ip{nq, cap, (int)io->depth, 0u, nq};
     launch_intersect(ctx, st, use_bvh, false, qg.isect_grid, sb, ip);
     const ShadeParams sp{nq, cap, (int)io->depth, 0x7FFFFFFF, 1u, 0u, 0u};
@@ -2241,7 +2556,12 @@ int rt_debug_bounce(RtCtx* ctx, const RtBounceIO* io) {
     const bool use_bvh = ctx->use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
 #define RT_DEBUG_BOUNCE(B, U, L, LDS)                                                                                                      \
     do {                                                                                                                                   \
-        if (ctx->motion)                                                                                                                   \
+        if (ctx->planar)                                                                                                                   \
+            hipLaunchKernelGGL((k_debug_bounce_planar<B, U, L>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n, \
+                               (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
+                               base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive),   \
+                               ctx->gplanar);                                                                                              \
+        else if (ctx->motion)                                                                                                              \
             hipLaunchKernelGGL((k_debug_bounce_motion<B, U, L>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n, \
                                (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
                                base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive),   \

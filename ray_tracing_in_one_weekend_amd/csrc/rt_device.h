@@ -623,6 +623,36 @@ __device__ __forceinline__ bool rect_root(float4 g0, float4 g1, V3 o, V3 d, floa
     return true;
 }
 
+// Planar primitives (rt_set_quads): the quadrilateral of "The Next Week" ch. 6, Q + a u + b v, and the triangle the same plane test
+// gives with another interior test.  g = 5 float4 per primitive, set up once on the host in f32 (rtow_mi355x.h):
+//   g[0] = (normal, D)   g[1] = (Q, kind bits)   g[2] = (u, 0)   g[3] = (v, 0)   g[4] = (w, 0)
+// Every operation below is one IEEE f32 operation (-ffp-contract=off); tests/quad_ref.py restates it.  The plane is read first: most
+// candidates fail the window, and the other four loads are not issued for them.
+#define RT_PLANAR_TRIANGLE_DEV 1u
+__device__ __forceinline__ void planar_coords(const float4* __restrict__ g, V3 P, float& alpha, float& beta) {
+    const float4 q4 = g[1], u4 = g[2], v4 = g[3], w4 = g[4];
+    const V3 p = P - v3(q4.x, q4.y, q4.z);
+    const V3 w = v3(w4.x, w4.y, w4.z);
+    alpha = dot(w, cross(p, v3(v4.x, v4.y, v4.z)));
+    beta = dot(w, cross(v3(u4.x, u4.y, u4.z), p));
+}
+__device__ __forceinline__ bool planar_root(const float4* __restrict__ g, V3 o, V3 d, float t_min, float t_max, float& t_hit) {
+    const float4 nd = g[0];
+    const V3 normal = v3(nd.x, nd.y, nd.z);
+    const float denom = dot(normal, d);
+    if (fabsf(denom) < 1e-8f) return false; // (a NaN denom goes on to a NaN t)
+    const float t = (nd.w - dot(normal, o)) / denom;
+    if (!(t == t) || t < t_min || t > t_max) return false;
+    const V3 P = o + d * t; // Ray::at
+    float alpha, beta;
+    planar_coords(g, P, alpha, beta);
+    const bool inside = __float_as_uint(g[1].w) == RT_PLANAR_TRIANGLE_DEV ? (alpha >= 0.0f && beta >= 0.0f && alpha + beta <= 1.0f)
+                                                                         : (alpha >= 0.0f && alpha <= 1.0f && beta >= 0.0f && beta <= 1.0f);
+    if (!inside) return false; // (NaN coordinates: a miss)
+    t_hit = t;
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Instance wrappers Translate / RotateY (hitable.rs:404-520) as a per-primitive chain
 // ---------------------------------------------------------------------------------------------
@@ -708,10 +738,12 @@ struct NoPrefetch {
     __device__ __forceinline__ void operator()() const {}
 };
 // MOTION: the hit sphere's centre is c(tm) (sphere_at; `sph_dc` = the per-sphere displacements, `tm` = the path's time).
-template <bool RECTS, class AfterLoads = NoPrefetch, bool NEST = false, bool MOTION = false>
+// PLANAR (rt_set_quads): an entry from `pbase` on is planar primitive hit - pbase of `pq` (planar_root); its shading record lies
+// behind the media's in sph_rec.  It is bare: no wrapper chain, no medium.
+template <bool RECTS, class AfterLoads = NoPrefetch, bool NEST = false, bool MOTION = false, bool PLANAR = false>
 __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro, V3 rd, int hit, float t, Rng& rng,
                                uint32_t& n_fetch, AfterLoads after_record_loads = AfterLoads(), const float4* sph_dc = nullptr,
-                               float tm = 0.0f) {
+                               float tm = 0.0f, const float4* pq = nullptr, uint32_t pbase = 0u) {
     Bounce out;
     out.radiance = splat(0.0f);
     out.attenuation = splat(1.0f);
@@ -730,8 +762,9 @@ __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro
         out.radiance = sky_value(sc, rd, n_fetch); // main.rs:58
         return out;
     }
-    const bool is_medium = RECTS && (uint32_t)hit >= sc.n_prims;
-    const bool is_rect = RECTS && !is_medium && (uint32_t)hit >= sc.n_spheres;
+    const bool is_planar = PLANAR && (uint32_t)hit >= pbase;
+    const bool is_medium = RECTS && !is_planar && (uint32_t)hit >= sc.n_prims;
+    const bool is_rect = RECTS && !is_planar && !is_medium && (uint32_t)hit >= sc.n_spheres;
     // RECTS also stands for "general scene": the primitive or medium may sit below Translate / RotateY wrappers.  The
     // HitRecord is then built from the innermost (object-space) ray and fixed on the way out (hitable.rs:412-414,
     // 494-506); `ro`/`rd` stay the world ray that scatter() receives (main.rs:48).
@@ -739,7 +772,7 @@ __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro
     chain.n = 0;
     uint32_t deep_n = 0u, deep_p0 = 0u; // a chain of more than RT_MAX_CHAIN wrappers: its length and its outermost-first list
     V3 wo = ro, wd = rd; // the world ray
-    if (RECTS && (NEST || !is_medium)) { // (a medium: the wrappers AROUND it, hitable.rs:409-416 with ptr = a ConstantMedium; those of its boundary are inside its hit())
+    if (RECTS && (NEST || !is_medium) && !is_planar) { // (a medium: the wrappers AROUND it, hitable.rs:409-416 with ptr = a ConstantMedium; those of its boundary are inside its hit())
         const uint32_t xf = NEST && is_medium ? sc.med_xform[(uint32_t)hit - sc.n_prims].y : sc.prim_xform[hit];
         deep_p0 = NEST && xf != RT_NO_XFORM_DEV ? __float_as_uint(sc.xf_param[xf].w) : 0u;
         if (NEST && deep_p0 != 0u) {
@@ -760,6 +793,11 @@ __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro
         const float pv = axis == 2u ? p.y : p.z;
         rect_uv = V2{(pu - g.y) / (g.z - g.y), (pv - g.w) / (g1.x - g.w)};
         on = v3(axis == 0u ? 1.0f : 0.0f, axis == 1u ? 1.0f : 0.0f, axis == 2u ? 1.0f : 0.0f);
+    } else if (is_planar) { // uv = (alpha, beta) of the hit point, normal = the unit normal of the set-up
+        const float4* g5 = pq + 5u * ((uint32_t)hit - pbase);
+        const float4 nd = g5[0];
+        planar_coords(g5, p, rect_uv.x, rect_uv.y);
+        on = v3(nd.x, nd.y, nd.z);
     } else if (is_medium) {
         on = v3(1.0f, 0.0f, 0.0f);                      // hitable.rs:574 rec.norm = Vec3A::X
     } else {
@@ -833,7 +871,7 @@ __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro
                                 (1u << 10) | (1u << 11);
     V3 tex0_value = splat(0.0f);
     if ((TEX0_USERS >> m.type) & 1u)
-        tex0_value = texture_value_inline(sc, pt, t0type, t0aux, rec[3].z, m.color(), __float_as_uint(rec[3].w), on, is_rect,
+        tex0_value = texture_value_inline(sc, pt, t0type, t0aux, rec[3].z, m.color(), __float_as_uint(rec[3].w), on, is_rect || is_planar,
                                           rect_uv, p, n_fetch);
 #define RT_TEX0() tex0_value
     switch (m.type) {
@@ -934,7 +972,7 @@ __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro
         float h_dot_i = dot(h, -rd);
         float h_dot_o = dot(h, dir_o);
         float n_dot_h = dot(n, h);
-        V3 kd = texture_value(sc, pt, m.tex1, on, is_rect, rect_uv, p, n_fetch);
+        V3 kd = texture_value(sc, pt, m.tex1, on, is_rect || is_planar, rect_uv, p, n_fetch);
         V3 ks = RT_TEX0();
         float roughness = clampf(m.p0(), 0.01f, 1.0f);
         float eta = m.p1();

@@ -100,6 +100,17 @@ static_assert(sizeof(GenLens) <= RT_MOTION_OFFSET && sizeof(GenParams) % 8u == 0
 __device__ __forceinline__ const GenMotion& gen_motion_of(const GenParams* gpd) {
     return *reinterpret_cast<const GenMotion*>(reinterpret_cast<const char*>(gpd + 1) + RT_MOTION_OFFSET);
 }
+// Planar primitives of a frame (rt_set_quads), read by the PLANAR instantiations only; behind the motion (k_set_planar puts it there), so
+// the other kernels keep their arguments, code and registers.  The plane data is read through L2 (DESIGN.md "Planar primitives").
+struct GenPlanar {
+    const float4* pq;  // [5 n] planar_root (rt_device.h)
+    uint32_t base, n;  // world entry of planar primitive 0 (n_prims + n_media), and how many there are
+};
+#define RT_PLANAR_OFFSET (RT_MOTION_OFFSET + 16u)
+static_assert(sizeof(GenMotion) <= 16u && sizeof(GenPlanar) == 16u, "GenPlanar behind GenMotion");
+__device__ __forceinline__ const GenPlanar& gen_planar_of(const GenParams* gpd) {
+    return *reinterpret_cast<const GenPlanar*>(reinterpret_cast<const char*>(gpd + 1) + RT_PLANAR_OFFSET);
+}
 #define RT_TIME_COUNTER 254u
 __device__ __forceinline__ float path_time(const GenMotion& gm, uint32_t k0, uint32_t k1) {
     Rng rng(k0, k1, RT_TIME_COUNTER);
@@ -234,6 +245,11 @@ __global__ __launch_bounds__(256) void k_init_counts(GenParams gp, uint32_t* __r
 // Parks the frame's motion behind the GenParams and the lens (gen_motion_of); launched in front of the depth-0 kernels when motion is set.
 __global__ void k_set_motion(GenParams* __restrict__ gp_dev, GenMotion gm) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<GenMotion*>(reinterpret_cast<char*>(gp_dev + 1) + RT_MOTION_OFFSET) = gm;
+}
+
+// Parks the frame's planar primitives behind the motion (gen_planar_of); launched in front of the depth-0 kernels when a set is present.
+__global__ void k_set_planar(GenParams* __restrict__ gp_dev, GenPlanar pl) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<GenPlanar*>(reinterpret_cast<char*>(gp_dev + 1) + RT_PLANAR_OFFSET) = pl;
 }
 
 // Materialises the primary rays in the queue.  Only the list-walk fallback uses it: on the BVH
@@ -711,6 +727,8 @@ struct BvhLds {
     GenTables gt;          // wrapper / medium tables of general scenes (HBM, or LDS with GLDS)
     unsigned short* stack; // this lane's column: stack[level * BLOCK]
     const float4* dc;      // MOTION: the spheres' displacements (LDS when the geometry is, behind everything else of the carve)
+    const float4* pq;      // PLANAR: the planar primitives' plane data (HBM / L2) and the world entry of the first one
+    uint32_t pbase;
 };
 
 // LDS_NODES = false: the tree and the primitive geometry stay in HBM (scenes whose tree does not fit the
@@ -753,7 +771,7 @@ __device__ __forceinline__ BvhLds stage_bvh(const DevScene& sc, char* smem) {
 
 // Exact test of world entry `s` (a BVH leaf or an entry of a primary-ray candidate list) and the order-independent
 // accept.  Sphere-only scenes: Sphere::hit roots (hitable.rs:75-91).
-template <bool RECTS, bool NEST = RECTS, bool MOTION = false>
+template <bool RECTS, bool NEST = RECTS, bool MOTION = false, bool PLANAR = false>
 __device__ __forceinline__ void leaf_test(const BvhLds& L, int s, V3 o, V3 d, float a, uint32_t& pend, float& tbest,
                                           int& hit, ChainCache* cc = nullptr, float tm = 0.0f) {
     float th;
@@ -767,7 +785,9 @@ __device__ __forceinline__ void leaf_test(const BvhLds& L, int s, V3 o, V3 d, fl
         // here it would stall the lanes of the wave that are at cheap leaves on every step.  It is only
         // noted in `pend` and tested after the traversal (media_step), when the lanes of the wave do so
         // together.  The winner rule is order-independent, so the result is the same.
-        if ((uint32_t)s >= L.gt.n_prims) {
+        if (PLANAR && (uint32_t)s >= L.pbase) { // a planar primitive (rt_set_quads): bare, behind the media in the entry order
+            ok = planar_root(L.pq + 5u * ((uint32_t)s - L.pbase), o, d, 1e-3f, RT_FLT_MAX, th);
+        } else if ((uint32_t)s >= L.gt.n_prims) {
             pend |= 1u << (NEST ? min((uint32_t)s - L.gt.n_prims, 31u) : (uint32_t)s - L.gt.n_prims); // NEST, bit 31: "one of the media from 31 on" (media_step)
             ok = false;
         } else {
@@ -819,7 +839,7 @@ struct SlabPlanes {
 // (24 of the ~120 vector instructions of a node step) go away.  Only the fma form relies on it — `exact` rays (inv
 // infinite or NaN among them, see k_intersect) still order the two distances with min / max, which does not care which
 // array a value came from.
-template <int BLOCK, bool RECTS, bool SORTED = false, bool NEST = RECTS, bool MOTION = false>
+template <int BLOCK, bool RECTS, bool SORTED = false, bool NEST = RECTS, bool MOTION = false, bool PLANAR = false>
 __device__ __forceinline__ bool bvh_step(const BvhLds& L, V3 o, V3 d, float ix, float iy, float iz, float nox, float noy,
                                          float noz, float eps, bool exact, float a, uint32_t& pend, int& cur, int& sp,
                                          float& tbest, int& hit, const SlabPlanes* sp6 = nullptr, float tm = 0.0f) {
@@ -889,7 +909,7 @@ __device__ __forceinline__ bool bvh_step(const BvhLds& L, V3 o, V3 d, float ix, 
             const int s = (int)(lq0 & 0xFFFFu) - 1;
             lq0 = (lq0 >> 16) | (lq1 << 16);
             lq1 >>= 16;
-            leaf_test<RECTS, NEST, MOTION>(L, s, o, d, a, pend, tbest, hit, RECTS ? &cc : nullptr, tm);
+            leaf_test<RECTS, NEST, MOTION, PLANAR>(L, s, o, d, a, pend, tbest, hit, RECTS ? &cc : nullptr, tm);
         }
         if (best != (int)0x80000000) {
             cur = best;
@@ -938,7 +958,8 @@ struct IntersectParams {
 // — measured +15 % on cornell_box and +20 % on final_scene against 7 waves = one workgroup.
 // GEN (depth 0): the ray is regenerated from its queue position instead of being loaded; LENS (with GEN): through the thin lens.
 // MOTION: moving spheres (rt_set_motion).  The time of the lane's ray is formed once, when the lane takes the ray.
-template <int BLOCK, bool GEN, bool RECTS, bool LDS_NODES, bool GLDS, bool NEST = false, bool LENS = false, bool MOTION = false>
+// PLANAR: planar primitives (rt_set_quads) as leaves behind the media; a scene may then hold nothing else.
+template <int BLOCK, bool GEN, bool RECTS, bool LDS_NODES, bool GLDS, bool NEST = false, bool LENS = false, bool MOTION = false, bool PLANAR = false>
 __global__ __launch_bounds__(BLOCK, 8) void k_intersect(DevScene sc, const float4* __restrict__ qa,
                                                      const float4* __restrict__ qb,
                                                      float2* __restrict__ qh, const uint32_t* __restrict__ in_counts,
@@ -969,12 +990,14 @@ __global__ __launch_bounds__(BLOCK, 8) void k_intersect(DevScene sc, const float
             L.dc = sdc;
         }
     }
+    L.pq = nullptr, L.pbase = 0xFFFFFFFFu;
+    if (PLANAR) L.pq = gen_planar_of(gpd).pq, L.pbase = gen_planar_of(gpd).base;
     float tm = 0.0f; // MOTION: this lane's ray's time
     uint32_t* s_work = reinterpret_cast<uint32_t*>(smem + bvh_lds_bytes(sc, BLOCK, LDS_NODES) - 16u);
     if (threadIdx.x == 0) *s_work = 0u;
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
-    const bool no_geometry = sc.n_prims == 0u;
+    const bool no_geometry = !PLANAR && sc.n_prims == 0u;
     bool exhausted = false; // wave-uniform: the workgroup has no unclaimed rays left
     bool has = false;
     bool exact = false; // this lane's ray uses the cancellation-free slab test (bvh_step)
@@ -1067,13 +1090,13 @@ __global__ __launch_bounds__(BLOCK, 8) void k_intersect(DevScene sc, const float
                 if (GEN && has && (list.x & 0xFFFFu) != RT_LIST_OVERFLOW) {
                     // primary ray of a pixel with a candidate list (k_primary_lists): the listed entries instead of the tree
                     const uint32_t n_list = list.x & 0xFFFFu;
-                    if (n_list > 0u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.x >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
-                    if (n_list > 1u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.y & 0xFFFFu), o, d, a, pend, tbest, hit, nullptr, tm);
-                    if (n_list > 2u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.y >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
-                    if (n_list > 3u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.z & 0xFFFFu), o, d, a, pend, tbest, hit, nullptr, tm);
-                    if (n_list > 4u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.z >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
-                    if (n_list > 5u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.w & 0xFFFFu), o, d, a, pend, tbest, hit, nullptr, tm);
-                    if (n_list > 6u) leaf_test<RECTS, NEST, MOTION>(L, (int)(list.w >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 0u) leaf_test<RECTS, NEST, MOTION, PLANAR>(L, (int)(list.x >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 1u) leaf_test<RECTS, NEST, MOTION, PLANAR>(L, (int)(list.y & 0xFFFFu), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 2u) leaf_test<RECTS, NEST, MOTION, PLANAR>(L, (int)(list.y >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 3u) leaf_test<RECTS, NEST, MOTION, PLANAR>(L, (int)(list.z & 0xFFFFu), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 4u) leaf_test<RECTS, NEST, MOTION, PLANAR>(L, (int)(list.z >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 5u) leaf_test<RECTS, NEST, MOTION, PLANAR>(L, (int)(list.w & 0xFFFFu), o, d, a, pend, tbest, hit, nullptr, tm);
+                    if (n_list > 6u) leaf_test<RECTS, NEST, MOTION, PLANAR>(L, (int)(list.w >> 16), o, d, a, pend, tbest, hit, nullptr, tm);
                     if (RECTS && pend) {
                         trav = false; // its media are tested in the media phase below
                     } else {
@@ -1099,7 +1122,7 @@ __global__ __launch_bounds__(BLOCK, 8) void k_intersect(DevScene sc, const float
                 continue;
             }
         }
-        if (has && trav && bvh_step<BLOCK, RECTS, SORTED, NEST, MOTION>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit, &planes, tm)) {
+        if (has && trav && bvh_step<BLOCK, RECTS, SORTED, NEST, MOTION, PLANAR>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit, &planes, tm)) {
             if (RECTS && pend) {
                 trav = false;
             } else {
@@ -1214,6 +1237,41 @@ __global__ __launch_bounds__(256) void k_intersect_list_motion(DevScene sc, cons
     }
 }
 
+// The planar primitives of the list walk: they follow the media in the tie order, read from HBM.
+__device__ __forceinline__ void closest_hit_planar(const GenPlanar& gq, V3 o, V3 d, float& tbest, int& hit) {
+    for (uint32_t i = 0; i < gq.n; ++i) {
+        float th;
+        if (planar_root(gq.pq + 5u * i, o, d, 1e-3f, tbest, th)) {
+            tbest = th;
+            hit = (int)(gq.base + i);
+        }
+    }
+}
+
+// k_intersect_list with planar primitives (rt_set_quads), a kernel of its own beside the static one, whose code stays as it was.  This
+// walk is the test path (RT_FLAG_BRUTE_FORCE) and the last resort: the spheres are read from HBM through the general loop (the same
+// sphere_root on the same operands as the LDS tiles), then rectangles, media and the planar primitives in entry order.
+__global__ __launch_bounds__(256) void k_intersect_list_planar(DevScene sc, const float4* __restrict__ qa, const float4* __restrict__ qb,
+                                                               float2* __restrict__ qh, const uint32_t* __restrict__ in_counts,
+                                                               IntersectParams ip, const GenParams* __restrict__ gpd) {
+    const uint32_t q = ip.q0 + blockIdx.x;
+    const uint32_t count = in_counts[q];
+    const size_t qbase = (size_t)q * ip.cap;
+    const GenPlanar gq = gen_planar_of(gpd);
+    for (uint32_t i = threadIdx.x; i < count; i += 256u) {
+        const float4 ra = qa[RT_QSTRIDE * (qbase + i)], rb = qb[RT_QSTRIDE * (qbase + i)];
+        const V3 o = v3(ra.x, ra.y, ra.z), d = v3(rb.x, rb.y, rb.z);
+        float tbest = RT_FLT_MAX;
+        int hit = -1;
+        closest_hit_spheres_general(sc, o, d, tbest, hit);
+        MediumCtx mc{0u, 0u, depth_counter_base(ip.depth)};
+        if (sc.n_media) path_key_of_slot(*gpd, __float_as_uint(ra.w), mc.k0, mc.k1);
+        closest_hit_rects(sc, o, d, mc, tbest, hit);
+        closest_hit_planar(gq, o, d, tbest, hit);
+        qh[qbase + i] = make_float2(tbest, __int_as_float(hit));
+    }
+}
+
 struct ShadeParams {
     uint32_t nq, cap;
     int depth, max_depth;
@@ -1271,7 +1329,7 @@ __host__ __device__ inline size_t shade_lds_bytes(uint32_t n_entries, uint32_t n
     b += (size_t)n_fused_spheres * 16u;
     return (b + 15u) & ~(size_t)15u;
 }
-template <bool PERLIN_LDS, bool GEN, bool RECTS, bool NEST = false, bool LENS = false, bool MOTION = false> // MOTION: moving spheres (rt_set_motion) — the time comes from the path key a hit that scatters needs anyway; the all-miss segments stay free of it.  NEST (general scenes only): rt_device.h, wrapper chains and media as loops; LENS (with GEN): the thin lens
+template <bool PERLIN_LDS, bool GEN, bool RECTS, bool NEST = false, bool LENS = false, bool MOTION = false, bool PLANAR = false> // PLANAR: planar primitives (rt_set_quads) — their classes and records lie behind the media's.  MOTION: moving spheres (rt_set_motion) — the time comes from the path key a hit that scatters needs anyway; the all-miss segments stay free of it.  NEST (general scenes only): rt_device.h, wrapper chains and media as loops; LENS (with GEN): the thin lens
 #ifndef RT_GEN_WAVES
 #define RT_GEN_WAVES 4 // waves per SIMD the depth-0 instantiations are compiled for (98 VGPR: 5 fit).  Round 2: 4 / 5 / 6 no difference.
                        // Round 3 (cheaper draws): alone on the chip, 6 (80 VGPR, 8 B of scratch) is 2.4-2.7 % faster at depth 0 on the
@@ -1303,7 +1361,7 @@ __global__ __launch_bounds__(256, GEN ? RT_GEN_WAVES : RT_SORTED_WAVES) void k_s
     const uint8_t* cls = sc.sph_class;
     if (sort) {
         lds_off += 4u * RT_SHADE_WAVE_LDS;
-        const uint32_t n_ent = sc.n_prims + sc.n_media;
+        const uint32_t n_ent = sc.n_prims + sc.n_media + (PLANAR ? gen_planar_of(gpd).n : 0u);
         if (n_ent <= RT_CLASS_LDS_MAX) {
             uint8_t* lc = reinterpret_cast<uint8_t*>(smem + lds_off);
             for (uint32_t i = threadIdx.x; i < n_ent; i += 256u) lc[i] = sc.sph_class[i];
@@ -1377,7 +1435,7 @@ __global__ __launch_bounds__(256, GEN ? RT_GEN_WAVES : RT_SORTED_WAVES) void k_s
                 if (j < n_here) {
                     const int hit = __float_as_int(h[k].y);
 #ifdef RT_DEBUG_QUEUE_BOUNDS // debug builds: a hit record names a world entry of the scene (a kernel that left qh unwritten would not)
-                    if (hit >= (int)(sc.n_prims + sc.n_media)) __builtin_trap();
+                    if (hit >= (int)(sc.n_prims + sc.n_media + (PLANAR ? gen_planar_of(gpd).n : 0u))) __builtin_trap();
 #endif
                     const uint32_t key = hit < 0 ? sc.key_miss : (uint32_t)cls[hit];
                     kr[k] = key | (atomicAdd(&s_hist[key], 1u) << 8);
@@ -1510,11 +1568,13 @@ __global__ __launch_bounds__(256, GEN ? RT_GEN_WAVES : RT_SORTED_WAVES) void k_s
                     ++n_bad;
                 } else {
 #ifdef RT_DEBUG_QUEUE_BOUNDS // debug builds: the record fetch of shade() is indexed by whatever the hit record holds
-                    if (__float_as_int(h.y) >= (int)(sc.n_prims + sc.n_media)) __builtin_trap();
+                    if (__float_as_int(h.y) >= (int)(sc.n_prims + sc.n_media + (PLANAR ? gen_planar_of(gpd).n : 0u))) __builtin_trap();
 #endif
                     Rng rng{k0, k1, depth_counter_base(tp.depth)};
-                    bo = shade<RECTS, decltype(prefetch), NEST, MOTION>(sc, pt, o, d, __float_as_int(h.y), h.x, rng, n_fetch, prefetch,
-                                                                        MOTION ? gen_motion_of(gpd).sph_dc : nullptr, tm);
+                    bo = shade<RECTS, decltype(prefetch), NEST, MOTION, PLANAR>(sc, pt, o, d, __float_as_int(h.y), h.x, rng, n_fetch, prefetch,
+                                                                                MOTION ? gen_motion_of(gpd).sph_dc : nullptr, tm,
+                                                                                PLANAR ? gen_planar_of(gpd).pq : nullptr,
+                                                                                PLANAR ? gen_planar_of(gpd).base : 0u);
                     if (bo.alive && tp.russian_roulette) { // main.rs:49-53
                         const float rr = rng.next();
                         rr_threshold = fmaxf(bo.attenuation.x, fmaxf(bo.attenuation.y, bo.attenuation.z)); // max_element
@@ -1780,6 +1840,62 @@ __global__ __launch_bounds__(BLOCK) void k_debug_bounce_motion(DevScene sc, uint
     Rng rng{in_key[2 * i], in_key[2 * i + 1], depth_counter_base(depth)};
     Bounce bo = shade<true, NoPrefetch, true, MOTION>(sc, PerlinTables{sc.perlin_vec, sc.perlin_perm2}, o, d, hit, tbest, rng, n_fetch, NoPrefetch(),
                                                       gm.sph_dc, tm);
+    out_hit[i] = hit;
+    out_t[i] = hit >= 0 ? tbest : 0.0f;
+    out_rad[3 * i] = bo.radiance.x, out_rad[3 * i + 1] = bo.radiance.y, out_rad[3 * i + 2] = bo.radiance.z;
+    out_att[3 * i] = bo.attenuation.x, out_att[3 * i + 1] = bo.attenuation.y, out_att[3 * i + 2] = bo.attenuation.z;
+    out_o[3 * i] = bo.o.x, out_o[3 * i + 1] = bo.o.y, out_o[3 * i + 2] = bo.o.z;
+    out_d[3 * i] = bo.d.x, out_d[3 * i + 1] = bo.d.y, out_d[3 * i + 2] = bo.d.z;
+    out_alive[i] = bo.alive ? 1 : 0;
+}
+
+// k_debug_bounce with planar primitives (rt_set_quads): a kernel of its own beside the static one, whose code stays as it was.
+template <int BLOCK, bool USE_BVH, bool LDS_NODES>
+__global__ __launch_bounds__(BLOCK) void k_debug_bounce_planar(DevScene sc, uint32_t n, int depth, const float* __restrict__ in_o,
+                                                  const float* __restrict__ in_d, const uint32_t* __restrict__ in_key,
+                                                  int* __restrict__ out_hit, float* __restrict__ out_t,
+                                                  float* __restrict__ out_rad, float* __restrict__ out_att,
+                                                  float* __restrict__ out_o, float* __restrict__ out_d,
+                                                  uint8_t* __restrict__ out_alive, GenPlanar gq) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    const bool active = i < n;
+    V3 o = splat(0.0f), d = v3(0.f, 0.f, 1.f);
+    if (active) {
+        o = v3(in_o[3 * i], in_o[3 * i + 1], in_o[3 * i + 2]);
+        d = v3(in_d[3 * i], in_d[3 * i + 1], in_d[3 * i + 2]);
+    }
+    float tbest = RT_FLT_MAX;
+    int hit = -1;
+    const float a = length_squared(d);
+    const MediumCtx mc{active ? in_key[2 * i] : 0u, active ? in_key[2 * i + 1] : 0u, depth_counter_base(depth)};
+    if (USE_BVH) {
+        BvhLds L = stage_bvh<BLOCK, LDS_NODES>(sc, smem);
+        L.dc = nullptr, L.pq = gq.pq, L.pbase = gq.base;
+        __syncthreads();
+        if (active) {
+            const float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
+            const float nox = -(o.x * ix), noy = -(o.y * iy), noz = -(o.z * iz);
+            float eps = 2.4e-7f * fmaxf(fmaxf(fabsf(nox), fabsf(noy)), fabsf(noz));
+            const bool exact = !(eps <= sc.bvh_exact_eps);
+            if (exact) eps = 0.0f;
+            int cur = 0, sp = 0;
+            uint32_t pend = 0u;
+            while (!bvh_step<BLOCK, true, false, true, false, true>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit)) {
+            }
+            while (pend && !media_step<true>(L, o, d, mc, sc.n_media, pend, tbest, hit)) {
+            }
+        }
+    } else {
+        closest_hit_spheres_general(sc, o, d, tbest, hit);
+        closest_hit_rects(sc, o, d, mc, tbest, hit);
+        closest_hit_planar(gq, o, d, tbest, hit);
+    }
+    if (!active) return;
+    uint32_t n_fetch = 0;
+    Rng rng{in_key[2 * i], in_key[2 * i + 1], depth_counter_base(depth)};
+    Bounce bo = shade<true, NoPrefetch, true, false, true>(sc, PerlinTables{sc.perlin_vec, sc.perlin_perm2}, o, d, hit, tbest, rng, n_fetch, NoPrefetch(),
+                                                           nullptr, 0.0f, gq.pq, gq.base);
     out_hit[i] = hit;
     out_t[i] = hit >= 0 ? tbest : 0.0f;
     out_rad[3 * i] = bo.radiance.x, out_rad[3 * i + 1] = bo.radiance.y, out_rad[3 * i + 2] = bo.radiance.z;

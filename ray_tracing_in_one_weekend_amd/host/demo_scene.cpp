@@ -147,6 +147,61 @@ std::pair<HitableList, Camera> moving_sphere_scene(float aspect_ratio) {
     return build_bvh(world, cam); // :85
 }
 
+// "The Next Week" chapter 6: the five coloured quads, camera at (0, 0, 9), vfov 80, aspect 1 in the book.  Planar primitives only.
+std::pair<HitableList, Camera> quads_scene(float aspect_ratio) {
+    SKY_COLOR_set(SkyFn::sky_color);
+    auto lambert = [](float r, float g, float b) { return std::make_shared<Diffuse>(std::make_shared<ConstantTex>(vec3a(r, g, b))); };
+    HitableList world = {
+        std::make_shared<Quad>(vec3a(-3.0f, -2.0f, 5.0f), vec3a(0.0f, 0.0f, -4.0f), vec3a(0.0f, 4.0f, 0.0f), lambert(1.0f, 0.2f, 0.2f)), // left, red
+        std::make_shared<Quad>(vec3a(-2.0f, -2.0f, 0.0f), vec3a(4.0f, 0.0f, 0.0f), vec3a(0.0f, 4.0f, 0.0f), lambert(0.2f, 1.0f, 0.2f)),  // back, green
+        std::make_shared<Quad>(vec3a(3.0f, -2.0f, 1.0f), vec3a(0.0f, 0.0f, 4.0f), vec3a(0.0f, 4.0f, 0.0f), lambert(0.2f, 0.2f, 1.0f)),   // right, blue
+        std::make_shared<Quad>(vec3a(-2.0f, 3.0f, 1.0f), vec3a(4.0f, 0.0f, 0.0f), vec3a(0.0f, 0.0f, 4.0f), lambert(1.0f, 0.5f, 0.0f)),   // upper, orange
+        std::make_shared<Quad>(vec3a(-2.0f, -3.0f, 5.0f), vec3a(4.0f, 0.0f, 0.0f), vec3a(0.0f, 0.0f, -4.0f), lambert(0.2f, 0.8f, 0.8f)), // lower, teal
+    };
+    Camera cam = Camera::new_(vec3a(0.0f, 0.0f, 9.0f), vec3a(0.0f, 0.0f, 0.0f), vec3a(0.0f, 1.0f, 0.0f), 80.0f, aspect_ratio);
+    return {world, cam};
+}
+
+// A mesh: the icosahedron subdivided four times (20 x 4^4 = 5 120 triangles, vertices pushed onto the unit sphere around (0, 1, 0)),
+// over a ground quad, lit by an emissive quad above it; black sky.
+std::pair<HitableList, Camera> mesh_scene(float aspect_ratio) {
+    SKY_COLOR_set(SkyFn::black_sky);
+    auto ground = std::make_shared<Diffuse>(std::make_shared<ConstantTex>(vec3a(0.5f, 0.5f, 0.5f)));
+    auto clay = std::make_shared<Diffuse>(std::make_shared<ConstantTex>(vec3a(0.7f, 0.3f, 0.2f)));
+    auto light = std::make_shared<Emission>(std::make_shared<ConstantTex>(vec3a(8.0f, 8.0f, 8.0f)));
+    struct P3 { double x, y, z; };
+    auto unit = [](P3 p) {
+        const double l = std::sqrt(p.x * p.x + p.y * p.y + p.z * p.z);
+        return P3{p.x / l, p.y / l, p.z / l};
+    };
+    const double g = (1.0 + std::sqrt(5.0)) / 2.0;
+    std::vector<P3> vert = {{-1, g, 0}, {1, g, 0}, {-1, -g, 0}, {1, -g, 0}, {0, -1, g}, {0, 1, g}, {0, -1, -g}, {0, 1, -g}, {g, 0, -1}, {g, 0, 1}, {-g, 0, -1}, {-g, 0, 1}};
+    for (P3& p : vert) p = unit(p);
+    struct Tri { P3 a, b, c; };
+    const int idx[20][3] = {{0, 11, 5}, {0, 5, 1}, {0, 1, 7}, {0, 7, 10}, {0, 10, 11}, {1, 5, 9}, {5, 11, 4}, {11, 10, 2}, {10, 7, 6}, {7, 1, 8},
+                            {3, 9, 4}, {3, 4, 2}, {3, 2, 6}, {3, 6, 8}, {3, 8, 9}, {4, 9, 5}, {2, 4, 11}, {6, 2, 10}, {8, 6, 7}, {9, 8, 1}};
+    std::vector<Tri> tris;
+    for (auto& t : idx) tris.push_back(Tri{vert[t[0]], vert[t[1]], vert[t[2]]});
+    for (int level = 0; level < 4; ++level) {
+        std::vector<Tri> next;
+        next.reserve(tris.size() * 4);
+        for (const Tri& t : tris) {
+            const P3 ab = unit(P3{t.a.x + t.b.x, t.a.y + t.b.y, t.a.z + t.b.z}), bc = unit(P3{t.b.x + t.c.x, t.b.y + t.c.y, t.b.z + t.c.z}),
+                     ca = unit(P3{t.c.x + t.a.x, t.c.y + t.a.y, t.c.z + t.a.z});
+            next.push_back(Tri{t.a, ab, ca}), next.push_back(Tri{t.b, bc, ab}), next.push_back(Tri{t.c, ca, bc}), next.push_back(Tri{ab, bc, ca});
+        }
+        tris.swap(next);
+    }
+    auto at = [](P3 p) { return vec3a((float)p.x, (float)(p.y + 1.0), (float)p.z); };
+    HitableList world = {
+        std::make_shared<Quad>(vec3a(-8.0f, 0.0f, -8.0f), vec3a(0.0f, 0.0f, 16.0f), vec3a(16.0f, 0.0f, 0.0f), ground),
+        std::make_shared<Quad>(vec3a(-1.5f, 4.0f, -1.5f), vec3a(3.0f, 0.0f, 0.0f), vec3a(0.0f, 0.0f, 3.0f), light),
+    };
+    for (const Tri& t : tris) world.push_back(std::make_shared<Triangle>(at(t.a), at(t.b), at(t.c), clay));
+    Camera cam = Camera::new_(vec3a(3.0f, 2.5f, 5.0f), vec3a(0.0f, 1.0f, 0.0f), vec3a(0.0f, 1.0f, 0.0f), 35.0f, aspect_ratio);
+    return {world, cam};
+}
+
 // demo_scene.rs:229-244 — two Lambert spheres, gradient sky, no BVH.
 std::pair<HitableList, Camera> test_sphere(float aspect_ratio) {
     SKY_COLOR_set(SkyFn::sky_color);

@@ -84,6 +84,8 @@ int rth_scene_build(const char* name, float aspect_ratio, RthScene** out) {
         SceneFn fn = nullptr;
         if (n == "sphere_scene") fn = sphere_scene;
         else if (n == "moving_sphere_scene") fn = moving_sphere_scene;
+        else if (n == "quads_scene") fn = quads_scene;
+        else if (n == "mesh_scene") fn = mesh_scene;
         else if (n == "test_sphere") fn = test_sphere;
         else if (n == "simple_light_scene") fn = simple_light_scene;
         else if (n == "cornell_box") fn = cornell_box;
@@ -178,6 +180,22 @@ uint32_t rth_moving_sphere(RthScene* s, const float c0[3], const float c1[3], fl
     return guarded_handle([&]() -> uint32_t {
         if (material >= s->materials.size()) throw std::runtime_error("rth_moving_sphere: bad material handle");
         s->world.push_back(std::make_shared<MovingSphere>(v(c0), v(c1), r, s->materials[material], name ? name : ""));
+        return (uint32_t)s->world.size() - 1;
+    });
+}
+
+uint32_t rth_quad(RthScene* s, const float Q[3], const float u[3], const float v3_[3], uint32_t material) {
+    return guarded_handle([&]() -> uint32_t {
+        if (material >= s->materials.size()) throw std::runtime_error("rth_quad: bad material handle");
+        s->world.push_back(std::make_shared<Quad>(v(Q), v(u), v(v3_), s->materials[material]));
+        return (uint32_t)s->world.size() - 1;
+    });
+}
+
+uint32_t rth_triangle(RthScene* s, const float a[3], const float b[3], const float c[3], uint32_t material) {
+    return guarded_handle([&]() -> uint32_t {
+        if (material >= s->materials.size()) throw std::runtime_error("rth_triangle: bad material handle");
+        s->world.push_back(std::make_shared<Triangle>(v(a), v(b), v(c), s->materials[material]));
         return (uint32_t)s->world.size() - 1;
     });
 }
@@ -313,6 +331,14 @@ int rth_scene_motion(const RthScene* s, RtMotion* out) {
     out->sphere = s->builder.motion_sphere.data();
     out->center1 = s->builder.motion_c1.data();
     out->shutter_open = s->camera.shutter_open, out->shutter_close = s->camera.shutter_close;
+    return RT_OK;
+}
+
+int rth_scene_quads(const RthScene* s, RtQuads* out) {
+    if (!s || !out || !s->finished) return RT_ERR_INVALID;
+    out->n = (uint32_t)s->builder.quad_kind.size();
+    out->q = s->builder.quad_q.data(), out->u = s->builder.quad_u.data(), out->v = s->builder.quad_v.data();
+    out->kind = s->builder.quad_kind.data(), out->mat = s->builder.quad_mat.data();
     return RT_OK;
 }
 

@@ -174,6 +174,13 @@ class FlatSceneBuilder {
         push3(motion_c1, c1);
         push_sphere(c0, r, mat, name);
     }
+    // a planar primitive (rt_set_quads): an entry of the planar table, Q, u, v as given; only bare, at the top level of the world
+    void push_planar(uint8_t kind, Vec3A Q, Vec3A u, Vec3A v, uint32_t mat) {
+        if (cur_xform != RT_NO_XFORM || cur_medium != RT_NO_MEDIUM)
+            throw std::runtime_error("flatten: a Quad / Triangle below a wrapper or as a medium boundary (planar primitives are bare: transform the vertices)");
+        push3(quad_q, Q), push3(quad_u, u), push3(quad_v, v);
+        quad_kind.push_back(kind), quad_mat.push_back(mat);
+    }
     // hitable.rs:523-533 ConstantMedium: primitives pushed until end_medium() bound medium `m`
     uint32_t begin_medium(float neg_inv_density, uint32_t mat) {
         if (cur_medium != RT_NO_MEDIUM) throw std::runtime_error("flatten: a ConstantMedium inside a ConstantMedium boundary");
@@ -227,6 +234,9 @@ class FlatSceneBuilder {
     }
 
     std::vector<float> sph_cx, sph_cy, sph_cz, sph_r;
+    std::vector<float> quad_q, quad_u, quad_v; // planar table (rt_set_quads): 3 floats per primitive each, kind and material
+    std::vector<uint8_t> quad_kind;
+    std::vector<uint32_t> quad_mat;
     std::vector<uint32_t> motion_sphere; // motion table: sphere indices (increasing: spheres are pushed in order) and centres at time 1
     std::vector<float> motion_c1;
     std::vector<uint32_t> sph_mat;
@@ -523,6 +533,33 @@ struct MovingSphere : Hitable {
     std::string memo() const override { return name; }
 };
 
+// "The Next Week" chapter 6: the parallelogram Q + a u + b v, 0 <= a, b <= 1, and the triangle Q, Q + u, Q + v the same plane test gives.
+// They flatten to entries of the planar table (rt_set_quads), not of RtFlatScene.  The box is the corners', padded like the book's.
+struct Planar : Hitable {
+    uint8_t kind;
+    Vec3A Q, u, v;
+    MaterialPtr mat;
+    Planar(uint8_t k, Vec3A Q_, Vec3A u_, Vec3A v_, MaterialPtr m) : kind(k), Q(Q_), u(u_), v(v_), mat(std::move(m)) {}
+    void flatten(FlatSceneBuilder& b) const override { b.push_planar(kind, Q, u, v, b.intern_material(mat.get())); }
+    bool bbox(AABB& aabb) const override {
+        const Vec3A c1 = Q + u, c2 = Q + v;
+        aabb = AABB{Q, Q}.surround(AABB{c1, c1}).surround(AABB{c2, c2});
+        if (kind == RT_PLANAR_QUAD) {
+            const Vec3A c3 = c1 + v;
+            aabb = aabb.surround(AABB{c3, c3});
+        }
+        aabb.min = aabb.min + (-0.0001f), aabb.max = aabb.max + 0.0001f;
+        return true;
+    }
+    std::string memo() const override { return kind == RT_PLANAR_QUAD ? "Quad" : "Triangle"; }
+};
+struct Quad : Planar {
+    Quad(Vec3A Q_, Vec3A u_, Vec3A v_, MaterialPtr m) : Planar(RT_PLANAR_QUAD, Q_, u_, v_, std::move(m)) {}
+};
+struct Triangle : Planar { // corners a, b, c: Q = a, u = b - a, v = c - a, rounded to f32 once
+    Triangle(Vec3A a, Vec3A b, Vec3A c, MaterialPtr m) : Planar(RT_PLANAR_TRIANGLE, a, b - a, c - a, std::move(m)) {}
+};
+
 // hitable.rs:244-362 — axis-aligned rectangles.  The plane coordinate is min[axis] (max[axis] is ignored by hit()).
 #define RTOW_RECT(Name, AXIS, MEMO)                                                                      \
     struct Name : Hitable {                                                                              \
@@ -810,6 +847,8 @@ inline void flatten_world(const HitableList& world, FlatSceneBuilder& b) {
 using SceneFn = std::pair<HitableList, Camera> (*)(float aspect_ratio);
 std::pair<HitableList, Camera> sphere_scene(float aspect_ratio); // demo_scene.rs:37-86  "random-spheres"
 std::pair<HitableList, Camera> moving_sphere_scene(float aspect_ratio); // sphere_scene with its small diffuse spheres bouncing ("The Next Week" cover)
+std::pair<HitableList, Camera> quads_scene(float aspect_ratio); // "The Next Week" ch. 6: five coloured quads (planar primitives only)
+std::pair<HitableList, Camera> mesh_scene(float aspect_ratio);  // an icosphere of 5 120 triangles over a ground quad, lit by an emissive quad
 std::pair<HitableList, Camera> test_sphere(float aspect_ratio);  // demo_scene.rs:229-244
 std::pair<HitableList, Camera> simple_light_scene(float aspect_ratio); // demo_scene.rs:88-110 (spheres + XYRect light)
 std::pair<HitableList, Camera> cornell_box(float aspect_ratio);        // demo_scene.rs:112-148 (walls + two smoke boxes)

@@ -13,7 +13,7 @@ import time
 from . import Renderer, Scene, make_params, output_file_name, register_default_images, save_png
 from . import _ffi
 
-SCENES = ("test_sphere", "sphere_scene", "moving_sphere_scene", "simple_light_scene", "cornell_box", "final_scene", "earth_env_scene",
+SCENES = ("test_sphere", "sphere_scene", "moving_sphere_scene", "quads_scene", "mesh_scene", "simple_light_scene", "cornell_box", "final_scene", "earth_env_scene",
           "pbr_sweep_scene")
 
 
@@ -52,6 +52,9 @@ def main(argv=None):
         if a.shutter:
             motion.shutter_open, motion.shutter_close = a.shutter
         rend.set_motion(motion)
+    quads = scene.quads  # and so are its quads and triangles
+    if quads.n:
+        rend.set_quads(quads)
     flags = _ffi.FLAG_RUSSIAN_ROULETTE if a.russian_roulette else 0
     params = make_params(a.nx, ny, a.spp, max_depth=a.max_depth, seed=a.seed, spp_slice=a.preview_every, flags=flags)
     if a.preview_every:
