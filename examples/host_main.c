@@ -12,7 +12,7 @@
  *   main.rs:77-108  the per-column pixel loop          -> rt_render
  *   main.rs:109-128 receive loop, flip, img.save(name) -> the RGB8 image rt_render returns (already flipped) + rth_png_write
  *
- * usage: host_main [scene [nx ny spp [max_depth [out.png [out.rgb8 [image_dir]]]]]]
+ * usage: host_main [scene [nx ny spp [max_depth [out.png [out.rgb8 [image_dir [lights]]]]]]]   (a 9th argument "lights": light sampling)
  *        (default: test_sphere 800 400 128 50 — the workload main.rs:64-74 ships with)
  * image_dir: decoded textures as binary PPM (P6, 8 bit), <image_dir>/earthmap.ppm and newport_loft.ppm, registered under the
  * paths the scene functions pass to ImageTex::new (main.rs:63, demo_scene.rs:42,160).  JPEG decoding is host I/O outside the
@@ -70,6 +70,7 @@ int main(int argc, char** argv) {
     const char* png_path = argc > 6 ? argv[6] : NULL;
     const char* raw_path = argc > 7 ? argv[7] : NULL;
     const char* image_dir = argc > 8 ? argv[8] : NULL;
+    const int light_sampling = argc > 9 && strcmp(argv[9], "lights") == 0;
     RthScene* scene = NULL;
     RtCtx* ctx = NULL;
     RtCamera cam;
@@ -121,6 +122,18 @@ int main(int argc, char** argv) {
         }
         if (quads.n && rt_set_quads(ctx, &quads) != 0) {
             fail("rt_set_quads", rt_last_error(ctx));
+            goto done;
+        }
+    }
+
+    if (light_sampling) { /* the scene's bare emissive rectangles and quads as sampling targets: the same mean, less noise */
+        RtLights lights;
+        if (rth_scene_lights(scene, &lights, NULL) != 0) {
+            fail("rth_scene_lights", rth_last_error());
+            goto done;
+        }
+        if (lights.n && rt_set_lights(ctx, &lights) != 0) {
+            fail("rt_set_lights", rt_last_error(ctx));
             goto done;
         }
     }

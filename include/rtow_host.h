@@ -98,6 +98,12 @@ int rth_scene_motion(const RthScene* s, RtMotion* out);
 /* The planar primitives of the finished scene for rt_set_quads (pointers into the scene, valid until rth_scene_free); n 0 for a scene
  * without any. */
 int rth_scene_quads(const RthScene* s, RtQuads* out);
+/* The light set of the finished scene for rt_set_lights (pointers into the scene, valid until rth_scene_free): the parallelogram of
+ * every BARE Emission axis-aligned rectangle and every bare Emission quad, in the order the world lists them; n 0 for a scene without
+ * any.  More than RT_MAX_LIGHTS: the first RT_MAX_LIGHTS are kept; *n_found (may be NULL) is how many there were.  Emitters below
+ * rth_translate / rth_rotate_y or inside a medium boundary, emissive spheres and emissive triangles are left out (rt_set_lights takes
+ * world-space parallelograms only: pass those yourself). */
+int rth_scene_lights(const RthScene* s, RtLights* out, uint32_t* n_found);
 const char* rth_scene_sphere_name(const RthScene* s, uint32_t index);
 void rth_scene_free(RthScene* s);
 

@@ -404,6 +404,45 @@ typedef struct RtQuads {
  * The arrays are copied. */
 int rt_set_quads(RtCtx* ctx, const RtQuads* quads);
 
+/* Light importance sampling ("The Rest of Your Life": the mixture density).  The lights are SAMPLING TARGETS ONLY: world-space
+ * parallelograms Q + a u + b v, 0 <= a, b <= 1, towards which scattering surfaces aim half of their rays.  They are not geometry and
+ * carry no material; the closest hit never sees them, no shadow ray is traced and emission is still picked up when a path hits an
+ * emitter.  One half of the mixture covers the whole hemisphere, so the estimator is unbiased for ANY set of parallelograms: a set
+ * that lies where the emitters are (an XZRect light, an emissive quad, an emitter below wrappers given by its world-space corners) is
+ * merely the one that lowers the variance, and a wrong or stale set costs noise, never a wrong mean.
+ * Set-up, once per light k in rt_set_lights: (normal_k, D_k, w_k) exactly as rt_set_quads computes them for a quad, and
+ *   area_k = sqrt(dot(n, n)), n = cross(u, v).
+ * Materials affected: RT_MAT_DIFFUSE (its density p_s = dot(n, dir) RT_FRAC_1_PI) and the materials that draw random_on_hemisphere —
+ * Lambert and the seven pbr.rs materials, tags 2 and 6..12 (p_s = 0.5 RT_FRAC_1_PI).  Emission, Metal, Dielectric, Isotropic, media,
+ * misses and the sky draw nothing new and are unchanged in every bit.  Per hit of an affected material, every operation one IEEE f32
+ * operation in this order, the rng standing where the material's first draw stands without a set:
+ *   1. s = next().
+ *   2. s < 0.5: the material's own direction with its own draws (Diffuse: normalize(n + normalize(random_in_unit_sphere)) with the
+ *      near-zero fix; the others: random_on_hemisphere(n)).
+ *   3. else: k = min((uint32)(next() * n_lights), n_lights - 1);  a = next();  b = next();  target = (Q_k + u_k a) + v_k b;
+ *      dir = normalize(target - po), po = offset_hit_point(p, n) = the scattered ray's origin.
+ *   4. c = dot(n, dir); !(c > 0) (a NaN dir too): the path ends with zero radiance, as a Metal scatter that returns false.
+ *   5. p_L = (sum_k pdf_k) / n_lights, summed in index order from 0; pdf_k = 0 unless the quad test of rt_set_quads accepts the ray
+ *      (po, dir) on light k with t_min = 1e-3, t_max = FLT_MAX, and then pdf_k = (t t) / (fabsf(dot(normal_k, dir)) area_k).
+ *   6. wgt = p_s / ((p_s + p_L) 0.5f).
+ *   7. attenuation = the material's formula evaluated with dir, each component then multiplied by wgt.
+ * RT_FLAG_RUSSIAN_ROULETTE acts on the weighted attenuation afterwards.  (A light-chosen target on the very edge of its quad may fail
+ * its own f32 hit test: pdf_k = 0 and the weight is 2, probability of the order 2^-20 per draw, not corrected.)
+ * rt_set_lens and rt_set_quads combine freely with a light set.  Moving spheres and a light set do not combine yet: rt_set_motion on a
+ * context that holds a light set, and rt_set_lights on one that holds a motion, are RT_ERR_UNSUPPORTED and the previous state stays. */
+#define RT_MAX_LIGHTS 16u
+typedef struct RtLights {
+    uint32_t n;        /* 1..RT_MAX_LIGHTS */
+    const float* q;    /* [3n] world-space parallelograms Q + a u + b v, 0 <= a,b <= 1 */
+    const float* u;    /* [3n] */
+    const float* v;    /* [3n] */
+} RtLights;
+/* The light set of every following render of `ctx`, after rt_scene_upload (RT_ERR_STATE before); rt_scene_upload clears it.  NULL or
+ * n 0: the renderer without light sampling, bit for bit.  RT_ERR_INVALID (n > RT_MAX_LIGHTS, a NULL array, a non-finite component, u, v
+ * that fail the RT_PLANAR_MIN_SIN2 conditioning of rt_set_quads — the same test, in double) or RT_ERR_UNSUPPORTED: the previous set
+ * stays.  The arrays are copied. */
+int rt_set_lights(RtCtx* ctx, const RtLights* lights);
+
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the
  * world shared read-only (main.rs:72-108); here the scene is replicated on every device, device r renders the image
@@ -441,6 +480,9 @@ int rt_multi_set_motion(RtMulti* m, const RtMotion* motion);
 /* rt_set_quads on every device, all or none as rt_multi_set_motion: a refusal comes from the first device and none has changed; a
  * device-side failure on a later device leaves every device WITHOUT planar primitives. */
 int rt_multi_set_quads(RtMulti* m, const RtQuads* quads);
+/* rt_set_lights on every device, all or none as rt_multi_set_quads: a refusal comes from the first device and none has changed; a
+ * device-side failure on a later device leaves every device WITHOUT a light set. */
+int rt_multi_set_lights(RtMulti* m, const RtLights* lights);
 /* The de-interleave step on its own: `d_gathered` is a DEVICE buffer of n_shards band buffers, each
  * max_r rt_shard_rows(ny, band, n_shards, r) rows of nx*3 floats (what the gather delivers); writes the frame in
  * image row order to d_out_rgb_f32 [ny*nx*3] and / or the quantised, flipped image to d_out_rgb8 (device pointers,

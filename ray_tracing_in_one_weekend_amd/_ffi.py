@@ -88,6 +88,12 @@ class RtQuads(C.Structure):
                 ("kind", C.POINTER(C.c_uint8)), ("mat", C.POINTER(C.c_uint32))]
 
 
+class RtLights(C.Structure):
+    """rt_set_lights: light i is the world-space parallelogram Q + a u + b v, a sampling target only (no geometry, no material)."""
+    _fields_ = [("n", C.c_uint32), ("q", C.POINTER(C.c_float)), ("u", C.POINTER(C.c_float)), ("v", C.POINTER(C.c_float))]
+
+
+MAX_LIGHTS = 16
 PLANAR_QUAD, PLANAR_TRIANGLE = 0, 1
 PLANAR_MIN_SIN2 = 2.0 ** -20
 PLANAR_REACH = 16.0
@@ -151,14 +157,15 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_debug_scene_info", "rt_debug_grid_build", "rt_debug_world_bounds", "rt_debug_render_parts", "rt_multi_create", "rt_multi_create_ex", "rt_multi_destroy", "rt_multi_device_count",
                "rt_multi_last_error", "rt_multi_scene_upload", "rt_multi_render", "rt_deinterleave_bands", "rt_set_lens", "rt_multi_set_lens",
                "rt_set_motion", "rt_multi_set_motion", "rt_debug_motion_bounds",
-               "rt_set_quads", "rt_multi_set_quads", "rt_debug_planar_info", "rt_debug_planar_bounds"]
+               "rt_set_quads", "rt_multi_set_quads", "rt_debug_planar_info", "rt_debug_planar_bounds",
+               "rt_set_lights", "rt_multi_set_lights"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
                 "rth_sphere", "rth_rect", "rth_gbox", "rth_translate", "rth_rotate_y", "rth_constant_medium", "rth_hitable_bbox", "rth_set_sky", "rth_set_camera", "rth_scene_finish", "rth_scene_flat",
                 "rth_scene_camera", "rth_scene_sphere_name", "rth_scene_free", "rth_png_write", "rth_output_file_name",
                 "rth_set_camera_lens", "rth_scene_lens",
                 "rth_moving_sphere", "rth_set_camera_shutter", "rth_scene_motion",
-                "rth_quad", "rth_triangle", "rth_scene_quads"]
+                "rth_quad", "rth_triangle", "rth_scene_quads", "rth_scene_lights"]
 
 _gpu_lib = None
 _host_lib = None
@@ -225,6 +232,10 @@ def load_gpu_library():
     lib.rt_set_quads.restype = C.c_int
     lib.rt_multi_set_quads.argtypes = [vp, C.POINTER(RtQuads)]
     lib.rt_multi_set_quads.restype = C.c_int
+    lib.rt_set_lights.argtypes = [vp, C.POINTER(RtLights)]
+    lib.rt_set_lights.restype = C.c_int
+    lib.rt_multi_set_lights.argtypes = [vp, C.POINTER(RtLights)]
+    lib.rt_multi_set_lights.restype = C.c_int
     lib.rt_debug_planar_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.rt_debug_planar_info.restype = C.c_int
     lib.rt_debug_planar_bounds.argtypes = [C.POINTER(RtQuads), C.c_float, vp, vp]
@@ -335,6 +346,8 @@ def load_host_library():
     lib.rth_triangle.restype = C.c_uint32
     lib.rth_scene_quads.argtypes = [vp, C.POINTER(RtQuads)]
     lib.rth_scene_quads.restype = C.c_int
+    lib.rth_scene_lights.argtypes = [vp, C.POINTER(RtLights), C.POINTER(C.c_uint32)]
+    lib.rth_scene_lights.restype = C.c_int
     lib.rth_scene_sphere_name.argtypes = [vp, C.c_uint32]
     lib.rth_scene_sphere_name.restype = C.c_char_p
     lib.rth_scene_free.argtypes = [vp]

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import RtBounceIO, RtCamera, RtFlatScene, RtLens, RtMotion, RtParams, RtQuads, RtStats
+from ._ffi import RtBounceIO, RtCamera, RtFlatScene, RtLens, RtLights, RtMotion, RtParams, RtQuads, RtStats
 
 
 class RtError(RuntimeError):
@@ -74,6 +74,29 @@ def _quads_ptr(quads):
     if not isinstance(quads, RtQuads):
         quads = make_quads(*quads)
     return C.byref(quads)
+
+
+def make_lights(q, u, v):
+    """An RtLights (with its arrays kept alive on it) from the world-space parallelograms Q + a u + b v: corners Q [n, 3] and edge
+    vectors u, v [n, 3].  They are sampling targets only."""
+    qa = np.ascontiguousarray(q, dtype=np.float32).reshape(-1)
+    ua = np.ascontiguousarray(u, dtype=np.float32).reshape(-1)
+    va = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+    if not (qa.size == ua.size == va.size and qa.size % 3 == 0):
+        raise RtError("make_lights: q, u, v must hold three floats per light")
+    fp = C.POINTER(C.c_float)
+    s = RtLights(qa.size // 3, qa.ctypes.data_as(fp), ua.ctypes.data_as(fp), va.ctypes.data_as(fp))
+    s._keep = (qa, ua, va)
+    return s
+
+
+def _lights_ptr(lights):
+    """None -> NULL (no light sampling); an RtLights (Scene.lights, make_lights) -> a pointer to it"""
+    if lights is None:
+        return None
+    if not isinstance(lights, RtLights):
+        lights = make_lights(*lights)
+    return C.byref(lights)
 
 
 def planar_bounds(quads, world_mag=0.0):
@@ -249,6 +272,19 @@ class Scene:
         if self._lib.rth_scene_quads(self._h, C.byref(s)) != 0:
             raise RtError("scene not finished")
         s._keep = self
+        return s
+
+    @property
+    def lights(self):
+        """RtLights of the scene (rth_scene_lights): the parallelograms of its bare Emission rectangles and quads, at most 16 (n_found
+        on the result: how many there were); n 0 for a scene without any.  Emitters below wrappers, spheres and triangles are left out.
+        It points into the scene.  Renderer.upload does not apply it: pass it to set_lights."""
+        s = RtLights()
+        found = C.c_uint32(0)
+        if self._lib.rth_scene_lights(self._h, C.byref(s), C.byref(found)) != 0:
+            raise RtError("scene not finished")
+        s._keep = self
+        s.n_found = found.value
         return s
 
     def sphere_name(self, i):
@@ -499,6 +535,14 @@ class Renderer:
         if rc != 0:
             self._raise("rt_set_quads", rc)
 
+    def set_lights(self, lights):
+        """rt_set_lights: light importance sampling for the following renders — Scene.lights, make_lights(..) or a (q, u, v) tuple of
+        world-space parallelograms; None: none.  After upload(); upload() clears it.  The lights are sampling targets only: any set gives
+        the same mean, the one that covers the emitters gives less noise.  Not together with set_motion."""
+        rc = self._lib.rt_set_lights(self._ctx, _lights_ptr(lights))
+        if rc != 0:
+            self._raise("rt_set_lights", rc)
+
     def motion_bounds(self):
         """rt_debug_motion_bounds as a dict: the bounds set_motion built (padded entry boxes, candidate-list spheres, entry ids, the
         grid and the cells that list each moving sphere; a cell list [0xFFFFFFFF] = tested for every ray)."""
@@ -690,6 +734,12 @@ class MultiRenderer:
         rc = self._lib.rt_multi_set_quads(self._m, _quads_ptr(quads))
         if rc != 0:
             self._raise("rt_multi_set_quads", rc)
+
+    def set_lights(self, lights):
+        """rt_multi_set_lights: Renderer.set_lights on every device."""
+        rc = self._lib.rt_multi_set_lights(self._m, _lights_ptr(lights))
+        if rc != 0:
+            self._raise("rt_multi_set_lights", rc)
 
     def render(self, camera, params, want_rgb8=False):
         """Returns (f32 image [ny, nx, 3] (row 0 = bottom), rgb8 or None, RtStats summed over the devices)."""

@@ -114,6 +114,10 @@ struct RtCtx {
     GenPlanar gplanar{};           // (pq in quads_region)
     double planar_reach = 0.0;     // RT_PLANAR_REACH W of the set: the leaf slack holds for ray origins within it (render_impl checks the camera)
     DevBuf quads_region;
+    // rt_set_lights: sampling targets for shade() only — no search structure knows them, so they live beside either search state
+    bool lights = false;           // the LIGHTS instantiations of k_shade (n > 0)
+    GenLights glights{};           // (table in lights_buf)
+    DevBuf lights_buf;
     bool motion = false;           // the MOTION instantiations (n_moving > 0)
     GenMotion gmotion{};           // (sph_dc in motion_region)
     size_t motion_lds = 0;         // 16 B per sphere beside the geometry where it is staged in LDS
@@ -318,6 +322,7 @@ struct StepBuffers {
     bool lens = false; // depth 0 through the thin lens (the LENS instantiations)
     bool motion = false; // moving spheres (the MOTION instantiations)
     bool planar = false; // planar primitives (the PLANAR instantiations)
+    bool lights = false; // a light set (the LIGHTS instantiations of k_shade)
 };
 bool scene_is_general(const RtCtx* ctx) { return ctx->general_kernels; }
 bool grid_enabled(const RtCtx* ctx) { return ctx->use_grid && ctx->opt[RT_OPT_GRID] != 1u && !scene_is_general(ctx); }
@@ -410,6 +415,30 @@ void launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32
     // sphere geometry for the closest hit inside k_shade<GEN>
     const uint32_t n_fused = (gen && fused_lists) ? ctx->ds.n_spheres * (b.motion ? 2u : 1u) : 0u; // (MOTION: the displacements behind the geometry)
     const size_t shade_lds = shade_lds_bytes(ctx->ds.n_prims + ctx->ds.n_media + (b.planar ? ctx->gplanar.n : 0u), perlin_lds ? ctx->ds.n_perlin : 0u, n_fused, !gen && sp.sort);
+    if (b.lights) { // a light set (rt_set_lights): the same choice among the forms as below, without MOTION (the two refuse each other)
+#define RT_LAUNCH_SHADE_L(P, G, R, X, L, Q)                                                                                                    \
+    hipLaunchKernelGGL((k_shade<P, G, R, X, L, false, Q, true>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, \
+                       b.cout, b.rad, sp, b.totals, b.gpd)
+#define RT_LAUNCH_SHADE_LR(P, G, L)                                           \
+    do {                                                                      \
+        if (b.planar) RT_LAUNCH_SHADE_L(P, G, true, true, L, true);           \
+        else if (rects && ctx->nest) RT_LAUNCH_SHADE_L(P, G, true, true, L, false); \
+        else if (rects) RT_LAUNCH_SHADE_L(P, G, true, false, L, false);       \
+        else RT_LAUNCH_SHADE_L(P, G, false, false, L, false);                 \
+    } while (0)
+#define RT_LAUNCH_SHADE_LP(G, L)                        \
+    do {                                                \
+        if (perlin_lds) RT_LAUNCH_SHADE_LR(true, G, L); \
+        else RT_LAUNCH_SHADE_LR(false, G, L);           \
+    } while (0)
+        if (gen && b.lens) RT_LAUNCH_SHADE_LP(true, true);
+        else if (gen) RT_LAUNCH_SHADE_LP(true, false);
+        else RT_LAUNCH_SHADE_LP(false, false);
+#undef RT_LAUNCH_SHADE_LP
+#undef RT_LAUNCH_SHADE_LR
+#undef RT_LAUNCH_SHADE_L
+        return;
+    }
     if (b.planar) { // (general, NEST: launch_intersect)
 #define RT_LAUNCH_SHADE_P(P, G, L)                                                                                                          \
     hipLaunchKernelGGL((k_shade<P, G, true, true, L, false, true>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, \
@@ -962,6 +991,19 @@ int rt_ctx_create(int device_id, RtCtx** out_ctx) {
 #undef RT_SHADE_PLANAR
             reinterpret_cast<const void*>(&k_debug_bounce_planar<RT_BVH_BLOCK, true, true>),
             reinterpret_cast<const void*>(&k_debug_bounce_planar<RT_BVH_BLOCK, true, false>),
+            // the instantiations of a light set (rt_set_lights): every k_shade launch_shade can pick, and the debug-bounce kernels
+#define RT_SHADE_LIGHTS_G(P, R, X, Q)                                                          \
+    reinterpret_cast<const void*>(&k_shade<P, false, R, X, false, false, Q, true>),            \
+        reinterpret_cast<const void*>(&k_shade<P, true, R, X, false, false, Q, true>),         \
+        reinterpret_cast<const void*>(&k_shade<P, true, R, X, true, false, Q, true>)
+#define RT_SHADE_LIGHTS(P) RT_SHADE_LIGHTS_G(P, false, false, false), RT_SHADE_LIGHTS_G(P, true, false, false), RT_SHADE_LIGHTS_G(P, true, true, false), RT_SHADE_LIGHTS_G(P, true, true, true)
+            RT_SHADE_LIGHTS(true), RT_SHADE_LIGHTS(false),
+#undef RT_SHADE_LIGHTS
+#undef RT_SHADE_LIGHTS_G
+            reinterpret_cast<const void*>(&k_debug_bounce_lights<RT_BVH_BLOCK, true, true, false>),
+            reinterpret_cast<const void*>(&k_debug_bounce_lights<RT_BVH_BLOCK, true, false, false>),
+            reinterpret_cast<const void*>(&k_debug_bounce_lights<RT_BVH_BLOCK, true, true, true>),
+            reinterpret_cast<const void*>(&k_debug_bounce_lights<RT_BVH_BLOCK, true, false, true>),
         };
         for (const void* fn : variants)
             if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_limit)) != hipSuccess)
@@ -991,7 +1033,7 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->acc), free_buf(ctx->counts), free_buf(ctx->totals);
     free_buf(ctx->out_f32), free_buf(ctx->out_u8), free_buf(ctx->dbg), free_buf(ctx->genp);
     free_buf(ctx->preview_u8), free_buf(ctx->lists);
-    free_buf(ctx->motion_region), free_buf(ctx->quads_region);
+    free_buf(ctx->motion_region), free_buf(ctx->quads_region), free_buf(ctx->lights_buf);
     for (auto ev : ctx->events) (void)hipEventDestroy(ev);
     for (auto ev : ctx->depth_events) (void)hipEventDestroy(ev);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
@@ -1404,6 +1446,7 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
             for (int k = 0; k < 3; ++k)
                 if (std::isfinite(b.mn[k]) && std::isfinite(b.mx[k])) ctx->keep.world_mag = std::max(ctx->keep.world_mag, (double)std::max(std::fabs(b.mn[k]), std::fabs(b.mx[k])));
         ctx->planar = false, ctx->gplanar = GenPlanar{};
+        ctx->lights = false, ctx->glights = GenLights{};
         ctx->motion = false, ctx->motion_lds = 0, ctx->gmotion = GenMotion{}, ctx->motion_dbg = RtCtx::MotionDebug{};
     }
     if ((rc = configure_search(ctx, bvh.depth, geo, nullptr))) {
@@ -1511,7 +1554,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     if ((rc = ensure(ctx, ctx->counts, counts_bytes))) return rc;
     const size_t totals_bytes = (size_t)(n_depths + 2) * sizeof(unsigned long long);
     if ((rc = ensure(ctx, ctx->totals, totals_bytes))) return rc;
-    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_PLANAR_OFFSET + sizeof(GenPlanar)))) return rc; // (the lens, the motion and the planar set behind the params: gen_lens_of, gen_motion_of, gen_planar_of)
+    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_LIGHTS_OFFSET + sizeof(GenLights)))) return rc; // (the lens, the motion, the planar set and the light set behind the params: gen_lens_of, gen_motion_of, gen_planar_of, gen_lights_of)
     if (want_lists &&(rc = ensure(ctx, ctx->lists, ((size_t)npix + 1u) * sizeof(uint4)))) return rc; // + the overflow counter behind the lists
     GenParams* gpd = (GenParams*)ctx->genp.p;
     float* acc = (float*)ctx->acc.p;
@@ -1665,6 +1708,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
         RT_HIP(ctx, hipMemsetAsync(counts, 0, counts_bytes, st));
         if (ctx->motion) hipLaunchKernelGGL(k_set_motion, dim3(1), dim3(64), 0, st, gpd, ctx->gmotion);
         if (ctx->planar) hipLaunchKernelGGL(k_set_planar, dim3(1), dim3(64), 0, st, gpd, ctx->gplanar);
+        if (ctx->lights) hipLaunchKernelGGL(k_set_lights, dim3(1), dim3(64), 0, st, gpd, ctx->glights);
         if (lens) hipLaunchKernelGGL(k_init_counts<true>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, gpd, glens);
         else hipLaunchKernelGGL(k_init_counts<false>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, gpd, glens);
         if (!fuse_gen && lens) hipLaunchKernelGGL(k_gen_primary<true>, dim3((gp.n_rays + 255u) / 256u), dim3(256), 0, st, gp, Q[0], glens);
@@ -1691,7 +1735,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
             const bool gen = fuse_gen && depth == 0;
             ip.depth = depth;
             ip.q0 = q0, ip.q1 = q1;
-            const StepBuffers sb{qi, qo, qhit, cin, cout, rad, totals, gpd, lens, ctx->motion, ctx->planar};
+            const StepBuffers sb{qi, qo, qhit, cin, cout, rad, totals, gpd, lens, ctx->motion, ctx->planar, ctx->lights};
             // depth 0 of a sphere-only scene whose pixels all have a candidate list: k_shade<GEN> finds every closest hit itself
             const bool no_primary_trace = gen && !rects && gp.lists != nullptr && no_overflow;
             if (!no_primary_trace) launch_intersect(ctx, sg, use_bvh, gen, isect_grid_g, sb, ip);
@@ -2042,6 +2086,7 @@ int rt_set_motion(RtCtx* ctx, const RtMotion* motion) {
         return RT_OK;
     }
     if (ctx->planar) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_set_motion: the context holds planar primitives (rt_set_quads); the two do not combine yet");
+    if (ctx->lights) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_set_motion: the context holds a light set (rt_set_lights); the two do not combine yet");
     const uint32_t n_sph = ctx->static_search.ds.n_spheres, nm = motion->n_moving;
     if (!motion->sphere || !motion->center1) return fail(ctx, RT_ERR_INVALID, "rt_set_motion: NULL array");
     if (!std::isfinite(motion->shutter_open) || !std::isfinite(motion->shutter_close) || motion->shutter_open < 0.0f ||
@@ -2421,6 +2466,53 @@ int rt_set_quads(RtCtx* ctx, const RtQuads* quads) {
     return RT_OK;
 }
 
+// ---- light importance sampling (rt_set_lights) -----------------------------------------------------------------------------------
+// The table the LIGHTS instantiations of k_shade read: per light the five float4 of a planar quad (planar_setup: the same conditioning
+// test in double and the same f32 plane set-up as rt_set_quads) with area = sqrt(dot(n, n)), n = cross(u, v), in the free w of g[3].
+// The lights are sampling targets only: no tree, grid or list knows them, so a set goes with either search state and survives
+// rt_set_quads.
+int rt_set_lights(RtCtx* ctx, const RtLights* lights) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!ctx->has_scene) return fail(ctx, RT_ERR_STATE, "rt_set_lights: no scene uploaded");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!lights || lights->n == 0) {
+        if (ctx->lights) RT_HIP(ctx, hipDeviceSynchronize());
+        ctx->lights = false, ctx->glights = GenLights{};
+        return RT_OK;
+    }
+    if (ctx->motion) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_set_lights: the context holds a motion (rt_set_motion); the two do not combine yet");
+    const uint32_t n = lights->n;
+    if (n > RT_MAX_LIGHTS) return fail(ctx, RT_ERR_INVALID, "rt_set_lights: more than RT_MAX_LIGHTS (16) lights");
+    if (!lights->q || !lights->u || !lights->v) return fail(ctx, RT_ERR_INVALID, "rt_set_lights: NULL array");
+    PlanarHost ph;
+    {
+        const std::vector<uint8_t> kind(n, (uint8_t)RT_PLANAR_QUAD);
+        const std::vector<uint32_t> mat(n, 0u);
+        const RtQuads as_quads{n, lights->q, lights->u, lights->v, kind.data(), mat.data()};
+        std::string err;
+        const int rc = planar_setup(&as_quads, 0.0, ph, err);
+        if (rc) return fail(ctx, rc, "rt_set_lights: " + err);
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* u = lights->u + 3 * (size_t)i;
+        const float* v = lights->v + 3 * (size_t)i;
+        const float nx = u[1] * v[2] - u[2] * v[1], ny = u[2] * v[0] - u[0] * v[2], nz = u[0] * v[1] - u[1] * v[0];
+        const float area = std::sqrt((nx * nx + ny * ny) + nz * nz);
+        if (!std::isfinite(area) || !(area > 0.0f)) return fail(ctx, RT_ERR_INVALID, "rt_set_lights: light " + std::to_string(i) + ": the f32 area overflows or underflows");
+        ph.pq[5 * (size_t)i + 3].w = area;
+    }
+    RT_HIP(ctx, hipDeviceSynchronize()); // nothing may still read the table of the set before
+    int rc;
+    if ((rc = ensure(ctx, ctx->lights_buf, (size_t)RT_MAX_LIGHTS * 5u * sizeof(float4)))) return rc;
+    if ((rc = copy_to_device(ctx, ctx->lights_buf.p, ph.pq.data(), ph.pq.size() * sizeof(float4)))) {
+        ctx->lights = false, ctx->glights = GenLights{};
+        return rc;
+    }
+    ctx->glights = GenLights{(const float4*)ctx->lights_buf.p, n, 0u};
+    ctx->lights = true;
+    return RT_OK;
+}
+
 int rt_get_depth_timings(RtCtx* ctx, uint32_t max_n, float* isect_ms, float* shade_ms, uint64_t* rays) {
     if (!ctx) return RT_ERR_INVALID;
     RT_HIP(ctx, hipSetDevice(ctx->device));
@@ -2447,7 +2539,7 @@ static int debug_bounce_production(RtCtx* ctx, const RtBounceIO* io) {
     int rc;
     if ((rc = ensure(ctx, ctx->counts, (size_t)2 * nq * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(ctx, ctx->totals, 4 * sizeof(unsigned long long)))) return rc;
-    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_PLANAR_OFFSET + sizeof(GenPlanar)))) return rc;
+    if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_LIGHTS_OFFSET + sizeof(GenLights)))) return rc;
     if ((rc = ensure(ctx, ctx->dbg, (size_t)n * 6 * sizeof(float)))) return rc;
     const WorkLayout wl = work_layout((size_t)nq * cap, n);
     const size_t wbase = work_base(ctx);
@@ -2473,10 +2565,11 @@ static int debug_bounce_production(RtCtx* ctx, const RtBounceIO* io) {
     hipLaunchKernelGGL(k_init_counts<false>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, (GenParams*)ctx->genp.p, GenLens{});
     if (ctx->motion) hipLaunchKernelGGL(k_set_motion, dim3(1), dim3(64), 0, st, (GenParams*)ctx->genp.p, ctx->gmotion); // (the time of slot i: its slot key)
     if (ctx->planar) hipLaunchKernelGGL(k_set_planar, dim3(1), dim3(64), 0, st, (GenParams*)ctx->genp.p, ctx->gplanar);
+    if (ctx->lights) hipLaunchKernelGGL(k_set_lights, dim3(1), dim3(64), 0, st, (GenParams*)ctx->genp.p, ctx->glights);
     hipLaunchKernelGGL(k_debug_fill, dim3((n + 255u) / 256u), dim3(256), 0, st, gp, Q[0], d_o, d_d);
     const bool use_bvh = ctx->use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
     const StepBuffers sb{Q[0], Q[1], wv.qhit, counts, counts + nq, wv.rad,
-                         (unsigned long long*)ctx->totals.p, (const GenParams*)ctx->genp.p, false, ctx->motion, ctx->planar};
+                         (unsigned long long*)ctx->totals.p, (const GenParams*)ctx->genp.p, false, ctx->motion, ctx->planar, ctx->lights};
     const IntersectParams ip{nq, cap, (int)io->depth, 0u, nq};
     launch_intersect(ctx, st, use_bvh, false, qg.isect_grid, sb, ip);
     const ShadeParams sp{nq, cap, (int)io->depth, 0x7FFFFFFF, 1u, 0u, 0u};
@@ -2556,7 +2649,17 @@ int rt_debug_bounce(RtCtx* ctx, const RtBounceIO* io) {
     const bool use_bvh = ctx->use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
 #define RT_DEBUG_BOUNCE(B, U, L, LDS)                                                                                                      \
     do {                                                                                                                                   \
-        if (ctx->planar)                                                                                                                   \
+        if (ctx->lights && ctx->planar)                                                                                                    \
+            hipLaunchKernelGGL((k_debug_bounce_lights<B, U, L, true>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n, \
+                               (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
+                               base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive),   \
+                               ctx->gplanar, ctx->glights);                                                                                \
+        else if (ctx->lights)                                                                                                              \
+            hipLaunchKernelGGL((k_debug_bounce_lights<B, U, L, false>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n, \
+                               (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
+                               base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive),   \
+                               ctx->gplanar, ctx->glights);                                                                                \
+        else if (ctx->planar)                                                                                                              \
             hipLaunchKernelGGL((k_debug_bounce_planar<B, U, L>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n, \
                                (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
                                base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive),   \

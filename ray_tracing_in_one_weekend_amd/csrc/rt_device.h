@@ -718,6 +718,40 @@ __device__ __forceinline__ void ray_to_object(const Tables& sc, uint32_t xf, V3&
     }
 }
 
+// Light importance sampling (rt_set_lights): the book's mixture density of "The Rest of Your Life" — half the scattering surface's own
+// density p_s, half the average of the lights' solid-angle densities p_L.  `lt` = 5 float4 per light in the layout of planar_root (a
+// quad), with the parallelogram's area in g[3].w.  It is read through the constant address space: the density loop runs over a
+// wave-uniform index, so its reads are scalar loads (one per wave, no vector registers for the table), while the read of the lane's own
+// chosen light has a divergent index and is a vector load.  The table is written by the host before the launch and never by a kernel.
+// Every operation is one IEEE f32 operation in the order of rtow_mi355x.h; tests/light_ref.py restates it.
+#define RT_MAX_LIGHTS_DEV 16u
+typedef const __attribute__((address_space(4))) float* LightTable;
+__device__ __forceinline__ float4 light_row(LightTable lt, uint32_t row) { // (four adjacent dwords: one x4 load)
+    const uint32_t i = 4u * row;
+    return make_float4(lt[i], lt[i + 1u], lt[i + 2u], lt[i + 3u]);
+}
+__device__ __forceinline__ V3 light_target_dir(LightTable lt, uint32_t n_lights, Rng& rng, V3 po) {
+    const uint32_t k = min((uint32_t)(rng.next() * (float)n_lights), n_lights - 1u);
+    const float a = rng.next();
+    const float b = rng.next();
+    const float4 q4 = light_row(lt, 5u * k + 1u), u4 = light_row(lt, 5u * k + 2u), v4 = light_row(lt, 5u * k + 3u);
+    const V3 target = (v3(q4.x, q4.y, q4.z) + v3(u4.x, u4.y, u4.z) * a) + v3(v4.x, v4.y, v4.z) * b;
+    return normalize(target - po);
+}
+// p_L of the ray (po, dir): (sum_k pdf_k) / n in index order, pdf_k = t^2 / (|dot(normal_k, dir)| area_k) where the quad test accepts
+__device__ __forceinline__ float light_pdf(LightTable lt, uint32_t n_lights, V3 po, V3 dir) {
+    float sum = 0.0f;
+    for (uint32_t k = 0; k < n_lights; ++k) { // (k and n_lights are wave-uniform)
+        float4 g[5];
+#pragma unroll
+        for (uint32_t j = 0; j < 5u; ++j) g[j] = light_row(lt, 5u * k + j);
+        float t;
+        if (planar_root(g, po, dir, 1e-3f, RT_FLT_MAX, t))
+            sum = sum + (t * t) / (fabsf(dot(v3(g[0].x, g[0].y, g[0].z), dir)) * g[3].w);
+    }
+    return sum / (float)n_lights;
+}
+
 // Result of one bounce for one ray.
 struct Bounce {
     V3 radiance;    // emitted (hit) or sky (miss) term of this segment, untinted
@@ -740,10 +774,13 @@ struct NoPrefetch {
 // MOTION: the hit sphere's centre is c(tm) (sphere_at; `sph_dc` = the per-sphere displacements, `tm` = the path's time).
 // PLANAR (rt_set_quads): an entry from `pbase` on is planar primitive hit - pbase of `pq` (planar_root); its shading record lies
 // behind the media's in sph_rec.  It is bare: no wrapper chain, no medium.
-template <bool RECTS, class AfterLoads = NoPrefetch, bool NEST = false, bool MOTION = false, bool PLANAR = false>
+// LIGHTS (rt_set_lights): Diffuse and the hemisphere family (Lambert, pbr.rs) pick their direction from the mixture density and weight
+// their attenuation by p_s / ((p_s + p_L) / 2) (light_pdf above); every other material, the emission and the sky are untouched.
+template <bool RECTS, class AfterLoads = NoPrefetch, bool NEST = false, bool MOTION = false, bool PLANAR = false, bool LIGHTS = false>
 __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro, V3 rd, int hit, float t, Rng& rng,
                                uint32_t& n_fetch, AfterLoads after_record_loads = AfterLoads(), const float4* sph_dc = nullptr,
-                               float tm = 0.0f, const float4* pq = nullptr, uint32_t pbase = 0u) {
+                               float tm = 0.0f, const float4* pq = nullptr, uint32_t pbase = 0u, const float4* lights = nullptr,
+                               uint32_t n_lights = 0u) {
     Bounce out;
     out.radiance = splat(0.0f);
     out.attenuation = splat(1.0f);
@@ -881,6 +918,7 @@ __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro
         return out;
     case 1: { // Diffuse material.rs:35-46
         RT_LANE_STAT(22, true);
+        if (LIGHTS) break; // (with the family below: one copy of the mixture code)
         V3 sd = n + normalize(random_in_unit_sphere(rng));
         const float eps = 1.1920929e-7f;
         if (fabsf(sd.x) < eps && fabsf(sd.y) < eps && fabsf(sd.z) < eps) sd = n; // math.rs:8-11
@@ -926,7 +964,39 @@ __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro
     // uniform hemisphere direction (pbr.rs:19-20 and equivalents).
     RT_LANE_STAT(24, true);
     V3 po = offset_hit_point(p, n);
-    V3 dir_o = random_on_hemisphere(rng, n);
+    V3 dir_o;
+    float light_wgt = 1.0f;
+    if (LIGHTS) {
+        const LightTable lt = (LightTable)lights;
+        const bool diffuse = m.type == 1u;
+        const float s = rng.next();
+        if (s < 0.5f) { // the material's own direction, with its own draws
+            if (diffuse) {
+                V3 sd = n + normalize(random_in_unit_sphere(rng));
+                const float eps = 1.1920929e-7f;
+                if (fabsf(sd.x) < eps && fabsf(sd.y) < eps && fabsf(sd.z) < eps) sd = n; // math.rs:8-11
+                dir_o = normalize(sd);
+            } else {
+                dir_o = random_on_hemisphere(rng, n);
+            }
+        } else { // towards a point of a light
+            dir_o = light_target_dir(lt, n_lights, rng, po);
+        }
+        out.o = po;
+        out.d = dir_o;
+        const float c = dot(n, dir_o);
+        if (!(c > 0.0f)) return out; // below the horizon (or a NaN direction): the path ends, as a Metal scatter that returns false
+        const float p_l = light_pdf(lt, n_lights, po, dir_o);
+        const float p_s = diffuse ? c * RT_FRAC_1_PI : 0.5f * RT_FRAC_1_PI;
+        light_wgt = p_s / ((p_s + p_l) * 0.5f);
+        if (diffuse) {
+            out.attenuation = RT_TEX0() * light_wgt;
+            out.alive = true;
+            return out;
+        }
+    } else {
+        dir_o = random_on_hemisphere(rng, n);
+    }
     out.o = po;
     out.d = dir_o;
     out.alive = true;
@@ -1054,6 +1124,7 @@ __device__ inline Bounce shade(const DevScene& sc, const PerlinTables& pt, V3 ro
         break;
     }
 #undef RT_TEX0
+    if (LIGHTS && out.alive) out.attenuation = out.attenuation * light_wgt;
     return out;
 }
 

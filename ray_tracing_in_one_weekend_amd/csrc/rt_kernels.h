@@ -111,6 +111,18 @@ static_assert(sizeof(GenMotion) <= 16u && sizeof(GenPlanar) == 16u, "GenPlanar b
 __device__ __forceinline__ const GenPlanar& gen_planar_of(const GenParams* gpd) {
     return *reinterpret_cast<const GenPlanar*>(reinterpret_cast<const char*>(gpd + 1) + RT_PLANAR_OFFSET);
 }
+// Light set of a frame (rt_set_lights), read by the LIGHTS instantiations of k_shade only; behind the planar set (k_set_lights puts it
+// there), so the other kernels keep their arguments, code and registers.  The table itself (at most RT_MAX_LIGHTS x 80 B) stays in
+// HBM / L2 and is read through the scalar cache (light_pdf, rt_device.h); whether LDS would serve it better is unmeasured.
+struct GenLights {
+    const float4* table; // [5 n] light_pdf (rt_device.h)
+    uint32_t n, pad;
+};
+#define RT_LIGHTS_OFFSET (RT_PLANAR_OFFSET + 16u)
+static_assert(sizeof(GenLights) == 16u, "GenLights behind GenPlanar");
+__device__ __forceinline__ const GenLights& gen_lights_of(const GenParams* gpd) {
+    return *reinterpret_cast<const GenLights*>(reinterpret_cast<const char*>(gpd + 1) + RT_LIGHTS_OFFSET);
+}
 #define RT_TIME_COUNTER 254u
 __device__ __forceinline__ float path_time(const GenMotion& gm, uint32_t k0, uint32_t k1) {
     Rng rng(k0, k1, RT_TIME_COUNTER);
@@ -250,6 +262,11 @@ __global__ void k_set_motion(GenParams* __restrict__ gp_dev, GenMotion gm) {
 // Parks the frame's planar primitives behind the motion (gen_planar_of); launched in front of the depth-0 kernels when a set is present.
 __global__ void k_set_planar(GenParams* __restrict__ gp_dev, GenPlanar pl) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<GenPlanar*>(reinterpret_cast<char*>(gp_dev + 1) + RT_PLANAR_OFFSET) = pl;
+}
+
+// Parks the frame's light set behind the planar set (gen_lights_of); launched in front of the depth-0 kernels when a set is present.
+__global__ void k_set_lights(GenParams* __restrict__ gp_dev, GenLights gl) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<GenLights*>(reinterpret_cast<char*>(gp_dev + 1) + RT_LIGHTS_OFFSET) = gl;
 }
 
 // Materialises the primary rays in the queue.  Only the list-walk fallback uses it: on the BVH
@@ -1329,7 +1346,7 @@ __host__ __device__ inline size_t shade_lds_bytes(uint32_t n_entries, uint32_t n
     b += (size_t)n_fused_spheres * 16u;
     return (b + 15u) & ~(size_t)15u;
 }
-template <bool PERLIN_LDS, bool GEN, bool RECTS, bool NEST = false, bool LENS = false, bool MOTION = false, bool PLANAR = false> // PLANAR: planar primitives (rt_set_quads) — their classes and records lie behind the media's.  MOTION: moving spheres (rt_set_motion) — the time comes from the path key a hit that scatters needs anyway; the all-miss segments stay free of it.  NEST (general scenes only): rt_device.h, wrapper chains and media as loops; LENS (with GEN): the thin lens
+template <bool PERLIN_LDS, bool GEN, bool RECTS, bool NEST = false, bool LENS = false, bool MOTION = false, bool PLANAR = false, bool LIGHTS = false> // LIGHTS: light importance sampling (rt_set_lights) — only shade() differs: the class sort already groups the affected materials, so a wave of other classes or of misses never enters the density loop.  PLANAR: planar primitives (rt_set_quads) — their classes and records lie behind the media's.  MOTION: moving spheres (rt_set_motion) — the time comes from the path key a hit that scatters needs anyway; the all-miss segments stay free of it.  NEST (general scenes only): rt_device.h, wrapper chains and media as loops; LENS (with GEN): the thin lens
 #ifndef RT_GEN_WAVES
 #define RT_GEN_WAVES 4 // waves per SIMD the depth-0 instantiations are compiled for (98 VGPR: 5 fit).  Round 2: 4 / 5 / 6 no difference.
                        // Round 3 (cheaper draws): alone on the chip, 6 (80 VGPR, 8 B of scratch) is 2.4-2.7 % faster at depth 0 on the
@@ -1571,10 +1588,12 @@ __global__ __launch_bounds__(256, GEN ? RT_GEN_WAVES : RT_SORTED_WAVES) void k_s
                     if (__float_as_int(h.y) >= (int)(sc.n_prims + sc.n_media + (PLANAR ? gen_planar_of(gpd).n : 0u))) __builtin_trap();
 #endif
                     Rng rng{k0, k1, depth_counter_base(tp.depth)};
-                    bo = shade<RECTS, decltype(prefetch), NEST, MOTION, PLANAR>(sc, pt, o, d, __float_as_int(h.y), h.x, rng, n_fetch, prefetch,
-                                                                                MOTION ? gen_motion_of(gpd).sph_dc : nullptr, tm,
-                                                                                PLANAR ? gen_planar_of(gpd).pq : nullptr,
-                                                                                PLANAR ? gen_planar_of(gpd).base : 0u);
+                    bo = shade<RECTS, decltype(prefetch), NEST, MOTION, PLANAR, LIGHTS>(sc, pt, o, d, __float_as_int(h.y), h.x, rng, n_fetch, prefetch,
+                                                                                        MOTION ? gen_motion_of(gpd).sph_dc : nullptr, tm,
+                                                                                        PLANAR ? gen_planar_of(gpd).pq : nullptr,
+                                                                                        PLANAR ? gen_planar_of(gpd).base : 0u,
+                                                                                        LIGHTS ? gen_lights_of(gpd).table : nullptr,
+                                                                                        LIGHTS ? gen_lights_of(gpd).n : 0u);
                     if (bo.alive && tp.russian_roulette) { // main.rs:49-53
                         const float rr = rng.next();
                         rr_threshold = fmaxf(bo.attenuation.x, fmaxf(bo.attenuation.y, bo.attenuation.z)); // max_element
@@ -1896,6 +1915,63 @@ __global__ __launch_bounds__(BLOCK) void k_debug_bounce_planar(DevScene sc, uint
     Rng rng{in_key[2 * i], in_key[2 * i + 1], depth_counter_base(depth)};
     Bounce bo = shade<true, NoPrefetch, true, false, true>(sc, PerlinTables{sc.perlin_vec, sc.perlin_perm2}, o, d, hit, tbest, rng, n_fetch, NoPrefetch(),
                                                            nullptr, 0.0f, gq.pq, gq.base);
+    out_hit[i] = hit;
+    out_t[i] = hit >= 0 ? tbest : 0.0f;
+    out_rad[3 * i] = bo.radiance.x, out_rad[3 * i + 1] = bo.radiance.y, out_rad[3 * i + 2] = bo.radiance.z;
+    out_att[3 * i] = bo.attenuation.x, out_att[3 * i + 1] = bo.attenuation.y, out_att[3 * i + 2] = bo.attenuation.z;
+    out_o[3 * i] = bo.o.x, out_o[3 * i + 1] = bo.o.y, out_o[3 * i + 2] = bo.o.z;
+    out_d[3 * i] = bo.d.x, out_d[3 * i + 1] = bo.d.y, out_d[3 * i + 2] = bo.d.z;
+    out_alive[i] = bo.alive ? 1 : 0;
+}
+
+// k_debug_bounce with a light set (rt_set_lights), with or without planar primitives: a kernel of its own beside the others, whose
+// code stays as it was.  The closest hit is the general one (the same roots on the same operands); only shade() knows the lights.
+template <int BLOCK, bool USE_BVH, bool LDS_NODES, bool PLANAR>
+__global__ __launch_bounds__(BLOCK) void k_debug_bounce_lights(DevScene sc, uint32_t n, int depth, const float* __restrict__ in_o,
+                                                  const float* __restrict__ in_d, const uint32_t* __restrict__ in_key,
+                                                  int* __restrict__ out_hit, float* __restrict__ out_t,
+                                                  float* __restrict__ out_rad, float* __restrict__ out_att,
+                                                  float* __restrict__ out_o, float* __restrict__ out_d,
+                                                  uint8_t* __restrict__ out_alive, GenPlanar gq, GenLights gl) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    const bool active = i < n;
+    V3 o = splat(0.0f), d = v3(0.f, 0.f, 1.f);
+    if (active) {
+        o = v3(in_o[3 * i], in_o[3 * i + 1], in_o[3 * i + 2]);
+        d = v3(in_d[3 * i], in_d[3 * i + 1], in_d[3 * i + 2]);
+    }
+    float tbest = RT_FLT_MAX;
+    int hit = -1;
+    const float a = length_squared(d);
+    const MediumCtx mc{active ? in_key[2 * i] : 0u, active ? in_key[2 * i + 1] : 0u, depth_counter_base(depth)};
+    if (USE_BVH) {
+        BvhLds L = stage_bvh<BLOCK, LDS_NODES>(sc, smem);
+        L.dc = nullptr, L.pq = PLANAR ? gq.pq : nullptr, L.pbase = PLANAR ? gq.base : 0xFFFFFFFFu;
+        __syncthreads();
+        if (active && (PLANAR || sc.n_prims)) {
+            const float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
+            const float nox = -(o.x * ix), noy = -(o.y * iy), noz = -(o.z * iz);
+            float eps = 2.4e-7f * fmaxf(fmaxf(fabsf(nox), fabsf(noy)), fabsf(noz));
+            const bool exact = !(eps <= sc.bvh_exact_eps);
+            if (exact) eps = 0.0f;
+            int cur = 0, sp = 0;
+            uint32_t pend = 0u;
+            while (!bvh_step<BLOCK, true, false, true, false, PLANAR>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit)) {
+            }
+            while (pend && !media_step<true>(L, o, d, mc, sc.n_media, pend, tbest, hit)) {
+            }
+        }
+    } else {
+        closest_hit_spheres_general(sc, o, d, tbest, hit);
+        closest_hit_rects(sc, o, d, mc, tbest, hit);
+        if (PLANAR) closest_hit_planar(gq, o, d, tbest, hit);
+    }
+    if (!active) return;
+    uint32_t n_fetch = 0;
+    Rng rng{in_key[2 * i], in_key[2 * i + 1], depth_counter_base(depth)};
+    Bounce bo = shade<true, NoPrefetch, true, false, PLANAR, true>(sc, PerlinTables{sc.perlin_vec, sc.perlin_perm2}, o, d, hit, tbest, rng, n_fetch,
+                                                                   NoPrefetch(), nullptr, 0.0f, gq.pq, gq.base, gl.table, gl.n);
     out_hit[i] = hit;
     out_t[i] = hit >= 0 ? tbest : 0.0f;
     out_rad[3 * i] = bo.radiance.x, out_rad[3 * i + 1] = bo.radiance.y, out_rad[3 * i + 2] = bo.radiance.z;

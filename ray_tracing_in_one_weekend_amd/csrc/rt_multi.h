@@ -219,6 +219,19 @@ int rt_multi_set_quads(RtMulti* m, const RtQuads* quads) {
     return RT_OK;
 }
 
+int rt_multi_set_lights(RtMulti* m, const RtLights* lights) {
+    if (!m) return RT_ERR_INVALID;
+    for (size_t i = 0; i < m->ctx.size(); ++i) { // (every context holds the same scene: the first refuses what all would, then none has changed)
+        const int rc = rt_set_lights(m->ctx[i], lights);
+        if (rc) { // a device-side failure behind the first context: the ones already changed go back to the renderer without a light set
+            const std::string err = rt_last_error(m->ctx[i]);
+            for (size_t k = 0; k < i; ++k) (void)rt_set_lights(m->ctx[k], nullptr);
+            return multi_fail(m, rc, std::string("device ") + std::to_string(m->devices[i]) + ": " + err);
+        }
+    }
+    return RT_OK;
+}
+
 int rt_deinterleave_bands(RtCtx* ctx, const void* d_gathered, uint32_t nx, uint32_t ny, uint32_t band, uint32_t n_shards,
                           void* d_out_rgb_f32, void* d_out_rgb8, void* stream) {
     if (!ctx) return RT_ERR_INVALID;

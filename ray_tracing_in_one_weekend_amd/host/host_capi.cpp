@@ -342,6 +342,14 @@ int rth_scene_quads(const RthScene* s, RtQuads* out) {
     return RT_OK;
 }
 
+int rth_scene_lights(const RthScene* s, RtLights* out, uint32_t* n_found) {
+    if (!s || !out || !s->finished) return RT_ERR_INVALID;
+    out->n = (uint32_t)(s->builder.light_q.size() / 3);
+    out->q = s->builder.light_q.data(), out->u = s->builder.light_u.data(), out->v = s->builder.light_v.data();
+    if (n_found) *n_found = s->builder.n_light_candidates;
+    return RT_OK;
+}
+
 const char* rth_scene_sphere_name(const RthScene* s, uint32_t index) {
     if (!s || !s->finished || index >= s->builder.sph_name.size()) return "";
     return s->builder.sph_name[index].c_str();

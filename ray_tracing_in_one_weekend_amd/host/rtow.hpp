@@ -159,6 +159,17 @@ class FlatSceneBuilder {
         rect_mat.push_back(mat);
         rect_xform.push_back(cur_xform);
         rect_medium.push_back(cur_medium);
+        Vec3A u{0.0f, 0.0f, 0.0f}, v{0.0f, 0.0f, 0.0f}; // the rectangle as a parallelogram in the plane min[axis] (hitable.rs:244-362)
+        if (axis == 0) u.y = mx.y - mn.y, v.z = mx.z - mn.z;
+        else if (axis == 1) u.x = mx.x - mn.x, v.z = mx.z - mn.z;
+        else u.x = mx.x - mn.x, v.y = mx.y - mn.y;
+        note_light(mn, u, v, mat);
+    }
+    // rth_scene_lights: the parallelogram of a BARE Emission rectangle or quad, in the order the world lists them; the first
+    // RT_MAX_LIGHTS are kept and all are counted.  Emitters below wrappers or inside a medium boundary, spheres and triangles are left out.
+    void note_light(Vec3A Q, Vec3A u, Vec3A v, uint32_t mat) {
+        if (cur_xform != RT_NO_XFORM || cur_medium != RT_NO_MEDIUM || mat_type[mat] != RT_MAT_EMISSION) return;
+        if (n_light_candidates++ < RT_MAX_LIGHTS) push3(light_q, Q), push3(light_u, u), push3(light_v, v);
     }
     void push_sphere(Vec3A c, float r, uint32_t mat, const std::string& name) {
         sph_cx.push_back(c.x), sph_cy.push_back(c.y), sph_cz.push_back(c.z), sph_r.push_back(r), sph_mat.push_back(mat);
@@ -180,6 +191,7 @@ class FlatSceneBuilder {
             throw std::runtime_error("flatten: a Quad / Triangle below a wrapper or as a medium boundary (planar primitives are bare: transform the vertices)");
         push3(quad_q, Q), push3(quad_u, u), push3(quad_v, v);
         quad_kind.push_back(kind), quad_mat.push_back(mat);
+        if (kind == RT_PLANAR_QUAD) note_light(Q, u, v, mat);
     }
     // hitable.rs:523-533 ConstantMedium: primitives pushed until end_medium() bound medium `m`
     uint32_t begin_medium(float neg_inv_density, uint32_t mat) {
@@ -237,6 +249,8 @@ class FlatSceneBuilder {
     std::vector<float> quad_q, quad_u, quad_v; // planar table (rt_set_quads): 3 floats per primitive each, kind and material
     std::vector<uint8_t> quad_kind;
     std::vector<uint32_t> quad_mat;
+    std::vector<float> light_q, light_u, light_v; // rth_scene_lights: at most RT_MAX_LIGHTS parallelograms, and how many emitters qualified
+    uint32_t n_light_candidates = 0;
     std::vector<uint32_t> motion_sphere; // motion table: sphere indices (increasing: spheres are pushed in order) and centres at time 1
     std::vector<float> motion_c1;
     std::vector<uint32_t> sph_mat;

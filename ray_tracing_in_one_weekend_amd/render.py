@@ -34,6 +34,8 @@ def main(argv=None):
     ap.add_argument("--focus-dist", type=float, default=10.0, help="distance of the plane of focus (with --aperture)")
     ap.add_argument("--shutter", type=float, nargs=2, default=None, metavar=("OPEN", "CLOSE"),
                     help="shutter interval within [0, 1] for a scene with moving spheres (default: the scene camera's, [0, 1])")
+    ap.add_argument("--light-sampling", action="store_true",
+                    help="aim half of the diffuse bounces at the scene's emissive rectangles and quads (Scene.lights): same mean, less noise")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     ny = a.ny
@@ -55,6 +57,8 @@ def main(argv=None):
     quads = scene.quads  # and so are its quads and triangles
     if quads.n:
         rend.set_quads(quads)
+    if a.light_sampling:
+        rend.set_lights(scene.lights)  # (a moving scene refuses it: RT_ERR_UNSUPPORTED)
     flags = _ffi.FLAG_RUSSIAN_ROULETTE if a.russian_roulette else 0
     params = make_params(a.nx, ny, a.spp, max_depth=a.max_depth, seed=a.seed, spp_slice=a.preview_every, flags=flags)
     if a.preview_every:
