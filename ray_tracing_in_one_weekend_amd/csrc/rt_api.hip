@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -17,6 +18,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 using namespace rt;
@@ -328,160 +330,137 @@ bool scene_is_general(const RtCtx* ctx) { return ctx->general_kernels; }
 bool grid_enabled(const RtCtx* ctx) { return ctx->use_grid && ctx->opt[RT_OPT_GRID] != 1u && !scene_is_general(ctx); }
 bool scene_perlin_lds(const RtCtx* ctx) { return ctx->ds.n_perlin > 0 && ctx->ds.n_perlin <= RT_PERLIN_LDS_MAX_SETS; }
 
-// closest hit of the shards [ip.q0, ip.q1): the tree instantiation that matches the scene, or the list walk
-void launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32_t grid, const StepBuffers& b, const IntersectParams& ip) {
-    const bool rects = scene_is_general(ctx);
+// ---- kernel variants ---------------------------------------------------------------------------------------------
+// k_shade, k_intersect and k_debug_bounce are families of instantiations over feature flags.  A family's key is the set of its flags (one
+// named bit each), `*_variant_exists` is the one rule that says which keys are instantiated — the single place a new flag is declared —
+// and the table, built from the rule at compile time, maps every key to its kernel (nullptr: there is none).  launch_* look a key up,
+// rt_ctx_create walks the same tables for the LDS attribute: no kernel can be launched that was not registered.
+constexpr bool has(unsigned key, unsigned flag) { return (key & flag) != 0u; }
+template <class Table>
+constexpr size_t n_variants(const Table& table) {
+    size_t n = 0;
+    for (auto fn : table) n += fn != nullptr;
+    return n;
+}
+template <size_t N>
+std::string flags_text(unsigned key, const char* const (&names)[N]) { // "GEN RECTS" (for the error of a key without kernel)
+    std::string t;
+    for (size_t k = 0; k < N; ++k)
+        if (has(key, 1u << k)) t += (t.empty() ? "" : " ") + std::string(names[k]);
+    return t.empty() ? "no flag" : t;
+}
+
+// k_shade<PERLIN_LDS, GEN, RECTS, NEST, LENS, MOTION, PLANAR, LIGHTS>
+enum : unsigned { SH_PERLIN_LDS = 1, SH_GEN = 2, SH_RECTS = 4, SH_NEST = 8, SH_LENS = 16, SH_MOTION = 32, SH_PLANAR = 64, SH_LIGHTS = 128, SH_KEYS = 256 };
+const char* const SH_NAMES[] = {"PERLIN_LDS", "GEN", "RECTS", "NEST", "LENS", "MOTION", "PLANAR", "LIGHTS"};
+constexpr bool shade_variant_exists(unsigned k) {
+    return (!has(k, SH_LENS) || has(k, SH_GEN))                              // the lens bends primary rays only
+           && (!has(k, SH_NEST) || has(k, SH_RECTS))                         // wrapper chains and media are a general scene's
+           && (!has(k, SH_PLANAR) || (has(k, SH_RECTS) && has(k, SH_NEST)))  // planar primitives run in the general NEST form
+           && !(has(k, SH_MOTION) && (has(k, SH_PLANAR) || has(k, SH_LIGHTS))); // rt_set_motion refuses rt_set_quads and rt_set_lights
+}
+using ShadeKernel = decltype(&k_shade<false, false, false>);
+template <unsigned K>
+constexpr ShadeKernel shade_variant() {
+    if constexpr (shade_variant_exists(K))
+        return &k_shade<has(K, SH_PERLIN_LDS), has(K, SH_GEN), has(K, SH_RECTS), has(K, SH_NEST), has(K, SH_LENS), has(K, SH_MOTION), has(K, SH_PLANAR), has(K, SH_LIGHTS)>;
+    else return nullptr;
+}
+template <size_t... K>
+constexpr std::array<ShadeKernel, sizeof...(K)> shade_variants(std::index_sequence<K...>) { return {{shade_variant<K>()...}}; }
+constexpr auto SHADE_KERNELS = shade_variants(std::make_index_sequence<SH_KEYS>{});
+static_assert(n_variants(SHADE_KERNELS) == 66, "k_shade: a feature that adds instantiations changes this number on purpose");
+
+// k_intersect<RT_BVH_BLOCK, GEN, RECTS, LDS_NODES, GLDS, NEST, LENS, MOTION, PLANAR>
+enum : unsigned { IS_GEN = 1, IS_RECTS = 2, IS_LDS_NODES = 4, IS_GLDS = 8, IS_NEST = 16, IS_LENS = 32, IS_MOTION = 64, IS_PLANAR = 128, IS_KEYS = 256 };
+const char* const IS_NAMES[] = {"GEN", "RECTS", "LDS_NODES", "GLDS", "NEST", "LENS", "MOTION", "PLANAR"};
+constexpr bool isect_variant_exists(unsigned k) {
+    return (!has(k, IS_LENS) || has(k, IS_GEN))                                                       // the lens bends primary rays only
+           && (has(k, IS_RECTS) || (has(k, IS_LDS_NODES) && !has(k, IS_GLDS) && !has(k, IS_NEST)))    // the sphere-only form: tree in LDS, no tables
+           && (!has(k, IS_PLANAR) || (has(k, IS_RECTS) && has(k, IS_NEST) && !has(k, IS_MOTION)));    // as k_shade
+}
+using IsectKernel = decltype(&k_intersect<RT_BVH_BLOCK, false, false, true, false>);
+template <unsigned K>
+constexpr IsectKernel isect_variant() {
+    if constexpr (isect_variant_exists(K))
+        return &k_intersect<RT_BVH_BLOCK, has(K, IS_GEN), has(K, IS_RECTS), has(K, IS_LDS_NODES), has(K, IS_GLDS), has(K, IS_NEST), has(K, IS_LENS), has(K, IS_MOTION), has(K, IS_PLANAR)>;
+    else return nullptr;
+}
+template <size_t... K>
+constexpr std::array<IsectKernel, sizeof...(K)> isect_variants(std::index_sequence<K...>) { return {{isect_variant<K>()...}}; }
+constexpr auto ISECT_KERNELS = isect_variants(std::make_index_sequence<IS_KEYS>{});
+static_assert(n_variants(ISECT_KERNELS) == 66, "k_intersect: a feature that adds instantiations changes this number on purpose");
+
+// k_debug_bounce<BLOCK, USE_BVH, LDS_NODES, MOTION, PLANAR, LIGHTS>: every set for each of the three search forms (rt_debug_bounce)
+enum : unsigned { DB_MOTION = 1, DB_PLANAR = 2, DB_LIGHTS = 4, DB_KEYS = 8 };
+const char* const DB_NAMES[] = {"MOTION", "PLANAR", "LIGHTS"};
+constexpr bool debug_variant_exists(unsigned k) { return !has(k, DB_MOTION) || k == DB_MOTION; } // as k_shade
+using DebugKernel = decltype(&k_debug_bounce<256, false, true, false, false, false>);
+template <int BLOCK, bool USE_BVH, bool LDS_NODES, unsigned K>
+constexpr DebugKernel debug_variant() {
+    if constexpr (debug_variant_exists(K)) return &k_debug_bounce<BLOCK, USE_BVH, LDS_NODES, has(K, DB_MOTION), has(K, DB_PLANAR), has(K, DB_LIGHTS)>;
+    else return nullptr;
+}
+template <int BLOCK, bool USE_BVH, bool LDS_NODES, size_t... K>
+constexpr std::array<DebugKernel, sizeof...(K)> debug_variants(std::index_sequence<K...>) { return {{debug_variant<BLOCK, USE_BVH, LDS_NODES, K>()...}}; }
+constexpr auto DEBUG_KERNELS_TREE_L2 = debug_variants<RT_BVH_BLOCK, true, false>(std::make_index_sequence<DB_KEYS>{});
+constexpr auto DEBUG_KERNELS_TREE_LDS = debug_variants<RT_BVH_BLOCK, true, true>(std::make_index_sequence<DB_KEYS>{});
+constexpr auto DEBUG_KERNELS_BRUTE = debug_variants<256, false, true>(std::make_index_sequence<DB_KEYS>{});
+static_assert(n_variants(DEBUG_KERNELS_TREE_L2) + n_variants(DEBUG_KERNELS_TREE_LDS) + n_variants(DEBUG_KERNELS_BRUTE) == 15, "k_debug_bounce");
+
+// closest hit of the shards [ip.q0, ip.q1): the tree instantiation that matches the scene, or the grid / list walk
+int launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32_t grid, const StepBuffers& b, const IntersectParams& ip) {
     if (use_bvh && !gen && grid_enabled(ctx)) { // sphere-only scene, depth >= 1: the grid walk (rt_grid.h), same hit records
         const size_t mlds = ctx->grid_lds + ctx->motion_lds;
         if (b.motion && ctx->grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid_motion<true>, dim3(grid), dim3(RT_BVH_BLOCK), mlds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
         else if (b.motion) hipLaunchKernelGGL(k_intersect_grid_motion<false>, dim3(grid), dim3(RT_BVH_BLOCK), mlds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
         else if (ctx->grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid<true>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->grid_lds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
         else hipLaunchKernelGGL(k_intersect_grid<false>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->grid_lds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
-        return;
+        return RT_OK;
     }
-    if (b.planar && use_bvh) {
-        // planar primitives (rt_set_quads): the general kernel in its NEST form (loops over wrapper chains and media: the same bits
-        // for a scene that needs none), so one instantiation per tree placement, table placement and depth-0 form
-#define RT_LAUNCH_ISECT_P(G, N, T, L)                                                                                                     \
-    hipLaunchKernelGGL((k_intersect<RT_BVH_BLOCK, G, true, N, T, true, L, false, true>), dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg, \
-                       ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd)
-#define RT_LAUNCH_ISECT_PT(G, N, L)                          \
-    do {                                                     \
-        if (ctx->general_lds) RT_LAUNCH_ISECT_P(G, N, true, L); \
-        else RT_LAUNCH_ISECT_P(G, N, false, L);              \
-    } while (0)
-#define RT_LAUNCH_ISECT_PN(G, L)                             \
-    do {                                                     \
-        if (ctx->bvh_in_lds) RT_LAUNCH_ISECT_PT(G, true, L); \
-        else RT_LAUNCH_ISECT_PT(G, false, L);                \
-    } while (0)
-        if (gen && b.lens) RT_LAUNCH_ISECT_PN(true, true);
-        else if (gen) RT_LAUNCH_ISECT_PN(true, false);
-        else RT_LAUNCH_ISECT_PN(false, false);
-#undef RT_LAUNCH_ISECT_PN
-#undef RT_LAUNCH_ISECT_PT
-#undef RT_LAUNCH_ISECT_P
-        return;
-    }
-    if (b.planar) {
-        hipLaunchKernelGGL(k_intersect_list_planar, dim3(ip.q1 - ip.q0), dim3(256), 0, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
-        return;
-    }
-#define RT_LAUNCH_ISECT_M(G, R, N, T, X, L)                                                                                      \
-    hipLaunchKernelGGL((k_intersect<RT_BVH_BLOCK, G, R, N, T, X, L, true>), dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg, ctx->ds, \
-                       b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd)
-#define RT_LAUNCH_ISECT_X(G, R, N, T, X)                                                                               \
-    do {                                                                                                                \
-        if (b.motion && G && b.lens) RT_LAUNCH_ISECT_M(G, R, N, T, X, G);                                               \
-        else if (b.motion) RT_LAUNCH_ISECT_M(G, R, N, T, X, false);                                                     \
-        else if (G && b.lens)                                                                                                \
-            hipLaunchKernelGGL((k_intersect<RT_BVH_BLOCK, G, R, N, T, X, G>), dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg, \
-                               ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);                                      \
-        else                                                                                                            \
-            hipLaunchKernelGGL((k_intersect<RT_BVH_BLOCK, G, R, N, T, X>), dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg,  \
-                               ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);                                      \
-    } while (0)
-#define RT_LAUNCH_ISECT(G, R, N, T) RT_LAUNCH_ISECT_X(G, R, N, T, false)
-    // general scenes: tables in LDS or not; and (ctx->nest) the instantiation whose wrapper chains and media masks are loops
-#define RT_LAUNCH_ISECT_G(G, N)                       \
-    do {                                              \
-        if (ctx->nest) {                              \
-            if (ctx->general_lds) RT_LAUNCH_ISECT_X(G, true, N, true, true); \
-            else RT_LAUNCH_ISECT_X(G, true, N, false, true);      \
-        } else if (ctx->general_lds) RT_LAUNCH_ISECT(G, true, N, true); \
-        else RT_LAUNCH_ISECT(G, true, N, false);      \
-    } while (0)
-    // trees that do not fit LDS use the general instantiation (R = true works for sphere-only scenes too)
-    if (use_bvh && !ctx->bvh_in_lds && gen) RT_LAUNCH_ISECT_G(true, false);
-    else if (use_bvh && !ctx->bvh_in_lds) RT_LAUNCH_ISECT_G(false, false);
-    else if (use_bvh && gen && rects) RT_LAUNCH_ISECT_G(true, true);
-    else if (use_bvh && gen) RT_LAUNCH_ISECT(true, false, true, false);
-    else if (use_bvh && rects) RT_LAUNCH_ISECT_G(false, true);
-    else if (use_bvh) RT_LAUNCH_ISECT(false, false, true, false);
-#undef RT_LAUNCH_ISECT_G
-#undef RT_LAUNCH_ISECT
-#undef RT_LAUNCH_ISECT_X
-#undef RT_LAUNCH_ISECT_M
-    else {
+    if (!use_bvh) { // no tree (or RT_FLAG_BRUTE_FORCE): every primitive, one workgroup per shard
         const size_t list_lds = (size_t)std::min<uint32_t>(std::max<uint32_t>(ctx->ds.n_spheres, 1u), RT_SPHERE_TILE) * sizeof(float4);
-        if (b.motion) hipLaunchKernelGGL(k_intersect_list_motion, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        if (b.planar) hipLaunchKernelGGL(k_intersect_list_planar, dim3(ip.q1 - ip.q0), dim3(256), 0, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        else if (b.motion) hipLaunchKernelGGL(k_intersect_list_motion, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
         else hipLaunchKernelGGL(k_intersect_list, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        return RT_OK;
     }
+    unsigned k = 0;
+    if (gen) k |= IS_GEN;                                               // depth 0 with the primary rays made in the kernel (render_impl)
+    if (scene_is_general(ctx) || !ctx->bvh_in_lds || b.planar) k |= IS_RECTS; // general scene; trees that do not fit LDS use the general instantiation
+                                                                        // (it works for sphere-only scenes too); planar primitives (rt_set_quads) likewise
+    if (ctx->bvh_in_lds) k |= IS_LDS_NODES;                             // tree and geometry staged in LDS (rt_scene_upload), else read through L2
+    if (has(k, IS_RECTS) && ctx->general_lds) k |= IS_GLDS;             // the wrapper / medium tables fit LDS beside them (rt_scene_upload)
+    if (has(k, IS_RECTS) && (ctx->nest || b.planar)) k |= IS_NEST;      // wrapper chains and media masks as loops (rt_scene_upload); planar primitives always
+                                                                        // (the same bits for a scene that needs none), so one instantiation per placement
+    if (gen && b.lens) k |= IS_LENS;                                    // depth 0 through the thin lens (rt_set_lens)
+    if (b.motion) k |= IS_MOTION;                                       // moving spheres (rt_set_motion)
+    if (b.planar) k |= IS_PLANAR;                                       // planar primitives (rt_set_quads)
+    const IsectKernel fn = ISECT_KERNELS[k];
+    if (!fn) return fail(ctx, RT_ERR_STATE, "launch_intersect: no k_intersect instantiation for " + flags_text(k, IS_NAMES));
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+    return RT_OK;
 }
 
 // shading of the shards [sp.q0, sp.q0 + n_shards); `fused_lists`: depth 0 of a sphere-only scene with candidate lists
-void launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32_t n_shards, const StepBuffers& b, const ShadeParams& sp) {
-    const bool rects = scene_is_general(ctx), perlin_lds = scene_perlin_lds(ctx);
+int launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32_t n_shards, const StepBuffers& b, const ShadeParams& sp) {
+    const bool perlin_lds = scene_perlin_lds(ctx);
     // sphere geometry for the closest hit inside k_shade<GEN>
     const uint32_t n_fused = (gen && fused_lists) ? ctx->ds.n_spheres * (b.motion ? 2u : 1u) : 0u; // (MOTION: the displacements behind the geometry)
     const size_t shade_lds = shade_lds_bytes(ctx->ds.n_prims + ctx->ds.n_media + (b.planar ? ctx->gplanar.n : 0u), perlin_lds ? ctx->ds.n_perlin : 0u, n_fused, !gen && sp.sort);
-    if (b.lights) { // a light set (rt_set_lights): the same choice among the forms as below, without MOTION (the two refuse each other)
-#define RT_LAUNCH_SHADE_L(P, G, R, X, L, Q)                                                                                                    \
-    hipLaunchKernelGGL((k_shade<P, G, R, X, L, false, Q, true>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, \
-                       b.cout, b.rad, sp, b.totals, b.gpd)
-#define RT_LAUNCH_SHADE_LR(P, G, L)                                           \
-    do {                                                                      \
-        if (b.planar) RT_LAUNCH_SHADE_L(P, G, true, true, L, true);           \
-        else if (rects && ctx->nest) RT_LAUNCH_SHADE_L(P, G, true, true, L, false); \
-        else if (rects) RT_LAUNCH_SHADE_L(P, G, true, false, L, false);       \
-        else RT_LAUNCH_SHADE_L(P, G, false, false, L, false);                 \
-    } while (0)
-#define RT_LAUNCH_SHADE_LP(G, L)                        \
-    do {                                                \
-        if (perlin_lds) RT_LAUNCH_SHADE_LR(true, G, L); \
-        else RT_LAUNCH_SHADE_LR(false, G, L);           \
-    } while (0)
-        if (gen && b.lens) RT_LAUNCH_SHADE_LP(true, true);
-        else if (gen) RT_LAUNCH_SHADE_LP(true, false);
-        else RT_LAUNCH_SHADE_LP(false, false);
-#undef RT_LAUNCH_SHADE_LP
-#undef RT_LAUNCH_SHADE_LR
-#undef RT_LAUNCH_SHADE_L
-        return;
-    }
-    if (b.planar) { // (general, NEST: launch_intersect)
-#define RT_LAUNCH_SHADE_P(P, G, L)                                                                                                          \
-    hipLaunchKernelGGL((k_shade<P, G, true, true, L, false, true>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, \
-                       b.cout, b.rad, sp, b.totals, b.gpd)
-#define RT_LAUNCH_SHADE_PP(G, L)                   \
-    do {                                           \
-        if (perlin_lds) RT_LAUNCH_SHADE_P(true, G, L); \
-        else RT_LAUNCH_SHADE_P(false, G, L);       \
-    } while (0)
-        if (gen && b.lens) RT_LAUNCH_SHADE_PP(true, true);
-        else if (gen) RT_LAUNCH_SHADE_PP(true, false);
-        else RT_LAUNCH_SHADE_PP(false, false);
-#undef RT_LAUNCH_SHADE_PP
-#undef RT_LAUNCH_SHADE_P
-        return;
-    }
-#define RT_LAUNCH_SHADE_M(P, G, R, X, L)                                                                                                       \
-    hipLaunchKernelGGL((k_shade<P, G, R, X, L, true>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, b.cout, b.rad, \
-                       sp, b.totals, b.gpd)
-#define RT_LAUNCH_SHADE(P, G, R, X)                                                                                                      \
-    do {                                                                                                                                  \
-        if (b.motion && G && b.lens) RT_LAUNCH_SHADE_M(P, G, R, X, G);                                                                    \
-        else if (b.motion) RT_LAUNCH_SHADE_M(P, G, R, X, false);                                                                          \
-        else if (G && b.lens)                                                                                                                  \
-            hipLaunchKernelGGL((k_shade<P, G, R, X, G>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, b.cout, \
-                               b.rad, sp, b.totals, b.gpd);                                                                               \
-        else                                                                                                                              \
-            hipLaunchKernelGGL((k_shade<P, G, R, X>), dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, b.cout,    \
-                               b.rad, sp, b.totals, b.gpd);                                                                               \
-    } while (0)
-#define RT_LAUNCH_SHADE_R(P, G)        \
-    do {                               \
-        if (rects && ctx->nest) RT_LAUNCH_SHADE(P, G, true, true); \
-        else if (rects) RT_LAUNCH_SHADE(P, G, true, false); \
-        else RT_LAUNCH_SHADE(P, G, false, false);      \
-    } while (0)
-    if (perlin_lds && gen) RT_LAUNCH_SHADE_R(true, true);
-    else if (perlin_lds) RT_LAUNCH_SHADE_R(true, false);
-    else if (gen) RT_LAUNCH_SHADE_R(false, true);
-    else RT_LAUNCH_SHADE_R(false, false);
-#undef RT_LAUNCH_SHADE_R
-#undef RT_LAUNCH_SHADE
-#undef RT_LAUNCH_SHADE_M
+    unsigned k = 0;
+    if (perlin_lds) k |= SH_PERLIN_LDS;                              // the scene's Perlin tables fit LDS (scene_perlin_lds)
+    if (gen) k |= SH_GEN;                                            // depth 0 with the primary rays made in the kernel (render_impl)
+    if (scene_is_general(ctx) || b.planar) k |= SH_RECTS;            // general scene; planar primitives (rt_set_quads) are shaded by the general form
+    if (has(k, SH_RECTS) && (ctx->nest || b.planar)) k |= SH_NEST;   // as launch_intersect
+    if (gen && b.lens) k |= SH_LENS;                                 // depth 0 through the thin lens (rt_set_lens)
+    if (b.motion) k |= SH_MOTION;                                    // moving spheres (rt_set_motion)
+    if (b.planar) k |= SH_PLANAR;                                    // planar primitives (rt_set_quads)
+    if (b.lights) k |= SH_LIGHTS;                                    // a light set (rt_set_lights)
+    const ShadeKernel fn = SHADE_KERNELS[k];
+    if (!fn) return fail(ctx, RT_ERR_STATE, "launch_shade: no k_shade instantiation for " + flags_text(k, SH_NAMES));
+    hipLaunchKernelGGL(fn, dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, b.cout, b.rad, sp, b.totals, b.gpd);
+    return RT_OK;
 }
 
 // Where the work buffers of a slice lie in the pool: two ray queues of n_queue rays (a / b records interleaved when RT_QSTRIDE is
@@ -930,84 +909,16 @@ int rt_ctx_create(int device_id, RtCtx** out_ctx) {
     // Kernels whose dynamic LDS can exceed the 64 KB default: the attribute is process-global per function, so it is
     // set to the device limit once (a per-scene value would be lowered by the next context's smaller scene).
     {
-        const void* variants[] = {
-#define RT_ISECT_VARIANTS(G, R, N, T) reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, G, R, N, T>)
-            RT_ISECT_VARIANTS(false, false, true, false), RT_ISECT_VARIANTS(false, true, true, false),
-            RT_ISECT_VARIANTS(true, false, true, false),  RT_ISECT_VARIANTS(true, true, true, false),
-            RT_ISECT_VARIANTS(false, true, false, false), RT_ISECT_VARIANTS(true, true, false, false),
-            RT_ISECT_VARIANTS(false, true, true, true),   RT_ISECT_VARIANTS(true, true, true, true),
-            RT_ISECT_VARIANTS(false, true, false, true),  RT_ISECT_VARIANTS(true, true, false, true),
-#undef RT_ISECT_VARIANTS
-#define RT_ISECT_VARIANTS(G, N, T) reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, G, true, N, T, true>)
-            RT_ISECT_VARIANTS(false, true, false), RT_ISECT_VARIANTS(true, true, false), RT_ISECT_VARIANTS(false, false, false), RT_ISECT_VARIANTS(true, false, false),
-            RT_ISECT_VARIANTS(false, true, true),  RT_ISECT_VARIANTS(true, true, true),  RT_ISECT_VARIANTS(false, false, true),  RT_ISECT_VARIANTS(true, false, true),
-#undef RT_ISECT_VARIANTS
-            reinterpret_cast<const void*>(&k_intersect_grid<true>), reinterpret_cast<const void*>(&k_intersect_grid<false>),
-            reinterpret_cast<const void*>(&k_debug_bounce<RT_BVH_BLOCK, true, true>),
-            reinterpret_cast<const void*>(&k_debug_bounce<RT_BVH_BLOCK, true, false>),
-#define RT_SHADE_VARIANTS(P, G) reinterpret_cast<const void*>(&k_shade<P, G, false>), reinterpret_cast<const void*>(&k_shade<P, G, true>), reinterpret_cast<const void*>(&k_shade<P, G, true, true>)
-            RT_SHADE_VARIANTS(true, true), RT_SHADE_VARIANTS(true, false), RT_SHADE_VARIANTS(false, true), RT_SHADE_VARIANTS(false, false),
-#undef RT_SHADE_VARIANTS
-            // the depth-0 instantiations of the thin lens (rt_set_lens): every GEN one launch_intersect / launch_shade can pick
-#define RT_ISECT_LENS(R, N, T, X) reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, true, R, N, T, X, true>)
-            RT_ISECT_LENS(false, true, false, false), RT_ISECT_LENS(true, true, false, false), RT_ISECT_LENS(true, true, true, false),
-            RT_ISECT_LENS(true, false, false, false), RT_ISECT_LENS(true, false, true, false), RT_ISECT_LENS(true, true, false, true),
-            RT_ISECT_LENS(true, true, true, true),    RT_ISECT_LENS(true, false, false, true), RT_ISECT_LENS(true, false, true, true),
-#undef RT_ISECT_LENS
-#define RT_SHADE_LENS(P) reinterpret_cast<const void*>(&k_shade<P, true, false, false, true>), reinterpret_cast<const void*>(&k_shade<P, true, true, false, true>), \
-                         reinterpret_cast<const void*>(&k_shade<P, true, true, true, true>)
-            RT_SHADE_LENS(true), RT_SHADE_LENS(false),
-#undef RT_SHADE_LENS
-            // the instantiations of moving spheres (rt_set_motion): every one launch_intersect / launch_shade can pick
-#define RT_ISECT_MOTION(R, N, T, X)                                                                     \
-    reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, false, R, N, T, X, false, true>),          \
-        reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, true, R, N, T, X, false, true>),       \
-        reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, true, R, N, T, X, true, true>)
-            RT_ISECT_MOTION(false, true, false, false), RT_ISECT_MOTION(true, true, false, false), RT_ISECT_MOTION(true, true, true, false),
-            RT_ISECT_MOTION(true, false, false, false), RT_ISECT_MOTION(true, false, true, false), RT_ISECT_MOTION(true, true, false, true),
-            RT_ISECT_MOTION(true, true, true, true),    RT_ISECT_MOTION(true, false, false, true), RT_ISECT_MOTION(true, false, true, true),
-#undef RT_ISECT_MOTION
-#define RT_SHADE_MOTION(P, R, X)                                                                                                           \
-    reinterpret_cast<const void*>(&k_shade<P, false, R, X, false, true>), reinterpret_cast<const void*>(&k_shade<P, true, R, X, false, true>), \
-        reinterpret_cast<const void*>(&k_shade<P, true, R, X, true, true>)
-            RT_SHADE_MOTION(true, false, false), RT_SHADE_MOTION(true, true, false), RT_SHADE_MOTION(true, true, true),
-            RT_SHADE_MOTION(false, false, false), RT_SHADE_MOTION(false, true, false), RT_SHADE_MOTION(false, true, true),
-#undef RT_SHADE_MOTION
-            reinterpret_cast<const void*>(&k_intersect_grid_motion<true>), reinterpret_cast<const void*>(&k_intersect_grid_motion<false>),
-            reinterpret_cast<const void*>(&k_debug_bounce_motion<RT_BVH_BLOCK, true, true>),
-            reinterpret_cast<const void*>(&k_debug_bounce_motion<RT_BVH_BLOCK, true, false>),
-            // the instantiations of planar primitives (rt_set_quads): every one launch_intersect / launch_shade can pick
-#define RT_ISECT_PLANAR(N, T)                                                                                   \
-    reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, false, true, N, T, true, false, false, true>),     \
-        reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, true, true, N, T, true, false, false, true>),  \
-        reinterpret_cast<const void*>(&k_intersect<RT_BVH_BLOCK, true, true, N, T, true, true, false, true>)
-            RT_ISECT_PLANAR(true, true), RT_ISECT_PLANAR(true, false), RT_ISECT_PLANAR(false, true), RT_ISECT_PLANAR(false, false),
-#undef RT_ISECT_PLANAR
-#define RT_SHADE_PLANAR(P)                                                                   \
-    reinterpret_cast<const void*>(&k_shade<P, false, true, true, false, false, true>),       \
-        reinterpret_cast<const void*>(&k_shade<P, true, true, true, false, false, true>),    \
-        reinterpret_cast<const void*>(&k_shade<P, true, true, true, true, false, true>)
-            RT_SHADE_PLANAR(true), RT_SHADE_PLANAR(false),
-#undef RT_SHADE_PLANAR
-            reinterpret_cast<const void*>(&k_debug_bounce_planar<RT_BVH_BLOCK, true, true>),
-            reinterpret_cast<const void*>(&k_debug_bounce_planar<RT_BVH_BLOCK, true, false>),
-            // the instantiations of a light set (rt_set_lights): every k_shade launch_shade can pick, and the debug-bounce kernels
-#define RT_SHADE_LIGHTS_G(P, R, X, Q)                                                          \
-    reinterpret_cast<const void*>(&k_shade<P, false, R, X, false, false, Q, true>),            \
-        reinterpret_cast<const void*>(&k_shade<P, true, R, X, false, false, Q, true>),         \
-        reinterpret_cast<const void*>(&k_shade<P, true, R, X, true, false, Q, true>)
-#define RT_SHADE_LIGHTS(P) RT_SHADE_LIGHTS_G(P, false, false, false), RT_SHADE_LIGHTS_G(P, true, false, false), RT_SHADE_LIGHTS_G(P, true, true, false), RT_SHADE_LIGHTS_G(P, true, true, true)
-            RT_SHADE_LIGHTS(true), RT_SHADE_LIGHTS(false),
-#undef RT_SHADE_LIGHTS
-#undef RT_SHADE_LIGHTS_G
-            reinterpret_cast<const void*>(&k_debug_bounce_lights<RT_BVH_BLOCK, true, true, false>),
-            reinterpret_cast<const void*>(&k_debug_bounce_lights<RT_BVH_BLOCK, true, false, false>),
-            reinterpret_cast<const void*>(&k_debug_bounce_lights<RT_BVH_BLOCK, true, true, true>),
-            reinterpret_cast<const void*>(&k_debug_bounce_lights<RT_BVH_BLOCK, true, false, true>),
+        auto raise_lds = [&](auto fn) { // (nullptr: a key without kernel)
+            if (fn && e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_limit);
         };
-        for (const void* fn : variants)
-            if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_limit)) != hipSuccess)
-                return bail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
+        for (auto fn : ISECT_KERNELS) raise_lds(fn);
+        for (auto fn : SHADE_KERNELS) raise_lds(fn);
+        for (auto fn : DEBUG_KERNELS_TREE_L2) raise_lds(fn);
+        for (auto fn : DEBUG_KERNELS_TREE_LDS) raise_lds(fn); // (DEBUG_KERNELS_BRUTE stage one tile of spheres: below the default)
+        raise_lds(&k_intersect_grid<true>), raise_lds(&k_intersect_grid<false>);
+        raise_lds(&k_intersect_grid_motion<true>), raise_lds(&k_intersect_grid_motion<false>);
+        if (e != hipSuccess) return bail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
     }
     if ((e = hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
     if ((e = hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
@@ -1738,12 +1649,12 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
             const StepBuffers sb{qi, qo, qhit, cin, cout, rad, totals, gpd, lens, ctx->motion, ctx->planar, ctx->lights};
             // depth 0 of a sphere-only scene whose pixels all have a candidate list: k_shade<GEN> finds every closest hit itself
             const bool no_primary_trace = gen && !rects && gp.lists != nullptr && no_overflow;
-            if (!no_primary_trace) launch_intersect(ctx, sg, use_bvh, gen, isect_grid_g, sb, ip);
+            if (!no_primary_trace && (rc = launch_intersect(ctx, sg, use_bvh, gen, isect_grid_g, sb, ip))) return rc;
             if (td) RT_HIP(ctx, hipEventRecord(ctx->depth_events[3 * (size_t)depth + 1], st));
             // class sort from depth 1 on: primary rays are coherent already (measured: sorting depth 0 costs 8 %)
             const ShadeParams sp{nq, cap, depth, prm->max_depth, depth > 0 ? 1u : 0u,
                                  (prm->flags & RT_FLAG_RUSSIAN_ROULETTE) ? 1u : 0u, q0};
-            launch_shade(ctx, sg, gen, !rects && gp.lists != nullptr, q1 - q0, sb, sp);
+            if ((rc = launch_shade(ctx, sg, gen, !rects && gp.lists != nullptr, q1 - q0, sb, sp))) return rc;
             if (td) RT_HIP(ctx, hipEventRecord(ctx->depth_events[3 * (size_t)depth + 2], st));
             if (grp == 0u) n_trace_launches += no_primary_trace ? 1u : 2u;
         }
@@ -2571,9 +2482,9 @@ static int debug_bounce_production(RtCtx* ctx, const RtBounceIO* io) {
     const StepBuffers sb{Q[0], Q[1], wv.qhit, counts, counts + nq, wv.rad,
                          (unsigned long long*)ctx->totals.p, (const GenParams*)ctx->genp.p, false, ctx->motion, ctx->planar, ctx->lights};
     const IntersectParams ip{nq, cap, (int)io->depth, 0u, nq};
-    launch_intersect(ctx, st, use_bvh, false, qg.isect_grid, sb, ip);
+    if ((rc = launch_intersect(ctx, st, use_bvh, false, qg.isect_grid, sb, ip))) return rc;
     const ShadeParams sp{nq, cap, (int)io->depth, 0x7FFFFFFF, 1u, 0u, 0u};
-    launch_shade(ctx, st, false, false, nq, sb, sp);
+    if ((rc = launch_shade(ctx, st, false, false, nq, sb, sp))) return rc;
     RT_HIP(ctx, hipGetLastError());
     std::vector<float4> ha((size_t)nq * cap), hb((size_t)nq * cap);
     std::vector<float> hrad((size_t)n * RT_RAD_FLOATS);
@@ -2647,42 +2558,16 @@ int rt_debug_bounce(RtCtx* ctx, const RtBounceIO* io) {
     RT_HIP(ctx, hipMemcpyAsync(base + off_d, io->in_d, 3 * n * 4, hipMemcpyHostToDevice, st));
     RT_HIP(ctx, hipMemcpyAsync(base + off_key, io->in_key, 2 * n * 4, hipMemcpyHostToDevice, st));
     const bool use_bvh = ctx->use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
-#define RT_DEBUG_BOUNCE(B, U, L, LDS)                                                                                                      \
-    do {                                                                                                                                   \
-        if (ctx->lights && ctx->planar)                                                                                                    \
-            hipLaunchKernelGGL((k_debug_bounce_lights<B, U, L, true>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n, \
-                               (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
-                               base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive),   \
-                               ctx->gplanar, ctx->glights);                                                                                \
-        else if (ctx->lights)                                                                                                              \
-            hipLaunchKernelGGL((k_debug_bounce_lights<B, U, L, false>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n, \
-                               (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
-                               base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive),   \
-                               ctx->gplanar, ctx->glights);                                                                                \
-        else if (ctx->planar)                                                                                                              \
-            hipLaunchKernelGGL((k_debug_bounce_planar<B, U, L>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n, \
-                               (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
-                               base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive),   \
-                               ctx->gplanar);                                                                                              \
-        else if (ctx->motion)                                                                                                              \
-            hipLaunchKernelGGL((k_debug_bounce_motion<B, U, L>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n, \
-                               (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
-                               base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive),   \
-                               ctx->gmotion);                                                                                              \
-        else                                                                                                                               \
-            hipLaunchKernelGGL((k_debug_bounce<B, U, L>), dim3((unsigned)((n + B - 1) / B)), dim3(B), LDS, st, ctx->ds, (uint32_t)n,       \
-                               (int)io->depth, base + off_o, base + off_d, (const uint32_t*)(base + off_key), (int*)(base + off_hit),      \
-                               base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd, (uint8_t*)(base + off_alive));  \
-    } while (0)
-    if (use_bvh && !ctx->bvh_in_lds) {
-        RT_DEBUG_BOUNCE(RT_BVH_BLOCK, true, false, ctx->isect_lds);
-    } else if (use_bvh) {
-        RT_DEBUG_BOUNCE(RT_BVH_BLOCK, true, true, ctx->isect_lds);
-    } else {
-        const size_t lds_bytes = (size_t)std::min<uint32_t>(std::max<uint32_t>(ctx->ds.n_spheres, 1u), RT_SPHERE_TILE) * sizeof(float4);
-        RT_DEBUG_BOUNCE(256, false, true, lds_bytes);
-    }
-#undef RT_DEBUG_BOUNCE
+    // the search form (the tree out of L2 or staged in LDS as k_intersect has it, or every primitive), then the sets of the context
+    const auto& forms = !use_bvh ? DEBUG_KERNELS_BRUTE : ctx->bvh_in_lds ? DEBUG_KERNELS_TREE_LDS : DEBUG_KERNELS_TREE_L2;
+    const unsigned block = use_bvh ? RT_BVH_BLOCK : 256u;
+    const size_t lds_bytes = use_bvh ? ctx->isect_lds : (size_t)std::min<uint32_t>(std::max<uint32_t>(ctx->ds.n_spheres, 1u), RT_SPHERE_TILE) * sizeof(float4);
+    const unsigned k = (ctx->motion ? DB_MOTION : 0u) | (ctx->planar ? DB_PLANAR : 0u) | (ctx->lights ? DB_LIGHTS : 0u);
+    const DebugKernel fn = forms[k];
+    if (!fn) return fail(ctx, RT_ERR_STATE, "rt_debug_bounce: no k_debug_bounce instantiation for " + flags_text(k, DB_NAMES));
+    hipLaunchKernelGGL(fn, dim3((unsigned)((n + block - 1) / block)), dim3(block), lds_bytes, st, ctx->ds, (uint32_t)n, (int)io->depth, base + off_o, base + off_d,
+                       (const uint32_t*)(base + off_key), (int*)(base + off_hit), base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd,
+                       (uint8_t*)(base + off_alive), DebugSets{ctx->gmotion, ctx->gplanar, ctx->glights});
     RT_HIP(ctx, hipGetLastError());
     RT_HIP(ctx, hipMemcpyAsync(io->out_hit, base + off_hit, n * 4, hipMemcpyDeviceToHost, st));
     RT_HIP(ctx, hipMemcpyAsync(io->out_t, base + off_t, n * 4, hipMemcpyDeviceToHost, st));

@@ -1733,152 +1733,26 @@ __global__ __launch_bounds__(256) void k_debug_arithmetic(uint32_t op, uint32_t 
     else out[i] = __uint_as_float(sat_u32(x[i]));
 }
 
-// Test hook: one bounce for caller-given rays, no queues (rt_debug_bounce).
-template <int BLOCK, bool USE_BVH, bool LDS_NODES>
+// Test hook: one bounce for caller-given rays, no queues (rt_debug_bounce).  MOTION (rt_set_motion): the ray's time comes from counter
+// 254 of in_key, the displacements are read from HBM.  PLANAR (rt_set_quads) and LIGHTS (rt_set_lights): the closest hit is the general
+// one (the same roots on the same operands); only shade() knows the lights.  The instantiations: rt_api.hip "kernel variants".
+struct DebugSets {
+    GenMotion motion;
+    GenPlanar planar;
+    GenLights lights;
+};
+template <int BLOCK, bool USE_BVH, bool LDS_NODES, bool MOTION, bool PLANAR, bool LIGHTS>
 __global__ __launch_bounds__(BLOCK) void k_debug_bounce(DevScene sc, uint32_t n, int depth, const float* __restrict__ in_o,
                                                         const float* __restrict__ in_d, const uint32_t* __restrict__ in_key,
                                                         int* __restrict__ out_hit, float* __restrict__ out_t,
                                                         float* __restrict__ out_rad, float* __restrict__ out_att,
                                                         float* __restrict__ out_o, float* __restrict__ out_d,
-                                                        uint8_t* __restrict__ out_alive) {
+                                                        uint8_t* __restrict__ out_alive, DebugSets g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     const bool active = i < n;
-    V3 o = splat(0.0f), d = v3(0.f, 0.f, 1.f);
-    if (active) {
-        o = v3(in_o[3 * i], in_o[3 * i + 1], in_o[3 * i + 2]);
-        d = v3(in_d[3 * i], in_d[3 * i + 1], in_d[3 * i + 2]);
-    }
-    float tbest = RT_FLT_MAX;
-    int hit = -1;
-    const float a = length_squared(d);
-    if (USE_BVH) {
-        const BvhLds L = stage_bvh<BLOCK, LDS_NODES>(sc, smem);
-        __syncthreads();
-        if (active && sc.n_prims) {
-            const float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
-            const float nox = -(o.x * ix), noy = -(o.y * iy), noz = -(o.z * iz);
-            float eps = 2.4e-7f * fmaxf(fmaxf(fabsf(nox), fabsf(noy)), fabsf(noz));
-            const bool exact = !(eps <= sc.bvh_exact_eps);
-            if (exact) eps = 0.0f;
-            int cur = 0, sp = 0;
-            const MediumCtx mc{active ? in_key[2 * i] : 0u, active ? in_key[2 * i + 1] : 0u, depth_counter_base(depth)};
-            uint32_t pend = 0u;
-            while (!bvh_step<BLOCK, true>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit)) {
-            }
-            while (pend && !media_step<true>(L, o, d, mc, sc.n_media, pend, tbest, hit)) {
-            }
-        }
-    } else {
-        float4* s_geo = reinterpret_cast<float4*>(smem);
-        if (sc.n_xforms || sc.n_media) {
-            closest_hit_spheres_general(sc, o, d, tbest, hit);
-        } else {
-            for (uint32_t t0 = 0; t0 < sc.n_spheres; t0 += RT_SPHERE_TILE) {
-                const uint32_t nn = min(RT_SPHERE_TILE, sc.n_spheres - t0);
-                __syncthreads();
-                for (uint32_t k = threadIdx.x; k < nn; k += BLOCK) s_geo[k] = sc.sph_geo[t0 + k];
-                __syncthreads();
-                closest_hit_tile(s_geo, nn, t0, o, d, a, tbest, hit);
-            }
-        }
-        const MediumCtx mc{active ? in_key[2 * i] : 0u, active ? in_key[2 * i + 1] : 0u, depth_counter_base(depth)};
-        closest_hit_rects(sc, o, d, mc, tbest, hit);
-    }
-    if (!active) return;
-    uint32_t n_fetch = 0;
-    Rng rng{in_key[2 * i], in_key[2 * i + 1], depth_counter_base(depth)};
-    Bounce bo = shade<true, NoPrefetch, true>(sc, PerlinTables{sc.perlin_vec, sc.perlin_perm2}, o, d, hit, tbest, rng, n_fetch);
-    out_hit[i] = hit;
-    out_t[i] = hit >= 0 ? tbest : 0.0f;
-    out_rad[3 * i] = bo.radiance.x, out_rad[3 * i + 1] = bo.radiance.y, out_rad[3 * i + 2] = bo.radiance.z;
-    out_att[3 * i] = bo.attenuation.x, out_att[3 * i + 1] = bo.attenuation.y, out_att[3 * i + 2] = bo.attenuation.z;
-    out_o[3 * i] = bo.o.x, out_o[3 * i + 1] = bo.o.y, out_o[3 * i + 2] = bo.o.z;
-    out_d[3 * i] = bo.d.x, out_d[3 * i + 1] = bo.d.y, out_d[3 * i + 2] = bo.d.z;
-    out_alive[i] = bo.alive ? 1 : 0;
-}
-
-// k_debug_bounce with moving spheres (rt_set_motion): the ray's time comes from counter 254 of in_key; the displacements are read from
-// HBM.  A kernel of its own beside the static one, whose code stays as it was.
-template <int BLOCK, bool USE_BVH, bool LDS_NODES>
-__global__ __launch_bounds__(BLOCK) void k_debug_bounce_motion(DevScene sc, uint32_t n, int depth, const float* __restrict__ in_o,
-                                                  const float* __restrict__ in_d, const uint32_t* __restrict__ in_key,
-                                                  int* __restrict__ out_hit, float* __restrict__ out_t,
-                                                  float* __restrict__ out_rad, float* __restrict__ out_att,
-                                                  float* __restrict__ out_o, float* __restrict__ out_d,
-                                                  uint8_t* __restrict__ out_alive, GenMotion gm) {
-    constexpr bool MOTION = true;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    const bool active = i < n;
-    const float tm = MOTION && active ? path_time(gm, in_key[2 * i], in_key[2 * i + 1]) : 0.0f;
-    V3 o = splat(0.0f), d = v3(0.f, 0.f, 1.f);
-    if (active) {
-        o = v3(in_o[3 * i], in_o[3 * i + 1], in_o[3 * i + 2]);
-        d = v3(in_d[3 * i], in_d[3 * i + 1], in_d[3 * i + 2]);
-    }
-    float tbest = RT_FLT_MAX;
-    int hit = -1;
-    const float a = length_squared(d);
-    if (USE_BVH) {
-        BvhLds L = stage_bvh<BLOCK, LDS_NODES>(sc, smem);
-        L.dc = gm.sph_dc;
-        __syncthreads();
-        if (active && sc.n_prims) {
-            const float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
-            const float nox = -(o.x * ix), noy = -(o.y * iy), noz = -(o.z * iz);
-            float eps = 2.4e-7f * fmaxf(fmaxf(fabsf(nox), fabsf(noy)), fabsf(noz));
-            const bool exact = !(eps <= sc.bvh_exact_eps);
-            if (exact) eps = 0.0f;
-            int cur = 0, sp = 0;
-            const MediumCtx mc{active ? in_key[2 * i] : 0u, active ? in_key[2 * i + 1] : 0u, depth_counter_base(depth)};
-            uint32_t pend = 0u;
-            while (!bvh_step<BLOCK, true, false, true, MOTION>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit, nullptr, tm)) {
-            }
-            while (pend && !media_step<true>(L, o, d, mc, sc.n_media, pend, tbest, hit)) {
-            }
-        }
-    } else {
-        float4* s_geo = reinterpret_cast<float4*>(smem);
-        if (sc.n_xforms || sc.n_media) {
-            closest_hit_spheres_general<MOTION>(sc, o, d, tbest, hit, gm.sph_dc, tm);
-        } else {
-            for (uint32_t t0 = 0; t0 < sc.n_spheres; t0 += RT_SPHERE_TILE) {
-                const uint32_t nn = min(RT_SPHERE_TILE, sc.n_spheres - t0);
-                __syncthreads();
-                for (uint32_t k = threadIdx.x; k < nn; k += BLOCK) s_geo[k] = sc.sph_geo[t0 + k];
-                __syncthreads();
-                closest_hit_tile<MOTION>(s_geo, nn, t0, o, d, a, tbest, hit, gm.sph_dc, tm);
-            }
-        }
-        const MediumCtx mc{active ? in_key[2 * i] : 0u, active ? in_key[2 * i + 1] : 0u, depth_counter_base(depth)};
-        closest_hit_rects(sc, o, d, mc, tbest, hit);
-    }
-    if (!active) return;
-    uint32_t n_fetch = 0;
-    Rng rng{in_key[2 * i], in_key[2 * i + 1], depth_counter_base(depth)};
-    Bounce bo = shade<true, NoPrefetch, true, MOTION>(sc, PerlinTables{sc.perlin_vec, sc.perlin_perm2}, o, d, hit, tbest, rng, n_fetch, NoPrefetch(),
-                                                      gm.sph_dc, tm);
-    out_hit[i] = hit;
-    out_t[i] = hit >= 0 ? tbest : 0.0f;
-    out_rad[3 * i] = bo.radiance.x, out_rad[3 * i + 1] = bo.radiance.y, out_rad[3 * i + 2] = bo.radiance.z;
-    out_att[3 * i] = bo.attenuation.x, out_att[3 * i + 1] = bo.attenuation.y, out_att[3 * i + 2] = bo.attenuation.z;
-    out_o[3 * i] = bo.o.x, out_o[3 * i + 1] = bo.o.y, out_o[3 * i + 2] = bo.o.z;
-    out_d[3 * i] = bo.d.x, out_d[3 * i + 1] = bo.d.y, out_d[3 * i + 2] = bo.d.z;
-    out_alive[i] = bo.alive ? 1 : 0;
-}
-
-// k_debug_bounce with planar primitives (rt_set_quads): a kernel of its own beside the static one, whose code stays as it was.
-template <int BLOCK, bool USE_BVH, bool LDS_NODES>
-__global__ __launch_bounds__(BLOCK) void k_debug_bounce_planar(DevScene sc, uint32_t n, int depth, const float* __restrict__ in_o,
-                                                  const float* __restrict__ in_d, const uint32_t* __restrict__ in_key,
-                                                  int* __restrict__ out_hit, float* __restrict__ out_t,
-                                                  float* __restrict__ out_rad, float* __restrict__ out_att,
-                                                  float* __restrict__ out_o, float* __restrict__ out_d,
-                                                  uint8_t* __restrict__ out_alive, GenPlanar gq) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    const bool active = i < n;
+    const float tm = MOTION && active ? path_time(g.motion, in_key[2 * i], in_key[2 * i + 1]) : 0.0f;
+    const float4* dc = MOTION ? g.motion.sph_dc : nullptr;
     V3 o = splat(0.0f), d = v3(0.f, 0.f, 1.f);
     if (active) {
         o = v3(in_o[3 * i], in_o[3 * i + 1], in_o[3 * i + 2]);
@@ -1890,64 +1764,8 @@ __global__ __launch_bounds__(BLOCK) void k_debug_bounce_planar(DevScene sc, uint
     const MediumCtx mc{active ? in_key[2 * i] : 0u, active ? in_key[2 * i + 1] : 0u, depth_counter_base(depth)};
     if (USE_BVH) {
         BvhLds L = stage_bvh<BLOCK, LDS_NODES>(sc, smem);
-        L.dc = nullptr, L.pq = gq.pq, L.pbase = gq.base;
-        __syncthreads();
-        if (active) {
-            const float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
-            const float nox = -(o.x * ix), noy = -(o.y * iy), noz = -(o.z * iz);
-            float eps = 2.4e-7f * fmaxf(fmaxf(fabsf(nox), fabsf(noy)), fabsf(noz));
-            const bool exact = !(eps <= sc.bvh_exact_eps);
-            if (exact) eps = 0.0f;
-            int cur = 0, sp = 0;
-            uint32_t pend = 0u;
-            while (!bvh_step<BLOCK, true, false, true, false, true>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit)) {
-            }
-            while (pend && !media_step<true>(L, o, d, mc, sc.n_media, pend, tbest, hit)) {
-            }
-        }
-    } else {
-        closest_hit_spheres_general(sc, o, d, tbest, hit);
-        closest_hit_rects(sc, o, d, mc, tbest, hit);
-        closest_hit_planar(gq, o, d, tbest, hit);
-    }
-    if (!active) return;
-    uint32_t n_fetch = 0;
-    Rng rng{in_key[2 * i], in_key[2 * i + 1], depth_counter_base(depth)};
-    Bounce bo = shade<true, NoPrefetch, true, false, true>(sc, PerlinTables{sc.perlin_vec, sc.perlin_perm2}, o, d, hit, tbest, rng, n_fetch, NoPrefetch(),
-                                                           nullptr, 0.0f, gq.pq, gq.base);
-    out_hit[i] = hit;
-    out_t[i] = hit >= 0 ? tbest : 0.0f;
-    out_rad[3 * i] = bo.radiance.x, out_rad[3 * i + 1] = bo.radiance.y, out_rad[3 * i + 2] = bo.radiance.z;
-    out_att[3 * i] = bo.attenuation.x, out_att[3 * i + 1] = bo.attenuation.y, out_att[3 * i + 2] = bo.attenuation.z;
-    out_o[3 * i] = bo.o.x, out_o[3 * i + 1] = bo.o.y, out_o[3 * i + 2] = bo.o.z;
-    out_d[3 * i] = bo.d.x, out_d[3 * i + 1] = bo.d.y, out_d[3 * i + 2] = bo.d.z;
-    out_alive[i] = bo.alive ? 1 : 0;
-}
-
-// k_debug_bounce with a light set (rt_set_lights), with or without planar primitives: a kernel of its own beside the others, whose
-// code stays as it was.  The closest hit is the general one (the same roots on the same operands); only shade() knows the lights.
-template <int BLOCK, bool USE_BVH, bool LDS_NODES, bool PLANAR>
-__global__ __launch_bounds__(BLOCK) void k_debug_bounce_lights(DevScene sc, uint32_t n, int depth, const float* __restrict__ in_o,
-                                                  const float* __restrict__ in_d, const uint32_t* __restrict__ in_key,
-                                                  int* __restrict__ out_hit, float* __restrict__ out_t,
-                                                  float* __restrict__ out_rad, float* __restrict__ out_att,
-                                                  float* __restrict__ out_o, float* __restrict__ out_d,
-                                                  uint8_t* __restrict__ out_alive, GenPlanar gq, GenLights gl) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    const bool active = i < n;
-    V3 o = splat(0.0f), d = v3(0.f, 0.f, 1.f);
-    if (active) {
-        o = v3(in_o[3 * i], in_o[3 * i + 1], in_o[3 * i + 2]);
-        d = v3(in_d[3 * i], in_d[3 * i + 1], in_d[3 * i + 2]);
-    }
-    float tbest = RT_FLT_MAX;
-    int hit = -1;
-    const float a = length_squared(d);
-    const MediumCtx mc{active ? in_key[2 * i] : 0u, active ? in_key[2 * i + 1] : 0u, depth_counter_base(depth)};
-    if (USE_BVH) {
-        BvhLds L = stage_bvh<BLOCK, LDS_NODES>(sc, smem);
-        L.dc = nullptr, L.pq = PLANAR ? gq.pq : nullptr, L.pbase = PLANAR ? gq.base : 0xFFFFFFFFu;
+        if (MOTION) L.dc = dc;
+        if (PLANAR || LIGHTS) L.dc = nullptr, L.pq = PLANAR ? g.planar.pq : nullptr, L.pbase = PLANAR ? g.planar.base : 0xFFFFFFFFu;
         __syncthreads();
         if (active && (PLANAR || sc.n_prims)) {
             const float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
@@ -1957,21 +1775,33 @@ __global__ __launch_bounds__(BLOCK) void k_debug_bounce_lights(DevScene sc, uint
             if (exact) eps = 0.0f;
             int cur = 0, sp = 0;
             uint32_t pend = 0u;
-            while (!bvh_step<BLOCK, true, false, true, false, PLANAR>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit)) {
+            while (!bvh_step<BLOCK, true, false, true, MOTION, PLANAR>(L, o, d, ix, iy, iz, nox, noy, noz, eps, exact, a, pend, cur, sp, tbest, hit, nullptr, tm)) {
             }
             while (pend && !media_step<true>(L, o, d, mc, sc.n_media, pend, tbest, hit)) {
             }
         }
     } else {
-        closest_hit_spheres_general(sc, o, d, tbest, hit);
+        if (PLANAR || LIGHTS || sc.n_xforms || sc.n_media) {
+            closest_hit_spheres_general<MOTION>(sc, o, d, tbest, hit, dc, tm);
+        } else {
+            float4* s_geo = reinterpret_cast<float4*>(smem);
+            for (uint32_t t0 = 0; t0 < sc.n_spheres; t0 += RT_SPHERE_TILE) {
+                const uint32_t nn = min(RT_SPHERE_TILE, sc.n_spheres - t0);
+                __syncthreads();
+                for (uint32_t k = threadIdx.x; k < nn; k += BLOCK) s_geo[k] = sc.sph_geo[t0 + k];
+                __syncthreads();
+                closest_hit_tile<MOTION>(s_geo, nn, t0, o, d, a, tbest, hit, dc, tm);
+            }
+        }
         closest_hit_rects(sc, o, d, mc, tbest, hit);
-        if (PLANAR) closest_hit_planar(gq, o, d, tbest, hit);
+        if (PLANAR) closest_hit_planar(g.planar, o, d, tbest, hit);
     }
     if (!active) return;
     uint32_t n_fetch = 0;
     Rng rng{in_key[2 * i], in_key[2 * i + 1], depth_counter_base(depth)};
-    Bounce bo = shade<true, NoPrefetch, true, false, PLANAR, true>(sc, PerlinTables{sc.perlin_vec, sc.perlin_perm2}, o, d, hit, tbest, rng, n_fetch,
-                                                                   NoPrefetch(), nullptr, 0.0f, gq.pq, gq.base, gl.table, gl.n);
+    Bounce bo = shade<true, NoPrefetch, true, MOTION, PLANAR, LIGHTS>(sc, PerlinTables{sc.perlin_vec, sc.perlin_perm2}, o, d, hit, tbest, rng, n_fetch, NoPrefetch(), dc,
+                                                                      tm, PLANAR || LIGHTS ? g.planar.pq : nullptr, PLANAR || LIGHTS ? g.planar.base : 0u,
+                                                                      LIGHTS ? g.lights.table : nullptr, LIGHTS ? g.lights.n : 0u);
     out_hit[i] = hit;
     out_t[i] = hit >= 0 ? tbest : 0.0f;
     out_rad[3 * i] = bo.radiance.x, out_rad[3 * i + 1] = bo.radiance.y, out_rad[3 * i + 2] = bo.radiance.z;

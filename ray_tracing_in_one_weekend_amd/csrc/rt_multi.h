@@ -75,6 +75,22 @@ int multi_fail(RtMulti* m, int code, const std::string& msg) {
     else g_multi_create_error = msg;
     return code;
 }
+
+// rt_set_motion / rt_set_quads / rt_set_lights on every context.  Every context holds the same scene: the first refuses what all would,
+// then none has changed.  After a device-side failure behind the first context, the ones already changed get the set cleared (nullptr).
+template <class Set>
+int multi_set(RtMulti* m, int (*set)(RtCtx*, const Set*), const Set* value) {
+    if (!m) return RT_ERR_INVALID;
+    for (size_t i = 0; i < m->ctx.size(); ++i) {
+        const int rc = set(m->ctx[i], value);
+        if (rc) {
+            const std::string err = rt_last_error(m->ctx[i]);
+            for (size_t k = 0; k < i; ++k) (void)set(m->ctx[k], nullptr);
+            return multi_fail(m, rc, std::string("device ") + std::to_string(m->devices[i]) + ": " + err);
+        }
+    }
+    return RT_OK;
+}
 } // namespace
 
 extern "C" {
@@ -193,44 +209,9 @@ int rt_multi_set_lens(RtMulti* m, const RtLens* lens) {
     return RT_OK;
 }
 
-int rt_multi_set_motion(RtMulti* m, const RtMotion* motion) {
-    if (!m) return RT_ERR_INVALID;
-    for (size_t i = 0; i < m->ctx.size(); ++i) { // (every context holds the same scene: the first refuses what all would, then none has changed)
-        const int rc = rt_set_motion(m->ctx[i], motion);
-        if (rc) { // a device-side failure behind the first context: the ones already changed go back to the static renderer
-            const std::string err = rt_last_error(m->ctx[i]);
-            for (size_t k = 0; k < i; ++k) (void)rt_set_motion(m->ctx[k], nullptr);
-            return multi_fail(m, rc, std::string("device ") + std::to_string(m->devices[i]) + ": " + err);
-        }
-    }
-    return RT_OK;
-}
-
-int rt_multi_set_quads(RtMulti* m, const RtQuads* quads) {
-    if (!m) return RT_ERR_INVALID;
-    for (size_t i = 0; i < m->ctx.size(); ++i) { // (every context holds the same scene: the first refuses what all would, then none has changed)
-        const int rc = rt_set_quads(m->ctx[i], quads);
-        if (rc) { // a device-side failure behind the first context: the ones already changed go back to the renderer without planar primitives
-            const std::string err = rt_last_error(m->ctx[i]);
-            for (size_t k = 0; k < i; ++k) (void)rt_set_quads(m->ctx[k], nullptr);
-            return multi_fail(m, rc, std::string("device ") + std::to_string(m->devices[i]) + ": " + err);
-        }
-    }
-    return RT_OK;
-}
-
-int rt_multi_set_lights(RtMulti* m, const RtLights* lights) {
-    if (!m) return RT_ERR_INVALID;
-    for (size_t i = 0; i < m->ctx.size(); ++i) { // (every context holds the same scene: the first refuses what all would, then none has changed)
-        const int rc = rt_set_lights(m->ctx[i], lights);
-        if (rc) { // a device-side failure behind the first context: the ones already changed go back to the renderer without a light set
-            const std::string err = rt_last_error(m->ctx[i]);
-            for (size_t k = 0; k < i; ++k) (void)rt_set_lights(m->ctx[k], nullptr);
-            return multi_fail(m, rc, std::string("device ") + std::to_string(m->devices[i]) + ": " + err);
-        }
-    }
-    return RT_OK;
-}
+int rt_multi_set_motion(RtMulti* m, const RtMotion* motion) { return multi_set(m, rt_set_motion, motion); }
+int rt_multi_set_quads(RtMulti* m, const RtQuads* quads) { return multi_set(m, rt_set_quads, quads); }
+int rt_multi_set_lights(RtMulti* m, const RtLights* lights) { return multi_set(m, rt_set_lights, lights); }
 
 int rt_deinterleave_bands(RtCtx* ctx, const void* d_gathered, uint32_t nx, uint32_t ny, uint32_t band, uint32_t n_shards,
                           void* d_out_rgb_f32, void* d_out_rgb8, void* stream) {

@@ -4,7 +4,7 @@ Runs scripts/gpu_final_like.py once per counter group under rocprofv3 (--pmc wit
 name, dispatch time and the wave-cycle split: waiting (s_waitcnt), waiting to issue, executing vector instructions, lane
 utilisation, LDS instructions per vector instruction and the LDS bank-conflict share.  gpu_final_like.py renders with the default
 placement, with the float tree through L2, and with the default again; the kernel names tell the placements apart
-(k_intersect<.., true> in its last template argument = the 58 B tree in LDS walked without a stack)."""
+(LDS_NODES, the fourth template argument of k_intersect<BLOCK, GEN, RECTS, LDS_NODES, ..>: true = the tree staged in LDS, false = through L2)."""
 import collections
 import csv
 import glob
