@@ -46,7 +46,6 @@ struct RtCtx {
     std::string err;
     // scene
     bool has_scene = false;
-    DevScene ds{};
     // Every device buffer of a context lies in its pool (rt_pool.h): the small persistent ones (scene, accumulator, counters,
     // candidate lists, output images) are carved from the bottom by a bump pointer, the per-frame work buffers start above
     // them.  Only the pool's helper thread ever asks the driver for device memory, so a request that the driver makes wait
@@ -70,38 +69,35 @@ struct RtCtx {
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     int n_cu = 256;
     size_t lds_limit = 64 * 1024;
-    bool use_bvh = false;      // scene BVH fits LDS next to the traversal stacks
-    size_t isect_lds = 0;      // k_intersect: nodes + geometry (when they fit) + stack levels + counters
-    bool bvh_in_lds = false;   // false: the tree is traversed out of HBM/L2, only the stacks are in LDS
-    bool general_lds = false;  // k_intersect<.., GLDS>: the wrapper / medium tables of a general scene are staged in LDS
+    // What the closest-hit kernels read and where it lies: configure_search fills one.  `search` is the ACTIVE state; `static_search` is
+    // what rt_scene_upload built.  rt_set_motion and rt_set_quads build another over the scene and their set, in a region of their own,
+    // and clearing either puts static_search back (restore_static_search): the static renderer, its arrays, kernels and bits.
+    struct Search {
+        DevScene ds{};
+        bool use_bvh = false;      // scene BVH fits LDS next to the traversal stacks
+        size_t isect_lds = 0;      // k_intersect: nodes + geometry (when they fit) + stack levels + counters
+        bool bvh_in_lds = false;   // false: the tree is traversed out of HBM/L2, only the stacks are in LDS
+        bool general_lds = false;  // k_intersect<.., GLDS>: the wrapper / medium tables of a general scene are staged in LDS
+        bool general_kernels = false; // the general instantiations (rectangles, wrappers, media — or RT_OPT_GENERAL_KERNELS at upload)
+        bool use_grid = false;     // sphere-only scene with a uniform grid (rt_grid.h): depth >= 1 runs k_intersect_grid
+        GridParams grid{};
+        size_t grid_lds = 0;
+        size_t motion_lds = 0;     // rt_set_motion: 16 B per sphere beside the geometry where it is staged in LDS
+    } search, static_search;
     bool nest = false;         // k_intersect<.., NEST>: a wrapper chain deeper than RT_MAX_CHAIN, more than 32 media or a wrapper around a medium (rt_device.h)
-    bool general_kernels = false; // the general instantiations (rectangles, wrappers, media — or RT_OPT_GENERAL_KERNELS at upload)
-    bool use_grid = false;     // sphere-only scene with a uniform grid (rt_grid.h): depth >= 1 runs k_intersect_grid
-    GridParams grid{};
-    size_t grid_lds = 0;
     uint32_t opt[RT_OPT__COUNT] = {}; // rt_debug_set_option: per context, every setting renders the same bits
     // Page-locked word for the one host decision inside a frame: how many pixels have more primary-ray candidates than a list
     // holds (k_primary_lists counts them; render_impl reads the count back 0.1 ms into the frame).
     uint32_t* h_overflow = nullptr;
     long long last_overflow = -1; // that count for the last frame (rt_debug_render_parts); -1: it made no lists or did not read it
     RtLens lens{0.0f, 1.0f};      // rt_set_lens (lens_radius 0: the pinhole)
-    // rt_set_motion.  The search state above (ds, tree placement, grid) is the ACTIVE one; `static_search` is what rt_scene_upload
-    // built, `keep` what rt_set_motion needs of the scene on the host to bound the moved spheres again.  Clearing the motion puts
-    // static_search back: the static renderer, its arrays, kernels and bits.
-    struct Search {
-        DevScene ds{};
-        bool use_bvh = false, bvh_in_lds = false, general_lds = false, use_grid = false;
-        size_t isect_lds = 0, grid_lds = 0;
-        GridParams grid{};
-        bool general_kernels = false;
-    } static_search;
+    // `keep`: what rt_set_motion needs of the scene on the host to bound the moved spheres again
     struct Keep {
         std::vector<float4> geo;         // spheres (c0, r)
         std::vector<PrimBox> eboxes;     // world entries, unpadded
         std::vector<uint32_t> entry_ids;
         std::vector<float4> ent_bs;
         std::vector<uint8_t> bare;       // per sphere: no wrapper, not a medium boundary
-        uint32_t bvh_depth = 0;
         // rt_set_quads: what the records and sort keys of planar primitives are made of, and the static ones they are appended to
         std::vector<MatRec> mats;
         std::vector<TexRec> texs;
@@ -110,8 +106,7 @@ struct RtCtx {
         uint32_t sky_type = 0;
         double world_mag = 0.0;          // largest coordinate magnitude of the world entries' bounds
     } keep;
-    // rt_set_quads.  As with the motion, the active search state is rebuilt over the scene's entries AND the set, in a region of its
-    // own; clearing the set puts static_search back.
+    // rt_set_quads: the active search state is rebuilt over the scene's entries AND the set
     bool planar = false;           // the PLANAR instantiations (n > 0)
     GenPlanar gplanar{};           // (pq in quads_region)
     double planar_reach = 0.0;     // RT_PLANAR_REACH W of the set: the leaf slack holds for ray origins within it (render_impl checks the camera)
@@ -122,7 +117,6 @@ struct RtCtx {
     DevBuf lights_buf;
     bool motion = false;           // the MOTION instantiations (n_moving > 0)
     GenMotion gmotion{};           // (sph_dc in motion_region)
-    size_t motion_lds = 0;         // 16 B per sphere beside the geometry where it is staged in LDS
     DevBuf motion_region;          // the arrays rt_set_motion uploads: displacements, tree, bounding spheres, grid
     struct MotionDebug {           // rt_debug_motion_bounds
         std::vector<uint32_t> sphere;
@@ -203,7 +197,7 @@ void free_buf(DevBuf& b) {
 void free_scene(RtCtx* ctx) { // (the region stays: the next upload carves it again)
     ctx->scene_used = 0;
     ctx->has_scene = false;
-    std::memset(&ctx->ds, 0, sizeof(ctx->ds));
+    ctx->search.ds = DevScene{};
 }
 
 // host -> device through the page-locked staging buffer, on the context's stream, complete on return
@@ -236,6 +230,67 @@ int upload(RtCtx* ctx, const std::vector<T>& host, const T** dev) {
     return RT_OK;
 }
 
+// One region for a set of arrays.  `fill` issues their upload() calls and runs twice: a first pass that only adds up what they need,
+// then, with `region` grown to that + 1 MiB (room for the grid's cell arrays; `spare`: + 25 % when it has to grow, so that the next,
+// larger scene fits too), the pass that copies — no hipMalloc per array, none at all in the common case, and the copies go through
+// page-locked staging.  upload() carves ctx->scene_region: a region other than that one stands in for it during the second pass, and the
+// scene's own region and fill level are put back on every path.
+template <class Fill>
+int carve_region(RtCtx* ctx, DevBuf& region, bool spare, Fill fill) {
+    ctx->scene_measuring = true, ctx->scene_measure = 0;
+    (void)fill();
+    ctx->scene_measuring = false;
+    const size_t need = ctx->scene_measure + (1u << 20);
+    int rc = need > region.bytes ? ensure(ctx, region, spare ? need + need / 4u : need) : RT_OK;
+    if (rc) return rc;
+    const bool stands_in = &region != &ctx->scene_region;
+    const DevBuf scene_region = ctx->scene_region;
+    const size_t scene_used = ctx->scene_used;
+    ctx->scene_region = region, ctx->scene_used = 0;
+    rc = fill();
+    if (stands_in) ctx->scene_region = scene_region, ctx->scene_used = scene_used;
+    return rc;
+}
+
+float fbits(uint32_t u) {
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+
+// The tree over a set of world entries as the kernels read it, and what the host decides by.
+struct HostTree {
+    HostBvh4 bvh4;
+    uint32_t depth = 0;     // of the binary tree it was collapsed from (configure_search holds it against RT_BVH_MAX_DEPTH)
+    float exact_eps = 0.0f; // DevScene::bvh_exact_eps
+};
+void build_tree(const std::vector<PrimBox>& eboxes, const std::vector<uint32_t>& entry_ids, HostTree& t) {
+    HostBvh bvh;
+    build_prim_bvh(eboxes, RT_BVH_MAX_DEPTH, bvh);
+    for (auto& dd : bvh.d) { // leaf ids: index into eboxes -> world entry id
+        if (dd.x < 0 && dd.x != INT_MIN) dd.x = ~(int)entry_ids[(size_t)~dd.x];
+        if (dd.y < 0 && dd.y != INT_MIN) dd.y = ~(int)entry_ids[(size_t)~dd.y];
+    }
+    collapse_bvh4(bvh, t.bvh4);
+    t.depth = bvh.depth;
+    // rays whose slab slack exceeds 2^-10 of the scene extent use the cancellation-free slab test (bvh_step)
+    double ext2 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        float lo = FLT_MAX, hi = -FLT_MAX;
+        for (const PrimBox& b : eboxes) lo = std::min(lo, b.mn[k]), hi = std::max(hi, b.mx[k]);
+        if (hi > lo) ext2 += ((double)hi - lo) * ((double)hi - lo);
+    }
+    t.exact_eps = (float)(std::sqrt(ext2) / 1024.0);
+}
+int upload_tree(RtCtx* ctx, const HostTree& t, DevScene& ds) {
+    ds.n_bvh4_nodes = (uint32_t)t.bvh4.id.size();
+    ds.bvh4_depth = t.bvh4.depth;
+    ds.bvh_exact_eps = t.exact_eps;
+    int rc = upload(ctx, t.bvh4.id, &ds.bvh4_id);
+    for (int k = 0; k < 6 && !rc; ++k) rc = upload(ctx, t.bvh4.p[k], &ds.bvh4_p[k]);
+    return rc;
+}
+
 bool mat_needs_tex0(uint32_t t) {
     return t == RT_MAT_EMISSION || t == RT_MAT_DIFFUSE || t == RT_MAT_LAMBERT || t == RT_MAT_ISOTROPIC ||
            t == RT_MAT_OREN_NAYAR || t == RT_MAT_BURLEY_DIFFUSE || t == RT_MAT_ROUGH_PLASTIC ||
@@ -248,6 +303,35 @@ bool class_is_light(uint32_t cls, uint32_t sky_type) {
     if (cls == 0) return sky_type != RT_SKY_ENV;
     const uint32_t ty = (cls - 1u) / 4u, tt = (cls - 1u) % 4u;
     return tt == RT_TEX_CONSTANT && ty <= RT_MAT_ISOTROPIC;
+}
+
+// Sort keys of k_shade's class sort: the classes present (a miss always is) ranked cheap classes first (a miss and the
+// constant-texture material.rs materials, then the textured and pbr.rs ones), so that the long Perlin / PBR segments of a block sit
+// together at its end.  Raw classes in, keys out; returns the key of a miss.
+uint32_t rank_classes(std::vector<uint8_t>& cls, uint32_t sky_type) {
+    bool class_present[RT_NCLASS] = {};
+    class_present[0] = true;
+    for (uint8_t c : cls) class_present[c] = true;
+    uint32_t class_key[RT_NCLASS] = {}, n_keys = 0;
+    for (int pass = 0; pass < 2; ++pass)
+        for (uint32_t c = 0; c < RT_NCLASS; ++c)
+            if (class_present[c] && class_is_light(c, sky_type) == (pass == 0)) class_key[c] = n_keys++;
+    for (uint8_t& c : cls) c = (uint8_t)class_key[c];
+    return class_key[0];
+}
+
+// The shading record (5 float4 at `rec`) of a world entry with material m and geometry (geo0, geo1); returns its raw class
+// (1 + material * 4 + texture of tex0, < RT_NCLASS).
+uint8_t shading_record(const MatRec& m, const std::vector<TexRec>& texs, float4 geo0, float4 geo1, float4* rec) {
+    const bool has_t0 = mat_needs_tex0(m.type) && m.tex0 < texs.size();
+    const TexRec t0 = has_t0 ? texs[m.tex0] : TexRec{};
+    rec[0] = geo0;
+    rec[1] = make_float4(fbits(m.type), fbits(t0.type), fbits(t0.aux), fbits(m.tex1));
+    // colour slot: the texture's colour 0 for textured materials, the albedo for Metal
+    rec[2] = has_t0 ? make_float4(t0.c0r, t0.c0g, t0.c0b, m.p0) : make_float4(m.cr, m.cg, m.cb, m.p0);
+    rec[3] = make_float4(m.p1, m.p2, t0.scale, fbits(m.tex0));
+    rec[4] = geo1;
+    return (uint8_t)(1u + m.type * 4u + t0.type);
 }
 
 
@@ -326,9 +410,9 @@ struct StepBuffers {
     bool planar = false; // planar primitives (the PLANAR instantiations)
     bool lights = false; // a light set (the LIGHTS instantiations of k_shade)
 };
-bool scene_is_general(const RtCtx* ctx) { return ctx->general_kernels; }
-bool grid_enabled(const RtCtx* ctx) { return ctx->use_grid && ctx->opt[RT_OPT_GRID] != 1u && !scene_is_general(ctx); }
-bool scene_perlin_lds(const RtCtx* ctx) { return ctx->ds.n_perlin > 0 && ctx->ds.n_perlin <= RT_PERLIN_LDS_MAX_SETS; }
+bool scene_is_general(const RtCtx* ctx) { return ctx->search.general_kernels; }
+bool grid_enabled(const RtCtx* ctx) { return ctx->search.use_grid && ctx->opt[RT_OPT_GRID] != 1u && !scene_is_general(ctx); }
+bool scene_perlin_lds(const RtCtx* ctx) { return ctx->search.ds.n_perlin > 0 && ctx->search.ds.n_perlin <= RT_PERLIN_LDS_MAX_SETS; }
 
 // ---- kernel variants ---------------------------------------------------------------------------------------------
 // k_shade, k_intersect and k_debug_bounce are families of instantiations over feature flags.  A family's key is the set of its flags (one
@@ -411,26 +495,26 @@ static_assert(n_variants(DEBUG_KERNELS_TREE_L2) + n_variants(DEBUG_KERNELS_TREE_
 // closest hit of the shards [ip.q0, ip.q1): the tree instantiation that matches the scene, or the grid / list walk
 int launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32_t grid, const StepBuffers& b, const IntersectParams& ip) {
     if (use_bvh && !gen && grid_enabled(ctx)) { // sphere-only scene, depth >= 1: the grid walk (rt_grid.h), same hit records
-        const size_t mlds = ctx->grid_lds + ctx->motion_lds;
-        if (b.motion && ctx->grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid_motion<true>, dim3(grid), dim3(RT_BVH_BLOCK), mlds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
-        else if (b.motion) hipLaunchKernelGGL(k_intersect_grid_motion<false>, dim3(grid), dim3(RT_BVH_BLOCK), mlds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
-        else if (ctx->grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid<true>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->grid_lds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
-        else hipLaunchKernelGGL(k_intersect_grid<false>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->grid_lds, sg, ctx->grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
+        const size_t mlds = ctx->search.grid_lds + ctx->search.motion_lds;
+        if (b.motion && ctx->search.grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid_motion<true>, dim3(grid), dim3(RT_BVH_BLOCK), mlds, sg, ctx->search.grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        else if (b.motion) hipLaunchKernelGGL(k_intersect_grid_motion<false>, dim3(grid), dim3(RT_BVH_BLOCK), mlds, sg, ctx->search.grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        else if (ctx->search.grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid<true>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->search.grid_lds, sg, ctx->search.grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
+        else hipLaunchKernelGGL(k_intersect_grid<false>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->search.grid_lds, sg, ctx->search.grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
         return RT_OK;
     }
     if (!use_bvh) { // no tree (or RT_FLAG_BRUTE_FORCE): every primitive, one workgroup per shard
-        const size_t list_lds = (size_t)std::min<uint32_t>(std::max<uint32_t>(ctx->ds.n_spheres, 1u), RT_SPHERE_TILE) * sizeof(float4);
-        if (b.planar) hipLaunchKernelGGL(k_intersect_list_planar, dim3(ip.q1 - ip.q0), dim3(256), 0, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
-        else if (b.motion) hipLaunchKernelGGL(k_intersect_list_motion, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
-        else hipLaunchKernelGGL(k_intersect_list, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        const size_t list_lds = (size_t)std::min<uint32_t>(std::max<uint32_t>(ctx->search.ds.n_spheres, 1u), RT_SPHERE_TILE) * sizeof(float4);
+        if (b.planar) hipLaunchKernelGGL(k_intersect_list_planar, dim3(ip.q1 - ip.q0), dim3(256), 0, sg, ctx->search.ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        else if (b.motion) hipLaunchKernelGGL(k_intersect_list_motion, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->search.ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+        else hipLaunchKernelGGL(k_intersect_list, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->search.ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
         return RT_OK;
     }
     unsigned k = 0;
     if (gen) k |= IS_GEN;                                               // depth 0 with the primary rays made in the kernel (render_impl)
-    if (scene_is_general(ctx) || !ctx->bvh_in_lds || b.planar) k |= IS_RECTS; // general scene; trees that do not fit LDS use the general instantiation
+    if (scene_is_general(ctx) || !ctx->search.bvh_in_lds || b.planar) k |= IS_RECTS; // general scene; trees that do not fit LDS use the general instantiation
                                                                         // (it works for sphere-only scenes too); planar primitives (rt_set_quads) likewise
-    if (ctx->bvh_in_lds) k |= IS_LDS_NODES;                             // tree and geometry staged in LDS (rt_scene_upload), else read through L2
-    if (has(k, IS_RECTS) && ctx->general_lds) k |= IS_GLDS;             // the wrapper / medium tables fit LDS beside them (rt_scene_upload)
+    if (ctx->search.bvh_in_lds) k |= IS_LDS_NODES;                             // tree and geometry staged in LDS (rt_scene_upload), else read through L2
+    if (has(k, IS_RECTS) && ctx->search.general_lds) k |= IS_GLDS;             // the wrapper / medium tables fit LDS beside them (rt_scene_upload)
     if (has(k, IS_RECTS) && (ctx->nest || b.planar)) k |= IS_NEST;      // wrapper chains and media masks as loops (rt_scene_upload); planar primitives always
                                                                         // (the same bits for a scene that needs none), so one instantiation per placement
     if (gen && b.lens) k |= IS_LENS;                                    // depth 0 through the thin lens (rt_set_lens)
@@ -438,7 +522,7 @@ int launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32_
     if (b.planar) k |= IS_PLANAR;                                       // planar primitives (rt_set_quads)
     const IsectKernel fn = ISECT_KERNELS[k];
     if (!fn) return fail(ctx, RT_ERR_STATE, "launch_intersect: no k_intersect instantiation for " + flags_text(k, IS_NAMES));
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(RT_BVH_BLOCK), ctx->isect_lds, sg, ctx->ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(RT_BVH_BLOCK), ctx->search.isect_lds, sg, ctx->search.ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
     return RT_OK;
 }
 
@@ -446,8 +530,8 @@ int launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32_
 int launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32_t n_shards, const StepBuffers& b, const ShadeParams& sp) {
     const bool perlin_lds = scene_perlin_lds(ctx);
     // sphere geometry for the closest hit inside k_shade<GEN>
-    const uint32_t n_fused = (gen && fused_lists) ? ctx->ds.n_spheres * (b.motion ? 2u : 1u) : 0u; // (MOTION: the displacements behind the geometry)
-    const size_t shade_lds = shade_lds_bytes(ctx->ds.n_prims + ctx->ds.n_media + (b.planar ? ctx->gplanar.n : 0u), perlin_lds ? ctx->ds.n_perlin : 0u, n_fused, !gen && sp.sort);
+    const uint32_t n_fused = (gen && fused_lists) ? ctx->search.ds.n_spheres * (b.motion ? 2u : 1u) : 0u; // (MOTION: the displacements behind the geometry)
+    const size_t shade_lds = shade_lds_bytes(ctx->search.ds.n_prims + ctx->search.ds.n_media + (b.planar ? ctx->gplanar.n : 0u), perlin_lds ? ctx->search.ds.n_perlin : 0u, n_fused, !gen && sp.sort);
     unsigned k = 0;
     if (perlin_lds) k |= SH_PERLIN_LDS;                              // the scene's Perlin tables fit LDS (scene_perlin_lds)
     if (gen) k |= SH_GEN;                                            // depth 0 with the primary rays made in the kernel (render_impl)
@@ -459,7 +543,7 @@ int launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32_
     if (b.lights) k |= SH_LIGHTS;                                    // a light set (rt_set_lights)
     const ShadeKernel fn = SHADE_KERNELS[k];
     if (!fn) return fail(ctx, RT_ERR_STATE, "launch_shade: no k_shade instantiation for " + flags_text(k, SH_NAMES));
-    hipLaunchKernelGGL(fn, dim3(n_shards), dim3(256), shade_lds, sg, ctx->ds, b.qi, b.qhit, b.qo, b.cin, b.cout, b.rad, sp, b.totals, b.gpd);
+    hipLaunchKernelGGL(fn, dim3(n_shards), dim3(256), shade_lds, sg, ctx->search.ds, b.qi, b.qhit, b.qo, b.cin, b.cout, b.rad, sp, b.totals, b.gpd);
     return RT_OK;
 }
 
@@ -511,7 +595,7 @@ QueueGeom queue_geom(const RtCtx* ctx, uint32_t n_max) {
     if (ctx->opt[RT_OPT_QUEUE_SHARDS]) g.nq = ctx->opt[RT_OPT_QUEUE_SHARDS];
     // k_intersect: as many 1024-thread workgroups per CU as LDS admits (two at <= 64 VGPRs); every
     // workgroup owns nq / isect_grid shards
-    const size_t isect_lds = grid_enabled(ctx) ? std::max(ctx->isect_lds, ctx->grid_lds) : ctx->isect_lds;
+    const size_t isect_lds = grid_enabled(ctx) ? std::max(ctx->search.isect_lds, ctx->search.grid_lds) : ctx->search.isect_lds;
     const uint32_t isect_wg_per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(2, ctx->lds_limit / std::max<size_t>(isect_lds, 1)));
     // ... in TWO rounds when the tree is more than a handful of nodes: a workgroup's persistent lanes end in a drain phase (its
     // work counter is empty, the last rays finish in ever emptier waves), and with exactly one resident round all workgroups
@@ -519,7 +603,7 @@ QueueGeom queue_geom(const RtCtx* ctx, uint32_t n_max) {
     // config 2: 61.9 -> 59.8 ms (-3.4 %), pbr_sweep_scene -3.6 %; scenes of a few primitives (simple_light_scene +5.6 %) and
     // trees read through L2 (final_scene +1.9 %) do better with one round (profiles/round3/nq_sweep*.txt; non-multiples of
     // the resident count lose outright: 1 280 / 1 792 workgroups 60.6 / 62.0 ms).
-    const uint32_t rounds = (ctx->bvh_in_lds && ctx->ds.n_bvh4_nodes >= 64u) ? 2u : 1u;
+    const uint32_t rounds = (ctx->search.bvh_in_lds && ctx->search.ds.n_bvh4_nodes >= 64u) ? 2u : 1u;
     g.isect_grid = std::min(g.nq, (uint32_t)ctx->n_cu * isect_wg_per_cu * rounds);
     if (ctx->opt[RT_OPT_ISECT_WORKGROUPS]) g.isect_grid = std::min(g.nq, ctx->opt[RT_OPT_ISECT_WORKGROUPS]);
     while ((g.nq + g.isect_grid - 1) / g.isect_grid > RT_ISECT_MAX_SHARDS) g.isect_grid *= 2;
@@ -800,18 +884,242 @@ void world_bounds(const RtFlatScene* s, WorldBounds& w) {
     }
 }
 
-// Where the closest-hit search of the scene in ctx->ds runs: tree in LDS or through L2, wrapper tables in LDS, a grid or none.
-// rt_scene_upload calls it for the static scene, rt_set_motion again for the scene with its moved spheres: `dc` (else NULL) = their
-// displacements, which take 16 B per sphere of LDS beside the geometry wherever the geometry is staged (k_intersect with the tree in
+// What rt_scene_upload refuses before it touches anything: a code and the message (RT_OK: the scene is valid).
+int validate_scene(const RtFlatScene* s, std::string& msg) {
+    if (s->n_spheres && (!s->sph_cx || !s->sph_cy || !s->sph_cz || !s->sph_r || !s->sph_mat))
+        return msg = "rt_scene_upload: sphere arrays missing", RT_ERR_INVALID;
+    if (s->n_materials && (!s->mat_type || !s->mat_color || !s->mat_p0 || !s->mat_p1 || !s->mat_p2 || !s->mat_p3 ||
+                           !s->mat_tex0 || !s->mat_tex1))
+        return msg = "rt_scene_upload: material arrays missing", RT_ERR_INVALID;
+    if (s->n_textures && (!s->tex_type || !s->tex_color0 || !s->tex_color1 || !s->tex_scale || !s->tex_aux))
+        return msg = "rt_scene_upload: texture arrays missing", RT_ERR_INVALID;
+    if (s->n_perlin && (!s->perlin_vec || !s->perlin_perm))
+        return msg = "rt_scene_upload: perlin tables missing", RT_ERR_INVALID;
+    if (s->n_images && (!s->img_w || !s->img_h || !s->img_offset || !s->texels))
+        return msg = "rt_scene_upload: image arrays missing", RT_ERR_INVALID;
+    for (uint32_t i = 0; i < s->n_spheres; ++i) {
+        if (s->sph_mat[i] >= s->n_materials)
+            return msg = "rt_scene_upload: sphere " + std::to_string(i) + " has material index out of range", RT_ERR_INVALID;
+        // non-finite geometry would reach the tree builder's sort comparators and bin casts (host-side UB)
+        if (!std::isfinite(s->sph_cx[i]) || !std::isfinite(s->sph_cy[i]) || !std::isfinite(s->sph_cz[i]) || !std::isfinite(s->sph_r[i]))
+            return msg = "rt_scene_upload: sphere " + std::to_string(i) + " has a centre or radius that is not finite", RT_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < 3u * s->n_rects && s->rect_min && s->rect_max; ++i)
+        if (!std::isfinite(s->rect_min[i]) || !std::isfinite(s->rect_max[i]))
+            return msg = "rt_scene_upload: rectangle " + std::to_string(i / 3u) + " has a bound that is not finite", RT_ERR_INVALID;
+    for (uint32_t i = 0; i < 4u * s->n_xforms && s->xf_param; ++i)
+        if (!std::isfinite(s->xf_param[i]))
+            return msg = "rt_scene_upload: transform " + std::to_string(i / 4u) + " has a parameter that is not finite", RT_ERR_INVALID;
+    if (s->n_xforms && (!s->xf_type || !s->xf_param || !s->xf_parent))
+        return msg = "rt_scene_upload: transform arrays missing", RT_ERR_INVALID;
+    for (uint32_t i = 0; i < s->n_xforms; ++i) {
+        if (s->xf_type[i] > RT_XF_ROTATE_Y) return msg = "rt_scene_upload: unknown transform type", RT_ERR_INVALID;
+        if (s->xf_parent[i] != RT_NO_XFORM && s->xf_parent[i] >= i)
+            return msg = "rt_scene_upload: transform parent must precede its child", RT_ERR_INVALID;
+    }
+    // (a parent precedes its child, so every chain ends; its length is xf_depth below: any number of nested wrappers, hitable.rs:404-520)
+    for (uint32_t i = 0; i < s->n_spheres && s->sph_xform; ++i)
+        if (s->sph_xform[i] != RT_NO_XFORM && s->sph_xform[i] >= s->n_xforms) return msg = "rt_scene_upload: bad sphere transform chain", RT_ERR_INVALID;
+    for (uint32_t i = 0; i < s->n_rects && s->rect_xform; ++i)
+        if (s->rect_xform[i] != RT_NO_XFORM && s->rect_xform[i] >= s->n_xforms) return msg = "rt_scene_upload: bad rectangle transform chain", RT_ERR_INVALID;
+    if (s->n_media > RT_MAX_MEDIA) return msg = "rt_scene_upload: more than RT_MAX_MEDIA media", RT_ERR_UNSUPPORTED;
+    if (s->n_media && (!s->med_neg_inv_density || !s->med_mat))
+        return msg = "rt_scene_upload: medium arrays missing", RT_ERR_INVALID;
+    for (uint32_t m = 0; m < s->n_media; ++m) {
+        if (s->med_xform && s->med_xform[m] != RT_NO_XFORM && s->med_xform[m] >= s->n_xforms)
+            return msg = "rt_scene_upload: bad wrapper around medium " + std::to_string(m), RT_ERR_INVALID;
+        if (s->med_mat[m] >= s->n_materials) return msg = "rt_scene_upload: medium material out of range", RT_ERR_INVALID;
+        const uint32_t mt = s->mat_type[s->med_mat[m]];
+        // a medium writes neither uv nor tang (hitable.rs:574-576): materials that read them see stale record state
+        if (mt == RT_MAT_DISNEY_METAL) return msg = "rt_scene_upload: DisneyMetal as a phase function reads a stale HitRecord.tang", RT_ERR_UNSUPPORTED;
+        if (mat_needs_tex0(mt) && s->mat_tex0[s->med_mat[m]] < s->n_textures && s->tex_type[s->mat_tex0[s->med_mat[m]]] == RT_TEX_IMAGE)
+            return msg = "rt_scene_upload: an image texture on a medium reads a stale HitRecord.uv", RT_ERR_UNSUPPORTED;
+    }
+    for (uint32_t i = 0; i < s->n_spheres && s->sph_medium; ++i)
+        if (s->sph_medium[i] != RT_NO_MEDIUM && s->sph_medium[i] >= s->n_media) return msg = "rt_scene_upload: bad sphere medium tag", RT_ERR_INVALID;
+    for (uint32_t i = 0; i < s->n_rects && s->rect_medium; ++i)
+        if (s->rect_medium[i] != RT_NO_MEDIUM && s->rect_medium[i] >= s->n_media) return msg = "rt_scene_upload: bad rectangle medium tag", RT_ERR_INVALID;
+    if (s->n_rects && (!s->rect_axis || !s->rect_min || !s->rect_max || !s->rect_mat))
+        return msg = "rt_scene_upload: rectangle arrays missing", RT_ERR_INVALID;
+    for (uint32_t i = 0; i < s->n_rects; ++i) {
+        if (s->rect_axis[i] > RT_RECT_XY) return msg = "rt_scene_upload: unknown rectangle axis", RT_ERR_INVALID;
+        if (s->rect_mat[i] >= s->n_materials)
+            return msg = "rt_scene_upload: rectangle " + std::to_string(i) + " has material index out of range", RT_ERR_INVALID;
+        // DisneyMetal reads rec.tang, which a rectangle never writes (hitable.rs:262-269): the reference then uses
+        // whatever an earlier candidate left in the record — not reproducible outside its traversal order
+        if (s->mat_type[s->rect_mat[i]] == RT_MAT_DISNEY_METAL)
+            return msg = "rt_scene_upload: DisneyMetal on a rectangle reads a stale HitRecord.tang in the reference", RT_ERR_UNSUPPORTED;
+    }
+    for (uint32_t m = 0; m < s->n_materials; ++m) {
+        uint32_t t = s->mat_type[m];
+        if (t >= RT_MAT__COUNT) return msg = "rt_scene_upload: unknown material type", RT_ERR_INVALID;
+        if (mat_needs_tex0(t) && s->mat_tex0[m] >= s->n_textures)
+            return msg = "rt_scene_upload: material " + std::to_string(m) + " needs tex0", RT_ERR_INVALID;
+        if (t == RT_MAT_ROUGH_PLASTIC && s->mat_tex1[m] >= s->n_textures)
+            return msg = "rt_scene_upload: RoughPlastic material needs tex1", RT_ERR_INVALID;
+    }
+    for (uint32_t t = 0; t < s->n_textures; ++t) {
+        uint32_t ty = s->tex_type[t];
+        if (ty >= RT_TEX__COUNT) return msg = "rt_scene_upload: unknown texture type", RT_ERR_INVALID;
+        if (ty == RT_TEX_PERLIN && s->tex_aux[t] >= s->n_perlin)
+            return msg = "rt_scene_upload: Perlin texture references a missing table set", RT_ERR_INVALID;
+        if (ty == RT_TEX_IMAGE && s->tex_aux[t] >= s->n_images)
+            return msg = "rt_scene_upload: image texture references a missing image", RT_ERR_INVALID;
+    }
+    for (uint32_t k = 0; k < s->n_perlin * 3u * RT_PERLIN_POINTS; ++k)
+        if (s->perlin_perm[k] >= RT_PERLIN_POINTS)
+            return msg = "rt_scene_upload: perlin permutation entry out of range", RT_ERR_INVALID;
+    for (uint32_t k = 0; k < s->n_images; ++k) {
+        if (s->img_w[k] == 0 || s->img_h[k] == 0) return msg = "rt_scene_upload: empty image", RT_ERR_INVALID;
+        if (s->img_offset[k] % 3u) return msg = "rt_scene_upload: image offset not a multiple of 3", RT_ERR_INVALID;
+        if (s->img_offset[k] + 3ull * s->img_w[k] * s->img_h[k] > s->n_texel_floats) return msg = "rt_scene_upload: image exceeds texel pool", RT_ERR_INVALID;
+    }
+    if (s->sky_type > RT_SKY_ENV) return msg = "rt_scene_upload: unknown sky type", RT_ERR_INVALID;
+    if (s->sky_type == RT_SKY_ENV && s->sky_image >= s->n_images)
+        return msg = "rt_scene_upload: env sky references a missing image", RT_ERR_INVALID;
+    return RT_OK;
+}
+
+// The arrays of an RtFlatScene as the kernels read them (`opt`: the context's options).
+struct PackedScene {
+    std::vector<float4> geo, rgeo;     // spheres (c, r); rectangles (k, u0, u1, v0), (v1, axis) with (u, v) the uv axes of hitable.rs:262-263 etc.
+    std::vector<uint32_t> smat;
+    std::vector<MatRec> mats;
+    std::vector<TexRec> texs;
+    std::vector<float4> pvec;
+    std::vector<unsigned short> pperm2;
+    std::vector<ImgRec> imgs;
+    bool all_u8 = false;               // the texel pool is RGBA8 (texels8), else float4 (texels)
+    std::vector<float4> texels;
+    std::vector<uint32_t> texels8;
+    std::vector<float4> xparam;
+    std::vector<uint2> xmeta;
+    uint32_t n_xf_listed = 0;
+    int pack(const RtFlatScene* s, const uint32_t* opt, std::string& msg) {
+        geo.resize(s->n_spheres), smat.resize(s->n_spheres);
+        for (uint32_t i = 0; i < s->n_spheres; ++i) {
+            geo[i] = make_float4(s->sph_cx[i], s->sph_cy[i], s->sph_cz[i], s->sph_r[i]);
+            smat[i] = s->sph_mat[i];
+        }
+        mats.resize(s->n_materials);
+        for (uint32_t m = 0; m < s->n_materials; ++m) {
+            MatRec r{};
+            r.type = s->mat_type[m];
+            r.tex0 = s->mat_tex0[m];
+            r.tex1 = s->mat_tex1[m];
+            r.cr = s->mat_color[3 * m], r.cg = s->mat_color[3 * m + 1], r.cb = s->mat_color[3 * m + 2];
+            r.p0 = s->mat_p0[m], r.p1 = s->mat_p1[m], r.p2 = s->mat_p2[m], r.p3 = s->mat_p3[m];
+            mats[m] = r;
+        }
+        texs.resize(s->n_textures);
+        for (uint32_t t = 0; t < s->n_textures; ++t) {
+            TexRec r{};
+            r.type = s->tex_type[t];
+            r.aux = s->tex_aux[t];
+            r.scale = s->tex_scale[t];
+            r.c0r = s->tex_color0[3 * t], r.c0g = s->tex_color0[3 * t + 1], r.c0b = s->tex_color0[3 * t + 2];
+            r.c1r = s->tex_color1[3 * t], r.c1g = s->tex_color1[3 * t + 1], r.c1b = s->tex_color1[3 * t + 2];
+            texs[t] = r;
+        }
+        pvec.resize((size_t)s->n_perlin * 256);
+        std::vector<uint8_t> pperm((size_t)s->n_perlin * 768);
+        for (size_t k = 0; k < pvec.size(); ++k)
+            pvec[k] = make_float4(s->perlin_vec[3 * k], s->perlin_vec[3 * k + 1], s->perlin_vec[3 * k + 2], 0.0f);
+        for (size_t k = 0; k < pperm.size(); ++k) pperm[k] = (uint8_t)s->perlin_perm[k];
+        pperm2.resize(pperm.size()); // entry i with its successor on the 256-ring (PerlinTables)
+        for (size_t k = 0; k < pperm.size(); ++k)
+            pperm2[k] = (unsigned short)(pperm[k] | (pperm[(k & ~(size_t)255) + ((k + 1) & 255)] << 8));
+        imgs.resize(s->n_images);
+        // The texel pool: RGBA8 when every component of every image is exactly k/255 (what image::open(..).to_rgb32f() makes of
+        // an 8-bit file, texture.rs:176-177; image_value() divides k by 255 again and gets the same float), float4 otherwise.
+        auto as_u8 = [](float t, uint32_t& k) {
+            if (!(t >= 0.0f && t <= 1.0f)) return false;
+            k = (uint32_t)std::lrintf(t * 255.0f);
+            const float back = (float)k / 255.0f;
+            return k <= 255u && std::memcmp(&back, &t, sizeof(float)) == 0;
+        };
+        all_u8 = s->n_images > 0 && opt[RT_OPT_TEXEL_POOL] != 1u;
+        for (uint32_t k = 0; k < s->n_images && all_u8; ++k) {
+            const float* src = s->texels + s->img_offset[k];
+            const size_t nc = (size_t)s->img_w[k] * s->img_h[k] * 3u;
+            uint32_t q;
+            for (size_t c = 0; c < nc && all_u8; ++c) all_u8 = as_u8(src[c], q);
+        }
+        uint64_t n_texels = 0;
+        for (uint32_t k = 0; k < s->n_images; ++k) n_texels = std::max<uint64_t>(n_texels, (s->img_offset[k] + 3ull * s->img_w[k] * s->img_h[k]) / 3u);
+        texels.resize(all_u8 ? 0 : (size_t)n_texels);
+        texels8.resize(all_u8 ? (size_t)n_texels : 0);
+        for (uint32_t k = 0; k < s->n_images; ++k) {
+            uint64_t off = s->img_offset[k] / 3u;
+            imgs[k] = ImgRec{s->img_w[k], s->img_h[k], (uint32_t)off, (uint32_t)(off >> 32)};
+            const float* src = s->texels + s->img_offset[k];
+            const size_t np = (size_t)s->img_w[k] * s->img_h[k];
+            for (size_t p = 0; p < np; ++p) {
+                if (all_u8) {
+                    uint32_t r = 0, g = 0, b = 0;
+                    as_u8(src[3 * p], r), as_u8(src[3 * p + 1], g), as_u8(src[3 * p + 2], b);
+                    texels8[off + p] = r | (g << 8) | (b << 16);
+                } else {
+                    texels[off + p] = make_float4(src[3 * p], src[3 * p + 1], src[3 * p + 2], 0.0f);
+                }
+            }
+        }
+
+        rgeo.resize((size_t)s->n_rects * 2);
+        for (uint32_t i = 0; i < s->n_rects; ++i) {
+            const uint32_t ax = s->rect_axis[i];
+            const float* mn = s->rect_min + 3 * (size_t)i;
+            const float* mx = s->rect_max + 3 * (size_t)i;
+            const int ua = ax == 0 ? 1 : 0, va = ax == 2 ? 1 : 2;
+            rgeo[2 * (size_t)i] = make_float4(mn[ax], mn[ua], mx[ua], mn[va]);
+            rgeo[2 * (size_t)i + 1] = make_float4(mx[va], fbits(ax), 0.0f, 0.0f);
+        }
+        // instance wrappers: the listed long chains (the per-primitive innermost wrapper and the world-space bounds come from world_bounds())
+        xparam.resize(s->n_xforms), xmeta.resize(s->n_xforms);
+        // xf_meta[x] = (type, parent).  A chain of more than RT_MAX_CHAIN wrappers is listed once more behind the table, outermost wrapper
+        // first, as (wrapper, chain length), and xf_param[x].w holds where — 0 for a short chain (rt_device.h: the kernels walk short
+        // chains through the parent links into registers and long ones through the list).
+        std::vector<uint32_t> xf_depth(s->n_xforms);
+        std::vector<uint8_t> xf_is_innermost(s->n_xforms, 0); // only the wrapper a primitive or a medium names is ever looked up by a kernel
+        for (uint32_t i = 0; i < s->n_spheres && s->sph_xform; ++i)
+            if (s->sph_xform[i] != RT_NO_XFORM) xf_is_innermost[s->sph_xform[i]] = 1;
+        for (uint32_t i = 0; i < s->n_rects && s->rect_xform; ++i)
+            if (s->rect_xform[i] != RT_NO_XFORM) xf_is_innermost[s->rect_xform[i]] = 1;
+        for (uint32_t m = 0; m < s->n_media && s->med_xform; ++m)
+            if (s->med_xform[m] != RT_NO_XFORM && s->med_xform[m] < s->n_xforms) xf_is_innermost[s->med_xform[m]] = 1;
+        for (uint32_t i = 0; i < s->n_xforms; ++i) {
+            const uint32_t depth = xf_depth[i] = s->xf_parent[i] == RT_NO_XFORM ? 1u : xf_depth[s->xf_parent[i]] + 1u;
+            xparam[i] = make_float4(s->xf_param[4 * i], s->xf_param[4 * i + 1], s->xf_param[4 * i + 2], 0.0f);
+            xmeta[i] = make_uint2(s->xf_type[i], s->xf_parent[i]);
+            if (depth > (uint32_t)RT_MAX_CHAIN && xf_is_innermost[i]) {
+                if ((uint64_t)s->n_xforms + n_xf_listed + depth > 0x7FFFFFFFull) return msg = "rt_scene_upload: wrapper chains too long to list", RT_ERR_UNSUPPORTED;
+                xparam[i].w = fbits(s->n_xforms + n_xf_listed);
+                n_xf_listed += depth;
+            }
+        }
+        xmeta.resize((size_t)s->n_xforms + n_xf_listed);
+        for (uint32_t i = 0; i < s->n_xforms; ++i) {
+            if (xf_depth[i] <= (uint32_t)RT_MAX_CHAIN || !xf_is_innermost[i]) continue;
+            uint32_t p0, k = xf_depth[i];
+            std::memcpy(&p0, &xparam[i].w, 4);
+            for (uint32_t x = i; x != RT_NO_XFORM; x = s->xf_parent[x]) xmeta[p0 + --k] = make_uint2(x, xf_depth[i]);
+        }
+        return RT_OK;
+    }
+};
+
+// Where the closest-hit search of the scene in sr.ds runs: tree in LDS or through L2, wrapper tables in LDS, a grid or none; fills the
+// rest of `sr`.  rt_scene_upload calls it for the static scene, rt_set_quads for the scene with `n_planar` planar primitives behind the
+// media, rt_set_motion for the scene with its moved spheres: `dc` (else NULL) = their displacements, which take 16 B per sphere of LDS beside the geometry wherever the geometry is staged (k_intersect with the tree in
 // LDS, k_intersect_grid) — counted in every budget below, so a scene that no longer fits two workgroups per CU with them falls back
 // exactly as a larger scene does (tree through L2, no grid).  The grid's arrays go through upload() into the current region.
-int configure_search(RtCtx* ctx, uint32_t bvh_depth, const std::vector<float4>& geo, const std::vector<float4>* dc) {
-    const DevScene& ds = ctx->ds;
-    const uint32_t n_entries = ds.n_prims + ds.n_media + ctx->gplanar.n; // (rt_set_quads: the planar primitives behind the media)
+int configure_search(RtCtx* ctx, RtCtx::Search& sr, uint32_t n_planar, uint32_t bvh_depth, const std::vector<float4>& geo, const std::vector<float4>* dc) {
+    const DevScene& ds = sr.ds;
+    const uint32_t n_entries = ds.n_prims + ds.n_media + n_planar;
     const size_t extra = dc ? (size_t)ds.n_spheres * sizeof(float4) : 0u;
     // k_intersect keeps nodes + geometry + one u16 stack column per lane in LDS when that fits 160 KB;
     // larger trees are traversed out of HBM/L2 with only the stacks in LDS; the list walk is the last resort
-    const bool bvh_ok = (ds.n_prims > 0 || ctx->gplanar.n > 0) && ds.n_bvh4_nodes > 0 && ds.n_bvh4_nodes < 32768 && n_entries <= 32768 &&
+    const bool bvh_ok = (ds.n_prims > 0 || n_planar > 0) && ds.n_bvh4_nodes > 0 && ds.n_bvh4_nodes < 32768 && n_entries <= 32768 &&
                         bvh_depth <= RT_BVH_MAX_DEPTH;
     const bool force_hbm = ctx->opt[RT_OPT_TREE_PLACEMENT] == 1u; // test hook: traverse out of HBM even when LDS would fit
     // General scenes (wrappers, rectangles, media): the tree goes to LDS only when TWO workgroups per CU still fit.  Their
@@ -820,25 +1128,25 @@ int configure_search(RtCtx* ctx, uint32_t bvh_depth, const std::vector<float4>& 
     // with tree AND wrapper tables in LDS and one (profiles/round3/final_like.txt) — which is also why final_scene's tree was
     // not squeezed into LDS with quantised boxes: 1 150 nodes x 48 B + 56 KB of stacks leave room for one workgroup only.
     // Sphere-only scenes keep their faster LDS-only kernel (sorted slab planes) even at one workgroup per CU.
-    const bool general = ds.n_rects > 0 || ds.n_xforms > 0 || ds.n_media > 0 || ctx->gplanar.n > 0 || ctx->opt[RT_OPT_GENERAL_KERNELS] == 1u;
-    ctx->general_kernels = general;
+    const bool general = ds.n_rects > 0 || ds.n_xforms > 0 || ds.n_media > 0 || n_planar > 0 || ctx->opt[RT_OPT_GENERAL_KERNELS] == 1u;
+    sr.general_kernels = general;
     const size_t lds_budget = general ? ctx->lds_limit / 2 : ctx->lds_limit;
-    ctx->bvh_in_lds = bvh_ok && bvh_lds_bytes(ds, RT_BVH_BLOCK, true) + extra <= lds_budget && !force_hbm;
-    ctx->isect_lds = bvh_lds_bytes(ds, RT_BVH_BLOCK, ctx->bvh_in_lds);
-    ctx->motion_lds = ctx->bvh_in_lds ? extra : 0u; // (a tree in HBM reads the displacements there too)
-    ctx->use_bvh = bvh_ok && ctx->isect_lds + ctx->motion_lds <= ctx->lds_limit;
+    sr.bvh_in_lds = bvh_ok && bvh_lds_bytes(ds, RT_BVH_BLOCK, true) + extra <= lds_budget && !force_hbm;
+    sr.isect_lds = bvh_lds_bytes(ds, RT_BVH_BLOCK, sr.bvh_in_lds);
+    sr.motion_lds = sr.bvh_in_lds ? extra : 0u; // (a tree in HBM reads the displacements there too)
+    sr.use_bvh = bvh_ok && sr.isect_lds + sr.motion_lds <= ctx->lds_limit;
     // general scenes: wrapper / medium tables behind the tree carve, when two workgroups per CU still fit
-    ctx->general_lds = false;
-    if (ctx->use_bvh && (ds.n_xforms || ds.n_media) && ctx->isect_lds + general_lds_bytes(ds) + ctx->motion_lds <= ctx->lds_limit / 2 &&
+    sr.general_lds = false;
+    if (sr.use_bvh && (ds.n_xforms || ds.n_media) && sr.isect_lds + general_lds_bytes(ds) + sr.motion_lds <= ctx->lds_limit / 2 &&
         ctx->opt[RT_OPT_GENERAL_LDS] != 1u) {
-        ctx->isect_lds += general_lds_bytes(ds);
-        ctx->general_lds = true;
+        sr.isect_lds += general_lds_bytes(ds);
+        sr.general_lds = true;
     }
     // Sphere-only scenes: a uniform grid over the spheres for the rays of depth >= 1 (rt_grid.h), when the scene suits one and
     // two workgroups per CU still fit.  The tree stays: depth 0 (candidate-list overflow), the single-kernel test hook and
     // RT_OPT_GRID = 1 use it, and the tests hold the two searches against each other bit for bit.
-    ctx->use_grid = false;
-    if (ctx->use_bvh && ctx->bvh_in_lds && !general && ctx->opt[RT_OPT_GRID] != 1u) {
+    sr.use_grid = false;
+    if (sr.use_bvh && sr.bvh_in_lds && !general && ctx->opt[RT_OPT_GRID] != 1u) {
         HostGrid hg;
         const size_t half_lds = ctx->lds_limit / 2; // (no room at all beside the displacements: budget 0, no grid)
         build_sphere_grid(geo, half_lds > extra ? half_lds - extra : 0u, (double)ctx->opt[RT_OPT_GRID_CELL] * 1e-3, hg, dc);
@@ -846,15 +1154,22 @@ int configure_search(RtCtx* ctx, uint32_t bvh_depth, const std::vector<float4>& 
             int rc;
             if ((rc = upload(ctx, hg.cells, &hg.gp.cells)) || (rc = upload(ctx, hg.refs, &hg.gp.refs))) return rc;
             hg.gp.sph_geo = ds.sph_geo;
-            ctx->grid = hg.gp;
-            ctx->grid_lds = grid_lds_bytes(hg.gp.n_spheres, hg.gp.n_cells, hg.gp.n_refs);
-            ctx->use_grid = true;
+            sr.grid = hg.gp;
+            sr.grid_lds = grid_lds_bytes(hg.gp.n_spheres, hg.gp.n_cells, hg.gp.n_refs);
+            sr.use_grid = true;
             if (dc) ctx->motion_dbg.grid = hg;
         }
     }
-    ctx->isect_lds += ctx->use_bvh ? ctx->motion_lds : 0u;
-    if (!ctx->use_bvh) ctx->motion_lds = 0u;
+    sr.isect_lds += sr.use_bvh ? sr.motion_lds : 0u;
+    if (!sr.use_bvh) sr.motion_lds = 0u;
     return RT_OK;
+}
+
+// The static renderer: what rt_scene_upload built, without motion or planar set (a light set belongs to neither search state and stays).
+void restore_static_search(RtCtx* ctx) {
+    ctx->search = ctx->static_search;
+    ctx->planar = false, ctx->gplanar = GenPlanar{};
+    ctx->motion = false, ctx->gmotion = GenMotion{}, ctx->motion_dbg = RtCtx::MotionDebug{};
 }
 
 } // namespace
@@ -980,221 +1295,15 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
     if (!ctx) return RT_ERR_INVALID;
     if (!s) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: scene is NULL");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    // ---- validate ---------------------------------------------------------------------------
-    if (s->n_spheres && (!s->sph_cx || !s->sph_cy || !s->sph_cz || !s->sph_r || !s->sph_mat))
-        return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: sphere arrays missing");
-    if (s->n_materials && (!s->mat_type || !s->mat_color || !s->mat_p0 || !s->mat_p1 || !s->mat_p2 || !s->mat_p3 ||
-                           !s->mat_tex0 || !s->mat_tex1))
-        return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: material arrays missing");
-    if (s->n_textures && (!s->tex_type || !s->tex_color0 || !s->tex_color1 || !s->tex_scale || !s->tex_aux))
-        return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: texture arrays missing");
-    if (s->n_perlin && (!s->perlin_vec || !s->perlin_perm))
-        return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: perlin tables missing");
-    if (s->n_images && (!s->img_w || !s->img_h || !s->img_offset || !s->texels))
-        return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: image arrays missing");
-    for (uint32_t i = 0; i < s->n_spheres; ++i) {
-        if (s->sph_mat[i] >= s->n_materials)
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: sphere " + std::to_string(i) + " has material index out of range");
-        // non-finite geometry would reach the tree builder's sort comparators and bin casts (host-side UB)
-        if (!std::isfinite(s->sph_cx[i]) || !std::isfinite(s->sph_cy[i]) || !std::isfinite(s->sph_cz[i]) || !std::isfinite(s->sph_r[i]))
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: sphere " + std::to_string(i) + " has a centre or radius that is not finite");
+    PackedScene pk;
+    {   // ---- validate, then pack
+        std::string msg;
+        int rc = validate_scene(s, msg);
+        if (!rc) rc = pk.pack(s, ctx->opt, msg);
+        if (rc) return fail(ctx, rc, msg);
     }
-    for (uint32_t i = 0; i < 3u * s->n_rects && s->rect_min && s->rect_max; ++i)
-        if (!std::isfinite(s->rect_min[i]) || !std::isfinite(s->rect_max[i]))
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: rectangle " + std::to_string(i / 3u) + " has a bound that is not finite");
-    for (uint32_t i = 0; i < 4u * s->n_xforms && s->xf_param; ++i)
-        if (!std::isfinite(s->xf_param[i]))
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: transform " + std::to_string(i / 4u) + " has a parameter that is not finite");
-    if (s->n_xforms && (!s->xf_type || !s->xf_param || !s->xf_parent))
-        return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: transform arrays missing");
-    for (uint32_t i = 0; i < s->n_xforms; ++i) {
-        if (s->xf_type[i] > RT_XF_ROTATE_Y) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: unknown transform type");
-        if (s->xf_parent[i] != RT_NO_XFORM && s->xf_parent[i] >= i)
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: transform parent must precede its child");
-    }
-    // (a parent precedes its child, so every chain ends; its length is xf_depth below: any number of nested wrappers, hitable.rs:404-520)
-    for (uint32_t i = 0; i < s->n_spheres && s->sph_xform; ++i)
-        if (s->sph_xform[i] != RT_NO_XFORM && s->sph_xform[i] >= s->n_xforms) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: bad sphere transform chain");
-    for (uint32_t i = 0; i < s->n_rects && s->rect_xform; ++i)
-        if (s->rect_xform[i] != RT_NO_XFORM && s->rect_xform[i] >= s->n_xforms) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: bad rectangle transform chain");
-    if (s->n_media > RT_MAX_MEDIA) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_scene_upload: more than RT_MAX_MEDIA media");
-    if (s->n_media && (!s->med_neg_inv_density || !s->med_mat))
-        return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: medium arrays missing");
-    for (uint32_t m = 0; m < s->n_media; ++m) {
-        if (s->med_xform && s->med_xform[m] != RT_NO_XFORM && s->med_xform[m] >= s->n_xforms)
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: bad wrapper around medium " + std::to_string(m));
-        if (s->med_mat[m] >= s->n_materials) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: medium material out of range");
-        const uint32_t mt = s->mat_type[s->med_mat[m]];
-        // a medium writes neither uv nor tang (hitable.rs:574-576): materials that read them see stale record state
-        if (mt == RT_MAT_DISNEY_METAL) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_scene_upload: DisneyMetal as a phase function reads a stale HitRecord.tang");
-        if (mat_needs_tex0(mt) && s->mat_tex0[s->med_mat[m]] < s->n_textures && s->tex_type[s->mat_tex0[s->med_mat[m]]] == RT_TEX_IMAGE)
-            return fail(ctx, RT_ERR_UNSUPPORTED, "rt_scene_upload: an image texture on a medium reads a stale HitRecord.uv");
-    }
-    for (uint32_t i = 0; i < s->n_spheres && s->sph_medium; ++i)
-        if (s->sph_medium[i] != RT_NO_MEDIUM && s->sph_medium[i] >= s->n_media) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: bad sphere medium tag");
-    for (uint32_t i = 0; i < s->n_rects && s->rect_medium; ++i)
-        if (s->rect_medium[i] != RT_NO_MEDIUM && s->rect_medium[i] >= s->n_media) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: bad rectangle medium tag");
-    if (s->n_rects && (!s->rect_axis || !s->rect_min || !s->rect_max || !s->rect_mat))
-        return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: rectangle arrays missing");
-    for (uint32_t i = 0; i < s->n_rects; ++i) {
-        if (s->rect_axis[i] > RT_RECT_XY) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: unknown rectangle axis");
-        if (s->rect_mat[i] >= s->n_materials)
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: rectangle " + std::to_string(i) + " has material index out of range");
-        // DisneyMetal reads rec.tang, which a rectangle never writes (hitable.rs:262-269): the reference then uses
-        // whatever an earlier candidate left in the record — not reproducible outside its traversal order
-        if (s->mat_type[s->rect_mat[i]] == RT_MAT_DISNEY_METAL)
-            return fail(ctx, RT_ERR_UNSUPPORTED, "rt_scene_upload: DisneyMetal on a rectangle reads a stale HitRecord.tang in the reference");
-    }
-    for (uint32_t m = 0; m < s->n_materials; ++m) {
-        uint32_t t = s->mat_type[m];
-        if (t >= RT_MAT__COUNT) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: unknown material type");
-        if (mat_needs_tex0(t) && s->mat_tex0[m] >= s->n_textures)
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: material " + std::to_string(m) + " needs tex0");
-        if (t == RT_MAT_ROUGH_PLASTIC && s->mat_tex1[m] >= s->n_textures)
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: RoughPlastic material needs tex1");
-    }
-    for (uint32_t t = 0; t < s->n_textures; ++t) {
-        uint32_t ty = s->tex_type[t];
-        if (ty >= RT_TEX__COUNT) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: unknown texture type");
-        if (ty == RT_TEX_PERLIN && s->tex_aux[t] >= s->n_perlin)
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: Perlin texture references a missing table set");
-        if (ty == RT_TEX_IMAGE && s->tex_aux[t] >= s->n_images)
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: image texture references a missing image");
-    }
-    for (uint32_t k = 0; k < s->n_perlin * 3u * RT_PERLIN_POINTS; ++k)
-        if (s->perlin_perm[k] >= RT_PERLIN_POINTS)
-            return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: perlin permutation entry out of range");
-    uint64_t n_texels = 0;
-    for (uint32_t k = 0; k < s->n_images; ++k) {
-        if (s->img_w[k] == 0 || s->img_h[k] == 0) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: empty image");
-        if (s->img_offset[k] % 3u) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: image offset not a multiple of 3");
-        uint64_t end = s->img_offset[k] + 3ull * s->img_w[k] * s->img_h[k];
-        if (end > s->n_texel_floats) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: image exceeds texel pool");
-        n_texels = std::max(n_texels, end / 3u);
-    }
-    if (s->sky_type > RT_SKY_ENV) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: unknown sky type");
-    if (s->sky_type == RT_SKY_ENV && s->sky_image >= s->n_images)
-        return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: env sky references a missing image");
-
-    // ---- pack -------------------------------------------------------------------------------
-    std::vector<float4> geo(s->n_spheres);
-    std::vector<uint32_t> smat(s->n_spheres);
-    for (uint32_t i = 0; i < s->n_spheres; ++i) {
-        geo[i] = make_float4(s->sph_cx[i], s->sph_cy[i], s->sph_cz[i], s->sph_r[i]);
-        smat[i] = s->sph_mat[i];
-    }
-    std::vector<MatRec> mats(s->n_materials);
-    for (uint32_t m = 0; m < s->n_materials; ++m) {
-        MatRec r{};
-        r.type = s->mat_type[m];
-        r.tex0 = s->mat_tex0[m];
-        r.tex1 = s->mat_tex1[m];
-        r.cr = s->mat_color[3 * m], r.cg = s->mat_color[3 * m + 1], r.cb = s->mat_color[3 * m + 2];
-        r.p0 = s->mat_p0[m], r.p1 = s->mat_p1[m], r.p2 = s->mat_p2[m], r.p3 = s->mat_p3[m];
-        mats[m] = r;
-    }
-    std::vector<TexRec> texs(s->n_textures);
-    for (uint32_t t = 0; t < s->n_textures; ++t) {
-        TexRec r{};
-        r.type = s->tex_type[t];
-        r.aux = s->tex_aux[t];
-        r.scale = s->tex_scale[t];
-        r.c0r = s->tex_color0[3 * t], r.c0g = s->tex_color0[3 * t + 1], r.c0b = s->tex_color0[3 * t + 2];
-        r.c1r = s->tex_color1[3 * t], r.c1g = s->tex_color1[3 * t + 1], r.c1b = s->tex_color1[3 * t + 2];
-        texs[t] = r;
-    }
-    std::vector<float4> pvec((size_t)s->n_perlin * 256);
-    std::vector<uint8_t> pperm((size_t)s->n_perlin * 768);
-    for (size_t k = 0; k < pvec.size(); ++k)
-        pvec[k] = make_float4(s->perlin_vec[3 * k], s->perlin_vec[3 * k + 1], s->perlin_vec[3 * k + 2], 0.0f);
-    for (size_t k = 0; k < pperm.size(); ++k) pperm[k] = (uint8_t)s->perlin_perm[k];
-    std::vector<unsigned short> pperm2(pperm.size()); // entry i with its successor on the 256-ring (PerlinTables)
-    for (size_t k = 0; k < pperm.size(); ++k)
-        pperm2[k] = (unsigned short)(pperm[k] | (pperm[(k & ~(size_t)255) + ((k + 1) & 255)] << 8));
-    std::vector<ImgRec> imgs(s->n_images);
-    // The texel pool: RGBA8 when every component of every image is exactly k/255 (what image::open(..).to_rgb32f() makes of
-    // an 8-bit file, texture.rs:176-177; image_value() divides k by 255 again and gets the same float), float4 otherwise.
-    auto as_u8 = [](float t, uint32_t& k) {
-        if (!(t >= 0.0f && t <= 1.0f)) return false;
-        k = (uint32_t)std::lrintf(t * 255.0f);
-        const float back = (float)k / 255.0f;
-        return k <= 255u && std::memcmp(&back, &t, sizeof(float)) == 0;
-    };
-    bool all_u8 = s->n_images > 0 && ctx->opt[RT_OPT_TEXEL_POOL] != 1u;
-    for (uint32_t k = 0; k < s->n_images && all_u8; ++k) {
-        const float* src = s->texels + s->img_offset[k];
-        const size_t nc = (size_t)s->img_w[k] * s->img_h[k] * 3u;
-        uint32_t q;
-        for (size_t c = 0; c < nc && all_u8; ++c) all_u8 = as_u8(src[c], q);
-    }
-    std::vector<float4> texels(all_u8 ? 0 : (size_t)n_texels);
-    std::vector<uint32_t> texels8(all_u8 ? (size_t)n_texels : 0);
-    for (uint32_t k = 0; k < s->n_images; ++k) {
-        uint64_t off = s->img_offset[k] / 3u;
-        imgs[k] = ImgRec{s->img_w[k], s->img_h[k], (uint32_t)off, (uint32_t)(off >> 32)};
-        const float* src = s->texels + s->img_offset[k];
-        const size_t np = (size_t)s->img_w[k] * s->img_h[k];
-        for (size_t p = 0; p < np; ++p) {
-            if (all_u8) {
-                uint32_t r = 0, g = 0, b = 0;
-                as_u8(src[3 * p], r), as_u8(src[3 * p + 1], g), as_u8(src[3 * p + 2], b);
-                texels8[off + p] = r | (g << 8) | (b << 16);
-            } else {
-                texels[off + p] = make_float4(src[3 * p], src[3 * p + 1], src[3 * p + 2], 0.0f);
-            }
-        }
-    }
-
-    // rectangles: device geometry (k, u0, u1, v0), (v1, axis) with (u, v) the uv axes of hitable.rs:262-263 etc.
     const uint32_t n_prims = s->n_spheres + s->n_rects;
-    std::vector<float4> rgeo((size_t)s->n_rects * 2);
-    auto fbits = [](uint32_t u) {
-        float f;
-        std::memcpy(&f, &u, 4);
-        return f;
-    };
-    for (uint32_t i = 0; i < s->n_rects; ++i) {
-        const uint32_t ax = s->rect_axis[i];
-        const float* mn = s->rect_min + 3 * (size_t)i;
-        const float* mx = s->rect_max + 3 * (size_t)i;
-        const int ua = ax == 0 ? 1 : 0, va = ax == 2 ? 1 : 2;
-        rgeo[2 * (size_t)i] = make_float4(mn[ax], mn[ua], mx[ua], mn[va]);
-        rgeo[2 * (size_t)i + 1] = make_float4(mx[va], fbits(ax), 0.0f, 0.0f);
-    }
-    // instance wrappers: the listed long chains; the per-primitive innermost wrapper and the world-space bounds come from
-    // world_bounds() below
-    std::vector<float4> xparam(s->n_xforms);
-    std::vector<uint2> xmeta(s->n_xforms);
-    // xf_meta[x] = (type, parent).  A chain of more than RT_MAX_CHAIN wrappers is listed once more behind the table, outermost wrapper
-    // first, as (wrapper, chain length), and xf_param[x].w holds where — 0 for a short chain (rt_device.h: the kernels walk short
-    // chains through the parent links into registers and long ones through the list).
-    uint32_t n_xf_listed = 0;
-    std::vector<uint32_t> xf_depth(s->n_xforms);
-    std::vector<uint8_t> xf_is_innermost(s->n_xforms, 0); // only the wrapper a primitive or a medium names is ever looked up by a kernel
-    for (uint32_t i = 0; i < s->n_spheres && s->sph_xform; ++i)
-        if (s->sph_xform[i] != RT_NO_XFORM) xf_is_innermost[s->sph_xform[i]] = 1;
-    for (uint32_t i = 0; i < s->n_rects && s->rect_xform; ++i)
-        if (s->rect_xform[i] != RT_NO_XFORM) xf_is_innermost[s->rect_xform[i]] = 1;
-    for (uint32_t m = 0; m < s->n_media && s->med_xform; ++m)
-        if (s->med_xform[m] != RT_NO_XFORM && s->med_xform[m] < s->n_xforms) xf_is_innermost[s->med_xform[m]] = 1;
-    for (uint32_t i = 0; i < s->n_xforms; ++i) {
-        const uint32_t depth = xf_depth[i] = s->xf_parent[i] == RT_NO_XFORM ? 1u : xf_depth[s->xf_parent[i]] + 1u;
-        xparam[i] = make_float4(s->xf_param[4 * i], s->xf_param[4 * i + 1], s->xf_param[4 * i + 2], 0.0f);
-        xmeta[i] = make_uint2(s->xf_type[i], s->xf_parent[i]);
-        if (depth > (uint32_t)RT_MAX_CHAIN && xf_is_innermost[i]) {
-            if ((uint64_t)s->n_xforms + n_xf_listed + depth > 0x7FFFFFFFull) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_scene_upload: wrapper chains too long to list");
-            xparam[i].w = fbits(s->n_xforms + n_xf_listed);
-            n_xf_listed += depth;
-        }
-    }
-    xmeta.resize((size_t)s->n_xforms + n_xf_listed);
-    for (uint32_t i = 0; i < s->n_xforms; ++i) {
-        if (xf_depth[i] <= (uint32_t)RT_MAX_CHAIN || !xf_is_innermost[i]) continue;
-        uint32_t p0, k = xf_depth[i];
-        std::memcpy(&p0, &xparam[i].w, 4);
-        for (uint32_t x = i; x != RT_NO_XFORM; x = s->xf_parent[x]) xmeta[p0 + --k] = make_uint2(x, xf_depth[i]);
-    }
-    // world-space bounds of primitives and world entries (culling only; the same code answers rt_debug_world_bounds)
+    // ---- world-space bounds of primitives and world entries (culling only; the same code answers rt_debug_world_bounds)
     WorldBounds wb;
     world_bounds(s, wb);
     const std::vector<uint32_t>& pxf = wb.pxf;
@@ -1237,135 +1346,87 @@ int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
             med_range[m].y |= kind << 24;
         }
     }
-    HostBvh bvh;
-    build_prim_bvh(eboxes, RT_BVH_MAX_DEPTH, bvh);
-    for (auto& dd : bvh.d) { // leaf ids: index into eboxes -> world entry id
-        if (dd.x < 0 && dd.x != INT_MIN) dd.x = ~(int)entry_ids[(size_t)~dd.x];
-        if (dd.y < 0 && dd.y != INT_MIN) dd.y = ~(int)entry_ids[(size_t)~dd.y];
-    }
-    std::vector<uint8_t> sclass(n_entries);
+    // ---- tree
+    HostTree tree;
+    build_tree(eboxes, entry_ids, tree);
+    // ---- shading records and sort keys
+    std::vector<uint8_t> raw_class(n_entries);
     // (at least one record: shade() issues the loads of record 0 for a miss too, see rt_device.h, so an empty scene
     // still needs 5 readable float4)
-    std::vector<float4> srec((size_t)std::max<uint32_t>(n_entries, 1u) * 5, make_float4(0.f, 0.f, 0.f, 0.f));
-    bool class_present[RT_NCLASS] = {};
-    class_present[0] = true; // "miss"
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    std::vector<float4> srec((size_t)std::max<uint32_t>(n_entries, 1u) * 5, zero4);
     for (uint32_t i = 0; i < n_entries; ++i) {
         const bool is_med = i >= n_prims;
         const bool is_rect = !is_med && i >= s->n_spheres;
         const uint32_t m = is_med ? s->med_mat[i - n_prims] : (is_rect ? s->rect_mat[i - s->n_spheres] : s->sph_mat[i]);
-        const uint32_t ty = s->mat_type[m];
-        const bool has_t0 = mat_needs_tex0(ty) && s->mat_tex0[m] < s->n_textures;
-        const uint32_t t0 = has_t0 ? s->mat_tex0[m] : 0u;
-        const uint32_t tt = has_t0 ? s->tex_type[t0] : 0u;
-        sclass[i] = (uint8_t)(1u + ty * 4u + tt); // < RT_NCLASS
-        class_present[sclass[i]] = true;
-        // colour slot: the texture's colour 0 for textured materials, the albedo for Metal
-        const float* col = has_t0 ? s->tex_color0 + 3 * (size_t)t0 : s->mat_color + 3 * (size_t)m;
-        srec[5 * (size_t)i + 0] = is_med ? make_float4(0.f, 0.f, 0.f, 1.f) : (is_rect ? rgeo[2 * (size_t)(i - s->n_spheres)] : geo[i]);
-        srec[5 * (size_t)i + 1] = make_float4(fbits(ty), fbits(tt), fbits(has_t0 ? s->tex_aux[t0] : 0u), fbits(s->mat_tex1[m]));
-        srec[5 * (size_t)i + 2] = make_float4(col[0], col[1], col[2], s->mat_p0[m]);
-        srec[5 * (size_t)i + 3] = make_float4(s->mat_p1[m], s->mat_p2[m], has_t0 ? s->tex_scale[t0] : 0.0f, fbits(s->mat_tex0[m]));
-        srec[5 * (size_t)i + 4] = is_rect ? rgeo[2 * (size_t)(i - s->n_spheres) + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4* rg = is_rect ? &pk.rgeo[2 * (size_t)(i - s->n_spheres)] : nullptr;
+        raw_class[i] = shading_record(pk.mats[m], pk.texs, is_med ? make_float4(0.f, 0.f, 0.f, 1.f) : (is_rect ? rg[0] : pk.geo[i]), is_rect ? rg[1] : zero4,
+                                      &srec[5 * (size_t)i]);
     }
+    std::vector<uint8_t> sclass(raw_class); // (rt_set_quads ranks the raw classes again with those of its primitives)
+    DevScene ds{};
+    ds.key_miss = rank_classes(sclass, s->sky_type);
 
-    // sort keys of k_shade's class sort: the classes present in the scene ranked cheap classes first (a miss and the
-    // constant-texture material.rs materials, then the textured and pbr.rs ones), so that the long Perlin / PBR
-    // segments of a block sit together at its end
-    uint32_t class_key[RT_NCLASS] = {}, n_keys = 0;
-    for (int pass = 0; pass < 2; ++pass)
-        for (uint32_t c = 0; c < RT_NCLASS; ++c)
-            if (class_present[c] && class_is_light(c, s->sky_type) == (pass == 0)) class_key[c] = n_keys++;
-    const std::vector<uint8_t> raw_class = sclass; // (rt_set_quads ranks the classes again with those of its primitives)
-    for (uint32_t i = 0; i < n_entries; ++i) sclass[i] = (uint8_t)class_key[sclass[i]];
-
-    HostBvh4 bvh4;
-    collapse_bvh4(bvh, bvh4);
-
-    // the arrays of the scene before lie in the region the new ones are about to be written to: nothing may still read them
+    // ---- carve and upload.  The arrays of the scene before lie in the region the new ones are about to be written to: nothing may
+    // still read them
     RT_HIP(ctx, hipDeviceSynchronize());
     free_scene(ctx);
-    DevScene ds{};
     ds.n_xforms = s->n_xforms;
     ds.n_media = s->n_media;
     ds.n_rects = s->n_rects;
     ds.n_prims = n_prims;
-    ds.n_bvh4_nodes = (uint32_t)bvh4.id.size();
     ds.n_entries = (uint32_t)eboxes.size();
     ds.n_med_prims = (uint32_t)med_prims.size();
-    ds.n_xf_listed = n_xf_listed;
+    ds.n_xf_listed = pk.n_xf_listed;
     // what only the NEST instantiations of k_intersect evaluate (rt_device.h): a listed chain, the media of mask bit 31, a wrapper around a medium
-    ctx->nest = n_xf_listed > 0 || s->n_media > 32u;
+    ctx->nest = pk.n_xf_listed > 0 || s->n_media > 32u;
     for (uint32_t m = 0; m < s->n_media && s->med_xform; ++m) ctx->nest = ctx->nest || s->med_xform[m] != RT_NO_XFORM;
-    {   // rays whose slab slack exceeds 2^-10 of the scene extent use the cancellation-free slab test (bvh_step)
-        double ext2 = 0.0;
-        for (int k = 0; k < 3; ++k) {
-            float lo = FLT_MAX, hi = -FLT_MAX;
-            for (const PrimBox& b : eboxes) lo = std::min(lo, b.mn[k]), hi = std::max(hi, b.mx[k]);
-            if (hi > lo) ext2 += ((double)hi - lo) * ((double)hi - lo);
-        }
-        ds.bvh_exact_eps = (float)(std::sqrt(ext2) / 1024.0);
-    }
-    ds.bvh4_depth = bvh4.depth;
-    ds.key_miss = class_key[0];
     ds.n_spheres = s->n_spheres, ds.n_materials = s->n_materials, ds.n_textures = s->n_textures;
     ds.n_perlin = s->n_perlin, ds.n_images = s->n_images, ds.sky_type = s->sky_type, ds.sky_image = s->sky_image;
-    int rc;
-    std::vector<float4> pgeo(geo);
-    pgeo.insert(pgeo.end(), rgeo.begin(), rgeo.end());
-    auto upload_all = [&]() -> int {
+    std::vector<float4> pgeo(pk.geo);
+    pgeo.insert(pgeo.end(), pk.rgeo.begin(), pk.rgeo.end());
+    // the scene's own region, the one of the scene before when it is large enough
+    int rc = carve_region(ctx, ctx->scene_region, true, [&]() -> int {
         int rc;
-        if ((rc = upload(ctx, pgeo, &ds.prim_geo)) || (rc = upload(ctx, smat, &ds.sph_mat)) || (rc = upload(ctx, mats, &ds.mats)) ||
-            (rc = upload(ctx, texs, &ds.texs)) || (rc = upload(ctx, pvec, &ds.perlin_vec)) ||
-            (rc = upload(ctx, pperm2, &ds.perlin_perm2)) || (rc = upload(ctx, imgs, &ds.imgs)) ||
-            (rc = upload(ctx, texels, &ds.texels)) || (rc = upload(ctx, texels8, &ds.texels8)) || (rc = upload(ctx, pmed, &ds.prim_medium)) || (rc = upload(ctx, med_prims, &ds.med_prims)) || (rc = upload(ctx, med_range, &ds.med_range)) || (rc = upload(ctx, med_xf, &ds.med_xform)) ||
+        if ((rc = upload(ctx, pgeo, &ds.prim_geo)) || (rc = upload(ctx, pk.smat, &ds.sph_mat)) || (rc = upload(ctx, pk.mats, &ds.mats)) ||
+            (rc = upload(ctx, pk.texs, &ds.texs)) || (rc = upload(ctx, pk.pvec, &ds.perlin_vec)) ||
+            (rc = upload(ctx, pk.pperm2, &ds.perlin_perm2)) || (rc = upload(ctx, pk.imgs, &ds.imgs)) ||
+            (rc = upload(ctx, pk.texels, &ds.texels)) || (rc = upload(ctx, pk.texels8, &ds.texels8)) || (rc = upload(ctx, pmed, &ds.prim_medium)) ||
+            (rc = upload(ctx, med_prims, &ds.med_prims)) || (rc = upload(ctx, med_range, &ds.med_range)) || (rc = upload(ctx, med_xf, &ds.med_xform)) ||
             (rc = upload(ctx, ent_bs, &ds.ent_bs)) || (rc = upload(ctx, entry_ids, &ds.ent_leaf)) ||
-            (rc = upload(ctx, med_nid, &ds.med_neg_inv_density)) || (rc = upload(ctx, pxf, &ds.prim_xform)) || (rc = upload(ctx, xparam, &ds.xf_param)) ||
-            (rc = upload(ctx, xmeta, &ds.xf_meta)) || (rc = upload(ctx, sclass, &ds.sph_class)) || (rc = upload(ctx, srec, &ds.sph_rec)) || (rc = upload(ctx, bvh4.id, &ds.bvh4_id)) ||
-            (rc = upload(ctx, bvh4.p[0], &ds.bvh4_p[0])) || (rc = upload(ctx, bvh4.p[1], &ds.bvh4_p[1])) ||
-            (rc = upload(ctx, bvh4.p[2], &ds.bvh4_p[2])) || (rc = upload(ctx, bvh4.p[3], &ds.bvh4_p[3])) ||
-            (rc = upload(ctx, bvh4.p[4], &ds.bvh4_p[4])) || (rc = upload(ctx, bvh4.p[5], &ds.bvh4_p[5]))) return rc;
-        return RT_OK;
-    };
-    // first pass: what the arrays need (upload() only adds up); then ONE region for them, the one of the scene before when it
-    // is large enough, else a new one from the pool (+ 25 %, + room for the grid's cell arrays) — no hipMalloc per array, none at
-    // all in the common case, and the copies go through page-locked staging
-    ctx->scene_measuring = true, ctx->scene_measure = 0;
-    (void)upload_all();
-    ctx->scene_measuring = false;
-    {
-        const size_t need = ctx->scene_measure + (1u << 20);
-        if (need > ctx->scene_region.bytes && (rc = ensure(ctx, ctx->scene_region, need + need / 4u))) return rc;
-        ctx->scene_used = 0;
-    }
-    if ((rc = upload_all())) {
+            (rc = upload(ctx, med_nid, &ds.med_neg_inv_density)) || (rc = upload(ctx, pxf, &ds.prim_xform)) || (rc = upload(ctx, pk.xparam, &ds.xf_param)) ||
+            (rc = upload(ctx, pk.xmeta, &ds.xf_meta)) || (rc = upload(ctx, sclass, &ds.sph_class)) || (rc = upload(ctx, srec, &ds.sph_rec))) return rc;
+        return upload_tree(ctx, tree, ds);
+    });
+    if (rc) {
         free_scene(ctx);
         return rc;
     }
     ds.sph_geo = ds.prim_geo;
     ds.rect_geo = ds.prim_geo + s->n_spheres;
-    if (!all_u8) ds.texels8 = nullptr; // (upload() hands out a 16 B allocation even for an empty pool)
-    ctx->ds = ds;
-    ctx->has_scene = true;
-    {   // what rt_set_motion needs to bound moved spheres again, and the state it puts back when the motion is cleared
-        ctx->keep.geo = geo, ctx->keep.eboxes = eboxes, ctx->keep.entry_ids = entry_ids, ctx->keep.ent_bs = ent_bs;
-        ctx->keep.bare.assign(s->n_spheres, 0);
-        for (uint32_t i = 0; i < s->n_spheres; ++i) ctx->keep.bare[i] = pxf[i] == RT_NO_XFORM && pmed[i] == RT_NO_MEDIUM;
-        ctx->keep.bvh_depth = bvh.depth;
-        ctx->keep.mats = mats, ctx->keep.texs = texs, ctx->keep.srec = srec, ctx->keep.raw_class = raw_class, ctx->keep.sky_type = s->sky_type;
-        ctx->keep.world_mag = 0.0;
+    if (!pk.all_u8) ds.texels8 = nullptr; // (upload() hands out a 16 B allocation even for an empty pool)
+    {   // what rt_set_motion and rt_set_quads need of the scene on the host
+        RtCtx::Keep& kp = ctx->keep;
+        kp.geo = pk.geo, kp.eboxes = eboxes, kp.entry_ids = entry_ids, kp.ent_bs = ent_bs;
+        kp.bare.assign(s->n_spheres, 0);
+        for (uint32_t i = 0; i < s->n_spheres; ++i) kp.bare[i] = pxf[i] == RT_NO_XFORM && pmed[i] == RT_NO_MEDIUM;
+        kp.mats = pk.mats, kp.texs = pk.texs, kp.srec = srec, kp.raw_class = raw_class, kp.sky_type = s->sky_type;
+        kp.world_mag = 0.0;
         for (const PrimBox& b : eboxes)
             for (int k = 0; k < 3; ++k)
-                if (std::isfinite(b.mn[k]) && std::isfinite(b.mx[k])) ctx->keep.world_mag = std::max(ctx->keep.world_mag, (double)std::max(std::fabs(b.mn[k]), std::fabs(b.mx[k])));
-        ctx->planar = false, ctx->gplanar = GenPlanar{};
-        ctx->lights = false, ctx->glights = GenLights{};
-        ctx->motion = false, ctx->motion_lds = 0, ctx->gmotion = GenMotion{}, ctx->motion_dbg = RtCtx::MotionDebug{};
+                if (std::isfinite(b.mn[k]) && std::isfinite(b.mx[k])) kp.world_mag = std::max(kp.world_mag, (double)std::max(std::fabs(b.mn[k]), std::fabs(b.mx[k])));
     }
-    if ((rc = configure_search(ctx, bvh.depth, geo, nullptr))) {
+    // ---- configure, and the snapshot: the static renderer is the active one, without any set of the scene before
+    RtCtx::Search sr;
+    sr.ds = ds;
+    if ((rc = configure_search(ctx, sr, 0u, tree.depth, pk.geo, nullptr))) { // (the grid's arrays go behind the scene's)
         free_scene(ctx);
         return rc;
     }
-    ctx->static_search = RtCtx::Search{ctx->ds, ctx->use_bvh, ctx->bvh_in_lds, ctx->general_lds, ctx->use_grid, ctx->isect_lds, ctx->grid_lds, ctx->grid,
-                                       ctx->general_kernels};
+    ctx->static_search = sr;
+    restore_static_search(ctx);
+    ctx->lights = false, ctx->glights = GenLights{};
+    ctx->has_scene = true;
     return RT_OK;
 }
 
@@ -1447,7 +1508,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     const uint32_t npix = (uint32_t)npix64;
     const int n_depths = prm->max_depth + 1;
     const uint32_t nq = queue_shards(ctx);
-    const bool use_bvh = ctx->use_bvh && !(prm->flags & RT_FLAG_BRUTE_FORCE);
+    const bool use_bvh = ctx->search.use_bvh && !(prm->flags & RT_FLAG_BRUTE_FORCE);
     // depth 0 regenerates the primary ray in both kernels instead of materialising the queue
     const bool fuse_gen = use_bvh && ctx->opt[RT_OPT_MATERIALISE_PRIMARIES] != 1u;
     // Candidate lists of the primary rays, once per frame (k_primary_lists): worth it when the samples of a pixel
@@ -1455,7 +1516,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     // 46.7 -> 41.9 ms, pbr_sweep_scene 41.2 -> 39.3, test_sphere 15.5 -> 14.8, cornell_box unchanged (its walls'
     // bounding spheres cover every pixel: overflow); final_scene (3 408 entries, most pixels overflow) would pay
     // 3 ms for nothing, hence the cap.
-    const bool want_lists = use_bvh && fuse_gen && spp >= 4 && ctx->ds.n_entries > 0 && ctx->ds.n_entries <= 2048 && ctx->opt[RT_OPT_PRIMARY_LISTS] != 1u &&
+    const bool want_lists = use_bvh && fuse_gen && spp >= 4 && ctx->search.ds.n_entries > 0 && ctx->search.ds.n_entries <= 2048 && ctx->opt[RT_OPT_PRIMARY_LISTS] != 1u &&
                             !ctx->planar; // (the lists know the static entries only)
 
     // the small persistent buffers first (they lie at the bottom of the pool); the work buffers of the slices start above them
@@ -1520,11 +1581,11 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
         uint32_t* n_overflow = (uint32_t*)((uint4*)ctx->lists.p + npix);
         gp.n_overflow = n_overflow;
         RT_HIP(ctx, hipMemsetAsync(n_overflow, 0, sizeof(uint4), st));
-        const size_t lists_lds = (size_t)ctx->ds.n_entries * sizeof(float4) + 4u * RT_LIST_WAVE_CAP * 2u;
+        const size_t lists_lds = (size_t)ctx->search.ds.n_entries * sizeof(float4) + 4u * RT_LIST_WAVE_CAP * 2u;
         if (lens)
-            hipLaunchKernelGGL(k_primary_lists<true>, dim3((npix + 255u) / 256u), dim3(256), lists_lds, st, ctx->ds, gp, (uint4*)ctx->lists.p, n_overflow, glens);
+            hipLaunchKernelGGL(k_primary_lists<true>, dim3((npix + 255u) / 256u), dim3(256), lists_lds, st, ctx->search.ds, gp, (uint4*)ctx->lists.p, n_overflow, glens);
         else
-            hipLaunchKernelGGL(k_primary_lists<false>, dim3((npix + 255u) / 256u), dim3(256), lists_lds, st, ctx->ds, gp, (uint4*)ctx->lists.p, n_overflow, glens);
+            hipLaunchKernelGGL(k_primary_lists<false>, dim3((npix + 255u) / 256u), dim3(256), lists_lds, st, ctx->search.ds, gp, (uint4*)ctx->lists.p, n_overflow, glens);
         // The one host decision of a frame: with no overflowing list (every headline configuration) depth 0 of a sphere-only scene
         // needs no closest-hit launch at all — k_shade<GEN> finds every hit from the lists.  An empty launch is not free: each of
         // its workgroups waits for 66 KB of LDS behind the other chain's shading waves and holds its own chain's shading back
@@ -1565,7 +1626,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     // with one; sphere_scene 18.0 -> 18.6, simple_light_scene's bare rectangles likewise prefer two:
     // profiles/round3/one_stream.txt).  RT_OPT_CHAINS = 1 / 2 force either.
     const uint32_t chains_opt = ctx->opt[RT_OPT_CHAINS];
-    const bool one_chain = chains_opt ? chains_opt == 1u : (ctx->ds.n_xforms > 0 || ctx->ds.n_media > 0 || (use_bvh && !ctx->bvh_in_lds));
+    const bool one_chain = chains_opt ? chains_opt == 1u : (ctx->search.ds.n_xforms > 0 || ctx->search.ds.n_media > 0 || (use_bvh && !ctx->search.bvh_in_lds));
     const uint32_t n_groups = (nq >= 2u * RT_ISECT_MAX_SHARDS && !time_depths && !one_chain) ? 2u : 1u;
     const uint32_t shards_per_wg = (nq + isect_grid - 1u) / isect_grid;
     // selects the "general scene" kernel instantiations (rectangles and Translate / RotateY wrappers)
@@ -1925,21 +1986,21 @@ int rt_debug_scene_info(const RtCtx* ctx, RtSceneInfo* info) {
     if (!ctx || !info) return RT_ERR_INVALID;
     std::memset(info, 0, sizeof(*info));
     if (!ctx->has_scene) return RT_ERR_STATE;
-    info->n_entries = ctx->ds.n_entries;
-    info->n_tree_nodes = ctx->ds.n_bvh4_nodes;
-    info->tree_depth = ctx->ds.bvh4_depth;
-    info->tree_in_lds = ctx->use_bvh && ctx->bvh_in_lds;
+    info->n_entries = ctx->search.ds.n_entries;
+    info->n_tree_nodes = ctx->search.ds.n_bvh4_nodes;
+    info->tree_depth = ctx->search.ds.bvh4_depth;
+    info->tree_in_lds = ctx->search.use_bvh && ctx->search.bvh_in_lds;
     info->general_kernels = scene_is_general(ctx);
-    info->closest_hit_lds_bytes = (uint32_t)ctx->isect_lds;
-    info->grid = ctx->use_grid;
-    info->general_tables_in_lds = ctx->general_lds;
+    info->closest_hit_lds_bytes = (uint32_t)ctx->search.isect_lds;
+    info->grid = ctx->search.use_grid;
+    info->general_tables_in_lds = ctx->search.general_lds;
     info->nest = ctx->nest;
-    if (ctx->use_grid) {
-        info->grid_cells[0] = ctx->grid.nx, info->grid_cells[1] = ctx->grid.ny, info->grid_cells[2] = ctx->grid.nz;
-        info->grid_refs = ctx->grid.all_rec >> RT_GRID_CNT_BITS;
-        info->grid_always = ctx->grid.n_always;
-        info->grid_lds_bytes = (uint32_t)ctx->grid_lds;
-        for (int k = 0; k < 3; ++k) info->grid_cell_size[k] = ctx->grid.cs[k];
+    if (ctx->search.use_grid) {
+        info->grid_cells[0] = ctx->search.grid.nx, info->grid_cells[1] = ctx->search.grid.ny, info->grid_cells[2] = ctx->search.grid.nz;
+        info->grid_refs = ctx->search.grid.all_rec >> RT_GRID_CNT_BITS;
+        info->grid_always = ctx->search.grid.n_always;
+        info->grid_lds_bytes = (uint32_t)ctx->search.grid_lds;
+        for (int k = 0; k < 3; ++k) info->grid_cell_size[k] = ctx->search.grid.cs[k];
     }
     return RT_OK;
 }
@@ -1964,12 +2025,11 @@ int rt_set_lens(RtCtx* ctx, const RtLens* lens) {
     return RT_OK;
 }
 
-static void restore_static_search(RtCtx* ctx) {
-    const RtCtx::Search& st = ctx->static_search;
-    ctx->ds = st.ds, ctx->use_bvh = st.use_bvh, ctx->bvh_in_lds = st.bvh_in_lds, ctx->general_lds = st.general_lds, ctx->use_grid = st.use_grid;
-    ctx->isect_lds = st.isect_lds, ctx->grid_lds = st.grid_lds, ctx->grid = st.grid, ctx->general_kernels = st.general_kernels;
-    ctx->planar = false, ctx->gplanar = GenPlanar{};
-    ctx->motion = false, ctx->motion_lds = 0, ctx->gmotion = GenMotion{}, ctx->motion_dbg = RtCtx::MotionDebug{};
+static int check_shutter(RtCtx* ctx, const RtMotion* m) {
+    if (!std::isfinite(m->shutter_open) || !std::isfinite(m->shutter_close) || m->shutter_open < 0.0f || m->shutter_close > 1.0f ||
+        m->shutter_open > m->shutter_close)
+        return fail(ctx, RT_ERR_INVALID, "rt_set_motion: the shutter must satisfy 0 <= shutter_open <= shutter_close <= 1");
+    return RT_OK;
 }
 
 // Moving spheres.  Everything that bounds a listed sphere is built again over the region it sweeps; the static arrays stay where they
@@ -1987,9 +2047,7 @@ int rt_set_motion(RtCtx* ctx, const RtMotion* motion) {
     if (!ctx->has_scene) return fail(ctx, RT_ERR_STATE, "rt_set_motion: no scene uploaded");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!motion || motion->n_moving == 0) {
-        if (motion && (!std::isfinite(motion->shutter_open) || !std::isfinite(motion->shutter_close) || motion->shutter_open < 0.0f ||
-                       motion->shutter_close > 1.0f || motion->shutter_open > motion->shutter_close))
-            return fail(ctx, RT_ERR_INVALID, "rt_set_motion: the shutter must satisfy 0 <= shutter_open <= shutter_close <= 1");
+        if (motion && check_shutter(ctx, motion)) return RT_ERR_INVALID;
         if (ctx->motion) {
             RT_HIP(ctx, hipDeviceSynchronize());
             restore_static_search(ctx);
@@ -2000,9 +2058,7 @@ int rt_set_motion(RtCtx* ctx, const RtMotion* motion) {
     if (ctx->lights) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_set_motion: the context holds a light set (rt_set_lights); the two do not combine yet");
     const uint32_t n_sph = ctx->static_search.ds.n_spheres, nm = motion->n_moving;
     if (!motion->sphere || !motion->center1) return fail(ctx, RT_ERR_INVALID, "rt_set_motion: NULL array");
-    if (!std::isfinite(motion->shutter_open) || !std::isfinite(motion->shutter_close) || motion->shutter_open < 0.0f ||
-        motion->shutter_close > 1.0f || motion->shutter_open > motion->shutter_close)
-        return fail(ctx, RT_ERR_INVALID, "rt_set_motion: the shutter must satisfy 0 <= shutter_open <= shutter_close <= 1");
+    if (check_shutter(ctx, motion)) return RT_ERR_INVALID;
     const RtCtx::Keep& kp = ctx->keep;
     for (uint32_t k = 0; k < nm; ++k) {
         const uint32_t i = motion->sphere[k];
@@ -2046,61 +2102,26 @@ int rt_set_motion(RtCtx* ctx, const RtMotion* motion) {
         bs.w = round_up((r + std::sqrt(half2) + std::sqrt(mx * mx + my * my + mz * mz) + 1.7321 * slack_max) * (1.0 + 1e-12));
         ent_bs[e] = bs;
     }
-    HostBvh bvh;
-    build_prim_bvh(eboxes, RT_BVH_MAX_DEPTH, bvh);
-    for (auto& dd : bvh.d) { // leaf ids: index into eboxes -> world entry id
-        if (dd.x < 0 && dd.x != INT_MIN) dd.x = ~(int)kp.entry_ids[(size_t)~dd.x];
-        if (dd.y < 0 && dd.y != INT_MIN) dd.y = ~(int)kp.entry_ids[(size_t)~dd.y];
-    }
-    HostBvh4 bvh4;
-    collapse_bvh4(bvh, bvh4);
+    HostTree tree;
+    build_tree(eboxes, kp.entry_ids, tree);
     // ---- device: nothing may still read the motion arrays of the call before
     RT_HIP(ctx, hipDeviceSynchronize());
     restore_static_search(ctx);
-    DevScene ds = ctx->static_search.ds;
-    ds.n_bvh4_nodes = (uint32_t)bvh4.id.size();
-    ds.bvh4_depth = bvh4.depth;
-    {
-        double ext2 = 0.0;
-        for (int k = 0; k < 3; ++k) {
-            float lo = FLT_MAX, hi = -FLT_MAX;
-            for (const PrimBox& b : eboxes) lo = std::min(lo, b.mn[k]), hi = std::max(hi, b.mx[k]);
-            if (hi > lo) ext2 += ((double)hi - lo) * ((double)hi - lo);
-        }
-        ds.bvh_exact_eps = (float)(std::sqrt(ext2) / 1024.0);
-    }
+    RtCtx::Search sr;
+    sr.ds = ctx->static_search.ds;
     const float4* d_dc = nullptr;
-    auto upload_all = [&]() -> int {
+    ctx->motion_dbg.sphere.assign(motion->sphere, motion->sphere + nm);
+    const int rc = carve_region(ctx, ctx->motion_region, false, [&]() -> int {
         int rc;
-        if ((rc = upload(ctx, dc, &d_dc)) || (rc = upload(ctx, ent_bs, &ds.ent_bs)) || (rc = upload(ctx, bvh4.id, &ds.bvh4_id)) ||
-            (rc = upload(ctx, bvh4.p[0], &ds.bvh4_p[0])) || (rc = upload(ctx, bvh4.p[1], &ds.bvh4_p[1])) ||
-            (rc = upload(ctx, bvh4.p[2], &ds.bvh4_p[2])) || (rc = upload(ctx, bvh4.p[3], &ds.bvh4_p[3])) ||
-            (rc = upload(ctx, bvh4.p[4], &ds.bvh4_p[4])) || (rc = upload(ctx, bvh4.p[5], &ds.bvh4_p[5]))) return rc;
-        return RT_OK;
-    };
-    // upload() carves the scene region: for this call the motion region stands in for it (measured first, + room for the grid's arrays)
-    const DevBuf scene_region = ctx->scene_region;
-    const size_t scene_used = ctx->scene_used;
-    ctx->scene_measuring = true, ctx->scene_measure = 0;
-    (void)upload_all();
-    ctx->scene_measuring = false;
-    int rc = ensure(ctx, ctx->motion_region, ctx->scene_measure + (1u << 20));
-    if (!rc) {
-        ctx->scene_region = ctx->motion_region, ctx->scene_used = 0;
-        rc = upload_all();
-        if (!rc) {
-            ctx->ds = ds;
-            ctx->motion_dbg.sphere.assign(motion->sphere, motion->sphere + nm);
-            rc = configure_search(ctx, bvh.depth, kp.geo, &dc);
-        }
-        ctx->scene_region = scene_region, ctx->scene_used = scene_used;
-    }
-    if (rc) { // (a device error: the static renderer)
-        const std::string err = ctx->err;
+        if ((rc = upload(ctx, dc, &d_dc)) || (rc = upload(ctx, ent_bs, &sr.ds.ent_bs)) || (rc = upload_tree(ctx, tree, sr.ds))) return rc;
+        // (the grid's arrays must land in this region too: they fit the room the first pass leaves, as they do behind a scene)
+        return ctx->scene_measuring ? RT_OK : configure_search(ctx, sr, 0u, tree.depth, kp.geo, &dc);
+    });
+    if (rc) { // (a device error, in ctx->err: the static renderer)
         restore_static_search(ctx);
-        ctx->err = err;
         return rc;
     }
+    ctx->search = sr;
     ctx->motion_dbg.eboxes = eboxes, ctx->motion_dbg.ent_bs = ent_bs;
     ctx->gmotion = GenMotion{d_dc, motion->shutter_open, motion->shutter_close - motion->shutter_open};
     ctx->motion = true;
@@ -2125,7 +2146,7 @@ int rt_debug_motion_bounds(const RtCtx* ctx, float* entry_box_padded, float* ent
             entry_ids[e] = ctx->keep.entry_ids[e];
         }
     bool cells_fit = true;
-    if (ctx->use_grid && md.grid.ok) {
+    if (ctx->search.use_grid && md.grid.ok) {
         const GridParams& g = md.grid.gp;
         dims[0] = g.nx, dims[1] = g.ny, dims[2] = g.nz;
         for (int k = 0; k < 3; ++k) grid[k] = g.g0[k], grid[3 + k] = g.cs[k];
@@ -2169,6 +2190,7 @@ struct PlanarHost {
     std::vector<float4> pq;     // 5 per primitive (planar_root)
     std::vector<PrimBox> boxes; // corners + slack
     std::vector<float> slack;
+    std::vector<float> len;     // |cross(u, v)| in f32: a parallelogram's area (rt_set_lights)
     double world_mag = 0.0;     // W: the scene's and the set's largest coordinate magnitude
 };
 static int planar_setup(const RtQuads* q, double world_mag, PlanarHost& out, std::string& err) {
@@ -2182,7 +2204,7 @@ static int planar_setup(const RtQuads* q, double world_mag, PlanarHost& out, std
     }
     out.world_mag = W;
     out.pq.assign(5 * (size_t)n, make_float4(0.f, 0.f, 0.f, 0.f));
-    out.boxes.resize(n), out.slack.resize(n);
+    out.boxes.resize(n), out.slack.resize(n), out.len.resize(n);
     for (uint32_t i = 0; i < n; ++i) {
         if (q->kind[i] > RT_PLANAR_TRIANGLE) return err = "primitive " + std::to_string(i) + " has a kind outside RtPlanarKind", RT_ERR_INVALID;
         const float* Q = q->q + 3 * (size_t)i;
@@ -2214,11 +2236,9 @@ static int planar_setup(const RtQuads* q, double world_mag, PlanarHost& out, std
         const float wx = nx / nn, wy = ny / nn, wz = nz / nn;
         if (!std::isfinite(ux) || !std::isfinite(uy) || !std::isfinite(uz) || !std::isfinite(D) || !std::isfinite(wx) || !std::isfinite(wy) || !std::isfinite(wz) || !(nn > 0.0f))
             return err = "primitive " + std::to_string(i) + ": the f32 plane set-up overflows or underflows", RT_ERR_INVALID;
-        uint32_t kb = q->kind[i];
-        float kf;
-        std::memcpy(&kf, &kb, 4);
+        out.len[i] = len;
         out.pq[5 * (size_t)i + 0] = make_float4(ux, uy, uz, D);
-        out.pq[5 * (size_t)i + 1] = make_float4(Q[0], Q[1], Q[2], kf);
+        out.pq[5 * (size_t)i + 1] = make_float4(Q[0], Q[1], Q[2], fbits(q->kind[i]));
         out.pq[5 * (size_t)i + 2] = make_float4(u[0], u[1], u[2], 0.0f);
         out.pq[5 * (size_t)i + 3] = make_float4(v[0], v[1], v[2], 0.0f);
         out.pq[5 * (size_t)i + 4] = make_float4(wx, wy, wz, 0.0f);
@@ -2276,104 +2296,43 @@ int rt_set_quads(RtCtx* ctx, const RtQuads* quads) {
             return fail(ctx, RT_ERR_UNSUPPORTED, "rt_set_quads: DisneyMetal on a planar primitive reads a tangent it does not carry");
     }
     // ---- records and sort keys: the static ones, then the set's; the classes present are ranked again (rt_scene_upload)
-    auto fbits = [](uint32_t u) {
-        float f;
-        std::memcpy(&f, &u, 4);
-        return f;
-    };
-    std::vector<float4> srec((size_t)(base + n) * 5, make_float4(0.f, 0.f, 0.f, 0.f));
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    std::vector<float4> srec((size_t)(base + n) * 5, zero4);
     std::copy(kp.srec.begin(), kp.srec.begin() + 5 * (size_t)base, srec.begin());
     std::vector<uint8_t> sclass(kp.raw_class);
     sclass.resize((size_t)base + n);
-    const uint32_t n_tex = (uint32_t)kp.texs.size();
-    for (uint32_t i = 0; i < n; ++i) {
-        const MatRec& m = kp.mats[quads->mat[i]];
-        const bool has_t0 = mat_needs_tex0(m.type) && m.tex0 < n_tex;
-        const uint32_t tt = has_t0 ? kp.texs[m.tex0].type : 0u;
-        sclass[base + i] = (uint8_t)(1u + m.type * 4u + tt);
-        const size_t r = 5 * (size_t)(base + i);
-        srec[r + 1] = make_float4(fbits(m.type), fbits(tt), fbits(has_t0 ? kp.texs[m.tex0].aux : 0u), fbits(m.tex1));
-        srec[r + 2] = has_t0 ? make_float4(kp.texs[m.tex0].c0r, kp.texs[m.tex0].c0g, kp.texs[m.tex0].c0b, m.p0) : make_float4(m.cr, m.cg, m.cb, m.p0);
-        srec[r + 3] = make_float4(m.p1, m.p2, has_t0 ? kp.texs[m.tex0].scale : 0.0f, fbits(m.tex0));
-    }
-    bool class_present[RT_NCLASS] = {};
-    class_present[0] = true;
-    for (uint8_t c : sclass) class_present[c] = true;
-    uint32_t class_key[RT_NCLASS] = {}, n_keys = 0;
-    for (int pass = 0; pass < 2; ++pass)
-        for (uint32_t c = 0; c < RT_NCLASS; ++c)
-            if (class_present[c] && class_is_light(c, kp.sky_type) == (pass == 0)) class_key[c] = n_keys++;
-    for (uint8_t& c : sclass) c = (uint8_t)class_key[c];
+    for (uint32_t i = 0; i < n; ++i) sclass[base + i] = shading_record(kp.mats[quads->mat[i]], kp.texs, zero4, zero4, &srec[5 * (size_t)(base + i)]);
+    RtCtx::Search sr;
+    sr.ds = ctx->static_search.ds;
+    sr.ds.key_miss = rank_classes(sclass, kp.sky_type);
     // ---- the tree over the scene's entries and the set
     std::vector<PrimBox> eboxes = kp.eboxes;
     std::vector<uint32_t> entry_ids = kp.entry_ids;
     for (uint32_t i = 0; i < n; ++i) eboxes.push_back(ph.boxes[i]), entry_ids.push_back(base + i);
-    HostBvh bvh;
-    build_prim_bvh(eboxes, RT_BVH_MAX_DEPTH, bvh);
-    for (auto& dd : bvh.d) {
-        if (dd.x < 0 && dd.x != INT_MIN) dd.x = ~(int)entry_ids[(size_t)~dd.x];
-        if (dd.y < 0 && dd.y != INT_MIN) dd.y = ~(int)entry_ids[(size_t)~dd.y];
-    }
-    HostBvh4 bvh4;
-    collapse_bvh4(bvh, bvh4);
-    if (bvh4.id.size() >= 32768u || bvh.depth > RT_BVH_MAX_DEPTH) return fail(ctx, RT_ERR_INVALID, "rt_set_quads: the tree over the set has more nodes or levels than the kernels index");
-    // ---- device: nothing may still read the arrays of the set before
+    sr.ds.n_entries = (uint32_t)eboxes.size();
+    HostTree tree;
+    build_tree(eboxes, entry_ids, tree);
+    if (tree.bvh4.id.size() >= 32768u || tree.depth > RT_BVH_MAX_DEPTH) return fail(ctx, RT_ERR_INVALID, "rt_set_quads: the tree over the set has more nodes or levels than the kernels index");
+    // ---- device: nothing may still read the arrays of the set before.  A set that replaces another is written to the other's region
+    // after this synchronize, while the context still names the old arrays: on a device error it goes back to the static renderer, not
+    // to the previous set.
     RT_HIP(ctx, hipDeviceSynchronize());
-    DevScene ds = ctx->static_search.ds;
-    ds.n_bvh4_nodes = (uint32_t)bvh4.id.size();
-    ds.bvh4_depth = bvh4.depth;
-    ds.n_entries = (uint32_t)eboxes.size();
-    ds.key_miss = class_key[0];
-    {
-        double ext2 = 0.0;
-        for (int k = 0; k < 3; ++k) {
-            float lo = FLT_MAX, hi = -FLT_MAX;
-            for (const PrimBox& b : eboxes) lo = std::min(lo, b.mn[k]), hi = std::max(hi, b.mx[k]);
-            if (hi > lo) ext2 += ((double)hi - lo) * ((double)hi - lo);
-        }
-        ds.bvh_exact_eps = (float)(std::sqrt(ext2) / 1024.0);
-    }
     const float4* d_pq = nullptr;
-    auto upload_all = [&]() -> int {
+    int rc = carve_region(ctx, ctx->quads_region, false, [&]() -> int {
         int rc;
-        if ((rc = upload(ctx, ph.pq, &d_pq)) || (rc = upload(ctx, srec, &ds.sph_rec)) || (rc = upload(ctx, sclass, &ds.sph_class)) ||
-            (rc = upload(ctx, bvh4.id, &ds.bvh4_id)) || (rc = upload(ctx, bvh4.p[0], &ds.bvh4_p[0])) || (rc = upload(ctx, bvh4.p[1], &ds.bvh4_p[1])) ||
-            (rc = upload(ctx, bvh4.p[2], &ds.bvh4_p[2])) || (rc = upload(ctx, bvh4.p[3], &ds.bvh4_p[3])) ||
-            (rc = upload(ctx, bvh4.p[4], &ds.bvh4_p[4])) || (rc = upload(ctx, bvh4.p[5], &ds.bvh4_p[5]))) return rc;
-        return RT_OK;
-    };
-    // upload() carves the scene region: for this call the quads region stands in for it (measured first), as in rt_set_motion.  A set
-    // that replaces another is written to the other's region after the synchronize above, while the context still names the old arrays:
-    // on a device error it goes back to the static renderer, not to the previous set.
-    const bool had_set = ctx->planar;
-    const DevBuf scene_region = ctx->scene_region;
-    const size_t scene_used = ctx->scene_used;
-    ctx->scene_measuring = true, ctx->scene_measure = 0;
-    (void)upload_all();
-    ctx->scene_measuring = false;
-    int rc = ensure(ctx, ctx->quads_region, ctx->scene_measure + (1u << 20));
-    if (!rc) {
-        ctx->scene_region = ctx->quads_region, ctx->scene_used = 0;
-        rc = upload_all();
-        ctx->scene_region = scene_region, ctx->scene_used = scene_used;
-    }
-    if (rc) {
-        const std::string err = ctx->err;
-        if (had_set) restore_static_search(ctx);
-        ctx->err = err;
+        if ((rc = upload(ctx, ph.pq, &d_pq)) || (rc = upload(ctx, srec, &sr.ds.sph_rec)) || (rc = upload(ctx, sclass, &sr.ds.sph_class))) return rc;
+        return upload_tree(ctx, tree, sr.ds);
+    });
+    if (!rc) rc = configure_search(ctx, sr, n, tree.depth, kp.geo, nullptr); // (no grid for a general scene: nothing is uploaded here)
+    if (rc) { // (a device error, in ctx->err)
+        if (ctx->planar) restore_static_search(ctx);
         return rc;
     }
     restore_static_search(ctx);
-    ctx->ds = ds;
+    ctx->search = sr;
     ctx->gplanar = GenPlanar{d_pq, base, n};
     ctx->planar = true;
     ctx->planar_reach = RT_PLANAR_REACH * ph.world_mag;
-    if ((rc = configure_search(ctx, bvh.depth, kp.geo, nullptr))) { // (no grid for a general scene: nothing is uploaded here)
-        const std::string err = ctx->err;
-        restore_static_search(ctx);
-        ctx->err = err;
-        return rc;
-    }
     return RT_OK;
 }
 
@@ -2405,10 +2364,7 @@ int rt_set_lights(RtCtx* ctx, const RtLights* lights) {
         if (rc) return fail(ctx, rc, "rt_set_lights: " + err);
     }
     for (uint32_t i = 0; i < n; ++i) {
-        const float* u = lights->u + 3 * (size_t)i;
-        const float* v = lights->v + 3 * (size_t)i;
-        const float nx = u[1] * v[2] - u[2] * v[1], ny = u[2] * v[0] - u[0] * v[2], nz = u[0] * v[1] - u[1] * v[0];
-        const float area = std::sqrt((nx * nx + ny * ny) + nz * nz);
+        const float area = ph.len[i];
         if (!std::isfinite(area) || !(area > 0.0f)) return fail(ctx, RT_ERR_INVALID, "rt_set_lights: light " + std::to_string(i) + ": the f32 area overflows or underflows");
         ph.pq[5 * (size_t)i + 3].w = area;
     }
@@ -2478,7 +2434,7 @@ static int debug_bounce_production(RtCtx* ctx, const RtBounceIO* io) {
     if (ctx->planar) hipLaunchKernelGGL(k_set_planar, dim3(1), dim3(64), 0, st, (GenParams*)ctx->genp.p, ctx->gplanar);
     if (ctx->lights) hipLaunchKernelGGL(k_set_lights, dim3(1), dim3(64), 0, st, (GenParams*)ctx->genp.p, ctx->glights);
     hipLaunchKernelGGL(k_debug_fill, dim3((n + 255u) / 256u), dim3(256), 0, st, gp, Q[0], d_o, d_d);
-    const bool use_bvh = ctx->use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
+    const bool use_bvh = ctx->search.use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
     const StepBuffers sb{Q[0], Q[1], wv.qhit, counts, counts + nq, wv.rad,
                          (unsigned long long*)ctx->totals.p, (const GenParams*)ctx->genp.p, false, ctx->motion, ctx->planar, ctx->lights};
     const IntersectParams ip{nq, cap, (int)io->depth, 0u, nq};
@@ -2557,15 +2513,15 @@ int rt_debug_bounce(RtCtx* ctx, const RtBounceIO* io) {
     RT_HIP(ctx, hipMemcpyAsync(base + off_o, io->in_o, 3 * n * 4, hipMemcpyHostToDevice, st));
     RT_HIP(ctx, hipMemcpyAsync(base + off_d, io->in_d, 3 * n * 4, hipMemcpyHostToDevice, st));
     RT_HIP(ctx, hipMemcpyAsync(base + off_key, io->in_key, 2 * n * 4, hipMemcpyHostToDevice, st));
-    const bool use_bvh = ctx->use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
+    const bool use_bvh = ctx->search.use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
     // the search form (the tree out of L2 or staged in LDS as k_intersect has it, or every primitive), then the sets of the context
-    const auto& forms = !use_bvh ? DEBUG_KERNELS_BRUTE : ctx->bvh_in_lds ? DEBUG_KERNELS_TREE_LDS : DEBUG_KERNELS_TREE_L2;
+    const auto& forms = !use_bvh ? DEBUG_KERNELS_BRUTE : ctx->search.bvh_in_lds ? DEBUG_KERNELS_TREE_LDS : DEBUG_KERNELS_TREE_L2;
     const unsigned block = use_bvh ? RT_BVH_BLOCK : 256u;
-    const size_t lds_bytes = use_bvh ? ctx->isect_lds : (size_t)std::min<uint32_t>(std::max<uint32_t>(ctx->ds.n_spheres, 1u), RT_SPHERE_TILE) * sizeof(float4);
+    const size_t lds_bytes = use_bvh ? ctx->search.isect_lds : (size_t)std::min<uint32_t>(std::max<uint32_t>(ctx->search.ds.n_spheres, 1u), RT_SPHERE_TILE) * sizeof(float4);
     const unsigned k = (ctx->motion ? DB_MOTION : 0u) | (ctx->planar ? DB_PLANAR : 0u) | (ctx->lights ? DB_LIGHTS : 0u);
     const DebugKernel fn = forms[k];
     if (!fn) return fail(ctx, RT_ERR_STATE, "rt_debug_bounce: no k_debug_bounce instantiation for " + flags_text(k, DB_NAMES));
-    hipLaunchKernelGGL(fn, dim3((unsigned)((n + block - 1) / block)), dim3(block), lds_bytes, st, ctx->ds, (uint32_t)n, (int)io->depth, base + off_o, base + off_d,
+    hipLaunchKernelGGL(fn, dim3((unsigned)((n + block - 1) / block)), dim3(block), lds_bytes, st, ctx->search.ds, (uint32_t)n, (int)io->depth, base + off_o, base + off_d,
                        (const uint32_t*)(base + off_key), (int*)(base + off_hit), base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd,
                        (uint8_t*)(base + off_alive), DebugSets{ctx->gmotion, ctx->gplanar, ctx->glights});
     RT_HIP(ctx, hipGetLastError());
