@@ -143,6 +143,44 @@ int rt_debug_world_bounds(const RtFlatScene* scene, float* prim_box, float* prim
 int rt_debug_motion_bounds(const RtCtx* ctx, float* entry_box_padded, float* entry_sphere, uint32_t* entry_id, uint32_t entry_cap, uint32_t* n_entries,
                            float grid[6], uint32_t dims[3], uint32_t* cell_begin, uint32_t* cell_id, uint32_t cell_cap, uint32_t* n_cell_ids);
 
+/* -- the launch ledger (test hooks, host code only) -----------------------------------------------------------------
+ * k_shade, k_intersect and k_debug_bounce are families of instantiations over feature flags; a key is the set of its flags, one bit
+ * each (csrc/rt_api.hip "kernel variants").  A ledger holds one bit per key: bit (k & 31) of word k >> 5 for the 256 keys of k_shade
+ * and of k_intersect, bit k of debug_bounce[form] for the 8 keys of each search form of k_debug_bounce, and one bit per closest-hit
+ * kernel that launch_intersect selects outside the tables (RT_UNTABLED_*).  tests/test_variant_matrix.py holds what a context has
+ * launched against what its rows claim, and tests/test_variant_matrix_host.py the union of the claims against the tables. */
+#define RT_LEDGER_WORDS 8
+#define RT_FAMILY_SHADE 0u
+#define RT_FAMILY_INTERSECT 1u
+#define RT_FAMILY_DEBUG_BOUNCE 2u
+#define RT_FAMILY_UNTABLED 3u
+#define RT_FAMILY_DEBUG_FORMS 4u /* rt_debug_variant_flag_names only: the names of the RT_DEBUG_FORM_* in index order */
+#define RT_DEBUG_FORM_TREE_L2 0
+#define RT_DEBUG_FORM_TREE_LDS 1
+#define RT_DEBUG_FORM_BRUTE 2
+#define RT_UNTABLED_GRID_FLAT 1u         /* k_intersect_grid<true>: a grid one cell high */
+#define RT_UNTABLED_GRID 2u              /* k_intersect_grid<false> */
+#define RT_UNTABLED_GRID_MOTION_FLAT 4u  /* k_intersect_grid_motion<true> */
+#define RT_UNTABLED_GRID_MOTION 8u       /* k_intersect_grid_motion<false> */
+#define RT_UNTABLED_LIST 16u             /* k_intersect_list */
+#define RT_UNTABLED_LIST_MOTION 32u      /* k_intersect_list_motion */
+#define RT_UNTABLED_LIST_PLANAR 64u      /* k_intersect_list_planar */
+typedef struct RtVariantLedger {
+    uint32_t shade[8];
+    uint32_t intersect[8];
+    uint32_t debug_bounce[3];
+    uint32_t untabled;
+} RtVariantLedger;
+/* The keys that have a kernel, read from the tables the launch functions index (no context, no GPU). */
+int rt_debug_variant_tables(RtVariantLedger* exists);
+/* The names of a family's flags in bit order, separated by blanks (RT_FAMILY_UNTABLED: the kernels of the RT_UNTABLED_* bits, RT_FAMILY_DEBUG_FORMS:
+ * the search forms that index RtVariantLedger.debug_bounce).  Writes at
+ * most cap bytes (NUL-terminated) and returns the size needed, or a negative RT_ERR_*. */
+int rt_debug_variant_flag_names(uint32_t family, char* buf, uint32_t cap);
+/* The keys `ctx` has launched since the last reset (launch_shade, launch_intersect, the table lookup of rt_debug_bounce); reset != 0
+ * clears them after reading.  `launched` may be NULL. */
+int rt_debug_launched_variants(RtCtx* ctx, RtVariantLedger* launched, int reset);
+
 #ifdef RT_PROFILE_LANES
 /* Diagnostic builds only (-DRT_PROFILE_LANES; absent from the product library): the lane-occupancy counters of
  * csrc/rt_kernels.h, optionally reset after reading. */

@@ -150,6 +150,15 @@ class RtSceneInfo(C.Structure):
         return d
 
 
+class RtVariantLedger(C.Structure):
+    """rt_debug_variant_tables / rt_debug_launched_variants: one bit per key of a kernel family (bit k & 31 of word k >> 5), one word per
+    search form of k_debug_bounce, one bit per closest-hit kernel outside the tables."""
+    _fields_ = [("shade", C.c_uint32 * 8), ("intersect", C.c_uint32 * 8), ("debug_bounce", C.c_uint32 * 3), ("untabled", C.c_uint32)]
+
+
+# RT_FAMILY_* of rt_debug_variant_flag_names (tests/test_abi.py holds them against the header); every NAME comes from the library
+FAMILY_SHADE, FAMILY_INTERSECT, FAMILY_DEBUG_BOUNCE, FAMILY_UNTABLED, FAMILY_DEBUG_FORMS = range(5)
+
 EXPECTED_ABI = 11  # RT_ABI_VERSION the struct layouts and prototypes below were written for
 GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy", "rt_last_error", "rt_scene_upload",
                "rt_shard_rows", "rt_shard_row_to_image_row", "rt_prepare", "rt_render", "rt_render_device", "rt_debug_bounce", "rt_debug_arithmetic",
@@ -158,7 +167,8 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_multi_last_error", "rt_multi_scene_upload", "rt_multi_render", "rt_deinterleave_bands", "rt_set_lens", "rt_multi_set_lens",
                "rt_set_motion", "rt_multi_set_motion", "rt_debug_motion_bounds",
                "rt_set_quads", "rt_multi_set_quads", "rt_debug_planar_info", "rt_debug_planar_bounds",
-               "rt_set_lights", "rt_multi_set_lights"]
+               "rt_set_lights", "rt_multi_set_lights",
+               "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
                 "rth_sphere", "rth_rect", "rth_gbox", "rth_translate", "rth_rotate_y", "rth_constant_medium", "rth_hitable_bbox", "rth_set_sky", "rth_set_camera", "rth_scene_finish", "rth_scene_flat",
@@ -240,6 +250,12 @@ def load_gpu_library():
     lib.rt_debug_planar_info.restype = C.c_int
     lib.rt_debug_planar_bounds.argtypes = [C.POINTER(RtQuads), C.c_float, vp, vp]
     lib.rt_debug_planar_bounds.restype = C.c_int
+    lib.rt_debug_variant_tables.argtypes = [C.POINTER(RtVariantLedger)]
+    lib.rt_debug_variant_tables.restype = C.c_int
+    lib.rt_debug_variant_flag_names.argtypes = [C.c_uint32, C.c_char_p, C.c_uint32]
+    lib.rt_debug_variant_flag_names.restype = C.c_int
+    lib.rt_debug_launched_variants.argtypes = [vp, C.POINTER(RtVariantLedger), C.c_int]
+    lib.rt_debug_launched_variants.restype = C.c_int
     lib.rt_host_alloc.argtypes = [C.c_size_t]
     lib.rt_host_alloc.restype = vp
     lib.rt_host_free.argtypes = [vp]

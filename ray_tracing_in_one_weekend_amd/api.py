@@ -385,6 +385,44 @@ def world_bounds(scene):
     return out
 
 
+def variant_flag_names(family):
+    """rt_debug_variant_flag_names: the flag names of a kernel family (_ffi.FAMILY_*) in bit order, read from the library."""
+    lib = _ffi.load_gpu_library()
+    buf = C.create_string_buffer(512)
+    n = lib.rt_debug_variant_flag_names(family, buf, len(buf))
+    if n < 0 or n > len(buf):
+        raise RtError(f"rt_debug_variant_flag_names({family}) failed ({n})")
+    return tuple(buf.value.decode().split())
+
+
+def _ledger_sets(ledger):
+    """An RtVariantLedger as {"shade": {flag-name tuples}, "intersect": {..}, "debug_bounce": {(form, flag names..)}, "untabled": {kernel
+    names}}; a key without flags is the empty tuple.  The bits are named by the library (variant_flag_names)."""
+    def keys(words, names):
+        out = set()
+        for k in range(32 * len(words)):
+            if words[k >> 5] >> (k & 31) & 1:
+                out.add(tuple(n for b, n in enumerate(names) if k >> b & 1))
+        return out
+    db = variant_flag_names(_ffi.FAMILY_DEBUG_BOUNCE)
+    return {"shade": keys(ledger.shade, variant_flag_names(_ffi.FAMILY_SHADE)),
+            "intersect": keys(ledger.intersect, variant_flag_names(_ffi.FAMILY_INTERSECT)),
+            "debug_bounce": {(form,) + k for f, form in enumerate(variant_flag_names(_ffi.FAMILY_DEBUG_FORMS)) for k in keys([ledger.debug_bounce[f]], db)},
+            "untabled": {n for b, n in enumerate(variant_flag_names(_ffi.FAMILY_UNTABLED)) if ledger.untabled >> b & 1}}
+
+
+def variant_tables():
+    """rt_debug_variant_tables (host code, no GPU): the keys of k_shade, k_intersect and k_debug_bounce that have a kernel, as sets of
+    flag-name tuples such as ("GEN", "RECTS", "NEST", "LIGHTS") (k_debug_bounce: the search form first), and the names of the closest-hit
+    kernels outside the tables."""
+    lib = _ffi.load_gpu_library()
+    led = _ffi.RtVariantLedger()
+    rc = lib.rt_debug_variant_tables(C.byref(led))
+    if rc != 0:
+        raise RtError(f"rt_debug_variant_tables failed ({rc})")
+    return _ledger_sets(led)
+
+
 def make_params(nx, ny, spp, max_depth=50, seed=95, shard_band=0, shard_count=1, shard_id=0, spp_slice=0, flags=0):
     p = RtParams()
     p.flags = flags
@@ -455,6 +493,15 @@ class Renderer:
             self._raise("rt_debug_planar_info", rc)
         d["n_planar"], d["plane_data_in_lds"] = n.value, lds.value  # (rt_set_quads: the count, and LDS or L2 for the plane data)
         return d
+
+    def launched_variants(self, reset=False):
+        """rt_debug_launched_variants: the kernel instantiations this context has launched since the last reset, in the form of
+        variant_tables()."""
+        led = _ffi.RtVariantLedger()
+        rc = self._lib.rt_debug_launched_variants(self._ctx, C.byref(led), 1 if reset else 0)
+        if rc != 0:
+            self._raise("rt_debug_launched_variants", rc)
+        return _ledger_sets(led)
 
     def shard_rows(self, params):
         return self._lib.rt_shard_rows(params.ny, params.shard_band or 1, params.shard_count, params.shard_id)

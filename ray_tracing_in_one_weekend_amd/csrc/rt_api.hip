@@ -86,6 +86,7 @@ struct RtCtx {
     } search, static_search;
     bool nest = false;         // k_intersect<.., NEST>: a wrapper chain deeper than RT_MAX_CHAIN, more than 32 media or a wrapper around a medium (rt_device.h)
     uint32_t opt[RT_OPT__COUNT] = {}; // rt_debug_set_option: per context, every setting renders the same bits
+    RtVariantLedger launched{};       // rt_debug_launched_variants: the table entries launch_* and rt_debug_bounce have launched (one thread drives a context)
     // Page-locked word for the one host decision inside a frame: how many pixels have more primary-ray candidates than a list
     // holds (k_primary_lists counts them; render_impl reads the count back 0.1 ms into the frame).
     uint32_t* h_overflow = nullptr;
@@ -418,7 +419,9 @@ bool scene_perlin_lds(const RtCtx* ctx) { return ctx->search.ds.n_perlin > 0 && 
 // k_shade, k_intersect and k_debug_bounce are families of instantiations over feature flags.  A family's key is the set of its flags (one
 // named bit each), `*_variant_exists` is the one rule that says which keys are instantiated — the single place a new flag is declared —
 // and the table, built from the rule at compile time, maps every key to its kernel (nullptr: there is none).  launch_* look a key up,
-// rt_ctx_create walks the same tables for the LDS attribute: no kernel can be launched that was not registered.
+// rt_ctx_create walks the same tables for the LDS attribute: no kernel can be launched that was not registered, and every registered
+// kernel is launched and checked by tests/test_variant_matrix.py — launch_* note each key in the context's ledger
+// (rt_debug_launched_variants), and the rows of tests/variant_matrix.py must claim exactly the keys of the tables.
 constexpr bool has(unsigned key, unsigned flag) { return (key & flag) != 0u; }
 template <class Table>
 constexpr size_t n_variants(const Table& table) {
@@ -491,11 +494,19 @@ constexpr auto DEBUG_KERNELS_TREE_L2 = debug_variants<RT_BVH_BLOCK, true, false>
 constexpr auto DEBUG_KERNELS_TREE_LDS = debug_variants<RT_BVH_BLOCK, true, true>(std::make_index_sequence<DB_KEYS>{});
 constexpr auto DEBUG_KERNELS_BRUTE = debug_variants<256, false, true>(std::make_index_sequence<DB_KEYS>{});
 static_assert(n_variants(DEBUG_KERNELS_TREE_L2) + n_variants(DEBUG_KERNELS_TREE_LDS) + n_variants(DEBUG_KERNELS_BRUTE) == 15, "k_debug_bounce");
+static_assert(SH_KEYS == 32u * RT_LEDGER_WORDS && IS_KEYS == 32u * RT_LEDGER_WORDS && DB_KEYS <= 32u, "RtVariantLedger holds one bit per key");
+// the closest-hit kernels launch_intersect selects outside the tables (RT_UNTABLED_*), in bit order
+const char* const UNTABLED_NAMES[] = {"k_intersect_grid<true>", "k_intersect_grid<false>", "k_intersect_grid_motion<true>", "k_intersect_grid_motion<false>",
+                                      "k_intersect_list", "k_intersect_list_motion", "k_intersect_list_planar"};
+const char* const DEBUG_FORM_NAMES[] = {"TREE_L2", "TREE_LDS", "BRUTE"}; // RT_DEBUG_FORM_*: the search forms of k_debug_bounce, in index order
+void note(uint32_t* words, unsigned key) { words[key >> 5] |= 1u << (key & 31u); }
 
 // closest hit of the shards [ip.q0, ip.q1): the tree instantiation that matches the scene, or the grid / list walk
 int launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32_t grid, const StepBuffers& b, const IntersectParams& ip) {
     if (use_bvh && !gen && grid_enabled(ctx)) { // sphere-only scene, depth >= 1: the grid walk (rt_grid.h), same hit records
         const size_t mlds = ctx->search.grid_lds + ctx->search.motion_lds;
+        ctx->launched.untabled |= b.motion ? (ctx->search.grid.ny == 1u ? RT_UNTABLED_GRID_MOTION_FLAT : RT_UNTABLED_GRID_MOTION)
+                                           : (ctx->search.grid.ny == 1u ? RT_UNTABLED_GRID_FLAT : RT_UNTABLED_GRID);
         if (b.motion && ctx->search.grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid_motion<true>, dim3(grid), dim3(RT_BVH_BLOCK), mlds, sg, ctx->search.grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
         else if (b.motion) hipLaunchKernelGGL(k_intersect_grid_motion<false>, dim3(grid), dim3(RT_BVH_BLOCK), mlds, sg, ctx->search.grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
         else if (ctx->search.grid.ny == 1u) hipLaunchKernelGGL(k_intersect_grid<true>, dim3(grid), dim3(RT_BVH_BLOCK), ctx->search.grid_lds, sg, ctx->search.grid, b.qi.a, b.qi.b, b.qhit, b.cin, ip);
@@ -504,6 +515,7 @@ int launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32_
     }
     if (!use_bvh) { // no tree (or RT_FLAG_BRUTE_FORCE): every primitive, one workgroup per shard
         const size_t list_lds = (size_t)std::min<uint32_t>(std::max<uint32_t>(ctx->search.ds.n_spheres, 1u), RT_SPHERE_TILE) * sizeof(float4);
+        ctx->launched.untabled |= b.planar ? RT_UNTABLED_LIST_PLANAR : b.motion ? RT_UNTABLED_LIST_MOTION : RT_UNTABLED_LIST;
         if (b.planar) hipLaunchKernelGGL(k_intersect_list_planar, dim3(ip.q1 - ip.q0), dim3(256), 0, sg, ctx->search.ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
         else if (b.motion) hipLaunchKernelGGL(k_intersect_list_motion, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->search.ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
         else hipLaunchKernelGGL(k_intersect_list, dim3(ip.q1 - ip.q0), dim3(256), list_lds, sg, ctx->search.ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
@@ -522,6 +534,7 @@ int launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32_
     if (b.planar) k |= IS_PLANAR;                                       // planar primitives (rt_set_quads)
     const IsectKernel fn = ISECT_KERNELS[k];
     if (!fn) return fail(ctx, RT_ERR_STATE, "launch_intersect: no k_intersect instantiation for " + flags_text(k, IS_NAMES));
+    note(ctx->launched.intersect, k);
     hipLaunchKernelGGL(fn, dim3(grid), dim3(RT_BVH_BLOCK), ctx->search.isect_lds, sg, ctx->search.ds, b.qi.a, b.qi.b, b.qhit, b.cin, ip, b.gpd);
     return RT_OK;
 }
@@ -543,6 +556,7 @@ int launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32_
     if (b.lights) k |= SH_LIGHTS;                                    // a light set (rt_set_lights)
     const ShadeKernel fn = SHADE_KERNELS[k];
     if (!fn) return fail(ctx, RT_ERR_STATE, "launch_shade: no k_shade instantiation for " + flags_text(k, SH_NAMES));
+    note(ctx->launched.shade, k);
     hipLaunchKernelGGL(fn, dim3(n_shards), dim3(256), shade_lds, sg, ctx->search.ds, b.qi, b.qhit, b.qo, b.cin, b.cout, b.rad, sp, b.totals, b.gpd);
     return RT_OK;
 }
@@ -2395,6 +2409,49 @@ int rt_get_depth_timings(RtCtx* ctx, uint32_t max_n, float* isect_ms, float* sha
     return n;
 }
 
+// ---- the launch ledger (test hooks, host code only) ---------------------------------------------------------------------------------
+int rt_debug_variant_tables(RtVariantLedger* exists) {
+    if (!exists) return RT_ERR_INVALID;
+    *exists = RtVariantLedger{};
+    for (unsigned k = 0; k < SH_KEYS; ++k)
+        if (SHADE_KERNELS[k]) note(exists->shade, k);
+    for (unsigned k = 0; k < IS_KEYS; ++k)
+        if (ISECT_KERNELS[k]) note(exists->intersect, k);
+    for (unsigned k = 0; k < DB_KEYS; ++k) {
+        if (DEBUG_KERNELS_TREE_L2[k]) exists->debug_bounce[RT_DEBUG_FORM_TREE_L2] |= 1u << k;
+        if (DEBUG_KERNELS_TREE_LDS[k]) exists->debug_bounce[RT_DEBUG_FORM_TREE_LDS] |= 1u << k;
+        if (DEBUG_KERNELS_BRUTE[k]) exists->debug_bounce[RT_DEBUG_FORM_BRUTE] |= 1u << k;
+    }
+    exists->untabled = (1u << (sizeof(UNTABLED_NAMES) / sizeof(UNTABLED_NAMES[0]))) - 1u;
+    return RT_OK;
+}
+
+int rt_debug_variant_flag_names(uint32_t family, char* buf, uint32_t cap) {
+    std::string t;
+    auto join = [&t](auto& names) {
+        for (const char* n : names) t += (t.empty() ? "" : " ") + std::string(n);
+    };
+    if (family == RT_FAMILY_SHADE) join(SH_NAMES);
+    else if (family == RT_FAMILY_INTERSECT) join(IS_NAMES);
+    else if (family == RT_FAMILY_DEBUG_BOUNCE) join(DB_NAMES);
+    else if (family == RT_FAMILY_UNTABLED) join(UNTABLED_NAMES);
+    else if (family == RT_FAMILY_DEBUG_FORMS) join(DEBUG_FORM_NAMES);
+    else return RT_ERR_INVALID;
+    if (buf && cap) {
+        const size_t n = std::min<size_t>(t.size(), cap - 1u);
+        std::memcpy(buf, t.data(), n);
+        buf[n] = 0;
+    }
+    return (int)t.size() + 1;
+}
+
+int rt_debug_launched_variants(RtCtx* ctx, RtVariantLedger* launched, int reset) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (launched) *launched = ctx->launched;
+    if (reset) ctx->launched = RtVariantLedger{};
+    return RT_OK;
+}
+
 // rt_debug_bounce with RT_FLAG_PRODUCTION_KERNELS: the rays go through the queue and the kernels rt_render launches for a
 // depth >= 1 (the scene's k_intersect instantiation, then the class-sorting k_shade), and the per-ray outcome is read
 // back from the queues: hit records by queue position, radiance slots of the finished paths, survivors by slot.
@@ -2521,6 +2578,7 @@ int rt_debug_bounce(RtCtx* ctx, const RtBounceIO* io) {
     const unsigned k = (ctx->motion ? DB_MOTION : 0u) | (ctx->planar ? DB_PLANAR : 0u) | (ctx->lights ? DB_LIGHTS : 0u);
     const DebugKernel fn = forms[k];
     if (!fn) return fail(ctx, RT_ERR_STATE, "rt_debug_bounce: no k_debug_bounce instantiation for " + flags_text(k, DB_NAMES));
+    ctx->launched.debug_bounce[!use_bvh ? RT_DEBUG_FORM_BRUTE : ctx->search.bvh_in_lds ? RT_DEBUG_FORM_TREE_LDS : RT_DEBUG_FORM_TREE_L2] |= 1u << k;
     hipLaunchKernelGGL(fn, dim3((unsigned)((n + block - 1) / block)), dim3(block), lds_bytes, st, ctx->search.ds, (uint32_t)n, (int)io->depth, base + off_o, base + off_d,
                        (const uint32_t*)(base + off_key), (int*)(base + off_hit), base + off_t, base + off_rad, base + off_att, base + off_so, base + off_sd,
                        (uint8_t*)(base + off_alive), DebugSets{ctx->gmotion, ctx->gplanar, ctx->glights});

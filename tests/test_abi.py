@@ -49,15 +49,17 @@ def test_host_library_exports_every_declared_symbol(rt):
 
 def test_struct_layouts_match_the_c_compiler(rt, tmp_path):
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "rtow_mi355x_debug.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n",'
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "rtow_mi355x_debug.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
                    'sizeof(RtFlatScene),sizeof(RtCamera),sizeof(RtParams),sizeof(RtStats),sizeof(RtBounceIO),'
-                   'offsetof(RtFlatScene,sky_type),offsetof(RtStats,rays_per_depth),offsetof(RtParams,seed));return 0;}\n')
+                   'offsetof(RtFlatScene,sky_type),offsetof(RtStats,rays_per_depth),offsetof(RtParams,seed),'
+                   'sizeof(RtVariantLedger),offsetof(RtVariantLedger,debug_bounce),offsetof(RtVariantLedger,untabled));return 0;}\n')
     exe = tmp_path / "sz"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     got = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
     f = rt._ffi
     want = [C.sizeof(f.RtFlatScene), C.sizeof(f.RtCamera), C.sizeof(f.RtParams), C.sizeof(f.RtStats), C.sizeof(f.RtBounceIO),
-            f.RtFlatScene.sky_type.offset, f.RtStats.rays_per_depth.offset, f.RtParams.seed.offset]
+            f.RtFlatScene.sky_type.offset, f.RtStats.rays_per_depth.offset, f.RtParams.seed.offset,
+            C.sizeof(f.RtVariantLedger), f.RtVariantLedger.debug_bounce.offset, f.RtVariantLedger.untabled.offset]
     assert got == want
 
 
@@ -189,6 +191,19 @@ def test_c_host_example_needs_only_the_product_headers(tmp_path):
         (inc / h).write_text(open(os.path.join(ROOT, "include", h)).read())
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", str(inc), "-c", os.path.join(ROOT, "examples", "host_main.c"),
                     "-o", str(tmp_path / "host_main.o")], check=True)
+
+
+def test_ledger_families_match_the_header(rt):
+    """_ffi.FAMILY_* are the header's RT_FAMILY_*; the names behind them (flags, search forms, untabled kernels) come from the library."""
+    src = open(os.path.join(ROOT, "include", DEBUG_HEADER)).read()
+    fams = {n: int(v) for n, v in re.findall(r"#define RT_FAMILY_(\w+) (\d+)u", src)}
+    f = rt._ffi
+    assert fams == {"SHADE": f.FAMILY_SHADE, "INTERSECT": f.FAMILY_INTERSECT, "DEBUG_BOUNCE": f.FAMILY_DEBUG_BOUNCE, "UNTABLED": f.FAMILY_UNTABLED,
+                    "DEBUG_FORMS": f.FAMILY_DEBUG_FORMS}
+    forms = {n: int(v) for n, v in re.findall(r"#define RT_DEBUG_FORM_(\w+) (\d+)", src)}
+    assert rt.variant_flag_names(f.FAMILY_DEBUG_FORMS) == tuple(sorted(forms, key=forms.get)) and len(forms) == 3
+    untabled = {n: int(v) for n, v in re.findall(r"#define RT_UNTABLED_(\w+) (\d+)u", src)}
+    assert sorted(untabled.values()) == [1 << b for b in range(len(rt.variant_flag_names(f.FAMILY_UNTABLED)))]
 
 
 def test_shard_helpers_need_no_gpu(rt):
