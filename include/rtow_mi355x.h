@@ -443,6 +443,62 @@ typedef struct RtLights {
  * stays.  The arrays are copied. */
 int rt_set_lights(RtCtx* ctx, const RtLights* lights);
 
+/* -- progressive accumulation, a per-pixel error estimate and a noise target ----------------------------------------
+ * rt_render traces a fixed spp and drops its running sums.  An ACCUMULATION keeps them: samples are added in any portions, the frame so
+ * far can be read at any time, and with it a measure of its noise.  Path keys are a function of (seed, pixel, sample) and a pixel's
+ * samples are summed in sample order, so after rt_accum_begin(first_sample 0) and adds of n1 + n2 + ... = n samples the images are, bit
+ * for bit, those of rt_render with spp = n, however the adds and their slices are cut.
+ * Moments, per pixel and per sample (r, g, b) — the f32 values the sum reads — every operation one IEEE f64 operation, no FMA:
+ *   Y = ((0.2126 (double)r + 0.7152 (double)g) + 0.0722 (double)b);   S1 += Y;   S2 += Y * Y   in sample order, across slices and adds.
+ * With n = samples done:  Ybar = S1 / n;  V = max(0, (S2 - S1 * S1 / n) / (n - 1)) / n, the variance of the mean (V = 0 where n < 2);
+ * out_sem = (float)sqrt(V), the standard error of the pixel's mean luminance.  A non-finite sample propagates as IEEE arithmetic has it
+ * (its pixel's sem, and with it the frame figures, become NaN); max(0, x) keeps a NaN.
+ * Frame figures, in f64, over the npix pixels of the shard:  mean_luminance = (sum_p Ybar_p) / npix;  rms_sem = sqrt((sum_p V_p) / npix);
+ * noise = rms_sem / mean_luminance — where mean_luminance == 0: 0 when rms_sem == 0, +inf otherwise — and +inf where n < 2.  The sums
+ * run over a fixed tree (per workgroup, then one workgroup over the partial sums in index order; no floating-point atomics): the same
+ * accumulation read twice gives the same bits.
+ * Cost: 28 B per pixel that the accumulation owns (an f32 x 3 sum, an f64 x 2 moment), apart from the frame renderer's buffers —
+ * rt_render and rt_render_device may be called in between and neither disturbs the other.
+ * Not covered: rt_multi_* (the noise of a frame split over devices needs a reduction across them); the rt_set_progress callback (a
+ * host that accumulates has its preview in rt_accum_read); per-pixel adaptive sampling (primary rays are generated over the whole
+ * lattice of the shard: every add gives every pixel the same number of samples). */
+typedef struct RtNoise {
+    uint32_t spp_done;      /* samples per pixel accumulated so far */
+    uint32_t reserved;
+    double mean_luminance;  /* (sum_p Ybar_p) / npix */
+    double rms_sem;         /* sqrt((sum_p V_p) / npix) */
+    double noise;           /* rms_sem / mean_luminance, see above */
+} RtNoise;
+/* Opens the accumulation of `ctx` (one per context; an open one is dropped) and clears its sums.  Fixes the frame: the camera, nx, ny,
+ * the shard fields, max_depth, seed, flags and spp_slice of `params`, and with them the context's lens, motion, planar primitives and
+ * lights and the pixel order — each of the calls listed below that could change one ends the accumulation.  params->spp (>= 1) is read
+ * only as the expected size of one add, for which the work buffers are requested now (as rt_prepare does); no result depends on it.
+ * first_sample: the sample index the first added sample gets.  0 starts the frame rt_render renders; another value lets two contexts
+ * or processes take disjoint sample windows of one frame.  RT_ERR_STATE without an uploaded scene. */
+int rt_accum_begin(RtCtx* ctx, const RtCamera* cam, const RtParams* params, uint32_t first_sample);
+/* Traces samples [first_sample + done, first_sample + done + n_samples) of every pixel of the shard, with the kernels and the slices
+ * of rt_render, and adds them to the running sums in sample order.  `stats` (may be NULL; it forces a synchronisation, as in
+ * rt_render_device) is what rt_render would report for these samples.  RT_ERR_INVALID: n_samples 0, or first_sample plus everything
+ * added would pass 2^32 - 1, the bound of RtParams.spp — nothing has changed then.  RT_ERR_STATE: no open accumulation. */
+int rt_accum_add(RtCtx* ctx, uint32_t n_samples, RtStats* stats);
+/* The frame so far; any number of times, each pointer may be NULL.  out_rgb_f32 and out_rgb8 are exactly what rt_render writes (sum /
+ * (float)done, gamma 2, the flip); out_sem is [rows_local*nx] f32 in the row order of out_rgb_f32.  Before the first add the images are
+ * zeros, spp_done is 0, mean_luminance and rms_sem are 0 and noise is +inf.  Synchronises the context's stream once. */
+int rt_accum_read(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_sem, RtNoise* noise);
+/* Ends the accumulation (RT_OK also when none is open); its buffers are kept for the next.  An accumulation is also ended by
+ * rt_ctx_destroy, rt_scene_upload, every successful rt_set_lens / rt_set_motion / rt_set_quads / rt_set_lights (and one that fails on
+ * the device) and rt_debug_set_option: the next rt_accum_add or rt_accum_read is RT_ERR_STATE.  rt_render and rt_render_device do not
+ * end it. */
+int rt_accum_end(RtCtx* ctx);
+/* Renders to a quality instead of a count: rt_accum_begin(first_sample 0), then adds of min(spp_step, what is left of params->spp)
+ * samples until noise <= target_noise or params->spp samples, the maximum, are done; the outputs as rt_accum_read writes them, `stats`
+ * summed over the adds (its times too); the accumulation is ended.  The image is, bit for bit, rt_render with spp = noise->spp_done.
+ * After each add the host reads the 24 B of frame figures to decide: one stream synchronisation per step, the price of the decision —
+ * choose spp_step so that a step is long against it (DESIGN.md "Accumulation and noise").  RT_ERR_STATE: an accumulation is open.
+ * RT_ERR_INVALID: spp_step 0, target_noise NaN or negative, params->spp < 2. */
+int rt_render_to_noise(RtCtx* ctx, const RtCamera* cam, const RtParams* params, double target_noise, uint32_t spp_step,
+                       float* out_rgb_f32, uint8_t* out_rgb8, float* out_sem, RtNoise* noise, RtStats* stats);
+
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the
  * world shared read-only (main.rs:72-108); here the scene is replicated on every device, device r renders the image

@@ -118,6 +118,12 @@ class RtStats(C.Structure):
         return d
 
 
+class RtNoise(C.Structure):
+    """rt_accum_read / rt_render_to_noise: the frame figures of an accumulation (rtow_mi355x.h "progressive accumulation")."""
+    _fields_ = [("spp_done", C.c_uint32), ("reserved", C.c_uint32), ("mean_luminance", C.c_double), ("rms_sem", C.c_double),
+                ("noise", C.c_double)]
+
+
 class RtBounceIO(C.Structure):
     _fields_ = [("n", C.c_uint32), ("depth", C.c_uint32), ("in_o", _f), ("in_d", _f), ("in_key", _u32),
                 ("out_hit", C.POINTER(C.c_int32)), ("out_t", _f), ("out_radiance", _f), ("out_attenuation", _f),
@@ -168,6 +174,7 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_set_motion", "rt_multi_set_motion", "rt_debug_motion_bounds",
                "rt_set_quads", "rt_multi_set_quads", "rt_debug_planar_info", "rt_debug_planar_bounds",
                "rt_set_lights", "rt_multi_set_lights",
+               "rt_accum_begin", "rt_accum_add", "rt_accum_read", "rt_accum_end", "rt_render_to_noise",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
@@ -246,6 +253,17 @@ def load_gpu_library():
     lib.rt_set_lights.restype = C.c_int
     lib.rt_multi_set_lights.argtypes = [vp, C.POINTER(RtLights)]
     lib.rt_multi_set_lights.restype = C.c_int
+    lib.rt_accum_begin.argtypes = [vp, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_uint32]
+    lib.rt_accum_begin.restype = C.c_int
+    lib.rt_accum_add.argtypes = [vp, C.c_uint32, C.POINTER(RtStats)]
+    lib.rt_accum_add.restype = C.c_int
+    lib.rt_accum_read.argtypes = [vp, _f, _u8, _f, C.POINTER(RtNoise)]
+    lib.rt_accum_read.restype = C.c_int
+    lib.rt_accum_end.argtypes = [vp]
+    lib.rt_accum_end.restype = C.c_int
+    lib.rt_render_to_noise.argtypes = [vp, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_double, C.c_uint32, _f, _u8, _f, C.POINTER(RtNoise),
+                                       C.POINTER(RtStats)]
+    lib.rt_render_to_noise.restype = C.c_int
     lib.rt_debug_planar_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.rt_debug_planar_info.restype = C.c_int
     lib.rt_debug_planar_bounds.argtypes = [C.POINTER(RtQuads), C.c_float, vp, vp]

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import RtBounceIO, RtCamera, RtFlatScene, RtLens, RtLights, RtMotion, RtParams, RtQuads, RtStats
+from ._ffi import RtBounceIO, RtCamera, RtFlatScene, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtStats
 
 
 class RtError(RuntimeError):
@@ -542,6 +542,58 @@ class Renderer:
         if rc != 0:
             self._raise("rt_render", rc)
         return img, rgb8, stats
+
+    def accum_begin(self, camera, params, first_sample=0):
+        """rt_accum_begin: opens the accumulation of this context for the frame of `params` (params.spp: the expected size of one add)
+        and clears its sums; the first added sample gets the index first_sample."""
+        rc = self._lib.rt_accum_begin(self._ctx, C.byref(camera), C.byref(params), int(first_sample))
+        if rc != 0:
+            self._raise("rt_accum_begin", rc)
+        self._accum_shape = (self.shard_rows(params), params.nx)
+
+    def accum_add(self, n):
+        """rt_accum_add: n more samples per pixel onto the running sums; returns the RtStats of these samples."""
+        stats = RtStats()
+        rc = self._lib.rt_accum_add(self._ctx, int(n), C.byref(stats))
+        if rc != 0:
+            self._raise("rt_accum_add", rc)
+        return stats
+
+    def _accum_outputs(self, want_rgb8, want_sem):
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        img = np.zeros((rows, nx, 3), dtype=np.float32)
+        rgb8 = np.zeros((rows, nx, 3), dtype=np.uint8) if want_rgb8 else None
+        sem = np.zeros((rows, nx), dtype=np.float32) if want_sem else None
+        return img, rgb8, sem, (img.ctypes.data_as(C.POINTER(C.c_float)), rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgb8 else None,
+                                sem.ctypes.data_as(C.POINTER(C.c_float)) if want_sem else None)
+
+    def accum_read(self, want_rgb8=False, want_sem=False):
+        """rt_accum_read: (f32 image [rows, nx, 3] as render() returns it, rgb8 or None, sem [rows, nx] f32 or None — the standard error
+        of each pixel's mean luminance —, RtNoise) of the samples accumulated so far."""
+        img, rgb8, sem, ptrs = self._accum_outputs(want_rgb8, want_sem)
+        noise = RtNoise()
+        rc = self._lib.rt_accum_read(self._ctx, *ptrs, C.byref(noise))
+        if rc != 0:
+            self._raise("rt_accum_read", rc)
+        return img, rgb8, sem, noise
+
+    def accum_end(self):
+        """rt_accum_end: ends the accumulation (no error when none is open)."""
+        rc = self._lib.rt_accum_end(self._ctx)
+        if rc != 0:
+            self._raise("rt_accum_end", rc)
+
+    def render_to_noise(self, camera, params, target, step, want_rgb8=False, want_sem=False):
+        """rt_render_to_noise: samples in steps of `step` until RtNoise.noise <= target or params.spp, the maximum, are done.  Returns
+        (img, rgb8 or None, sem or None, RtNoise, RtStats summed over the steps); img is render() with spp = RtNoise.spp_done, bit for bit."""
+        self._accum_shape = (self.shard_rows(params), params.nx)
+        img, rgb8, sem, ptrs = self._accum_outputs(want_rgb8, want_sem)
+        noise, stats = RtNoise(), RtStats()
+        rc = self._lib.rt_render_to_noise(self._ctx, C.byref(camera), C.byref(params), float(target), int(step), *ptrs, C.byref(noise),
+                                          C.byref(stats))
+        if rc != 0:
+            self._raise("rt_render_to_noise", rc)
+        return img, rgb8, sem, noise, stats
 
     def set_progress(self, fn):
         """fn(spp_done, spp_total, rgb8[rows, nx, 3]) after every slice but the last of a following render()

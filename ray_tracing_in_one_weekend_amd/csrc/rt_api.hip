@@ -131,6 +131,18 @@ struct RtCtx {
     bool progress_armed = false; // set by rt_render around render_impl, so rt_render_device stays callback-free
     DevBuf preview_u8;
     std::vector<uint8_t> preview_host;
+    // rt_accum_*: at most one open accumulation per context.  It owns its running state — an f32 x 3 sum and an f64 x 2 luminance moment per
+    // pixel, 28 B, in the local pixel order fixed at rt_accum_begin — so that `acc` stays the frame renderer's and rt_render may run in
+    // between.  The work buffers, counters and candidate lists are the frame renderer's: every add sets them up again, as a frame does.
+    struct Accum {
+        bool open = false;
+        RtCamera cam{};
+        RtParams prm{};
+        uint32_t first = 0, done = 0; // the next sample to trace is first + done
+        uint32_t nx = 0, rows = 0, npix = 0, tiles_per_row = 0, tile_pixels = 0;
+    } accum;
+    DevBuf accum_sum, accum_mom, accum_sem, accum_partials; // (accum_sem: staging of out_sem; accum_partials: one f64 pair per workgroup + the 3 frame figures)
+    double* h_noise = nullptr;   // page-locked: mean_luminance, rms_sem, noise as k_noise_final wrote them
     // Host-side timeline of the last render_impl (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
     // render of a process is where allocations, code-object loads and the queue probe happen; this says which.
     std::vector<std::pair<const char*, double>> parts;
@@ -1273,6 +1285,8 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->acc), free_buf(ctx->counts), free_buf(ctx->totals);
     free_buf(ctx->out_f32), free_buf(ctx->out_u8), free_buf(ctx->dbg), free_buf(ctx->genp);
     free_buf(ctx->preview_u8), free_buf(ctx->lists);
+    free_buf(ctx->accum_sum), free_buf(ctx->accum_mom), free_buf(ctx->accum_sem), free_buf(ctx->accum_partials);
+    if (ctx->h_noise) (void)hipHostFree(ctx->h_noise);
     free_buf(ctx->motion_region), free_buf(ctx->quads_region), free_buf(ctx->lights_buf);
     for (auto ev : ctx->events) (void)hipEventDestroy(ev);
     for (auto ev : ctx->depth_events) (void)hipEventDestroy(ev);
@@ -1308,6 +1322,7 @@ uint32_t rt_shard_row_to_image_row(uint32_t local_row, uint32_t shard_band, uint
 int rt_scene_upload(RtCtx* ctx, const RtFlatScene* s) {
     if (!ctx) return RT_ERR_INVALID;
     if (!s) return fail(ctx, RT_ERR_INVALID, "rt_scene_upload: scene is NULL");
+    ctx->accum.open = false; // (an accumulation belongs to a scene)
     RT_HIP(ctx, hipSetDevice(ctx->device));
     PackedScene pk;
     {   // ---- validate, then pack
@@ -1491,10 +1506,39 @@ static int check_params(RtCtx* ctx, const RtCamera* cam, const RtParams* p) {
     return RT_OK;
 }
 
-// h_out_*: host destinations of the two images (rt_render) or NULL; the copies are enqueued behind the last kernel, before the
-// one synchronisation that reads the counters.
-static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, void* d_out_rgb_f32, void* d_out_rgb8,
-                       void* stream_v, RtStats* stats, float* h_out_f32 = nullptr, uint8_t* h_out_u8 = nullptr) {
+// Local pixel order of a shard's frame (rt_kernels.h GenParams): 8 x 8 pixel tiles per wave of depth 0 when the frame allows it.  A strip
+// of 64 x 1 pixels crosses more silhouettes than a block of 8 x 8, and at depth 0 a wave runs the union of what its lanes hit.  Frames are
+// bit-identical (keys and the resolve order are functions of (pixel, sample)).  sphere_scene: depth-0 shading 7.17 -> 6.67 ms
+// per 128 spp, frame 58.6 -> 57.4 ms; pbr_sweep_scene -1.5 %; cornell_box +-0; final_scene +1.7 % (its deeper bounces,
+// 42.0 -> 43.6 ms of k_intersect), so general scenes keep the rows (profiles/round3/ab_tiles.txt).
+static void pixel_order(const RtCtx* ctx, uint32_t nx, uint32_t rows, uint32_t& tiles_per_row, uint32_t& tile_pixels) {
+    const uint32_t po = ctx->opt[RT_OPT_PIXEL_ORDER]; // 1 = rows, 2 = tiles wherever the frame allows
+    const bool want_tiles = po ? po == 2u : !scene_is_general(ctx);
+    tiles_per_row = (nx % 8u == 0u && rows >= 8u && want_tiles) ? nx / 8u : 0u;
+    tile_pixels = tiles_per_row * 64u * (rows / 8u); // the last rows % 8 rows stay row-major
+}
+
+// Where the resolved samples of a call go.  The frame renderer (sum NULL): ctx->acc, cleared first, samples 0 .. spp - 1.  An accumulation
+// (rt_accum_add): its own running sum and luminance moments, kept from call to call, samples first_sample .. first_sample + spp - 1.
+struct SampleSink {
+    float* sum = nullptr;
+    double2* mom = nullptr;
+    uint32_t first_sample = 0;
+};
+// What trace_samples enqueued, for the finalize, the copies and the statistics of its caller.
+struct Traced {
+    hipStream_t st = nullptr;
+    std::chrono::steady_clock::time_point wall0;
+    uint32_t nx = 0, rows = 0, npix = 0, tiles_per_row = 0, tile_pixels = 0;
+    int n_depths = 0;
+    uint32_t n_slices = 0, n_trace_launches = 0;
+    float* acc = nullptr; // the running sum the samples went to
+};
+
+// Traces prm->spp samples of every pixel of the shard in slices, with the production kernels, and resolves them onto `sink` in sample
+// order.  Everything of a frame but its last three steps (k_finalize, the copies to the host, the statistics): rt_render,
+// rt_render_device and rt_accum_add share it.  ctx->ev_begin is recorded; the caller records ctx->ev_end.  npix 0: nothing to do.
+static int trace_samples(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, void* stream_v, const SampleSink& sink, Traced& tr) {
     int rc = check_params(ctx, cam, prm);
     if (rc) return rc;
     if (ctx->planar) { // the leaf slack of the set is derived for ray origins within RT_PLANAR_REACH W: the eye (and its lens) must lie there
@@ -1515,10 +1559,9 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     const uint32_t scount = prm->shard_count <= 1 ? 1u : prm->shard_count;
     const uint32_t rows = rt_shard_rows(ny, band, scount, prm->shard_id);
     const uint64_t npix64 = (uint64_t)rows * nx;
-    if (npix64 == 0) {
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
+    tr = Traced{};
+    tr.st = st, tr.wall0 = wall0;
+    if (npix64 == 0) return RT_OK;
     const uint32_t npix = (uint32_t)npix64;
     const int n_depths = prm->max_depth + 1;
     const uint32_t nq = queue_shards(ctx);
@@ -1535,7 +1578,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
 
     // the small persistent buffers first (they lie at the bottom of the pool); the work buffers of the slices start above them
     ctx->pool.chunk_delay_us.store(ctx->opt[RT_OPT_POOL_CHUNK_DELAY_US]);
-    if ((rc = ensure(ctx, ctx->acc, (size_t)npix * 3 * sizeof(float)))) return rc;
+    if (!sink.sum && (rc = ensure(ctx, ctx->acc, (size_t)npix * 3 * sizeof(float)))) return rc;
     const size_t counts_bytes = (size_t)(n_depths + 1) * nq * sizeof(uint32_t); // queue sizes [depth][shard]
     if ((rc = ensure(ctx, ctx->counts, counts_bytes))) return rc;
     const size_t totals_bytes = (size_t)(n_depths + 2) * sizeof(unsigned long long);
@@ -1543,7 +1586,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_LIGHTS_OFFSET + sizeof(GenLights)))) return rc; // (the lens, the motion, the planar set and the light set behind the params: gen_lens_of, gen_motion_of, gen_planar_of, gen_lights_of)
     if (want_lists &&(rc = ensure(ctx, ctx->lists, ((size_t)npix + 1u) * sizeof(uint4)))) return rc; // + the overflow counter behind the lists
     GenParams* gpd = (GenParams*)ctx->genp.p;
-    float* acc = (float*)ctx->acc.p;
+    float* acc = sink.sum ? sink.sum : (float*)ctx->acc.p;
     uint32_t* counts = (uint32_t*)ctx->counts.p;
     unsigned long long* totals = (unsigned long long*)ctx->totals.p; // [0]=tex fetches [1]=bad dirs [2..]=rays per depth
     SlicePlan plan;
@@ -1557,7 +1600,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     if (nq >= 2u * RT_ISECT_MAX_SHARDS && (rc = ensure_concurrent_chains(ctx, st))) return rc;
     ctx->mark("queue_probe"); // (the first kernel launch of a process: the code object is loaded here)
     RT_HIP(ctx, hipEventRecord(ctx->ev_begin, st));
-    RT_HIP(ctx, hipMemsetAsync(acc, 0, (size_t)npix * 3 * sizeof(float), st));
+    if (!sink.sum) RT_HIP(ctx, hipMemsetAsync(acc, 0, (size_t)npix * 3 * sizeof(float), st));
     RT_HIP(ctx, hipMemsetAsync(totals, 0, totals_bytes, st));
 
     GenParams gp{};
@@ -1579,15 +1622,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     {   // udiv_inv: reciprocals that keep the float quotient at or below the true one
         auto inv = [](uint32_t d) { return (float)((1.0 / (double)d) * (1.0 - 1.0 / 4194304.0)); };
         gp.inv_npix = inv(npix), gp.inv_nx = inv(nx), gp.inv_band = inv(band);
-        // 8 x 8 pixel tiles per wave of depth 0 when the shard's frame allows it (rt_kernels.h GenParams): a strip of 64 x 1 pixels
-        // crosses more silhouettes than a block of 8 x 8, and at depth 0 a wave runs the union of what its lanes hit.  Frames are
-        // bit-identical (keys and the resolve order are functions of (pixel, sample)).  sphere_scene: depth-0 shading 7.17 -> 6.67 ms
-        // per 128 spp, frame 58.6 -> 57.4 ms; pbr_sweep_scene -1.5 %; cornell_box +-0; final_scene +1.7 % (its deeper bounces,
-        // 42.0 -> 43.6 ms of k_intersect), so general scenes keep the rows (profiles/round3/ab_tiles.txt).
-        const uint32_t po = ctx->opt[RT_OPT_PIXEL_ORDER]; // 1 = rows, 2 = tiles wherever the frame allows
-        const bool want_tiles = po ? po == 2u : !scene_is_general(ctx);
-        gp.tiles_per_row = (nx % 8u == 0u && rows >= 8u && want_tiles) ? nx / 8u : 0u;
-        gp.tile_pixels = gp.tiles_per_row * 64u * (rows / 8u); // the last rows % 8 rows stay row-major
+        pixel_order(ctx, nx, rows, gp.tiles_per_row, gp.tile_pixels);
         gp.inv_tpr = gp.tiles_per_row ? inv(gp.tiles_per_row) : 0.0f;
     }
     if (want_lists) {
@@ -1689,7 +1724,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
             ctx->events.push_back(ev);
         }
         ++n_slices;
-        gp.s0 = s0;
+        gp.s0 = sink.first_sample + s0;
         gp.n_rays = npix * sc;
         RT_HIP(ctx, hipMemsetAsync(counts, 0, counts_bytes, st));
         if (ctx->motion) hipLaunchKernelGGL(k_set_motion, dim3(1), dim3(64), 0, st, gpd, ctx->gmotion);
@@ -1747,7 +1782,8 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
                 for (uint32_t k = 0; k < nq; ++k) ctx->timed_rays[(size_t)d] += hc[(size_t)d * nq + k];
         }
         RT_HIP(ctx, hipEventRecord(ctx->events[2 * sl + 1], st));
-        hipLaunchKernelGGL(k_resolve, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, acc, npix, sc);
+        if (sink.mom) hipLaunchKernelGGL(k_resolve_moments, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, acc, sink.mom, npix, sc);
+        else hipLaunchKernelGGL(k_resolve, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, acc, npix, sc);
         hipLaunchKernelGGL(k_accum_counts, dim3((unsigned)n_depths), dim3(256), 0, st, counts, nq, (uint32_t)n_depths, totals + 2);
         if (ctx->progress_armed && ctx->progress_fn && s0 + sc < spp) { // the last slice is the final image itself
             const uint32_t done = s0 + sc;
@@ -1760,8 +1796,62 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
         s0 += sc;
     }
     if (pool_wait_ms > 0.0) ctx->parts.emplace_back("of_which_waiting_for_the_pool", pool_wait_ms);
-    hipLaunchKernelGGL(k_finalize, dim3((npix + 255u) / 256u), dim3(256), 0, st, acc, (float*)d_out_rgb_f32,
-                       (uint8_t*)d_out_rgb8, nx, rows, spp, gp.tiles_per_row, gp.tile_pixels);
+    tr.nx = nx, tr.rows = rows, tr.npix = npix, tr.tiles_per_row = gp.tiles_per_row, tr.tile_pixels = gp.tile_pixels;
+    tr.n_depths = n_depths, tr.n_slices = n_slices, tr.n_trace_launches = n_trace_launches, tr.acc = acc;
+    return RT_OK;
+}
+
+// RtStats of the `spp` samples per pixel that trace_samples enqueued, after waiting for the stream (ctx->ev_end recorded behind them).
+static int read_stats(RtCtx* ctx, const Traced& tr, uint32_t spp, RtStats* stats) {
+    const hipStream_t st = tr.st;
+    const int n_depths = tr.n_depths;
+    const size_t totals_bytes = (size_t)(n_depths + 2) * sizeof(unsigned long long);
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    ctx->mark("wait_for_the_device");
+    std::vector<unsigned long long> h((size_t)n_depths + 2);
+    RT_HIP(ctx, hipMemcpy(h.data(), ctx->totals.p, totals_bytes, hipMemcpyDeviceToHost));
+    std::memset(stats, 0, sizeof(*stats));
+    stats->n_paths = (uint64_t)tr.npix * spp;
+    stats->n_texture_fetches = h[0];
+    stats->n_bad_dir = h[1];
+    for (int d = 0; d < n_depths; ++d) {
+        stats->n_rays += h[(size_t)d + 2];
+        if (d < 64) stats->rays_per_depth[d] = h[(size_t)d + 2];
+    }
+    stats->n_rays_secondary = stats->n_rays - std::min(stats->n_rays, stats->n_paths);
+    float ms = 0.0f;
+    double trace_ms = 0.0;
+    for (uint32_t sl = 0; sl < tr.n_slices; ++sl) {
+        RT_HIP(ctx, hipEventElapsedTime(&ms, ctx->events[2 * sl], ctx->events[2 * sl + 1]));
+        trace_ms += ms;
+    }
+    RT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
+    stats->seconds_trace = trace_ms * 1e-3;
+    stats->seconds_device = ms * 1e-3;
+    stats->bytes_algorithmic = 96ull * stats->n_rays + 24ull * stats->n_paths + 12ull * stats->n_texture_fetches;
+    stats->bytes_trace_algorithmic = 48ull * stats->n_rays + 48ull * stats->n_rays_secondary + 12ull * stats->n_paths +
+                                     12ull * stats->n_texture_fetches;
+    stats->n_trace_launches = tr.n_trace_launches;
+    stats->n_slices = tr.n_slices;
+    stats->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - tr.wall0).count();
+    return RT_OK;
+}
+
+// h_out_*: host destinations of the two images (rt_render) or NULL; the copies are enqueued behind the last kernel, before the
+// one synchronisation that reads the counters.
+static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, void* d_out_rgb_f32, void* d_out_rgb8,
+                       void* stream_v, RtStats* stats, float* h_out_f32 = nullptr, uint8_t* h_out_u8 = nullptr) {
+    Traced tr;
+    const int rc = trace_samples(ctx, cam, prm, stream_v, SampleSink{}, tr);
+    if (rc) return rc;
+    if (tr.npix == 0u) {
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    const hipStream_t st = tr.st;
+    const uint32_t npix = tr.npix;
+    hipLaunchKernelGGL(k_finalize, dim3((npix + 255u) / 256u), dim3(256), 0, st, tr.acc, (float*)d_out_rgb_f32,
+                       (uint8_t*)d_out_rgb8, tr.nx, tr.rows, prm->spp, tr.tiles_per_row, tr.tile_pixels);
     RT_HIP(ctx, hipEventRecord(ctx->ev_end, st));
     RT_HIP(ctx, hipGetLastError());
     ctx->mark("enqueue_all_launches");
@@ -1771,38 +1861,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     if (h_out_f32) RT_HIP(ctx, hipMemcpyAsync(h_out_f32, d_out_rgb_f32, (size_t)npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
     if (h_out_u8) RT_HIP(ctx, hipMemcpyAsync(h_out_u8, d_out_rgb8, (size_t)npix * 3, hipMemcpyDeviceToHost, st));
     if ((h_out_f32 || h_out_u8) && !stats) RT_HIP(ctx, hipStreamSynchronize(st));
-
-    if (stats) {
-        RT_HIP(ctx, hipStreamSynchronize(st));
-        ctx->mark("wait_for_the_device");
-        std::vector<unsigned long long> h((size_t)n_depths + 2);
-        RT_HIP(ctx, hipMemcpy(h.data(), totals, totals_bytes, hipMemcpyDeviceToHost));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n_paths = (uint64_t)npix * spp;
-        stats->n_texture_fetches = h[0];
-        stats->n_bad_dir = h[1];
-        for (int d = 0; d < n_depths; ++d) {
-            stats->n_rays += h[(size_t)d + 2];
-            if (d < 64) stats->rays_per_depth[d] = h[(size_t)d + 2];
-        }
-        stats->n_rays_secondary = stats->n_rays - std::min(stats->n_rays, stats->n_paths);
-        float ms = 0.0f;
-        double trace_ms = 0.0;
-        for (uint32_t sl = 0; sl < n_slices; ++sl) {
-            RT_HIP(ctx, hipEventElapsedTime(&ms, ctx->events[2 * sl], ctx->events[2 * sl + 1]));
-            trace_ms += ms;
-        }
-        RT_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_begin, ctx->ev_end));
-        stats->seconds_trace = trace_ms * 1e-3;
-        stats->seconds_device = ms * 1e-3;
-        stats->bytes_algorithmic = 96ull * stats->n_rays + 24ull * stats->n_paths + 12ull * stats->n_texture_fetches;
-        stats->bytes_trace_algorithmic = 48ull * stats->n_rays + 48ull * stats->n_rays_secondary + 12ull * stats->n_paths +
-                                         12ull * stats->n_texture_fetches;
-        stats->n_trace_launches = n_trace_launches;
-        stats->n_slices = n_slices;
-        stats->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
-    }
-    return RT_OK;
+    return stats ? read_stats(ctx, tr, prm->spp, stats) : RT_OK;
 }
 
 int rt_prepare(RtCtx* ctx, const RtParams* prm) {
@@ -1852,6 +1911,164 @@ int rt_render(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, float* out_r
     return rc;
 }
 
+// ---- accumulation and noise (rtow_mi355x.h "Progressive accumulation") ------------------------------------------------------------
+// The frame figures of the open accumulation: two kernels and a 24 B copy into ctx->h_noise, valid after the next wait for `st`.
+static int enqueue_noise(RtCtx* ctx, hipStream_t st) {
+    const RtCtx::Accum& a = ctx->accum;
+    const uint32_t nb = (a.npix + 255u) / 256u;
+    double2* partials = (double2*)ctx->accum_partials.p;
+    double* figures = (double*)(partials + nb);
+    hipLaunchKernelGGL(k_noise_partials, dim3(nb), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, partials, a.npix, a.done);
+    hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, a.npix, a.done, figures);
+    RT_HIP(ctx, hipMemcpyAsync(ctx->h_noise, figures, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    return RT_OK;
+}
+static void fill_noise(const RtCtx* ctx, RtNoise* noise) {
+    const RtCtx::Accum& a = ctx->accum;
+    std::memset(noise, 0, sizeof(*noise));
+    noise->spp_done = a.done;
+    if (a.npix == 0u) { // a shard without rows: nothing to measure
+        noise->noise = a.done < 2u ? (double)INFINITY : 0.0;
+        return;
+    }
+    noise->mean_luminance = ctx->h_noise[0], noise->rms_sem = ctx->h_noise[1], noise->noise = ctx->h_noise[2];
+}
+
+int rt_accum_begin(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, uint32_t first_sample) {
+    int rc = check_params(ctx, cam, prm);
+    if (rc) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->accum.open = false;
+    RtCtx::Accum a{};
+    a.cam = *cam, a.prm = *prm, a.first = first_sample;
+    a.nx = prm->nx;
+    a.rows = rt_shard_rows(prm->ny, prm->shard_band ? prm->shard_band : 1u, prm->shard_count, prm->shard_id);
+    const uint64_t npix64 = (uint64_t)a.rows * a.nx;
+    a.npix = (uint32_t)npix64;
+    pixel_order(ctx, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+    if (a.npix) {
+        const uint32_t nb = (a.npix + 255u) / 256u;
+        if ((rc = ensure(ctx, ctx->accum_sum, (size_t)a.npix * 3 * sizeof(float)))) return rc;
+        if ((rc = ensure(ctx, ctx->accum_mom, (size_t)a.npix * sizeof(double2)))) return rc;
+        if ((rc = ensure(ctx, ctx->accum_partials, (size_t)nb * sizeof(double2) + 3 * sizeof(double)))) return rc;
+        if (!ctx->h_noise) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_noise, 3 * sizeof(double), hipHostMallocDefault));
+        RT_HIP(ctx, hipMemsetAsync(ctx->accum_sum.p, 0, (size_t)a.npix * 3 * sizeof(float), ctx->stream));
+        RT_HIP(ctx, hipMemsetAsync(ctx->accum_mom.p, 0, (size_t)a.npix * sizeof(double2), ctx->stream));
+        // the work buffers of one add of prm->spp samples, requested now (as rt_prepare does for a frame)
+        SlicePlan plan;
+        if ((rc = plan_slices(ctx, prm, npix64, plan))) return rc;
+        ctx->pool.chunk_delay_us.store(ctx->opt[RT_OPT_POOL_CHUNK_DELAY_US]);
+        if (const char* e = pool_request(ctx->pool, plan.want_bytes)) return fail(ctx, RT_ERR_NOMEM, std::string("rt_accum_begin: ") + e);
+    }
+    ctx->accum = a;
+    ctx->accum.open = true;
+    return RT_OK;
+}
+
+// figures: the frame figures are enqueued behind the samples, so that the one wait of the call (for its statistics) delivers them too
+static int accum_add(RtCtx* ctx, uint32_t n_samples, RtStats* stats, bool figures) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_add: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (n_samples == 0u) return fail(ctx, RT_ERR_INVALID, "rt_accum_add: n_samples must be > 0");
+    if ((uint64_t)a.first + a.done + n_samples > 0xFFFFFFFFull)
+        return fail(ctx, RT_ERR_INVALID, "rt_accum_add: first_sample + the samples added must stay below 2^32, as RtParams.spp does");
+    RtParams p = a.prm;
+    p.spp = n_samples;
+    Traced tr;
+    const SampleSink sink{(float*)ctx->accum_sum.p, (double2*)ctx->accum_mom.p, a.first + a.done};
+    const int rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr);
+    if (rc) return rc;
+    if (tr.npix == 0u) {
+        a.done += n_samples;
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    if (tr.npix != a.npix || tr.tiles_per_row != a.tiles_per_row || tr.tile_pixels != a.tile_pixels) {
+        a.open = false; // (cannot happen: everything the order hangs on ends the accumulation)
+        return fail(ctx, RT_ERR_STATE, "rt_accum_add: the pixel order changed since rt_accum_begin (internal)");
+    }
+    a.done += n_samples;
+    if (figures)
+        if (const int rn = enqueue_noise(ctx, tr.st)) return rn;
+    RT_HIP(ctx, hipEventRecord(ctx->ev_end, tr.st));
+    RT_HIP(ctx, hipGetLastError());
+    ctx->mark("enqueue_all_launches");
+    if (stats) return read_stats(ctx, tr, n_samples, stats);
+    if (figures) RT_HIP(ctx, hipStreamSynchronize(tr.st));
+    return RT_OK;
+}
+
+int rt_accum_add(RtCtx* ctx, uint32_t n_samples, RtStats* stats) { return accum_add(ctx, n_samples, stats, false); }
+
+int rt_accum_read(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_sem, RtNoise* noise) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_read: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (a.npix == 0u) {
+        if (noise) fill_noise(ctx, noise);
+        return RT_OK;
+    }
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const uint32_t npix = a.npix, grid = (npix + 255u) / 256u;
+    const size_t n = (size_t)npix * 3;
+    int rc;
+    if (out_rgb_f32 && (rc = ensure(ctx, ctx->out_f32, n * sizeof(float)))) return rc;
+    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
+    if (out_sem && (rc = ensure(ctx, ctx->accum_sem, (size_t)npix * sizeof(float)))) return rc;
+    if (out_rgb_f32 || out_rgb8) // (before the first add the sums are zeros: divided by 1, not by 0)
+        hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, out_rgb_f32 ? (float*)ctx->out_f32.p : (float*)nullptr,
+                           out_rgb8 ? (uint8_t*)ctx->out_u8.p : (uint8_t*)nullptr, a.nx, a.rows, std::max(a.done, 1u), a.tiles_per_row, a.tile_pixels);
+    if (out_sem)
+        hipLaunchKernelGGL(k_sem, dim3(grid), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, (float*)ctx->accum_sem.p, a.nx, a.rows, a.done,
+                           a.tiles_per_row, a.tile_pixels);
+    if (noise && (rc = enqueue_noise(ctx, st))) return rc;
+    RT_HIP(ctx, hipGetLastError());
+    if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->out_f32.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (out_rgb8) RT_HIP(ctx, hipMemcpyAsync(out_rgb8, ctx->out_u8.p, n, hipMemcpyDeviceToHost, st));
+    if (out_sem) RT_HIP(ctx, hipMemcpyAsync(out_sem, ctx->accum_sem.p, (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    if (noise) fill_noise(ctx, noise);
+    return RT_OK;
+}
+
+int rt_accum_end(RtCtx* ctx) {
+    if (!ctx) return RT_ERR_INVALID;
+    ctx->accum.open = false;
+    return RT_OK;
+}
+
+int rt_render_to_noise(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, double target_noise, uint32_t spp_step, float* out_rgb_f32,
+                       uint8_t* out_rgb8, float* out_sem, RtNoise* noise, RtStats* stats) {
+    int rc = check_params(ctx, cam, prm);
+    if (rc) return rc;
+    if (ctx->accum.open) return fail(ctx, RT_ERR_STATE, "rt_render_to_noise: an accumulation is open (rt_accum_end it first)");
+    if (spp_step == 0u) return fail(ctx, RT_ERR_INVALID, "rt_render_to_noise: spp_step must be > 0");
+    if (!(target_noise >= 0.0)) return fail(ctx, RT_ERR_INVALID, "rt_render_to_noise: target_noise must be >= 0 (and not NaN)");
+    if (prm->spp < 2u) return fail(ctx, RT_ERR_INVALID, "rt_render_to_noise: spp, the maximum, must be >= 2 (one sample has no variance estimate)");
+    RtParams p = *prm;
+    p.spp = std::min(spp_step, prm->spp); // (the expected size of one add)
+    if ((rc = rt_accum_begin(ctx, cam, &p, 0u))) return rc;
+    RtStats total;
+    std::memset(&total, 0, sizeof(total));
+    while (ctx->accum.done < prm->spp) {
+        RtStats s;
+        if ((rc = accum_add(ctx, std::min(spp_step, prm->spp - ctx->accum.done), &s, true))) break;
+        total.n_paths += s.n_paths, total.n_rays += s.n_rays, total.n_rays_secondary += s.n_rays_secondary;
+        total.n_texture_fetches += s.n_texture_fetches, total.n_bad_dir += s.n_bad_dir;
+        total.seconds_total += s.seconds_total, total.seconds_trace += s.seconds_trace, total.seconds_device += s.seconds_device;
+        total.bytes_algorithmic += s.bytes_algorithmic, total.bytes_trace_algorithmic += s.bytes_trace_algorithmic;
+        total.n_trace_launches += s.n_trace_launches, total.n_slices += s.n_slices;
+        for (int d = 0; d < 64; ++d) total.rays_per_depth[d] += s.rays_per_depth[d];
+        if (ctx->accum.npix == 0u || ctx->h_noise[2] <= target_noise) break;
+    }
+    if (!rc) rc = rt_accum_read(ctx, out_rgb_f32, out_rgb8, out_sem, noise);
+    ctx->accum.open = false;
+    if (!rc && stats) *stats = total;
+    return rc;
+}
+
 void* rt_host_alloc(size_t bytes) {
     void* p = nullptr;
     if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
@@ -1868,6 +2085,7 @@ void rt_host_free(void* p) {
 int rt_debug_set_option(RtCtx* ctx, uint32_t option, uint32_t value) {
     if (!ctx) return RT_ERR_INVALID;
     if (option >= RT_OPT__COUNT) return fail(ctx, RT_ERR_INVALID, "rt_debug_set_option: unknown option");
+    ctx->accum.open = false; // (the pixel order and the kernel choice of an accumulation hang on options)
     ctx->opt[option] = value;
     return RT_OK;
 }
@@ -2026,7 +2244,7 @@ int rt_set_progress(RtCtx* ctx, RtProgressFn fn, void* user) {
     return RT_OK;
 }
 
-int rt_set_lens(RtCtx* ctx, const RtLens* lens) {
+static int set_lens_impl(RtCtx* ctx, const RtLens* lens) {
     if (!ctx) return RT_ERR_INVALID;
     if (!lens) {
         ctx->lens = RtLens{0.0f, 1.0f};
@@ -2056,7 +2274,7 @@ static int check_shutter(RtCtx* ctx, const RtMotion* m) {
 //   tree leaf  = [min(c0, e1) - r - slack, max(c0, e1) + r + slack], then pad_prim_box as for every leaf;
 //   ent_bs     = centre (c0 + e1) / 2, radius r + |e1 - c0| / 2 + the distance the rounded centre moved + sqrt(3) slack, rounded up;
 //   grid       = build_sphere_grid's swept boxes (its own argument for the roundings, rt_grid.h).
-int rt_set_motion(RtCtx* ctx, const RtMotion* motion) {
+static int set_motion_impl(RtCtx* ctx, const RtMotion* motion) {
     if (!ctx) return RT_ERR_INVALID;
     if (!ctx->has_scene) return fail(ctx, RT_ERR_STATE, "rt_set_motion: no scene uploaded");
     RT_HIP(ctx, hipSetDevice(ctx->device));
@@ -2282,7 +2500,7 @@ int rt_debug_planar_info(const RtCtx* ctx, uint32_t* n_planar, uint32_t* plane_d
     return RT_OK;
 }
 
-int rt_set_quads(RtCtx* ctx, const RtQuads* quads) {
+static int set_quads_impl(RtCtx* ctx, const RtQuads* quads) {
     if (!ctx) return RT_ERR_INVALID;
     if (!ctx->has_scene) return fail(ctx, RT_ERR_STATE, "rt_set_quads: no scene uploaded");
     RT_HIP(ctx, hipSetDevice(ctx->device));
@@ -2355,7 +2573,7 @@ int rt_set_quads(RtCtx* ctx, const RtQuads* quads) {
 // test in double and the same f32 plane set-up as rt_set_quads) with area = sqrt(dot(n, n)), n = cross(u, v), in the free w of g[3].
 // The lights are sampling targets only: no tree, grid or list knows them, so a set goes with either search state and survives
 // rt_set_quads.
-int rt_set_lights(RtCtx* ctx, const RtLights* lights) {
+static int set_lights_impl(RtCtx* ctx, const RtLights* lights) {
     if (!ctx) return RT_ERR_INVALID;
     if (!ctx->has_scene) return fail(ctx, RT_ERR_STATE, "rt_set_lights: no scene uploaded");
     RT_HIP(ctx, hipSetDevice(ctx->device));
@@ -2393,6 +2611,17 @@ int rt_set_lights(RtCtx* ctx, const RtLights* lights) {
     ctx->lights = true;
     return RT_OK;
 }
+
+// A set that took effect — or that failed on the device, which leaves the context without the set — ends an open accumulation: its
+// samples were traced with the previous one.  A refused set (the previous state stays) does not.
+static int set_ends_accum(RtCtx* ctx, int rc) {
+    if (ctx && (rc == RT_OK || rc == RT_ERR_DEVICE || rc == RT_ERR_NOMEM)) ctx->accum.open = false;
+    return rc;
+}
+int rt_set_lens(RtCtx* ctx, const RtLens* lens) { return set_ends_accum(ctx, set_lens_impl(ctx, lens)); }
+int rt_set_motion(RtCtx* ctx, const RtMotion* motion) { return set_ends_accum(ctx, set_motion_impl(ctx, motion)); }
+int rt_set_quads(RtCtx* ctx, const RtQuads* quads) { return set_ends_accum(ctx, set_quads_impl(ctx, quads)); }
+int rt_set_lights(RtCtx* ctx, const RtLights* lights) { return set_ends_accum(ctx, set_lights_impl(ctx, lights)); }
 
 int rt_get_depth_timings(RtCtx* ctx, uint32_t max_n, float* isect_ms, float* shade_ms, uint64_t* rays) {
     if (!ctx) return RT_ERR_INVALID;

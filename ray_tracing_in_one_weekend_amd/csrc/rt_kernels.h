@@ -1811,4 +1811,86 @@ __global__ __launch_bounds__(BLOCK) void k_debug_bounce(DevScene sc, uint32_t n,
     out_alive[i] = bo.alive ? 1 : 0;
 }
 
+// ---- accumulation and noise (rt_accum_*, rtow_mi355x.h): the running sum of k_resolve and two f64 luminance moments per pixel -------
+// Rec. 709 luminance of one sample, every operation one f64 operation in this order (no FMA: -ffp-contract=off).
+__device__ __forceinline__ double sample_luminance(float r, float g, float b) {
+    return (0.2126 * (double)r + 0.7152 * (double)g) + 0.0722 * (double)b;
+}
+// k_resolve — the same loads, the same loop order, the same f32 sums — plus S1 += Y and S2 += Y Y per sample.  A lane reads 12 B at
+// stride 12 B like k_resolve (a wave: 768 contiguous bytes per sample); the two f64 chains are 2 adds and 4 multiplies per 12 B read.
+__global__ __launch_bounds__(256) void k_resolve_moments(const float* __restrict__ rad, float* __restrict__ acc, double2* __restrict__ mom,
+                                                         uint32_t npix, uint32_t s_count) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= npix) return;
+    float r = acc[3 * (size_t)p], g = acc[3 * (size_t)p + 1], b = acc[3 * (size_t)p + 2];
+    double2 m = mom[p];
+    for (uint32_t s = 0; s < s_count; ++s) {
+        const float* src = rad + RT_RAD_FLOATS * ((size_t)s * npix + p);
+        const float sx = src[0], sy = src[1], sz = src[2];
+        r += sx;
+        g += sy;
+        b += sz;
+        const double y = sample_luminance(sx, sy, sz);
+        m.x += y;
+        m.y += y * y;
+    }
+    acc[3 * (size_t)p] = r, acc[3 * (size_t)p + 1] = g, acc[3 * (size_t)p + 2] = b;
+    mom[p] = m;
+}
+
+// Mean luminance and variance of the mean of one pixel after n samples (rtow_mi355x.h "Moments"); n < 2: no variance estimate, 0.
+__device__ __forceinline__ void pixel_noise(double2 m, uint32_t n, double& ybar, double& v) {
+    const double dn = (double)n;
+    ybar = n ? m.x / dn : 0.0;
+    v = 0.0;
+    if (n >= 2u) {
+        const double q = (m.y - m.x * m.x / dn) / (dn - 1.0);
+        v = (q < 0.0 ? 0.0 : q) / dn; // (a NaN stays one)
+    }
+}
+// out_sem in output pixel order, as k_finalize maps it.
+__global__ __launch_bounds__(256) void k_sem(const double2* __restrict__ mom, float* __restrict__ out_sem, uint32_t nx, uint32_t rows,
+                                             uint32_t n, uint32_t tiles_per_row, uint32_t tile_pixels) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= nx * rows) return;
+    const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx);
+    double ybar, v;
+    pixel_noise(mom[ap], n, ybar, v);
+    out_sem[p] = (float)sqrt(v);
+}
+// Frame figures, a fixed tree and no atomics: per workgroup (sum Ybar, sum V) of its 256 pixels — lanes by __shfl_down, the four waves
+// through LDS in wave order — then ONE workgroup over the partials, thread t taking partials t, t + 256, ... in index order and the same
+// two steps.  The same moments give the same bits, whatever else the device runs.
+__device__ __forceinline__ double2 block_sum_256(double a, double b, double2* part) {
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_down(a, off);
+        b += __shfl_down(b, off);
+    }
+    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = make_double2(a, b);
+    __syncthreads();
+    return make_double2(((part[0].x + part[1].x) + part[2].x) + part[3].x, ((part[0].y + part[1].y) + part[2].y) + part[3].y);
+}
+__global__ __launch_bounds__(256) void k_noise_partials(const double2* __restrict__ mom, double2* __restrict__ partials, uint32_t npix, uint32_t n) {
+    __shared__ double2 part[4];
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    double ybar = 0.0, v = 0.0; // (tail slots contribute nothing)
+    if (p < npix) pixel_noise(mom[p], n, ybar, v);
+    const double2 s = block_sum_256(ybar, v, part);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+// out[0] = mean_luminance, out[1] = rms_sem, out[2] = noise (RtNoise)
+__global__ __launch_bounds__(256) void k_noise_final(const double2* __restrict__ partials, uint32_t n_partials, uint32_t npix, uint32_t n,
+                                                     double* __restrict__ out) {
+    __shared__ double2 part[4];
+    double a = 0.0, b = 0.0;
+    for (uint32_t k = threadIdx.x; k < n_partials; k += 256u) a += partials[k].x, b += partials[k].y;
+    const double2 s = block_sum_256(a, b, part);
+    if (threadIdx.x != 0) return;
+    const double mean = s.x / (double)npix, rms = sqrt(s.y / (double)npix);
+    double noise = rms / mean;
+    if (mean == 0.0) noise = rms == 0.0 ? 0.0 : (double)INFINITY;
+    if (n < 2u) noise = (double)INFINITY;
+    out[0] = mean, out[1] = rms, out[2] = noise;
+}
+
 } // namespace rt

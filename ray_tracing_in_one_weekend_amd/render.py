@@ -36,6 +36,12 @@ def main(argv=None):
                     help="shutter interval within [0, 1] for a scene with moving spheres (default: the scene camera's, [0, 1])")
     ap.add_argument("--light-sampling", action="store_true",
                     help="aim half of the diffuse bounces at the scene's emissive rectangles and quads (Scene.lights): same mean, less noise")
+    ap.add_argument("--noise-target", type=float, default=None, metavar="X",
+                    help="render to a quality: add samples until the frame's noise (RMS standard error of the pixels' mean luminance over "
+                         "the mean luminance, RtNoise.noise) is at most X; --spp is then the maximum")
+    ap.add_argument("--spp-step", type=int, default=64, metavar="N",
+                    help="samples per pixel between two looks at the noise (with --noise-target); a step costs about 2 ms beyond its samples at "
+                         "1920 x 1080 (DESIGN.md \"Accumulation and noise\"): 64 keeps that below a fifth")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     ny = a.ny
@@ -60,6 +66,8 @@ def main(argv=None):
     if a.light_sampling:
         rend.set_lights(scene.lights)  # (a moving scene refuses it: RT_ERR_UNSUPPORTED)
     flags = _ffi.FLAG_RUSSIAN_ROULETTE if a.russian_roulette else 0
+    if a.noise_target is not None:
+        return render_to_noise(a, rend, scene, flags, file_name, t0)
     params = make_params(a.nx, ny, a.spp, max_depth=a.max_depth, seed=a.seed, spp_slice=a.preview_every, flags=flags)
     if a.preview_every:
         def progress(done, total, rgb8):
@@ -71,6 +79,33 @@ def main(argv=None):
     save_png(file_name, rgb8)                                                  # main.rs:127-128
     print(f"{file_name}: {a.nx}x{ny}, {a.spp} spp, {st.n_rays} rays, {st.n_rays / st.seconds_device / 1e6:.0f} Mray/s on the device",
           file=sys.stderr)
+    return 0
+
+
+def render_to_noise(a, rend, scene, flags, file_name, t0):
+    """--noise-target: samples in steps of --spp-step until the noise is reached or --spp are done.  With --preview-every the steps are
+    taken here and the partial image of accum_read is saved after each; without, the library's rt_render_to_noise does the same."""
+    params = make_params(a.nx, a.ny, a.spp, max_depth=a.max_depth, seed=a.seed, flags=flags)
+    if a.preview_every:
+        step = make_params(a.nx, a.ny, min(a.spp_step, a.spp), max_depth=a.max_depth, seed=a.seed, flags=flags)
+        rend.accum_begin(scene.camera, step)
+        n_rays, seconds, done = 0, 0.0, 0
+        while True:
+            st = rend.accum_add(min(a.spp_step, a.spp - done))
+            n_rays, seconds, done = n_rays + st.n_rays, seconds + st.seconds_device, done + st.n_paths // (a.nx * a.ny)
+            _, rgb8, _, noise = rend.accum_read(want_rgb8=True)
+            print(f"{noise.spp_done}/{a.spp} noise {noise.noise:.4g}", file=sys.stderr)
+            save_png(file_name, rgb8)
+            if noise.noise <= a.noise_target or noise.spp_done >= a.spp:
+                break
+        rend.accum_end()
+    else:
+        _, rgb8, _, noise, st = rend.render_to_noise(scene.camera, params, a.noise_target, a.spp_step, want_rgb8=True)
+        n_rays, seconds = st.n_rays, st.seconds_device
+        save_png(file_name, rgb8)
+    print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
+    print(f"{file_name}: {a.nx}x{a.ny}, {noise.spp_done} of at most {a.spp} spp, noise {noise.noise:.4g} (target {a.noise_target:g}), "
+          f"{n_rays} rays, {n_rays / seconds / 1e6:.0f} Mray/s on the device", file=sys.stderr)
     return 0
 
 
