@@ -458,7 +458,8 @@ int rt_set_lights(RtCtx* ctx, const RtLights* lights);
  * run over a fixed tree (per workgroup, then one workgroup over the partial sums in index order; no floating-point atomics): the same
  * accumulation read twice gives the same bits.
  * Cost: 28 B per pixel that the accumulation owns (an f32 x 3 sum, an f64 x 2 moment), apart from the frame renderer's buffers —
- * rt_render and rt_render_device may be called in between and neither disturbs the other.
+ * rt_render and rt_render_device may be called in between and neither disturbs the other.  The first rt_accum_denoise of a context adds
+ * 20 B + 12 B per pixel (the filter's inputs c, y, v in image order and its output), kept for the next like the accumulation's buffers.
  * Not covered: rt_multi_* (the noise of a frame split over devices needs a reduction across them); the rt_set_progress callback (a
  * host that accumulates has its preview in rt_accum_read); per-pixel adaptive sampling (primary rays are generated over the whole
  * lattice of the shard: every add gives every pixel the same number of samples). */
@@ -498,6 +499,45 @@ int rt_accum_end(RtCtx* ctx);
  * RT_ERR_INVALID: spp_step 0, target_noise NaN or negative, params->spp < 2. */
 int rt_render_to_noise(RtCtx* ctx, const RtCamera* cam, const RtParams* params, double target_noise, uint32_t spp_step,
                        float* out_rgb_f32, uint8_t* out_rgb8, float* out_sem, RtNoise* noise, RtStats* stats);
+
+/* -- denoising: a non-local-means filter guided by the accumulation's own variance -----------------------------------------------------
+ * The two moments of a pixel say how far two pixel means may differ by chance; the filter averages what differs only by that much and
+ * keeps what differs by more (Rousselle, Knaus, Zwicker 2012: "Adaptive rendering with non-local means filtering").  Image space: it
+ * reads the running sum and the moments an open accumulation owns, through kernels of its own, and changes nothing in them.
+ * Every operation is one IEEE f32 operation in the order written, no FMA; `/` is the correctly rounded division.
+ * Inputs.  Pixel a in image order, row 0 at the bottom, as out_rgb_f32; the accumulation holds n samples:
+ *   c_a = the three channel sums, each divided by (float)n — what rt_accum_read writes;  y_a = (float)Ybar_a;  v_a = (float)V_a,
+ *   Ybar and V the f64 figures of "Moments" above.
+ * Parameters.  R = radius, 1 .. RT_DENOISE_MAX_RADIUS;  F = patch, 0 .. RT_DENOISE_MAX_PATCH;  k = strength, finite and > 0;
+ *   k2 = k * k;  eps = 1e-10f;  cnt = (float)((2F+1)*(2F+1)).
+ * Per output pixel p = (px, py): visit delta = (dx, dy) with dy from -R to R in the outer loop and dx from -R to R in the inner one;
+ * q = p + delta, skipped where it lies outside the image.
+ *   1. Patch distance.  Coordinates are clamped to the image per axis, those of a and of b independently; row sums come first:
+ *        S = 0;  for oy = -F..F: { row = 0;  for ox = -F..F: row = row + d(clamp(p + o), clamp(q + o));  S = S + row; }   D = S / cnt;
+ *        d(a, b) = ((y_a - y_b) * (y_a - y_b) - (v_a + min(v_a, v_b))) / (eps + k2 * (v_a + v_b)),  min(v_a, v_b) = v_b < v_a ? v_b : v_a.
+ *   2. Weight.  m = (D < 0) ? 0 : D (a NaN stays NaN);  u = 1 - 0.25f * m;  u = (u > 0) ? u : 0 (a NaN becomes 0);  w = (u * u) * (u * u).
+ *      w follows exp(-m) closely, has compact support (0 from D = 4 on) and needs no transcendental function.
+ *   3. Accumulate, only where u != 0:  den = den + w,  and per channel  num = num + w * c_q.
+ * Output.  out_p = num / den per channel; out_p = c_p where den == 0.  That happens only where p itself is not finite: its own patch
+ * makes every D NaN.  A non-finite pixel does not spread: any patch that holds it has D = NaN, u = 0, and such terms are skipped, not
+ * multiplied by 0.  For a finite p the term q = p has D <= 0 and w = 1, so den >= 1.
+ * The order of the sums is part of the definition; it lets row sums be shared between neighbouring pixels without changing a bit.
+ * Not covered: the distance is on LUMINANCE, the one quantity whose variance the accumulation keeps — edges between colours of equal
+ * luminance blur (per-channel moments would cost 48 B per pixel more and change k_resolve_moments); the weights are chosen from the
+ * image they filter (there are no two half buffers, so the filter is slightly biased towards its own noise); rt_multi_* is not supported.
+ * DESIGN.md "Denoising". */
+typedef struct RtDenoise { uint32_t radius, patch; float strength; uint32_t reserved; } RtDenoise;
+#define RT_DENOISE_MAX_RADIUS 10u
+#define RT_DENOISE_MAX_PATCH 3u
+#define RT_DENOISE_DEFAULT_STRENGTH 1.0f /* of 0.45, 0.7 and 1.0 the one with the lowest error on rendered frames (DESIGN.md "Denoising") */
+/* Filters the frame of the open accumulation; `dn` NULL: radius 5, patch 1, strength RT_DENOISE_DEFAULT_STRENGTH.  The outputs are laid
+ * out as rt_accum_read lays them out, either may be NULL; out_rgb8 is the filtered image through the quantisation and flip of rt_render.
+ * The accumulation is read and not changed: rt_accum_read returns the same bits afterwards and further rt_accum_adds continue as if the
+ * call had not happened.  Synchronises the context's stream once.  RT_ERR_STATE: no accumulation is open, or fewer than 2 samples are
+ * done (there is no variance yet).  RT_ERR_UNSUPPORTED: shard_count > 1 (the local rows of an interleaved shard are not neighbours in
+ * the image).  RT_ERR_INVALID: radius 0 or above the maximum, patch above the maximum, strength non-finite or <= 0, reserved != 0.  A
+ * shard without pixels: RT_OK, nothing is written. */
+int rt_accum_denoise(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8);
 
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the

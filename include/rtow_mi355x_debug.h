@@ -227,6 +227,12 @@ int rt_debug_bounce(RtCtx* ctx, const RtBounceIO* io);
 #define RT_ARITH_TO_U32 3u
 int rt_debug_arithmetic(RtCtx* ctx, uint32_t op, uint32_t n, const float* x, const float* a, float* out);
 
+/* Test hook for the filter of rt_accum_denoise (rtow_mi355x.h "denoising"): the same kernel over host arrays in image order — rgb
+ * [3 * nx * rows] = c, y and v [nx * rows] — with `dn` as rt_accum_denoise reads it (NULL: the defaults); out_rgb_f32 [3 * nx * rows].
+ * No scene and no accumulation is needed: the tests feed borders, NaNs and zero variances at chosen sizes.  RT_ERR_INVALID: a NULL
+ * array, nx * rows outside 1 .. 2^28, or parameters rt_accum_denoise would refuse. */
+int rt_debug_denoise(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* y, const float* v, const RtDenoise* dn,
+                     float* out_rgb_f32);
 
 #ifdef __cplusplus
 }

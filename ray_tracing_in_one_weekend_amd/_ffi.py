@@ -124,6 +124,16 @@ class RtNoise(C.Structure):
                 ("noise", C.c_double)]
 
 
+class RtDenoise(C.Structure):
+    """rt_accum_denoise: window radius (1..MAX), patch radius (0..MAX) and strength k of the variance-guided non-local-means filter
+    (rtow_mi355x.h "denoising")."""
+    _fields_ = [("radius", C.c_uint32), ("patch", C.c_uint32), ("strength", C.c_float), ("reserved", C.c_uint32)]
+
+
+DENOISE_MAX_RADIUS, DENOISE_MAX_PATCH = 10, 3
+DENOISE_DEFAULT_STRENGTH = 1.0  # RT_DENOISE_DEFAULT_STRENGTH
+
+
 class RtBounceIO(C.Structure):
     _fields_ = [("n", C.c_uint32), ("depth", C.c_uint32), ("in_o", _f), ("in_d", _f), ("in_key", _u32),
                 ("out_hit", C.POINTER(C.c_int32)), ("out_t", _f), ("out_radiance", _f), ("out_attenuation", _f),
@@ -175,6 +185,7 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_set_quads", "rt_multi_set_quads", "rt_debug_planar_info", "rt_debug_planar_bounds",
                "rt_set_lights", "rt_multi_set_lights",
                "rt_accum_begin", "rt_accum_add", "rt_accum_read", "rt_accum_end", "rt_render_to_noise",
+               "rt_accum_denoise", "rt_debug_denoise",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
@@ -264,6 +275,10 @@ def load_gpu_library():
     lib.rt_render_to_noise.argtypes = [vp, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_double, C.c_uint32, _f, _u8, _f, C.POINTER(RtNoise),
                                        C.POINTER(RtStats)]
     lib.rt_render_to_noise.restype = C.c_int
+    lib.rt_accum_denoise.argtypes = [vp, C.POINTER(RtDenoise), _f, _u8]
+    lib.rt_accum_denoise.restype = C.c_int
+    lib.rt_debug_denoise.argtypes = [vp, C.c_uint32, C.c_uint32, _f, _f, _f, C.POINTER(RtDenoise), _f]
+    lib.rt_debug_denoise.restype = C.c_int
     lib.rt_debug_planar_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.rt_debug_planar_info.restype = C.c_int
     lib.rt_debug_planar_bounds.argtypes = [C.POINTER(RtQuads), C.c_float, vp, vp]

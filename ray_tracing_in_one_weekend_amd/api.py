@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import RtBounceIO, RtCamera, RtFlatScene, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtStats
+from ._ffi import RtBounceIO, RtCamera, RtDenoise, RtFlatScene, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtStats
 
 
 class RtError(RuntimeError):
@@ -594,6 +594,35 @@ class Renderer:
         if rc != 0:
             self._raise("rt_render_to_noise", rc)
         return img, rgb8, sem, noise, stats
+
+    @staticmethod
+    def _denoise_ptr(radius, patch, strength):
+        dn = RtDenoise(int(radius), int(patch), float(_ffi.DENOISE_DEFAULT_STRENGTH if strength is None else strength), 0)
+        return C.byref(dn)
+
+    def accum_denoise(self, radius=5, patch=1, strength=None, want_rgb8=False):
+        """rt_accum_denoise: the frame of the open accumulation through the variance-guided non-local-means filter (window radius, patch
+        radius, strength; None: RT_DENOISE_DEFAULT_STRENGTH).  Returns (img [rows, nx, 3] f32, rgb8 or None) laid out as accum_read's; the
+        accumulation itself is not changed."""
+        img, rgb8, _, ptrs = self._accum_outputs(want_rgb8, False)
+        rc = self._lib.rt_accum_denoise(self._ctx, self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
+        if rc != 0:
+            self._raise("rt_accum_denoise", rc)
+        return img, rgb8
+
+    def debug_denoise(self, rgb, y, v, radius=5, patch=1, strength=None):
+        """rt_debug_denoise: the filter kernel of accum_denoise over host arrays in image order — rgb [rows, nx, 3], y and v [rows, nx]
+        (a pixel's mean luminance and the variance of that mean); returns the filtered [rows, nx, 3] f32 image."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        y, v = np.ascontiguousarray(y, dtype=np.float32), np.ascontiguousarray(v, dtype=np.float32)
+        rows, nx = y.shape
+        assert rgb.shape == (rows, nx, 3) and v.shape == (rows, nx)
+        out = np.zeros_like(rgb)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        rc = self._lib.rt_debug_denoise(self._ctx, nx, rows, fp(rgb), fp(y), fp(v), self._denoise_ptr(radius, patch, strength), fp(out))
+        if rc != 0:
+            self._raise("rt_debug_denoise", rc)
+        return out
 
     def set_progress(self, fn):
         """fn(spp_done, spp_total, rgb8[rows, nx, 3]) after every slice but the last of a following render()

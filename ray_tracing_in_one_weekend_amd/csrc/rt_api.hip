@@ -3,6 +3,7 @@
 // of a slice is enqueued without any host synchronisation (queue sizes live in HBM).
 #include "../../include/rtow_mi355x_debug.h"
 #include "rt_kernels.h"
+#include "rt_denoise.h"
 #include "rt_bvh.h"
 #include "rt_grid.h"
 #include "rt_pool.h"
@@ -143,6 +144,7 @@ struct RtCtx {
     } accum;
     DevBuf accum_sum, accum_mom, accum_sem, accum_partials; // (accum_sem: staging of out_sem; accum_partials: one f64 pair per workgroup + the 3 frame figures)
     double* h_noise = nullptr;   // page-locked: mean_luminance, rms_sem, noise as k_noise_final wrote them
+    DevBuf dn_c, dn_yv, dn_out;  // rt_accum_denoise: the filter's inputs (c 12 B, (y, v) 8 B) and its output (12 B) per pixel, in image order
     // Host-side timeline of the last render_impl (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
     // render of a process is where allocations, code-object loads and the queue probe happen; this says which.
     std::vector<std::pair<const char*, double>> parts;
@@ -1286,6 +1288,7 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->out_f32), free_buf(ctx->out_u8), free_buf(ctx->dbg), free_buf(ctx->genp);
     free_buf(ctx->preview_u8), free_buf(ctx->lists);
     free_buf(ctx->accum_sum), free_buf(ctx->accum_mom), free_buf(ctx->accum_sem), free_buf(ctx->accum_partials);
+    free_buf(ctx->dn_c), free_buf(ctx->dn_yv), free_buf(ctx->dn_out);
     if (ctx->h_noise) (void)hipHostFree(ctx->h_noise);
     free_buf(ctx->motion_region), free_buf(ctx->quads_region), free_buf(ctx->lights_buf);
     for (auto ev : ctx->events) (void)hipEventDestroy(ev);
@@ -2067,6 +2070,90 @@ int rt_render_to_noise(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, dou
     ctx->accum.open = false;
     if (!rc && stats) *stats = total;
     return rc;
+}
+
+// ---- denoising (rtow_mi355x.h "Denoising", csrc/rt_denoise.h) -----------------------------------------------------------------------
+// The parameters of a call: `dn` checked, or the defaults for NULL.
+static int denoise_params(RtCtx* ctx, const RtDenoise* dn, RtDenoise& d, const char* who) {
+    d = RtDenoise{5u, 1u, RT_DENOISE_DEFAULT_STRENGTH, 0u};
+    if (!dn) return RT_OK;
+    if (dn->radius == 0u || dn->radius > RT_DENOISE_MAX_RADIUS) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": radius must be 1 .. RT_DENOISE_MAX_RADIUS");
+    if (dn->patch > RT_DENOISE_MAX_PATCH) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": patch must be 0 .. RT_DENOISE_MAX_PATCH");
+    if (!std::isfinite(dn->strength) || !(dn->strength > 0.0f)) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": strength must be finite and > 0");
+    if (dn->reserved != 0u) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": reserved must be 0");
+    d = *dn;
+    return RT_OK;
+}
+// k_denoise over an image in image order: c, yv -> out (device pointers), nx, rows >= 1
+static void launch_denoise(hipStream_t st, const float* c, const float2* yv, float* out, uint32_t nx, uint32_t rows, const RtDenoise& d) {
+    const dim3 grid((nx + RT_DN_TILE - 1u) / RT_DN_TILE, (rows + RT_DN_TILE - 1u) / RT_DN_TILE), block(RT_DN_TILE, RT_DN_TILE);
+    const int R = (int)d.radius;
+    const float k2 = d.strength * d.strength;
+    const size_t lds = denoise_lds_bytes(d.radius, d.patch);
+    switch (d.patch) {
+    case 0u: hipLaunchKernelGGL(k_denoise<0>, grid, block, lds, st, c, yv, out, nx, rows, R, k2); break;
+    case 1u: hipLaunchKernelGGL(k_denoise<1>, grid, block, lds, st, c, yv, out, nx, rows, R, k2); break;
+    case 2u: hipLaunchKernelGGL(k_denoise<2>, grid, block, lds, st, c, yv, out, nx, rows, R, k2); break;
+    default: hipLaunchKernelGGL(k_denoise<3>, grid, block, lds, st, c, yv, out, nx, rows, R, k2); break;
+    }
+}
+static int ensure_denoise(RtCtx* ctx, size_t npix) {
+    int rc;
+    if ((rc = ensure(ctx, ctx->dn_c, npix * 3 * sizeof(float)))) return rc;
+    if ((rc = ensure(ctx, ctx->dn_yv, npix * sizeof(float2)))) return rc;
+    return ensure(ctx, ctx->dn_out, npix * 3 * sizeof(float));
+}
+
+int rt_accum_denoise(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    RtDenoise d;
+    int rc = denoise_params(ctx, dn, d, "rt_accum_denoise");
+    if (rc) return rc;
+    if (a.prm.shard_count > 1u)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_denoise: a sharded frame (shard_count > 1): the local rows of a shard are not neighbours in the image");
+    if (a.done < 2u) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise: fewer than 2 samples accumulated: there is no variance yet");
+    if (a.npix == 0u) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const uint32_t npix = a.npix, grid = (npix + 255u) / 256u;
+    const size_t n = (size_t)npix * 3;
+    if ((rc = ensure_denoise(ctx, npix))) return rc;
+    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
+    hipLaunchKernelGGL(k_denoise_inputs, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, (const double2*)ctx->accum_mom.p, (float*)ctx->dn_c.p,
+                       (float2*)ctx->dn_yv.p, a.nx, a.rows, a.done, a.tiles_per_row, a.tile_pixels);
+    launch_denoise(st, (const float*)ctx->dn_c.p, (const float2*)ctx->dn_yv.p, (float*)ctx->dn_out.p, a.nx, a.rows, d);
+    if (out_rgb8) // k_finalize's quantisation and flip of the filtered image: row-major (no tiles), and / (float)1 changes no bit
+        hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, st, (const float*)ctx->dn_out.p, (float*)nullptr, (uint8_t*)ctx->out_u8.p, a.nx, a.rows, 1u, 0u,
+                           0u);
+    RT_HIP(ctx, hipGetLastError());
+    if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->dn_out.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (out_rgb8) RT_HIP(ctx, hipMemcpyAsync(out_rgb8, ctx->out_u8.p, n, hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+int rt_debug_denoise(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* y, const float* v, const RtDenoise* dn, float* out_rgb_f32) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!rgb || !y || !v || !out_rgb_f32) return fail(ctx, RT_ERR_INVALID, "rt_debug_denoise: NULL array");
+    if (nx == 0u || rows == 0u || (uint64_t)nx * rows > (1ull << 28)) return fail(ctx, RT_ERR_INVALID, "rt_debug_denoise: nx * rows must be 1 .. 2^28");
+    RtDenoise d;
+    int rc = denoise_params(ctx, dn, d, "rt_debug_denoise");
+    if (rc) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t npix = (size_t)nx * rows;
+    if ((rc = ensure_denoise(ctx, npix))) return rc;
+    std::vector<float2> yv(npix);
+    for (size_t p = 0; p < npix; ++p) yv[p] = make_float2(y[p], v[p]);
+    const hipStream_t st = ctx->stream;
+    RT_HIP(ctx, hipMemcpyAsync(ctx->dn_c.p, rgb, npix * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    RT_HIP(ctx, hipMemcpyAsync(ctx->dn_yv.p, yv.data(), npix * sizeof(float2), hipMemcpyHostToDevice, st));
+    launch_denoise(st, (const float*)ctx->dn_c.p, (const float2*)ctx->dn_yv.p, (float*)ctx->dn_out.p, nx, rows, d);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->dn_out.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    return RT_OK;
 }
 
 void* rt_host_alloc(size_t bytes) {

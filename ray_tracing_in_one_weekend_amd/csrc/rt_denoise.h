@@ -1,0 +1,130 @@
+// rt_denoise.h — the variance-guided non-local-means filter of rt_accum_denoise (rtow_mi355x.h "Denoising"): image space, new kernels
+// only, fed by what an accumulation already owns (the running f32 sum and the two f64 luminance moments per pixel).
+//
+//   k_denoise_inputs : c = sum / (float)n, y = (float)Ybar, v = (float)V per pixel, in image order
+//   k_denoise<F>     : the filter; one thread per pixel, the (y, v) tile of a workgroup and its halo in LDS, the distance terms that the
+//                      patches of neighbouring pixels share evaluated once per workgroup
+//
+// Every operation of the filter is one IEEE f32 operation in the header's order (-ffp-contract=off, the compiler's correctly rounded
+// `/`): tests/denoise_ref.py restates it in numpy and the kernel is held to it bit for bit.
+#pragma once
+#include "rt_kernels.h"
+
+namespace rt {
+
+constexpr uint32_t RT_DN_TILE = 16u; // a workgroup filters 16 x 16 pixels: 256 threads, four waves of four rows
+// Pitch of the LDS tile in float2 entries.  A tile row is at most 16 + 2 (10 + 3) = 42 entries wide.  ds_read_b64 resolves bank conflicts
+// per 32-lane half, bank = (byte address / 4) % 64; a half holds two tile rows of 16 lanes, 32 banks each, which fall on the two halves of
+// the 64 banks exactly when the pitch is 16 mod 32 entries: 48 for every radius and patch, 48 * 42 * 8 B = 15.75 KiB at the most.
+constexpr uint32_t RT_DN_PITCH = 48u;
+
+// The filter's inputs of one accumulation after n samples, in image order (p = row * nx + column, row 0 at the bottom).
+__global__ __launch_bounds__(256) void k_denoise_inputs(const float* __restrict__ sum, const double2* __restrict__ mom, float* __restrict__ c,
+                                                        float2* __restrict__ yv, uint32_t nx, uint32_t rows, uint32_t n, uint32_t tiles_per_row,
+                                                        uint32_t tile_pixels) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= nx * rows) return;
+    const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx);
+    const float fs = (float)n;
+    c[3 * (size_t)p] = sum[3 * ap] / fs, c[3 * (size_t)p + 1] = sum[3 * ap + 1] / fs, c[3 * (size_t)p + 2] = sum[3 * ap + 2] / fs;
+    double ybar, v;
+    pixel_noise(mom[ap], n, ybar, v);
+    yv[p] = make_float2((float)ybar, (float)v);
+}
+
+// d(a, b) of the header: a, b = (y, v) of two pixels
+__device__ __forceinline__ float denoise_distance(float2 a, float2 b, float k2) {
+    const float dy = a.x - b.x;
+    const float vmin = b.y < a.y ? b.y : a.y; // min(v_a, v_b); either being NaN makes the quotient NaN whichever is picked
+    return (dy * dy - (a.y + vmin)) / (1e-10f + k2 * (a.y + b.y));
+}
+
+// Pitch of the distance map in floats.  ds_read_b32 banks are (byte address / 4) % 32 within a 32-lane half, two rows of 16 lanes: 16 mod 32
+// puts them on the two halves of the banks; a map row is at most 16 + 2 * 3 = 22 wide.
+constexpr uint32_t RT_DN_MAP_PITCH = 48u;
+
+// F: the patch radius (0 .. RT_DENOISE_MAX_PATCH), a template parameter so that the patch loops unroll.  R: 1 .. RT_DENOISE_MAX_RADIUS.
+// Grid: ceil(nx / 16) x ceil(rows / 16) workgroups of 16 x 16 threads; dynamic LDS: denoise_lds_bytes(R, F).
+//
+// The tile.  LDS entry (lx, ly) holds (y, v) of the pixel clamp(x0 - H + lx), clamp(y0 - H + ly), H = R + F, each axis clamped on its
+// own: the clamped patch coordinates of the header ARE the entries at p + o and q + o, since q itself lies in the image.
+//
+// Shared terms.  The term of offset o in the patch distance of (p, q = p + delta) is e(x, delta) = d(clamp(x), clamp(x + delta)) with
+// x = p + o: a function of x and delta alone, and the same term for the (2F + 1)^2 pixels p = x - o.  So per delta the workgroup
+// evaluates e ONCE for every x of its tile grown by F — (16 + 2F)^2 terms, each with its division, instead of 256 (2F + 1)^2 — into a
+// map in LDS, and a pixel sums its (2F + 1)^2 entries in the header's order (rows first): the same operands in the same order, the
+// same bits.  The map is double-buffered, so one barrier per delta is enough: a thread that runs ahead writes the other buffer, and
+// reaches the buffer being read only behind the next barrier, which every reader has then passed.  Every thread of the workgroup walks all
+// deltas (the barriers), whether its pixel or its q lies in the image or not; only the accumulation is guarded.
+template <int F>
+__global__ __launch_bounds__(256) void k_denoise(const float* __restrict__ c, const float2* __restrict__ yv, float* __restrict__ out,
+                                                 uint32_t nx, uint32_t rows, int R, float k2) {
+    extern __shared__ float2 dn_tile[];
+    constexpr int T = (int)RT_DN_TILE, TP = (int)RT_DN_PITCH, MP = (int)RT_DN_MAP_PITCH;
+    constexpr int E = T + 2 * F; // side of the distance map
+    const int H = R + F;
+    const int side = T + 2 * H;
+    float* const dmap = reinterpret_cast<float*>(dn_tile + TP * side); // 2 buffers of MP * E floats
+    const int x0 = (int)(blockIdx.x * RT_DN_TILE) - H, y0 = (int)(blockIdx.y * RT_DN_TILE) - H;
+    const int tx = (int)threadIdx.x, ty = (int)threadIdx.y;
+    const int tid = ty * T + tx;
+    for (int e = tid; e < side * side; e += 256) {
+        const int ly = e / side, lx = e - ly * side;
+        const int gx = min(max(x0 + lx, 0), (int)nx - 1), gy = min(max(y0 + ly, 0), (int)rows - 1);
+        dn_tile[ly * TP + lx] = yv[(size_t)gy * nx + gx];
+    }
+    __syncthreads();
+    const int px = (int)(blockIdx.x * RT_DN_TILE) + tx, py = (int)(blockIdx.y * RT_DN_TILE) + ty;
+    const bool live = px < (int)nx && py < (int)rows;
+    // the map entries this thread evaluates: e0 = tid and, for the E * E - 256 first threads, e1 = tid + 256 (E * E <= 484 < 512)
+    const int m0y = tid / E, m0x = tid - m0y * E;
+    const int e1 = tid + 256;
+    const bool two = e1 < E * E;
+    const int m1y = two ? e1 / E : 0, m1x = two ? e1 - m1y * E : 0;
+    const float2* const a0p = dn_tile + (m0y + R) * TP + m0x + R; // map entry (mx, my) is x = tile origin - F + (mx, my): tile entry + R
+    const float2* const a1p = dn_tile + (m1y + R) * TP + m1x + R;
+    const float2 a0 = *a0p, a1 = *a1p;
+    constexpr float cnt = (float)((2 * F + 1) * (2 * F + 1));
+    float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
+    int buf = 0;
+    for (int dy = -R; dy <= R; ++dy) {
+        const int qy = py + dy;
+        for (int dx = -R; dx <= R; ++dx, buf ^= 1) {
+            float* const map = dmap + buf * (MP * E);
+            const int off = dy * TP + dx;
+            map[m0y * MP + m0x] = denoise_distance(a0, a0p[off], k2);
+            if (two) map[m1y * MP + m1x] = denoise_distance(a1, a1p[off], k2);
+            __syncthreads();
+            const int qx = px + dx;
+            if (!live || qy < 0 || qy >= (int)rows || qx < 0 || qx >= (int)nx) continue;
+            const float* const mine = map + (ty + F) * MP + tx + F; // the map entry of x = p
+            float S = 0.0f;
+            for (int oy = -F; oy <= F; ++oy) {
+                float row = 0.0f;
+                for (int ox = -F; ox <= F; ++ox) row = row + mine[oy * MP + ox];
+                S = S + row;
+            }
+            const float D = S / cnt;
+            const float m = D < 0.0f ? 0.0f : D; // (a NaN stays one)
+            float u = 1.0f - 0.25f * m;
+            u = u > 0.0f ? u : 0.0f;             // (a NaN becomes 0)
+            if (u != 0.0f) {
+                const float w = (u * u) * (u * u);
+                const float* cq = c + 3 * ((size_t)qy * nx + qx);
+                den = den + w;
+                nr = nr + w * cq[0], ng = ng + w * cq[1], nb = nb + w * cq[2];
+            }
+        }
+    }
+    if (!live) return;
+    const size_t p = (size_t)py * nx + px;
+    float r = c[3 * p], g = c[3 * p + 1], b = c[3 * p + 2]; // den == 0: p itself is not finite and stays what it is
+    if (den != 0.0f) r = nr / den, g = ng / den, b = nb / den;
+    out[3 * p] = r, out[3 * p + 1] = g, out[3 * p + 2] = b;
+}
+// dynamic LDS of k_denoise<F>: the (y, v) tile and the two distance maps
+__host__ inline size_t denoise_lds_bytes(uint32_t R, uint32_t F) {
+    return (size_t)RT_DN_PITCH * (RT_DN_TILE + 2u * (R + F)) * sizeof(float2) + 2u * RT_DN_MAP_PITCH * (RT_DN_TILE + 2u * F) * sizeof(float);
+}
+
+} // namespace rt

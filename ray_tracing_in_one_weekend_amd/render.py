@@ -42,6 +42,12 @@ def main(argv=None):
     ap.add_argument("--spp-step", type=int, default=64, metavar="N",
                     help="samples per pixel between two looks at the noise (with --noise-target); a step costs about 2 ms beyond its samples at "
                          "1920 x 1080 (DESIGN.md \"Accumulation and noise\"): 64 keeps that below a fifth")
+    ap.add_argument("--denoise", action="store_true",
+                    help="save the frame through the variance-guided non-local-means filter (rt_accum_denoise); needs --spp >= 2")
+    ap.add_argument("--denoise-radius", type=int, default=5, metavar="R", help="search window radius, 1..%d" % _ffi.DENOISE_MAX_RADIUS)
+    ap.add_argument("--denoise-patch", type=int, default=1, metavar="F", help="patch radius, 0..%d" % _ffi.DENOISE_MAX_PATCH)
+    ap.add_argument("--denoise-strength", type=float, default=None, metavar="K",
+                    help="how many standard errors two pixels may differ and still be averaged (default %g)" % _ffi.DENOISE_DEFAULT_STRENGTH)
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     ny = a.ny
@@ -68,6 +74,8 @@ def main(argv=None):
     flags = _ffi.FLAG_RUSSIAN_ROULETTE if a.russian_roulette else 0
     if a.noise_target is not None:
         return render_to_noise(a, rend, scene, flags, file_name, t0)
+    if a.denoise:
+        return render_denoised(a, rend, scene, flags, file_name, t0)
     params = make_params(a.nx, ny, a.spp, max_depth=a.max_depth, seed=a.seed, spp_slice=a.preview_every, flags=flags)
     if a.preview_every:
         def progress(done, total, rgb8):
@@ -86,7 +94,7 @@ def render_to_noise(a, rend, scene, flags, file_name, t0):
     """--noise-target: samples in steps of --spp-step until the noise is reached or --spp are done.  With --preview-every the steps are
     taken here and the partial image of accum_read is saved after each; without, the library's rt_render_to_noise does the same."""
     params = make_params(a.nx, a.ny, a.spp, max_depth=a.max_depth, seed=a.seed, flags=flags)
-    if a.preview_every:
+    if a.preview_every or a.denoise:  # (rt_render_to_noise ends its accumulation: the filter needs it open)
         step = make_params(a.nx, a.ny, min(a.spp_step, a.spp), max_depth=a.max_depth, seed=a.seed, flags=flags)
         rend.accum_begin(scene.camera, step)
         n_rays, seconds, done = 0, 0.0, 0
@@ -95,9 +103,12 @@ def render_to_noise(a, rend, scene, flags, file_name, t0):
             n_rays, seconds, done = n_rays + st.n_rays, seconds + st.seconds_device, done + st.n_paths // (a.nx * a.ny)
             _, rgb8, _, noise = rend.accum_read(want_rgb8=True)
             print(f"{noise.spp_done}/{a.spp} noise {noise.noise:.4g}", file=sys.stderr)
-            save_png(file_name, rgb8)
+            if a.preview_every or not a.denoise:
+                save_png(file_name, rgb8)
             if noise.noise <= a.noise_target or noise.spp_done >= a.spp:
                 break
+        if a.denoise:
+            save_png(file_name, _denoised(a, rend))
         rend.accum_end()
     else:
         _, rgb8, _, noise, st = rend.render_to_noise(scene.camera, params, a.noise_target, a.spp_step, want_rgb8=True)
@@ -105,7 +116,25 @@ def render_to_noise(a, rend, scene, flags, file_name, t0):
         save_png(file_name, rgb8)
     print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
     print(f"{file_name}: {a.nx}x{a.ny}, {noise.spp_done} of at most {a.spp} spp, noise {noise.noise:.4g} (target {a.noise_target:g}), "
-          f"{n_rays} rays, {n_rays / seconds / 1e6:.0f} Mray/s on the device", file=sys.stderr)
+          f"{n_rays} rays, {n_rays / seconds / 1e6:.0f} Mray/s on the device{', denoised' if a.denoise else ''}", file=sys.stderr)
+    return 0
+
+
+def _denoised(a, rend):
+    return rend.accum_denoise(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
+
+
+def render_denoised(a, rend, scene, flags, file_name, t0):
+    """--denoise without --noise-target: begin, one add of --spp samples, the filter, end."""
+    rend.accum_begin(scene.camera, make_params(a.nx, a.ny, a.spp, max_depth=a.max_depth, seed=a.seed, flags=flags))
+    st = rend.accum_add(a.spp)
+    noise = rend.accum_read()[3]
+    rgb8 = _denoised(a, rend)
+    rend.accum_end()
+    print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
+    save_png(file_name, rgb8)
+    print(f"{file_name}: {a.nx}x{a.ny}, {a.spp} spp, noise {noise.noise:.4g} before the filter, denoised, {st.n_rays} rays, "
+          f"{st.n_rays / st.seconds_device / 1e6:.0f} Mray/s on the device", file=sys.stderr)
     return 0
 
 
