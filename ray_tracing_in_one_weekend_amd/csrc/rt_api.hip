@@ -8,6 +8,7 @@
 #include "rt_grid.h"
 #include "rt_pool.h"
 #include "rt_scene_prep.h"
+#include "rt_frame_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -40,7 +41,7 @@ struct DevBuf {
 struct RtCtx {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;            // second shard group of a slice (render_impl)
+    hipStream_t stream2 = nullptr;            // second shard group of a slice (enqueue_bounce)
     std::vector<hipStream_t> parked_streams;  // streams that turned out to share a hardware queue with the first chain's (ensure_concurrent_chains)
     hipStream_t paired_with = nullptr;        // the launch stream stream2 was last checked against
     bool chains_concurrent = true;            // what that check found (false: no stream of this process ran beside the launch stream)
@@ -90,7 +91,7 @@ struct RtCtx {
     uint32_t opt[RT_OPT__COUNT] = {}; // rt_debug_set_option: per context, every setting renders the same bits
     RtVariantLedger launched{};       // rt_debug_launched_variants: the table entries launch_* and rt_debug_bounce have launched (one thread drives a context)
     // Page-locked word for the one host decision inside a frame: how many pixels have more primary-ray candidates than a list
-    // holds (k_primary_lists counts them; render_impl reads the count back 0.1 ms into the frame).
+    // holds (k_primary_lists counts them; primary_lists reads the count back 0.1 ms into the frame).
     uint32_t* h_overflow = nullptr;
     long long last_overflow = -1; // that count for the last frame (rt_debug_render_parts); -1: it made no lists or did not read it
     RtLens lens{0.0f, 1.0f};      // rt_set_lens (lens_radius 0: the pinhole)
@@ -98,7 +99,7 @@ struct RtCtx {
     // rt_set_quads: the active search state is rebuilt over the scene's entries AND the set
     bool planar = false;           // the PLANAR instantiations (n > 0)
     GenPlanar gplanar{};           // (pq in quads_region)
-    double planar_reach = 0.0;     // RT_PLANAR_REACH W of the set: the leaf slack holds for ray origins within it (render_impl checks the camera)
+    double planar_reach = 0.0;     // RT_PLANAR_REACH W of the set: the leaf slack holds for ray origins within it (trace_samples checks the camera)
     DevBuf quads_region;
     // rt_set_lights: sampling targets for shade() only — no search structure knows them, so they live beside either search state
     bool lights = false;           // the LIGHTS instantiations of k_shade (n > 0)
@@ -114,7 +115,7 @@ struct RtCtx {
     // progressive preview (rt_set_progress): called from rt_render after every slice
     RtProgressFn progress_fn = nullptr;
     void* progress_user = nullptr;
-    bool progress_armed = false; // set by rt_render around render_impl, so rt_render_device stays callback-free
+    bool progress_armed = false; // set by rt_render around its frame, so rt_render_device stays callback-free
     DevBuf preview_u8;
     std::vector<uint8_t> preview_host;
     // rt_accum_*: at most one open accumulation per context.  It owns its running state — an f32 x 3 sum and an f64 x 2 luminance moment per
@@ -130,7 +131,7 @@ struct RtCtx {
     DevBuf accum_sum, accum_mom, accum_sem, accum_partials; // (accum_sem: staging of out_sem; accum_partials: one f64 pair per workgroup + the 3 frame figures)
     double* h_noise = nullptr;   // page-locked: mean_luminance, rms_sem, noise as k_noise_final wrote them
     DevBuf dn_c, dn_yv, dn_out;  // rt_accum_denoise: the filter's inputs (c 12 B, (y, v) 8 B) and its output (12 B) per pixel, in image order
-    // Host-side timeline of the last render_impl (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
+    // Host-side timeline of the last trace_samples and what its caller enqueued behind it (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
     // render of a process is where allocations, code-object loads and the queue probe happen; this says which.
     std::vector<std::pair<const char*, double>> parts;
     std::chrono::steady_clock::time_point parts_t{};
@@ -322,7 +323,7 @@ int ensure_concurrent_chains(RtCtx* ctx, hipStream_t st) {
     return rc;
 }
 
-// ---- the two trace-step launches (render_impl and the production-kernel test hook share them) ----------------
+// ---- the two trace-step launches (enqueue_bounce and the production-kernel test hook share them) ----------------
 struct StepBuffers {
     Queue qi, qo;
     float2* qhit;
@@ -447,7 +448,7 @@ int launch_intersect(RtCtx* ctx, hipStream_t sg, bool use_bvh, bool gen, uint32_
         return RT_OK;
     }
     unsigned k = 0;
-    if (gen) k |= IS_GEN;                                               // depth 0 with the primary rays made in the kernel (render_impl)
+    if (gen) k |= IS_GEN;                                               // depth 0 with the primary rays made in the kernel (enqueue_bounce)
     if (scene_is_general(ctx) || !ctx->search.bvh_in_lds || b.planar) k |= IS_RECTS; // general scene; trees that do not fit LDS use the general instantiation
                                                                         // (it works for sphere-only scenes too); planar primitives (rt_set_quads) likewise
     if (ctx->search.bvh_in_lds) k |= IS_LDS_NODES;                             // tree and geometry staged in LDS (rt_scene_upload), else read through L2
@@ -472,7 +473,7 @@ int launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32_
     const size_t shade_lds = shade_lds_bytes(ctx->search.ds.n_prims + ctx->search.ds.n_media + (b.planar ? ctx->gplanar.n : 0u), perlin_lds ? ctx->search.ds.n_perlin : 0u, n_fused, !gen && sp.sort);
     unsigned k = 0;
     if (perlin_lds) k |= SH_PERLIN_LDS;                              // the scene's Perlin tables fit LDS (scene_perlin_lds)
-    if (gen) k |= SH_GEN;                                            // depth 0 with the primary rays made in the kernel (render_impl)
+    if (gen) k |= SH_GEN;                                            // depth 0 with the primary rays made in the kernel (enqueue_bounce)
     if (scene_is_general(ctx) || b.planar) k |= SH_RECTS;            // general scene; planar primitives (rt_set_quads) are shaded by the general form
     if (has(k, SH_RECTS) && (ctx->nest || b.planar)) k |= SH_NEST;   // as launch_intersect
     if (gen && b.lens) k |= SH_LENS;                                 // depth 0 through the thin lens (rt_set_lens)
@@ -486,29 +487,7 @@ int launch_shade(RtCtx* ctx, hipStream_t sg, bool gen, bool fused_lists, uint32_
     return RT_OK;
 }
 
-// Where the work buffers of a slice lie in the pool: two ray queues of n_queue rays (a / b records interleaved when RT_QSTRIDE is
-// 2, a separate b array in the RT_QSTRIDE 1 build; the c array), n_queue hit records, n_paths radiance slots.
-struct WorkLayout {
-    size_t q_ab[2], q_b[2], q_c[2], qhit, rad, total;
-};
-WorkLayout work_layout(size_t n_queue, size_t n_paths) {
-    WorkLayout w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255u) & ~(size_t)255u;
-        return o;
-    };
-    for (int k = 0; k < 2; ++k) {
-        w.q_ab[k] = take(RT_QSTRIDE * n_queue * sizeof(float4));
-        w.q_b[k] = RT_QSTRIDE == 1u ? take(n_queue * sizeof(float4)) : w.q_ab[k] + sizeof(float4);
-        w.q_c[k] = take(n_queue * sizeof(float2));
-    }
-    w.qhit = take(n_queue * sizeof(float2));
-    w.rad = take(n_paths * RT_RAD_FLOATS * sizeof(float));
-    w.total = off;
-    return w;
-}
+// the work buffers of a slice (WorkLayout: rt_frame_plan.h) at `base` of the pool
 struct WorkView {
     Queue Q[2];
     float2* qhit;
@@ -522,16 +501,17 @@ WorkView work_view(const RtCtx* ctx, const WorkLayout& w, size_t base) {
     return v;
 }
 
-// Queue geometry of a slice of n_max rays: shard count, k_intersect grid, shard capacity.
+// Queue shards: one per k_shade workgroup (8 workgroups of 256 threads per CU), each owned by one
+// workgroup per kernel so that queue positions come from LDS counters (rt_kernels.h).
+uint32_t queue_shards(const RtCtx* ctx) { return ctx->opt[RT_OPT_QUEUE_SHARDS] ? ctx->opt[RT_OPT_QUEUE_SHARDS] : (uint32_t)ctx->n_cu * 8u; }
+
+// Queue geometry of a slice of n_max rays: shard count, k_intersect grid (the same for every n_max), shard capacity.
 struct QueueGeom {
     uint32_t nq, isect_grid, cap;
 };
 QueueGeom queue_geom(const RtCtx* ctx, uint32_t n_max) {
     QueueGeom g;
-    // Queue shards: one per k_shade workgroup (8 workgroups of 256 threads per CU), each owned by one
-    // workgroup per kernel so that queue positions come from LDS counters (rt_kernels.h).
-    g.nq = (uint32_t)ctx->n_cu * 8u;
-    if (ctx->opt[RT_OPT_QUEUE_SHARDS]) g.nq = ctx->opt[RT_OPT_QUEUE_SHARDS];
+    g.nq = queue_shards(ctx);
     // k_intersect: as many 1024-thread workgroups per CU as LDS admits (two at <= 64 VGPRs); every
     // workgroup owns nq / isect_grid shards
     const size_t isect_lds = grid_enabled(ctx) ? std::max(ctx->search.isect_lds, ctx->search.grid_lds) : ctx->search.isect_lds;
@@ -547,58 +527,38 @@ QueueGeom queue_geom(const RtCtx* ctx, uint32_t n_max) {
     if (ctx->opt[RT_OPT_ISECT_WORKGROUPS]) g.isect_grid = std::min(g.nq, ctx->opt[RT_OPT_ISECT_WORKGROUPS]);
     while ((g.nq + g.isect_grid - 1) / g.isect_grid > RT_ISECT_MAX_SHARDS) g.isect_grid *= 2;
     g.isect_grid = std::min(g.isect_grid, g.nq);
-    const uint32_t nchunks = (n_max + 255u) / 256u;
-    g.cap = ((nchunks + g.nq - 1) / g.nq) * 256u;
+    g.cap = shard_cap(g.nq, n_max);
     return g;
 }
 
-// ---- slice sizing (rt_prepare and render_impl) ----------------------------------------------------------------
-// A ray of a slice costs 100 B of work buffers (two 40 B queues, 8 B hit record, 12 B radiance slot).  Few, large slices amortise
-// the short-queue tail of the bounce loop (depths > ~12 hold a few thousand rays: config 2 measured 99 / 88 / 82 / 79.5 ms per
-// frame with 8 / 4 / 2 / 1 slices), so the library's own choice is up to 1 280 Mi rays (134 GB of the 288 GB HBM) and never more
-// than half of what the device has free.
-#ifndef RT_MAX_SLICE_MI_RAYS
-#define RT_MAX_SLICE_MI_RAYS 1280 // Mi rays of the largest slice the library chooses by itself (134 GB of work buffers).  640 until round 6:
-                                  // config 3 (4K, 1024 spp) in 7 slices instead of 13 is 1.6 % faster, config 5 1 % (the tail of a slice costs 3.7 ms)
-#endif
-uint32_t queue_shards(const RtCtx* ctx) { return ctx->opt[RT_OPT_QUEUE_SHARDS] ? ctx->opt[RT_OPT_QUEUE_SHARDS] : (uint32_t)ctx->n_cu * 8u; }
-size_t slice_bytes(const RtCtx* ctx, uint32_t npix, uint32_t sc) {
-    const uint32_t nq = queue_shards(ctx), n_max = npix * sc;
-    const uint32_t cap = (((n_max + 255u) / 256u + nq - 1u) / nq) * 256u; // (queue_geom's shard capacity)
-    return work_layout((size_t)nq * cap, n_max).total;
-}
-// the most samples per pixel (<= sc_max) whose slice fits `bytes`; 0 when not even one does
-uint32_t slice_fit(const RtCtx* ctx, uint32_t npix, size_t bytes, uint32_t sc_max) {
-    uint32_t sc = (uint32_t)std::min<uint64_t>(sc_max, bytes / (100ull * npix) + 1u);
-    while (sc > 0u && slice_bytes(ctx, npix, sc) > bytes) --sc;
-    return sc;
-}
-struct SlicePlan {
-    uint32_t S_cap;    // most samples per pixel a slice may hold
-    bool by_library;   // RtParams.spp_slice == 0: the library chose, and may start a frame with smaller slices while the pool grows
-    size_t want_bytes; // pool size that holds such a slice
-};
+// ---- slice sizing (rt_frame_plan.h) for rt_prepare, rt_accum_begin and trace_samples ----------------------------
 // (the work buffers of a slice start at work_base(ctx): behind the small persistent buffers carved from the pool so far)
 size_t work_base(const RtCtx* ctx) { return (ctx->arena_top + 4095u) & ~(size_t)4095u; }
-int plan_slices(RtCtx* ctx, const RtParams* prm, uint64_t npix64, SlicePlan& pl) {
-    const uint32_t spp = prm->spp;
-    uint32_t S = prm->spp_slice;
-    pl.by_library = S == 0u;
-    if (pl.by_library) S = (uint32_t)std::max<uint64_t>(1, ((uint64_t)RT_MAX_SLICE_MI_RAYS << 20) / npix64);
-    S = std::min(std::min(S, spp), 1u << 20); // udiv_inv (slot -> sample, pixel) wants quotients below 2^21
-    if ((uint64_t)S * npix64 > 0xFFFFFF00ull) S = (uint32_t)(0xFFFFFF00ull / npix64);
-    if (S == 0) return fail(ctx, RT_ERR_UNSUPPORTED, "render: shard has more than 2^32 pixels");
-    const uint32_t npix = (uint32_t)npix64;
-    if (pl.by_library) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t half = (free_b + ctx->pool.mapped.load()) / 2u, base = work_base(ctx);
-            if (base + slice_bytes(ctx, npix, S) > half) S = std::max(1u, slice_fit(ctx, npix, half > base ? half - base : 0u, S));
-        }
-    }
-    pl.S_cap = S;
-    pl.want_bytes = work_base(ctx) + slice_bytes(ctx, npix, S);
+// Plans the slices of a frame and asks the pool for what one of them takes, + `extra` bytes; `who` opens the error text of the pool.
+int request_slices(RtCtx* ctx, const RtParams* prm, uint64_t npix64, const char* who, size_t extra, SlicePlan& plan) {
+    size_t free_b = SIZE_MAX, total_b = 0; // (only a slice size the library chooses is held to what the device has free)
+    if (prm->spp_slice == 0u && hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = SIZE_MAX;
+    if (!plan_slice_size(*prm, npix64, queue_shards(ctx), free_b, ctx->pool.mapped.load(), work_base(ctx), plan))
+        return fail(ctx, RT_ERR_UNSUPPORTED, "render: shard has more than 2^32 pixels");
+    ctx->pool.chunk_delay_us.store(ctx->opt[RT_OPT_POOL_CHUNK_DELAY_US]);
+    if (const char* e = pool_request(ctx->pool, plan.want_bytes + extra)) return fail(ctx, RT_ERR_NOMEM, std::string(who) + ": " + e);
     return RT_OK;
+}
+
+int grow_events(RtCtx* ctx, std::vector<hipEvent_t>& events, size_t n) {
+    while (events.size() < n) {
+        hipEvent_t ev;
+        RT_HIP(ctx, hipEventCreate(&ev));
+        events.push_back(ev);
+    }
+    return RT_OK;
+}
+
+// parks the context's motion, planar set and light set behind the GenParams at gpd (disjoint bytes: gen_motion_of, gen_planar_of, gen_lights_of)
+void launch_sets(const RtCtx* ctx, hipStream_t st, GenParams* gpd) {
+    if (ctx->motion) hipLaunchKernelGGL(k_set_motion, dim3(1), dim3(64), 0, st, gpd, ctx->gmotion);
+    if (ctx->planar) hipLaunchKernelGGL(k_set_planar, dim3(1), dim3(64), 0, st, gpd, ctx->gplanar);
+    if (ctx->lights) hipLaunchKernelGGL(k_set_lights, dim3(1), dim3(64), 0, st, gpd, ctx->glights);
 }
 
 // Where the closest-hit search of the scene in sr.ds runs: tree in LDS or through L2, wrapper tables in LDS, a grid or none; fills the
@@ -772,13 +732,7 @@ void rt_ctx_destroy(RtCtx* ctx) {
 }
 
 uint32_t rt_shard_rows(uint32_t ny, uint32_t shard_band, uint32_t shard_count, uint32_t shard_id) {
-    if (shard_count <= 1) return ny;
-    if (shard_band == 0) shard_band = 1;
-    if (shard_id >= shard_count) return 0;
-    // rows j with (j / band) % count == id: `band` rows out of every cycle of band * count, plus what the last partial cycle holds
-    const uint64_t cycle = (uint64_t)shard_band * shard_count;
-    const uint64_t rem = ny % cycle, lo = (uint64_t)shard_id * shard_band;
-    return (uint32_t)((ny / cycle) * shard_band + (rem > lo ? std::min<uint64_t>(rem - lo, shard_band) : 0u));
+    return shard_rows(ny, shard_band, shard_count, shard_id);
 }
 
 uint32_t rt_shard_row_to_image_row(uint32_t local_row, uint32_t shard_band, uint32_t shard_count, uint32_t shard_id) {
@@ -882,21 +836,9 @@ static int check_params(RtCtx* ctx, const RtCamera* cam, const RtParams* p) {
     if (p->shard_count > 1 && p->shard_id >= p->shard_count) return fail(ctx, RT_ERR_INVALID, "render: shard_id >= shard_count");
     // slot -> (sample, row, column) goes through udiv_inv (rt_kernels.h), exact for quotients below 2^21: the sample index is
     // capped by the slice size, the row index by this
-    if (rt_shard_rows(p->ny, p->shard_band ? p->shard_band : 1u, p->shard_count, p->shard_id) >= (1u << 21))
+    if (shard_geom(*p).rows >= (1u << 21))
         return fail(ctx, RT_ERR_UNSUPPORTED, "render: a shard of 2^21 or more image rows is not supported");
     return RT_OK;
-}
-
-// Local pixel order of a shard's frame (rt_kernels.h GenParams): 8 x 8 pixel tiles per wave of depth 0 when the frame allows it.  A strip
-// of 64 x 1 pixels crosses more silhouettes than a block of 8 x 8, and at depth 0 a wave runs the union of what its lanes hit.  Frames are
-// bit-identical (keys and the resolve order are functions of (pixel, sample)).  sphere_scene: depth-0 shading 7.17 -> 6.67 ms
-// per 128 spp, frame 58.6 -> 57.4 ms; pbr_sweep_scene -1.5 %; cornell_box +-0; final_scene +1.7 % (its deeper bounces,
-// 42.0 -> 43.6 ms of k_intersect), so general scenes keep the rows (profiles/round3/ab_tiles.txt).
-static void pixel_order(const RtCtx* ctx, uint32_t nx, uint32_t rows, uint32_t& tiles_per_row, uint32_t& tile_pixels) {
-    const uint32_t po = ctx->opt[RT_OPT_PIXEL_ORDER]; // 1 = rows, 2 = tiles wherever the frame allows
-    const bool want_tiles = po ? po == 2u : !scene_is_general(ctx);
-    tiles_per_row = (nx % 8u == 0u && rows >= 8u && want_tiles) ? nx / 8u : 0u;
-    tile_pixels = tiles_per_row * 64u * (rows / 8u); // the last rows % 8 rows stay row-major
 }
 
 // Where the resolved samples of a call go.  The frame renderer (sum NULL): ctx->acc, cleared first, samples 0 .. spp - 1.  An accumulation
@@ -916,6 +858,215 @@ struct Traced {
     float* acc = nullptr; // the running sum the samples went to
 };
 
+// The decisions of a frame: functions of the context and the params, made before anything is enqueued.
+struct FrameDecisions {
+    bool use_bvh, fuse_gen, want_lists, lens, time_depths, one_chain, rects;
+    uint32_t nq, isect_grid, shards_per_wg, n_groups;
+};
+static FrameDecisions frame_decisions(const RtCtx* ctx, const RtParams* prm) {
+    FrameDecisions d;
+    const QueueGeom qg = queue_geom(ctx, 0u);
+    d.nq = qg.nq, d.isect_grid = qg.isect_grid;
+    d.use_bvh = ctx->search.use_bvh && !(prm->flags & RT_FLAG_BRUTE_FORCE);
+    // depth 0 regenerates the primary ray in both kernels instead of materialising the queue
+    d.fuse_gen = d.use_bvh && ctx->opt[RT_OPT_MATERIALISE_PRIMARIES] != 1u;
+    // Candidate lists of the primary rays, once per frame (k_primary_lists): worth it when the samples of a pixel
+    // share them (>= 4 spp) and pixels see few entries.  Measured per 128-spp slice: sphere_scene (533 entries)
+    // 46.7 -> 41.9 ms, pbr_sweep_scene 41.2 -> 39.3, test_sphere 15.5 -> 14.8, cornell_box unchanged (its walls'
+    // bounding spheres cover every pixel: overflow); final_scene (3 408 entries, most pixels overflow) would pay
+    // 3 ms for nothing, hence the cap.
+    d.want_lists = d.use_bvh && d.fuse_gen && prm->spp >= 4 && ctx->search.ds.n_entries > 0 && ctx->search.ds.n_entries <= 2048 && ctx->opt[RT_OPT_PRIMARY_LISTS] != 1u &&
+                   !ctx->planar; // (the lists know the static entries only)
+    d.lens = ctx->lens.lens_radius > 0.0f; // depth 0 through the thin lens: the LENS instantiations
+    d.time_depths = (prm->flags & RT_FLAG_TIME_DEPTHS) != 0;
+    // Two shard groups on two streams: k_intersect is bound by VALU issue and leaves HBM idle, k_shade past depth 0
+    // waits on HBM and leaves the VALUs idle (profiles/round2).  Each half of the shards runs its own chain
+    // intersect -> shade -> intersect ... on its own stream; the two chains drift apart because the kernels differ in
+    // length, and the dispatcher fills every CU with waves of both kinds.  Same kernels, same results; config 2 runs
+    // 2.2 % faster than with one chain over all shards (68.0 -> 66.5 ms; three, four and eight groups: 83 / 82 / 104 ms;
+    // forcing the two chains half a step apart with events, so that one always intersects while the other shades: 75 ms,
+    // half-size grids in lockstep).  The two half-grid launches of a depth run side by side, so a "launch" in RtStats is
+    // the logical one — one kernel, one depth, all shards — and rocprof shows each half lasting about that long.
+    // Per-depth timing needs the single chain.
+    // Scenes whose k_intersect waits on dependent loads like k_shade does — wrapper chains, media, a tree read through L2 —
+    // run ONE chain: two would only share the same pipes (final_scene 41.4 -> 39.3 ms, cornell_box 32.7 -> 30.8 ms per 64 spp
+    // with one; sphere_scene 18.0 -> 18.6, simple_light_scene's bare rectangles likewise prefer two:
+    // profiles/round3/one_stream.txt).  RT_OPT_CHAINS = 1 / 2 force either.
+    const uint32_t chains_opt = ctx->opt[RT_OPT_CHAINS];
+    d.one_chain = chains_opt ? chains_opt == 1u : (ctx->search.ds.n_xforms > 0 || ctx->search.ds.n_media > 0 || (d.use_bvh && !ctx->search.bvh_in_lds));
+    d.n_groups = (d.nq >= 2u * RT_ISECT_MAX_SHARDS && !d.time_depths && !d.one_chain) ? 2u : 1u;
+    d.shards_per_wg = (d.nq + d.isect_grid - 1u) / d.isect_grid;
+    // selects the "general scene" kernel instantiations (rectangles and Translate / RotateY wrappers)
+    d.rects = scene_is_general(ctx);
+    return d;
+}
+
+// A frame in flight: what the phases of trace_samples share.
+struct Frame {
+    FrameDecisions d;
+    hipStream_t st;
+    const RtParams* prm;
+    uint32_t npix;
+    int n_depths;
+    SlicePlan plan;
+    size_t wbase;         // the work buffers of every slice start here (work_base)
+    GenParams gp;         // (cap, s0, n_rays: of the current slice)
+    GenLens glens;
+    bool no_overflow;     // every pixel of this frame has a candidate list (read back from k_primary_lists)
+    GenParams* gpd;
+    float* acc;
+    uint32_t* counts;     // queue sizes [depth][shard]
+    size_t counts_bytes;
+    unsigned long long* totals; // [0]=tex fetches [1]=bad dirs [2..]=rays per depth
+    uint32_t n_trace_launches;
+};
+
+// Candidate lists of the primary rays, and the one host decision of a frame: f.no_overflow.
+static int primary_lists(RtCtx* ctx, Frame& f) {
+    const hipStream_t st = f.st;
+    f.gp.lists = (const uint4*)ctx->lists.p;
+    uint32_t* n_overflow = (uint32_t*)((uint4*)ctx->lists.p + f.npix);
+    f.gp.n_overflow = n_overflow;
+    RT_HIP(ctx, hipMemsetAsync(n_overflow, 0, sizeof(uint4), st));
+    const size_t lists_lds = (size_t)ctx->search.ds.n_entries * sizeof(float4) + 4u * RT_LIST_WAVE_CAP * 2u;
+    const auto make_lists = f.d.lens ? &k_primary_lists<true> : &k_primary_lists<false>;
+    hipLaunchKernelGGL(make_lists, dim3((f.npix + 255u) / 256u), dim3(256), lists_lds, st, ctx->search.ds, f.gp, (uint4*)ctx->lists.p, n_overflow, f.glens);
+    // The one host decision of a frame: with no overflowing list (every headline configuration) depth 0 of a sphere-only scene
+    // needs no closest-hit launch at all — k_shade<GEN> finds every hit from the lists.  An empty launch is not free: each of
+    // its workgroups waits for 66 KB of LDS behind the other chain's shading waves and holds its own chain's shading back
+    // (config 2: 1.6 ms of 47.6).  The count is there 0.1 ms into the frame; reading it costs one stream synchronisation while
+    // nothing else of the frame is enqueued yet, and the first frame of a view is as fast as any later one (the reference
+    // renders exactly one, main.rs:62-129).
+    if (!scene_is_general(ctx)) {
+        RT_HIP(ctx, hipMemcpyAsync(ctx->h_overflow, n_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        RT_HIP(ctx, hipStreamSynchronize(st));
+        f.no_overflow = *ctx->h_overflow == 0u;
+        ctx->last_overflow = *ctx->h_overflow;
+    }
+    ctx->mark("primary_lists_and_in_frame_sync");
+    return RT_OK;
+}
+
+// How many samples per pixel slice `sl` gets: as many as the plan allows (sc_max) and the pool holds NOW.  While the helper thread is
+// still backing the pool (the first frame of a process, rt_pool.h) a frame whose slice size the library chose starts with what is
+// mapped — at least 1/32 of its samples, one such slice ahead of the device at most — instead of waiting for the rest; slices are
+// independent and the frame is bit-identical for any slicing.  A slice size the caller asked for is waited for.
+static int slice_samples(RtCtx* ctx, const Frame& f, uint32_t sl, uint32_t sc_max, uint32_t& sc, double& pool_wait_ms) {
+    const uint32_t nq = f.d.nq, npix = f.npix;
+    const uint32_t S_progress = std::min(f.plan.S_cap, std::max(1u, (f.prm->spp + 31u) / 32u));
+    for (;;) {
+        const size_t mapped = ctx->pool.mapped.load();
+        const uint32_t fits = slice_fit(nq, npix, mapped > f.wbase ? mapped - f.wbase : 0u, sc_max);
+        if (fits >= sc_max) { sc = sc_max; break; }
+        const bool growing = pool_growing(ctx->pool);
+        if (!growing) { // the device had no more to give: the frame takes more slices; nothing at all is an error
+            if (ctx->pool.mapped.load() != mapped) continue;
+            if (fits == 0u) return fail(ctx, RT_ERR_NOMEM, "render: no device memory for the work buffers of one sample per pixel (" +
+                                                                std::to_string(slice_bytes(nq, npix, 1u) >> 20) + " MB): " + pool_error(ctx->pool));
+            sc = fits;
+            break;
+        }
+        // one small slice ahead of the device at most: the next is cut when the device is about to run dry
+        const bool device_idle = sl == 0u || hipEventQuery(ctx->events[2 * (size_t)sl - 1]) == hipSuccess;
+        if (f.plan.by_library && fits >= std::min(S_progress, sc_max) && device_idle) { sc = fits; break; }
+        const auto tw = std::chrono::steady_clock::now();
+        pool_wait_progress(ctx->pool, mapped, 200u);
+        pool_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
+    }
+    (void)hipGetLastError(); // (hipEventQuery: hipErrorNotReady is not an error)
+    return RT_OK;
+}
+
+// One bounce of one shard group of slice `sl`: closest hit, then shading, on the group's stream.
+static int enqueue_bounce(RtCtx* ctx, Frame& f, const WorkView& wv, uint32_t sl, int depth, uint32_t grp) {
+    const FrameDecisions& d = f.d;
+    const uint32_t nq = d.nq;
+    hipStream_t st = f.st, sg = grp ? ctx->stream2 : st;
+    const uint32_t q0 = grp * (nq / d.n_groups), q1 = grp + 1u == d.n_groups ? nq : q0 + nq / d.n_groups;
+    const uint32_t isect_grid_g = (q1 - q0 + d.shards_per_wg - 1u) / d.shards_per_wg;
+    const Queue& qi = wv.Q[depth & 1];
+    const Queue& qo = wv.Q[(depth + 1) & 1];
+    const uint32_t* cin = f.counts + (size_t)depth * nq;
+    uint32_t* cout = f.counts + (size_t)(depth + 1) * nq;
+    const bool td = d.time_depths && sl == 0;
+    int rc;
+    if (td) RT_HIP(ctx, hipEventRecord(ctx->depth_events[3 * (size_t)depth], st));
+    const bool gen = d.fuse_gen && depth == 0;
+    const IntersectParams ip{nq, f.gp.cap, depth, q0, q1};
+    const StepBuffers sb{qi, qo, wv.qhit, cin, cout, wv.rad, f.totals, f.gpd, d.lens, ctx->motion, ctx->planar, ctx->lights};
+    // depth 0 of a sphere-only scene whose pixels all have a candidate list: k_shade<GEN> finds every closest hit itself
+    const bool no_primary_trace = gen && !d.rects && f.gp.lists != nullptr && f.no_overflow;
+    if (!no_primary_trace && (rc = launch_intersect(ctx, sg, d.use_bvh, gen, isect_grid_g, sb, ip))) return rc;
+    if (td) RT_HIP(ctx, hipEventRecord(ctx->depth_events[3 * (size_t)depth + 1], st));
+    // class sort from depth 1 on: primary rays are coherent already (measured: sorting depth 0 costs 8 %)
+    const ShadeParams sp{nq, f.gp.cap, depth, f.prm->max_depth, depth > 0 ? 1u : 0u,
+                         (f.prm->flags & RT_FLAG_RUSSIAN_ROULETTE) ? 1u : 0u, q0};
+    if ((rc = launch_shade(ctx, sg, gen, !d.rects && f.gp.lists != nullptr, q1 - q0, sb, sp))) return rc;
+    if (td) RT_HIP(ctx, hipEventRecord(ctx->depth_events[3 * (size_t)depth + 2], st));
+    if (grp == 0u) f.n_trace_launches += no_primary_trace ? 1u : 2u;
+    return RT_OK;
+}
+
+// Enqueues slice `sl` (f.gp holds its cap, s0 and n_rays): counters and primaries, then every depth of every shard group — without
+// any host synchronisation but the read-back of a timed frame — between the slice's two events.
+static int enqueue_slice(RtCtx* ctx, Frame& f, const WorkView& wv, uint32_t sl) {
+    const FrameDecisions& d = f.d;
+    const hipStream_t st = f.st;
+    int rc = grow_events(ctx, ctx->events, 2 * (size_t)(sl + 1u));
+    if (rc) return rc;
+    RT_HIP(ctx, hipMemsetAsync(f.counts, 0, f.counts_bytes, st));
+    launch_sets(ctx, st, f.gpd);
+    const auto init_counts = d.lens ? &k_init_counts<true> : &k_init_counts<false>;
+    hipLaunchKernelGGL(init_counts, dim3((d.nq + 255u) / 256u), dim3(256), 0, st, f.gp, f.counts, f.gpd, f.glens);
+    const auto gen_primaries = d.lens ? &k_gen_primary<true> : &k_gen_primary<false>;
+    if (!d.fuse_gen) hipLaunchKernelGGL(gen_primaries, dim3((f.gp.n_rays + 255u) / 256u), dim3(256), 0, st, f.gp, wv.Q[0], f.glens);
+    RT_HIP(ctx, hipEventRecord(ctx->events[2 * sl], st));
+    if (d.n_groups > 1u) {
+        RT_HIP(ctx, hipEventRecord(ctx->ev_fork, st));
+        RT_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+    }
+    // (Starting the second chain k depths behind the first — one wait on the first chain's depth-k shading, then free —
+    // so that the chains are in different phases: config 2 62.9 ms -> 69.6 / 71.4 / 71.0 / 72.9 ms for k = 0 / 1 / 2 / 4,
+    // profiles/round3/stagger_sphere_scene.txt.  The chains do best side by side.)
+    for (int depth = 0; depth < f.n_depths; ++depth)
+        for (uint32_t grp = 0; grp < d.n_groups; ++grp)
+            if ((rc = enqueue_bounce(ctx, f, wv, sl, depth, grp))) return rc;
+    if (d.n_groups > 1u) {
+        RT_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
+        RT_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
+    }
+    if (d.time_depths && sl == 0) {
+        const int n_depths = f.n_depths;
+        ctx->timed_depths = n_depths;
+        ctx->timed_rays.assign((size_t)n_depths, 0ull);
+        std::vector<uint32_t> hc((size_t)(n_depths + 1) * d.nq);
+        RT_HIP(ctx, hipMemcpyAsync(hc.data(), f.counts, hc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        RT_HIP(ctx, hipStreamSynchronize(st));
+        for (int k = 0; k < n_depths; ++k)
+            for (uint32_t q = 0; q < d.nq; ++q) ctx->timed_rays[(size_t)k] += hc[(size_t)k * d.nq + q];
+    }
+    RT_HIP(ctx, hipEventRecord(ctx->events[2 * sl + 1], st));
+    return RT_OK;
+}
+
+// Resolves the slice's `sc` samples per pixel onto the running sum, in sample order, and shows the `done` of `spp` samples so far to
+// the progress callback.
+static int resolve_and_preview(RtCtx* ctx, const Frame& f, const SampleSink& sink, const float* rad, uint32_t sc, uint32_t done, uint32_t rows) {
+    const hipStream_t st = f.st;
+    const uint32_t npix = f.npix, spp = f.prm->spp, nx = f.prm->nx;
+    if (sink.mom) hipLaunchKernelGGL(k_resolve_moments, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, npix, sc);
+    else hipLaunchKernelGGL(k_resolve, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, npix, sc);
+    hipLaunchKernelGGL(k_accum_counts, dim3((unsigned)f.n_depths), dim3(256), 0, st, f.counts, f.d.nq, (uint32_t)f.n_depths, f.totals + 2);
+    if (ctx->progress_armed && ctx->progress_fn && done < spp) { // the last slice is the final image itself
+        hipLaunchKernelGGL(k_finalize, dim3((npix + 255u) / 256u), dim3(256), 0, st, f.acc, (float*)nullptr,
+                           (uint8_t*)ctx->preview_u8.p, nx, rows, done, f.gp.tiles_per_row, f.gp.tile_pixels);
+        RT_HIP(ctx, hipMemcpyAsync(ctx->preview_host.data(), ctx->preview_u8.p, (size_t)npix * 3, hipMemcpyDeviceToHost, st));
+        RT_HIP(ctx, hipStreamSynchronize(st));
+        ctx->progress_fn(ctx->progress_user, done, spp, ctx->preview_host.data(), nx, rows);
+    }
+    return RT_OK;
+}
+
 // Traces prm->spp samples of every pixel of the shard in slices, with the production kernels, and resolves them onto `sink` in sample
 // order.  Everything of a frame but its last three steps (k_finalize, the copies to the host, the statistics): rt_render,
 // rt_render_device and rt_accum_add share it.  ctx->ev_begin is recorded; the caller records ctx->ev_end.  npix 0: nothing to do.
@@ -931,254 +1082,56 @@ static int trace_samples(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, v
     }
     RT_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream_v ? (hipStream_t)stream_v : ctx->stream;
-    const auto wall0 = std::chrono::steady_clock::now();
+    tr = Traced{};
+    tr.st = st, tr.wall0 = std::chrono::steady_clock::now();
     ctx->parts_begin();
     ctx->last_overflow = -1;
-
-    const uint32_t nx = prm->nx, ny = prm->ny, spp = prm->spp;
-    const uint32_t band = prm->shard_band ? prm->shard_band : 1u;
-    const uint32_t scount = prm->shard_count <= 1 ? 1u : prm->shard_count;
-    const uint32_t rows = rt_shard_rows(ny, band, scount, prm->shard_id);
-    const uint64_t npix64 = (uint64_t)rows * nx;
-    tr = Traced{};
-    tr.st = st, tr.wall0 = wall0;
-    if (npix64 == 0) return RT_OK;
-    const uint32_t npix = (uint32_t)npix64;
-    const int n_depths = prm->max_depth + 1;
-    const uint32_t nq = queue_shards(ctx);
-    const bool use_bvh = ctx->search.use_bvh && !(prm->flags & RT_FLAG_BRUTE_FORCE);
-    // depth 0 regenerates the primary ray in both kernels instead of materialising the queue
-    const bool fuse_gen = use_bvh && ctx->opt[RT_OPT_MATERIALISE_PRIMARIES] != 1u;
-    // Candidate lists of the primary rays, once per frame (k_primary_lists): worth it when the samples of a pixel
-    // share them (>= 4 spp) and pixels see few entries.  Measured per 128-spp slice: sphere_scene (533 entries)
-    // 46.7 -> 41.9 ms, pbr_sweep_scene 41.2 -> 39.3, test_sphere 15.5 -> 14.8, cornell_box unchanged (its walls'
-    // bounding spheres cover every pixel: overflow); final_scene (3 408 entries, most pixels overflow) would pay
-    // 3 ms for nothing, hence the cap.
-    const bool want_lists = use_bvh && fuse_gen && spp >= 4 && ctx->search.ds.n_entries > 0 && ctx->search.ds.n_entries <= 2048 && ctx->opt[RT_OPT_PRIMARY_LISTS] != 1u &&
-                            !ctx->planar; // (the lists know the static entries only)
+    const ShardGeom sh = shard_geom(*prm);
+    if (sh.npix64 == 0) return RT_OK;
+    const uint32_t npix = (uint32_t)sh.npix64, spp = prm->spp;
+    Frame f{};
+    f.d = frame_decisions(ctx, prm), f.st = st, f.prm = prm, f.npix = npix, f.n_depths = prm->max_depth + 1;
+    const uint32_t nq = f.d.nq;
 
     // the small persistent buffers first (they lie at the bottom of the pool); the work buffers of the slices start above them
-    ctx->pool.chunk_delay_us.store(ctx->opt[RT_OPT_POOL_CHUNK_DELAY_US]);
+    ctx->pool.chunk_delay_us.store(ctx->opt[RT_OPT_POOL_CHUNK_DELAY_US]); // (before request_slices: carving the small buffers grows the pool too)
     if (!sink.sum && (rc = ensure(ctx, ctx->acc, (size_t)npix * 3 * sizeof(float)))) return rc;
-    const size_t counts_bytes = (size_t)(n_depths + 1) * nq * sizeof(uint32_t); // queue sizes [depth][shard]
-    if ((rc = ensure(ctx, ctx->counts, counts_bytes))) return rc;
-    const size_t totals_bytes = (size_t)(n_depths + 2) * sizeof(unsigned long long);
+    f.counts_bytes = (size_t)(f.n_depths + 1) * nq * sizeof(uint32_t);
+    if ((rc = ensure(ctx, ctx->counts, f.counts_bytes))) return rc;
+    const size_t totals_bytes = (size_t)(f.n_depths + 2) * sizeof(unsigned long long);
     if ((rc = ensure(ctx, ctx->totals, totals_bytes))) return rc;
     if ((rc = ensure(ctx, ctx->genp, sizeof(GenParams) + RT_LIGHTS_OFFSET + sizeof(GenLights)))) return rc; // (the lens, the motion, the planar set and the light set behind the params: gen_lens_of, gen_motion_of, gen_planar_of, gen_lights_of)
-    if (want_lists &&(rc = ensure(ctx, ctx->lists, ((size_t)npix + 1u) * sizeof(uint4)))) return rc; // + the overflow counter behind the lists
-    GenParams* gpd = (GenParams*)ctx->genp.p;
-    float* acc = sink.sum ? sink.sum : (float*)ctx->acc.p;
-    uint32_t* counts = (uint32_t*)ctx->counts.p;
-    unsigned long long* totals = (unsigned long long*)ctx->totals.p; // [0]=tex fetches [1]=bad dirs [2..]=rays per depth
-    SlicePlan plan;
-    if ((rc = plan_slices(ctx, prm, npix64, plan))) return rc;
-    if (const char* e = pool_request(ctx->pool, plan.want_bytes)) return fail(ctx, RT_ERR_NOMEM, std::string("render: ") + e);
-    const size_t wbase = work_base(ctx);
-    const uint32_t isect_grid = queue_geom(ctx, npix * plan.S_cap).isect_grid;
+    if (f.d.want_lists && (rc = ensure(ctx, ctx->lists, ((size_t)npix + 1u) * sizeof(uint4)))) return rc; // + the overflow counter behind the lists
+    f.gpd = (GenParams*)ctx->genp.p, f.counts = (uint32_t*)ctx->counts.p, f.totals = (unsigned long long*)ctx->totals.p;
+    f.acc = sink.sum ? sink.sum : (float*)ctx->acc.p;
+    if ((rc = request_slices(ctx, prm, sh.npix64, "render", 0u, f.plan))) return rc;
+    f.wbase = work_base(ctx);
     ctx->mark("small_buffers_and_pool_request");
 
     // (before the frame's own clock starts: once per launch stream, 0.3 ms of spin kernels; see ensure_concurrent_chains)
     if (nq >= 2u * RT_ISECT_MAX_SHARDS && (rc = ensure_concurrent_chains(ctx, st))) return rc;
     ctx->mark("queue_probe"); // (the first kernel launch of a process: the code object is loaded here)
     RT_HIP(ctx, hipEventRecord(ctx->ev_begin, st));
-    if (!sink.sum) RT_HIP(ctx, hipMemsetAsync(acc, 0, (size_t)npix * 3 * sizeof(float), st));
-    RT_HIP(ctx, hipMemsetAsync(totals, 0, totals_bytes, st));
-
-    GenParams gp{};
-    for (int k = 0; k < 3; ++k) {
-        gp.cam_origin[k] = cam->origin[k];
-        gp.cam_horizontal[k] = cam->horizontal[k];
-        gp.cam_vertical[k] = cam->vertical[k];
-        gp.cam_llc[k] = cam->lower_left_corner[k];
-    }
-    gp.nx = nx, gp.ny = ny, gp.npix = npix;
-    gp.shard_band = band, gp.shard_count = scount, gp.shard_id = prm->shard_id;
-    gp.nq = nq, gp.cap = 0u; // (cap: per slice)
-    gp.seed_lo = (uint32_t)prm->seed, gp.seed_hi = (uint32_t)(prm->seed >> 32);
-    gp.lists = nullptr;
-    gp.n_overflow = nullptr;
-    const bool lens = ctx->lens.lens_radius > 0.0f; // depth 0 through the thin lens: the LENS instantiations
-    const GenLens glens = lens ? host_gen_lens(cam, ctx->lens) : GenLens{};
-    bool no_overflow = false; // every pixel of this frame has a candidate list (read back from k_primary_lists below)
-    {   // udiv_inv: reciprocals that keep the float quotient at or below the true one
-        auto inv = [](uint32_t d) { return (float)((1.0 / (double)d) * (1.0 - 1.0 / 4194304.0)); };
-        gp.inv_npix = inv(npix), gp.inv_nx = inv(nx), gp.inv_band = inv(band);
-        pixel_order(ctx, nx, rows, gp.tiles_per_row, gp.tile_pixels);
-        gp.inv_tpr = gp.tiles_per_row ? inv(gp.tiles_per_row) : 0.0f;
-    }
-    if (want_lists) {
-        gp.lists = (const uint4*)ctx->lists.p;
-        uint32_t* n_overflow = (uint32_t*)((uint4*)ctx->lists.p + npix);
-        gp.n_overflow = n_overflow;
-        RT_HIP(ctx, hipMemsetAsync(n_overflow, 0, sizeof(uint4), st));
-        const size_t lists_lds = (size_t)ctx->search.ds.n_entries * sizeof(float4) + 4u * RT_LIST_WAVE_CAP * 2u;
-        if (lens)
-            hipLaunchKernelGGL(k_primary_lists<true>, dim3((npix + 255u) / 256u), dim3(256), lists_lds, st, ctx->search.ds, gp, (uint4*)ctx->lists.p, n_overflow, glens);
-        else
-            hipLaunchKernelGGL(k_primary_lists<false>, dim3((npix + 255u) / 256u), dim3(256), lists_lds, st, ctx->search.ds, gp, (uint4*)ctx->lists.p, n_overflow, glens);
-        // The one host decision of a frame: with no overflowing list (every headline configuration) depth 0 of a sphere-only scene
-        // needs no closest-hit launch at all — k_shade<GEN> finds every hit from the lists.  An empty launch is not free: each of
-        // its workgroups waits for 66 KB of LDS behind the other chain's shading waves and holds its own chain's shading back
-        // (config 2: 1.6 ms of 47.6).  The count is there 0.1 ms into the frame; reading it costs one stream synchronisation while
-        // nothing else of the frame is enqueued yet, and the first frame of a view is as fast as any later one (the reference
-        // renders exactly one, main.rs:62-129).
-        if (!scene_is_general(ctx)) {
-            RT_HIP(ctx, hipMemcpyAsync(ctx->h_overflow, n_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            RT_HIP(ctx, hipStreamSynchronize(st));
-            no_overflow = *ctx->h_overflow == 0u;
-            ctx->last_overflow = *ctx->h_overflow;
-        }
-        ctx->mark("primary_lists_and_in_frame_sync");
-    }
-
-    uint32_t n_trace_launches = 0;
-    const bool time_depths = (prm->flags & RT_FLAG_TIME_DEPTHS) != 0;
+    if (!sink.sum) RT_HIP(ctx, hipMemsetAsync(f.acc, 0, (size_t)npix * 3 * sizeof(float), st));
+    RT_HIP(ctx, hipMemsetAsync(f.totals, 0, totals_bytes, st));
+    f.gp = frame_gen_params(*cam, *prm, sh, nq, pixel_order(ctx->opt[RT_OPT_PIXEL_ORDER], scene_is_general(ctx), prm->nx, sh.rows));
+    f.glens = f.d.lens ? host_gen_lens(cam, ctx->lens) : GenLens{};
+    if (f.d.want_lists && (rc = primary_lists(ctx, f))) return rc;
     ctx->timed_depths = 0;
-    if (time_depths) {
-        while (ctx->depth_events.size() < 3 * (size_t)n_depths) {
-            hipEvent_t ev;
-            RT_HIP(ctx, hipEventCreate(&ev));
-            ctx->depth_events.push_back(ev);
-        }
-    }
-    IntersectParams ip{nq, 0u, 0, 0u, nq};
-    // Two shard groups on two streams: k_intersect is bound by VALU issue and leaves HBM idle, k_shade past depth 0
-    // waits on HBM and leaves the VALUs idle (profiles/round2).  Each half of the shards runs its own chain
-    // intersect -> shade -> intersect ... on its own stream; the two chains drift apart because the kernels differ in
-    // length, and the dispatcher fills every CU with waves of both kinds.  Same kernels, same results; config 2 runs
-    // 2.2 % faster than with one chain over all shards (68.0 -> 66.5 ms; three, four and eight groups: 83 / 82 / 104 ms;
-    // forcing the two chains half a step apart with events, so that one always intersects while the other shades: 75 ms,
-    // half-size grids in lockstep).  The two half-grid launches of a depth run side by side, so a "launch" in RtStats is
-    // the logical one — one kernel, one depth, all shards — and rocprof shows each half lasting about that long.
-    // Per-depth timing needs the single chain.
-    // Scenes whose k_intersect waits on dependent loads like k_shade does — wrapper chains, media, a tree read through L2 —
-    // run ONE chain: two would only share the same pipes (final_scene 41.4 -> 39.3 ms, cornell_box 32.7 -> 30.8 ms per 64 spp
-    // with one; sphere_scene 18.0 -> 18.6, simple_light_scene's bare rectangles likewise prefer two:
-    // profiles/round3/one_stream.txt).  RT_OPT_CHAINS = 1 / 2 force either.
-    const uint32_t chains_opt = ctx->opt[RT_OPT_CHAINS];
-    const bool one_chain = chains_opt ? chains_opt == 1u : (ctx->search.ds.n_xforms > 0 || ctx->search.ds.n_media > 0 || (use_bvh && !ctx->search.bvh_in_lds));
-    const uint32_t n_groups = (nq >= 2u * RT_ISECT_MAX_SHARDS && !time_depths && !one_chain) ? 2u : 1u;
-    const uint32_t shards_per_wg = (nq + isect_grid - 1u) / isect_grid;
-    // selects the "general scene" kernel instantiations (rectangles and Translate / RotateY wrappers)
-    const bool rects = scene_is_general(ctx);
-    // Slices: as many samples per pixel as the plan allows and the pool holds NOW.  While the helper thread is still backing the
-    // pool (the first frame of a process, rt_pool.h) a frame whose slice size the library chose starts with what is mapped — at
-    // least 1/32 of its samples, one such slice ahead of the device at most — instead of waiting for the rest; slices are
-    // independent and the frame is bit-identical for any slicing.  A slice size the caller asked for is waited for.
-    uint32_t n_slices = 0, s0 = 0;
-    const uint32_t S_progress = std::min(plan.S_cap, std::max(1u, (spp + 31u) / 32u));
+    if (f.d.time_depths && (rc = grow_events(ctx, ctx->depth_events, 3 * (size_t)f.n_depths))) return rc;
+
+    uint32_t n_slices = 0;
     double pool_wait_ms = 0.0;
-    while (s0 < spp) {
-        const uint32_t sl = n_slices;
-        const uint32_t sc_max = std::min(plan.S_cap, spp - s0);
-        uint32_t sc = 0;
-        for (;;) {
-            const size_t mapped = ctx->pool.mapped.load();
-            const uint32_t fits = slice_fit(ctx, npix, mapped > wbase ? mapped - wbase : 0u, sc_max);
-            if (fits >= sc_max) { sc = sc_max; break; }
-            const bool growing = pool_growing(ctx->pool);
-            if (!growing) { // the device had no more to give: the frame takes more slices; nothing at all is an error
-                if (ctx->pool.mapped.load() != mapped) continue;
-                if (fits == 0u) return fail(ctx, RT_ERR_NOMEM, "render: no device memory for the work buffers of one sample per pixel (" +
-                                                                    std::to_string(slice_bytes(ctx, npix, 1u) >> 20) + " MB): " + pool_error(ctx->pool));
-                sc = fits;
-                break;
-            }
-            // one small slice ahead of the device at most: the next is cut when the device is about to run dry
-            const bool device_idle = sl == 0u || hipEventQuery(ctx->events[2 * (size_t)sl - 1]) == hipSuccess;
-            if (plan.by_library && fits >= std::min(S_progress, sc_max) && device_idle) { sc = fits; break; }
-            const auto tw = std::chrono::steady_clock::now();
-            pool_wait_progress(ctx->pool, mapped, 200u);
-            pool_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
-        }
-        (void)hipGetLastError(); // (hipEventQuery: hipErrorNotReady is not an error)
-        const uint32_t n_max = npix * sc;
-        const uint32_t cap = queue_geom(ctx, n_max).cap;
-        const WorkView wv = work_view(ctx, work_layout((size_t)nq * cap, n_max), wbase);
-        const Queue* Q = wv.Q;
-        float2* qhit = wv.qhit;
-        float* rad = wv.rad;
-        gp.cap = cap, ip.cap = cap;
-        while (ctx->events.size() < 2 * (size_t)(sl + 1u)) {
-            hipEvent_t ev;
-            RT_HIP(ctx, hipEventCreate(&ev));
-            ctx->events.push_back(ev);
-        }
-        ++n_slices;
-        gp.s0 = sink.first_sample + s0;
-        gp.n_rays = npix * sc;
-        RT_HIP(ctx, hipMemsetAsync(counts, 0, counts_bytes, st));
-        if (ctx->motion) hipLaunchKernelGGL(k_set_motion, dim3(1), dim3(64), 0, st, gpd, ctx->gmotion);
-        if (ctx->planar) hipLaunchKernelGGL(k_set_planar, dim3(1), dim3(64), 0, st, gpd, ctx->gplanar);
-        if (ctx->lights) hipLaunchKernelGGL(k_set_lights, dim3(1), dim3(64), 0, st, gpd, ctx->glights);
-        if (lens) hipLaunchKernelGGL(k_init_counts<true>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, gpd, glens);
-        else hipLaunchKernelGGL(k_init_counts<false>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, gpd, glens);
-        if (!fuse_gen && lens) hipLaunchKernelGGL(k_gen_primary<true>, dim3((gp.n_rays + 255u) / 256u), dim3(256), 0, st, gp, Q[0], glens);
-        else if (!fuse_gen) hipLaunchKernelGGL(k_gen_primary<false>, dim3((gp.n_rays + 255u) / 256u), dim3(256), 0, st, gp, Q[0], glens);
-        RT_HIP(ctx, hipEventRecord(ctx->events[2 * sl], st));
-        if (n_groups > 1u) {
-            RT_HIP(ctx, hipEventRecord(ctx->ev_fork, st));
-            RT_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        }
-        // (Starting the second chain k depths behind the first — one wait on the first chain's depth-k shading, then free —
-        // so that the chains are in different phases: config 2 62.9 ms -> 69.6 / 71.4 / 71.0 / 72.9 ms for k = 0 / 1 / 2 / 4,
-        // profiles/round3/stagger_sphere_scene.txt.  The chains do best side by side.)
-        for (int depth = 0; depth < n_depths; ++depth)
-        for (uint32_t grp = 0; grp < n_groups; ++grp) {
-            hipStream_t sg = grp ? ctx->stream2 : st;
-            const uint32_t q0 = grp * (nq / n_groups), q1 = grp + 1u == n_groups ? nq : q0 + nq / n_groups;
-            const uint32_t isect_grid_g = (q1 - q0 + shards_per_wg - 1u) / shards_per_wg;
-            const Queue& qi = Q[depth & 1];
-            const Queue& qo = Q[(depth + 1) & 1];
-            const uint32_t* cin = counts + (size_t)depth * nq;
-            uint32_t* cout = counts + (size_t)(depth + 1) * nq;
-            const bool td = time_depths && sl == 0;
-            if (td) RT_HIP(ctx, hipEventRecord(ctx->depth_events[3 * (size_t)depth], st));
-            const bool gen = fuse_gen && depth == 0;
-            ip.depth = depth;
-            ip.q0 = q0, ip.q1 = q1;
-            const StepBuffers sb{qi, qo, qhit, cin, cout, rad, totals, gpd, lens, ctx->motion, ctx->planar, ctx->lights};
-            // depth 0 of a sphere-only scene whose pixels all have a candidate list: k_shade<GEN> finds every closest hit itself
-            const bool no_primary_trace = gen && !rects && gp.lists != nullptr && no_overflow;
-            if (!no_primary_trace && (rc = launch_intersect(ctx, sg, use_bvh, gen, isect_grid_g, sb, ip))) return rc;
-            if (td) RT_HIP(ctx, hipEventRecord(ctx->depth_events[3 * (size_t)depth + 1], st));
-            // class sort from depth 1 on: primary rays are coherent already (measured: sorting depth 0 costs 8 %)
-            const ShadeParams sp{nq, cap, depth, prm->max_depth, depth > 0 ? 1u : 0u,
-                                 (prm->flags & RT_FLAG_RUSSIAN_ROULETTE) ? 1u : 0u, q0};
-            if ((rc = launch_shade(ctx, sg, gen, !rects && gp.lists != nullptr, q1 - q0, sb, sp))) return rc;
-            if (td) RT_HIP(ctx, hipEventRecord(ctx->depth_events[3 * (size_t)depth + 2], st));
-            if (grp == 0u) n_trace_launches += no_primary_trace ? 1u : 2u;
-        }
-        if (n_groups > 1u) {
-            RT_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-            RT_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
-        }
-        if (time_depths && sl == 0) {
-            ctx->timed_depths = n_depths;
-            ctx->timed_rays.assign((size_t)n_depths, 0ull);
-            std::vector<uint32_t> hc((size_t)(n_depths + 1) * nq);
-            RT_HIP(ctx, hipMemcpyAsync(hc.data(), counts, hc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            RT_HIP(ctx, hipStreamSynchronize(st));
-            for (int d = 0; d < n_depths; ++d)
-                for (uint32_t k = 0; k < nq; ++k) ctx->timed_rays[(size_t)d] += hc[(size_t)d * nq + k];
-        }
-        RT_HIP(ctx, hipEventRecord(ctx->events[2 * sl + 1], st));
-        if (sink.mom) hipLaunchKernelGGL(k_resolve_moments, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, acc, sink.mom, npix, sc);
-        else hipLaunchKernelGGL(k_resolve, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, acc, npix, sc);
-        hipLaunchKernelGGL(k_accum_counts, dim3((unsigned)n_depths), dim3(256), 0, st, counts, nq, (uint32_t)n_depths, totals + 2);
-        if (ctx->progress_armed && ctx->progress_fn && s0 + sc < spp) { // the last slice is the final image itself
-            const uint32_t done = s0 + sc;
-            hipLaunchKernelGGL(k_finalize, dim3((npix + 255u) / 256u), dim3(256), 0, st, acc, (float*)nullptr,
-                               (uint8_t*)ctx->preview_u8.p, nx, rows, done, gp.tiles_per_row, gp.tile_pixels);
-            RT_HIP(ctx, hipMemcpyAsync(ctx->preview_host.data(), ctx->preview_u8.p, (size_t)npix * 3, hipMemcpyDeviceToHost, st));
-            RT_HIP(ctx, hipStreamSynchronize(st));
-            ctx->progress_fn(ctx->progress_user, done, spp, ctx->preview_host.data(), nx, rows);
-        }
-        s0 += sc;
+    for (uint32_t s0 = 0, sc = 0; s0 < spp; s0 += sc, ++n_slices) {
+        if ((rc = slice_samples(ctx, f, n_slices, std::min(f.plan.S_cap, spp - s0), sc, pool_wait_ms))) return rc;
+        f.gp.n_rays = npix * sc, f.gp.s0 = sink.first_sample + s0, f.gp.cap = shard_cap(nq, f.gp.n_rays);
+        const WorkView wv = work_view(ctx, work_layout((size_t)nq * f.gp.cap, f.gp.n_rays), f.wbase);
+        if ((rc = enqueue_slice(ctx, f, wv, n_slices))) return rc;
+        if ((rc = resolve_and_preview(ctx, f, sink, wv.rad, sc, s0 + sc, sh.rows))) return rc;
     }
     if (pool_wait_ms > 0.0) ctx->parts.emplace_back("of_which_waiting_for_the_pool", pool_wait_ms);
-    tr.nx = nx, tr.rows = rows, tr.npix = npix, tr.tiles_per_row = gp.tiles_per_row, tr.tile_pixels = gp.tile_pixels;
-    tr.n_depths = n_depths, tr.n_slices = n_slices, tr.n_trace_launches = n_trace_launches, tr.acc = acc;
+    tr.nx = prm->nx, tr.rows = sh.rows, tr.npix = npix, tr.tiles_per_row = f.gp.tiles_per_row, tr.tile_pixels = f.gp.tile_pixels;
+    tr.n_depths = f.n_depths, tr.n_slices = n_slices, tr.n_trace_launches = f.n_trace_launches, tr.acc = f.acc;
     return RT_OK;
 }
 
@@ -1250,18 +1203,14 @@ int rt_prepare(RtCtx* ctx, const RtParams* prm) {
     if (!prm || prm->nx == 0 || prm->ny == 0 || prm->spp == 0) return fail(ctx, RT_ERR_INVALID, "rt_prepare: params NULL, or nx, ny or spp 0");
     if (prm->shard_count > 1 && prm->shard_id >= prm->shard_count) return fail(ctx, RT_ERR_INVALID, "rt_prepare: shard_id >= shard_count");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    const uint64_t npix64 = (uint64_t)rt_shard_rows(prm->ny, prm->shard_band ? prm->shard_band : 1u, prm->shard_count, prm->shard_id) * prm->nx;
+    const uint64_t npix64 = shard_geom(*prm).npix64;
     if (npix64 == 0) return RT_OK;
     if (npix64 > 0xFFFFFFFFull) return fail(ctx, RT_ERR_INVALID, "rt_prepare: image too large");
-    SlicePlan plan;
-    int rc = plan_slices(ctx, prm, npix64, plan);
-    if (rc) return rc;
-    ctx->pool.chunk_delay_us.store(ctx->opt[RT_OPT_POOL_CHUNK_DELAY_US]);
     // + what the frame's small buffers will take below the work area (accumulator, candidate lists, the two output images: 43 B a
     // pixel) and the scene (an estimate: a pool that turns out a little short simply keeps growing while the frame starts)
     const size_t small = (size_t)npix64 * 48u + (64u << 20);
-    if (const char* e = pool_request(ctx->pool, plan.want_bytes + small)) return fail(ctx, RT_ERR_NOMEM, std::string("rt_prepare: ") + e);
-    return RT_OK;
+    SlicePlan plan;
+    return request_slices(ctx, prm, npix64, "rt_prepare", small, plan);
 }
 
 int rt_render_device(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, void* d_out_rgb_f32, void* stream_v,
@@ -1274,9 +1223,7 @@ int rt_render(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, float* out_r
     int rc = check_params(ctx, cam, prm);
     if (rc) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t band = prm->shard_band ? prm->shard_band : 1u;
-    const uint32_t rows = rt_shard_rows(prm->ny, band, prm->shard_count, prm->shard_id);
-    const size_t n = (size_t)rows * prm->nx * 3;
+    const size_t n = (size_t)shard_geom(*prm).npix64 * 3;
     if ((rc = ensure(ctx, ctx->out_f32, n * sizeof(float)))) return rc;
     // the u8 image is produced only on request
     if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
@@ -1323,10 +1270,10 @@ int rt_accum_begin(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, uint32_
     RtCtx::Accum a{};
     a.cam = *cam, a.prm = *prm, a.first = first_sample;
     a.nx = prm->nx;
-    a.rows = rt_shard_rows(prm->ny, prm->shard_band ? prm->shard_band : 1u, prm->shard_count, prm->shard_id);
-    const uint64_t npix64 = (uint64_t)a.rows * a.nx;
-    a.npix = (uint32_t)npix64;
-    pixel_order(ctx, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+    const ShardGeom sh = shard_geom(*prm);
+    a.rows = sh.rows, a.npix = (uint32_t)sh.npix64;
+    const PixelOrder po = pixel_order(ctx->opt[RT_OPT_PIXEL_ORDER], scene_is_general(ctx), a.nx, a.rows);
+    a.tiles_per_row = po.tiles_per_row, a.tile_pixels = po.tile_pixels;
     if (a.npix) {
         const uint32_t nb = (a.npix + 255u) / 256u;
         if ((rc = ensure(ctx, ctx->accum_sum, (size_t)a.npix * 3 * sizeof(float)))) return rc;
@@ -1337,9 +1284,7 @@ int rt_accum_begin(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, uint32_
         RT_HIP(ctx, hipMemsetAsync(ctx->accum_mom.p, 0, (size_t)a.npix * sizeof(double2), ctx->stream));
         // the work buffers of one add of prm->spp samples, requested now (as rt_prepare does for a frame)
         SlicePlan plan;
-        if ((rc = plan_slices(ctx, prm, npix64, plan))) return rc;
-        ctx->pool.chunk_delay_us.store(ctx->opt[RT_OPT_POOL_CHUNK_DELAY_US]);
-        if (const char* e = pool_request(ctx->pool, plan.want_bytes)) return fail(ctx, RT_ERR_NOMEM, std::string("rt_accum_begin: ") + e);
+        if ((rc = request_slices(ctx, prm, sh.npix64, "rt_accum_begin", 0u, plan))) return rc;
     }
     ctx->accum = a;
     ctx->accum.open = true;
@@ -1975,16 +1920,12 @@ static int debug_bounce_production(RtCtx* ctx, const RtBounceIO* io) {
     RT_HIP(ctx, hipMemsetAsync(ctx->totals.p, 0, 4 * sizeof(unsigned long long), st));
     RT_HIP(ctx, hipMemsetAsync(wv.rad, 0xFF, (size_t)n * RT_RAD_FLOATS * sizeof(float), st)); // NaN pattern: a survivor has no slot
     // one "image row" of n pixels, one sample: slot i is pixel i, so its key is path_key(seed 0, pix i, sample 0)
-    GenParams gp{};
-    gp.nx = n, gp.ny = 1, gp.npix = n, gp.n_rays = n, gp.s0 = 0;
-    gp.shard_band = 1, gp.shard_count = 1, gp.shard_id = 0;
-    gp.nq = nq, gp.cap = cap;
-    gp.inv_npix = gp.inv_nx = (float)((1.0 / (double)n) * (1.0 - 1.0 / 4194304.0));
-    gp.inv_band = (float)(1.0 - 1.0 / 4194304.0);
+    RtParams one_row{};
+    one_row.nx = n, one_row.ny = 1;
+    GenParams gp = frame_gen_params(RtCamera{}, one_row, shard_geom(one_row), nq, PixelOrder{0u, 0u});
+    gp.cap = cap, gp.n_rays = n, gp.s0 = 0;
+    launch_sets(ctx, st, (GenParams*)ctx->genp.p); // (MOTION: the time of slot i comes from its slot key)
     hipLaunchKernelGGL(k_init_counts<false>, dim3((nq + 255u) / 256u), dim3(256), 0, st, gp, counts, (GenParams*)ctx->genp.p, GenLens{});
-    if (ctx->motion) hipLaunchKernelGGL(k_set_motion, dim3(1), dim3(64), 0, st, (GenParams*)ctx->genp.p, ctx->gmotion); // (the time of slot i: its slot key)
-    if (ctx->planar) hipLaunchKernelGGL(k_set_planar, dim3(1), dim3(64), 0, st, (GenParams*)ctx->genp.p, ctx->gplanar);
-    if (ctx->lights) hipLaunchKernelGGL(k_set_lights, dim3(1), dim3(64), 0, st, (GenParams*)ctx->genp.p, ctx->glights);
     hipLaunchKernelGGL(k_debug_fill, dim3((n + 255u) / 256u), dim3(256), 0, st, gp, Q[0], d_o, d_d);
     const bool use_bvh = ctx->search.use_bvh && !(io->flags & RT_FLAG_BRUTE_FORCE);
     const StepBuffers sb{Q[0], Q[1], wv.qhit, counts, counts + nq, wv.rad,

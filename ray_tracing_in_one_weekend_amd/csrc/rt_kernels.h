@@ -130,8 +130,9 @@ __device__ __forceinline__ float path_time(const GenMotion& gm, uint32_t k0, uin
 }
 
 // x / d for the slot arithmetic of gen_primary / path_key_of_slot (quotients below 2^21): a float product that never exceeds the true quotient
-// (inv = (1/d)(1 - 2^-22) absorbs the roundings of the conversion and of the product) and two correction steps.
-__device__ __forceinline__ uint32_t udiv_inv(uint32_t x, uint32_t d, float inv, uint32_t& rem) {
+// (inv = (1/d)(1 - 2^-22), udiv_reciprocal of rt_frame_plan.h, absorbs the roundings of the conversion and of the product) and two correction
+// steps.  __host__ too: tests/frame_plan_main.hip runs this very function against integer division.
+__host__ __device__ __forceinline__ uint32_t udiv_inv(uint32_t x, uint32_t d, float inv, uint32_t& rem) {
     uint32_t qt = (uint32_t)((float)x * inv);
     uint32_t r = x - qt * d;
     if (r >= d) ++qt, r -= d;

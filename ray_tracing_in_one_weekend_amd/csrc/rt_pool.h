@@ -13,7 +13,7 @@
 //     "invalid argument" for a mapping whose size differs from that of the first mapping of the reservation
 //     (alloc_probe vmmmix), so a smaller fallback size for a device that is nearly full is not an option;
 //   * rt_prepare() starts the growth for a frame size before the scene exists, so that it overlaps the host's scene build;
-//   * render_impl sizes every slice by what is mapped when the slice is enqueued: while the pool is still growing the frame
+//   * trace_samples sizes every slice by what is mapped when the slice is enqueued: while the pool is still growing the frame
 //     starts in small slices instead of waiting (slices are independent and frames bit-identical for any slicing), a stalled
 //     chunk delays the growth and not the frame, and a device that has little memory to give yields more slices, not an error.
 // The pool only grows; it is kept across frames and scene uploads and released by rt_ctx_destroy.
@@ -118,7 +118,7 @@ inline void pool_grower(WorkPool* p) {
 // started if it is not running.  A pool that stopped at the device's limit earlier tries again: memory may have come back.
 // Returns the error text of a failed reservation, or nullptr.
 inline const char* pool_request(WorkPool& p, size_t bytes) {
-    constexpr size_t RESERVE = 160ull << 30; // RT_MAX_SLICE_RAYS x 100 B + the small buffers + rounding: the largest slice render_impl ever asks for
+    constexpr size_t RESERVE = 160ull << 30; // RT_MAX_SLICE_RAYS x 100 B + the small buffers + rounding: the largest slice trace_samples ever asks for
     if (!p.base) {
         void* va = nullptr;
         if (hipMemAddressReserve(&va, RESERVE, 2ull << 20, nullptr, 0) != hipSuccess) {
