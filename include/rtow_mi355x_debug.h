@@ -218,13 +218,22 @@ int rt_debug_bounce(RtCtx* ctx, const RtBounceIO* io);
  *   RT_ARITH_SQRT             out[i] = sqrt(x[i]) as the kernels take it of a discriminant and of a squared length: the compiler's
  *       own sequence without the scaling of arguments below 2^-96 (`a` is not read);
  *   RT_ARITH_TO_I32, _TO_U32  out[i] = the BITS of `x[i] as i32` / `x[i] as u32` with Rust's rule (toward zero, saturating, NaN -> 0;
- *       math.rs:137-152 offset_hit_point, texture.rs:183-193): v_cvt_i32_f32 / v_cvt_u32_f32 (`a` is not read).
+ *       math.rs:137-152 offset_hit_point, texture.rs:183-193): v_cvt_i32_f32 / v_cvt_u32_f32 (`a` is not read);
+ *   RT_ARITH_ACOS, _ATAN2, _SIN, _COS, _LOG  out[i] = acosf(x[i]), atan2f(x[i], a[i]) (`x` is y, `a` is x), sinf(x[i]), cosf(x[i]),
+ *       logf(x[i]): the very calls of Sphere::get_uv (hitable.rs:65-71), CheckerTex / PerlinTex (texture.rs:40-49, 164-168),
+ *       world_to_local_with_rot (hitable.rs:37-41) and gtr1 (pbr.rs:72-79) in the kernels (`a` is read by _ATAN2 only).
  * The test holds the first two against IEEE bit for bit over the operand range the kernels use them on and maps where they may
- * differ, the conversions against the Rust rule over every kind of argument. */
+ * differ, the conversions against the Rust rule over every kind of argument, and the math library's functions against float64 to
+ * the single-precision ulp bounds of the OpenCL full profile (acos 4, atan2 6, sin and cos 4, log 3). */
 #define RT_ARITH_SHARED_DIVISION 0u
 #define RT_ARITH_SQRT 1u
 #define RT_ARITH_TO_I32 2u
 #define RT_ARITH_TO_U32 3u
+#define RT_ARITH_ACOS 4u
+#define RT_ARITH_ATAN2 5u
+#define RT_ARITH_SIN 6u
+#define RT_ARITH_COS 7u
+#define RT_ARITH_LOG 8u
 int rt_debug_arithmetic(RtCtx* ctx, uint32_t op, uint32_t n, const float* x, const float* a, float* out);
 
 /* Test hook for the filter of rt_accum_denoise (rtow_mi355x.h "denoising"): the same kernel over host arrays in image order — rgb

@@ -762,6 +762,26 @@ class Renderer:
         """`x as u32` as the kernels convert (rt_debug_arithmetic)."""
         return self._debug_arithmetic(3, x, None).view(np.uint32)
 
+    def debug_acos(self, x):
+        """acosf(x) element by element as Sphere::get_uv calls it (rt_debug_arithmetic)."""
+        return self._debug_arithmetic(4, x, None)
+
+    def debug_atan2(self, y, x):
+        """atan2f(y, x) element by element as Sphere::get_uv calls it (rt_debug_arithmetic)."""
+        return self._debug_arithmetic(5, y, x)
+
+    def debug_sin(self, x):
+        """sinf(x) element by element as the checker and Perlin textures and world_to_local_with_rot call it (rt_debug_arithmetic)."""
+        return self._debug_arithmetic(6, x, None)
+
+    def debug_cos(self, x):
+        """cosf(x) element by element as world_to_local_with_rot calls it (rt_debug_arithmetic)."""
+        return self._debug_arithmetic(7, x, None)
+
+    def debug_log(self, x):
+        """logf(x) element by element as gtr1 and the media's free path call it (rt_debug_arithmetic)."""
+        return self._debug_arithmetic(8, x, None)
+
     def _debug_arithmetic(self, op, x, a):
         x = np.ascontiguousarray(x, dtype=np.float32).ravel()
         a = x if a is None else np.ascontiguousarray(a, dtype=np.float32).ravel()

@@ -2034,8 +2034,9 @@ int rt_debug_bounce(RtCtx* ctx, const RtBounceIO* io) {
 
 int rt_debug_arithmetic(RtCtx* ctx, uint32_t op, uint32_t n, const float* x, const float* a, float* out) {
     if (!ctx) return RT_ERR_INVALID;
-    if (op > RT_ARITH_TO_U32) return fail(ctx, RT_ERR_INVALID, "rt_debug_arithmetic: unknown operation");
-    if (!x || !out || (op == RT_ARITH_SHARED_DIVISION && !a)) return fail(ctx, RT_ERR_INVALID, "rt_debug_arithmetic: NULL array");
+    if (op > RT_ARITH_LOG) return fail(ctx, RT_ERR_INVALID, "rt_debug_arithmetic: unknown operation");
+    const bool two = op == RT_ARITH_SHARED_DIVISION || op == RT_ARITH_ATAN2;
+    if (!x || !out || (two && !a)) return fail(ctx, RT_ERR_INVALID, "rt_debug_arithmetic: NULL array");
     if (n == 0) return RT_OK;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
@@ -2045,7 +2046,7 @@ int rt_debug_arithmetic(RtCtx* ctx, uint32_t op, uint32_t n, const float* x, con
     float* dq = da + n;
     hipStream_t st = ctx->stream;
     RT_HIP(ctx, hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (op == RT_ARITH_SHARED_DIVISION) RT_HIP(ctx, hipMemcpyAsync(da, a, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (two) RT_HIP(ctx, hipMemcpyAsync(da, a, (size_t)n * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_debug_arithmetic, dim3((n + 255u) / 256u), dim3(256), 0, st, op, n, dx, da, dq);
     RT_HIP(ctx, hipGetLastError());
     RT_HIP(ctx, hipMemcpyAsync(out, dq, (size_t)n * 4, hipMemcpyDeviceToHost, st));

@@ -1723,7 +1723,8 @@ __global__ __launch_bounds__(256) void k_debug_fill(GenParams gp, Queue q, const
 }
 
 
-// Test hook (rt_debug_arithmetic): div_shared, sqrt_ns and the saturating conversions as the kernels use them.
+// Test hook (rt_debug_arithmetic): div_shared, sqrt_ns and the saturating conversions as the kernels use them, and the math library's
+// functions as sphere_get_uv, the checker and Perlin textures, world_to_local_with_rot and gtr1 call them.
 __global__ __launch_bounds__(256) void k_debug_arithmetic(uint32_t op, uint32_t n, const float* __restrict__ x, const float* __restrict__ a,
                                                           float* __restrict__ out) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -1731,7 +1732,12 @@ __global__ __launch_bounds__(256) void k_debug_arithmetic(uint32_t op, uint32_t 
     if (op == 0u) out[i] = div_shared(x[i], shared_rcp(a[i]));
     else if (op == 1u) out[i] = sqrt_ns(x[i]);
     else if (op == 2u) out[i] = __int_as_float(sat_i32(x[i]));
-    else out[i] = __uint_as_float(sat_u32(x[i]));
+    else if (op == 3u) out[i] = __uint_as_float(sat_u32(x[i]));
+    else if (op == 4u) out[i] = acosf(x[i]);
+    else if (op == 5u) out[i] = atan2f(x[i], a[i]);
+    else if (op == 6u) out[i] = sinf(x[i]);
+    else if (op == 7u) out[i] = cosf(x[i]);
+    else out[i] = logf(x[i]);
 }
 
 // Test hook: one bounce for caller-given rays, no queues (rt_debug_bounce).  MOTION (rt_set_motion): the ray's time comes from counter
