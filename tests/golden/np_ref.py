@@ -169,13 +169,14 @@ def sphere_hit(c, r, o, d, t_min, t_max):  # hitable.rs:75-102
     return {"t": root, "p": p, "on": on, "front": front, "n": on if front else neg(on)}
 
 
-def rotate_y_sphere_hit(sin_t, cos_t, c, r, o, d, t_min, t_max):
-    """RotateY::hit over a Sphere (hitable.rs:469-511): the ray is rotated into object space, the record's point and
-    (already face-flipped) normal are rotated back, and set_face_normal runs a second time with the OBJECT-space
-    direction against the WORLD-space normal (hitable.rs:505) — the quirk the flat scene reproduces."""
+def rotate_y_hit(sin_t, cos_t, inner_hit, o, d, t_min, t_max):
+    """RotateY::hit over any hitable (hitable.rs:482-510); inner_hit(o, d, t_min, t_max) -> record or None.  The ray is rotated into the
+    inner space, the record's point and (already face-flipped) normal are rotated back, and set_face_normal runs a second time with the
+    INNER-space direction against the OUTER-space normal (hitable.rs:505) — the quirk the flat scene reproduces.  The outward normal
+    `on`, from which Sphere::hit took the tangent (hitable.rs:96), stays as the inner hit left it."""
     ro = (cos_t * o[0] - sin_t * o[2], o[1], sin_t * o[0] + cos_t * o[2])
     rd = (cos_t * d[0] - sin_t * d[2], d[1], sin_t * d[0] + cos_t * d[2])
-    h = sphere_hit(c, r, ro, rd, t_min, t_max)
+    h = inner_hit(ro, rd, t_min, t_max)
     if h is None:
         return None
     p, n = h["p"], h["n"]
@@ -184,6 +185,11 @@ def rotate_y_sphere_hit(sin_t, cos_t, c, r, o, d, t_min, t_max):
     front = dot(rd, n2) < f32(0.0)
     h.update(p=p2, front=front, n=n2 if front else neg(n2))
     return h
+
+
+def rotate_y_sphere_hit(sin_t, cos_t, c, r, o, d, t_min, t_max):
+    """RotateY::hit over a Sphere: rotate_y_hit around Sphere::hit"""
+    return rotate_y_hit(sin_t, cos_t, lambda ro, rd, t0, t1: sphere_hit(c, r, ro, rd, t0, t1), o, d, t_min, t_max)
 
 
 def rect_hit(axis, mn, mx, o, d, t_min, t_max):
@@ -362,36 +368,13 @@ def world_to_local_with_rot(norm, tang0, v, rot):  # hitable.rs:37-41
 ZERO = v3(0, 0, 0)
 
 
-def scatter(mat, rd, rec, rng):
+def family_attenuation(mat, rd, rec, dir_o):
+    """The attenuation of a hemisphere-family material (Lambert and the seven pbr.rs materials) for the scattered direction dir_o:
+    what scatter() returns for its own uniform draw, and what tests/light_ref.py weights for a direction of the mixture density."""
     ty = mat["type"]
-    n, p = rec["n"], rec["p"]
+    n = rec["n"]
     tex = tuple(f32(x) for x in mat.get("tex", (0, 0, 0)))
     p0, p1, p2 = f32(mat.get("p0", 0)), f32(mat.get("p1", 0)), f32(mat.get("p2", 0))
-    if ty == 0:  # Emission material.rs:21-28
-        return False, ZERO, ZERO, ZERO, tex
-    if ty == 1:  # Diffuse material.rs:35-46
-        sd = add(n, normalize(random_in_unit_sphere(rng)))
-        eps = f32(np.finfo(np.float32).eps)
-        if abs(sd[0]) < eps and abs(sd[1]) < eps and abs(sd[2]) < eps:  # math.rs:8-11
-            sd = n
-        return True, tex, offset_hit_point(p, n), normalize(sd), ZERO
-    if ty == 3:  # Metal material.rs:66-73 (the ball is drawn even when fuzz == 0)
-        refl = add(reflect(rd, n), scale(random_in_unit_sphere(rng), p0))
-        col = tuple(f32(x) for x in mat["color"])
-        return bool(dot(refl, n) > f32(0.0)), col, p, normalize(refl), ZERO
-    if ty == 4:  # Dielectric material.rs:79-97
-        ref_idx = f32(1.0) / p0 if rec["front"] else p0
-        cos_theta = -min(dot(rd, n), f32(1.0))
-        sin_theta = np.sqrt(f32(1.0) - cos_theta * cos_theta)
-        cannot = sin_theta * ref_idx > f32(1.0)
-        xi = rng.next()
-        d = reflect(rd, n) if (cannot or reflectance(cos_theta, ref_idx) > xi) else refract(rd, n, ref_idx)
-        return True, v3(1, 1, 1), p, normalize(d), ZERO
-    if ty == 5:  # Isotropic material.rs:103-113
-        return True, tex, p, normalize(random_in_unit_sphere(rng)), ZERO
-    # Lambert and the seven pbr.rs materials: offset origin + uniform hemisphere direction
-    po = offset_hit_point(p, n)
-    dir_o = random_on_hemisphere(rng, n)
     n_dot_i = dot(n, neg(rd))
     n_dot_o = dot(n, dir_o)
     two = f32(2.0)
@@ -470,7 +453,40 @@ def scatter(mat, rd, rec, rng):
         att = scale(scale(scale((cc, cc, cc), n_dot_o), two), PI)
     else:
         raise ValueError(ty)
-    return True, att, po, dir_o, ZERO
+    return att
+
+
+def scatter(mat, rd, rec, rng):
+    ty = mat["type"]
+    n, p = rec["n"], rec["p"]
+    tex = tuple(f32(x) for x in mat.get("tex", (0, 0, 0)))
+    p0 = f32(mat.get("p0", 0))
+    if ty == 0:  # Emission material.rs:21-28
+        return False, ZERO, ZERO, ZERO, tex
+    if ty == 1:  # Diffuse material.rs:35-46
+        sd = add(n, normalize(random_in_unit_sphere(rng)))
+        eps = f32(np.finfo(np.float32).eps)
+        if abs(sd[0]) < eps and abs(sd[1]) < eps and abs(sd[2]) < eps:  # math.rs:8-11
+            sd = n
+        return True, tex, offset_hit_point(p, n), normalize(sd), ZERO
+    if ty == 3:  # Metal material.rs:66-73 (the ball is drawn even when fuzz == 0)
+        refl = add(reflect(rd, n), scale(random_in_unit_sphere(rng), p0))
+        col = tuple(f32(x) for x in mat["color"])
+        return bool(dot(refl, n) > f32(0.0)), col, p, normalize(refl), ZERO
+    if ty == 4:  # Dielectric material.rs:79-97
+        ref_idx = f32(1.0) / p0 if rec["front"] else p0
+        cos_theta = -min(dot(rd, n), f32(1.0))
+        sin_theta = np.sqrt(f32(1.0) - cos_theta * cos_theta)
+        cannot = sin_theta * ref_idx > f32(1.0)
+        xi = rng.next()
+        d = reflect(rd, n) if (cannot or reflectance(cos_theta, ref_idx) > xi) else refract(rd, n, ref_idx)
+        return True, v3(1, 1, 1), p, normalize(d), ZERO
+    if ty == 5:  # Isotropic material.rs:103-113
+        return True, tex, p, normalize(random_in_unit_sphere(rng)), ZERO
+    # Lambert and the seven pbr.rs materials: offset origin + uniform hemisphere direction
+    po = offset_hit_point(p, n)
+    dir_o = random_on_hemisphere(rng, n)
+    return True, family_attenuation(mat, rd, rec, dir_o), po, dir_o, ZERO
 
 
 def sky_gradient(d):  # demo_scene.rs:28-31

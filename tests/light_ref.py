@@ -1,8 +1,9 @@
 """Light importance sampling (rt_set_lights, DESIGN.md "Light sampling") in numpy float32, every operation rounded once in the kernels'
 order: the set-up of a light, the selection between the material's own direction and a light, the light draw, p_L, the weight and the
-weighted attenuation.  The oracle knows no light sampling, so this restatement is the reference of tests/test_lights.py and
-tests/test_lights_host.py.  Hit records come from tests/golden/np_ref.py and tests/quad_ref.py; the quad test inside p_L is
-quad_ref.hit_one; unaffected materials go through np_ref.scatter unchanged."""
+weighted attenuation.  The oracle knows no light sampling, so this restatement is the reference of tests/test_lights.py,
+tests/test_lights_materials.py and tests/test_lights_host.py.  Hit records come from tests/golden/np_ref.py and tests/quad_ref.py; the quad
+test inside p_L is quad_ref.hit_one; the family's BRDF at the chosen direction is np_ref.family_attenuation, the one statement np_ref.scatter
+uses too (`tex`, `tex1` and p0..p2 of `mat` pass through); unaffected materials go through np_ref.scatter unchanged."""
 import numpy as np
 
 import quad_ref
@@ -51,46 +52,10 @@ def light_dir(L, rng, po):
         return np_ref.normalize(np_ref.sub(target, po)), k
 
 
-def _family_attenuation(mat, rd, rec, dir_o):
-    """today's attenuation of a hemisphere-family material (np_ref.scatter's formulas) evaluated with dir_o"""
-    ty = mat["type"]
-    n = rec["n"]
-    tex = tuple(f32(x) for x in mat.get("tex", (0, 0, 0)))
-    p0, p1 = f32(mat.get("p0", 0)), f32(mat.get("p1", 0))
-    sc, two, one = np_ref.scale, f32(2.0), f32(1.0)
-    n_dot_i = np_ref.dot(n, np_ref.neg(rd))
-    n_dot_o = np_ref.dot(n, dir_o)
-    if ty == 2:
-        return sc(sc(tex, two), np_ref.dot(n, dir_o))
-    if ty == 6:
-        cos_i, cos_o = abs(np_ref.dot(n, rd)), n_dot_o
-        sin_i, sin_o = np.sqrt(one - cos_i * cos_i), np.sqrt(one - cos_o * cos_o)
-        max_cos = max(cos_i * cos_o + sin_i * sin_o, f32(0.0))
-        r2 = p0 * p0
-        a = one - f32(0.5) * r2 / (r2 + f32(0.33))
-        b = f32(0.45) * r2 / (r2 + f32(0.09))
-        sin_alpha, tan_beta = (sin_o, sin_i / cos_i) if cos_i > cos_o else (sin_i, sin_o / cos_o)
-        return sc(sc(sc(tex, a + b * max_cos * sin_alpha * tan_beta), two), cos_o)
-    h = np_ref.normalize(np_ref.sub(dir_o, rd))
-    h_dot_o = np_ref.dot(h, dir_o)
-    if ty == 7:
-        fl, fv = np_ref.schlick_fresnel(n_dot_o), np_ref.schlick_fresnel(n_dot_i)
-        fd90 = f32(0.5) + two * h_dot_o * h_dot_o * p0
-        fd = np_ref.lerp(one, fd90, fl) * np_ref.lerp(one, fd90, fv)
-        return sc(sc(sc(tex, fd), two), n_dot_o)
-    if ty == 9:
-        fo, fi = np_ref.schlick_fresnel(n_dot_o), np_ref.schlick_fresnel(n_dot_i)
-        fd90 = f32(0.5) + two * h_dot_o * h_dot_o * p0
-        fd = np_ref.lerp(one, fd90, fo) * np_ref.lerp(one, fd90, fi)
-        fss90 = p0 * h_dot_o * h_dot_o
-        fss = f32(1.25) * (np_ref.lerp(one, fss90, fi) * np_ref.lerp(one, fss90, fo) * (one / (n_dot_i + n_dot_o) - f32(0.5)) + f32(0.5))
-        return sc(sc(sc(tex, np_ref.lerp(fd, fss, p1)), two), n_dot_o)
-    raise NotImplementedError("light_ref restates Lambert, OrenNayar, BurleyDiffuse and DisneyDiffuse of the family, not tag %d" % ty)
-
-
 def scatter(mat, rd, rec, rng, L):
     """One hit with the light set L (None or n 0: np_ref.scatter).  Returns (alive, attenuation, o, d, emitted, info); info names the
-    branch ("own", "light" or None for an unaffected material), c, p_L, how many lights contributed and the weight."""
+    branch ("own", "light" or None for an unaffected material), c, p_L, how many lights contributed, the weight and (of a live ray) the
+    attenuation before the weight."""
     ty = mat["type"]
     if L is None or L["n"] == 0 or ty not in AFFECTED:
         return np_ref.scatter(mat, rd, rec, rng) + ({"branch": None},)
@@ -119,6 +84,6 @@ def scatter(mat, rd, rec, rng, L):
     p_l = f32(pl[0])
     p_s = c * np_ref.FRAC_1_PI if ty == 1 else f32(0.5) * np_ref.FRAC_1_PI
     wgt = p_s / ((p_s + p_l) * f32(0.5))
-    info.update(p_L=p_l, n_contrib=int(cnt[0]), wgt=wgt)
-    att = tex if ty == 1 else _family_attenuation(mat, rd, rec, d)
+    att = tex if ty == 1 else np_ref.family_attenuation(mat, rd, rec, d)
+    info.update(p_L=p_l, n_contrib=int(cnt[0]), wgt=wgt, att=att)
     return True, np_ref.scale(att, wgt), po, d, np_ref.ZERO, info
