@@ -461,8 +461,8 @@ int rt_set_lights(RtCtx* ctx, const RtLights* lights);
  * rt_render and rt_render_device may be called in between and neither disturbs the other.  The first rt_accum_denoise of a context adds
  * 20 B + 12 B per pixel (the filter's inputs c, y, v in image order and its output), kept for the next like the accumulation's buffers.
  * Not covered: rt_multi_* (the noise of a frame split over devices needs a reduction across them); the rt_set_progress callback (a
- * host that accumulates has its preview in rt_accum_read); per-pixel adaptive sampling (primary rays are generated over the whole
- * lattice of the shard: every add gives every pixel the same number of samples). */
+ * host that accumulates has its preview in rt_accum_read).  rt_accum_add gives every pixel the same number of samples; "Adaptive
+ * sampling" below gives them to the pixels that still need them. */
 typedef struct RtNoise {
     uint32_t spp_done;      /* samples per pixel accumulated so far */
     uint32_t reserved;
@@ -499,6 +499,66 @@ int rt_accum_end(RtCtx* ctx);
  * RT_ERR_INVALID: spp_step 0, target_noise NaN or negative, params->spp < 2. */
 int rt_render_to_noise(RtCtx* ctx, const RtCamera* cam, const RtParams* params, double target_noise, uint32_t spp_step,
                        float* out_rgb_f32, uint8_t* out_rgb8, float* out_sem, RtNoise* noise, RtStats* stats);
+
+/* -- adaptive sampling: converged pixels stop, the noisy ones go on -----------------------------------------------------------------
+ * The sampling half of Rousselle, Knaus, Zwicker 2012, on the moments an accumulation keeps anyway.  The accumulation gains a sample
+ * count n_p (u32) and a converged flag per pixel, 5 B per pixel in the local pixel order of its sums, allocated by the first adaptive add.
+ * Decision, at the START of rt_accum_add_adaptive, from the moments of the samples a pixel holds so far; every operation one IEEE f64
+ * operation, no FMA:
+ *   (Ybar_p, V_p) = the figures of "Moments" above with n = n_p;   thr = tolerance * max(Ybar_p, luminance_floor), max(a, b) = a > b ? a : b;
+ *   pixel p becomes CONVERGED iff  n_p >= min_samples && V_p <= thr * thr.
+ * A comparison with a NaN is false: a pixel that holds a non-finite sample (its V is NaN from two samples on) stays active until the
+ * caller stops, and spreads to no other pixel.  Converged is STICKY: no later decision looks at the pixel again.  Every pixel that is
+ * still active after the decision then receives the samples [first_sample + n_p, first_sample + n_p + n_samples) — all active pixels
+ * share one n_p, the number of samples the accumulation has issued — added in sample order.  Hence the defining property:
+ *   pixel p of an adaptive accumulation is, bit for bit (sum, moments, sem), pixel p of rt_render / rt_accum_add with spp = n_p,
+ * whatever the queue shards, chains, slices and pixel order (the place a primary ray takes in its queue shard depends on the order in
+ * which workgroups arrive there; no result depends on the place).
+ * Statistics.  A stopping rule that reads the estimate it stops on is biased: a pixel whose first samples happen to agree stops early
+ * and keeps its — too low — variance and whatever mean it had, so rare bright samples it has not seen yet (fireflies) are under-represented.  The bias
+ * falls with the number of samples the first decision sees: min_samples bounds it, and uniform warm-up adds raise that number for all.
+ * tolerance is a relative standard error of the pixel's mean luminance; luminance_floor keeps dark pixels from asking for an absolute
+ * error of 0 (with V_p = 0 — black sky — a pixel converges at min_samples for every tolerance, 0 included).
+ * Mixing.  rt_accum_add calls BEFORE the first adaptive add are allowed (a warm-up: n_p starts at what they added); rt_accum_add AFTER
+ * an adaptive add is RT_ERR_STATE.  Everything that ends an accumulation ends an adaptive one; rt_render in between disturbs nothing.
+ * Reading.  rt_accum_read divides by (float)n_p per pixel; out_sem and the frame figures use n_p per pixel (V_p = 0 where n_p < 2) over
+ * the same fixed tree; noise is +inf where any n_p < 2; RtNoise.spp_done = max_p n_p.  rt_accum_denoise takes c, y, v with n_p per pixel.
+ * Depth 0 of an adaptive add runs on the materialised ray queue (the fused depth-0 kernels and the candidate lists invert a queue position
+ * into a pixel, which a compacted queue does not allow): per traced sample it costs what RT_OPT_MATERIALISE_PRIMARIES costs (DESIGN.md
+ * "Adaptive sampling").  Not covered: rt_multi_*; un-sticking a pixel; per-channel criteria. */
+typedef struct RtAdaptive {
+    double tolerance;        /* finite, >= 0: relative standard error of the mean luminance at which a pixel stops */
+    double luminance_floor;  /* finite, > 0: the mean luminance below which the error is measured against this floor */
+    uint32_t min_samples;    /* >= 2: no pixel stops on fewer samples */
+    uint32_t reserved;       /* 0 */
+} RtAdaptive;
+typedef struct RtAdaptiveInfo {
+    uint64_t n_active;       /* pixels of the shard not converged, as decided by the last adaptive add (all, before the first) */
+    uint64_t n_samples;      /* sum of n_p over the shard */
+    uint32_t spp_min, spp_max; /* min_p n_p, max_p n_p */
+} RtAdaptiveInfo;
+/* The decision above, then n_samples more samples for every pixel still active.  `stats` (may be NULL; it forces a synchronisation) are
+ * those of the rays actually traced: n_paths = active pixels x n_samples (0 when every pixel has converged: nothing is traced and no image
+ * changes), the depth totals as in rt_accum_add.  RT_ERR_INVALID: `ad` NULL or outside the ranges of RtAdaptive, n_samples 0, or
+ * first_sample plus everything issued would pass 2^32 - 1 — nothing has changed then.  RT_ERR_STATE: no open accumulation. */
+int rt_accum_add_adaptive(RtCtx* ctx, uint32_t n_samples, const RtAdaptive* ad, RtStats* stats);
+/* The sample counts of the open accumulation: out_counts [rows_local*nx] in the row order of out_rgb_f32 (may be NULL), and the sums
+ * over the shard (may be NULL).  Before the first adaptive add every n_p is the number of samples added so far and every pixel is
+ * active.  Synchronises the context's stream once.  RT_ERR_STATE: no open accumulation. */
+int rt_accum_read_counts(RtCtx* ctx, uint32_t* out_counts, RtAdaptiveInfo* info);
+/* rt_accum_begin(first_sample 0), then adaptive adds of min(spp_step, what is left of params->spp) samples until no pixel is active or
+ * params->spp samples, the maximum, are issued; the outputs as rt_accum_read and rt_accum_read_counts write them (each may be NULL),
+ * `stats` summed over the adds; the accumulation is ended.  After each add the host reads n_active with the frame figures: one stream
+ * synchronisation per step, as rt_render_to_noise pays.  The add that finds no active pixel traces nothing and is the last.
+ * RT_ERR_STATE: an accumulation is open.  RT_ERR_INVALID: spp_step 0, params->spp < 2, `ad` outside its ranges. */
+int rt_render_adaptive(RtCtx* ctx, const RtCamera* cam, const RtParams* params, const RtAdaptive* ad, uint32_t spp_step,
+                       float* out_rgb_f32, uint8_t* out_rgb8, float* out_sem, uint32_t* out_counts, RtNoise* noise, RtAdaptiveInfo* info,
+                       RtStats* stats);
+/* The two GPU-free halves of the decision, for a host that plans or checks one (no context, no device).  rt_adaptive_check: RT_OK or
+ * RT_ERR_INVALID as rt_accum_add_adaptive judges `ad` and n_samples.  rt_adaptive_converged: 1 when a pixel with the moments (s1, s2)
+ * of n samples meets the criterion of `ad`, 0 when not, RT_ERR_INVALID for an `ad` outside its ranges. */
+int rt_adaptive_check(const RtAdaptive* ad, uint32_t n_samples);
+int rt_adaptive_converged(const RtAdaptive* ad, double s1, double s2, uint32_t n);
 
 /* -- denoising: a non-local-means filter guided by the accumulation's own variance -----------------------------------------------------
  * The two moments of a pixel say how far two pixel means may differ by chance; the filter averages what differs only by that much and

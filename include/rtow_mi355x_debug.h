@@ -243,6 +243,11 @@ int rt_debug_arithmetic(RtCtx* ctx, uint32_t op, uint32_t n, const float* x, con
 int rt_debug_denoise(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* y, const float* v, const RtDenoise* dn,
                      float* out_rgb_f32);
 
+/* Test hook for adaptive sampling (rtow_mi355x.h "adaptive sampling"): overwrites the two luminance moments (S1, S2) of pixel `pixel` of
+ * the open accumulation, `pixel` an index into out_sem (row order of out_rgb_f32).  The tests plant a NaN with it: such a pixel never
+ * converges and spreads to no other.  The f32 sum and n_p stay.  RT_ERR_STATE: no open accumulation; RT_ERR_INVALID: pixel outside the shard. */
+int rt_debug_accum_set_moments(RtCtx* ctx, uint32_t pixel, double s1, double s2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,17 @@ class RtDenoise(C.Structure):
     _fields_ = [("radius", C.c_uint32), ("patch", C.c_uint32), ("strength", C.c_float), ("reserved", C.c_uint32)]
 
 
+class RtAdaptive(C.Structure):
+    """rt_accum_add_adaptive / rt_render_adaptive: a pixel stops once it holds min_samples samples and the variance of its mean luminance
+    is at most (tolerance * max(mean luminance, luminance_floor))^2 (rtow_mi355x.h "adaptive sampling")."""
+    _fields_ = [("tolerance", C.c_double), ("luminance_floor", C.c_double), ("min_samples", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RtAdaptiveInfo(C.Structure):
+    """rt_accum_read_counts: pixels still active, the sum of the per-pixel sample counts and their extremes over the shard."""
+    _fields_ = [("n_active", C.c_uint64), ("n_samples", C.c_uint64), ("spp_min", C.c_uint32), ("spp_max", C.c_uint32)]
+
+
 DENOISE_MAX_RADIUS, DENOISE_MAX_PATCH = 10, 3
 DENOISE_DEFAULT_STRENGTH = 1.0  # RT_DENOISE_DEFAULT_STRENGTH
 
@@ -186,6 +197,8 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_set_lights", "rt_multi_set_lights",
                "rt_accum_begin", "rt_accum_add", "rt_accum_read", "rt_accum_end", "rt_render_to_noise",
                "rt_accum_denoise", "rt_debug_denoise",
+               "rt_accum_add_adaptive", "rt_accum_read_counts", "rt_render_adaptive", "rt_adaptive_check", "rt_adaptive_converged",
+               "rt_debug_accum_set_moments",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
@@ -279,6 +292,19 @@ def load_gpu_library():
     lib.rt_accum_denoise.restype = C.c_int
     lib.rt_debug_denoise.argtypes = [vp, C.c_uint32, C.c_uint32, _f, _f, _f, C.POINTER(RtDenoise), _f]
     lib.rt_debug_denoise.restype = C.c_int
+    lib.rt_accum_add_adaptive.argtypes = [vp, C.c_uint32, C.POINTER(RtAdaptive), C.POINTER(RtStats)]
+    lib.rt_accum_add_adaptive.restype = C.c_int
+    lib.rt_accum_read_counts.argtypes = [vp, _u32, C.POINTER(RtAdaptiveInfo)]
+    lib.rt_accum_read_counts.restype = C.c_int
+    lib.rt_render_adaptive.argtypes = [vp, C.POINTER(RtCamera), C.POINTER(RtParams), C.POINTER(RtAdaptive), C.c_uint32, _f, _u8, _f, _u32,
+                                       C.POINTER(RtNoise), C.POINTER(RtAdaptiveInfo), C.POINTER(RtStats)]
+    lib.rt_render_adaptive.restype = C.c_int
+    lib.rt_adaptive_check.argtypes = [C.POINTER(RtAdaptive), C.c_uint32]
+    lib.rt_adaptive_check.restype = C.c_int
+    lib.rt_adaptive_converged.argtypes = [C.POINTER(RtAdaptive), C.c_double, C.c_double, C.c_uint32]
+    lib.rt_adaptive_converged.restype = C.c_int
+    lib.rt_debug_accum_set_moments.argtypes = [vp, C.c_uint32, C.c_double, C.c_double]
+    lib.rt_debug_accum_set_moments.restype = C.c_int
     lib.rt_debug_planar_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.rt_debug_planar_info.restype = C.c_int
     lib.rt_debug_planar_bounds.argtypes = [C.POINTER(RtQuads), C.c_float, vp, vp]

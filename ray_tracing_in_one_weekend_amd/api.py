@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import RtBounceIO, RtCamera, RtDenoise, RtFlatScene, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtStats
+from ._ffi import RtAdaptive, RtAdaptiveInfo, RtBounceIO, RtCamera, RtDenoise, RtFlatScene, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtStats
 
 
 class RtError(RuntimeError):
@@ -431,6 +431,24 @@ def make_params(nx, ny, spp, max_depth=50, seed=95, shard_band=0, shard_count=1,
     return p
 
 
+def make_adaptive(tolerance, luminance_floor=0.01, min_samples=16):
+    """An RtAdaptive: the stopping criterion of Renderer.accum_add_adaptive / render_adaptive."""
+    return RtAdaptive(float(tolerance), float(luminance_floor), int(min_samples), 0)
+
+
+def adaptive_check(ad, n_samples=1):
+    """rt_adaptive_check (no GPU): True when rt_accum_add_adaptive would accept the RtAdaptive and n_samples."""
+    return _ffi.load_gpu_library().rt_adaptive_check(C.byref(ad) if ad is not None else None, int(n_samples)) == 0
+
+
+def adaptive_converged(ad, s1, s2, n):
+    """rt_adaptive_converged (no GPU): the criterion on the luminance moments (S1, S2) of a pixel's n samples."""
+    rc = _ffi.load_gpu_library().rt_adaptive_converged(C.byref(ad), float(s1), float(s2), int(n))
+    if rc < 0:
+        raise RtError(f"rt_adaptive_converged failed ({rc}): the RtAdaptive is outside its ranges")
+    return rc == 1
+
+
 class Renderer:
     """One GPU context (rt_ctx_create).  Replaces the render half of main.rs:62-129."""
 
@@ -594,6 +612,45 @@ class Renderer:
         if rc != 0:
             self._raise("rt_render_to_noise", rc)
         return img, rgb8, sem, noise, stats
+
+    def accum_add_adaptive(self, n, tolerance, luminance_floor=0.01, min_samples=16):
+        """rt_accum_add_adaptive: pixels that hold min_samples samples and whose mean luminance has a variance of at most
+        (tolerance * max(mean, luminance_floor))^2 stop for good; every other pixel gets n more samples.  Returns the RtStats of the rays
+        traced (n_paths = active pixels x n)."""
+        ad, stats = make_adaptive(tolerance, luminance_floor, min_samples), RtStats()
+        rc = self._lib.rt_accum_add_adaptive(self._ctx, int(n), C.byref(ad), C.byref(stats))
+        if rc != 0:
+            self._raise("rt_accum_add_adaptive", rc)
+        return stats
+
+    def accum_counts(self):
+        """rt_accum_read_counts: (sample counts [rows, nx] u32 laid out as accum_read's sem, RtAdaptiveInfo)."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        counts, info = np.zeros((rows, nx), dtype=np.uint32), RtAdaptiveInfo()
+        rc = self._lib.rt_accum_read_counts(self._ctx, counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(info))
+        if rc != 0:
+            self._raise("rt_accum_read_counts", rc)
+        return counts, info
+
+    def render_adaptive(self, camera, params, tolerance, step, luminance_floor=0.01, min_samples=16, want_rgb8=False, want_sem=False):
+        """rt_render_adaptive: adaptive adds of `step` samples until no pixel is active or params.spp, the maximum, are issued.  Returns
+        (img, rgb8 or None, sem or None, counts [rows, nx] u32, RtNoise, RtAdaptiveInfo, RtStats summed over the steps); pixel p of img is
+        pixel p of render() with spp = counts[p], bit for bit."""
+        self._accum_shape = (self.shard_rows(params), params.nx)
+        img, rgb8, sem, ptrs = self._accum_outputs(want_rgb8, want_sem)
+        counts = np.zeros(self._accum_shape, dtype=np.uint32)
+        ad, noise, info, stats = make_adaptive(tolerance, luminance_floor, min_samples), RtNoise(), RtAdaptiveInfo(), RtStats()
+        rc = self._lib.rt_render_adaptive(self._ctx, C.byref(camera), C.byref(params), C.byref(ad), int(step), *ptrs,
+                                          counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(noise), C.byref(info), C.byref(stats))
+        if rc != 0:
+            self._raise("rt_render_adaptive", rc)
+        return img, rgb8, sem, counts, noise, info, stats
+
+    def debug_accum_set_moments(self, pixel, s1, s2):
+        """rt_debug_accum_set_moments: overwrites (S1, S2) of pixel `pixel` (an index into accum_read's sem, flattened) of the open accumulation."""
+        rc = self._lib.rt_debug_accum_set_moments(self._ctx, int(pixel), float(s1), float(s2))
+        if rc != 0:
+            self._raise("rt_debug_accum_set_moments", rc)
 
     @staticmethod
     def _denoise_ptr(radius, patch, strength):

@@ -4,6 +4,7 @@
 #include "../../include/rtow_mi355x_debug.h"
 #include "rt_kernels.h"
 #include "rt_denoise.h"
+#include "rt_adaptive.h"
 #include "rt_bvh.h"
 #include "rt_grid.h"
 #include "rt_pool.h"
@@ -127,9 +128,14 @@ struct RtCtx {
         RtParams prm{};
         uint32_t first = 0, done = 0; // the next sample to trace is first + done
         uint32_t nx = 0, rows = 0, npix = 0, tiles_per_row = 0, tile_pixels = 0;
+        bool adaptive = false; // an adaptive add has happened: accum_cnt / accum_flag hold n_p and the converged flags, `done` is the n_p of the active pixels
     } accum;
     DevBuf accum_sum, accum_mom, accum_sem, accum_partials; // (accum_sem: staging of out_sem; accum_partials: one f64 pair per workgroup + the 3 frame figures)
     double* h_noise = nullptr;   // page-locked: mean_luminance, rms_sem, noise as k_noise_final wrote them
+    // rt_accum_add_adaptive: a u32 sample count and a u8 converged flag per pixel in the order of accum_sum, carved by the first adaptive
+    // add; accum_info: the integer partial sums of k_adaptive_decide (one per workgroup) + the frame's RtAdaptiveInfo behind them
+    DevBuf accum_cnt, accum_flag, accum_info, accum_cnt_out; // (accum_cnt_out: staging of out_counts)
+    RtAdaptiveInfo* h_info = nullptr; // page-locked: the frame's sums as k_adaptive_info wrote them
     DevBuf dn_c, dn_yv, dn_out;  // rt_accum_denoise: the filter's inputs (c 12 B, (y, v) 8 B) and its output (12 B) per pixel, in image order
     // Host-side timeline of the last trace_samples and what its caller enqueued behind it (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
     // render of a process is where allocations, code-object loads and the queue probe happen; this says which.
@@ -713,6 +719,8 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->out_f32), free_buf(ctx->out_u8), free_buf(ctx->dbg), free_buf(ctx->genp);
     free_buf(ctx->preview_u8), free_buf(ctx->lists);
     free_buf(ctx->accum_sum), free_buf(ctx->accum_mom), free_buf(ctx->accum_sem), free_buf(ctx->accum_partials);
+    free_buf(ctx->accum_cnt), free_buf(ctx->accum_flag), free_buf(ctx->accum_info), free_buf(ctx->accum_cnt_out);
+    if (ctx->h_info) (void)hipHostFree(ctx->h_info);
     free_buf(ctx->dn_c), free_buf(ctx->dn_yv), free_buf(ctx->dn_out);
     if (ctx->h_noise) (void)hipHostFree(ctx->h_noise);
     free_buf(ctx->motion_region), free_buf(ctx->quads_region), free_buf(ctx->lights_buf);
@@ -847,6 +855,10 @@ struct SampleSink {
     float* sum = nullptr;
     double2* mom = nullptr;
     uint32_t first_sample = 0;
+    // An adaptive add (rt_adaptive.h): `converged` flags the pixels that get no samples, `cnt` their sample counts.  Depth 0 then runs on
+    // the materialised queue, filled by k_gen_primary_active with the rays of the other pixels only.
+    const uint8_t* converged = nullptr;
+    uint32_t* cnt = nullptr;
 };
 // What trace_samples enqueued, for the finalize, the copies and the statistics of its caller.
 struct Traced {
@@ -856,6 +868,7 @@ struct Traced {
     int n_depths = 0;
     uint32_t n_slices = 0, n_trace_launches = 0;
     float* acc = nullptr; // the running sum the samples went to
+    bool paths_from_depth0 = false; // an adaptive add: n_paths is the number of primary rays traced (the depth-0 total), not npix * spp
 };
 
 // The decisions of a frame: functions of the context and the params, made before anything is enqueued.
@@ -863,13 +876,13 @@ struct FrameDecisions {
     bool use_bvh, fuse_gen, want_lists, lens, time_depths, one_chain, rects;
     uint32_t nq, isect_grid, shards_per_wg, n_groups;
 };
-static FrameDecisions frame_decisions(const RtCtx* ctx, const RtParams* prm) {
+static FrameDecisions frame_decisions(const RtCtx* ctx, const RtParams* prm, bool masked = false) {
     FrameDecisions d;
     const QueueGeom qg = queue_geom(ctx, 0u);
     d.nq = qg.nq, d.isect_grid = qg.isect_grid;
     d.use_bvh = ctx->search.use_bvh && !(prm->flags & RT_FLAG_BRUTE_FORCE);
     // depth 0 regenerates the primary ray in both kernels instead of materialising the queue
-    d.fuse_gen = d.use_bvh && ctx->opt[RT_OPT_MATERIALISE_PRIMARIES] != 1u;
+    d.fuse_gen = d.use_bvh && ctx->opt[RT_OPT_MATERIALISE_PRIMARIES] != 1u && !masked; // (masked: an adaptive add, a compacted queue)
     // Candidate lists of the primary rays, once per frame (k_primary_lists): worth it when the samples of a pixel
     // share them (>= 4 spp) and pixels see few entries.  Measured per 128-spp slice: sphere_scene (533 entries)
     // 46.7 -> 41.9 ms, pbr_sweep_scene 41.2 -> 39.3, test_sphere 15.5 -> 14.8, cornell_box unchanged (its walls'
@@ -919,6 +932,7 @@ struct Frame {
     size_t counts_bytes;
     unsigned long long* totals; // [0]=tex fetches [1]=bad dirs [2..]=rays per depth
     uint32_t n_trace_launches;
+    const uint8_t* converged; // SampleSink::converged
 };
 
 // Candidate lists of the primary rays, and the one host decision of a frame: f.no_overflow.
@@ -1019,7 +1033,11 @@ static int enqueue_slice(RtCtx* ctx, Frame& f, const WorkView& wv, uint32_t sl) 
     const auto init_counts = d.lens ? &k_init_counts<true> : &k_init_counts<false>;
     hipLaunchKernelGGL(init_counts, dim3((d.nq + 255u) / 256u), dim3(256), 0, st, f.gp, f.counts, f.gpd, f.glens);
     const auto gen_primaries = d.lens ? &k_gen_primary<true> : &k_gen_primary<false>;
-    if (!d.fuse_gen) hipLaunchKernelGGL(gen_primaries, dim3((f.gp.n_rays + 255u) / 256u), dim3(256), 0, st, f.gp, wv.Q[0], f.glens);
+    if (f.converged) { // the depth-0 counts come from the generator: k_init_counts has parked the GenParams, its closed-form counts go
+        RT_HIP(ctx, hipMemsetAsync(f.counts, 0, (size_t)d.nq * sizeof(uint32_t), st));
+        const auto gen_active = d.lens ? &k_gen_primary_active<true> : &k_gen_primary_active<false>;
+        hipLaunchKernelGGL(gen_active, dim3((f.gp.n_rays + 255u) / 256u), dim3(256), 0, st, f.gp, wv.Q[0], f.glens, f.converged, f.counts);
+    } else if (!d.fuse_gen) hipLaunchKernelGGL(gen_primaries, dim3((f.gp.n_rays + 255u) / 256u), dim3(256), 0, st, f.gp, wv.Q[0], f.glens);
     RT_HIP(ctx, hipEventRecord(ctx->events[2 * sl], st));
     if (d.n_groups > 1u) {
         RT_HIP(ctx, hipEventRecord(ctx->ev_fork, st));
@@ -1054,7 +1072,8 @@ static int enqueue_slice(RtCtx* ctx, Frame& f, const WorkView& wv, uint32_t sl) 
 static int resolve_and_preview(RtCtx* ctx, const Frame& f, const SampleSink& sink, const float* rad, uint32_t sc, uint32_t done, uint32_t rows) {
     const hipStream_t st = f.st;
     const uint32_t npix = f.npix, spp = f.prm->spp, nx = f.prm->nx;
-    if (sink.mom) hipLaunchKernelGGL(k_resolve_moments, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, npix, sc);
+    if (sink.converged) hipLaunchKernelGGL(k_resolve_moments_active, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.converged, sink.cnt, npix, sc);
+    else if (sink.mom) hipLaunchKernelGGL(k_resolve_moments, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, npix, sc);
     else hipLaunchKernelGGL(k_resolve, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, npix, sc);
     hipLaunchKernelGGL(k_accum_counts, dim3((unsigned)f.n_depths), dim3(256), 0, st, f.counts, f.d.nq, (uint32_t)f.n_depths, f.totals + 2);
     if (ctx->progress_armed && ctx->progress_fn && done < spp) { // the last slice is the final image itself
@@ -1090,7 +1109,7 @@ static int trace_samples(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, v
     if (sh.npix64 == 0) return RT_OK;
     const uint32_t npix = (uint32_t)sh.npix64, spp = prm->spp;
     Frame f{};
-    f.d = frame_decisions(ctx, prm), f.st = st, f.prm = prm, f.npix = npix, f.n_depths = prm->max_depth + 1;
+    f.d = frame_decisions(ctx, prm, sink.converged != nullptr), f.converged = sink.converged, f.st = st, f.prm = prm, f.npix = npix, f.n_depths = prm->max_depth + 1;
     const uint32_t nq = f.d.nq;
 
     // the small persistent buffers first (they lie at the bottom of the pool); the work buffers of the slices start above them
@@ -1132,6 +1151,7 @@ static int trace_samples(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, v
     if (pool_wait_ms > 0.0) ctx->parts.emplace_back("of_which_waiting_for_the_pool", pool_wait_ms);
     tr.nx = prm->nx, tr.rows = sh.rows, tr.npix = npix, tr.tiles_per_row = f.gp.tiles_per_row, tr.tile_pixels = f.gp.tile_pixels;
     tr.n_depths = f.n_depths, tr.n_slices = n_slices, tr.n_trace_launches = f.n_trace_launches, tr.acc = f.acc;
+    tr.paths_from_depth0 = sink.converged != nullptr;
     return RT_OK;
 }
 
@@ -1145,7 +1165,7 @@ static int read_stats(RtCtx* ctx, const Traced& tr, uint32_t spp, RtStats* stats
     std::vector<unsigned long long> h((size_t)n_depths + 2);
     RT_HIP(ctx, hipMemcpy(h.data(), ctx->totals.p, totals_bytes, hipMemcpyDeviceToHost));
     std::memset(stats, 0, sizeof(*stats));
-    stats->n_paths = (uint64_t)tr.npix * spp;
+    stats->n_paths = tr.paths_from_depth0 ? h[2] : (uint64_t)tr.npix * spp;
     stats->n_texture_fetches = h[0];
     stats->n_bad_dir = h[1];
     for (int d = 0; d < n_depths; ++d) {
@@ -1241,20 +1261,41 @@ int rt_render(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, float* out_r
 
 // ---- accumulation and noise (rtow_mi355x.h "Progressive accumulation") ------------------------------------------------------------
 // The frame figures of the open accumulation: two kernels and a 24 B copy into ctx->h_noise, valid after the next wait for `st`.
+// The integer sums of an adaptive accumulation (npix > 0): with `decide` the criterion first (the start of an adaptive add), then two
+// kernels' worth of sums and a 24 B copy into ctx->h_info, valid after the next wait for `st`.
+static int enqueue_adaptive_info(RtCtx* ctx, hipStream_t st, const RtAdaptive* decide) {
+    const RtCtx::Accum& a = ctx->accum;
+    const uint32_t nb = (a.npix + 255u) / 256u;
+    AdaptiveSums* partials = (AdaptiveSums*)ctx->accum_info.p;
+    const double2* mom = (const double2*)ctx->accum_mom.p;
+    const uint32_t* cnt = (const uint32_t*)ctx->accum_cnt.p;
+    uint8_t* flag = (uint8_t*)ctx->accum_flag.p;
+    if (decide) hipLaunchKernelGGL(k_adaptive_decide<true>, dim3(nb), dim3(256), 0, st, mom, cnt, flag, partials, a.npix, decide->tolerance, decide->luminance_floor, decide->min_samples);
+    else hipLaunchKernelGGL(k_adaptive_decide<false>, dim3(nb), dim3(256), 0, st, mom, cnt, flag, partials, a.npix, 0.0, 0.0, 0u);
+    hipLaunchKernelGGL(k_adaptive_info, dim3(1), dim3(256), 0, st, (const AdaptiveSums*)partials, nb, partials + nb);
+    RT_HIP(ctx, hipMemcpyAsync(ctx->h_info, partials + nb, sizeof(RtAdaptiveInfo), hipMemcpyDeviceToHost, st));
+    return RT_OK;
+}
 static int enqueue_noise(RtCtx* ctx, hipStream_t st) {
     const RtCtx::Accum& a = ctx->accum;
     const uint32_t nb = (a.npix + 255u) / 256u;
     double2* partials = (double2*)ctx->accum_partials.p;
     double* figures = (double*)(partials + nb);
-    hipLaunchKernelGGL(k_noise_partials, dim3(nb), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, partials, a.npix, a.done);
-    hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, a.npix, a.done, figures);
+    if (a.adaptive) { // n_p per pixel; spp_min and spp_max come with the figures
+        if (const int rc = enqueue_adaptive_info(ctx, st, nullptr)) return rc;
+        hipLaunchKernelGGL(k_noise_partials_counts, dim3(nb), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, (const uint32_t*)ctx->accum_cnt.p, partials, a.npix);
+        hipLaunchKernelGGL(k_noise_final_counts, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, a.npix, (const AdaptiveSums*)ctx->accum_info.p + nb, figures);
+    } else {
+        hipLaunchKernelGGL(k_noise_partials, dim3(nb), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, partials, a.npix, a.done);
+        hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, a.npix, a.done, figures);
+    }
     RT_HIP(ctx, hipMemcpyAsync(ctx->h_noise, figures, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     return RT_OK;
 }
 static void fill_noise(const RtCtx* ctx, RtNoise* noise) {
     const RtCtx::Accum& a = ctx->accum;
     std::memset(noise, 0, sizeof(*noise));
-    noise->spp_done = a.done;
+    noise->spp_done = a.adaptive && a.npix ? ctx->h_info->spp_max : a.done;
     if (a.npix == 0u) { // a shard without rows: nothing to measure
         noise->noise = a.done < 2u ? (double)INFINITY : 0.0;
         return;
@@ -1296,6 +1337,7 @@ static int accum_add(RtCtx* ctx, uint32_t n_samples, RtStats* stats, bool figure
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
     if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_add: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_add: the accumulation is adaptive (uniform adds come before the first rt_accum_add_adaptive)");
     if (n_samples == 0u) return fail(ctx, RT_ERR_INVALID, "rt_accum_add: n_samples must be > 0");
     if ((uint64_t)a.first + a.done + n_samples > 0xFFFFFFFFull)
         return fail(ctx, RT_ERR_INVALID, "rt_accum_add: first_sample + the samples added must stay below 2^32, as RtParams.spp does");
@@ -1343,12 +1385,22 @@ int rt_accum_read(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_
     if (out_rgb_f32 && (rc = ensure(ctx, ctx->out_f32, n * sizeof(float)))) return rc;
     if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
     if (out_sem && (rc = ensure(ctx, ctx->accum_sem, (size_t)npix * sizeof(float)))) return rc;
-    if (out_rgb_f32 || out_rgb8) // (before the first add the sums are zeros: divided by 1, not by 0)
-        hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, out_rgb_f32 ? (float*)ctx->out_f32.p : (float*)nullptr,
-                           out_rgb8 ? (uint8_t*)ctx->out_u8.p : (uint8_t*)nullptr, a.nx, a.rows, std::max(a.done, 1u), a.tiles_per_row, a.tile_pixels);
-    if (out_sem)
-        hipLaunchKernelGGL(k_sem, dim3(grid), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, (float*)ctx->accum_sem.p, a.nx, a.rows, a.done,
-                           a.tiles_per_row, a.tile_pixels);
+    if (a.adaptive) { // the same two steps with the pixel's own n_p (rt_adaptive.h)
+        const uint32_t* cnt = (const uint32_t*)ctx->accum_cnt.p;
+        if (out_rgb_f32 || out_rgb8)
+            hipLaunchKernelGGL(k_finalize_counts, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, cnt, out_rgb_f32 ? (float*)ctx->out_f32.p : (float*)nullptr,
+                               out_rgb8 ? (uint8_t*)ctx->out_u8.p : (uint8_t*)nullptr, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        if (out_sem)
+            hipLaunchKernelGGL(k_sem_counts, dim3(grid), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, cnt, (float*)ctx->accum_sem.p, (uint32_t*)nullptr, a.nx, a.rows,
+                               a.tiles_per_row, a.tile_pixels);
+    } else {
+        if (out_rgb_f32 || out_rgb8) // (before the first add the sums are zeros: divided by 1, not by 0)
+            hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, out_rgb_f32 ? (float*)ctx->out_f32.p : (float*)nullptr,
+                               out_rgb8 ? (uint8_t*)ctx->out_u8.p : (uint8_t*)nullptr, a.nx, a.rows, std::max(a.done, 1u), a.tiles_per_row, a.tile_pixels);
+        if (out_sem)
+            hipLaunchKernelGGL(k_sem, dim3(grid), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, (float*)ctx->accum_sem.p, a.nx, a.rows, a.done,
+                               a.tiles_per_row, a.tile_pixels);
+    }
     if (noise && (rc = enqueue_noise(ctx, st))) return rc;
     RT_HIP(ctx, hipGetLastError());
     if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->out_f32.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -1393,6 +1445,135 @@ int rt_render_to_noise(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, dou
     ctx->accum.open = false;
     if (!rc && stats) *stats = total;
     return rc;
+}
+
+// ---- adaptive sampling (rtow_mi355x.h "Adaptive sampling", csrc/rt_adaptive.h, csrc/rt_adaptive_plan.h) ---------------------------------
+int rt_adaptive_check(const RtAdaptive* ad, uint32_t n_samples) { return adaptive_invalid(ad, n_samples) ? RT_ERR_INVALID : RT_OK; }
+int rt_adaptive_converged(const RtAdaptive* ad, double s1, double s2, uint32_t n) {
+    if (adaptive_invalid(ad, 1u)) return RT_ERR_INVALID;
+    return adaptive_converged_moments(s1, s2, n, *ad) ? 1 : 0;
+}
+
+// figures: the frame figures and the integer sums are enqueued behind the samples, so that the one wait of the call delivers them too
+static int accum_add_adaptive(RtCtx* ctx, uint32_t n_samples, const RtAdaptive* ad, RtStats* stats, bool figures) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_add_adaptive: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (const char* why = adaptive_invalid(ad, n_samples)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_add_adaptive: ") + why);
+    if ((uint64_t)a.first + a.done + n_samples > 0xFFFFFFFFull)
+        return fail(ctx, RT_ERR_INVALID, "rt_accum_add_adaptive: first_sample + the samples issued must stay below 2^32, as RtParams.spp does");
+    if (a.npix == 0u) { // a shard without rows
+        a.adaptive = true, a.done += n_samples;
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const uint32_t nb = (a.npix + 255u) / 256u;
+    int rc;
+    if (!a.adaptive) { // the first adaptive add: n_p = what the uniform adds gave every pixel, nobody converged
+        if ((rc = ensure(ctx, ctx->accum_cnt, (size_t)a.npix * sizeof(uint32_t)))) return rc;
+        if ((rc = ensure(ctx, ctx->accum_flag, (size_t)a.npix))) return rc;
+        if ((rc = ensure(ctx, ctx->accum_info, ((size_t)nb + 1u) * sizeof(AdaptiveSums)))) return rc;
+        if (!ctx->h_info) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_info, sizeof(RtAdaptiveInfo), hipHostMallocDefault));
+        hipLaunchKernelGGL(k_adaptive_begin, dim3(nb), dim3(256), 0, st, (uint32_t*)ctx->accum_cnt.p, (uint8_t*)ctx->accum_flag.p, a.npix, a.done);
+        a.adaptive = true;
+    }
+    if ((rc = enqueue_adaptive_info(ctx, st, ad))) return rc; // the decision
+    RtParams p = a.prm;
+    p.spp = n_samples;
+    Traced tr;
+    SampleSink sink{(float*)ctx->accum_sum.p, (double2*)ctx->accum_mom.p, a.first + a.done};
+    sink.converged = (const uint8_t*)ctx->accum_flag.p, sink.cnt = (uint32_t*)ctx->accum_cnt.p;
+    if ((rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr))) return rc;
+    if (tr.npix != a.npix || tr.tiles_per_row != a.tiles_per_row || tr.tile_pixels != a.tile_pixels) {
+        a.open = false; // (cannot happen: everything the order hangs on ends the accumulation)
+        return fail(ctx, RT_ERR_STATE, "rt_accum_add_adaptive: the pixel order changed since rt_accum_begin (internal)");
+    }
+    a.done += n_samples;
+    if (figures && (rc = enqueue_noise(ctx, tr.st))) return rc;
+    RT_HIP(ctx, hipEventRecord(ctx->ev_end, tr.st));
+    RT_HIP(ctx, hipGetLastError());
+    ctx->mark("enqueue_all_launches");
+    if (stats) return read_stats(ctx, tr, n_samples, stats);
+    if (figures) RT_HIP(ctx, hipStreamSynchronize(tr.st));
+    return RT_OK;
+}
+
+int rt_accum_add_adaptive(RtCtx* ctx, uint32_t n_samples, const RtAdaptive* ad, RtStats* stats) { return accum_add_adaptive(ctx, n_samples, ad, stats, false); }
+
+int rt_accum_read_counts(RtCtx* ctx, uint32_t* out_counts, RtAdaptiveInfo* info) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_read_counts: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!a.adaptive || a.npix == 0u) { // uniform so far: every pixel holds `done` samples and is active
+        if (out_counts) std::fill(out_counts, out_counts + a.npix, a.done);
+        if (info) info->n_active = a.npix, info->n_samples = (uint64_t)a.npix * a.done, info->spp_min = info->spp_max = a.done;
+        return RT_OK;
+    }
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    int rc;
+    if (out_counts) {
+        if ((rc = ensure(ctx, ctx->accum_cnt_out, (size_t)a.npix * sizeof(uint32_t)))) return rc;
+        hipLaunchKernelGGL(k_sem_counts, dim3((a.npix + 255u) / 256u), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, (const uint32_t*)ctx->accum_cnt.p,
+                           (float*)nullptr, (uint32_t*)ctx->accum_cnt_out.p, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        RT_HIP(ctx, hipMemcpyAsync(out_counts, ctx->accum_cnt_out.p, (size_t)a.npix * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    if (info && (rc = enqueue_adaptive_info(ctx, st, nullptr))) return rc;
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    if (info) *info = *ctx->h_info;
+    return RT_OK;
+}
+
+static void add_stats(RtStats& total, const RtStats& s) {
+    total.n_paths += s.n_paths, total.n_rays += s.n_rays, total.n_rays_secondary += s.n_rays_secondary;
+    total.n_texture_fetches += s.n_texture_fetches, total.n_bad_dir += s.n_bad_dir;
+    total.seconds_total += s.seconds_total, total.seconds_trace += s.seconds_trace, total.seconds_device += s.seconds_device;
+    total.bytes_algorithmic += s.bytes_algorithmic, total.bytes_trace_algorithmic += s.bytes_trace_algorithmic;
+    total.n_trace_launches += s.n_trace_launches, total.n_slices += s.n_slices;
+    for (int d = 0; d < 64; ++d) total.rays_per_depth[d] += s.rays_per_depth[d];
+}
+
+int rt_render_adaptive(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, const RtAdaptive* ad, uint32_t spp_step, float* out_rgb_f32,
+                       uint8_t* out_rgb8, float* out_sem, uint32_t* out_counts, RtNoise* noise, RtAdaptiveInfo* info, RtStats* stats) {
+    int rc = check_params(ctx, cam, prm);
+    if (rc) return rc;
+    if (ctx->accum.open) return fail(ctx, RT_ERR_STATE, "rt_render_adaptive: an accumulation is open (rt_accum_end it first)");
+    if (spp_step == 0u) return fail(ctx, RT_ERR_INVALID, "rt_render_adaptive: spp_step must be > 0");
+    if (const char* why = adaptive_invalid(ad, spp_step)) return fail(ctx, RT_ERR_INVALID, std::string("rt_render_adaptive: ") + why);
+    if (prm->spp < 2u) return fail(ctx, RT_ERR_INVALID, "rt_render_adaptive: spp, the maximum, must be >= 2 (one sample has no variance estimate)");
+    RtParams p = *prm;
+    p.spp = std::min(spp_step, prm->spp); // (the expected size of one add)
+    if ((rc = rt_accum_begin(ctx, cam, &p, 0u))) return rc;
+    RtStats total;
+    std::memset(&total, 0, sizeof(total));
+    while (ctx->accum.done < prm->spp) {
+        RtStats s;
+        if ((rc = accum_add_adaptive(ctx, std::min(spp_step, prm->spp - ctx->accum.done), ad, &s, true))) break;
+        add_stats(total, s);
+        if (ctx->accum.npix == 0u || ctx->h_info->n_active == 0u) break; // (this add found nobody active and traced nothing)
+    }
+    if (!rc) rc = rt_accum_read(ctx, out_rgb_f32, out_rgb8, out_sem, noise);
+    if (!rc && (out_counts || info)) rc = rt_accum_read_counts(ctx, out_counts, info);
+    ctx->accum.open = false;
+    if (!rc && stats) *stats = total;
+    return rc;
+}
+
+int rt_debug_accum_set_moments(RtCtx* ctx, uint32_t pixel, double s1, double s2) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_debug_accum_set_moments: no accumulation begun");
+    if (pixel >= a.npix) return fail(ctx, RT_ERR_INVALID, "rt_debug_accum_set_moments: pixel outside the shard");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ap = local_of_pixel(a.nx, a.tiles_per_row, a.tile_pixels, pixel % a.nx, pixel / a.nx);
+    const double2 m = make_double2(s1, s2);
+    RT_HIP(ctx, hipMemcpyAsync((double2*)ctx->accum_mom.p + ap, &m, sizeof(m), hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
 }
 
 // ---- denoising (rtow_mi355x.h "Denoising", csrc/rt_denoise.h) -----------------------------------------------------------------------
@@ -1444,8 +1625,12 @@ int rt_accum_denoise(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_
     const size_t n = (size_t)npix * 3;
     if ((rc = ensure_denoise(ctx, npix))) return rc;
     if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
-    hipLaunchKernelGGL(k_denoise_inputs, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, (const double2*)ctx->accum_mom.p, (float*)ctx->dn_c.p,
-                       (float2*)ctx->dn_yv.p, a.nx, a.rows, a.done, a.tiles_per_row, a.tile_pixels);
+    if (a.adaptive) // (every n_p >= 2: a pixel stops on min_samples >= 2 at the earliest, and done >= 2 was checked)
+        hipLaunchKernelGGL(k_denoise_inputs_counts, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, (const double2*)ctx->accum_mom.p,
+                           (const uint32_t*)ctx->accum_cnt.p, (float*)ctx->dn_c.p, (float2*)ctx->dn_yv.p, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+    else
+        hipLaunchKernelGGL(k_denoise_inputs, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, (const double2*)ctx->accum_mom.p, (float*)ctx->dn_c.p,
+                           (float2*)ctx->dn_yv.p, a.nx, a.rows, a.done, a.tiles_per_row, a.tile_pixels);
     launch_denoise(st, (const float*)ctx->dn_c.p, (const float2*)ctx->dn_yv.p, (float*)ctx->dn_out.p, a.nx, a.rows, d);
     if (out_rgb8) // k_finalize's quantisation and flip of the filtered image: row-major (no tiles), and / (float)1 changes no bit
         hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, st, (const float*)ctx->dn_out.p, (float*)nullptr, (uint8_t*)ctx->out_u8.p, a.nx, a.rows, 1u, 0u,

@@ -10,6 +10,8 @@ import argparse
 import sys
 import time
 
+import numpy as np
+
 from . import Renderer, Scene, make_params, output_file_name, register_default_images, save_png
 from . import _ffi
 
@@ -42,6 +44,15 @@ def main(argv=None):
     ap.add_argument("--spp-step", type=int, default=64, metavar="N",
                     help="samples per pixel between two looks at the noise (with --noise-target); a step costs about 2 ms beyond its samples at "
                          "1920 x 1080 (DESIGN.md \"Accumulation and noise\"): 64 keeps that below a fifth")
+    ap.add_argument("--adaptive-tolerance", type=float, default=None, metavar="T",
+                    help="adaptive sampling: in steps of --spp-step, a pixel stops once the standard error of its mean luminance is at most "
+                         "T x max(mean luminance, --luminance-floor); the others go on until --spp, the maximum (rt_render_adaptive)")
+    ap.add_argument("--min-spp", type=int, default=16, metavar="N", help="with --adaptive-tolerance: no pixel stops on fewer samples (>= 2)")
+    ap.add_argument("--luminance-floor", type=float, default=0.01, metavar="L",
+                    help="with --adaptive-tolerance: below this mean luminance the error is measured against L (a floor near the frame's "
+                         "mean luminance makes the criterion an absolute one for the darker pixels)")
+    ap.add_argument("--counts-out", default=None, metavar="FILE",
+                    help="with --adaptive-tolerance: the per-pixel sample counts as a grey PNG, white = --spp")
     ap.add_argument("--denoise", action="store_true",
                     help="save the frame through the variance-guided non-local-means filter (rt_accum_denoise); needs --spp >= 2")
     ap.add_argument("--denoise-radius", type=int, default=5, metavar="R", help="search window radius, 1..%d" % _ffi.DENOISE_MAX_RADIUS)
@@ -72,6 +83,10 @@ def main(argv=None):
     if a.light_sampling:
         rend.set_lights(scene.lights)  # (a moving scene refuses it: RT_ERR_UNSUPPORTED)
     flags = _ffi.FLAG_RUSSIAN_ROULETTE if a.russian_roulette else 0
+    if a.adaptive_tolerance is not None:
+        if a.noise_target is not None or a.denoise or a.preview_every:
+            ap.error("--adaptive-tolerance does not combine with --noise-target, --denoise or --preview-every")
+        return render_adaptive(a, rend, scene, flags, file_name, t0)
     if a.noise_target is not None:
         return render_to_noise(a, rend, scene, flags, file_name, t0)
     if a.denoise:
@@ -117,6 +132,22 @@ def render_to_noise(a, rend, scene, flags, file_name, t0):
     print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
     print(f"{file_name}: {a.nx}x{a.ny}, {noise.spp_done} of at most {a.spp} spp, noise {noise.noise:.4g} (target {a.noise_target:g}), "
           f"{n_rays} rays, {n_rays / seconds / 1e6:.0f} Mray/s on the device{', denoised' if a.denoise else ''}", file=sys.stderr)
+    return 0
+
+
+def render_adaptive(a, rend, scene, flags, file_name, t0):
+    """--adaptive-tolerance: rt_render_adaptive in steps of --spp-step up to --spp; --counts-out saves the sample-count map."""
+    params = make_params(a.nx, a.ny, a.spp, max_depth=a.max_depth, seed=a.seed, flags=flags)
+    _, rgb8, _, counts, noise, info, st = rend.render_adaptive(scene.camera, params, a.adaptive_tolerance, a.spp_step, a.luminance_floor, a.min_spp,
+                                                               want_rgb8=True)
+    print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
+    save_png(file_name, rgb8)
+    if a.counts_out:
+        grey = np.minimum(counts.astype(np.float64) * (255.0 / max(a.spp, 1)), 255.0).astype(np.uint8)[::-1]  # (row 0 of the counts is the bottom row)
+        save_png(a.counts_out, np.ascontiguousarray(np.repeat(grey[..., None], 3, axis=2)))
+    print(f"{file_name}: {a.nx}x{a.ny}, {info.n_samples / max(counts.size, 1):.1f} spp on average ({info.spp_min}..{info.spp_max} of at most {a.spp}), "
+          f"{info.n_active} pixels still active, noise {noise.noise:.4g}, {st.n_rays} rays, "
+          f"{st.n_rays / max(st.seconds_device, 1e-9) / 1e6:.0f} Mray/s on the device", file=sys.stderr)
     return 0
 
 
