@@ -582,8 +582,9 @@ int rt_adaptive_converged(const RtAdaptive* ad, double s1, double s2, uint32_t n
  * makes every D NaN.  A non-finite pixel does not spread: any patch that holds it has D = NaN, u = 0, and such terms are skipped, not
  * multiplied by 0.  For a finite p the term q = p has D <= 0 and w = 1, so den >= 1.
  * The order of the sums is part of the definition; it lets row sums be shared between neighbouring pixels without changing a bit.
- * Not covered: the distance is on LUMINANCE, the one quantity whose variance the accumulation keeps — edges between colours of equal
- * luminance blur (per-channel moments would cost 48 B per pixel more and change k_resolve_moments); the weights are chosen from the
+ * Not covered: the distance is on LUMINANCE, the one quantity whose variance an accumulation keeps by default — edges between colours of
+ * equal luminance blur; "Channel moments and the colour-guided filter" below keeps a variance per channel (48 B per pixel more, opt-in)
+ * and filters on it; the weights are chosen from the
  * image they filter (there are no two half buffers, so the filter is slightly biased towards its own noise); rt_multi_* is not supported.
  * DESIGN.md "Denoising". */
 typedef struct RtDenoise { uint32_t radius, patch; float strength; uint32_t reserved; } RtDenoise;
@@ -598,6 +599,39 @@ typedef struct RtDenoise { uint32_t radius, patch; float strength; uint32_t rese
  * the image).  RT_ERR_INVALID: radius 0 or above the maximum, patch above the maximum, strength non-finite or <= 0, reserved != 0.  A
  * shard without pixels: RT_OK, nothing is written. */
 int rt_accum_denoise(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8);
+
+/* -- channel moments and the colour-guided filter ------------------------------------------------------------------------------------------
+ * The filter above cannot tell two colours of equal luminance apart, and more samples only make it surer that they are "the same".  An
+ * accumulation that TRACKS CHANNELS also keeps, per pixel and channel c in {r, g, b}, two f64 moments of the f32 sample values x_c — the
+ * values the running sum reads — every operation one IEEE f64 operation, no FMA:
+ *   S1_c += (double)x_c;   S2_c += (double)x_c * (double)x_c   in sample order, across slices and adds, uniform or adaptive.
+ * With n samples (n_p of the pixel after adaptive adds):  V_c = max(0, (S2_c - S1_c * S1_c / n) / (n - 1)) / n, V_c = 0 where n < 2; a
+ * NaN stays a NaN, as in "Moments".  Cost: 48 B per pixel more, in the local pixel order of the sums, allocated by
+ * rt_accum_track_channels and kept for the next accumulation like the other accumulation buffers; the first rt_accum_denoise_channels of a
+ * context adds 24 B per pixel (its inputs) to the filter's 12 B output.  Everything an accumulation returned before — the running sum,
+ * the luminance moments, out_sem, the frame figures, the counts, rt_accum_denoise, the defining properties of "Progressive accumulation"
+ * and "Adaptive sampling" — is unchanged in every bit, with tracking on or off.
+ * The colour-guided filter is "Denoising" word for word with these differences:
+ *   Inputs.  c_a as there;  v_a,ch = (float)V_ch, the three channel variances of pixel a.
+ *   Per-channel term.  d_ch(a, b) = ((c_a,ch - c_b,ch) * (c_a,ch - c_b,ch) - (v_a,ch + min(v_a,ch, v_b,ch))) / (eps + k2 * (v_a,ch + v_b,ch)),
+ *     min(x, y) = y < x ? y : x.  The term of one patch offset is e = (d_r + d_g) + d_b.
+ *   Patch sum.  S = 0;  for oy = -F..F: { row = 0;  for ox = -F..F: row = row + e(clamp(p + o), clamp(q + o));  S = S + row; }
+ *     D = S / cnt3,  cnt3 = (float)(3*(2F+1)*(2F+1)).
+ * The clamp per axis, the weight with its NaN rules, "accumulate only where u != 0", out = num / den, out = c_p where den == 0 and the
+ * visiting order of delta are those of "Denoising"; a non-finite pixel spreads to no other, for the same reason.
+ * Not covered: rt_multi_*; sharded frames for the filter (RT_ERR_UNSUPPORTED, as rt_accum_denoise); a per-channel adaptive criterion
+ * (rt_accum_add_adaptive decides on luminance); rt_render_to_noise and rt_render_adaptive, which open and end their own accumulation — a
+ * host that wants the filter drives the adds itself.  DESIGN.md "Channel moments and the colour-guided filter". */
+/* Makes the open accumulation track channels and clears the channel moments.  After rt_accum_begin and before the first add, uniform or
+ * adaptive: RT_ERR_STATE without an open accumulation or after samples were added.  A second call is RT_OK and changes nothing.  Tracking
+ * ends with the accumulation, through every call that rt_accum_end lists as ending one. */
+int rt_accum_track_channels(RtCtx* ctx);
+/* out_sem_rgb [rows_local*nx*3] = (float)sqrt(V_c), in the row order of out_rgb_f32; with n_p per pixel after adaptive adds.  Works on
+ * shards.  Synchronises the context's stream once.  RT_ERR_STATE: no open accumulation, or it does not track channels. */
+int rt_accum_read_channel_sem(RtCtx* ctx, float* out_sem_rgb);
+/* rt_accum_denoise with the colour-guided filter: the same arguments, defaults, outputs and errors, the accumulation read and not changed.
+ * RtDenoise.reserved stays 0.  In addition RT_ERR_STATE where the accumulation does not track channels. */
+int rt_accum_denoise_channels(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8);
 
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the

@@ -242,6 +242,10 @@ int rt_debug_arithmetic(RtCtx* ctx, uint32_t op, uint32_t n, const float* x, con
  * array, nx * rows outside 1 .. 2^28, or parameters rt_accum_denoise would refuse. */
 int rt_debug_denoise(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* y, const float* v, const RtDenoise* dn,
                      float* out_rgb_f32);
+/* The same for the colour-guided filter of rt_accum_denoise_channels (rtow_mi355x.h "channel moments and the colour-guided filter"):
+ * rgb [3 * nx * rows] = c and var_rgb [3 * nx * rows] = the three channel variances, both in image order; errors as rt_debug_denoise. */
+int rt_debug_denoise_channels(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* var_rgb, const RtDenoise* dn,
+                              float* out_rgb_f32);
 
 /* Test hook for adaptive sampling (rtow_mi355x.h "adaptive sampling"): overwrites the two luminance moments (S1, S2) of pixel `pixel` of
  * the open accumulation, `pixel` an index into out_sem (row order of out_rgb_f32).  The tests plant a NaN with it: such a pixel never

@@ -197,6 +197,7 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_set_lights", "rt_multi_set_lights",
                "rt_accum_begin", "rt_accum_add", "rt_accum_read", "rt_accum_end", "rt_render_to_noise",
                "rt_accum_denoise", "rt_debug_denoise",
+               "rt_accum_track_channels", "rt_accum_read_channel_sem", "rt_accum_denoise_channels", "rt_debug_denoise_channels",
                "rt_accum_add_adaptive", "rt_accum_read_counts", "rt_render_adaptive", "rt_adaptive_check", "rt_adaptive_converged",
                "rt_debug_accum_set_moments",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
@@ -292,6 +293,14 @@ def load_gpu_library():
     lib.rt_accum_denoise.restype = C.c_int
     lib.rt_debug_denoise.argtypes = [vp, C.c_uint32, C.c_uint32, _f, _f, _f, C.POINTER(RtDenoise), _f]
     lib.rt_debug_denoise.restype = C.c_int
+    lib.rt_accum_track_channels.argtypes = [vp]
+    lib.rt_accum_track_channels.restype = C.c_int
+    lib.rt_accum_read_channel_sem.argtypes = [vp, _f]
+    lib.rt_accum_read_channel_sem.restype = C.c_int
+    lib.rt_accum_denoise_channels.argtypes = [vp, C.POINTER(RtDenoise), _f, _u8]
+    lib.rt_accum_denoise_channels.restype = C.c_int
+    lib.rt_debug_denoise_channels.argtypes = [vp, C.c_uint32, C.c_uint32, _f, _f, C.POINTER(RtDenoise), _f]
+    lib.rt_debug_denoise_channels.restype = C.c_int
     lib.rt_accum_add_adaptive.argtypes = [vp, C.c_uint32, C.POINTER(RtAdaptive), C.POINTER(RtStats)]
     lib.rt_accum_add_adaptive.restype = C.c_int
     lib.rt_accum_read_counts.argtypes = [vp, _u32, C.POINTER(RtAdaptiveInfo)]

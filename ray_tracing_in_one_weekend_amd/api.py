@@ -681,6 +681,44 @@ class Renderer:
             self._raise("rt_debug_denoise", rc)
         return out
 
+    def accum_track_channels(self):
+        """rt_accum_track_channels: the open accumulation also keeps two f64 moments per pixel and channel (48 B per pixel); right after
+        accum_begin, before the first add.  Everything else the accumulation returns stays bit for bit."""
+        rc = self._lib.rt_accum_track_channels(self._ctx)
+        if rc != 0:
+            self._raise("rt_accum_track_channels", rc)
+
+    def accum_channel_sem(self):
+        """rt_accum_read_channel_sem: [rows, nx, 3] f32, the standard error of each pixel's mean per channel, laid out as accum_read's image."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        sem = np.zeros((rows, nx, 3), dtype=np.float32)
+        rc = self._lib.rt_accum_read_channel_sem(self._ctx, sem.ctypes.data_as(C.POINTER(C.c_float)))
+        if rc != 0:
+            self._raise("rt_accum_read_channel_sem", rc)
+        return sem
+
+    def accum_denoise_channels(self, radius=5, patch=1, strength=None, want_rgb8=False):
+        """rt_accum_denoise_channels: accum_denoise with the distance on the three channels and their own variances, so that edges between
+        colours of equal luminance stay; the accumulation must track channels (accum_track_channels).  Returns (img, rgb8 or None)."""
+        img, rgb8, _, ptrs = self._accum_outputs(want_rgb8, False)
+        rc = self._lib.rt_accum_denoise_channels(self._ctx, self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
+        if rc != 0:
+            self._raise("rt_accum_denoise_channels", rc)
+        return img, rgb8
+
+    def debug_denoise_channels(self, rgb, var_rgb, radius=5, patch=1, strength=None):
+        """rt_debug_denoise_channels: the filter kernel of accum_denoise_channels over host arrays in image order — rgb and var_rgb
+        [rows, nx, 3] (a pixel's channel means and the variances of those means); returns the filtered [rows, nx, 3] f32 image."""
+        rgb, var_rgb = np.ascontiguousarray(rgb, dtype=np.float32), np.ascontiguousarray(var_rgb, dtype=np.float32)
+        rows, nx, _ = rgb.shape
+        assert rgb.shape == (rows, nx, 3) == var_rgb.shape
+        out = np.zeros_like(rgb)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        rc = self._lib.rt_debug_denoise_channels(self._ctx, nx, rows, fp(rgb), fp(var_rgb), self._denoise_ptr(radius, patch, strength), fp(out))
+        if rc != 0:
+            self._raise("rt_debug_denoise_channels", rc)
+        return out
+
     def set_progress(self, fn):
         """fn(spp_done, spp_total, rgb8[rows, nx, 3]) after every slice but the last of a following render()
         (main.rs:114-123, the partial saves); None removes it.  Pick the cadence with make_params(spp_slice=...)."""

@@ -4,6 +4,7 @@
 #include "../../include/rtow_mi355x_debug.h"
 #include "rt_kernels.h"
 #include "rt_denoise.h"
+#include "rt_channels.h"
 #include "rt_adaptive.h"
 #include "rt_bvh.h"
 #include "rt_grid.h"
@@ -129,6 +130,7 @@ struct RtCtx {
         uint32_t first = 0, done = 0; // the next sample to trace is first + done
         uint32_t nx = 0, rows = 0, npix = 0, tiles_per_row = 0, tile_pixels = 0;
         bool adaptive = false; // an adaptive add has happened: accum_cnt / accum_flag hold n_p and the converged flags, `done` is the n_p of the active pixels
+        bool channels = false; // rt_accum_track_channels: accum_chm holds the channel moments and every add keeps them
     } accum;
     DevBuf accum_sum, accum_mom, accum_sem, accum_partials; // (accum_sem: staging of out_sem; accum_partials: one f64 pair per workgroup + the 3 frame figures)
     double* h_noise = nullptr;   // page-locked: mean_luminance, rms_sem, noise as k_noise_final wrote them
@@ -136,6 +138,9 @@ struct RtCtx {
     // add; accum_info: the integer partial sums of k_adaptive_decide (one per workgroup) + the frame's RtAdaptiveInfo behind them
     DevBuf accum_cnt, accum_flag, accum_info, accum_cnt_out; // (accum_cnt_out: staging of out_counts)
     RtAdaptiveInfo* h_info = nullptr; // page-locked: the frame's sums as k_adaptive_info wrote them
+    // rt_accum_track_channels (rt_channels.h): three planes of f64 x 2 channel moments, 48 B per pixel, each in the order of accum_sum;
+    // accum_chsem: staging of out_sem_rgb; dn_cv: the inputs of rt_accum_denoise_channels, (c, v) x 3 per pixel in image order, 24 B
+    DevBuf accum_chm, accum_chsem, dn_cv;
     DevBuf dn_c, dn_yv, dn_out;  // rt_accum_denoise: the filter's inputs (c 12 B, (y, v) 8 B) and its output (12 B) per pixel, in image order
     // Host-side timeline of the last trace_samples and what its caller enqueued behind it (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
     // render of a process is where allocations, code-object loads and the queue probe happen; this says which.
@@ -718,6 +723,7 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->acc), free_buf(ctx->counts), free_buf(ctx->totals);
     free_buf(ctx->out_f32), free_buf(ctx->out_u8), free_buf(ctx->dbg), free_buf(ctx->genp);
     free_buf(ctx->preview_u8), free_buf(ctx->lists);
+    free_buf(ctx->accum_chm), free_buf(ctx->accum_chsem), free_buf(ctx->dn_cv);
     free_buf(ctx->accum_sum), free_buf(ctx->accum_mom), free_buf(ctx->accum_sem), free_buf(ctx->accum_partials);
     free_buf(ctx->accum_cnt), free_buf(ctx->accum_flag), free_buf(ctx->accum_info), free_buf(ctx->accum_cnt_out);
     if (ctx->h_info) (void)hipHostFree(ctx->h_info);
@@ -859,6 +865,8 @@ struct SampleSink {
     // the materialised queue, filled by k_gen_primary_active with the rays of the other pixels only.
     const uint8_t* converged = nullptr;
     uint32_t* cnt = nullptr;
+    // rt_accum_track_channels (rt_channels.h): the channel moments the resolve keeps beside `mom`
+    double2* chm = nullptr;
 };
 // What trace_samples enqueued, for the finalize, the copies and the statistics of its caller.
 struct Traced {
@@ -1072,7 +1080,12 @@ static int enqueue_slice(RtCtx* ctx, Frame& f, const WorkView& wv, uint32_t sl) 
 static int resolve_and_preview(RtCtx* ctx, const Frame& f, const SampleSink& sink, const float* rad, uint32_t sc, uint32_t done, uint32_t rows) {
     const hipStream_t st = f.st;
     const uint32_t npix = f.npix, spp = f.prm->spp, nx = f.prm->nx;
-    if (sink.converged) hipLaunchKernelGGL(k_resolve_moments_active, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.converged, sink.cnt, npix, sc);
+    if (sink.chm && sink.converged)
+        hipLaunchKernelGGL(k_resolve_moments_channels<true>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.chm, sink.converged, sink.cnt, npix, sc);
+    else if (sink.chm)
+        hipLaunchKernelGGL(k_resolve_moments_channels<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.chm, (const uint8_t*)nullptr,
+                           (uint32_t*)nullptr, npix, sc);
+    else if (sink.converged) hipLaunchKernelGGL(k_resolve_moments_active, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.converged, sink.cnt, npix, sc);
     else if (sink.mom) hipLaunchKernelGGL(k_resolve_moments, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, npix, sc);
     else hipLaunchKernelGGL(k_resolve, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, npix, sc);
     hipLaunchKernelGGL(k_accum_counts, dim3((unsigned)f.n_depths), dim3(256), 0, st, f.counts, f.d.nq, (uint32_t)f.n_depths, f.totals + 2);
@@ -1344,7 +1357,8 @@ static int accum_add(RtCtx* ctx, uint32_t n_samples, RtStats* stats, bool figure
     RtParams p = a.prm;
     p.spp = n_samples;
     Traced tr;
-    const SampleSink sink{(float*)ctx->accum_sum.p, (double2*)ctx->accum_mom.p, a.first + a.done};
+    SampleSink sink{(float*)ctx->accum_sum.p, (double2*)ctx->accum_mom.p, a.first + a.done};
+    if (a.channels) sink.chm = (double2*)ctx->accum_chm.p;
     const int rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr);
     if (rc) return rc;
     if (tr.npix == 0u) {
@@ -1485,6 +1499,7 @@ static int accum_add_adaptive(RtCtx* ctx, uint32_t n_samples, const RtAdaptive* 
     Traced tr;
     SampleSink sink{(float*)ctx->accum_sum.p, (double2*)ctx->accum_mom.p, a.first + a.done};
     sink.converged = (const uint8_t*)ctx->accum_flag.p, sink.cnt = (uint32_t*)ctx->accum_cnt.p;
+    if (a.channels) sink.chm = (double2*)ctx->accum_chm.p;
     if ((rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr))) return rc;
     if (tr.npix != a.npix || tr.tiles_per_row != a.tiles_per_row || tr.tile_pixels != a.tile_pixels) {
         a.open = false; // (cannot happen: everything the order hangs on ends the accumulation)
@@ -1658,6 +1673,121 @@ int rt_debug_denoise(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, c
     RT_HIP(ctx, hipMemcpyAsync(ctx->dn_c.p, rgb, npix * 3 * sizeof(float), hipMemcpyHostToDevice, st));
     RT_HIP(ctx, hipMemcpyAsync(ctx->dn_yv.p, yv.data(), npix * sizeof(float2), hipMemcpyHostToDevice, st));
     launch_denoise(st, (const float*)ctx->dn_c.p, (const float2*)ctx->dn_yv.p, (float*)ctx->dn_out.p, nx, rows, d);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->dn_out.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+// ---- channel moments and the colour-guided filter (rtow_mi355x.h "Channel moments and the colour-guided filter", csrc/rt_channels.h) ------
+int rt_accum_track_channels(RtCtx* ctx) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_track_channels: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (a.channels) return RT_OK;
+    if (a.done != 0u || a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_track_channels: samples were added already (call it right after rt_accum_begin)");
+    if (a.npix) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        const size_t bytes = (size_t)a.npix * 3 * sizeof(double2);
+        if (const int rc = ensure(ctx, ctx->accum_chm, bytes)) return rc;
+        RT_HIP(ctx, hipMemsetAsync(ctx->accum_chm.p, 0, bytes, ctx->stream));
+    }
+    a.channels = true;
+    return RT_OK;
+}
+
+int rt_accum_read_channel_sem(RtCtx* ctx, float* out_sem_rgb) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_read_channel_sem: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (!a.channels) return fail(ctx, RT_ERR_STATE, "rt_accum_read_channel_sem: the accumulation does not track channels (rt_accum_track_channels)");
+    if (!out_sem_rgb) return fail(ctx, RT_ERR_INVALID, "rt_accum_read_channel_sem: NULL array");
+    if (a.npix == 0u) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const uint32_t grid = (a.npix + 255u) / 256u;
+    const size_t bytes = (size_t)a.npix * 3 * sizeof(float);
+    if (const int rc = ensure(ctx, ctx->accum_chsem, bytes)) return rc;
+    if (a.adaptive)
+        hipLaunchKernelGGL(k_channel_sem<true>, dim3(grid), dim3(256), 0, st, (const double2*)ctx->accum_chm.p, (const uint32_t*)ctx->accum_cnt.p,
+                           (float*)ctx->accum_chsem.p, a.nx, a.rows, 0u, a.tiles_per_row, a.tile_pixels);
+    else
+        hipLaunchKernelGGL(k_channel_sem<false>, dim3(grid), dim3(256), 0, st, (const double2*)ctx->accum_chm.p, (const uint32_t*)nullptr,
+                           (float*)ctx->accum_chsem.p, a.nx, a.rows, a.done, a.tiles_per_row, a.tile_pixels);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(out_sem_rgb, ctx->accum_chsem.p, bytes, hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+// k_denoise_channels over an image in image order: cv -> out (device pointers), nx, rows >= 1
+static void launch_denoise_channels(hipStream_t st, const float2* cv, float* out, uint32_t nx, uint32_t rows, const RtDenoise& d) {
+    const dim3 grid((nx + RT_DN_TILE - 1u) / RT_DN_TILE, (rows + RT_DN_TILE - 1u) / RT_DN_TILE), block(RT_DN_TILE, RT_DN_TILE);
+    const int R = (int)d.radius;
+    const float k2 = d.strength * d.strength;
+    const size_t lds = denoise_channels_lds_bytes(d.radius, d.patch);
+    switch (d.patch) {
+    case 0u: hipLaunchKernelGGL(k_denoise_channels<0>, grid, block, lds, st, cv, out, nx, rows, R, k2); break;
+    case 1u: hipLaunchKernelGGL(k_denoise_channels<1>, grid, block, lds, st, cv, out, nx, rows, R, k2); break;
+    case 2u: hipLaunchKernelGGL(k_denoise_channels<2>, grid, block, lds, st, cv, out, nx, rows, R, k2); break;
+    default: hipLaunchKernelGGL(k_denoise_channels<3>, grid, block, lds, st, cv, out, nx, rows, R, k2); break;
+    }
+}
+static int ensure_denoise_channels(RtCtx* ctx, size_t npix) {
+    if (const int rc = ensure(ctx, ctx->dn_cv, npix * 3 * sizeof(float2))) return rc;
+    return ensure(ctx, ctx->dn_out, npix * 3 * sizeof(float));
+}
+
+int rt_accum_denoise_channels(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_channels: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (!a.channels) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_channels: the accumulation does not track channels (rt_accum_track_channels)");
+    RtDenoise d;
+    int rc = denoise_params(ctx, dn, d, "rt_accum_denoise_channels");
+    if (rc) return rc;
+    if (a.prm.shard_count > 1u)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_denoise_channels: a sharded frame (shard_count > 1): the local rows of a shard are not neighbours in the image");
+    if (a.done < 2u) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_channels: fewer than 2 samples accumulated: there is no variance yet");
+    if (a.npix == 0u) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const uint32_t npix = a.npix, grid = (npix + 255u) / 256u;
+    const size_t n = (size_t)npix * 3;
+    if ((rc = ensure_denoise_channels(ctx, npix))) return rc;
+    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
+    if (a.adaptive) // (every n_p >= 2, as in rt_accum_denoise)
+        hipLaunchKernelGGL(k_denoise_inputs_channels<true>, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, (const double2*)ctx->accum_chm.p,
+                           (const uint32_t*)ctx->accum_cnt.p, (float2*)ctx->dn_cv.p, a.nx, a.rows, 0u, a.tiles_per_row, a.tile_pixels);
+    else
+        hipLaunchKernelGGL(k_denoise_inputs_channels<false>, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, (const double2*)ctx->accum_chm.p,
+                           (const uint32_t*)nullptr, (float2*)ctx->dn_cv.p, a.nx, a.rows, a.done, a.tiles_per_row, a.tile_pixels);
+    launch_denoise_channels(st, (const float2*)ctx->dn_cv.p, (float*)ctx->dn_out.p, a.nx, a.rows, d);
+    if (out_rgb8) // k_finalize's quantisation and flip of the filtered image, as in rt_accum_denoise
+        hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, st, (const float*)ctx->dn_out.p, (float*)nullptr, (uint8_t*)ctx->out_u8.p, a.nx, a.rows, 1u, 0u,
+                           0u);
+    RT_HIP(ctx, hipGetLastError());
+    if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->dn_out.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (out_rgb8) RT_HIP(ctx, hipMemcpyAsync(out_rgb8, ctx->out_u8.p, n, hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+int rt_debug_denoise_channels(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* var_rgb, const RtDenoise* dn, float* out_rgb_f32) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!rgb || !var_rgb || !out_rgb_f32) return fail(ctx, RT_ERR_INVALID, "rt_debug_denoise_channels: NULL array");
+    if (nx == 0u || rows == 0u || (uint64_t)nx * rows > (1ull << 28)) return fail(ctx, RT_ERR_INVALID, "rt_debug_denoise_channels: nx * rows must be 1 .. 2^28");
+    RtDenoise d;
+    int rc = denoise_params(ctx, dn, d, "rt_debug_denoise_channels");
+    if (rc) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t npix = (size_t)nx * rows;
+    if ((rc = ensure_denoise_channels(ctx, npix))) return rc;
+    std::vector<float2> cv(3 * npix);
+    for (size_t k = 0; k < 3 * npix; ++k) cv[k] = make_float2(rgb[k], var_rgb[k]);
+    const hipStream_t st = ctx->stream;
+    RT_HIP(ctx, hipMemcpyAsync(ctx->dn_cv.p, cv.data(), 3 * npix * sizeof(float2), hipMemcpyHostToDevice, st));
+    launch_denoise_channels(st, (const float2*)ctx->dn_cv.p, (float*)ctx->dn_out.p, nx, rows, d);
     RT_HIP(ctx, hipGetLastError());
     RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->dn_out.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
     RT_HIP(ctx, hipStreamSynchronize(st));

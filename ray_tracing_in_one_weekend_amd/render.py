@@ -59,6 +59,9 @@ def main(argv=None):
     ap.add_argument("--denoise-patch", type=int, default=1, metavar="F", help="patch radius, 0..%d" % _ffi.DENOISE_MAX_PATCH)
     ap.add_argument("--denoise-strength", type=float, default=None, metavar="K",
                     help="how many standard errors two pixels may differ and still be averaged (default %g)" % _ffi.DENOISE_DEFAULT_STRENGTH)
+    ap.add_argument("--denoise-guide", choices=("luminance", "channels"), default="luminance",
+                    help="what the filter measures distance on: the mean luminance and its variance (rt_accum_denoise), or the three channels and "
+                         "theirs (rt_accum_denoise_channels: 48 B per pixel more, keeps edges between colours of equal luminance)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     ny = a.ny
@@ -112,6 +115,8 @@ def render_to_noise(a, rend, scene, flags, file_name, t0):
     if a.preview_every or a.denoise:  # (rt_render_to_noise ends its accumulation: the filter needs it open)
         step = make_params(a.nx, a.ny, min(a.spp_step, a.spp), max_depth=a.max_depth, seed=a.seed, flags=flags)
         rend.accum_begin(scene.camera, step)
+        if a.denoise and a.denoise_guide == "channels":
+            rend.accum_track_channels()
         n_rays, seconds, done = 0, 0.0, 0
         while True:
             st = rend.accum_add(min(a.spp_step, a.spp - done))
@@ -152,12 +157,16 @@ def render_adaptive(a, rend, scene, flags, file_name, t0):
 
 
 def _denoised(a, rend):
+    if a.denoise_guide == "channels":
+        return rend.accum_denoise_channels(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
     return rend.accum_denoise(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
 
 
 def render_denoised(a, rend, scene, flags, file_name, t0):
     """--denoise without --noise-target: begin, one add of --spp samples, the filter, end."""
     rend.accum_begin(scene.camera, make_params(a.nx, a.ny, a.spp, max_depth=a.max_depth, seed=a.seed, flags=flags))
+    if a.denoise_guide == "channels":
+        rend.accum_track_channels()
     st = rend.accum_add(a.spp)
     noise = rend.accum_read()[3]
     rgb8 = _denoised(a, rend)
