@@ -101,8 +101,9 @@ def _expected(scene, p, lens, spheres):
 
 @pytest.mark.parametrize("lens", [(0.0, 1.0), (0.05, 1.5), (0.05, 3.0), (0.05, 9.0), (0.5, 1.5), (0.5, 3.0), (0.5, 9.0)])
 def test_lens_rays_are_the_restatement_bit_for_bit(rt, lensed, lens):
-    """Focus in front of all spheres (1.5), at the front of the middle one (3.0) and behind all (9.0).  1 spp (no candidate lists):
-    every pixel bit for bit; 8 spp (lists on): within 2 ulp of the in-order sum."""
+    """Focus in front of all spheres (1.5), at the front of the middle one (3.0) and behind all (9.0).  1 spp (no candidate lists) and
+    8 spp (lists on): every pixel bit for bit.  (The 8-spp frames once had an allowance of 2 ulp; a radiance slot is written once and
+    k_resolve adds the samples in order, so nothing can differ, and on the MI355X nothing does: the largest difference measured is 0.)"""
     scene = _black_spheres(rt, SPHERES, CAM)
     lensed.upload(scene)
     lensed.set_lens(lens)
@@ -114,7 +115,8 @@ def test_lens_rays_are_the_restatement_bit_for_bit(rt, lensed, lens):
         hit = (want == 0).all(axis=2)
         assert 0.03 < hit.mean() < 0.9  # spheres and sky both in the frame
         ulp = np.abs(img.view(np.int32).astype(np.int64) - want.view(np.int32).astype(np.int64)).max()
-        assert ulp == 0 if spp == 1 else ulp <= 2, (lens, spp, ulp)
+        print("lens %r, %d spp: the largest difference is %d ulp" % (lens, spp, ulp))
+        assert ulp == 0, (lens, spp, ulp)
         if spp == 8:
             assert lensed.render_parts()["primary_lists_overflow"] >= 0  # the frame had candidate lists
 
