@@ -591,8 +591,13 @@ __device__ __forceinline__ bool boundary_both_sphere(const Tables& sc, const flo
 }
 // ConstantMedium::hit, hitable.rs:536-579, up to the accepted t.  The random draw is counter slot
 // 224 + m of the depth block (DESIGN.md "RNG"): independent of the order in which media are visited.
-// t_max clamps like the reference's (hitable.rs:553-555); callers pass FLT_MAX and apply the
-// order-independent winner rule, which differs from the clamp only by rounding at exact ties.
+// t_max clamps like the reference's (hitable.rs:553-555).  Two acceptance rules use it.  The list walk (closest_hit_rects) passes
+// t_max = t_cull = the closest hit so far and accepts whatever comes back: the reference's clamp under HitableList::hit's shrinking
+// t_max.  The tree (leaf_test, media_step) passes FLT_MAX and applies the order-independent winner rule: smallest t, a tie to the
+// later entry.  The two part only where the medium's scatter point and another candidate have the same t bit for bit (0 ulp apart on
+// every ray of tests/medium_edge_cases.py that tells them apart): a wall exactly at the entry t1 and a free path below half an ulp of
+// t1 is "medium" to the winner rule (the tie goes to the later entry) and "wall" to the clamp (t1 >= t2).  tests/test_medium_edges.py
+// holds each path to the set of outcomes of its own rule (tests/medium_ref.py).
 // `t_cull`: a scatter point cannot lie before the entry t1, so a medium entered beyond the best hit so far
 // cannot win and the second boundary search is skipped (pure culling, no effect on the result).
 // When all boundary primitives sit below the same wrapper chain (a GBox under RotateY/Translate) the ray is

@@ -1385,6 +1385,21 @@ def test_translate_and_rotate_y_instances(rt, orc, renderer):
     _compare_frames(orc, scene, p, img, ref, "cornell box with instances", rt, renderer)
 
 
+def _medium_t_in_its_set(scene, g, o, d, keys, depth):
+    """every medium hit of the tree search `g`: its t is, bit for bit, one that ConstantMedium::hit's binary32 arithmetic gives for a
+    logarithm within 3 ulp of float64 log(xi) (tests/medium_ref.py: the medium alone, t_max = FLT_MAX as the tree passes it)"""
+    import medium_ref
+    W = medium_ref.World(scene)
+    n = 0
+    for m in range(W.n_media):
+        of = g["hit"] == W.n_prims + m
+        ts = medium_ref.medium_t_set(W, m, o[of], d[of], keys[of], depth)
+        bad = ~(medium_ref.bits(ts) == medium_ref.bits(g["t"][of])[:, None]).any(axis=1)
+        assert not bad.any(), (m, int(bad.sum()), g["t"][of][bad][:3], ts[bad][:3])
+        n += int(of.sum())
+    assert n >= 20
+
+
 def test_constant_medium_and_cornell_box(rt, orc, renderer):
     """hitable.rs:523-588 on the GPU and the reference's cornell_box (demo_scene.rs:112-148).  A medium's scatter
     distance goes through ln(), where device and host libm differ in the last ulp, so medium hits agree to 1e-6
@@ -1411,6 +1426,7 @@ def test_constant_medium_and_cornell_box(rt, orc, renderer):
     assert 0.05 < med.mean() < 0.6                       # a good share of the rays scatters inside the smoke
     assert np.array_equal(g["t"][~med].view(np.uint32), c["t"][~med].view(np.uint32))
     assert np.allclose(g["t"][med], c["t"][med], rtol=2e-6)
+    _medium_t_in_its_set(scene, g, o, d, keys, 3)
     assert np.allclose(g["o"], c["o"], rtol=1e-5, atol=1e-4) and np.array_equal(g["d"].view(np.uint32), c["d"].view(np.uint32))
     assert np.allclose(g["attenuation"], c["attenuation"], rtol=2e-5, atol=1e-6)
     p = rt.make_params(200, 200, 16, max_depth=50)
@@ -1669,6 +1685,7 @@ def test_final_scene(rt, orc, renderer):
     solid = hit & ~med
     assert np.array_equal(g["t"][solid].view(np.uint32), c["t"][solid].view(np.uint32))
     assert np.allclose(g["t"][hit], c["t"][hit], rtol=2e-6)
+    _medium_t_in_its_set(scene, g, o, d, keys, 2)
     assert np.allclose(g["attenuation"], c["attenuation"], rtol=2e-5, atol=1e-6)
     p = rt.make_params(160, 160, 8, max_depth=50)
     img, _, st = renderer.render(scene.camera, p)
