@@ -633,6 +633,70 @@ int rt_accum_read_channel_sem(RtCtx* ctx, float* out_sem_rgb);
  * RtDenoise.reserved stays 0.  In addition RT_ERR_STATE where the accumulation does not track channels. */
 int rt_accum_denoise_channels(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8);
 
+/* -- accumulation state: export, import and merge -------------------------------------------------------------------------------------------
+ * Everything an open accumulation owns, as host arrays: the running f32 sums (NOT divided), the luminance moments, after adaptive adds
+ * the per-pixel counts and converged flags, with tracking the channel moments.  A state outlives the accumulation, the context and the
+ * process: rt_accum_import puts it into a fresh accumulation, which then goes on as the exported one would have (resume), and
+ * rt_accum_merge adds the state of the sample window that FOLLOWS the accumulation's onto it, so that contexts, processes or GPUs can each
+ * take a window of one frame (rt_accum_begin(first_sample)) and one of them ends up with all of them.
+ * Layout.  Every plane is in the row order of out_rgb_f32, local row 0 lowest — never in the accumulation's local pixel order — so a state
+ * does not depend on RT_OPT_PIXEL_ORDER, slices, chains or queue shards.  Cost: 28 B per pixel, + 5 B with counts, + 48 B with channel
+ * moments, on the host and once more in a staging buffer on the device that is kept for the next call like the accumulation's buffers.
+ * Identity.  frame_id = rt_accum_frame_id(camera, params) says which samples the state holds.  It covers the camera and the RtParams
+ * fields a sample depends on.  The SCENE and what rt_set_lens / rt_set_motion / rt_set_quads / rt_set_lights installed are NOT in it:
+ * keeping them equal between the exporter and the importer is the caller's duty, and a state imported over another scene is accepted and
+ * means nothing.
+ * Resume.  After rt_accum_begin(f), adds, rt_accum_export and then — in any context or process with the same scene and sets —
+ * rt_accum_begin(f), rt_accum_import, everything the accumulation returns from then on is bit for bit what the uninterrupted one returns:
+ * further adds (uniform or adaptive), rt_accum_read, rt_accum_read_counts, rt_accum_read_channel_sem, both filters, the frame figures.
+ * Merge.  Per pixel one IEEE operation each, no FMA:  sum_c = sum_c + st.sum_c in f32;  S1 = S1 + st.S1, S2 = S2 + st.S2 in f64;  the six
+ * channel moments likewise.  The merged image is therefore NOT rt_render(spp = n1 + n2) in every bit — an f32 sum of n1 + n2 terms was cut
+ * in two: ((x0 + .. + x_{n1-1}) + (x_{n1} + .. + x_{n1+n2-1})) — it is the arithmetic above exactly; per channel of non-negative radiance
+ * the two differ by at most (2 n + 2) 2^-24 of the larger, n = n1 + n2.  Moments, out_sem and the figures follow from the merged sums.
+ * Failed calls leave the accumulation as it was.  A shard without pixels: RT_OK.  Not covered: rt_multi_*; planes in device memory.
+ * DESIGN.md "Accumulation state". */
+#define RT_ACCUM_STATE_COUNTS   1u  /* adaptive: counts and converged are part of the state */
+#define RT_ACCUM_STATE_CHANNELS 2u  /* channel moments are part of the state */
+typedef struct RtAccumState {
+    uint32_t nx, rows;           /* the shard: rows = rows_local */
+    uint32_t first_sample, done; /* uniform: the window [first_sample, first_sample + done); adaptive: done = samples issued (n_p of the active pixels) */
+    uint32_t planes;             /* RT_ACCUM_STATE_* */
+    uint32_t reserved;           /* 0 */
+    uint64_t frame_id;           /* rt_accum_frame_id of the frame */
+    float*    sum;               /* [rows*nx*3] the running f32 sums, NOT divided */
+    double*   moments;           /* [rows*nx*2] S1, S2 */
+    uint32_t* counts;            /* [rows*nx]   n_p */
+    uint8_t*  converged;         /* [rows*nx]   0 / 1 */
+    double*   channel_moments;   /* [rows*nx*6] S1_r, S2_r, S1_g, S2_g, S1_b, S2_b */
+} RtAccumState;
+/* GPU-free.  FNV-1a 64 (offset 0xcbf29ce484222325, prime 0x100000001b3) over these little-endian bytes, in this order: the 12 camera floats
+ * as bit patterns in struct order; nx, ny, (uint32_t)max_depth; seed (8 B); shard_band, shard_count, shard_id, with shard_count <= 1 mapped
+ * to (0, 1, 0); flags & RT_FLAG_RUSSIAN_ROULETTE.  spp, spp_slice, RT_FLAG_BRUTE_FORCE and the diagnostic bits do not enter: no result
+ * depends on them.  0 for a NULL argument. */
+uint64_t rt_accum_frame_id(const RtCamera* cam, const RtParams* params);
+/* GPU-free.  RT_OK, or RT_ERR_INVALID unless: reserved == 0 and planes holds no unknown bit; sum and moments non-NULL; counts and converged
+ * non-NULL exactly when RT_ACCUM_STATE_COUNTS is set, channel_moments exactly when RT_ACCUM_STATE_CHANNELS is; first_sample + done <=
+ * 2^32 - 1; with counts every converged[p] is 0 or 1, every counts[p] <= done, and counts[p] == done wherever converged[p] == 0 (all
+ * active pixels share one n_p: "Adaptive sampling"). */
+int rt_accum_state_check(const RtAccumState* st);
+/* Fills the scalar fields of `st` (planes: what the accumulation holds) and writes every plane whose pointer is non-NULL; a NULL pointer
+ * skips that plane (all NULL: the scalar fields alone, without any device work).  On a uniform accumulation counts gets `done` and converged 0 for every pixel, as rt_accum_read_counts reports there
+ * (clear both pointers before handing such a state to rt_accum_import or rt_accum_merge).  Reads, and changes nothing.  Synchronises the
+ * context's stream once.  RT_ERR_STATE: no open accumulation, or channel_moments non-NULL on one that does not track channels. */
+int rt_accum_export(RtCtx* ctx, RtAccumState* st);
+/* Puts `st` into the open accumulation, which must hold no sample yet: after rt_accum_begin (rt_accum_track_channels may come in between)
+ * and before the first add of either kind, else RT_ERR_STATE.  Values are copied as bits: NaN and inf travel unchanged.  A state with
+ * channel moments turns tracking on, with the allocation of rt_accum_track_channels; one with counts makes the accumulation adaptive, with
+ * the allocation of the first adaptive add; `done` becomes st->done.  RT_ERR_INVALID: rt_accum_state_check fails; nx, rows, frame_id or
+ * first_sample differ from the accumulation's; the accumulation tracks channels and the state has none.  Synchronises once. */
+int rt_accum_import(RtCtx* ctx, const RtAccumState* st);
+/* Adds `st`, the window that continues the open accumulation's, onto it by the arithmetic of "Merge" above: both uniform, st->first_sample
+ * == first_sample + done of the accumulation (which may hold no sample yet: the result is 0 + x), nx, rows and frame_id equal, channel
+ * moments in both or in neither.  done += st->done; adds of either kind then go on from first_sample + done.  RT_ERR_STATE: no open
+ * accumulation.  RT_ERR_UNSUPPORTED: either side is adaptive (windows of pixels with different n_p are not contiguous).  RT_ERR_INVALID:
+ * every other mismatch, a state rt_accum_state_check refuses, samples past 2^32 - 1.  Synchronises once. */
+int rt_accum_merge(RtCtx* ctx, const RtAccumState* st);
+
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the
  * world shared read-only (main.rs:72-108); here the scene is replicated on every device, device r renders the image

@@ -141,6 +141,17 @@ class RtAdaptiveInfo(C.Structure):
     _fields_ = [("n_active", C.c_uint64), ("n_samples", C.c_uint64), ("spp_min", C.c_uint32), ("spp_max", C.c_uint32)]
 
 
+ACCUM_STATE_COUNTS, ACCUM_STATE_CHANNELS = 1, 2  # RT_ACCUM_STATE_*
+
+
+class RtAccumState(C.Structure):
+    """rt_accum_export / rt_accum_import / rt_accum_merge: what an accumulation owns, as host arrays in the row order of the f32 image
+    (rtow_mi355x.h "accumulation state")."""
+    _fields_ = [("nx", C.c_uint32), ("rows", C.c_uint32), ("first_sample", C.c_uint32), ("done", C.c_uint32), ("planes", C.c_uint32),
+                ("reserved", C.c_uint32), ("frame_id", C.c_uint64), ("sum", _f), ("moments", C.POINTER(C.c_double)), ("counts", _u32),
+                ("converged", _u8), ("channel_moments", C.POINTER(C.c_double))]
+
+
 DENOISE_MAX_RADIUS, DENOISE_MAX_PATCH = 10, 3
 DENOISE_DEFAULT_STRENGTH = 1.0  # RT_DENOISE_DEFAULT_STRENGTH
 
@@ -200,6 +211,7 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_accum_track_channels", "rt_accum_read_channel_sem", "rt_accum_denoise_channels", "rt_debug_denoise_channels",
                "rt_accum_add_adaptive", "rt_accum_read_counts", "rt_render_adaptive", "rt_adaptive_check", "rt_adaptive_converged",
                "rt_debug_accum_set_moments",
+               "rt_accum_frame_id", "rt_accum_state_check", "rt_accum_export", "rt_accum_import", "rt_accum_merge",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
@@ -314,7 +326,17 @@ def load_gpu_library():
     lib.rt_adaptive_converged.restype = C.c_int
     lib.rt_debug_accum_set_moments.argtypes = [vp, C.c_uint32, C.c_double, C.c_double]
     lib.rt_debug_accum_set_moments.restype = C.c_int
-    lib.rt_debug_planar_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.rt_accum_frame_id.argtypes = [C.POINTER(RtCamera), C.POINTER(RtParams)]
+    lib.rt_accum_frame_id.restype = C.c_uint64
+    lib.rt_accum_state_check.argtypes = [C.POINTER(RtAccumState)]
+    lib.rt_accum_state_check.restype = C.c_int
+    lib.rt_accum_export.argtypes = [vp, C.POINTER(RtAccumState)]
+    lib.rt_accum_export.restype = C.c_int
+    lib.rt_accum_import.argtypes = [vp, C.POINTER(RtAccumState)]
+    lib.rt_accum_import.restype = C.c_int
+    lib.rt_accum_merge.argtypes = [vp, C.POINTER(RtAccumState)]
+    lib.rt_accum_merge.restype = C.c_int
+    lib.rt_debug_planar_info.argtypes =[vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.rt_debug_planar_info.restype = C.c_int
     lib.rt_debug_planar_bounds.argtypes = [C.POINTER(RtQuads), C.c_float, vp, vp]
     lib.rt_debug_planar_bounds.restype = C.c_int

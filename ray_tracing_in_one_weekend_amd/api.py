@@ -449,6 +449,87 @@ def adaptive_converged(ad, s1, s2, n):
     return rc == 1
 
 
+def accum_frame_id(camera, params):
+    """rt_accum_frame_id (no GPU): the 64-bit identity of the frame a camera and an RtParams describe — what an AccumState carries so that
+    it is only imported into, or merged with, an accumulation of the same samples.  The scene and the sets are not part of it."""
+    return int(_ffi.load_gpu_library().rt_accum_frame_id(C.byref(camera), C.byref(params)))
+
+
+class AccumState:
+    """What an accumulation owns (rtow_mi355x.h "accumulation state"), as numpy arrays in the row order of the f32 image plus the scalar
+    fields of RtAccumState: sum [rows, nx, 3] f32 (not divided), moments [rows, nx, 2] f64, counts [rows, nx] u32, converged [rows, nx] u8,
+    channel_moments [rows, nx, 6] f64 or None.  `planes` says which of counts / converged and channel_moments belong to the state
+    (_ffi.ACCUM_STATE_*); on a uniform state counts and converged are informative (done and 0) and are not handed to the library."""
+    _SCALARS = ("nx", "rows", "first_sample", "done", "planes", "frame_id")
+    _ARRAYS = (("sum", np.float32, 3), ("moments", np.float64, 2), ("counts", np.uint32, 0), ("converged", np.uint8, 0),
+               ("channel_moments", np.float64, 6))
+
+    def __init__(self, nx, rows, first_sample=0, done=0, planes=0, frame_id=0, sum=None, moments=None, counts=None, converged=None,
+                 channel_moments=None):
+        self.nx, self.rows, self.first_sample, self.done = int(nx), int(rows), int(first_sample), int(done)
+        self.planes, self.frame_id = int(planes), int(frame_id)
+        given = dict(sum=sum, moments=moments, counts=counts, converged=converged, channel_moments=channel_moments)
+        for name, dt, k in self._ARRAYS:
+            arr = given[name]
+            if arr is not None:
+                shape = (self.rows, self.nx, k) if k else (self.rows, self.nx)
+                arr = np.ascontiguousarray(arr, dtype=dt)
+                if arr.shape != shape:
+                    raise ValueError(f"AccumState.{name}: shape {arr.shape}, expected {shape}")
+            setattr(self, name, arr)
+
+    @property
+    def adaptive(self):
+        return bool(self.planes & _ffi.ACCUM_STATE_COUNTS)
+
+    @property
+    def channels(self):
+        return bool(self.planes & _ffi.ACCUM_STATE_CHANNELS)
+
+    def as_struct(self):
+        """The RtAccumState over these arrays (which must stay alive while it is used): the planes that `planes` names, NULL for the others."""
+        def ptr(arr, ctype):
+            return arr.ctypes.data_as(C.POINTER(ctype)) if arr is not None else None
+        st = _ffi.RtAccumState(self.nx, self.rows, self.first_sample, self.done, self.planes, 0, self.frame_id)
+        st.sum, st.moments = ptr(self.sum, C.c_float), ptr(self.moments, C.c_double)
+        if self.adaptive:
+            st.counts, st.converged = ptr(self.counts, C.c_uint32), ptr(self.converged, C.c_uint8)
+        if self.channels:
+            st.channel_moments = ptr(self.channel_moments, C.c_double)
+        return st
+
+    def check(self):
+        """rt_accum_state_check (no GPU): True when the library would accept the state before comparing it with an accumulation."""
+        st = self.as_struct()
+        return _ffi.load_gpu_library().rt_accum_state_check(C.byref(st)) == 0
+
+    def save(self, path):
+        """Writes the state as an .npz at exactly `path`, through a temporary file beside it and os.replace: a process killed while
+        saving leaves the previous checkpoint or none, never half of one."""
+        import os
+        import tempfile
+        data = {k: np.asarray(getattr(self, k), dtype=np.uint64) for k in self._SCALARS}
+        data.update({name: getattr(self, name) for name, _, _ in self._ARRAYS if getattr(self, name) is not None})
+        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(path)))
+        try:
+            with os.fdopen(fd, "wb") as f:
+                np.savez(f, **data)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            kw = {k: int(z[k]) for k in cls._SCALARS}
+            kw.update({name: z[name] for name, _, _ in cls._ARRAYS if name in z.files})
+        return cls(**kw)
+
+
 class Renderer:
     """One GPU context (rt_ctx_create).  Replaces the render half of main.rs:62-129."""
 
@@ -718,6 +799,41 @@ class Renderer:
         if rc != 0:
             self._raise("rt_debug_denoise_channels", rc)
         return out
+
+    def accum_export(self):
+        """rt_accum_export: the open accumulation as an AccumState — every plane it holds; on a uniform accumulation counts and converged
+        are `done` and 0.  The accumulation is read and not changed."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        probe = _ffi.RtAccumState()
+        rc = self._lib.rt_accum_export(self._ctx, C.byref(probe))  # the scalar fields only: which planes are there to ask for
+        if rc != 0:
+            self._raise("rt_accum_export", rc)
+        channels = bool(probe.planes & _ffi.ACCUM_STATE_CHANNELS)
+        state = AccumState(probe.nx, probe.rows, sum=np.zeros((rows, nx, 3), np.float32), moments=np.zeros((rows, nx, 2), np.float64),
+                           counts=np.zeros((rows, nx), np.uint32), converged=np.zeros((rows, nx), np.uint8),
+                           channel_moments=np.zeros((rows, nx, 6), np.float64) if channels else None)
+        state.planes = _ffi.ACCUM_STATE_COUNTS | (_ffi.ACCUM_STATE_CHANNELS if channels else 0)  # (every array below gets a pointer)
+        st = state.as_struct()
+        rc = self._lib.rt_accum_export(self._ctx, C.byref(st))
+        if rc != 0:
+            self._raise("rt_accum_export", rc)
+        state.first_sample, state.done, state.planes, state.frame_id = st.first_sample, st.done, st.planes, st.frame_id
+        return state
+
+    def accum_import(self, state):
+        """rt_accum_import: puts an AccumState into the accumulation just begun (before its first add); it then goes on, bit for bit, as
+        the exported one would have."""
+        st = state.as_struct()
+        rc = self._lib.rt_accum_import(self._ctx, C.byref(st))
+        if rc != 0:
+            self._raise("rt_accum_import", rc)
+
+    def accum_merge(self, state):
+        """rt_accum_merge: adds the AccumState of the sample window that follows the open accumulation's onto it (both uniform)."""
+        st = state.as_struct()
+        rc = self._lib.rt_accum_merge(self._ctx, C.byref(st))
+        if rc != 0:
+            self._raise("rt_accum_merge", rc)
 
     def set_progress(self, fn):
         """fn(spp_done, spp_total, rgb8[rows, nx, 3]) after every slice but the last of a following render()

@@ -6,6 +6,8 @@
 #include "rt_denoise.h"
 #include "rt_channels.h"
 #include "rt_adaptive.h"
+#include "rt_accum_state.h"
+#include "rt_accum_state_kernels.h"
 #include "rt_bvh.h"
 #include "rt_grid.h"
 #include "rt_pool.h"
@@ -141,6 +143,7 @@ struct RtCtx {
     // rt_accum_track_channels (rt_channels.h): three planes of f64 x 2 channel moments, 48 B per pixel, each in the order of accum_sum;
     // accum_chsem: staging of out_sem_rgb; dn_cv: the inputs of rt_accum_denoise_channels, (c, v) x 3 per pixel in image order, 24 B
     DevBuf accum_chm, accum_chsem, dn_cv;
+    DevBuf accum_stage;          // rt_accum_export / _import / _merge: the planes of a state in image order (rt_accum_state.h: accum_state_staging), at most 81 B per pixel
     DevBuf dn_c, dn_yv, dn_out;  // rt_accum_denoise: the filter's inputs (c 12 B, (y, v) 8 B) and its output (12 B) per pixel, in image order
     // Host-side timeline of the last trace_samples and what its caller enqueued behind it (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
     // render of a process is where allocations, code-object loads and the queue probe happen; this says which.
@@ -726,6 +729,7 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->accum_chm), free_buf(ctx->accum_chsem), free_buf(ctx->dn_cv);
     free_buf(ctx->accum_sum), free_buf(ctx->accum_mom), free_buf(ctx->accum_sem), free_buf(ctx->accum_partials);
     free_buf(ctx->accum_cnt), free_buf(ctx->accum_flag), free_buf(ctx->accum_info), free_buf(ctx->accum_cnt_out);
+    free_buf(ctx->accum_stage);
     if (ctx->h_info) (void)hipHostFree(ctx->h_info);
     free_buf(ctx->dn_c), free_buf(ctx->dn_yv), free_buf(ctx->dn_out);
     if (ctx->h_noise) (void)hipHostFree(ctx->h_noise);
@@ -1791,6 +1795,159 @@ int rt_debug_denoise_channels(RtCtx* ctx, uint32_t nx, uint32_t rows, const floa
     RT_HIP(ctx, hipGetLastError());
     RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->dn_out.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
     RT_HIP(ctx, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+// ---- accumulation state (rtow_mi355x.h "Accumulation state", csrc/rt_accum_state.h, csrc/rt_accum_state_kernels.h) -------------------------
+uint64_t rt_accum_frame_id(const RtCamera* cam, const RtParams* prm) { return cam && prm ? accum_frame_id(*cam, *prm) : 0ull; }
+int rt_accum_state_check(const RtAccumState* st) { return accum_state_invalid(st) ? RT_ERR_INVALID : RT_OK; }
+
+// The accumulation's planes and the staging planes of a state with `planes`, carved from ctx->accum_stage (grown on demand, kept).
+static AccumPlanes accum_planes(RtCtx* ctx) {
+    return AccumPlanes{(float*)ctx->accum_sum.p, (double2*)ctx->accum_mom.p, (uint32_t*)ctx->accum_cnt.p, (uint8_t*)ctx->accum_flag.p,
+                       (double2*)ctx->accum_chm.p};
+}
+static int stage_planes(RtCtx* ctx, uint32_t npix, uint32_t planes, StagedPlanes& s) {
+    const StateStaging lay = accum_state_staging(npix, planes);
+    if (const int rc = ensure(ctx, ctx->accum_stage, lay.total)) return rc;
+    char* base = (char*)ctx->accum_stage.p;
+    s = StagedPlanes{(float*)(base + lay.sum), (double2*)(base + lay.moments), (uint32_t*)(base + lay.counts), (uint8_t*)(base + lay.flags),
+                     (double2*)(base + lay.channels)};
+    return RT_OK;
+}
+// What rt_accum_import and rt_accum_merge both ask of a state against the open accumulation `a`, beyond accum_state_invalid: NULL or the
+// mismatch.  (Which first_sample fits is each caller's own question.)
+static const char* state_mismatch(const RtCtx::Accum& a, const RtAccumState& st) {
+    if (st.nx != a.nx || st.rows != a.rows) return "nx and rows of the state are not the accumulation's";
+    if (st.frame_id != accum_frame_id(a.cam, a.prm)) return "frame_id of the state is not rt_accum_frame_id of the accumulation's camera and params";
+    return nullptr;
+}
+// state -> staging planes, enqueued on `st_` in front of the kernel that reads them
+static int upload_state(RtCtx* ctx, const RtAccumState& st, const StagedPlanes& s, uint32_t npix, hipStream_t st_) {
+    RT_HIP(ctx, hipMemcpyAsync(s.sum, st.sum, (size_t)npix * RT_STATE_SUM_BYTES, hipMemcpyHostToDevice, st_));
+    RT_HIP(ctx, hipMemcpyAsync(s.mom, st.moments, (size_t)npix * RT_STATE_MOMENT_BYTES, hipMemcpyHostToDevice, st_));
+    if (st.planes & RT_ACCUM_STATE_COUNTS) {
+        RT_HIP(ctx, hipMemcpyAsync(s.cnt, st.counts, (size_t)npix * RT_STATE_COUNT_BYTES, hipMemcpyHostToDevice, st_));
+        RT_HIP(ctx, hipMemcpyAsync(s.flag, st.converged, (size_t)npix * RT_STATE_FLAG_BYTES, hipMemcpyHostToDevice, st_));
+    }
+    if (st.planes & RT_ACCUM_STATE_CHANNELS)
+        RT_HIP(ctx, hipMemcpyAsync(s.chm, st.channel_moments, (size_t)npix * RT_STATE_CHANNEL_BYTES, hipMemcpyHostToDevice, st_));
+    return RT_OK;
+}
+
+int rt_accum_export(RtCtx* ctx, RtAccumState* st) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!st) return fail(ctx, RT_ERR_INVALID, "rt_accum_export: the RtAccumState is NULL");
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_export: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (st->channel_moments && !a.channels)
+        return fail(ctx, RT_ERR_STATE, "rt_accum_export: channel_moments asked of an accumulation that does not track channels (rt_accum_track_channels)");
+    const uint32_t npix = a.npix;
+    const bool want_counts = st->counts || st->converged;
+    if (npix && (st->sum || st->moments || want_counts || st->channel_moments)) { // (no pointer at all: the scalar fields only, no device work)
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        const hipStream_t s_ = ctx->stream;
+        const bool counts = a.adaptive && want_counts, channels = st->channel_moments != nullptr;
+        StagedPlanes s;
+        if (const int rc = stage_planes(ctx, npix, (counts ? RT_ACCUM_STATE_COUNTS : 0u) | (channels ? RT_ACCUM_STATE_CHANNELS : 0u), s)) return rc;
+        const AccumPlanes ap = accum_planes(ctx);
+        const dim3 grid((npix + 255u) / 256u), block(256);
+        if (counts && channels) hipLaunchKernelGGL((k_accum_export<true, true>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        else if (counts) hipLaunchKernelGGL((k_accum_export<true, false>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        else if (channels) hipLaunchKernelGGL((k_accum_export<false, true>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        else hipLaunchKernelGGL((k_accum_export<false, false>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        RT_HIP(ctx, hipGetLastError());
+        if (st->sum) RT_HIP(ctx, hipMemcpyAsync(st->sum, s.sum, (size_t)npix * RT_STATE_SUM_BYTES, hipMemcpyDeviceToHost, s_));
+        if (st->moments) RT_HIP(ctx, hipMemcpyAsync(st->moments, s.mom, (size_t)npix * RT_STATE_MOMENT_BYTES, hipMemcpyDeviceToHost, s_));
+        if (counts && st->counts) RT_HIP(ctx, hipMemcpyAsync(st->counts, s.cnt, (size_t)npix * RT_STATE_COUNT_BYTES, hipMemcpyDeviceToHost, s_));
+        if (counts && st->converged) RT_HIP(ctx, hipMemcpyAsync(st->converged, s.flag, (size_t)npix * RT_STATE_FLAG_BYTES, hipMemcpyDeviceToHost, s_));
+        if (channels) RT_HIP(ctx, hipMemcpyAsync(st->channel_moments, s.chm, (size_t)npix * RT_STATE_CHANNEL_BYTES, hipMemcpyDeviceToHost, s_));
+        RT_HIP(ctx, hipStreamSynchronize(s_));
+        if (!a.adaptive) { // uniform: every pixel holds `done` samples and is active (rt_accum_read_counts)
+            if (st->counts) std::fill(st->counts, st->counts + npix, a.done);
+            if (st->converged) std::fill(st->converged, st->converged + npix, (uint8_t)0u);
+        }
+    }
+    st->nx = a.nx, st->rows = a.rows, st->first_sample = a.first, st->done = a.done;
+    st->planes = (a.adaptive ? RT_ACCUM_STATE_COUNTS : 0u) | (a.channels ? RT_ACCUM_STATE_CHANNELS : 0u);
+    st->reserved = 0u;
+    st->frame_id = accum_frame_id(a.cam, a.prm);
+    return RT_OK;
+}
+
+int rt_accum_import(RtCtx* ctx, const RtAccumState* st) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_import: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (a.done != 0u || a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_import: samples were added already (call it right after rt_accum_begin)");
+    if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import: ") + why);
+    if (const char* why = state_mismatch(a, *st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import: ") + why);
+    if (st->first_sample != a.first) return fail(ctx, RT_ERR_INVALID, "rt_accum_import: first_sample of the state is not the accumulation's");
+    const bool counts = (st->planes & RT_ACCUM_STATE_COUNTS) != 0u, channels = (st->planes & RT_ACCUM_STATE_CHANNELS) != 0u;
+    if (a.channels && !channels) return fail(ctx, RT_ERR_INVALID, "rt_accum_import: the accumulation tracks channels and the state holds no channel moments");
+    const uint32_t npix = a.npix;
+    if (npix) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        const hipStream_t s_ = ctx->stream;
+        const uint32_t nb = (npix + 255u) / 256u;
+        int rc;
+        // every allocation first: a failure below this block cannot leave the accumulation half imported
+        if (channels && (rc = ensure(ctx, ctx->accum_chm, (size_t)npix * 3 * sizeof(double2)))) return rc; // (as rt_accum_track_channels)
+        if (counts) { // (as the first adaptive add)
+            if ((rc = ensure(ctx, ctx->accum_cnt, (size_t)npix * sizeof(uint32_t)))) return rc;
+            if ((rc = ensure(ctx, ctx->accum_flag, (size_t)npix))) return rc;
+            if ((rc = ensure(ctx, ctx->accum_info, ((size_t)nb + 1u) * sizeof(AdaptiveSums)))) return rc;
+            if (!ctx->h_info) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_info, sizeof(RtAdaptiveInfo), hipHostMallocDefault));
+        }
+        StagedPlanes s;
+        if ((rc = stage_planes(ctx, npix, st->planes, s))) return rc;
+        if ((rc = upload_state(ctx, *st, s, npix, s_))) return rc;
+        const AccumPlanes ap = accum_planes(ctx);
+        const dim3 grid(nb), block(256);
+        if (counts && channels) hipLaunchKernelGGL((k_accum_import<true, true>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        else if (counts) hipLaunchKernelGGL((k_accum_import<true, false>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        else if (channels) hipLaunchKernelGGL((k_accum_import<false, true>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        else hipLaunchKernelGGL((k_accum_import<false, false>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        RT_HIP(ctx, hipGetLastError());
+        RT_HIP(ctx, hipStreamSynchronize(s_)); // (the caller's arrays are free again)
+    }
+    a.channels = a.channels || channels;
+    a.adaptive = counts;
+    a.done = st->done;
+    return RT_OK;
+}
+
+int rt_accum_merge(RtCtx* ctx, const RtAccumState* st) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_merge: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_merge: ") + why);
+    if (a.adaptive || (st->planes & RT_ACCUM_STATE_COUNTS))
+        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: an adaptive accumulation or state: windows of pixels with different sample counts are not contiguous");
+    if (const char* why = state_mismatch(a, *st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_merge: ") + why);
+    if ((uint64_t)st->first_sample != (uint64_t)a.first + a.done)
+        return fail(ctx, RT_ERR_INVALID, "rt_accum_merge: the state's window is not adjacent: its first_sample (" + std::to_string(st->first_sample) +
+                                             ") must be the accumulation's first_sample + done (" + std::to_string((uint64_t)a.first + a.done) + ")");
+    const bool channels = (st->planes & RT_ACCUM_STATE_CHANNELS) != 0u;
+    if (channels != a.channels) return fail(ctx, RT_ERR_INVALID, "rt_accum_merge: channel moments must be in both the accumulation and the state, or in neither");
+    if ((uint64_t)a.first + a.done + st->done > 0xFFFFFFFFull)
+        return fail(ctx, RT_ERR_INVALID, "rt_accum_merge: first_sample + the samples merged must stay below 2^32, as RtParams.spp does");
+    const uint32_t npix = a.npix;
+    if (npix) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        const hipStream_t s_ = ctx->stream;
+        StagedPlanes s;
+        int rc;
+        if ((rc = stage_planes(ctx, npix, st->planes, s))) return rc;
+        if ((rc = upload_state(ctx, *st, s, npix, s_))) return rc;
+        const AccumPlanes ap = accum_planes(ctx);
+        const dim3 grid((npix + 255u) / 256u), block(256);
+        if (channels) hipLaunchKernelGGL((k_accum_merge<true>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        else hipLaunchKernelGGL((k_accum_merge<false>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        RT_HIP(ctx, hipGetLastError());
+        RT_HIP(ctx, hipStreamSynchronize(s_));
+    }
+    a.done += st->done;
     return RT_OK;
 }
 

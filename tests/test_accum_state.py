@@ -1,0 +1,707 @@
+"""Export, import and merge of accumulations on the GPU (rt_accum_export, rt_accum_import, rt_accum_merge).  The exported state is held to
+tests/accum_state_ref.py — the numpy accumulation of the single-sample frames the accumulation itself delivers through first_sample —
+bit for bit; a resumed accumulation to the uninterrupted one on another context, bit for bit in everything it returns; a merge to the
+reference's np.float32 / np.float64 additions, bit for bit, and to rt_render within the bound the header derives.
+
+Frames are those of tests/test_accum.py: 40 x 20 (sixteen rows in 8 x 8 tiles and four row-major) and 24 x 16, spp_slice 3; the adaptive
+case is "grid" of tests/test_adaptive.py with its parameters."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import accum_state_ref as ref
+import adaptive_ref
+import denoise_ref
+import noise_ref
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CASES = {
+    "A": dict(scene="test_sphere", nx=40, ny=20, kw=dict(max_depth=50)),
+    "B": dict(scene="cornell_box", nx=24, ny=16, kw=dict(max_depth=8)),
+    "C": dict(scene="test_sphere", nx=40, ny=20, kw=dict(max_depth=50, shard_count=2, shard_band=4, shard_id=1)),
+    "D_lens": dict(scene="test_sphere", nx=40, ny=20, kw=dict(max_depth=50), lens=(0.05, 3.0)),
+    # tests/test_adaptive.py "grid": SEED 4321, spp_slice 4, floor 0.01, min_samples 6, steps of 6, at most 24
+    "grid": dict(scene="sphere_scene", nx=24, ny=16, kw=dict(max_depth=50, spp_slice=4), seed=4321),
+}
+SEED = 1234
+FLOOR, MIN, STEP, MAX = 0.01, 6, 6, 24
+BRUTE = 1  # RT_FLAG_BRUTE_FORCE
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
+
+
+def _same(a, b, what):
+    assert a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b)), (what, int((_bits(a) != _bits(b)).sum()), "values differ")
+
+
+def _raises(rt, code, fn, *a, **kw):
+    with pytest.raises(rt.RtError, match=r"\(-%d\)" % code):
+        fn(*a, **kw)
+
+
+@pytest.fixture(scope="module")
+def ctx(rt):
+    r = rt.Renderer(0)
+    yield r
+    r.close()
+
+
+@pytest.fixture(scope="module")
+def ctx2(rt):
+    """The second context: what a state is imported into, with nothing but the scene and the sets in common with the first."""
+    r = rt.Renderer(0)
+    yield r
+    for opt in rt._ffi.OPT_NAMES.values():
+        r.set_option(opt, 0)
+    r.close()
+
+
+_scenes, _single = {}, {}
+
+
+def _setup(rt, r, case):
+    """Uploads the case's scene with its sets; returns (scene, params(spp, **kw))."""
+    c = CASES[case]
+    key = (c["scene"], c["nx"], c["ny"])
+    if key not in _scenes:
+        _scenes[key] = rt.Scene.build(c["scene"], c["nx"] / c["ny"])
+    scene = _scenes[key]
+    r.upload(scene)
+    r.set_lens(c.get("lens"))
+    return scene, lambda spp, **kw: rt.make_params(c["nx"], c["ny"], spp, **{"seed": c.get("seed", SEED), "spp_slice": 3, **c["kw"], **kw})
+
+
+def _singles(r, scene, prm, case, n):
+    """x[s], s < n: the single-sample frames of the case (computed once, never changed)."""
+    have = _single.setdefault(case, [])
+    for s in range(len(have), n):
+        r.accum_begin(scene.camera, prm(1), first_sample=s)
+        r.accum_add(1)
+        img = r.accum_read()[0]
+        img.setflags(write=False)
+        have.append(img)
+    r.accum_end()
+    return have[:n]
+
+
+def _state_is(got, want, what, informative_counts=True):
+    """An exported AccumState against a reference dict: the scalar fields and every plane, bit for bit."""
+    for k in ("nx", "rows", "first_sample", "done", "planes", "frame_id"):
+        assert getattr(got, k) == want[k], (what, k, getattr(got, k), want[k])
+    _same(got.sum, want["sum"], (what, "sum"))
+    _same(got.moments, want["moments"], (what, "moments"))
+    if want["planes"] & ref.COUNTS:
+        _same(got.counts, want["counts"], (what, "counts"))
+        _same(got.converged, want["converged"], (what, "converged"))
+    elif informative_counts:
+        assert (got.counts == want["done"]).all() and not got.converged.any(), (what, "uniform counts")
+    if want["planes"] & ref.CHANNELS:
+        _same(got.channel_moments, want["channel_moments"], (what, "channel moments"))
+    else:
+        assert got.channel_moments is None
+    assert got.check()
+
+
+def _states_equal(a, b, what):
+    for k in ("nx", "rows", "first_sample", "done", "planes", "frame_id"):
+        assert getattr(a, k) == getattr(b, k), (what, k)
+    for name in ("sum", "moments", "counts", "converged", "channel_moments"):
+        x, y = getattr(a, name), getattr(b, name)
+        assert (x is None) == (y is None), (what, name)
+        if x is not None:
+            _same(x, y, (what, name))
+
+
+def _everything(r, channels=False, denoise=True):
+    """Everything an open accumulation returns, as a list of (name, array or bytes)."""
+    img, rgb8, sem, noise = r.accum_read(want_rgb8=True, want_sem=True)
+    counts, info = r.accum_counts()
+    out = [("f32", img), ("rgb8", rgb8), ("sem", sem), ("noise", bytes(noise)), ("counts", counts), ("info", bytes(info))]
+    if denoise:
+        out += [("denoise", r.accum_denoise()[0])]
+    if channels:
+        out += [("channel sem", r.accum_channel_sem())]
+        if denoise:
+            dn = r.accum_denoise_channels(want_rgb8=True)
+            out += [("denoise channels", dn[0]), ("denoise channels rgb8", dn[1])]
+    return out
+
+
+def _all_same(got, want, what):
+    assert [k for k, _ in got] == [k for k, _ in want]
+    for (k, a), (_, b) in zip(got, want):
+        if isinstance(a, bytes):
+            assert a == b, (what, k)
+        else:
+            _same(a, b, (what, k))
+
+
+# ---- 1. export is the reference ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["A", "B", "C", "D_lens"])
+def test_export_is_the_reference(rt, ctx, case):
+    r = ctx
+    scene, prm = _setup(rt, r, case)
+    x = _singles(r, scene, prm, case, 7)
+    fid = ref.frame_id_of(scene.camera, prm(1))
+    assert fid == rt.accum_frame_id(scene.camera, prm(2))
+    r.accum_begin(scene.camera, prm(2))
+    empty = r.accum_export()
+    assert (empty.done, empty.planes) == (0, 0) and not empty.sum.any() and not empty.moments.any() and not empty.counts.any()
+    for n in (1, 2, 4):
+        r.accum_add(n)
+    before = r.accum_read(want_rgb8=True, want_sem=True)
+    got = r.accum_export()
+    want = ref.uniform_state(x, 0, fid)
+    assert want["done"] == 7 and (want["sum"] != 0).any() and ref.state_check(want)
+    _state_is(got, want, case)
+    assert got.sum.shape == (r.shard_rows(prm(1)), CASES[case]["nx"], 3) and (got.counts == 7).all() and not got.converged.any()
+    # a window that begins at sample 3
+    r.accum_begin(scene.camera, prm(4), first_sample=3)
+    r.accum_add(1), r.accum_add(3)
+    _state_is(r.accum_export(), ref.uniform_state(x[3:], 3, fid), (case, "window 3..6"))
+    # the export read and changed nothing
+    r.accum_begin(scene.camera, prm(2))
+    for n in (1, 2, 4):
+        r.accum_add(n)
+    r.accum_export()
+    after = r.accum_read(want_rgb8=True, want_sem=True)
+    for k in range(3):
+        _same(after[k], before[k], (case, "read after the export", k))
+    assert bytes(after[3]) == bytes(before[3])
+    r.accum_end()
+
+
+# ---- 2. resume, uniform -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["A", "B", "C", "D_lens"])
+def test_resume_uniform(rt, ctx, ctx2, case):
+    r, r2 = ctx, ctx2
+    scene, prm = _setup(rt, r, case)
+    sharded = CASES[case]["kw"].get("shard_count", 1) > 1
+    want7 = r.render(scene.camera, prm(7), want_rgb8=True)
+    r.accum_begin(scene.camera, prm(4))
+    r.accum_add(3)
+    state = r.accum_export()
+    r.accum_add(4)
+    want = _everything(r, denoise=not sharded)
+    r.accum_end()
+    _same(want[0][1], want7[0], (case, "the uninterrupted accumulation is rt_render(7)"))
+    _setup(rt, r2, case)
+    r2.accum_begin(scene.camera, prm(4))
+    r2.accum_import(state)
+    _states_equal(r2.accum_export(), state, (case, "an export straight after the import"))
+    st = r2.accum_add(4)
+    assert st.n_paths == state.sum.shape[0] * state.sum.shape[1] * 4
+    got = _everything(r2, denoise=not sharded)
+    _all_same(got, want, case)
+    _same(got[0][1], want7[0], (case, "f32 against rt_render(7)"))
+    _same(got[1][1], want7[1], (case, "rgb8 against rt_render(7)"))
+    r2.accum_end()
+
+
+# ---- 3. resume under another schedule ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case,options,kw", [
+    ("A", {"pixel_order": 1, "queue_shards": 7}, dict(spp_slice=2)),   # the exporter: 8 x 8 tiles by default; the importer row by row
+    ("A", {"pixel_order": 2, "queue_shards": 9, "chains": 1}, dict(spp_slice=1)),
+    ("B", {"pixel_order": 2, "queue_shards": 8}, dict(spp_slice=5)),   # a general scene: rows by default; the importer in tiles
+    ("A", {}, dict(flags=BRUTE)),
+])
+def test_resume_under_another_schedule(rt, ctx, ctx2, case, options, kw):
+    r, r2 = ctx, ctx2
+    scene, prm = _setup(rt, r, case)
+    r.accum_begin(scene.camera, prm(4))
+    r.accum_add(3)
+    state = r.accum_export()
+    r.accum_add(4)
+    want = _everything(r)
+    r.accum_end()
+    try:
+        for opt, value in options.items():
+            r2.set_option(opt, value)
+        _setup(rt, r2, case)
+        assert rt.accum_frame_id(scene.camera, prm(4, **kw)) == state.frame_id  # spp_slice and brute force are not part of the identity
+        r2.accum_begin(scene.camera, prm(4, **kw))  # the uninterrupted accumulation under the importer's schedule
+        r2.accum_add(3), r2.accum_add(4)
+        want2 = _everything(r2)
+        r2.accum_begin(scene.camera, prm(4, **kw))
+        r2.accum_import(state)
+        _states_equal(r2.accum_export(), state, (case, options, kw, "an export straight after the import"))
+        r2.accum_add(4)
+        got = _everything(r2)
+        _all_same(got, want2, (case, options, kw, "against the uninterrupted accumulation under the importer's schedule"))
+        # Against the exporter's schedule every per-pixel result is the same bits.  The three frame figures are sums over the pixels in the
+        # accumulation's local pixel order (rtow_mi355x.h "Frame figures": a fixed tree over that order), so another pixel order adds the
+        # same terms in another order: within npix 2^-52, the bound tests/test_accum.py holds them to.
+        skip = [k for k, _ in got].index("noise")
+        _all_same(got[:skip] + got[skip + 1:], want[:skip] + want[skip + 1:], (case, options, kw))
+        a, b = rt.RtNoise.from_buffer_copy(got[skip][1]), rt.RtNoise.from_buffer_copy(want[skip][1])
+        tol = got[2][1].size * 2.0 ** -52
+        print(f"{case} {options} {kw}: figures {a.mean_luminance!r} / {b.mean_luminance!r}, {a.rms_sem!r} / {b.rms_sem!r}, {a.noise!r} / {b.noise!r}")
+        assert a.spp_done == b.spp_done == 7
+        for x, y in ((a.mean_luminance, b.mean_luminance), (a.rms_sem, b.rms_sem), (a.noise, b.noise)):
+            assert abs(x - y) <= tol * abs(y), (case, options, kw, x, y)
+        if options.get("pixel_order", 0) == 0:
+            assert got[skip][1] == want[skip][1], (case, options, kw, "the same pixel order: the same figures")
+        r2.accum_end()
+    finally:
+        for opt in options:
+            r2.set_option(opt, 0)
+
+
+# ---- 4. resume, adaptive ----------------------------------------------------------------------------------------------------------------
+def _tolerance(x):
+    """tests/test_adaptive.py: the median, over the pixels with any variance, of the relative standard error after 12 samples."""
+    rel = adaptive_ref.relative_error(x, 12, FLOOR)
+    rel = rel[np.isfinite(rel) & (rel > 0)]
+    return float(np.quantile(rel, 0.5))
+
+
+def _adaptive_replay_is(r, rp, what, stats=None):
+    img, rgb8, sem, noise = r.accum_read(want_rgb8=True, want_sem=True)
+    counts, info = r.accum_counts()
+    assert np.array_equal(counts, rp.cnt), (what, "counts")
+    _same(img, rp.image(), (what, "f32"))
+    _same(rgb8, denoise_ref.finalize_rgb8(rp.image()), (what, "rgb8"))
+    _same(sem, rp.sem(), (what, "sem"))
+    assert (info.n_active, info.n_samples, info.spp_min, info.spp_max) == rp.info(), (what, "info")
+    if stats is not None:
+        assert stats.n_paths == rp.traced[-1] == stats.rays_per_depth[0], (what, stats.n_paths, rp.traced[-1])
+
+
+@pytest.mark.parametrize("channels", [False, True])
+def test_resume_adaptive(rt, ctx, ctx2, channels):
+    r, r2 = ctx, ctx2
+    scene, prm = _setup(rt, r, "grid")
+    x = _singles(r, scene, prm, "grid", MAX)
+    tol = _tolerance(x)
+    fid = ref.frame_id_of(scene.camera, prm(STEP))
+    rp = adaptive_ref.Replay(x)
+    r.accum_begin(scene.camera, prm(STEP))
+    if channels:
+        r.accum_track_channels()
+    for _ in range(3):  # decisions at 0, 6 and 12 samples
+        r.accum_add_adaptive(STEP, tol, FLOOR, MIN), rp.adaptive(STEP, tol, FLOOR, MIN)
+    state = r.accum_export()
+    # coverage, on the state itself: some pixels have stopped, some go on, and they hold different numbers of samples
+    n_active = int((state.converged == 0).sum())
+    assert 0 < n_active < state.converged.size, n_active
+    assert len(np.unique(state.counts)) >= 2, np.unique(state.counts)
+    want_state = ref.replay_state(rp, fid)
+    if channels:
+        want_state["planes"] |= ref.CHANNELS
+        want_state["channel_moments"] = ref.channel_moments_counted(x, rp.cnt)
+    _state_is(state, want_state, ("adaptive", channels))
+    assert state.adaptive and state.done == 18 and state.check()
+    want_before = _everything(r, channels)
+    stats = r.accum_add_adaptive(STEP, tol, FLOOR, MIN)  # the uninterrupted run: the decision at 18 samples, then 6 more
+    want_after = _everything(r, channels)
+    r.accum_end()
+    _setup(rt, r2, "grid")
+    r2.accum_begin(scene.camera, prm(STEP))
+    r2.accum_import(state)
+    _states_equal(r2.accum_export(), state, ("adaptive", channels, "an export straight after the import"))
+    _all_same(_everything(r2, channels), want_before, ("adaptive", channels, "before the next add"))
+    st = r2.accum_add_adaptive(STEP, tol, FLOOR, MIN)
+    rp.adaptive(STEP, tol, FLOOR, MIN)
+    assert (st.n_paths, st.n_rays, list(st.rays_per_depth)) == (stats.n_paths, stats.n_rays, list(stats.rays_per_depth))
+    assert 0 < st.n_paths < state.converged.size * STEP
+    _adaptive_replay_is(r2, rp, ("adaptive", channels, "the add after the import"), st)
+    _all_same(_everything(r2, channels), want_after, ("adaptive", channels, "after the next add"))
+    _raises(rt, rt._ffi.ERR_STATE, r2.accum_add, 1)  # the imported accumulation is adaptive: a uniform add is refused as ever
+    r2.accum_end()
+
+
+# ---- 5. resume with channels ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["A", "B"])
+def test_resume_with_channels_uniform(rt, ctx, ctx2, case):
+    r, r2 = ctx, ctx2
+    scene, prm = _setup(rt, r, case)
+    x = _singles(r, scene, prm, case, 7)
+    fid = ref.frame_id_of(scene.camera, prm(1))
+    r.accum_begin(scene.camera, prm(4))
+    r.accum_track_channels()
+    r.accum_add(3)
+    state = r.accum_export()
+    _state_is(state, ref.uniform_state(x[:3], 0, fid, channels=True), (case, "channels"))
+    assert state.channels and (state.channel_moments != 0).any()
+    r.accum_add(4)
+    want = _everything(r, channels=True)
+    _state_is(r.accum_export(), ref.uniform_state(x, 0, fid, channels=True), (case, "channels, 7 samples"))
+    r.accum_end()
+    _setup(rt, r2, case)
+    for track_first in (False, True):  # the state turns tracking on; rt_accum_track_channels in between is accepted
+        r2.accum_begin(scene.camera, prm(4))
+        if track_first:
+            r2.accum_track_channels()
+        r2.accum_import(state)
+        _states_equal(r2.accum_export(), state, (case, track_first, "an export straight after the import"))
+        r2.accum_add(4)
+        _all_same(_everything(r2, channels=True), want, (case, track_first))
+    r2.accum_end()
+
+
+# ---- 6. merge ---------------------------------------------------------------------------------------------------------------------------
+def _window(rt, r, scene, prm, first, n, channels=False):
+    r.accum_begin(scene.camera, prm(max(n, 1)), first_sample=first)
+    if channels:
+        r.accum_track_channels()
+    if n:
+        r.accum_add(n)
+    return r.accum_export()
+
+
+@pytest.mark.parametrize("case", ["A", "B", "C", "D_lens"])
+def test_merge_of_two_windows(rt, ctx, ctx2, case):
+    r, r2 = ctx, ctx2
+    scene, prm = _setup(rt, r, case)
+    _setup(rt, r2, case)
+    x = _singles(r, scene, prm, case, 9)
+    fid = ref.frame_id_of(scene.camera, prm(1))
+    n, sharded = 7, CASES[case]["kw"].get("shard_count", 1) > 1
+    second = _window(rt, r2, scene, prm, 3, 4)  # [3, 7) on the second context
+    r2.accum_end()
+    _state_is(second, ref.uniform_state(x[3:7], 3, fid), (case, "the second window"))
+    _window(rt, r, scene, prm, 0, 3)            # [0, 3) on the first, left open
+    r.accum_merge(second)
+    merged = r.accum_export()
+    want = ref.merge(ref.uniform_state(x[:3], 0, fid), ref.uniform_state(x[3:7], 3, fid))
+    _state_is(merged, want, (case, "merged"))
+    assert (merged.first_sample, merged.done) == (0, 7)
+    img, rgb8, sem, noise = r.accum_read(want_rgb8=True, want_sem=True)
+    s1, s2 = want["moments"][..., 0], want["moments"][..., 1]
+    _same(sem, noise_ref.sem(s1, s2, n), (case, "sem on the merged moments"))
+    _same(img, (want["sum"] / np.float32(n)).astype(np.float32), (case, "the merged image"))
+    _same(rgb8, denoise_ref.finalize_rgb8(img), (case, "the merged rgb8"))
+    mean, rms, nz = noise_ref.frame_figures(s1, s2, n)
+    tol = sem.size * 2.0 ** -52
+    print(f"{case}: mean {noise.mean_luminance!r} / {mean!r}, rms_sem {noise.rms_sem!r} / {rms!r}, noise {noise.noise!r} / {nz!r}")
+    assert noise.spp_done == n
+    assert abs(noise.mean_luminance - mean) <= tol * mean and abs(noise.rms_sem - rms) <= tol * rms and abs(noise.noise - nz) <= tol * nz
+    # against one render of 7 samples: two sequential f32 sums of at most n terms, one add and one division on either side
+    one = r.render(scene.camera, prm(n))[0]
+    assert (one >= 0).all() and (img >= 0).all(), (case, "radiance is non-negative in these scenes")
+    big = np.maximum(img, one).astype(np.float64)
+    err = np.abs(img.astype(np.float64) - one.astype(np.float64))
+    bound = (2 * n + 2) * 2.0 ** -24 * big
+    differ = int((_bits(img) != _bits(one)).sum())
+    print(f"{case}: merged against rt_render({n}): {differ} of {img.size} values differ, largest error / bound {float((err / np.where(bound > 0, bound, 1)).max()):.3f}")
+    assert (err <= bound).all(), (case, float((err - bound).max()))
+    assert differ >= 1, (case, "the merged image is rt_render(7) in every bit: this frame cannot tell a merge from a render")
+    # two more uniform samples on the merged accumulation: the merged sum, then x[7] and x[8] in order
+    r.accum_add(2)
+    total, m1, m2 = want["sum"], s1, s2
+    for s in (7, 8):
+        total = (total + x[s]).astype(np.float32)
+        y = noise_ref.luminance(x[s])
+        m1, m2 = m1 + y, m2 + y * y
+    after = r.accum_export()
+    _same(after.sum, total, (case, "sum after two more samples"))
+    _same(after.moments, np.stack([m1, m2], axis=-1), (case, "moments after two more samples"))
+    assert (after.first_sample, after.done) == (0, 9)
+    _same(r.accum_read()[0], (total / np.float32(9)).astype(np.float32), (case, "image after two more samples"))
+    if not sharded:  # a merged accumulation has both filters for free
+        ybar, var = noise_ref.pixel_figures(m1, m2, 9)
+        c = (total / np.float32(9)).astype(np.float32)
+        _same(r.accum_denoise()[0], denoise_ref.denoise(c, ybar.astype(np.float32), var.astype(np.float32), 5, 1, rt._ffi.DENOISE_DEFAULT_STRENGTH)[0],
+              (case, "the filter on the merged accumulation"))
+    r.accum_end()
+
+
+def test_merge_chain_channels_and_an_empty_accumulation(rt, ctx, ctx2):
+    r, r2 = ctx, ctx2
+    scene, prm = _setup(rt, r, "A")
+    _setup(rt, r2, "A")
+    x = _singles(r, scene, prm, "A", 7)
+    fid = ref.frame_id_of(scene.camera, prm(1))
+    # a chain of three windows, 2 + 2 + 3, with channel moments
+    w = [_window(rt, r2, scene, prm, f, n, channels=True) for f, n in ((2, 2), (4, 3))]
+    r2.accum_end()
+    _window(rt, r, scene, prm, 0, 2, channels=True)
+    r.accum_merge(w[0]), r.accum_merge(w[1])
+    want = ref.merge(ref.merge(ref.uniform_state(x[:2], 0, fid, True), ref.uniform_state(x[2:4], 2, fid, True)), ref.uniform_state(x[4:7], 4, fid, True))
+    got = r.accum_export()
+    _state_is(got, want, "2 + 2 + 3 with channels")
+    assert got.done == 7 and got.channels
+    import denoise_channels_ref
+    _same(r.accum_channel_sem(), denoise_channels_ref.channel_sem(want["channel_moments"][..., 0::2], want["channel_moments"][..., 1::2], 7),
+          "channel sem on the merged moments")
+    # the same chain without channels differs from 3 + 4 in the grouping only: both are their own reference
+    _window(rt, r, scene, prm, 0, 2)
+    for f, n in ((2, 2), (4, 3)):
+        r.accum_merge(_window(rt, r2, scene, prm, f, n))
+    _state_is(r.accum_export(), ref.merge(ref.merge(ref.uniform_state(x[:2], 0, fid), ref.uniform_state(x[2:4], 2, fid)), ref.uniform_state(x[4:7], 4, fid)),
+              "2 + 2 + 3")
+    # a merge into an accumulation that holds no sample: 0 + x
+    first = _window(rt, r2, scene, prm, 0, 3)
+    r.accum_begin(scene.camera, prm(3))
+    r.accum_merge(first)
+    got = r.accum_export()
+    _state_is(got, ref.uniform_state(x[:3], 0, fid), "0 + x")
+    _same(r.accum_read()[0], r.render(scene.camera, prm(3))[0], "0 + x is rt_render(3)")
+    r.accum_add(4)  # and goes on from sample 3
+    _same(r.accum_read()[0], r.render(scene.camera, prm(7))[0], "0 + x, then four more samples")
+    # ... and one that begins later: the empty accumulation at sample 3 takes the window [3, 7)
+    later = _window(rt, r2, scene, prm, 3, 4)
+    r.accum_begin(scene.camera, prm(3), first_sample=3)
+    r.accum_merge(later)
+    _state_is(r.accum_export(), ref.uniform_state(x[3:7], 3, fid), "0 + x at sample 3")
+    r.accum_end(), r2.accum_end()
+
+
+# ---- 7. non-finite values ---------------------------------------------------------------------------------------------------------------
+def test_non_finite_values_travel_as_bits(rt, ctx):
+    r = ctx
+    scene, prm = _setup(rt, r, "A")
+    r.accum_begin(scene.camera, prm(7))
+    r.accum_add(7)
+    clean = r.accum_export()
+    clean_read = r.accum_read(want_sem=True)
+    state = r.accum_export()
+    nan_px, inf_px = (5, 7), (12, 30)
+    state.sum.view(np.uint32)[nan_px] = [0x7FC01234, 0xFFC00001, 0x7FC00000]  # NaNs with payloads
+    state.moments.view(np.uint64)[nan_px] = [0x7FF8DEADBEEF0001, 0x7FF8000000000002]
+    state.sum[inf_px] = np.inf
+    state.moments[inf_px] = np.inf
+    r.accum_begin(scene.camera, prm(7))
+    r.accum_import(state)
+    _states_equal(r.accum_export(), state, "NaN payloads and infinities through import and export")
+    img, _, sem, noise = r.accum_read(want_sem=True)
+    other = np.ones(sem.shape, bool)
+    other[nan_px] = other[inf_px] = False
+    assert np.isnan(img[nan_px]).all() and np.isinf(img[inf_px]).all() and np.isnan(sem[nan_px]) and np.isnan(sem[inf_px])
+    assert np.array_equal(_bits(img)[other], _bits(clean_read[0])[other]) and np.array_equal(_bits(sem)[other], _bits(clean_read[2])[other])
+    want_noise = noise_ref.frame_figures(state.moments[..., 0], state.moments[..., 1], 7)[2]
+    assert np.isnan(want_noise) and np.isnan(noise.noise)  # a frame figure over a NaN pixel is NaN, in the reference and on the device
+    # the filter on it: what "Denoising" says — the reference on these inputs, the two pixels stay what they are and spread to no other
+    ybar, var = noise_ref.pixel_figures(state.moments[..., 0], state.moments[..., 1], 7)
+    want = denoise_ref.denoise(img, ybar.astype(np.float32), var.astype(np.float32), 5, 1, rt._ffi.DENOISE_DEFAULT_STRENGTH)[0]
+    got = r.accum_denoise()[0]
+    _same(got, want, "the filter over a NaN and an inf pixel")
+    assert np.isfinite(got[other]).all() and np.array_equal(_bits(got[nan_px]), _bits(img[nan_px])) and np.isinf(got[inf_px]).all()
+    # a merge carries them too: NaN + x and inf + x
+    r.accum_begin(scene.camera, prm(7), first_sample=0)
+    state.first_sample, state.done = 0, 7
+    r.accum_merge(state)
+    m = r.accum_export()
+    assert np.isnan(m.sum[nan_px]).all() and np.isinf(m.sum[inf_px]).all() and np.array_equal(_bits(m.sum)[other], _bits(clean.sum)[other])
+    r.accum_end()
+
+
+# ---- 8. state and arguments -------------------------------------------------------------------------------------------------------------
+def test_state_and_arguments(rt, ctx, ctx2):
+    import copy
+    f = rt._ffi
+    r, r2 = ctx, ctx2
+    scene, prm = _setup(rt, r, "A")
+    _setup(rt, r2, "A")
+    r.accum_end()
+    blank = rt.AccumState(40, 20, sum=np.zeros((20, 40, 3), np.float32), moments=np.zeros((20, 40, 2)))
+    # no open accumulation
+    _raises(rt, f.ERR_STATE, r.accum_export)
+    _raises(rt, f.ERR_STATE, r.accum_import, blank)
+    _raises(rt, f.ERR_STATE, r.accum_merge, blank)
+    uniform = _window(rt, r2, scene, prm, 0, 3)
+    tracked = _window(rt, r2, scene, prm, 0, 3, channels=True)
+    nextwin = _window(rt, r2, scene, prm, 3, 4)
+    r2.accum_begin(scene.camera, prm(3))
+    r2.accum_add_adaptive(3, 0.05, 0.01, 2)
+    adaptive = r2.accum_export()
+    r2.accum_end()
+    assert adaptive.adaptive and adaptive.check()
+
+    def held(what, fn, code, *a):
+        """fn(*a) fails with `code` and the open accumulation of r returns the bits from before, from a read and from an export."""
+        before_read, before_state = r.accum_read(want_rgb8=True, want_sem=True), r.accum_export()
+        _raises(rt, code, fn, *a)
+        after = r.accum_read(want_rgb8=True, want_sem=True)
+        for k in range(3):
+            _same(after[k], before_read[k], (what, "read", k))
+        assert bytes(after[3]) == bytes(before_read[3]), what
+        _states_equal(r.accum_export(), before_state, (what, "export"))
+
+    def variant(s, **kw):
+        t = copy.copy(s)
+        for k, v in kw.items():
+            setattr(t, k, v)
+        return t
+
+    # ---- rt_accum_export: channel_moments asked of an accumulation that does not track channels
+    r.accum_begin(scene.camera, prm(3))
+    r.accum_add(3)
+    st = variant(tracked).as_struct()
+    before = r.accum_export()
+    assert r._lib.rt_accum_export(r._ctx, st) == -f.ERR_STATE
+    _states_equal(r.accum_export(), before, "after the refused export")
+    assert r._lib.rt_accum_export(r._ctx, None) == -f.ERR_INVALID
+    # NULL pointers skip their planes: the scalar fields alone, and one plane alone
+    bare = f.RtAccumState()
+    assert r._lib.rt_accum_export(r._ctx, bare) == 0 and (bare.nx, bare.rows, bare.first_sample, bare.done, bare.planes, bare.frame_id) == \
+        (40, 20, 0, 3, 0, before.frame_id)
+    only = rt.AccumState(40, 20, moments=np.full((20, 40, 2), -1.0))
+    st = f.RtAccumState()
+    st.moments = only.moments.ctypes.data_as(type(st.moments))
+    assert r._lib.rt_accum_export(r._ctx, st) == 0
+    _same(only.moments, before.moments, "the moments alone")
+    # ---- rt_accum_import: after samples were added
+    held("import after an add", r.accum_import, f.ERR_STATE, uniform)
+    r.accum_begin(scene.camera, prm(3))
+    r.accum_add_adaptive(3, 0.05, 0.01, 2)
+    held("import after an adaptive add", r.accum_import, f.ERR_STATE, adaptive)
+    # ---- rt_accum_import: a state the check refuses, and every mismatch, one by one
+    r.accum_begin(scene.camera, prm(3))
+    bad_counts = variant(adaptive, counts=adaptive.counts.copy())
+    bad_counts.counts[3, 3] += 1
+    wrong = [("planes", variant(uniform, planes=4)), ("counts past done", bad_counts), ("first + done", variant(uniform, done=2 ** 32 - 1, first_sample=1)),
+             ("frame_id", variant(uniform, frame_id=uniform.frame_id ^ 1)), ("first_sample", variant(nextwin)),
+             ("nx", rt.AccumState(20, 40, 0, 3, 0, uniform.frame_id, sum=uniform.sum.reshape(40, 20, 3), moments=uniform.moments.reshape(40, 20, 2))),
+             ("rows", rt.AccumState(40, 10, 0, 3, 0, uniform.frame_id, sum=uniform.sum[:10], moments=uniform.moments[:10]))]
+    for what, s in wrong:
+        held(("import", what), r.accum_import, f.ERR_INVALID, s)
+    st = uniform.as_struct()
+    st.reserved = 1
+    assert r._lib.rt_accum_import(r._ctx, st) == -f.ERR_INVALID and r._lib.rt_accum_import(r._ctx, None) == -f.ERR_INVALID
+    for name in ("sum", "moments"):
+        st = uniform.as_struct()
+        setattr(st, name, None)
+        assert r._lib.rt_accum_import(r._ctx, st) == -f.ERR_INVALID, name
+    st = uniform.as_struct()  # counts on a state without RT_ACCUM_STATE_COUNTS: what a careless export of a uniform accumulation leaves
+    st.counts, st.converged = uniform.counts.ctypes.data_as(type(st.counts)), uniform.converged.ctypes.data_as(type(st.converged))
+    assert r._lib.rt_accum_import(r._ctx, st) == -f.ERR_INVALID
+    # another frame: the same state against a camera, a seed, a depth and a shard of its own
+    r.accum_begin(scene.camera, prm(3, seed=SEED + 1))
+    held("import, another seed", r.accum_import, f.ERR_INVALID, uniform)
+    r.accum_begin(scene.camera, prm(3, max_depth=49))
+    held("import, another depth", r.accum_import, f.ERR_INVALID, uniform)
+    r.accum_begin(scene.camera, prm(3, flags=f.FLAG_RUSSIAN_ROULETTE))
+    held("import, Russian roulette", r.accum_import, f.ERR_INVALID, uniform)
+    # the accumulation tracks channels and the state has none
+    r.accum_begin(scene.camera, prm(3))
+    r.accum_track_channels()
+    held("import without channels into tracking", r.accum_import, f.ERR_INVALID, uniform)
+    r.accum_import(tracked)  # (still importable after the refusals)
+    _states_equal(r.accum_export(), tracked, "import after refused imports")
+    # ---- rt_accum_merge
+    r.accum_begin(scene.camera, prm(3))
+    r.accum_add(3)
+    held("merge of an adaptive state", r.accum_merge, f.ERR_UNSUPPORTED, variant(adaptive, first_sample=3))
+    for what, s in [("not adjacent: the same window", uniform), ("not adjacent: a gap", variant(nextwin, first_sample=4)),
+                    ("frame_id", variant(nextwin, frame_id=nextwin.frame_id ^ 1)), ("planes", variant(nextwin, planes=8)),
+                    ("channels in the state only", variant(tracked, first_sample=3)),
+                    ("rows", rt.AccumState(40, 10, 3, 4, 0, nextwin.frame_id, sum=nextwin.sum[:10], moments=nextwin.moments[:10]))]:
+        held(("merge", what), r.accum_merge, f.ERR_INVALID, s)
+    with pytest.raises(rt.RtError, match="not adjacent"):
+        r.accum_merge(uniform)
+    r.accum_merge(nextwin)  # (still mergeable after the refusals)
+    assert r.accum_export().done == 7
+    r.accum_begin(scene.camera, prm(3))
+    r.accum_track_channels()
+    r.accum_add(3)
+    held("merge, channels in the accumulation only", r.accum_merge, f.ERR_INVALID, nextwin)
+    r.accum_begin(scene.camera, prm(3))
+    r.accum_add_adaptive(3, 0.05, 0.01, 2)
+    held("merge into an adaptive accumulation", r.accum_merge, f.ERR_UNSUPPORTED, nextwin)
+    # past 2^32 - 1: the window [2^32 - 3, 2^32 - 2) and a state that claims three samples behind it
+    r.accum_begin(scene.camera, prm(1), first_sample=2 ** 32 - 3)
+    r.accum_add(1)
+    held("merge past the bound", r.accum_merge, f.ERR_INVALID, variant(nextwin, first_sample=2 ** 32 - 2, done=3))
+    r.accum_merge(variant(nextwin, first_sample=2 ** 32 - 2, done=1))  # up to the bound it goes
+    assert r.accum_export().done == 2
+    _raises(rt, f.ERR_INVALID, r.accum_add, 1)
+    # what ends an accumulation ends these calls too
+    r.upload(scene)
+    _raises(rt, f.ERR_STATE, r.accum_export)
+    # ---- a shard without pixels: RT_OK for all three
+    r.accum_begin(scene.camera, prm(3, shard_count=8, shard_band=4, shard_id=7))  # 20 rows in bands of 4: shards 5, 6 and 7 own none
+    assert r.shard_rows(prm(3, shard_count=8, shard_band=4, shard_id=7)) == 0
+    r.accum_add(3)
+    e = r.accum_export()
+    assert (e.nx, e.rows, e.done, e.sum.size) == (40, 0, 3, 0) and e.check()
+    r.accum_begin(scene.camera, prm(3, shard_count=8, shard_band=4, shard_id=7))
+    r.accum_import(e)
+    assert r.accum_export().done == 3
+    r.accum_merge(variant(e, first_sample=3, done=4))
+    assert r.accum_export().done == 7
+    r.accum_end()
+
+
+# ---- 9. ledger --------------------------------------------------------------------------------------------------------------------------
+def test_the_three_calls_launch_no_tabled_kernel(rt, ctx, ctx2):
+    r, r2 = ctx, ctx2
+    scene, prm = _setup(rt, r, "A")
+    _setup(rt, r2, "A")
+    nextwin = _window(rt, r2, scene, prm, 3, 4, channels=True)
+    r2.accum_end()
+    r.launched_variants(reset=True)
+    nothing = r.launched_variants()
+    assert not any(nothing.values()), nothing
+    r.accum_begin(scene.camera, prm(4))
+    r.accum_track_channels()
+    r.accum_add(3)
+    plain_add = r.launched_variants(reset=True)
+    assert plain_add["shade"] and not plain_add["debug_bounce"]
+    state = r.accum_export()
+    r.accum_merge(nextwin)
+    r.accum_begin(scene.camera, prm(4))
+    r.accum_import(state)
+    assert r.launched_variants(reset=True) == nothing, "export, merge and import launch kernels outside the tables and the ledger families"
+    r.accum_add(3)
+    assert r.launched_variants(reset=True) == plain_add, "the ledger of an add after an import is that of an add without one"
+    r.accum_end()
+
+
+# ---- 10. render.py ----------------------------------------------------------------------------------------------------------------------
+def _render_py(tmp_path, *args):
+    cmd = [sys.executable, "-m", "ray_tracing_in_one_weekend_amd.render", "--scene", "test_sphere", "--nx", "40", "--ny", "20", "--max-depth", "8",
+           "--seed", "7", *[str(a) for a in args]]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    return p
+
+
+def test_render_py_checkpoint_and_resume(rt, tmp_path):
+    whole, part, resumed, ck = (tmp_path / n for n in ("whole.png", "part.png", "resumed.png", "ck.npz"))
+    p = _render_py(tmp_path, "--spp", 12, "--spp-step", 4, "--out", whole)
+    assert p.returncode == 0, p.stderr[-2000:]
+    p = _render_py(tmp_path, "--spp", 4, "--spp-step", 4, "--checkpoint", ck, "--out", part)  # stopped after the first step
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert sorted(os.listdir(tmp_path)) == ["ck.npz", "part.png", "whole.png"]
+    state = rt.AccumState.load(str(ck))
+    assert (state.first_sample, state.done, state.planes) == (0, 4, 0) and state.check()
+    p = _render_py(tmp_path, "--spp", 12, "--spp-step", 4, "--resume", ck, "--out", resumed)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert "8/12" in p.stderr and "12/12" in p.stderr and "4/12" not in p.stderr  # two steps were left
+    assert open(resumed, "rb").read() == open(whole, "rb").read()
+    assert open(part, "rb").read() != open(whole, "rb").read()
+
+
+def test_render_py_windows_and_merge(rt, tmp_path):
+    from PIL import Image
+    w0, w1, out = (tmp_path / n for n in ("w0.npz", "w1.npz", "merged.png"))
+    p = _render_py(tmp_path, "--first-sample", 5, "--spp", 7, "--spp-step", 4, "--checkpoint", w1, "--out", tmp_path / "w1.png")
+    assert p.returncode == 0, p.stderr[-2000:]
+    p = _render_py(tmp_path, "--first-sample", 0, "--spp", 5, "--spp-step", 4, "--checkpoint", w0, "--merge", w1, "--out", out)
+    assert p.returncode == 0, p.stderr[-2000:]
+    a, b = rt.AccumState.load(str(w0)), rt.AccumState.load(str(w1))
+    assert (b.first_sample, b.done) == (5, 7) and (a.first_sample, a.done) == (0, 12)  # the merged state is the checkpoint's last word
+    # the first window alone, for the reference: resume nothing, render [0, 5) again without the merge
+    p = _render_py(tmp_path, "--first-sample", 0, "--spp", 5, "--spp-step", 4, "--checkpoint", w0, "--out", tmp_path / "w0.png")
+    assert p.returncode == 0, p.stderr[-2000:]
+    a0 = rt.AccumState.load(str(w0))
+    assert (a0.first_sample, a0.done) == (0, 5)
+
+    def as_dict(s):
+        return dict(nx=s.nx, rows=s.rows, first_sample=s.first_sample, done=s.done, planes=s.planes, frame_id=s.frame_id, sum=s.sum, moments=s.moments)
+    want = ref.merge(as_dict(a0), as_dict(b))
+    _same(a.sum, want["sum"], "the merged checkpoint")
+    _same(a.moments, want["moments"], "the merged checkpoint, moments")
+    img = (want["sum"] / np.float32(12)).astype(np.float32)
+    assert np.array_equal(np.asarray(Image.open(out)), denoise_ref.finalize_rgb8(img))
+    # a window that is not adjacent is an error with the library's text
+    p = _render_py(tmp_path, "--first-sample", 0, "--spp", 4, "--spp-step", 4, "--merge", w1, "--out", tmp_path / "bad.png")
+    assert p.returncode != 0 and "not adjacent" in p.stderr and not (tmp_path / "bad.png").exists(), p.stderr[-2000:]
