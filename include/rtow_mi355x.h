@@ -522,7 +522,9 @@ int rt_render_to_noise(RtCtx* ctx, const RtCamera* cam, const RtParams* params, 
  * Mixing.  rt_accum_add calls BEFORE the first adaptive add are allowed (a warm-up: n_p starts at what they added); rt_accum_add AFTER
  * an adaptive add is RT_ERR_STATE.  Everything that ends an accumulation ends an adaptive one; rt_render in between disturbs nothing.
  * Reading.  rt_accum_read divides by (float)n_p per pixel; out_sem and the frame figures use n_p per pixel (V_p = 0 where n_p < 2) over
- * the same fixed tree; noise is +inf where any n_p < 2; RtNoise.spp_done = max_p n_p.  rt_accum_denoise takes c, y, v with n_p per pixel.
+ * the same fixed tree; noise is +inf where any n_p < 2; RtNoise.spp_done = max_p n_p.  rt_accum_denoise takes c, y, v with n_p per pixel;
+ * a pixel with n_p < 2 beside done >= 2 (only an imported state holds one: "Accumulation state") has no variance to be compared by: its c
+ * is sum / (float)max(n_p, 1) as rt_accum_read writes it, its y and v are NaN, so it stays what it is and spreads to no other pixel.
  * Depth 0 of an adaptive add runs on the materialised ray queue (the fused depth-0 kernels and the candidate lists invert a queue position
  * into a pixel, which a compacted queue does not allow): per traced sample it costs what RT_OPT_MATERIALISE_PRIMARIES costs (DESIGN.md
  * "Adaptive sampling").  Not covered: rt_multi_*; un-sticking a pixel; per-channel criteria. */

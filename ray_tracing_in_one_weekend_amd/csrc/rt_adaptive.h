@@ -215,7 +215,9 @@ __global__ __launch_bounds__(256) void k_noise_final_counts(const double2* __res
     if (info->spp_min < 2u) noise = (double)INFINITY;
     out[0] = mean, out[1] = rms, out[2] = noise;
 }
-// k_denoise_inputs with the pixel's own n_p: c = sum / (float)n_p, (y, v) from its moments and n_p.
+// k_denoise_inputs with the pixel's own n_p: c = sum / (float)n_p, (y, v) from its moments and n_p.  A pixel with n_p < 2 has no variance
+// (only an imported state holds one beside done >= 2: rt_accum_state_check accepts a converged pixel with any counts[p] <= done): its c is
+// what rt_accum_read returns, sum / (float)max(n_p, 1), and its guide is NaN, so that it stays what it is and spreads to no other pixel.
 __global__ __launch_bounds__(256) void k_denoise_inputs_counts(const float* __restrict__ sum, const double2* __restrict__ mom, const uint32_t* __restrict__ cnt,
                                                                float* __restrict__ c, float2* __restrict__ yv, uint32_t nx, uint32_t rows,
                                                                uint32_t tiles_per_row, uint32_t tile_pixels) {
@@ -223,11 +225,12 @@ __global__ __launch_bounds__(256) void k_denoise_inputs_counts(const float* __re
     if (p >= nx * rows) return;
     const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx);
     const uint32_t n = cnt[ap];
-    const float fs = (float)n;
+    const float fs = (float)(n ? n : 1u);
     c[3 * (size_t)p] = sum[3 * ap] / fs, c[3 * (size_t)p + 1] = sum[3 * ap + 1] / fs, c[3 * (size_t)p + 2] = sum[3 * ap + 2] / fs;
     double ybar, v;
     pixel_noise(mom[ap], n, ybar, v);
-    yv[p] = make_float2((float)ybar, (float)v);
+    const float none = __uint_as_float(0x7FC00000u);
+    yv[p] = n >= 2u ? make_float2((float)ybar, (float)v) : make_float2(none, none);
 }
 
 } // namespace rt

@@ -1872,7 +1872,7 @@ __global__ __launch_bounds__(256) void k_sem(const double2* __restrict__ mom, fl
 }
 // Frame figures, a fixed tree and no atomics: per workgroup (sum Ybar, sum V) of its 256 pixels — lanes by __shfl_down, the four waves
 // through LDS in wave order — then ONE workgroup over the partials, thread t taking partials t, t + 256, ... in index order and the same
-// two steps.  The same moments give the same bits, whatever else the device runs.
+// two steps.  The same moments give the same bits, whatever else the device runs (tests/noise_tree_ref.py adds over this tree in numpy).
 __device__ __forceinline__ double2 block_sum_256(double a, double b, double2* part) {
     for (int off = 32; off > 0; off >>= 1) {
         a += __shfl_down(a, off);
