@@ -587,7 +587,8 @@ int rt_adaptive_converged(const RtAdaptive* ad, double s1, double s2, uint32_t n
  * Not covered: the distance is on LUMINANCE, the one quantity whose variance an accumulation keeps by default — edges between colours of
  * equal luminance blur; "Channel moments and the colour-guided filter" below keeps a variance per channel (48 B per pixel more, opt-in)
  * and filters on it; the weights are chosen from the
- * image they filter (there are no two half buffers, so the filter is slightly biased towards its own noise); rt_multi_* is not supported.
+ * image they filter — "Half buffers" below keeps the even and the odd samples apart (56 B per pixel more, opt-in), filters each half with
+ * the other's weights and reports the variance that is left; rt_multi_* is not supported.
  * DESIGN.md "Denoising". */
 typedef struct RtDenoise { uint32_t radius, patch; float strength; uint32_t reserved; } RtDenoise;
 #define RT_DENOISE_MAX_RADIUS 10u
@@ -698,6 +699,94 @@ int rt_accum_import(RtCtx* ctx, const RtAccumState* st);
  * accumulation.  RT_ERR_UNSUPPORTED: either side is adaptive (windows of pixels with different n_p are not contiguous).  RT_ERR_INVALID:
  * every other mismatch, a state rt_accum_state_check refuses, samples past 2^32 - 1.  Synchronises once. */
 int rt_accum_merge(RtCtx* ctx, const RtAccumState* st);
+
+/* -- half buffers: the even and the odd samples of every pixel, the cross-filtered denoise and its residual ---------------------------------
+ * "Denoising" chooses its weights from the image it filters, so it leans towards its own noise, and once it has run nothing says how
+ * noisy its result still is.  Rousselle, Knaus, Zwicker 2012 (section 4) answer both with two HALF BUFFERS: the even and the odd samples
+ * of every pixel are kept apart, each half is filtered with weights taken from the OTHER one, the two results are averaged, and the
+ * variance that is left is read off their difference.  The two half images are also what external denoisers ask a renderer for.
+ * Tracking.  An accumulation that TRACKS HALVES also keeps, per pixel and half h in {0, 1}, an f32 x 3 sum and the two f64 luminance
+ * moments of "Moments": 56 B per pixel more, in the local pixel order of the sums, allocated by rt_accum_track_halves (or
+ * rt_accum_import_halves) and kept for the next accumulation like the other accumulation buffers.  The sample with the ABSOLUTE index
+ * i = first_sample + k goes to half i & 1, in sample order, with the arithmetic of "Moments" (IEEE f32 / f64 additions, no FMA), across
+ * slices and adds, uniform or adaptive.  Of the n samples a pixel holds (n_p after adaptive adds), n_0 = the number of even i in
+ * [first_sample, first_sample + n) and n_1 = n - n_0 belong to the halves; they follow from (first_sample, n) and are stored nowhere.
+ * Defining property: half h of pixel p is, bit for bit, what the in-order f32 / f64 additions of the pixel's samples of parity h give,
+ * however adds and slices are cut, for either pixel order, on shards, and after adaptive adds with n = n_p.
+ * Everything an accumulation returned before — the images, sem, the frame figures, the counts, both filters, the exported state — is
+ * unchanged in every bit with tracking on or off: the resolve kernels are the same ones, a kernel of its own reads the radiance of a slice
+ * a second time for the halves.
+ * The cross filter.  Per half, in image order:  c_h = sum_h / (float)max(n_h, 1);  y_h = (float)Ybar_h, v_h = (float)V_h from the half's
+ * moments with n = n_h, both NaN where n_h < 2 (as a pixel with n_p < 2 in "Adaptive sampling").  f_h is "Denoising" word for word with the
+ * colours c_h and the guide (y, v) = (y_{1-h}, v_{1-h}).  Combine, per channel, every operation one IEEE f32 operation:
+ *   a_h = (float)n_h;   out = (f_0 * a_0 + f_1 * a_1) / (a_0 + a_1);   out = f_0 where n_1 == 0, else f_1 where n_0 == 0.
+ * Residual, every operation one IEEE f32 operation:  l(x) = (0.2126f x_r + 0.7152f x_g) + 0.0722f x_b;  d = l(f_0) - l(f_1);
+ *   e_p = (d * d) * ((a_0 * a_1) / ((a_0 + a_1) * (a_0 + a_1)));   e_p = NaN where n_0 == 0 or n_1 == 0.
+ * For two independent estimates with variances sigma^2 / n_h, e_p estimates the variance of their n_h-weighted mean.
+ * Frame figures (RtResidual), in f64 over the pixels in image order, on the fixed tree of "Moments" (per workgroup of 256 pixels, then
+ * one workgroup over the partial sums in index order; no floating-point atomics):
+ *   mean_luminance = sum_p (double)l(out_p) / npix;   residual_rms = sqrt(sum_p (double)e_p / npix);
+ *   residual_noise = residual_rms / mean_luminance, with the zero rule of RtNoise.noise; a NaN propagates.
+ * WHAT THE FIGURE IS.  The difference of the halves sees the VARIANCE of the filtered frame; it does not see the blur that both halves
+ * share.  residual_rms is therefore the variance half of the filtered frame's error — a LOWER BOUND of the error, never the error.
+ * Numpy restatement on a synthetic 37 x 21 frame, two halves of 8 heavy-tailed samples, R 5, F 1:
+ *   strength   RMSE cross-filtered   RMSE self-guided (16 samples)   residual_rms   true luminance RMSE
+ *     0.45          0.1008                  0.0991                      0.064            0.100
+ *     1.0           0.1245                  0.0980                      0.031            0.121
+ * A NON-FINITE SAMPLE lands in one half.  The other half's guide is finite there, so — unlike in "Denoising" — the half that holds it is
+ * filtered with finite weights and carries the value to the pixels within R of it; out, e_p and the frame figures follow (NaN).  The
+ * half guided by the bad one keeps it out.  A host that must contain such pixels reads the halves and masks them.
+ * Half guides are noisier than the whole pixel's, so the best strength is not that of "Denoising": RT_DENOISE_HALVES_DEFAULT_STRENGTH
+ * is chosen by measurement on rendered frames (DESIGN.md "Half buffers").
+ * State.  RtAccumHalves carries the four planes in the row order of out_rgb_f32, as RtAccumState carries the accumulation's.  Resume is
+ * rt_accum_begin, rt_accum_import, rt_accum_import_halves: from then on everything, the calls of this section included, is bit for bit
+ * what the uninterrupted accumulation returns.  rt_accum_import and rt_accum_merge on an accumulation that already tracks halves are
+ * RT_ERR_UNSUPPORTED and change nothing (the halves would no longer belong to the sums; a merge of halves is not covered).
+ * Tracking can only be turned on while the accumulation holds no sample or — through rt_accum_import_halves — together with the halves
+ * that belong to its samples, so a tracking accumulation's halves are always those of its samples.
+ * Not covered: the colour-guided cross filter (channel moments per half); a merge of halves; rt_multi_*; sharded frames for the filter
+ * (RT_ERR_UNSUPPORTED, as rt_accum_denoise; the half images read on shards).  DESIGN.md "Half buffers". */
+#define RT_DENOISE_HALVES_DEFAULT_STRENGTH 0.7f /* of 0.45, 0.7 and 1.0 by the rule of RT_DENOISE_DEFAULT_STRENGTH (DESIGN.md "Half buffers") */
+typedef struct RtResidual {
+    double mean_luminance;   /* (sum_p l(out_p)) / npix of the cross-filtered frame */
+    double residual_rms;     /* sqrt((sum_p e_p) / npix): the variance half of the filtered frame's error, a lower bound */
+    double residual_noise;   /* residual_rms / mean_luminance, the zero rule of RtNoise.noise */
+    uint32_t reserved[2];
+} RtResidual;
+typedef struct RtAccumHalves {
+    uint32_t nx, rows;           /* the shard: rows = rows_local */
+    uint32_t first_sample, done; /* those of the accumulation the halves belong to */
+    uint32_t reserved[2];        /* 0 */
+    uint64_t frame_id;           /* rt_accum_frame_id of the frame */
+    float*  sum[2];              /* [rows*nx*3] per half: the running f32 sums, NOT divided */
+    double* moments[2];          /* [rows*nx*2] per half: S1, S2 */
+} RtAccumHalves;
+/* Makes the open accumulation track halves and clears them.  The rules of rt_accum_track_channels: after rt_accum_begin and before the
+ * first add, uniform or adaptive, else RT_ERR_STATE (also after an rt_accum_import that brought samples: their halves come through
+ * rt_accum_import_halves).  A second call is RT_OK and changes nothing.  Tracking ends with the accumulation.  Combines freely with
+ * rt_accum_track_channels. */
+int rt_accum_track_halves(RtCtx* ctx);
+/* Half h of the frame so far: out_rgb_f32 [rows_local*nx*3] = sum_h / (float)max(n_h, 1); out_sem [rows_local*nx] = (float)sqrt(V_h) with
+ * n = n_h, 0 where n_h < 2; the layouts of rt_accum_read, each pointer may be NULL.  Works on shards.  Synchronises the context's stream
+ * once.  RT_ERR_INVALID: h > 1.  RT_ERR_STATE: no open accumulation, or it does not track halves. */
+int rt_accum_read_halves(RtCtx* ctx, uint32_t h, float* out_rgb_f32, float* out_sem);
+/* The cross filter above.  `dn` NULL: radius 5, patch 1, strength RT_DENOISE_HALVES_DEFAULT_STRENGTH.  out_rgb_f32 and out_rgb8 as
+ * rt_accum_denoise writes them; out_err [rows_local*nx] = e_p in the row order of out_rgb_f32; each of the four outputs may be NULL.  The
+ * accumulation is read and not changed.  Synchronises the context's stream once.  The errors of rt_accum_denoise, and RT_ERR_STATE where
+ * the accumulation does not track halves or fewer than 4 samples are done (a uniform accumulation then has a half with n_h < 2). */
+int rt_accum_denoise_halves(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8, float* out_err, RtResidual* res);
+/* GPU-free.  RT_OK, or RT_ERR_INVALID unless: `hs` non-NULL, both reserved words 0, the four planes non-NULL, first_sample + done <=
+ * 2^32 - 1.  Values are not judged. */
+int rt_accum_halves_check(const RtAccumHalves* hs);
+/* Fills the scalar fields of `hs` and writes every plane whose pointer is non-NULL; a NULL pointer skips that plane (all NULL: the scalar
+ * fields alone, without any device work).  Reads, and changes nothing.  Synchronises the context's stream once.  RT_ERR_STATE: no open
+ * accumulation, or it does not track halves. */
+int rt_accum_export_halves(RtCtx* ctx, RtAccumHalves* hs);
+/* Puts `hs` into the open accumulation and turns tracking on, with the allocation of rt_accum_track_halves.  Allowed while the
+ * accumulation has had no add (and no merge) since rt_accum_begin — fresh with done 0, or after rt_accum_import — else RT_ERR_STATE.
+ * Values are copied as bits.  RT_ERR_INVALID: rt_accum_halves_check fails, or nx, rows, frame_id, first_sample or done differ from the
+ * accumulation's.  A failed call leaves the accumulation as it was.  Synchronises once. */
+int rt_accum_import_halves(RtCtx* ctx, const RtAccumHalves* hs);
 
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the

@@ -154,6 +154,20 @@ class RtAccumState(C.Structure):
 
 DENOISE_MAX_RADIUS, DENOISE_MAX_PATCH = 10, 3
 DENOISE_DEFAULT_STRENGTH = 1.0  # RT_DENOISE_DEFAULT_STRENGTH
+DENOISE_HALVES_DEFAULT_STRENGTH = 0.7  # RT_DENOISE_HALVES_DEFAULT_STRENGTH
+
+
+class RtResidual(C.Structure):
+    """rt_accum_denoise_halves: the frame figures of the cross-filtered frame (rtow_mi355x.h "half buffers"); residual_rms is the variance
+    half of the filtered frame's error, a lower bound."""
+    _fields_ = [("mean_luminance", C.c_double), ("residual_rms", C.c_double), ("residual_noise", C.c_double), ("reserved", C.c_uint32 * 2)]
+
+
+class RtAccumHalves(C.Structure):
+    """rt_accum_export_halves / rt_accum_import_halves: the two half buffers of an accumulation, as host arrays in the row order of the f32
+    image (rtow_mi355x.h "half buffers")."""
+    _fields_ = [("nx", C.c_uint32), ("rows", C.c_uint32), ("first_sample", C.c_uint32), ("done", C.c_uint32), ("reserved", C.c_uint32 * 2),
+                ("frame_id", C.c_uint64), ("sum", _f * 2), ("moments", C.POINTER(C.c_double) * 2)]
 
 
 class RtBounceIO(C.Structure):
@@ -212,6 +226,8 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_accum_add_adaptive", "rt_accum_read_counts", "rt_render_adaptive", "rt_adaptive_check", "rt_adaptive_converged",
                "rt_debug_accum_set_moments",
                "rt_accum_frame_id", "rt_accum_state_check", "rt_accum_export", "rt_accum_import", "rt_accum_merge",
+               "rt_accum_track_halves", "rt_accum_read_halves", "rt_accum_denoise_halves", "rt_accum_halves_check", "rt_accum_export_halves",
+               "rt_accum_import_halves",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
@@ -336,6 +352,18 @@ def load_gpu_library():
     lib.rt_accum_import.restype = C.c_int
     lib.rt_accum_merge.argtypes = [vp, C.POINTER(RtAccumState)]
     lib.rt_accum_merge.restype = C.c_int
+    lib.rt_accum_track_halves.argtypes = [vp]
+    lib.rt_accum_track_halves.restype = C.c_int
+    lib.rt_accum_read_halves.argtypes = [vp, C.c_uint32, _f, _f]
+    lib.rt_accum_read_halves.restype = C.c_int
+    lib.rt_accum_denoise_halves.argtypes = [vp, C.POINTER(RtDenoise), _f, _u8, _f, C.POINTER(RtResidual)]
+    lib.rt_accum_denoise_halves.restype = C.c_int
+    lib.rt_accum_halves_check.argtypes = [C.POINTER(RtAccumHalves)]
+    lib.rt_accum_halves_check.restype = C.c_int
+    lib.rt_accum_export_halves.argtypes = [vp, C.POINTER(RtAccumHalves)]
+    lib.rt_accum_export_halves.restype = C.c_int
+    lib.rt_accum_import_halves.argtypes = [vp, C.POINTER(RtAccumHalves)]
+    lib.rt_accum_import_halves.restype = C.c_int
     lib.rt_debug_planar_info.argtypes =[vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.rt_debug_planar_info.restype = C.c_int
     lib.rt_debug_planar_bounds.argtypes = [C.POINTER(RtQuads), C.c_float, vp, vp]

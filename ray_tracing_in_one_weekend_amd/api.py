@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import RtAdaptive, RtAdaptiveInfo, RtBounceIO, RtCamera, RtDenoise, RtFlatScene, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtStats
+from ._ffi import RtAdaptive, RtAdaptiveInfo, RtBounceIO, RtCamera, RtDenoise, RtFlatScene, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtResidual, RtStats
 
 
 class RtError(RuntimeError):
@@ -423,6 +423,65 @@ def variant_tables():
     return _ledger_sets(led)
 
 
+class AccumHalves:
+    """The two half buffers of an accumulation (rtow_mi355x.h "half buffers"), as numpy arrays in the row order of the f32 image plus the
+    scalar fields of RtAccumHalves: sum [2, rows, nx, 3] f32 (not divided) and moments [2, rows, nx, 2] f64, half 0 (the samples with an
+    even absolute index) first.  It goes with the AccumState of the same accumulation: first_sample and done are that state's."""
+    _SCALARS = ("nx", "rows", "first_sample", "done", "frame_id")
+
+    def __init__(self, nx, rows, first_sample=0, done=0, frame_id=0, sum=None, moments=None):
+        self.nx, self.rows, self.first_sample, self.done, self.frame_id = int(nx), int(rows), int(first_sample), int(done), int(frame_id)
+        for name, arr, dt, k in (("sum", sum, np.float32, 3), ("moments", moments, np.float64, 2)):
+            arr = np.zeros((2, self.rows, self.nx, k), dt) if arr is None else np.ascontiguousarray(arr, dtype=dt)
+            if arr.shape != (2, self.rows, self.nx, k):
+                raise ValueError(f"AccumHalves.{name}: shape {arr.shape}, expected {(2, self.rows, self.nx, k)}")
+            setattr(self, name, arr)
+
+    def as_struct(self):
+        """The RtAccumHalves over these arrays (which must stay alive while it is used)."""
+        hs = _ffi.RtAccumHalves(self.nx, self.rows, self.first_sample, self.done)
+        hs.frame_id = self.frame_id
+        for h in range(2):
+            hs.sum[h] = self.sum[h].ctypes.data_as(C.POINTER(C.c_float))
+            hs.moments[h] = self.moments[h].ctypes.data_as(C.POINTER(C.c_double))
+        return hs
+
+    def check(self):
+        """rt_accum_halves_check (no GPU): True when the library would accept the halves before comparing them with an accumulation."""
+        hs = self.as_struct()
+        return _ffi.load_gpu_library().rt_accum_halves_check(C.byref(hs)) == 0
+
+    def counts(self, n=None):
+        """(n_0, n_1): how many of the `n` samples of a pixel (default: done; an array of per-pixel counts after adaptive adds) each half holds."""
+        n = np.asarray(self.done if n is None else n, dtype=np.uint64)
+        n0 = n // 2 + (n & 1 & ~np.uint64(self.first_sample))
+        return n0, n - n0
+
+    def save(self, path):
+        """Writes the halves as an .npz at exactly `path`, through a temporary file beside it and os.replace, as AccumState.save does."""
+        import os
+        import tempfile
+        data = {k: np.asarray(getattr(self, k), dtype=np.uint64) for k in self._SCALARS}
+        data.update(sum=self.sum, moments=self.moments)
+        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(path)))
+        try:
+            with os.fdopen(fd, "wb") as f:
+                np.savez(f, **data)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            kw = {k: int(z[k]) for k in cls._SCALARS}
+            return cls(sum=z["sum"], moments=z["moments"], **kw)
+
+
 def make_params(nx, ny, spp, max_depth=50, seed=95, shard_band=0, shard_count=1, shard_id=0, spp_slice=0, flags=0):
     p = RtParams()
     p.flags = flags
@@ -834,6 +893,80 @@ class Renderer:
         rc = self._lib.rt_accum_merge(self._ctx, C.byref(st))
         if rc != 0:
             self._raise("rt_accum_merge", rc)
+
+    def accum_track_halves(self):
+        """rt_accum_track_halves: the open accumulation also keeps the even and the odd samples of every pixel apart (56 B per pixel); right
+        after accum_begin, before the first add.  Everything else the accumulation returns stays bit for bit."""
+        rc = self._lib.rt_accum_track_halves(self._ctx)
+        if rc != 0:
+            self._raise("rt_accum_track_halves", rc)
+
+    def accum_half(self, h, want_sem=False):
+        """rt_accum_read_halves: (img [rows, nx, 3] f32 of half h — 0: the samples with an even absolute index —, sem [rows, nx] f32 or None),
+        laid out as accum_read's."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        img = np.zeros((rows, nx, 3), dtype=np.float32)
+        sem = np.zeros((rows, nx), dtype=np.float32) if want_sem else None
+        rc = self._lib.rt_accum_read_halves(self._ctx, int(h), img.ctypes.data_as(C.POINTER(C.c_float)),
+                                            sem.ctypes.data_as(C.POINTER(C.c_float)) if want_sem else None)
+        if rc != 0:
+            self._raise("rt_accum_read_halves", rc)
+        return img, sem
+
+    def accum_denoise_halves(self, radius=5, patch=1, strength=None, want_rgb8=False, want_err=False):
+        """rt_accum_denoise_halves: each half filtered with the weights of the other, the two combined; the accumulation must track halves.
+        Returns (img [rows, nx, 3] f32, rgb8 or None, err [rows, nx] f32 or None — the per-pixel residual variance e_p —, RtResidual).
+        RtResidual.residual_rms is the variance half of the filtered frame's error: a lower bound, blur is not in it.  strength None:
+        RT_DENOISE_HALVES_DEFAULT_STRENGTH."""
+        img, rgb8, err, ptrs = self._accum_outputs(want_rgb8, want_err)
+        res = RtResidual()
+        dn = RtDenoise(int(radius), int(patch), float(_ffi.DENOISE_HALVES_DEFAULT_STRENGTH if strength is None else strength), 0)
+        rc = self._lib.rt_accum_denoise_halves(self._ctx, C.byref(dn), ptrs[0], ptrs[1], ptrs[2], C.byref(res))
+        if rc != 0:
+            self._raise("rt_accum_denoise_halves", rc)
+        return img, rgb8, err, res
+
+    def accum_export_halves(self):
+        """rt_accum_export_halves: the half buffers of the open accumulation as an AccumHalves.  Read, not changed."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        halves = AccumHalves(nx, rows)
+        hs = halves.as_struct()
+        rc = self._lib.rt_accum_export_halves(self._ctx, C.byref(hs))
+        if rc != 0:
+            self._raise("rt_accum_export_halves", rc)
+        halves.first_sample, halves.done, halves.frame_id = hs.first_sample, hs.done, hs.frame_id
+        return halves
+
+    def accum_import_halves(self, halves):
+        """rt_accum_import_halves: puts an AccumHalves into the accumulation just begun — fresh, or right after accum_import of the state it
+        belongs to — and turns tracking on."""
+        hs = halves.as_struct()
+        rc = self._lib.rt_accum_import_halves(self._ctx, C.byref(hs))
+        if rc != 0:
+            self._raise("rt_accum_import_halves", rc)
+
+    def render_to_residual(self, camera, params, target, step, radius=5, patch=1, strength=None, want_rgb8=False, want_err=False):
+        """Renders until the DENOISED frame is clean: an accumulation that tracks halves gets adds of `step` samples (the first one at least
+        4) until RtResidual.residual_noise <= target or params.spp, the maximum, are issued; one cross filter per step, a host loop.
+        Returns what accum_denoise_halves returns plus the samples per pixel done.  residual_noise is a lower bound of the filtered
+        frame's relative error (its variance half), so the target bounds the noise that is left, not the blur."""
+        if step <= 0 or not target >= 0.0 or params.spp < 4:
+            raise ValueError("render_to_residual: step must be > 0, target >= 0 and params.spp, the maximum, >= 4")
+        p = RtParams.from_buffer_copy(params)
+        p.spp = min(max(int(step), 4), params.spp)
+        self.accum_begin(camera, p, 0)
+        try:
+            self.accum_track_halves()
+            done = 0
+            while True:
+                n = min(max(int(step), 4 - done), params.spp - done)
+                self.accum_add(n)
+                done += n
+                out = self.accum_denoise_halves(radius, patch, strength, want_rgb8, want_err)
+                if done >= params.spp or out[3].residual_noise <= target or out[0].size == 0:
+                    return out + (done,)
+        finally:
+            self.accum_end()
 
     def set_progress(self, fn):
         """fn(spp_done, spp_total, rgb8[rows, nx, 3]) after every slice but the last of a following render()

@@ -8,6 +8,7 @@
 #include "rt_adaptive.h"
 #include "rt_accum_state.h"
 #include "rt_accum_state_kernels.h"
+#include "rt_halves.h"
 #include "rt_bvh.h"
 #include "rt_grid.h"
 #include "rt_pool.h"
@@ -133,6 +134,8 @@ struct RtCtx {
         uint32_t nx = 0, rows = 0, npix = 0, tiles_per_row = 0, tile_pixels = 0;
         bool adaptive = false; // an adaptive add has happened: accum_cnt / accum_flag hold n_p and the converged flags, `done` is the n_p of the active pixels
         bool channels = false; // rt_accum_track_channels: accum_chm holds the channel moments and every add keeps them
+        bool halves = false;   // rt_accum_track_halves / rt_accum_import_halves: accum_halves holds the half sums and moments and every add keeps them
+        bool added = false;    // an add of either kind or a merge has happened since rt_accum_begin (rt_accum_import_halves comes before)
     } accum;
     DevBuf accum_sum, accum_mom, accum_sem, accum_partials; // (accum_sem: staging of out_sem; accum_partials: one f64 pair per workgroup + the 3 frame figures)
     double* h_noise = nullptr;   // page-locked: mean_luminance, rms_sem, noise as k_noise_final wrote them
@@ -143,6 +146,12 @@ struct RtCtx {
     // rt_accum_track_channels (rt_channels.h): three planes of f64 x 2 channel moments, 48 B per pixel, each in the order of accum_sum;
     // accum_chsem: staging of out_sem_rgb; dn_cv: the inputs of rt_accum_denoise_channels, (c, v) x 3 per pixel in image order, 24 B
     DevBuf accum_chm, accum_chsem, dn_cv;
+    // rt_accum_track_halves (rt_halves.h): per half a plane of f32 x 3 sums and one of f64 x 2 moments, 56 B per pixel, each in the order of
+    // accum_sum (rt_halves_plan.h: halves_layout); halves_stage: the same planes in image order (a state of halves) and the staging of
+    // rt_accum_read_halves; dn_halves: what rt_accum_denoise_halves needs beside dn_c, dn_yv and dn_out (the second half's inputs and filter
+    // output, out, e: 48 B per pixel, the partial sums and the three frame figures)
+    DevBuf accum_halves, halves_stage, dn_halves;
+    double* h_resid = nullptr;   // page-locked: mean_luminance, residual_rms, residual_noise as k_halves_final wrote them
     DevBuf accum_stage;          // rt_accum_export / _import / _merge: the planes of a state in image order (rt_accum_state.h: accum_state_staging), at most 81 B per pixel
     DevBuf dn_c, dn_yv, dn_out;  // rt_accum_denoise: the filter's inputs (c 12 B, (y, v) 8 B) and its output (12 B) per pixel, in image order
     // Host-side timeline of the last trace_samples and what its caller enqueued behind it (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
@@ -207,6 +216,13 @@ int ensure(RtCtx* ctx, DevBuf& b, size_t bytes, bool plain = false) {
 void free_buf(DevBuf& b) {
     if (b.p && !b.arena) (void)hipFree(b.p);
     b = DevBuf{};
+}
+
+// The four planes of halves in `b` (rt_halves_plan.h: halves_layout over npix pixels)
+HalfPlanes half_planes(const DevBuf& b, uint32_t npix) {
+    const HalvesLayout l = halves_layout(npix);
+    char* base = (char*)b.p;
+    return HalfPlanes{{(float*)(base + l.sum[0]), (float*)(base + l.sum[1])}, {(double2*)(base + l.moments[0]), (double2*)(base + l.moments[1])}};
 }
 
 void free_scene(RtCtx* ctx) { // (the region stays: the next upload carves it again)
@@ -730,6 +746,8 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->accum_sum), free_buf(ctx->accum_mom), free_buf(ctx->accum_sem), free_buf(ctx->accum_partials);
     free_buf(ctx->accum_cnt), free_buf(ctx->accum_flag), free_buf(ctx->accum_info), free_buf(ctx->accum_cnt_out);
     free_buf(ctx->accum_stage);
+    free_buf(ctx->accum_halves), free_buf(ctx->halves_stage), free_buf(ctx->dn_halves);
+    if (ctx->h_resid) (void)hipHostFree(ctx->h_resid);
     if (ctx->h_info) (void)hipHostFree(ctx->h_info);
     free_buf(ctx->dn_c), free_buf(ctx->dn_yv), free_buf(ctx->dn_out);
     if (ctx->h_noise) (void)hipHostFree(ctx->h_noise);
@@ -871,6 +889,9 @@ struct SampleSink {
     uint32_t* cnt = nullptr;
     // rt_accum_track_channels (rt_channels.h): the channel moments the resolve keeps beside `mom`
     double2* chm = nullptr;
+    // rt_accum_track_halves (rt_halves.h): the half sums and moments, kept by a kernel of their own in front of the resolve
+    bool halves = false;
+    HalfPlanes hp{};
 };
 // What trace_samples enqueued, for the finalize, the copies and the statistics of its caller.
 struct Traced {
@@ -1084,6 +1105,11 @@ static int enqueue_slice(RtCtx* ctx, Frame& f, const WorkView& wv, uint32_t sl) 
 static int resolve_and_preview(RtCtx* ctx, const Frame& f, const SampleSink& sink, const float* rad, uint32_t sc, uint32_t done, uint32_t rows) {
     const hipStream_t st = f.st;
     const uint32_t npix = f.npix, spp = f.prm->spp, nx = f.prm->nx;
+    if (sink.halves) { // the slice's first sample has the absolute index first_sample + (done - sc)
+        const uint32_t i0 = sink.first_sample + (done - sc);
+        if (sink.converged) hipLaunchKernelGGL(k_resolve_halves<true>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, sink.hp, sink.converged, npix, i0, sc);
+        else hipLaunchKernelGGL(k_resolve_halves<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, sink.hp, (const uint8_t*)nullptr, npix, i0, sc);
+    }
     if (sink.chm && sink.converged)
         hipLaunchKernelGGL(k_resolve_moments_channels<true>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.chm, sink.converged, sink.cnt, npix, sc);
     else if (sink.chm)
@@ -1363,10 +1389,11 @@ static int accum_add(RtCtx* ctx, uint32_t n_samples, RtStats* stats, bool figure
     Traced tr;
     SampleSink sink{(float*)ctx->accum_sum.p, (double2*)ctx->accum_mom.p, a.first + a.done};
     if (a.channels) sink.chm = (double2*)ctx->accum_chm.p;
+    if (a.halves) sink.halves = true, sink.hp = half_planes(ctx->accum_halves, a.npix);
     const int rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr);
     if (rc) return rc;
     if (tr.npix == 0u) {
-        a.done += n_samples;
+        a.done += n_samples, a.added = true;
         if (stats) std::memset(stats, 0, sizeof(*stats));
         return RT_OK;
     }
@@ -1374,7 +1401,7 @@ static int accum_add(RtCtx* ctx, uint32_t n_samples, RtStats* stats, bool figure
         a.open = false; // (cannot happen: everything the order hangs on ends the accumulation)
         return fail(ctx, RT_ERR_STATE, "rt_accum_add: the pixel order changed since rt_accum_begin (internal)");
     }
-    a.done += n_samples;
+    a.done += n_samples, a.added = true;
     if (figures)
         if (const int rn = enqueue_noise(ctx, tr.st)) return rn;
     RT_HIP(ctx, hipEventRecord(ctx->ev_end, tr.st));
@@ -1481,7 +1508,7 @@ static int accum_add_adaptive(RtCtx* ctx, uint32_t n_samples, const RtAdaptive* 
     if ((uint64_t)a.first + a.done + n_samples > 0xFFFFFFFFull)
         return fail(ctx, RT_ERR_INVALID, "rt_accum_add_adaptive: first_sample + the samples issued must stay below 2^32, as RtParams.spp does");
     if (a.npix == 0u) { // a shard without rows
-        a.adaptive = true, a.done += n_samples;
+        a.adaptive = true, a.done += n_samples, a.added = true;
         if (stats) std::memset(stats, 0, sizeof(*stats));
         return RT_OK;
     }
@@ -1504,12 +1531,13 @@ static int accum_add_adaptive(RtCtx* ctx, uint32_t n_samples, const RtAdaptive* 
     SampleSink sink{(float*)ctx->accum_sum.p, (double2*)ctx->accum_mom.p, a.first + a.done};
     sink.converged = (const uint8_t*)ctx->accum_flag.p, sink.cnt = (uint32_t*)ctx->accum_cnt.p;
     if (a.channels) sink.chm = (double2*)ctx->accum_chm.p;
+    if (a.halves) sink.halves = true, sink.hp = half_planes(ctx->accum_halves, a.npix);
     if ((rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr))) return rc;
     if (tr.npix != a.npix || tr.tiles_per_row != a.tiles_per_row || tr.tile_pixels != a.tile_pixels) {
         a.open = false; // (cannot happen: everything the order hangs on ends the accumulation)
         return fail(ctx, RT_ERR_STATE, "rt_accum_add_adaptive: the pixel order changed since rt_accum_begin (internal)");
     }
-    a.done += n_samples;
+    a.done += n_samples, a.added = true;
     if (figures && (rc = enqueue_noise(ctx, tr.st))) return rc;
     RT_HIP(ctx, hipEventRecord(ctx->ev_end, tr.st));
     RT_HIP(ctx, hipGetLastError());
@@ -1597,8 +1625,8 @@ int rt_debug_accum_set_moments(RtCtx* ctx, uint32_t pixel, double s1, double s2)
 
 // ---- denoising (rtow_mi355x.h "Denoising", csrc/rt_denoise.h) -----------------------------------------------------------------------
 // The parameters of a call: `dn` checked, or the defaults for NULL.
-static int denoise_params(RtCtx* ctx, const RtDenoise* dn, RtDenoise& d, const char* who) {
-    d = RtDenoise{5u, 1u, RT_DENOISE_DEFAULT_STRENGTH, 0u};
+static int denoise_params(RtCtx* ctx, const RtDenoise* dn, RtDenoise& d, const char* who, float default_strength = RT_DENOISE_DEFAULT_STRENGTH) {
+    d = RtDenoise{5u, 1u, default_strength, 0u};
     if (!dn) return RT_OK;
     if (dn->radius == 0u || dn->radius > RT_DENOISE_MAX_RADIUS) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": radius must be 1 .. RT_DENOISE_MAX_RADIUS");
     if (dn->patch > RT_DENOISE_MAX_PATCH) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": patch must be 0 .. RT_DENOISE_MAX_PATCH");
@@ -1879,6 +1907,7 @@ int rt_accum_import(RtCtx* ctx, const RtAccumState* st) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
     if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_import: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks halves already (import the state first, then rt_accum_import_halves)");
     if (a.done != 0u || a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_import: samples were added already (call it right after rt_accum_begin)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import: ") + why);
     if (const char* why = state_mismatch(a, *st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import: ") + why);
@@ -1921,6 +1950,7 @@ int rt_accum_merge(RtCtx* ctx, const RtAccumState* st) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
     if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_merge: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks halves: a merge of halves is not covered (rtow_mi355x.h)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_merge: ") + why);
     if (a.adaptive || (st->planes & RT_ACCUM_STATE_COUNTS))
         return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: an adaptive accumulation or state: windows of pixels with different sample counts are not contiguous");
@@ -1947,7 +1977,173 @@ int rt_accum_merge(RtCtx* ctx, const RtAccumState* st) {
         RT_HIP(ctx, hipGetLastError());
         RT_HIP(ctx, hipStreamSynchronize(s_));
     }
-    a.done += st->done;
+    a.done += st->done, a.added = true;
+    return RT_OK;
+}
+
+// ---- half buffers (rtow_mi355x.h "Half buffers", csrc/rt_halves.h, csrc/rt_halves_plan.h) --------------------------------------------------
+int rt_accum_halves_check(const RtAccumHalves* hs) { return accum_halves_invalid(hs) ? RT_ERR_INVALID : RT_OK; }
+
+// The accumulation's buffer of halves for npix pixels (kept for the next accumulation).
+static int ensure_halves(RtCtx* ctx, uint32_t npix) { return ensure(ctx, ctx->accum_halves, halves_layout(npix).total); }
+
+int rt_accum_track_halves(RtCtx* ctx) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_track_halves: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (a.halves) return RT_OK;
+    if (a.done != 0u || a.adaptive || a.added)
+        return fail(ctx, RT_ERR_STATE, "rt_accum_track_halves: the accumulation holds samples already (call it right after rt_accum_begin; after rt_accum_import "
+                                       "the halves come through rt_accum_import_halves)");
+    if (a.npix) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        if (const int rc = ensure_halves(ctx, a.npix)) return rc;
+        RT_HIP(ctx, hipMemsetAsync(ctx->accum_halves.p, 0, halves_layout(a.npix).total, ctx->stream));
+    }
+    a.halves = true;
+    return RT_OK;
+}
+
+int rt_accum_read_halves(RtCtx* ctx, uint32_t h, float* out_rgb_f32, float* out_sem) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_read_halves: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (!a.halves) return fail(ctx, RT_ERR_STATE, "rt_accum_read_halves: the accumulation does not track halves (rt_accum_track_halves)");
+    if (h > 1u) return fail(ctx, RT_ERR_INVALID, "rt_accum_read_halves: h must be 0 or 1");
+    if (a.npix == 0u || (!out_rgb_f32 && !out_sem)) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const uint32_t npix = a.npix, grid = (npix + 255u) / 256u;
+    if (const int rc = ensure(ctx, ctx->halves_stage, halves_layout(npix).total)) return rc;
+    float* d_rgb = (float*)ctx->halves_stage.p; // (staging: 12 B + 4 B of the 56 B per pixel a state of halves takes there)
+    float* d_sem = d_rgb + 3 * (size_t)npix;
+    const HalfPlanes hp = half_planes(ctx->accum_halves, npix);
+    if (a.adaptive)
+        hipLaunchKernelGGL(k_halves_read<true>, dim3(grid), dim3(256), 0, st, hp, (const uint32_t*)ctx->accum_cnt.p, h, out_rgb_f32 ? d_rgb : (float*)nullptr,
+                           out_sem ? d_sem : (float*)nullptr, a.nx, a.rows, a.first, 0u, a.tiles_per_row, a.tile_pixels);
+    else
+        hipLaunchKernelGGL(k_halves_read<false>, dim3(grid), dim3(256), 0, st, hp, (const uint32_t*)nullptr, h, out_rgb_f32 ? d_rgb : (float*)nullptr,
+                           out_sem ? d_sem : (float*)nullptr, a.nx, a.rows, a.first, a.done, a.tiles_per_row, a.tile_pixels);
+    RT_HIP(ctx, hipGetLastError());
+    if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, d_rgb, (size_t)npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (out_sem) RT_HIP(ctx, hipMemcpyAsync(out_sem, d_sem, (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+int rt_accum_denoise_halves(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8, float* out_err, RtResidual* res) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_halves: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (!a.halves) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_halves: the accumulation does not track halves (rt_accum_track_halves)");
+    RtDenoise d;
+    int rc = denoise_params(ctx, dn, d, "rt_accum_denoise_halves", RT_DENOISE_HALVES_DEFAULT_STRENGTH);
+    if (rc) return rc;
+    if (a.prm.shard_count > 1u)
+        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_denoise_halves: a sharded frame (shard_count > 1): the local rows of a shard are not neighbours in the image");
+    if (a.done < 4u) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_halves: fewer than 4 samples accumulated: a half has no variance yet");
+    if (res) std::memset(res, 0, sizeof(*res));
+    if (a.npix == 0u) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const uint32_t npix = a.npix, nb = (npix + 255u) / 256u;
+    const size_t n = (size_t)npix * 3;
+    if ((rc = ensure_denoise(ctx, npix))) return rc;
+    // dn_halves: the partial sums and the figures, (y, v)_1, then c_1, f_1, out (12 B each) and e (4 B) per pixel
+    const size_t part_bytes = ((size_t)nb * sizeof(double2) + 3 * sizeof(double) + 15u) & ~(size_t)15u;
+    if ((rc = ensure(ctx, ctx->dn_halves, part_bytes + (size_t)npix * (sizeof(float2) + 10 * sizeof(float))))) return rc;
+    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
+    if (!ctx->h_resid) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_resid, 3 * sizeof(double), hipHostMallocDefault));
+    double2* partials = (double2*)ctx->dn_halves.p;
+    double* figures = (double*)(partials + nb);
+    float2* yv1 = (float2*)((char*)ctx->dn_halves.p + part_bytes);
+    float* c1 = (float*)(yv1 + npix);
+    float *f1 = c1 + n, *out = f1 + n, *err = out + n;
+    float *c0 = (float*)ctx->dn_c.p, *f0 = (float*)ctx->dn_out.p;
+    float2* yv0 = (float2*)ctx->dn_yv.p;
+    const HalfPlanes hp = half_planes(ctx->accum_halves, npix);
+    const uint32_t* cnt = a.adaptive ? (const uint32_t*)ctx->accum_cnt.p : (const uint32_t*)nullptr;
+    if (a.adaptive)
+        hipLaunchKernelGGL(k_denoise_inputs_halves<true>, dim3(nb), dim3(256), 0, st, hp, cnt, c0, c1, yv0, yv1, a.nx, a.rows, a.first, 0u, a.tiles_per_row, a.tile_pixels);
+    else
+        hipLaunchKernelGGL(k_denoise_inputs_halves<false>, dim3(nb), dim3(256), 0, st, hp, cnt, c0, c1, yv0, yv1, a.nx, a.rows, a.first, a.done, a.tiles_per_row, a.tile_pixels);
+    launch_denoise(st, c0, yv1, f0, a.nx, a.rows, d); // each half by the other's guide
+    launch_denoise(st, c1, yv0, f1, a.nx, a.rows, d);
+    if (a.adaptive)
+        hipLaunchKernelGGL(k_halves_combine<true>, dim3(nb), dim3(256), 0, st, (const float*)f0, (const float*)f1, cnt, out, err, partials, a.nx, a.rows, a.first, 0u,
+                           a.tiles_per_row, a.tile_pixels);
+    else
+        hipLaunchKernelGGL(k_halves_combine<false>, dim3(nb), dim3(256), 0, st, (const float*)f0, (const float*)f1, cnt, out, err, partials, a.nx, a.rows, a.first, a.done,
+                           a.tiles_per_row, a.tile_pixels);
+    hipLaunchKernelGGL(k_halves_final, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, npix, figures);
+    if (out_rgb8) // k_finalize's quantisation and flip of the filtered image, as in rt_accum_denoise
+        hipLaunchKernelGGL(k_finalize, dim3(nb), dim3(256), 0, st, (const float*)out, (float*)nullptr, (uint8_t*)ctx->out_u8.p, a.nx, a.rows, 1u, 0u, 0u);
+    RT_HIP(ctx, hipGetLastError());
+    if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, out, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (out_rgb8) RT_HIP(ctx, hipMemcpyAsync(out_rgb8, ctx->out_u8.p, n, hipMemcpyDeviceToHost, st));
+    if (out_err) RT_HIP(ctx, hipMemcpyAsync(out_err, err, (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipMemcpyAsync(ctx->h_resid, figures, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    if (res) res->mean_luminance = ctx->h_resid[0], res->residual_rms = ctx->h_resid[1], res->residual_noise = ctx->h_resid[2];
+    return RT_OK;
+}
+
+int rt_accum_export_halves(RtCtx* ctx, RtAccumHalves* hs) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!hs) return fail(ctx, RT_ERR_INVALID, "rt_accum_export_halves: the RtAccumHalves is NULL");
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_export_halves: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (!a.halves) return fail(ctx, RT_ERR_STATE, "rt_accum_export_halves: the accumulation does not track halves (rt_accum_track_halves)");
+    const uint32_t npix = a.npix;
+    if (npix && (hs->sum[0] || hs->sum[1] || hs->moments[0] || hs->moments[1])) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        const hipStream_t s_ = ctx->stream;
+        if (const int rc = ensure(ctx, ctx->halves_stage, halves_layout(npix).total)) return rc;
+        const HalfPlanes s = half_planes(ctx->halves_stage, npix);
+        hipLaunchKernelGGL(k_halves_export, dim3((npix + 255u) / 256u), dim3(256), 0, s_, half_planes(ctx->accum_halves, npix), s, a.nx, a.rows, a.tiles_per_row,
+                           a.tile_pixels);
+        RT_HIP(ctx, hipGetLastError());
+        for (int h = 0; h < 2; ++h) {
+            if (hs->sum[h]) RT_HIP(ctx, hipMemcpyAsync(hs->sum[h], s.sum[h], (size_t)npix * RT_HALVES_SUM_BYTES, hipMemcpyDeviceToHost, s_));
+            if (hs->moments[h]) RT_HIP(ctx, hipMemcpyAsync(hs->moments[h], s.mom[h], (size_t)npix * RT_HALVES_MOMENT_BYTES, hipMemcpyDeviceToHost, s_));
+        }
+        RT_HIP(ctx, hipStreamSynchronize(s_));
+    }
+    hs->nx = a.nx, hs->rows = a.rows, hs->first_sample = a.first, hs->done = a.done;
+    hs->reserved[0] = hs->reserved[1] = 0u;
+    hs->frame_id = accum_frame_id(a.cam, a.prm);
+    return RT_OK;
+}
+
+int rt_accum_import_halves(RtCtx* ctx, const RtAccumHalves* hs) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_import_halves: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (a.added) return fail(ctx, RT_ERR_STATE, "rt_accum_import_halves: samples were added since rt_accum_begin (call it right after rt_accum_begin or rt_accum_import)");
+    if (const char* why = accum_halves_invalid(hs)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import_halves: ") + why);
+    if (hs->nx != a.nx || hs->rows != a.rows) return fail(ctx, RT_ERR_INVALID, "rt_accum_import_halves: nx and rows of the halves are not the accumulation's");
+    if (hs->frame_id != accum_frame_id(a.cam, a.prm))
+        return fail(ctx, RT_ERR_INVALID, "rt_accum_import_halves: frame_id of the halves is not rt_accum_frame_id of the accumulation's camera and params");
+    if (hs->first_sample != a.first || hs->done != a.done)
+        return fail(ctx, RT_ERR_INVALID, "rt_accum_import_halves: first_sample and done of the halves are not the accumulation's (rt_accum_import comes first)");
+    const uint32_t npix = a.npix;
+    if (npix) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        const hipStream_t s_ = ctx->stream;
+        int rc;
+        if ((rc = ensure_halves(ctx, npix))) return rc; // every allocation first: a failure cannot leave the accumulation half imported
+        if ((rc = ensure(ctx, ctx->halves_stage, halves_layout(npix).total))) return rc;
+        const HalfPlanes s = half_planes(ctx->halves_stage, npix);
+        for (int h = 0; h < 2; ++h) {
+            RT_HIP(ctx, hipMemcpyAsync(s.sum[h], hs->sum[h], (size_t)npix * RT_HALVES_SUM_BYTES, hipMemcpyHostToDevice, s_));
+            RT_HIP(ctx, hipMemcpyAsync(s.mom[h], hs->moments[h], (size_t)npix * RT_HALVES_MOMENT_BYTES, hipMemcpyHostToDevice, s_));
+        }
+        hipLaunchKernelGGL(k_halves_import, dim3((npix + 255u) / 256u), dim3(256), 0, s_, half_planes(ctx->accum_halves, npix), s, a.nx, a.rows, a.tiles_per_row,
+                           a.tile_pixels);
+        RT_HIP(ctx, hipGetLastError());
+        RT_HIP(ctx, hipStreamSynchronize(s_)); // (the caller's arrays are free again)
+    }
+    a.halves = true;
     return RT_OK;
 }
 

@@ -59,9 +59,15 @@ def main(argv=None):
     ap.add_argument("--denoise-patch", type=int, default=1, metavar="F", help="patch radius, 0..%d" % _ffi.DENOISE_MAX_PATCH)
     ap.add_argument("--denoise-strength", type=float, default=None, metavar="K",
                     help="how many standard errors two pixels may differ and still be averaged (default %g)" % _ffi.DENOISE_DEFAULT_STRENGTH)
-    ap.add_argument("--denoise-guide", choices=("luminance", "channels"), default="luminance",
-                    help="what the filter measures distance on: the mean luminance and its variance (rt_accum_denoise), or the three channels and "
-                         "theirs (rt_accum_denoise_channels: 48 B per pixel more, keeps edges between colours of equal luminance)")
+    ap.add_argument("--denoise-guide", choices=("luminance", "channels", "halves"), default="luminance",
+                    help="what the filter measures distance on: the mean luminance and its variance (rt_accum_denoise), the three channels and "
+                         "theirs (rt_accum_denoise_channels: 48 B per pixel more, keeps edges between colours of equal luminance), or, per half "
+                         "of the samples, the luminance of the OTHER half (rt_accum_denoise_halves: 56 B per pixel more, default strength %g, "
+                         "reports the variance left in the filtered frame)" % _ffi.DENOISE_HALVES_DEFAULT_STRENGTH)
+    ap.add_argument("--residual-target", type=float, default=None, metavar="X",
+                    help="render until the DENOISED frame is clean: samples in steps of --spp-step, the cross filter of --denoise-guide halves "
+                         "after each, until its residual_noise <= X or --spp are done.  The figure is the variance half of the filtered "
+                         "frame's relative error, a lower bound: blur is not in it")
     ap.add_argument("--checkpoint", default=None, metavar="FILE",
                     help="drive the samples in steps of --spp-step and write the accumulation's state (AccumState, an .npz) to FILE after every "
                          "--checkpoint-every-th step and at the end, each time through a temporary file: a killed render leaves a whole checkpoint")
@@ -102,6 +108,17 @@ def main(argv=None):
     if a.light_sampling:
         rend.set_lights(scene.lights)  # (a moving scene refuses it: RT_ERR_UNSUPPORTED)
     flags = _ffi.FLAG_RUSSIAN_ROULETTE if a.russian_roulette else 0
+    halves = a.residual_target is not None or (a.denoise and a.denoise_guide == "halves")
+    if halves:
+        if a.checkpoint or a.resume or a.merge:
+            ap.error("--denoise-guide halves and --residual-target do not combine with --checkpoint, --resume or --merge")
+        if a.first_sample is not None or a.adaptive_tolerance is not None or a.noise_target is not None or a.preview_every:
+            ap.error("--denoise-guide halves and --residual-target do not combine with --first-sample, --adaptive-tolerance, --noise-target or --preview-every")
+        if a.denoise_guide not in ("luminance", "halves") or (a.residual_target is not None and not a.residual_target >= 0.0):
+            ap.error("--residual-target needs --denoise-guide halves (or none) and a value >= 0")
+        if a.spp < 4:
+            ap.error("the cross filter needs --spp >= 4: two samples per half")
+        return render_halves(a, rend, scene, flags, file_name, t0)
     if a.checkpoint or a.resume or a.merge or a.first_sample is not None:
         if a.preview_every:
             ap.error("--checkpoint, --resume, --first-sample and --merge do not combine with --preview-every")
@@ -239,6 +256,26 @@ def _denoised(a, rend):
     if a.denoise_guide == "channels":
         return rend.accum_denoise_channels(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
     return rend.accum_denoise(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
+
+
+def render_halves(a, rend, scene, flags, file_name, t0):
+    """--denoise --denoise-guide halves: one add of --spp samples and the cross filter; --residual-target: Renderer.render_to_residual."""
+    params = make_params(a.nx, a.ny, a.spp, max_depth=a.max_depth, seed=a.seed, flags=flags)
+    if a.residual_target is not None:
+        _, rgb8, _, res, done = rend.render_to_residual(scene.camera, params, a.residual_target, a.spp_step, a.denoise_radius, a.denoise_patch,
+                                                        a.denoise_strength, want_rgb8=True)
+    else:
+        rend.accum_begin(scene.camera, params)
+        rend.accum_track_halves()
+        rend.accum_add(a.spp)
+        _, rgb8, _, res = rend.accum_denoise_halves(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)
+        rend.accum_end()
+        done = a.spp
+    print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
+    save_png(file_name, rgb8)
+    print(f"{file_name}: {a.nx}x{a.ny}, {done} of at most {a.spp} spp, cross-filtered, residual noise {res.residual_noise:.4g} (a lower bound of "
+          f"the filtered frame's relative error)" + (f", target {a.residual_target:g}" if a.residual_target is not None else ""), file=sys.stderr)
+    return 0
 
 
 def render_denoised(a, rend, scene, flags, file_name, t0):
