@@ -5,9 +5,9 @@
 //                                 DECIDE false: only the sums (rt_accum_read_counts after the samples were added)
 //   k_adaptive_info             : one workgroup over the partial sums
 //   k_gen_primary_active<LENS>  : k_gen_primary for the pixels still active: the depth-0 queue holds their rays only, compacted
-//   k_resolve_moments_active    : k_resolve_moments for the pixels still active; n_p += s_count
-//   k_finalize_counts, k_sem_counts, k_noise_partials_counts, k_noise_final_counts, k_denoise_inputs_counts:
-//                                 the readers of an accumulation with the pixel's own n_p in the place of the one n
+// What an adaptive accumulation shares with a uniform one is one kernel with a template flag, beside its uniform form:
+// k_resolve_moments<true> (the active pixels; n_p += s_count) and the readers k_finalize<true>, k_sem<true>, k_noise_partials<true>,
+// k_noise_final<true> (rt_kernels.h) and k_denoise_inputs<true> (rt_denoise.h), with the pixel's own n_p in the place of the one n.
 //
 // Nothing downstream of depth 0's materialised queue changes: a ray's identity is the slot in its record (qa.w), its key and its
 // radiance slot follow from the slot (path_key_of_slot, rad_store), and every kernel reads `counts[shard]` rays from the front of a
@@ -26,12 +26,7 @@ __global__ __launch_bounds__(256) void k_adaptive_begin(uint32_t* __restrict__ c
     flag[p] = 0u;
 }
 
-// Integer partial sums of one workgroup, and of the frame (k_adaptive_info writes the frame's as an RtAdaptiveInfo: the same layout).
-struct AdaptiveSums {
-    unsigned long long n_active, n_samples;
-    uint32_t spp_min, spp_max;
-};
-static_assert(sizeof(AdaptiveSums) == sizeof(RtAdaptiveInfo) && sizeof(AdaptiveSums) == 24u, "AdaptiveSums is RtAdaptiveInfo");
+// The integer sums are AdaptiveSums (rt_kernels.h, beside k_noise_final, which reads the frame's spp_min).
 // The fixed tree of block_sum_256 over integers: lanes by __shfl_down, the four waves through LDS in wave order.  (Integer sums do not
 // depend on their order; the tree spares the atomics.)  Every thread of the workgroup calls it; thread 0 holds the result.
 __device__ __forceinline__ AdaptiveSums adaptive_block_sums(AdaptiveSums s, AdaptiveSums* part) {
@@ -126,111 +121,6 @@ __global__ __launch_bounds__(256) void k_gen_primary_active(GenParams gp, Queue 
     q.a[RT_QSTRIDE * pos] = make_float4(o.x, o.y, o.z, __uint_as_float(idx));
     q.b[RT_QSTRIDE * pos] = make_float4(d.x, d.y, d.z, 1.0f);
     q.c[pos] = make_float2(1.0f, 1.0f);
-}
-
-// k_resolve_moments for the active pixels: the same loads, loop order and sums, and n_p += s_count.  A converged pixel touches neither
-// its radiance slots (nothing wrote them) nor its sums.
-__global__ __launch_bounds__(256) void k_resolve_moments_active(const float* __restrict__ rad, float* __restrict__ acc, double2* __restrict__ mom,
-                                                                const uint8_t* __restrict__ flag, uint32_t* __restrict__ cnt, uint32_t npix,
-                                                                uint32_t s_count) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= npix) return;
-    if (flag[p] != 0u) return;
-    float r = acc[3 * (size_t)p], g = acc[3 * (size_t)p + 1], b = acc[3 * (size_t)p + 2];
-    double2 m = mom[p];
-    for (uint32_t s = 0; s < s_count; ++s) {
-        const float* src = rad + RT_RAD_FLOATS * ((size_t)s * npix + p);
-        const float sx = src[0], sy = src[1], sz = src[2];
-        r += sx;
-        g += sy;
-        b += sz;
-        const double y = sample_luminance(sx, sy, sz);
-        m.x += y;
-        m.y += y * y;
-    }
-    acc[3 * (size_t)p] = r, acc[3 * (size_t)p + 1] = g, acc[3 * (size_t)p + 2] = b;
-    mom[p] = m;
-    cnt[p] += s_count;
-}
-
-// ---- the readers, with n_p per pixel ----------------------------------------------------------------------------------------------
-// k_finalize with sum / (float)n_p (n_p 0, before the first sample: / 1, the sums are zeros).
-__global__ __launch_bounds__(256) void k_finalize_counts(const float* __restrict__ acc, const uint32_t* __restrict__ cnt, float* __restrict__ out_f32,
-                                                         uint8_t* __restrict__ out_u8, uint32_t nx, uint32_t rows, uint32_t tiles_per_row,
-                                                         uint32_t tile_pixels) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= nx * rows) return;
-    const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx);
-    const uint32_t n = cnt[ap];
-    const float fs = (float)(n ? n : 1u);
-    float c[3] = {acc[3 * ap] / fs, acc[3 * ap + 1] / fs, acc[3 * ap + 2] / fs};
-    if (out_f32) {
-        out_f32[3 * (size_t)p] = c[0], out_f32[3 * (size_t)p + 1] = c[1], out_f32[3 * (size_t)p + 2] = c[2];
-    }
-    if (out_u8) {
-        const uint32_t lj = p / nx, i = p - lj * nx;
-        const size_t dst = ((size_t)(rows - 1u - lj) * nx + i) * 3u;
-        for (int k = 0; k < 3; ++k) {
-            float g = sqrtf(c[k]) * 255.99f;
-            uint32_t u = (g == g && g > 0.0f) ? (g >= 255.0f ? 255u : (uint32_t)g) : 0u;
-            out_u8[dst + k] = (uint8_t)u;
-        }
-    }
-}
-// out_sem and, on request, the sample counts, both in output pixel order.
-__global__ __launch_bounds__(256) void k_sem_counts(const double2* __restrict__ mom, const uint32_t* __restrict__ cnt, float* __restrict__ out_sem,
-                                                    uint32_t* __restrict__ out_cnt, uint32_t nx, uint32_t rows, uint32_t tiles_per_row,
-                                                    uint32_t tile_pixels) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= nx * rows) return;
-    const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx);
-    const uint32_t n = cnt[ap];
-    if (out_sem) {
-        double ybar, v;
-        pixel_noise(mom[ap], n, ybar, v);
-        out_sem[p] = (float)sqrt(v);
-    }
-    if (out_cnt) out_cnt[p] = n;
-}
-__global__ __launch_bounds__(256) void k_noise_partials_counts(const double2* __restrict__ mom, const uint32_t* __restrict__ cnt,
-                                                               double2* __restrict__ partials, uint32_t npix) {
-    __shared__ double2 part[4];
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    double ybar = 0.0, v = 0.0;
-    if (p < npix) pixel_noise(mom[p], cnt[p], ybar, v);
-    const double2 s = block_sum_256(ybar, v, part);
-    if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
-// k_noise_final; the noise is +inf where any pixel has fewer than two samples (info->spp_min, of k_adaptive_info just before)
-__global__ __launch_bounds__(256) void k_noise_final_counts(const double2* __restrict__ partials, uint32_t n_partials, uint32_t npix,
-                                                            const AdaptiveSums* __restrict__ info, double* __restrict__ out) {
-    __shared__ double2 part[4];
-    double a = 0.0, b = 0.0;
-    for (uint32_t k = threadIdx.x; k < n_partials; k += 256u) a += partials[k].x, b += partials[k].y;
-    const double2 s = block_sum_256(a, b, part);
-    if (threadIdx.x != 0) return;
-    const double mean = s.x / (double)npix, rms = sqrt(s.y / (double)npix);
-    double noise = rms / mean;
-    if (mean == 0.0) noise = rms == 0.0 ? 0.0 : (double)INFINITY;
-    if (info->spp_min < 2u) noise = (double)INFINITY;
-    out[0] = mean, out[1] = rms, out[2] = noise;
-}
-// k_denoise_inputs with the pixel's own n_p: c = sum / (float)n_p, (y, v) from its moments and n_p.  A pixel with n_p < 2 has no variance
-// (only an imported state holds one beside done >= 2: rt_accum_state_check accepts a converged pixel with any counts[p] <= done): its c is
-// what rt_accum_read returns, sum / (float)max(n_p, 1), and its guide is NaN, so that it stays what it is and spreads to no other pixel.
-__global__ __launch_bounds__(256) void k_denoise_inputs_counts(const float* __restrict__ sum, const double2* __restrict__ mom, const uint32_t* __restrict__ cnt,
-                                                               float* __restrict__ c, float2* __restrict__ yv, uint32_t nx, uint32_t rows,
-                                                               uint32_t tiles_per_row, uint32_t tile_pixels) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= nx * rows) return;
-    const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx);
-    const uint32_t n = cnt[ap];
-    const float fs = (float)(n ? n : 1u);
-    c[3 * (size_t)p] = sum[3 * ap] / fs, c[3 * (size_t)p + 1] = sum[3 * ap + 1] / fs, c[3 * (size_t)p + 2] = sum[3 * ap + 2] / fs;
-    double ybar, v;
-    pixel_noise(mom[ap], n, ybar, v);
-    const float none = __uint_as_float(0x7FC00000u);
-    yv[p] = n >= 2u ? make_float2((float)ybar, (float)v) : make_float2(none, none);
 }
 
 } // namespace rt

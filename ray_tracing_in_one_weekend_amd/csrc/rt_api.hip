@@ -39,6 +39,8 @@ struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
     bool arena = false; // carved from the context's pool (rt_pool.h) instead of hipMalloc'ed: never freed on its own
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
 };
 
 } // namespace
@@ -1115,12 +1117,13 @@ static int resolve_and_preview(RtCtx* ctx, const Frame& f, const SampleSink& sin
     else if (sink.chm)
         hipLaunchKernelGGL(k_resolve_moments_channels<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.chm, (const uint8_t*)nullptr,
                            (uint32_t*)nullptr, npix, sc);
-    else if (sink.converged) hipLaunchKernelGGL(k_resolve_moments_active, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.converged, sink.cnt, npix, sc);
-    else if (sink.mom) hipLaunchKernelGGL(k_resolve_moments, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, npix, sc);
+    else if (sink.converged) hipLaunchKernelGGL(k_resolve_moments<true>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.converged, sink.cnt, npix, sc);
+    else if (sink.mom)
+        hipLaunchKernelGGL(k_resolve_moments<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, (const uint8_t*)nullptr, (uint32_t*)nullptr, npix, sc);
     else hipLaunchKernelGGL(k_resolve, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, npix, sc);
     hipLaunchKernelGGL(k_accum_counts, dim3((unsigned)f.n_depths), dim3(256), 0, st, f.counts, f.d.nq, (uint32_t)f.n_depths, f.totals + 2);
     if (ctx->progress_armed && ctx->progress_fn && done < spp) { // the last slice is the final image itself
-        hipLaunchKernelGGL(k_finalize, dim3((npix + 255u) / 256u), dim3(256), 0, st, f.acc, (float*)nullptr,
+        hipLaunchKernelGGL(k_finalize<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, f.acc, (const uint32_t*)nullptr, (float*)nullptr,
                            (uint8_t*)ctx->preview_u8.p, nx, rows, done, f.gp.tiles_per_row, f.gp.tile_pixels);
         RT_HIP(ctx, hipMemcpyAsync(ctx->preview_host.data(), ctx->preview_u8.p, (size_t)npix * 3, hipMemcpyDeviceToHost, st));
         RT_HIP(ctx, hipStreamSynchronize(st));
@@ -1247,7 +1250,7 @@ static int render_impl(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, voi
     }
     const hipStream_t st = tr.st;
     const uint32_t npix = tr.npix;
-    hipLaunchKernelGGL(k_finalize, dim3((npix + 255u) / 256u), dim3(256), 0, st, tr.acc, (float*)d_out_rgb_f32,
+    hipLaunchKernelGGL(k_finalize<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, tr.acc, (const uint32_t*)nullptr, (float*)d_out_rgb_f32,
                        (uint8_t*)d_out_rgb8, tr.nx, tr.rows, prm->spp, tr.tiles_per_row, tr.tile_pixels);
     RT_HIP(ctx, hipEventRecord(ctx->ev_end, st));
     RT_HIP(ctx, hipGetLastError());
@@ -1303,16 +1306,53 @@ int rt_render(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, float* out_r
 }
 
 // ---- accumulation and noise (rtow_mi355x.h "Progressive accumulation") ------------------------------------------------------------
+// Every call on the open accumulation refuses first where there is none.
+static int require_open(RtCtx* ctx, const char* who) {
+    return ctx->accum.open ? RT_OK : fail(ctx, RT_ERR_STATE, std::string(who) + ": no accumulation begun (or it was ended: rtow_mi355x.h)");
+}
+// What every reader of the open accumulation is launched with: one lane per pixel in workgroups of 256 on `st`.  ACCUM_READER launches
+// K<true> on an adaptive accumulation and K<false> on a uniform one, with the same arguments: among them `cnt` (NULL or a finished
+// accumulation's on a uniform one) and `n` = done, of which each instantiation ignores the other's (rt_kernels.h).
+struct AccumReader {
+    hipStream_t st;
+    dim3 grid;
+    uint32_t nx, rows, tiles_per_row, tile_pixels;
+    const uint32_t* cnt;
+    uint32_t n;
+    bool counts;
+};
+static AccumReader accum_reader(const RtCtx* ctx, hipStream_t st) {
+    const RtCtx::Accum& a = ctx->accum;
+    return AccumReader{st, dim3((a.npix + 255u) / 256u), a.nx, a.rows, a.tiles_per_row, a.tile_pixels, ctx->accum_cnt.as<const uint32_t>(), a.done, a.adaptive};
+}
+#define ACCUM_READER(K, r, ...)                                                                       \
+    do {                                                                                              \
+        if ((r).counts) hipLaunchKernelGGL(K<true>, (r).grid, dim3(256), 0, (r).st, __VA_ARGS__);     \
+        else hipLaunchKernelGGL(K<false>, (r).grid, dim3(256), 0, (r).st, __VA_ARGS__);               \
+    } while (0)
+
+// The buffers of an adaptive accumulation of npix pixels (kept for the next one): n_p, the flags, the integer sums and their host copy.
+static int ensure_adaptive(RtCtx* ctx, uint32_t npix) {
+    int rc;
+    if ((rc = ensure(ctx, ctx->accum_cnt, (size_t)npix * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(ctx, ctx->accum_flag, (size_t)npix))) return rc;
+    if ((rc = ensure(ctx, ctx->accum_info, ((size_t)((npix + 255u) / 256u) + 1u) * sizeof(AdaptiveSums)))) return rc;
+    if (!ctx->h_info) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_info, sizeof(RtAdaptiveInfo), hipHostMallocDefault));
+    return RT_OK;
+}
+// The three planes of channel moments for npix pixels (kept for the next accumulation).
+static int ensure_channels(RtCtx* ctx, uint32_t npix) { return ensure(ctx, ctx->accum_chm, (size_t)npix * 3 * sizeof(double2)); }
+
 // The frame figures of the open accumulation: two kernels and a 24 B copy into ctx->h_noise, valid after the next wait for `st`.
 // The integer sums of an adaptive accumulation (npix > 0): with `decide` the criterion first (the start of an adaptive add), then two
 // kernels' worth of sums and a 24 B copy into ctx->h_info, valid after the next wait for `st`.
 static int enqueue_adaptive_info(RtCtx* ctx, hipStream_t st, const RtAdaptive* decide) {
     const RtCtx::Accum& a = ctx->accum;
     const uint32_t nb = (a.npix + 255u) / 256u;
-    AdaptiveSums* partials = (AdaptiveSums*)ctx->accum_info.p;
-    const double2* mom = (const double2*)ctx->accum_mom.p;
-    const uint32_t* cnt = (const uint32_t*)ctx->accum_cnt.p;
-    uint8_t* flag = (uint8_t*)ctx->accum_flag.p;
+    AdaptiveSums* partials = ctx->accum_info.as<AdaptiveSums>();
+    const double2* mom = ctx->accum_mom.as<const double2>();
+    const uint32_t* cnt = ctx->accum_cnt.as<const uint32_t>();
+    uint8_t* flag = ctx->accum_flag.as<uint8_t>();
     if (decide) hipLaunchKernelGGL(k_adaptive_decide<true>, dim3(nb), dim3(256), 0, st, mom, cnt, flag, partials, a.npix, decide->tolerance, decide->luminance_floor, decide->min_samples);
     else hipLaunchKernelGGL(k_adaptive_decide<false>, dim3(nb), dim3(256), 0, st, mom, cnt, flag, partials, a.npix, 0.0, 0.0, 0u);
     hipLaunchKernelGGL(k_adaptive_info, dim3(1), dim3(256), 0, st, (const AdaptiveSums*)partials, nb, partials + nb);
@@ -1321,17 +1361,19 @@ static int enqueue_adaptive_info(RtCtx* ctx, hipStream_t st, const RtAdaptive* d
 }
 static int enqueue_noise(RtCtx* ctx, hipStream_t st) {
     const RtCtx::Accum& a = ctx->accum;
-    const uint32_t nb = (a.npix + 255u) / 256u;
-    double2* partials = (double2*)ctx->accum_partials.p;
+    const AccumReader r = accum_reader(ctx, st);
+    const uint32_t nb = r.grid.x;
+    double2* partials = ctx->accum_partials.as<double2>();
     double* figures = (double*)(partials + nb);
-    if (a.adaptive) { // n_p per pixel; spp_min and spp_max come with the figures
+    const AdaptiveSums* info = nullptr; // n_p per pixel: spp_min and spp_max come with the figures
+    if (a.adaptive) {
         if (const int rc = enqueue_adaptive_info(ctx, st, nullptr)) return rc;
-        hipLaunchKernelGGL(k_noise_partials_counts, dim3(nb), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, (const uint32_t*)ctx->accum_cnt.p, partials, a.npix);
-        hipLaunchKernelGGL(k_noise_final_counts, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, a.npix, (const AdaptiveSums*)ctx->accum_info.p + nb, figures);
-    } else {
-        hipLaunchKernelGGL(k_noise_partials, dim3(nb), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, partials, a.npix, a.done);
-        hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, a.npix, a.done, figures);
+        info = ctx->accum_info.as<const AdaptiveSums>() + nb;
     }
+    ACCUM_READER(k_noise_partials, r, ctx->accum_mom.as<const double2>(), r.cnt, partials, a.npix, r.n);
+    // (ONE workgroup over the partials, not a lane per pixel)
+    if (a.adaptive) hipLaunchKernelGGL(k_noise_final<true>, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, a.npix, info, r.n, figures);
+    else hipLaunchKernelGGL(k_noise_final<false>, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, a.npix, info, r.n, figures);
     RT_HIP(ctx, hipMemcpyAsync(ctx->h_noise, figures, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     return RT_OK;
 }
@@ -1375,35 +1417,57 @@ int rt_accum_begin(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, uint32_
     return RT_OK;
 }
 
-// figures: the frame figures are enqueued behind the samples, so that the one wait of the call (for its statistics) delivers them too
-static int accum_add(RtCtx* ctx, uint32_t n_samples, RtStats* stats, bool figures) {
+// One add to the open accumulation, for rt_accum_add_adaptive (adaptive: with the caller's `ad`, refused like any invalid one where it is
+// NULL) or for rt_accum_add (`ad` is not looked at).  figures: the frame figures — and an adaptive add's integer sums — are enqueued
+// behind the samples, so that the one wait of the call (for its statistics) delivers them too.
+static int accum_add(RtCtx* ctx, uint32_t n_samples, bool adaptive, const RtAdaptive* ad, RtStats* stats, bool figures) {
     if (!ctx) return RT_ERR_INVALID;
-    RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_add: no accumulation begun (or it was ended: rtow_mi355x.h)");
-    if (a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_add: the accumulation is adaptive (uniform adds come before the first rt_accum_add_adaptive)");
-    if (n_samples == 0u) return fail(ctx, RT_ERR_INVALID, "rt_accum_add: n_samples must be > 0");
-    if ((uint64_t)a.first + a.done + n_samples > 0xFFFFFFFFull)
-        return fail(ctx, RT_ERR_INVALID, "rt_accum_add: first_sample + the samples added must stay below 2^32, as RtParams.spp does");
-    RtParams p = a.prm;
-    p.spp = n_samples;
-    Traced tr;
-    SampleSink sink{(float*)ctx->accum_sum.p, (double2*)ctx->accum_mom.p, a.first + a.done};
-    if (a.channels) sink.chm = (double2*)ctx->accum_chm.p;
-    if (a.halves) sink.halves = true, sink.hp = half_planes(ctx->accum_halves, a.npix);
-    const int rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr);
+    const char* name = adaptive ? "rt_accum_add_adaptive" : "rt_accum_add";
+    int rc = require_open(ctx, name);
     if (rc) return rc;
-    if (tr.npix == 0u) {
+    const std::string who = std::string(name) + ": ";
+    RtCtx::Accum& a = ctx->accum;
+    const bool too_many = (uint64_t)a.first + a.done + n_samples > 0xFFFFFFFFull;
+    const auto nothing_traced = [&] { // a shard without rows
         a.done += n_samples, a.added = true;
         if (stats) std::memset(stats, 0, sizeof(*stats));
         return RT_OK;
+    };
+    if (adaptive) {
+        if (const char* why = adaptive_invalid(ad, n_samples)) return fail(ctx, RT_ERR_INVALID, who + why);
+        if (too_many) return fail(ctx, RT_ERR_INVALID, who + "first_sample + the samples issued must stay below 2^32, as RtParams.spp does");
+        if (a.npix == 0u) {
+            a.adaptive = true;
+            return nothing_traced();
+        }
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        if (!a.adaptive) { // the first adaptive add: n_p = what the uniform adds gave every pixel, nobody converged
+            if ((rc = ensure_adaptive(ctx, a.npix))) return rc;
+            hipLaunchKernelGGL(k_adaptive_begin, dim3((a.npix + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->accum_cnt.as<uint32_t>(), ctx->accum_flag.as<uint8_t>(),
+                               a.npix, a.done);
+            a.adaptive = true;
+        }
+        if ((rc = enqueue_adaptive_info(ctx, ctx->stream, ad))) return rc; // the decision
+    } else {
+        if (a.adaptive) return fail(ctx, RT_ERR_STATE, who + "the accumulation is adaptive (uniform adds come before the first rt_accum_add_adaptive)");
+        if (n_samples == 0u) return fail(ctx, RT_ERR_INVALID, who + "n_samples must be > 0");
+        if (too_many) return fail(ctx, RT_ERR_INVALID, who + "first_sample + the samples added must stay below 2^32, as RtParams.spp does");
     }
+    RtParams p = a.prm;
+    p.spp = n_samples;
+    Traced tr;
+    SampleSink sink{ctx->accum_sum.as<float>(), ctx->accum_mom.as<double2>(), a.first + a.done};
+    if (adaptive) sink.converged = ctx->accum_flag.as<const uint8_t>(), sink.cnt = ctx->accum_cnt.as<uint32_t>();
+    if (a.channels) sink.chm = ctx->accum_chm.as<double2>();
+    if (a.halves) sink.halves = true, sink.hp = half_planes(ctx->accum_halves, a.npix);
+    if ((rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr))) return rc;
+    if (tr.npix == 0u) return nothing_traced();
     if (tr.npix != a.npix || tr.tiles_per_row != a.tiles_per_row || tr.tile_pixels != a.tile_pixels) {
         a.open = false; // (cannot happen: everything the order hangs on ends the accumulation)
-        return fail(ctx, RT_ERR_STATE, "rt_accum_add: the pixel order changed since rt_accum_begin (internal)");
+        return fail(ctx, RT_ERR_STATE, who + "the pixel order changed since rt_accum_begin (internal)");
     }
     a.done += n_samples, a.added = true;
-    if (figures)
-        if (const int rn = enqueue_noise(ctx, tr.st)) return rn;
+    if (figures && (rc = enqueue_noise(ctx, tr.st))) return rc;
     RT_HIP(ctx, hipEventRecord(ctx->ev_end, tr.st));
     RT_HIP(ctx, hipGetLastError());
     ctx->mark("enqueue_all_launches");
@@ -1412,40 +1476,31 @@ static int accum_add(RtCtx* ctx, uint32_t n_samples, RtStats* stats, bool figure
     return RT_OK;
 }
 
-int rt_accum_add(RtCtx* ctx, uint32_t n_samples, RtStats* stats) { return accum_add(ctx, n_samples, stats, false); }
+int rt_accum_add(RtCtx* ctx, uint32_t n_samples, RtStats* stats) { return accum_add(ctx, n_samples, false, nullptr, stats, false); }
 
 int rt_accum_read(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_sem, RtNoise* noise) {
     if (!ctx) return RT_ERR_INVALID;
+    int rc = require_open(ctx, "rt_accum_read");
+    if (rc) return rc;
     const RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_read: no accumulation begun (or it was ended: rtow_mi355x.h)");
     if (a.npix == 0u) {
         if (noise) fill_noise(ctx, noise);
         return RT_OK;
     }
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
-    const uint32_t npix = a.npix, grid = (npix + 255u) / 256u;
+    const uint32_t npix = a.npix;
     const size_t n = (size_t)npix * 3;
-    int rc;
     if (out_rgb_f32 && (rc = ensure(ctx, ctx->out_f32, n * sizeof(float)))) return rc;
     if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
     if (out_sem && (rc = ensure(ctx, ctx->accum_sem, (size_t)npix * sizeof(float)))) return rc;
-    if (a.adaptive) { // the same two steps with the pixel's own n_p (rt_adaptive.h)
-        const uint32_t* cnt = (const uint32_t*)ctx->accum_cnt.p;
-        if (out_rgb_f32 || out_rgb8)
-            hipLaunchKernelGGL(k_finalize_counts, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, cnt, out_rgb_f32 ? (float*)ctx->out_f32.p : (float*)nullptr,
-                               out_rgb8 ? (uint8_t*)ctx->out_u8.p : (uint8_t*)nullptr, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-        if (out_sem)
-            hipLaunchKernelGGL(k_sem_counts, dim3(grid), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, cnt, (float*)ctx->accum_sem.p, (uint32_t*)nullptr, a.nx, a.rows,
-                               a.tiles_per_row, a.tile_pixels);
-    } else {
-        if (out_rgb_f32 || out_rgb8) // (before the first add the sums are zeros: divided by 1, not by 0)
-            hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, out_rgb_f32 ? (float*)ctx->out_f32.p : (float*)nullptr,
-                               out_rgb8 ? (uint8_t*)ctx->out_u8.p : (uint8_t*)nullptr, a.nx, a.rows, std::max(a.done, 1u), a.tiles_per_row, a.tile_pixels);
-        if (out_sem)
-            hipLaunchKernelGGL(k_sem, dim3(grid), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, (float*)ctx->accum_sem.p, a.nx, a.rows, a.done,
-                               a.tiles_per_row, a.tile_pixels);
-    }
+    const AccumReader r = accum_reader(ctx, st);
+    if (out_rgb_f32 || out_rgb8) // (a uniform accumulation before the first add: the sums are zeros, divided by 1, not by 0)
+        ACCUM_READER(k_finalize, r, ctx->accum_sum.as<const float>(), r.cnt, out_rgb_f32 ? ctx->out_f32.as<float>() : nullptr,
+                     out_rgb8 ? ctx->out_u8.as<uint8_t>() : nullptr, r.nx, r.rows, std::max(r.n, 1u), r.tiles_per_row, r.tile_pixels);
+    if (out_sem)
+        ACCUM_READER(k_sem, r, ctx->accum_mom.as<const double2>(), r.cnt, ctx->accum_sem.as<float>(), (uint32_t*)nullptr, r.nx, r.rows, r.n, r.tiles_per_row,
+                     r.tile_pixels);
     if (noise && (rc = enqueue_noise(ctx, st))) return rc;
     RT_HIP(ctx, hipGetLastError());
     if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->out_f32.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -1462,119 +1517,6 @@ int rt_accum_end(RtCtx* ctx) {
     return RT_OK;
 }
 
-int rt_render_to_noise(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, double target_noise, uint32_t spp_step, float* out_rgb_f32,
-                       uint8_t* out_rgb8, float* out_sem, RtNoise* noise, RtStats* stats) {
-    int rc = check_params(ctx, cam, prm);
-    if (rc) return rc;
-    if (ctx->accum.open) return fail(ctx, RT_ERR_STATE, "rt_render_to_noise: an accumulation is open (rt_accum_end it first)");
-    if (spp_step == 0u) return fail(ctx, RT_ERR_INVALID, "rt_render_to_noise: spp_step must be > 0");
-    if (!(target_noise >= 0.0)) return fail(ctx, RT_ERR_INVALID, "rt_render_to_noise: target_noise must be >= 0 (and not NaN)");
-    if (prm->spp < 2u) return fail(ctx, RT_ERR_INVALID, "rt_render_to_noise: spp, the maximum, must be >= 2 (one sample has no variance estimate)");
-    RtParams p = *prm;
-    p.spp = std::min(spp_step, prm->spp); // (the expected size of one add)
-    if ((rc = rt_accum_begin(ctx, cam, &p, 0u))) return rc;
-    RtStats total;
-    std::memset(&total, 0, sizeof(total));
-    while (ctx->accum.done < prm->spp) {
-        RtStats s;
-        if ((rc = accum_add(ctx, std::min(spp_step, prm->spp - ctx->accum.done), &s, true))) break;
-        total.n_paths += s.n_paths, total.n_rays += s.n_rays, total.n_rays_secondary += s.n_rays_secondary;
-        total.n_texture_fetches += s.n_texture_fetches, total.n_bad_dir += s.n_bad_dir;
-        total.seconds_total += s.seconds_total, total.seconds_trace += s.seconds_trace, total.seconds_device += s.seconds_device;
-        total.bytes_algorithmic += s.bytes_algorithmic, total.bytes_trace_algorithmic += s.bytes_trace_algorithmic;
-        total.n_trace_launches += s.n_trace_launches, total.n_slices += s.n_slices;
-        for (int d = 0; d < 64; ++d) total.rays_per_depth[d] += s.rays_per_depth[d];
-        if (ctx->accum.npix == 0u || ctx->h_noise[2] <= target_noise) break;
-    }
-    if (!rc) rc = rt_accum_read(ctx, out_rgb_f32, out_rgb8, out_sem, noise);
-    ctx->accum.open = false;
-    if (!rc && stats) *stats = total;
-    return rc;
-}
-
-// ---- adaptive sampling (rtow_mi355x.h "Adaptive sampling", csrc/rt_adaptive.h, csrc/rt_adaptive_plan.h) ---------------------------------
-int rt_adaptive_check(const RtAdaptive* ad, uint32_t n_samples) { return adaptive_invalid(ad, n_samples) ? RT_ERR_INVALID : RT_OK; }
-int rt_adaptive_converged(const RtAdaptive* ad, double s1, double s2, uint32_t n) {
-    if (adaptive_invalid(ad, 1u)) return RT_ERR_INVALID;
-    return adaptive_converged_moments(s1, s2, n, *ad) ? 1 : 0;
-}
-
-// figures: the frame figures and the integer sums are enqueued behind the samples, so that the one wait of the call delivers them too
-static int accum_add_adaptive(RtCtx* ctx, uint32_t n_samples, const RtAdaptive* ad, RtStats* stats, bool figures) {
-    if (!ctx) return RT_ERR_INVALID;
-    RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_add_adaptive: no accumulation begun (or it was ended: rtow_mi355x.h)");
-    if (const char* why = adaptive_invalid(ad, n_samples)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_add_adaptive: ") + why);
-    if ((uint64_t)a.first + a.done + n_samples > 0xFFFFFFFFull)
-        return fail(ctx, RT_ERR_INVALID, "rt_accum_add_adaptive: first_sample + the samples issued must stay below 2^32, as RtParams.spp does");
-    if (a.npix == 0u) { // a shard without rows
-        a.adaptive = true, a.done += n_samples, a.added = true;
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    const hipStream_t st = ctx->stream;
-    const uint32_t nb = (a.npix + 255u) / 256u;
-    int rc;
-    if (!a.adaptive) { // the first adaptive add: n_p = what the uniform adds gave every pixel, nobody converged
-        if ((rc = ensure(ctx, ctx->accum_cnt, (size_t)a.npix * sizeof(uint32_t)))) return rc;
-        if ((rc = ensure(ctx, ctx->accum_flag, (size_t)a.npix))) return rc;
-        if ((rc = ensure(ctx, ctx->accum_info, ((size_t)nb + 1u) * sizeof(AdaptiveSums)))) return rc;
-        if (!ctx->h_info) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_info, sizeof(RtAdaptiveInfo), hipHostMallocDefault));
-        hipLaunchKernelGGL(k_adaptive_begin, dim3(nb), dim3(256), 0, st, (uint32_t*)ctx->accum_cnt.p, (uint8_t*)ctx->accum_flag.p, a.npix, a.done);
-        a.adaptive = true;
-    }
-    if ((rc = enqueue_adaptive_info(ctx, st, ad))) return rc; // the decision
-    RtParams p = a.prm;
-    p.spp = n_samples;
-    Traced tr;
-    SampleSink sink{(float*)ctx->accum_sum.p, (double2*)ctx->accum_mom.p, a.first + a.done};
-    sink.converged = (const uint8_t*)ctx->accum_flag.p, sink.cnt = (uint32_t*)ctx->accum_cnt.p;
-    if (a.channels) sink.chm = (double2*)ctx->accum_chm.p;
-    if (a.halves) sink.halves = true, sink.hp = half_planes(ctx->accum_halves, a.npix);
-    if ((rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr))) return rc;
-    if (tr.npix != a.npix || tr.tiles_per_row != a.tiles_per_row || tr.tile_pixels != a.tile_pixels) {
-        a.open = false; // (cannot happen: everything the order hangs on ends the accumulation)
-        return fail(ctx, RT_ERR_STATE, "rt_accum_add_adaptive: the pixel order changed since rt_accum_begin (internal)");
-    }
-    a.done += n_samples, a.added = true;
-    if (figures && (rc = enqueue_noise(ctx, tr.st))) return rc;
-    RT_HIP(ctx, hipEventRecord(ctx->ev_end, tr.st));
-    RT_HIP(ctx, hipGetLastError());
-    ctx->mark("enqueue_all_launches");
-    if (stats) return read_stats(ctx, tr, n_samples, stats);
-    if (figures) RT_HIP(ctx, hipStreamSynchronize(tr.st));
-    return RT_OK;
-}
-
-int rt_accum_add_adaptive(RtCtx* ctx, uint32_t n_samples, const RtAdaptive* ad, RtStats* stats) { return accum_add_adaptive(ctx, n_samples, ad, stats, false); }
-
-int rt_accum_read_counts(RtCtx* ctx, uint32_t* out_counts, RtAdaptiveInfo* info) {
-    if (!ctx) return RT_ERR_INVALID;
-    const RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_read_counts: no accumulation begun (or it was ended: rtow_mi355x.h)");
-    if (info) std::memset(info, 0, sizeof(*info));
-    if (!a.adaptive || a.npix == 0u) { // uniform so far: every pixel holds `done` samples and is active
-        if (out_counts) std::fill(out_counts, out_counts + a.npix, a.done);
-        if (info) info->n_active = a.npix, info->n_samples = (uint64_t)a.npix * a.done, info->spp_min = info->spp_max = a.done;
-        return RT_OK;
-    }
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    const hipStream_t st = ctx->stream;
-    int rc;
-    if (out_counts) {
-        if ((rc = ensure(ctx, ctx->accum_cnt_out, (size_t)a.npix * sizeof(uint32_t)))) return rc;
-        hipLaunchKernelGGL(k_sem_counts, dim3((a.npix + 255u) / 256u), dim3(256), 0, st, (const double2*)ctx->accum_mom.p, (const uint32_t*)ctx->accum_cnt.p,
-                           (float*)nullptr, (uint32_t*)ctx->accum_cnt_out.p, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-        RT_HIP(ctx, hipMemcpyAsync(out_counts, ctx->accum_cnt_out.p, (size_t)a.npix * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    if (info && (rc = enqueue_adaptive_info(ctx, st, nullptr))) return rc;
-    RT_HIP(ctx, hipGetLastError());
-    RT_HIP(ctx, hipStreamSynchronize(st));
-    if (info) *info = *ctx->h_info;
-    return RT_OK;
-}
-
 static void add_stats(RtStats& total, const RtStats& s) {
     total.n_paths += s.n_paths, total.n_rays += s.n_rays, total.n_rays_secondary += s.n_rays_secondary;
     total.n_texture_fetches += s.n_texture_fetches, total.n_bad_dir += s.n_bad_dir;
@@ -1584,30 +1526,87 @@ static void add_stats(RtStats& total, const RtStats& s) {
     for (int d = 0; d < 64; ++d) total.rays_per_depth[d] += s.rays_per_depth[d];
 }
 
-int rt_render_adaptive(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, const RtAdaptive* ad, uint32_t spp_step, float* out_rgb_f32,
-                       uint8_t* out_rgb8, float* out_sem, uint32_t* out_counts, RtNoise* noise, RtAdaptiveInfo* info, RtStats* stats) {
-    int rc = check_params(ctx, cam, prm);
-    if (rc) return rc;
-    if (ctx->accum.open) return fail(ctx, RT_ERR_STATE, "rt_render_adaptive: an accumulation is open (rt_accum_end it first)");
-    if (spp_step == 0u) return fail(ctx, RT_ERR_INVALID, "rt_render_adaptive: spp_step must be > 0");
-    if (const char* why = adaptive_invalid(ad, spp_step)) return fail(ctx, RT_ERR_INVALID, std::string("rt_render_adaptive: ") + why);
-    if (prm->spp < 2u) return fail(ctx, RT_ERR_INVALID, "rt_render_adaptive: spp, the maximum, must be >= 2 (one sample has no variance estimate)");
+// The loop of rt_render_to_noise (uniform adds up to *target_noise) and of rt_render_adaptive (adaptive adds with `ad`, no target), behind
+// their own argument checks: an accumulation of its own, adds of spp_step samples with their figures until prm->spp samples, the maximum,
+// are issued or the figures that the last add delivered meet the caller's stop rule, the read-out, the end.
+static int render_loop(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, const double* target_noise, const RtAdaptive* ad, uint32_t spp_step,
+                       float* out_rgb_f32, uint8_t* out_rgb8, float* out_sem, uint32_t* out_counts, RtNoise* noise, RtAdaptiveInfo* info, RtStats* stats) {
     RtParams p = *prm;
     p.spp = std::min(spp_step, prm->spp); // (the expected size of one add)
-    if ((rc = rt_accum_begin(ctx, cam, &p, 0u))) return rc;
+    int rc = rt_accum_begin(ctx, cam, &p, 0u);
+    if (rc) return rc;
     RtStats total;
     std::memset(&total, 0, sizeof(total));
     while (ctx->accum.done < prm->spp) {
         RtStats s;
-        if ((rc = accum_add_adaptive(ctx, std::min(spp_step, prm->spp - ctx->accum.done), ad, &s, true))) break;
+        if ((rc = accum_add(ctx, std::min(spp_step, prm->spp - ctx->accum.done), ad != nullptr, ad, &s, true))) break;
         add_stats(total, s);
-        if (ctx->accum.npix == 0u || ctx->h_info->n_active == 0u) break; // (this add found nobody active and traced nothing)
+        if (ctx->accum.npix == 0u) break;
+        if (target_noise ? ctx->h_noise[2] <= *target_noise : ctx->h_info->n_active == 0u) break; // (nobody active: this add traced nothing)
     }
     if (!rc) rc = rt_accum_read(ctx, out_rgb_f32, out_rgb8, out_sem, noise);
     if (!rc && (out_counts || info)) rc = rt_accum_read_counts(ctx, out_counts, info);
     ctx->accum.open = false;
     if (!rc && stats) *stats = total;
     return rc;
+}
+
+int rt_render_to_noise(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, double target_noise, uint32_t spp_step, float* out_rgb_f32,
+                       uint8_t* out_rgb8, float* out_sem, RtNoise* noise, RtStats* stats) {
+    const int rc = check_params(ctx, cam, prm);
+    if (rc) return rc;
+    if (ctx->accum.open) return fail(ctx, RT_ERR_STATE, "rt_render_to_noise: an accumulation is open (rt_accum_end it first)");
+    if (spp_step == 0u) return fail(ctx, RT_ERR_INVALID, "rt_render_to_noise: spp_step must be > 0");
+    if (!(target_noise >= 0.0)) return fail(ctx, RT_ERR_INVALID, "rt_render_to_noise: target_noise must be >= 0 (and not NaN)");
+    if (prm->spp < 2u) return fail(ctx, RT_ERR_INVALID, "rt_render_to_noise: spp, the maximum, must be >= 2 (one sample has no variance estimate)");
+    return render_loop(ctx, cam, prm, &target_noise, nullptr, spp_step, out_rgb_f32, out_rgb8, out_sem, nullptr, noise, nullptr, stats);
+}
+
+// ---- adaptive sampling (rtow_mi355x.h "Adaptive sampling", csrc/rt_adaptive.h, csrc/rt_adaptive_plan.h) ---------------------------------
+int rt_adaptive_check(const RtAdaptive* ad, uint32_t n_samples) { return adaptive_invalid(ad, n_samples) ? RT_ERR_INVALID : RT_OK; }
+int rt_adaptive_converged(const RtAdaptive* ad, double s1, double s2, uint32_t n) {
+    if (adaptive_invalid(ad, 1u)) return RT_ERR_INVALID;
+    return adaptive_converged_moments(s1, s2, n, *ad) ? 1 : 0;
+}
+
+int rt_accum_add_adaptive(RtCtx* ctx, uint32_t n_samples, const RtAdaptive* ad, RtStats* stats) { return accum_add(ctx, n_samples, true, ad, stats, false); }
+
+int rt_accum_read_counts(RtCtx* ctx, uint32_t* out_counts, RtAdaptiveInfo* info) {
+    if (!ctx) return RT_ERR_INVALID;
+    int rc = require_open(ctx, "rt_accum_read_counts");
+    if (rc) return rc;
+    const RtCtx::Accum& a = ctx->accum;
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!a.adaptive || a.npix == 0u) { // uniform so far: every pixel holds `done` samples and is active
+        if (out_counts) std::fill(out_counts, out_counts + a.npix, a.done);
+        if (info) info->n_active = a.npix, info->n_samples = (uint64_t)a.npix * a.done, info->spp_min = info->spp_max = a.done;
+        return RT_OK;
+    }
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    if (out_counts) {
+        if ((rc = ensure(ctx, ctx->accum_cnt_out, (size_t)a.npix * sizeof(uint32_t)))) return rc;
+        const AccumReader r = accum_reader(ctx, st);
+        ACCUM_READER(k_sem, r, ctx->accum_mom.as<const double2>(), r.cnt, (float*)nullptr, ctx->accum_cnt_out.as<uint32_t>(), r.nx, r.rows, r.n, r.tiles_per_row,
+                     r.tile_pixels);
+        RT_HIP(ctx, hipMemcpyAsync(out_counts, ctx->accum_cnt_out.p, (size_t)a.npix * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    if (info && (rc = enqueue_adaptive_info(ctx, st, nullptr))) return rc;
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    if (info) *info = *ctx->h_info;
+    return RT_OK;
+}
+
+int rt_render_adaptive(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, const RtAdaptive* ad, uint32_t spp_step, float* out_rgb_f32,
+                       uint8_t* out_rgb8, float* out_sem, uint32_t* out_counts, RtNoise* noise, RtAdaptiveInfo* info, RtStats* stats) {
+    const int rc = check_params(ctx, cam, prm);
+    if (rc) return rc;
+    if (ctx->accum.open) return fail(ctx, RT_ERR_STATE, "rt_render_adaptive: an accumulation is open (rt_accum_end it first)");
+    if (spp_step == 0u) return fail(ctx, RT_ERR_INVALID, "rt_render_adaptive: spp_step must be > 0");
+    if (const char* why = adaptive_invalid(ad, spp_step)) return fail(ctx, RT_ERR_INVALID, std::string("rt_render_adaptive: ") + why);
+    if (prm->spp < 2u) return fail(ctx, RT_ERR_INVALID, "rt_render_adaptive: spp, the maximum, must be >= 2 (one sample has no variance estimate)");
+    return render_loop(ctx, cam, prm, nullptr, ad, spp_step, out_rgb_f32, out_rgb8, out_sem, out_counts, noise, info, stats);
 }
 
 int rt_debug_accum_set_moments(RtCtx* ctx, uint32_t pixel, double s1, double s2) {
@@ -1655,36 +1654,52 @@ static int ensure_denoise(RtCtx* ctx, size_t npix) {
     return ensure(ctx, ctx->dn_out, npix * 3 * sizeof(float));
 }
 
+// What the three rt_accum_denoise* calls refuse, in this order, and the parameters of the call.  `untracked`: NULL, or what the accumulation
+// lacks for this filter; `min_done`: the samples below which there is no variance, and `no_variance` says whose.
+static int denoise_begin(RtCtx* ctx, const char* who, const RtDenoise* dn, RtDenoise& d, float default_strength, const char* untracked, uint32_t min_done,
+                         const char* no_variance) {
+    int rc = require_open(ctx, who);
+    if (rc) return rc;
+    const RtCtx::Accum& a = ctx->accum;
+    if (untracked) return fail(ctx, RT_ERR_STATE, std::string(who) + ": " + untracked);
+    if ((rc = denoise_params(ctx, dn, d, who, default_strength))) return rc;
+    if (a.prm.shard_count > 1u)
+        return fail(ctx, RT_ERR_UNSUPPORTED, std::string(who) + ": a sharded frame (shard_count > 1): the local rows of a shard are not neighbours in the image");
+    if (a.done < min_done) return fail(ctx, RT_ERR_STATE, std::string(who) + ": fewer than " + std::to_string(min_done) + " samples accumulated: " + no_variance);
+    return RT_OK;
+}
+// Their shared end: the filtered image `img` (device, image order) through k_finalize's quantisation and flip into ctx->out_u8 where rgb8 is
+// asked — row-major (no tiles), and / (float)1 changes no bit — and the copies to the host, enqueued on the context's stream.
+static int denoise_finish(RtCtx* ctx, const float* img, float* out_rgb_f32, uint8_t* out_rgb8) {
+    const RtCtx::Accum& a = ctx->accum;
+    const hipStream_t st = ctx->stream;
+    const size_t n = (size_t)a.npix * 3;
+    if (out_rgb8)
+        hipLaunchKernelGGL(k_finalize<false>, dim3((a.npix + 255u) / 256u), dim3(256), 0, st, img, (const uint32_t*)nullptr, (float*)nullptr, ctx->out_u8.as<uint8_t>(), a.nx,
+                           a.rows, 1u, 0u, 0u);
+    RT_HIP(ctx, hipGetLastError());
+    if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, img, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (out_rgb8) RT_HIP(ctx, hipMemcpyAsync(out_rgb8, ctx->out_u8.p, n, hipMemcpyDeviceToHost, st));
+    return RT_OK;
+}
+
 int rt_accum_denoise(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8) {
     if (!ctx) return RT_ERR_INVALID;
-    const RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise: no accumulation begun (or it was ended: rtow_mi355x.h)");
     RtDenoise d;
-    int rc = denoise_params(ctx, dn, d, "rt_accum_denoise");
+    int rc = denoise_begin(ctx, "rt_accum_denoise", dn, d, RT_DENOISE_DEFAULT_STRENGTH, nullptr, 2u, "there is no variance yet");
     if (rc) return rc;
-    if (a.prm.shard_count > 1u)
-        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_denoise: a sharded frame (shard_count > 1): the local rows of a shard are not neighbours in the image");
-    if (a.done < 2u) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise: fewer than 2 samples accumulated: there is no variance yet");
+    const RtCtx::Accum& a = ctx->accum;
     if (a.npix == 0u) return RT_OK;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
-    const uint32_t npix = a.npix, grid = (npix + 255u) / 256u;
-    const size_t n = (size_t)npix * 3;
-    if ((rc = ensure_denoise(ctx, npix))) return rc;
-    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
-    if (a.adaptive) // (every n_p >= 2: a pixel stops on min_samples >= 2 at the earliest, and done >= 2 was checked)
-        hipLaunchKernelGGL(k_denoise_inputs_counts, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, (const double2*)ctx->accum_mom.p,
-                           (const uint32_t*)ctx->accum_cnt.p, (float*)ctx->dn_c.p, (float2*)ctx->dn_yv.p, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-    else
-        hipLaunchKernelGGL(k_denoise_inputs, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, (const double2*)ctx->accum_mom.p, (float*)ctx->dn_c.p,
-                           (float2*)ctx->dn_yv.p, a.nx, a.rows, a.done, a.tiles_per_row, a.tile_pixels);
-    launch_denoise(st, (const float*)ctx->dn_c.p, (const float2*)ctx->dn_yv.p, (float*)ctx->dn_out.p, a.nx, a.rows, d);
-    if (out_rgb8) // k_finalize's quantisation and flip of the filtered image: row-major (no tiles), and / (float)1 changes no bit
-        hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, st, (const float*)ctx->dn_out.p, (float*)nullptr, (uint8_t*)ctx->out_u8.p, a.nx, a.rows, 1u, 0u,
-                           0u);
-    RT_HIP(ctx, hipGetLastError());
-    if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->dn_out.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (out_rgb8) RT_HIP(ctx, hipMemcpyAsync(out_rgb8, ctx->out_u8.p, n, hipMemcpyDeviceToHost, st));
+    if ((rc = ensure_denoise(ctx, a.npix))) return rc;
+    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, (size_t)a.npix * 3))) return rc;
+    const AccumReader r = accum_reader(ctx, st);
+    // (adaptive: every n_p >= 2 unless a state was imported: a pixel stops on min_samples >= 2 at the earliest, and done >= 2 was checked)
+    ACCUM_READER(k_denoise_inputs, r, ctx->accum_sum.as<const float>(), ctx->accum_mom.as<const double2>(), r.cnt, ctx->dn_c.as<float>(), ctx->dn_yv.as<float2>(), r.nx,
+                 r.rows, r.n, r.tiles_per_row, r.tile_pixels);
+    launch_denoise(st, ctx->dn_c.as<const float>(), ctx->dn_yv.as<const float2>(), ctx->dn_out.as<float>(), a.nx, a.rows, d);
+    if ((rc = denoise_finish(ctx, ctx->dn_out.as<const float>(), out_rgb_f32, out_rgb8))) return rc;
     RT_HIP(ctx, hipStreamSynchronize(st));
     return RT_OK;
 }
@@ -1714,15 +1729,14 @@ int rt_debug_denoise(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, c
 // ---- channel moments and the colour-guided filter (rtow_mi355x.h "Channel moments and the colour-guided filter", csrc/rt_channels.h) ------
 int rt_accum_track_channels(RtCtx* ctx) {
     if (!ctx) return RT_ERR_INVALID;
+    if (const int rc = require_open(ctx, "rt_accum_track_channels")) return rc;
     RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_track_channels: no accumulation begun (or it was ended: rtow_mi355x.h)");
     if (a.channels) return RT_OK;
     if (a.done != 0u || a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_track_channels: samples were added already (call it right after rt_accum_begin)");
     if (a.npix) {
         RT_HIP(ctx, hipSetDevice(ctx->device));
-        const size_t bytes = (size_t)a.npix * 3 * sizeof(double2);
-        if (const int rc = ensure(ctx, ctx->accum_chm, bytes)) return rc;
-        RT_HIP(ctx, hipMemsetAsync(ctx->accum_chm.p, 0, bytes, ctx->stream));
+        if (const int rc = ensure_channels(ctx, a.npix)) return rc;
+        RT_HIP(ctx, hipMemsetAsync(ctx->accum_chm.p, 0, (size_t)a.npix * 3 * sizeof(double2), ctx->stream));
     }
     a.channels = true;
     return RT_OK;
@@ -1730,22 +1744,17 @@ int rt_accum_track_channels(RtCtx* ctx) {
 
 int rt_accum_read_channel_sem(RtCtx* ctx, float* out_sem_rgb) {
     if (!ctx) return RT_ERR_INVALID;
+    if (const int rc = require_open(ctx, "rt_accum_read_channel_sem")) return rc;
     const RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_read_channel_sem: no accumulation begun (or it was ended: rtow_mi355x.h)");
     if (!a.channels) return fail(ctx, RT_ERR_STATE, "rt_accum_read_channel_sem: the accumulation does not track channels (rt_accum_track_channels)");
     if (!out_sem_rgb) return fail(ctx, RT_ERR_INVALID, "rt_accum_read_channel_sem: NULL array");
     if (a.npix == 0u) return RT_OK;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
-    const uint32_t grid = (a.npix + 255u) / 256u;
     const size_t bytes = (size_t)a.npix * 3 * sizeof(float);
     if (const int rc = ensure(ctx, ctx->accum_chsem, bytes)) return rc;
-    if (a.adaptive)
-        hipLaunchKernelGGL(k_channel_sem<true>, dim3(grid), dim3(256), 0, st, (const double2*)ctx->accum_chm.p, (const uint32_t*)ctx->accum_cnt.p,
-                           (float*)ctx->accum_chsem.p, a.nx, a.rows, 0u, a.tiles_per_row, a.tile_pixels);
-    else
-        hipLaunchKernelGGL(k_channel_sem<false>, dim3(grid), dim3(256), 0, st, (const double2*)ctx->accum_chm.p, (const uint32_t*)nullptr,
-                           (float*)ctx->accum_chsem.p, a.nx, a.rows, a.done, a.tiles_per_row, a.tile_pixels);
+    const AccumReader r = accum_reader(ctx, st);
+    ACCUM_READER(k_channel_sem, r, ctx->accum_chm.as<const double2>(), r.cnt, ctx->accum_chsem.as<float>(), r.nx, r.rows, r.n, r.tiles_per_row, r.tile_pixels);
     RT_HIP(ctx, hipGetLastError());
     RT_HIP(ctx, hipMemcpyAsync(out_sem_rgb, ctx->accum_chsem.p, bytes, hipMemcpyDeviceToHost, st));
     RT_HIP(ctx, hipStreamSynchronize(st));
@@ -1773,34 +1782,20 @@ static int ensure_denoise_channels(RtCtx* ctx, size_t npix) {
 int rt_accum_denoise_channels(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8) {
     if (!ctx) return RT_ERR_INVALID;
     const RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_channels: no accumulation begun (or it was ended: rtow_mi355x.h)");
-    if (!a.channels) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_channels: the accumulation does not track channels (rt_accum_track_channels)");
     RtDenoise d;
-    int rc = denoise_params(ctx, dn, d, "rt_accum_denoise_channels");
+    int rc = denoise_begin(ctx, "rt_accum_denoise_channels", dn, d, RT_DENOISE_DEFAULT_STRENGTH,
+                           a.channels ? nullptr : "the accumulation does not track channels (rt_accum_track_channels)", 2u, "there is no variance yet");
     if (rc) return rc;
-    if (a.prm.shard_count > 1u)
-        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_denoise_channels: a sharded frame (shard_count > 1): the local rows of a shard are not neighbours in the image");
-    if (a.done < 2u) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_channels: fewer than 2 samples accumulated: there is no variance yet");
     if (a.npix == 0u) return RT_OK;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
-    const uint32_t npix = a.npix, grid = (npix + 255u) / 256u;
-    const size_t n = (size_t)npix * 3;
-    if ((rc = ensure_denoise_channels(ctx, npix))) return rc;
-    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
-    if (a.adaptive) // (every n_p >= 2, as in rt_accum_denoise)
-        hipLaunchKernelGGL(k_denoise_inputs_channels<true>, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, (const double2*)ctx->accum_chm.p,
-                           (const uint32_t*)ctx->accum_cnt.p, (float2*)ctx->dn_cv.p, a.nx, a.rows, 0u, a.tiles_per_row, a.tile_pixels);
-    else
-        hipLaunchKernelGGL(k_denoise_inputs_channels<false>, dim3(grid), dim3(256), 0, st, (const float*)ctx->accum_sum.p, (const double2*)ctx->accum_chm.p,
-                           (const uint32_t*)nullptr, (float2*)ctx->dn_cv.p, a.nx, a.rows, a.done, a.tiles_per_row, a.tile_pixels);
-    launch_denoise_channels(st, (const float2*)ctx->dn_cv.p, (float*)ctx->dn_out.p, a.nx, a.rows, d);
-    if (out_rgb8) // k_finalize's quantisation and flip of the filtered image, as in rt_accum_denoise
-        hipLaunchKernelGGL(k_finalize, dim3(grid), dim3(256), 0, st, (const float*)ctx->dn_out.p, (float*)nullptr, (uint8_t*)ctx->out_u8.p, a.nx, a.rows, 1u, 0u,
-                           0u);
-    RT_HIP(ctx, hipGetLastError());
-    if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->dn_out.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (out_rgb8) RT_HIP(ctx, hipMemcpyAsync(out_rgb8, ctx->out_u8.p, n, hipMemcpyDeviceToHost, st));
+    if ((rc = ensure_denoise_channels(ctx, a.npix))) return rc;
+    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, (size_t)a.npix * 3))) return rc;
+    const AccumReader r = accum_reader(ctx, st);
+    ACCUM_READER(k_denoise_inputs_channels, r, ctx->accum_sum.as<const float>(), ctx->accum_chm.as<const double2>(), r.cnt, ctx->dn_cv.as<float2>(), r.nx, r.rows, r.n,
+                 r.tiles_per_row, r.tile_pixels);
+    launch_denoise_channels(st, ctx->dn_cv.as<const float2>(), ctx->dn_out.as<float>(), a.nx, a.rows, d);
+    if ((rc = denoise_finish(ctx, ctx->dn_out.as<const float>(), out_rgb_f32, out_rgb8))) return rc;
     RT_HIP(ctx, hipStreamSynchronize(st));
     return RT_OK;
 }
@@ -1867,7 +1862,7 @@ int rt_accum_export(RtCtx* ctx, RtAccumState* st) {
     if (!ctx) return RT_ERR_INVALID;
     const RtCtx::Accum& a = ctx->accum;
     if (!st) return fail(ctx, RT_ERR_INVALID, "rt_accum_export: the RtAccumState is NULL");
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_export: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (const int rc = require_open(ctx, "rt_accum_export")) return rc;
     if (st->channel_moments && !a.channels)
         return fail(ctx, RT_ERR_STATE, "rt_accum_export: channel_moments asked of an accumulation that does not track channels (rt_accum_track_channels)");
     const uint32_t npix = a.npix;
@@ -1906,7 +1901,7 @@ int rt_accum_export(RtCtx* ctx, RtAccumState* st) {
 int rt_accum_import(RtCtx* ctx, const RtAccumState* st) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_import: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (const int rc = require_open(ctx, "rt_accum_import")) return rc;
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks halves already (import the state first, then rt_accum_import_halves)");
     if (a.done != 0u || a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_import: samples were added already (call it right after rt_accum_begin)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import: ") + why);
@@ -1921,13 +1916,8 @@ int rt_accum_import(RtCtx* ctx, const RtAccumState* st) {
         const uint32_t nb = (npix + 255u) / 256u;
         int rc;
         // every allocation first: a failure below this block cannot leave the accumulation half imported
-        if (channels && (rc = ensure(ctx, ctx->accum_chm, (size_t)npix * 3 * sizeof(double2)))) return rc; // (as rt_accum_track_channels)
-        if (counts) { // (as the first adaptive add)
-            if ((rc = ensure(ctx, ctx->accum_cnt, (size_t)npix * sizeof(uint32_t)))) return rc;
-            if ((rc = ensure(ctx, ctx->accum_flag, (size_t)npix))) return rc;
-            if ((rc = ensure(ctx, ctx->accum_info, ((size_t)nb + 1u) * sizeof(AdaptiveSums)))) return rc;
-            if (!ctx->h_info) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_info, sizeof(RtAdaptiveInfo), hipHostMallocDefault));
-        }
+        if (channels && (rc = ensure_channels(ctx, npix))) return rc;
+        if (counts && (rc = ensure_adaptive(ctx, npix))) return rc;
         StagedPlanes s;
         if ((rc = stage_planes(ctx, npix, st->planes, s))) return rc;
         if ((rc = upload_state(ctx, *st, s, npix, s_))) return rc;
@@ -1949,7 +1939,7 @@ int rt_accum_import(RtCtx* ctx, const RtAccumState* st) {
 int rt_accum_merge(RtCtx* ctx, const RtAccumState* st) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_merge: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (const int rc = require_open(ctx, "rt_accum_merge")) return rc;
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks halves: a merge of halves is not covered (rtow_mi355x.h)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_merge: ") + why);
     if (a.adaptive || (st->planes & RT_ACCUM_STATE_COUNTS))
@@ -1990,7 +1980,7 @@ static int ensure_halves(RtCtx* ctx, uint32_t npix) { return ensure(ctx, ctx->ac
 int rt_accum_track_halves(RtCtx* ctx) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_track_halves: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (const int rc = require_open(ctx, "rt_accum_track_halves")) return rc;
     if (a.halves) return RT_OK;
     if (a.done != 0u || a.adaptive || a.added)
         return fail(ctx, RT_ERR_STATE, "rt_accum_track_halves: the accumulation holds samples already (call it right after rt_accum_begin; after rt_accum_import "
@@ -2007,23 +1997,19 @@ int rt_accum_track_halves(RtCtx* ctx) {
 int rt_accum_read_halves(RtCtx* ctx, uint32_t h, float* out_rgb_f32, float* out_sem) {
     if (!ctx) return RT_ERR_INVALID;
     const RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_read_halves: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (const int rc = require_open(ctx, "rt_accum_read_halves")) return rc;
     if (!a.halves) return fail(ctx, RT_ERR_STATE, "rt_accum_read_halves: the accumulation does not track halves (rt_accum_track_halves)");
     if (h > 1u) return fail(ctx, RT_ERR_INVALID, "rt_accum_read_halves: h must be 0 or 1");
     if (a.npix == 0u || (!out_rgb_f32 && !out_sem)) return RT_OK;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
-    const uint32_t npix = a.npix, grid = (npix + 255u) / 256u;
+    const uint32_t npix = a.npix;
     if (const int rc = ensure(ctx, ctx->halves_stage, halves_layout(npix).total)) return rc;
-    float* d_rgb = (float*)ctx->halves_stage.p; // (staging: 12 B + 4 B of the 56 B per pixel a state of halves takes there)
+    float* d_rgb = ctx->halves_stage.as<float>(); // (staging: 12 B + 4 B of the 56 B per pixel a state of halves takes there)
     float* d_sem = d_rgb + 3 * (size_t)npix;
     const HalfPlanes hp = half_planes(ctx->accum_halves, npix);
-    if (a.adaptive)
-        hipLaunchKernelGGL(k_halves_read<true>, dim3(grid), dim3(256), 0, st, hp, (const uint32_t*)ctx->accum_cnt.p, h, out_rgb_f32 ? d_rgb : (float*)nullptr,
-                           out_sem ? d_sem : (float*)nullptr, a.nx, a.rows, a.first, 0u, a.tiles_per_row, a.tile_pixels);
-    else
-        hipLaunchKernelGGL(k_halves_read<false>, dim3(grid), dim3(256), 0, st, hp, (const uint32_t*)nullptr, h, out_rgb_f32 ? d_rgb : (float*)nullptr,
-                           out_sem ? d_sem : (float*)nullptr, a.nx, a.rows, a.first, a.done, a.tiles_per_row, a.tile_pixels);
+    const AccumReader r = accum_reader(ctx, st);
+    ACCUM_READER(k_halves_read, r, hp, r.cnt, h, out_rgb_f32 ? d_rgb : nullptr, out_sem ? d_sem : nullptr, r.nx, r.rows, a.first, r.n, r.tiles_per_row, r.tile_pixels);
     RT_HIP(ctx, hipGetLastError());
     if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, d_rgb, (size_t)npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
     if (out_sem) RT_HIP(ctx, hipMemcpyAsync(out_sem, d_sem, (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -2034,14 +2020,10 @@ int rt_accum_read_halves(RtCtx* ctx, uint32_t h, float* out_rgb_f32, float* out_
 int rt_accum_denoise_halves(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8, float* out_err, RtResidual* res) {
     if (!ctx) return RT_ERR_INVALID;
     const RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_halves: no accumulation begun (or it was ended: rtow_mi355x.h)");
-    if (!a.halves) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_halves: the accumulation does not track halves (rt_accum_track_halves)");
     RtDenoise d;
-    int rc = denoise_params(ctx, dn, d, "rt_accum_denoise_halves", RT_DENOISE_HALVES_DEFAULT_STRENGTH);
+    int rc = denoise_begin(ctx, "rt_accum_denoise_halves", dn, d, RT_DENOISE_HALVES_DEFAULT_STRENGTH,
+                           a.halves ? nullptr : "the accumulation does not track halves (rt_accum_track_halves)", 4u, "a half has no variance yet");
     if (rc) return rc;
-    if (a.prm.shard_count > 1u)
-        return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_denoise_halves: a sharded frame (shard_count > 1): the local rows of a shard are not neighbours in the image");
-    if (a.done < 4u) return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_halves: fewer than 4 samples accumulated: a half has no variance yet");
     if (res) std::memset(res, 0, sizeof(*res));
     if (a.npix == 0u) return RT_OK;
     RT_HIP(ctx, hipSetDevice(ctx->device));
@@ -2054,33 +2036,21 @@ int rt_accum_denoise_halves(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32,
     if ((rc = ensure(ctx, ctx->dn_halves, part_bytes + (size_t)npix * (sizeof(float2) + 10 * sizeof(float))))) return rc;
     if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
     if (!ctx->h_resid) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_resid, 3 * sizeof(double), hipHostMallocDefault));
-    double2* partials = (double2*)ctx->dn_halves.p;
+    double2* partials = ctx->dn_halves.as<double2>();
     double* figures = (double*)(partials + nb);
-    float2* yv1 = (float2*)((char*)ctx->dn_halves.p + part_bytes);
+    float2* yv1 = (float2*)(ctx->dn_halves.as<char>() + part_bytes);
     float* c1 = (float*)(yv1 + npix);
     float *f1 = c1 + n, *out = f1 + n, *err = out + n;
-    float *c0 = (float*)ctx->dn_c.p, *f0 = (float*)ctx->dn_out.p;
-    float2* yv0 = (float2*)ctx->dn_yv.p;
+    float *c0 = ctx->dn_c.as<float>(), *f0 = ctx->dn_out.as<float>();
+    float2* yv0 = ctx->dn_yv.as<float2>();
     const HalfPlanes hp = half_planes(ctx->accum_halves, npix);
-    const uint32_t* cnt = a.adaptive ? (const uint32_t*)ctx->accum_cnt.p : (const uint32_t*)nullptr;
-    if (a.adaptive)
-        hipLaunchKernelGGL(k_denoise_inputs_halves<true>, dim3(nb), dim3(256), 0, st, hp, cnt, c0, c1, yv0, yv1, a.nx, a.rows, a.first, 0u, a.tiles_per_row, a.tile_pixels);
-    else
-        hipLaunchKernelGGL(k_denoise_inputs_halves<false>, dim3(nb), dim3(256), 0, st, hp, cnt, c0, c1, yv0, yv1, a.nx, a.rows, a.first, a.done, a.tiles_per_row, a.tile_pixels);
+    const AccumReader r = accum_reader(ctx, st);
+    ACCUM_READER(k_denoise_inputs_halves, r, hp, r.cnt, c0, c1, yv0, yv1, r.nx, r.rows, a.first, r.n, r.tiles_per_row, r.tile_pixels);
     launch_denoise(st, c0, yv1, f0, a.nx, a.rows, d); // each half by the other's guide
     launch_denoise(st, c1, yv0, f1, a.nx, a.rows, d);
-    if (a.adaptive)
-        hipLaunchKernelGGL(k_halves_combine<true>, dim3(nb), dim3(256), 0, st, (const float*)f0, (const float*)f1, cnt, out, err, partials, a.nx, a.rows, a.first, 0u,
-                           a.tiles_per_row, a.tile_pixels);
-    else
-        hipLaunchKernelGGL(k_halves_combine<false>, dim3(nb), dim3(256), 0, st, (const float*)f0, (const float*)f1, cnt, out, err, partials, a.nx, a.rows, a.first, a.done,
-                           a.tiles_per_row, a.tile_pixels);
+    ACCUM_READER(k_halves_combine, r, (const float*)f0, (const float*)f1, r.cnt, out, err, partials, r.nx, r.rows, a.first, r.n, r.tiles_per_row, r.tile_pixels);
     hipLaunchKernelGGL(k_halves_final, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, npix, figures);
-    if (out_rgb8) // k_finalize's quantisation and flip of the filtered image, as in rt_accum_denoise
-        hipLaunchKernelGGL(k_finalize, dim3(nb), dim3(256), 0, st, (const float*)out, (float*)nullptr, (uint8_t*)ctx->out_u8.p, a.nx, a.rows, 1u, 0u, 0u);
-    RT_HIP(ctx, hipGetLastError());
-    if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, out, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (out_rgb8) RT_HIP(ctx, hipMemcpyAsync(out_rgb8, ctx->out_u8.p, n, hipMemcpyDeviceToHost, st));
+    if ((rc = denoise_finish(ctx, out, out_rgb_f32, out_rgb8))) return rc;
     if (out_err) RT_HIP(ctx, hipMemcpyAsync(out_err, err, (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, st));
     RT_HIP(ctx, hipMemcpyAsync(ctx->h_resid, figures, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     RT_HIP(ctx, hipStreamSynchronize(st));
@@ -2092,7 +2062,7 @@ int rt_accum_export_halves(RtCtx* ctx, RtAccumHalves* hs) {
     if (!ctx) return RT_ERR_INVALID;
     const RtCtx::Accum& a = ctx->accum;
     if (!hs) return fail(ctx, RT_ERR_INVALID, "rt_accum_export_halves: the RtAccumHalves is NULL");
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_export_halves: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (const int rc = require_open(ctx, "rt_accum_export_halves")) return rc;
     if (!a.halves) return fail(ctx, RT_ERR_STATE, "rt_accum_export_halves: the accumulation does not track halves (rt_accum_track_halves)");
     const uint32_t npix = a.npix;
     if (npix && (hs->sum[0] || hs->sum[1] || hs->moments[0] || hs->moments[1])) {
@@ -2118,7 +2088,7 @@ int rt_accum_export_halves(RtCtx* ctx, RtAccumHalves* hs) {
 int rt_accum_import_halves(RtCtx* ctx, const RtAccumHalves* hs) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
-    if (!a.open) return fail(ctx, RT_ERR_STATE, "rt_accum_import_halves: no accumulation begun (or it was ended: rtow_mi355x.h)");
+    if (const int rc = require_open(ctx, "rt_accum_import_halves")) return rc;
     if (a.added) return fail(ctx, RT_ERR_STATE, "rt_accum_import_halves: samples were added since rt_accum_begin (call it right after rt_accum_begin or rt_accum_import)");
     if (const char* why = accum_halves_invalid(hs)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import_halves: ") + why);
     if (hs->nx != a.nx || hs->rows != a.rows) return fail(ctx, RT_ERR_INVALID, "rt_accum_import_halves: nx and rows of the halves are not the accumulation's");

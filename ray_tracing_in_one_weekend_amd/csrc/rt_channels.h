@@ -1,7 +1,7 @@
 // rt_channels.h — per-channel moments of an accumulation and the colour-guided filter (rtow_mi355x.h "Channel moments and the
 // colour-guided filter"): new kernels only; no kernel of rt_kernels.h, rt_adaptive.h or rt_denoise.h changes.
 //
-//   k_resolve_moments_channels<ACTIVE> : k_resolve_moments (ACTIVE: k_resolve_moments_active) plus S1_c += x_c, S2_c += x_c x_c per channel
+//   k_resolve_moments_channels<ACTIVE> : k_resolve_moments<ACTIVE> plus S1_c += x_c, S2_c += x_c x_c per channel
 //   k_channel_sem<COUNTS>              : (float)sqrt(V_c) per pixel and channel, in image order
 //   k_denoise_inputs_channels<COUNTS>  : (c_ch, v_ch) per pixel and channel, in image order
 //   k_denoise_channels<F>              : the filter; k_denoise<F> with three (c, v) planes in LDS and the channel-summed term in the map

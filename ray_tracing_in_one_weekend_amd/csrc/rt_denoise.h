@@ -1,7 +1,7 @@
 // rt_denoise.h — the variance-guided non-local-means filter of rt_accum_denoise (rtow_mi355x.h "Denoising"): image space, new kernels
 // only, fed by what an accumulation already owns (the running f32 sum and the two f64 luminance moments per pixel).
 //
-//   k_denoise_inputs : c = sum / (float)n, y = (float)Ybar, v = (float)V per pixel, in image order
+//   k_denoise_inputs<COUNTS> : c = sum / (float)n, y = (float)Ybar, v = (float)V per pixel, in image order (COUNTS: n = the pixel's n_p)
 //   k_denoise<F>     : the filter; one thread per pixel, the (y, v) tile of a workgroup and its halo in LDS, the distance terms that the
 //                      patches of neighbouring pixels share evaluated once per workgroup
 //
@@ -19,17 +19,23 @@ constexpr uint32_t RT_DN_TILE = 16u; // a workgroup filters 16 x 16 pixels: 256 
 constexpr uint32_t RT_DN_PITCH = 48u;
 
 // The filter's inputs of one accumulation after n samples, in image order (p = row * nx + column, row 0 at the bottom).
-__global__ __launch_bounds__(256) void k_denoise_inputs(const float* __restrict__ sum, const double2* __restrict__ mom, float* __restrict__ c,
-                                                        float2* __restrict__ yv, uint32_t nx, uint32_t rows, uint32_t n, uint32_t tiles_per_row,
-                                                        uint32_t tile_pixels) {
+// COUNTS: with the pixel's own n_p (`n` is not used; otherwise `cnt` is not read).  There a pixel with n_p < 2 has no variance (only an
+// imported state holds one beside done >= 2: rt_accum_state_check accepts a converged pixel with any counts[p] <= done): its c is what
+// rt_accum_read returns, sum / (float)max(n_p, 1), and its guide is NaN, so that it stays what it is and spreads to no other pixel.
+template <bool COUNTS>
+__global__ __launch_bounds__(256) void k_denoise_inputs(const float* __restrict__ sum, const double2* __restrict__ mom, const uint32_t* __restrict__ cnt,
+                                                        float* __restrict__ c, float2* __restrict__ yv, uint32_t nx, uint32_t rows, uint32_t n,
+                                                        uint32_t tiles_per_row, uint32_t tile_pixels) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= nx * rows) return;
     const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx);
-    const float fs = (float)n;
+    if (COUNTS) n = cnt[ap];
+    const float fs = (float)(COUNTS && n == 0u ? 1u : n);
     c[3 * (size_t)p] = sum[3 * ap] / fs, c[3 * (size_t)p + 1] = sum[3 * ap + 1] / fs, c[3 * (size_t)p + 2] = sum[3 * ap + 2] / fs;
     double ybar, v;
     pixel_noise(mom[ap], n, ybar, v);
-    yv[p] = make_float2((float)ybar, (float)v);
+    const float none = __uint_as_float(0x7FC00000u);
+    yv[p] = COUNTS && n < 2u ? make_float2(none, none) : make_float2((float)ybar, (float)v);
 }
 
 // d(a, b) of the header: a, b = (y, v) of two pixels

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void k_halves_read(HalfPlanes hp, const uint32
 }
 
 // The inputs of the two filter launches: per half c_h and (y_h, v_h) = ((float)Ybar_h, (float)V_h) with n = n_h, NaN where n_h < 2 as in
-// k_denoise_inputs_counts: such a half pixel guides nobody and, as a guide of the other half, makes that pixel keep its own colour.
+// k_denoise_inputs<true>: such a half pixel guides nobody and, as a guide of the other half, makes that pixel keep its own colour.
 template <bool COUNTS>
 __global__ __launch_bounds__(256) void k_denoise_inputs_halves(HalfPlanes hp, const uint32_t* __restrict__ cnt, float* __restrict__ c0, float* __restrict__ c1,
                                                                float2* __restrict__ yv0, float2* __restrict__ yv1, uint32_t nx, uint32_t rows,

@@ -11,7 +11,10 @@
 //   k_shade          : main.rs:45-58: emitted + scatter (material.rs, pbr.rs, texture.rs), sky on
 //                      a miss, radiance retirement, wave64 ballot compaction of the survivors
 //   k_resolve        : main.rs:95-98 sample sum in sample order
-//   k_finalize       : main.rs:98-105,127 /spp, gamma 2, *255.99 as u8, vertical flip
+//   k_finalize<COUNTS> : main.rs:98-105,127 /spp, gamma 2, *255.99 as u8, vertical flip (a frame: <false>)
+//   k_resolve_moments<ACTIVE>, k_sem<COUNTS>, k_noise_partials<COUNTS>, k_noise_final<COUNTS>:
+//                      an accumulation's moments and their readers (the end of this file); COUNTS and ACTIVE:
+//                      with the n_p, flags and counts of an adaptive accumulation (rt_adaptive.h)
 //
 // Ray queue layout in HBM (SoA, 40 B per ray: two 16 B arrays that k_intersect reads and an 8 B one that only
 // k_shade needs), plus an 8 B hit record per ray between the kernels:
@@ -28,6 +31,7 @@
 // (One device-scope atomic per wave on 32 shared counters cost 2x in k_shade: the waves sat in
 // s_waitcnt for the returned slot index, profiles/round1.)
 #pragma once
+#include "../../include/rtow_mi355x.h"
 #include "rt_device.h"
 
 namespace rt {
@@ -1678,13 +1682,17 @@ __global__ __launch_bounds__(256) void k_resolve(const float* __restrict__ rad, 
 
 // main.rs:98-105,127.  out_f32: linear mean (before gamma), local row order; out_u8: gamma 2,
 // *255.99 saturating cast, rows flipped.  sqrtf is the correctly rounded value of powf(x, 0.5).
-__global__ __launch_bounds__(256) void k_finalize(const float* __restrict__ acc, float* __restrict__ out_f32,
-                                                  uint8_t* __restrict__ out_u8, uint32_t nx, uint32_t rows, uint32_t spp,
+// COUNTS (an adaptive accumulation): sum / (float)n_p of the pixel's own count (n_p 0, before the first sample: / 1, the sums are zeros),
+// and `n` is not used; otherwise sum / (float)n as passed, and `cnt` is not read.
+template <bool COUNTS>
+__global__ __launch_bounds__(256) void k_finalize(const float* __restrict__ acc, const uint32_t* __restrict__ cnt, float* __restrict__ out_f32,
+                                                  uint8_t* __restrict__ out_u8, uint32_t nx, uint32_t rows, uint32_t n,
                                                   uint32_t tiles_per_row, uint32_t tile_pixels) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x; // output pixel, row-major in the shard's local rows
     if (p >= nx * rows) return;
-    const float fs = (float)spp;
     const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx); // where the path slots keep this pixel (GenParams)
+    if (COUNTS) n = cnt[ap] ? cnt[ap] : 1u;
+    const float fs = (float)n;
     float c[3] = {acc[3 * ap] / fs, acc[3 * ap + 1] / fs, acc[3 * ap + 2] / fs};
     if (out_f32) {
         out_f32[3 * (size_t)p] = c[0], out_f32[3 * (size_t)p + 1] = c[1], out_f32[3 * (size_t)p + 2] = c[2];
@@ -1830,10 +1838,15 @@ __device__ __forceinline__ double sample_luminance(float r, float g, float b) {
 }
 // k_resolve — the same loads, the same loop order, the same f32 sums — plus S1 += Y and S2 += Y Y per sample.  A lane reads 12 B at
 // stride 12 B like k_resolve (a wave: 768 contiguous bytes per sample); the two f64 chains are 2 adds and 4 multiplies per 12 B read.
+// ACTIVE (an adaptive add): for the pixels still active, and n_p += s_count; a converged pixel touches neither its radiance slots (nothing
+// wrote them) nor its sums.  Otherwise `flag` and `cnt` are not read.
+template <bool ACTIVE>
 __global__ __launch_bounds__(256) void k_resolve_moments(const float* __restrict__ rad, float* __restrict__ acc, double2* __restrict__ mom,
-                                                         uint32_t npix, uint32_t s_count) {
+                                                         const uint8_t* __restrict__ flag, uint32_t* __restrict__ cnt, uint32_t npix,
+                                                         uint32_t s_count) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= npix) return;
+    if (ACTIVE && flag[p] != 0u) return;
     float r = acc[3 * (size_t)p], g = acc[3 * (size_t)p + 1], b = acc[3 * (size_t)p + 2];
     double2 m = mom[p];
     for (uint32_t s = 0; s < s_count; ++s) {
@@ -1848,6 +1861,7 @@ __global__ __launch_bounds__(256) void k_resolve_moments(const float* __restrict
     }
     acc[3 * (size_t)p] = r, acc[3 * (size_t)p + 1] = g, acc[3 * (size_t)p + 2] = b;
     mom[p] = m;
+    if (ACTIVE) cnt[p] += s_count;
 }
 
 // Mean luminance and variance of the mean of one pixel after n samples (rtow_mi355x.h "Moments"); n < 2: no variance estimate, 0.
@@ -1860,15 +1874,24 @@ __device__ __forceinline__ void pixel_noise(double2 m, uint32_t n, double& ybar,
         v = (q < 0.0 ? 0.0 : q) / dn; // (a NaN stays one)
     }
 }
-// out_sem in output pixel order, as k_finalize maps it.
-__global__ __launch_bounds__(256) void k_sem(const double2* __restrict__ mom, float* __restrict__ out_sem, uint32_t nx, uint32_t rows,
-                                             uint32_t n, uint32_t tiles_per_row, uint32_t tile_pixels) {
+// The readers below come as <COUNTS>: true reads the pixel's own n_p from `cnt` (an adaptive accumulation) and never uses `n`; false uses
+// the one `n` and never reads `cnt`.  So the host passes both to either (rt_api.hip: ACCUM_READER).
+//
+// out_sem and, on request, the sample counts (COUNTS; rt_accum_read_counts), both in output pixel order, as k_finalize maps it.  Either may be NULL.
+template <bool COUNTS>
+__global__ __launch_bounds__(256) void k_sem(const double2* __restrict__ mom, const uint32_t* __restrict__ cnt, float* __restrict__ out_sem,
+                                             uint32_t* __restrict__ out_cnt, uint32_t nx, uint32_t rows, uint32_t n, uint32_t tiles_per_row,
+                                             uint32_t tile_pixels) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= nx * rows) return;
     const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx);
-    double ybar, v;
-    pixel_noise(mom[ap], n, ybar, v);
-    out_sem[p] = (float)sqrt(v);
+    if (COUNTS) n = cnt[ap];
+    if (out_sem) {
+        double ybar, v;
+        pixel_noise(mom[ap], n, ybar, v);
+        out_sem[p] = (float)sqrt(v);
+    }
+    if (out_cnt) out_cnt[p] = n;
 }
 // Frame figures, a fixed tree and no atomics: per workgroup (sum Ybar, sum V) of its 256 pixels — lanes by __shfl_down, the four waves
 // through LDS in wave order — then ONE workgroup over the partials, thread t taking partials t, t + 256, ... in index order and the same
@@ -1882,17 +1905,28 @@ __device__ __forceinline__ double2 block_sum_256(double a, double b, double2* pa
     __syncthreads();
     return make_double2(((part[0].x + part[1].x) + part[2].x) + part[3].x, ((part[0].y + part[1].y) + part[2].y) + part[3].y);
 }
-__global__ __launch_bounds__(256) void k_noise_partials(const double2* __restrict__ mom, double2* __restrict__ partials, uint32_t npix, uint32_t n) {
+template <bool COUNTS>
+__global__ __launch_bounds__(256) void k_noise_partials(const double2* __restrict__ mom, const uint32_t* __restrict__ cnt, double2* __restrict__ partials,
+                                                        uint32_t npix, uint32_t n) {
     __shared__ double2 part[4];
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     double ybar = 0.0, v = 0.0; // (tail slots contribute nothing)
-    if (p < npix) pixel_noise(mom[p], n, ybar, v);
+    if (p < npix) pixel_noise(mom[p], COUNTS ? cnt[p] : n, ybar, v);
     const double2 s = block_sum_256(ybar, v, part);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
-// out[0] = mean_luminance, out[1] = rms_sem, out[2] = noise (RtNoise)
-__global__ __launch_bounds__(256) void k_noise_final(const double2* __restrict__ partials, uint32_t n_partials, uint32_t npix, uint32_t n,
-                                                     double* __restrict__ out) {
+// Integer partial sums of one workgroup of an adaptive accumulation, and of the frame (rt_adaptive.h: k_adaptive_info writes the frame's as an
+// RtAdaptiveInfo: the same layout).
+struct AdaptiveSums {
+    unsigned long long n_active, n_samples;
+    uint32_t spp_min, spp_max;
+};
+static_assert(sizeof(AdaptiveSums) == sizeof(RtAdaptiveInfo) && sizeof(AdaptiveSums) == 24u, "AdaptiveSums is RtAdaptiveInfo");
+// out[0] = mean_luminance, out[1] = rms_sem, out[2] = noise (RtNoise); the noise is +inf below two samples: n, or under COUNTS where any pixel
+// has fewer (info->spp_min, of k_adaptive_info just before; `info` is not read otherwise)
+template <bool COUNTS>
+__global__ __launch_bounds__(256) void k_noise_final(const double2* __restrict__ partials, uint32_t n_partials, uint32_t npix,
+                                                     const AdaptiveSums* __restrict__ info, uint32_t n, double* __restrict__ out) {
     __shared__ double2 part[4];
     double a = 0.0, b = 0.0;
     for (uint32_t k = threadIdx.x; k < n_partials; k += 256u) a += partials[k].x, b += partials[k].y;
@@ -1901,7 +1935,7 @@ __global__ __launch_bounds__(256) void k_noise_final(const double2* __restrict__
     const double mean = s.x / (double)npix, rms = sqrt(s.y / (double)npix);
     double noise = rms / mean;
     if (mean == 0.0) noise = rms == 0.0 ? 0.0 : (double)INFINITY;
-    if (n < 2u) noise = (double)INFINITY;
+    if ((COUNTS ? info->spp_min : n) < 2u) noise = (double)INFINITY;
     out[0] = mean, out[1] = rms, out[2] = noise;
 }
 

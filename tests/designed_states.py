@@ -210,7 +210,7 @@ def variance_before_clamp(s1, s2, n):
 
 
 def denoise_inputs(st):
-    """(c, y, v) f32 as k_denoise_inputs(_counts) forms them: c = sum / (float)n_p, y = (float)Ybar, v = (float)V; a pixel with n_p < 2:
+    """(c, y, v) f32 as k_denoise_inputs<COUNTS> forms them: c = sum / (float)n_p, y = (float)Ybar, v = (float)V; a pixel with n_p < 2:
     c = sum / (float)max(n_p, 1), y = v = NaN."""
     ybar, v = figures(st)
     n = pixel_counts(st)

@@ -130,3 +130,16 @@ def primary_rays(scene, p, pix_i, pix_j, samp):
     inv = (f(1.0) / np.sqrt(len2).astype(f)).astype(f)
     dirs = (dirs * inv[:, None]).astype(f)
     return np.tile(org, (len(u), 1)).astype(f), dirs, keys
+
+
+STATS_COUNTERS = ("n_paths", "n_rays", "n_rays_secondary", "n_texture_fetches", "n_bad_dir", "n_slices", "n_trace_launches")
+
+
+def stats_are_the_sum(total, adds, what):
+    """The RtStats a render loop returns against those of the same adds made by hand: every counter and every depth is their sum; the
+    times are only required to be times."""
+    for k in STATS_COUNTERS:
+        assert getattr(total, k) == sum(getattr(s, k) for s in adds), (what, k, getattr(total, k), [getattr(s, k) for s in adds])
+    assert list(total.rays_per_depth) == [sum(s.rays_per_depth[d] for s in adds) for d in range(64)], (what, "rays_per_depth")
+    for k in ("seconds_total", "seconds_trace", "seconds_device"):
+        assert np.isfinite(getattr(total, k)) and getattr(total, k) >= 0.0, (what, k, getattr(total, k))

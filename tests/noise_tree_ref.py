@@ -1,5 +1,5 @@
 """The frame figures of an accumulation (rtow_mi355x.h "Frame figures") by the very tree the kernels add over, so that they can be held
-bit for bit: block_sum_256 of csrc/rt_kernels.h, k_noise_partials(_counts), k_noise_final(_counts), and the integer sums of
+bit for bit: block_sum_256 of csrc/rt_kernels.h, k_noise_partials<COUNTS>, k_noise_final<COUNTS>, and the integer sums of
 adaptive_block_sums, k_adaptive_decide and k_adaptive_info (csrc/rt_adaptive.h), restated in numpy f64 — every addition one IEEE
 addition, in the kernel's order.
 
@@ -74,7 +74,7 @@ def tree_sum(local, tail=True):
 
 
 def figures(ybar_local, v_local, spp_min, tail=True):
-    """(mean_luminance, rms_sem, noise) as k_noise_final / k_noise_final_counts write them; spp_min: `done` of a uniform accumulation."""
+    """(mean_luminance, rms_sem, noise) as k_noise_final<false> / k_noise_final<true> write them; spp_min: `done` of a uniform accumulation."""
     npix = np.float64(ybar_local.size)
     with np.errstate(all="ignore"):
         mean = np.float64(tree_sum(ybar_local, tail)) / npix

@@ -5,6 +5,7 @@ accumulation itself delivers through first_sample.  The frames are the smallest 
 import numpy as np
 import pytest
 
+import helpers
 import noise_ref
 
 pytestmark = pytest.mark.gpu
@@ -159,6 +160,20 @@ def test_noise_falls_and_the_stopping_rule(rt, ctx):
     _same(img, r.render(scene.camera, prm(4))[0], "render_to_noise, target inf")
     # a maximum that is no multiple of the step: the last add takes what is left
     assert r.render_to_noise(scene.camera, prm(10), 0.0, 4)[3].spp_done == 10
+
+
+def test_render_to_noise_sums_the_statistics_of_its_adds(rt, ctx):
+    """10 samples at the most in steps of 4, target 0: the adds are 4, 4 and 2, the last one short."""
+    r = ctx
+    scene, prm = _setup(rt, r, "B")
+    r.accum_begin(scene.camera, prm(4))
+    adds = [r.accum_add(n) for n in (4, 4, 2)]
+    by_hand = r.accum_read()[0]
+    r.accum_end()
+    img, _, _, noise, total = r.render_to_noise(scene.camera, prm(10), 0.0, 4)
+    assert noise.spp_done == 10 and total.n_paths == 24 * 16 * 10 and total.n_slices == sum(s.n_slices for s in adds) >= 3
+    _same(img, by_hand, "render_to_noise against the same adds by hand")
+    helpers.stats_are_the_sum(total, adds, "render_to_noise")
 
 
 @pytest.mark.parametrize("case", ["A", "B"])

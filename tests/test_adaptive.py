@@ -14,6 +14,7 @@ import pytest
 
 import adaptive_ref
 import denoise_ref
+import helpers
 import noise_ref
 
 pytestmark = pytest.mark.gpu
@@ -321,6 +322,22 @@ def test_render_adaptive_equals_the_manual_loop(rt, ctx, case):
     assert got[6].n_paths == rp.cnt.size * 12
 
 
+def test_render_adaptive_sums_the_statistics_of_its_adds(rt, ctx):
+    """22 samples at the most in steps of 5: the adds are 5, 5, 5, 5 and 2, the last one short, each on the pixels still active."""
+    r = ctx
+    scene, prm = _setup(rt, r, "tree")
+    tol = _tolerance(_singles(r, scene, prm, "tree"))
+    r.accum_begin(scene.camera, prm(5))
+    adds = [r.accum_add_adaptive(n, tol, FLOOR, MIN) for n in (5, 5, 5, 5, 2)]
+    counts = r.accum_counts()[0]
+    r.accum_end()
+    assert 0 < adds[-1].n_paths < adds[0].n_paths == counts.size * 5  # (some pixels stopped, some run to the maximum)
+    got = r.render_adaptive(scene.camera, prm(22), tol, 5, FLOOR, MIN)
+    total = got[6]
+    assert np.array_equal(got[3], counts) and total.n_paths == int(counts.sum())
+    helpers.stats_are_the_sum(total, adds, "render_adaptive")
+
+
 # ---- 6. state machine and errors ------------------------------------------------------------------------------------------------------------
 def test_state_and_arguments(rt, ctx):
     f = rt._ffi
@@ -328,6 +345,9 @@ def test_state_and_arguments(rt, ctx):
     bare = rt.Renderer(0)
     try:
         _raises(rt, f.ERR_STATE, bare.accum_add_adaptive, 1, 0.1)
+        # a NULL RtAdaptive: refused by the state first, under the adaptive add's own name (both adds share their host path)
+        assert bare._lib.rt_accum_add_adaptive(bare._ctx, 1, None, None) == -f.ERR_STATE
+        assert bare._lib.rt_last_error(bare._ctx).decode().startswith("rt_accum_add_adaptive: no accumulation begun")
         _raises(rt, f.ERR_STATE, bare.accum_counts)
         _raises(rt, f.ERR_STATE, bare.render_adaptive, _scenes_any(rt).camera, rt.make_params(24, 16, 4), 0.1, 2)  # no scene
     finally:
@@ -339,6 +359,8 @@ def test_state_and_arguments(rt, ctx):
     _raises(rt, f.ERR_STATE, r.accum_counts)
     # before the first adaptive add: the counts of a uniform accumulation
     r.accum_begin(scene.camera, prm(STEP))
+    assert r._lib.rt_accum_add_adaptive(r._ctx, 1, None, None) == -f.ERR_INVALID  # (not taken for a uniform add: nothing was added)
+    assert r._lib.rt_last_error(r._ctx).decode() == "rt_accum_add_adaptive: the RtAdaptive is NULL"
     counts, info = r.accum_counts()
     assert not counts.any() and (info.n_active, info.n_samples, info.spp_min, info.spp_max) == (counts.size, 0, 0, 0)
     r.accum_add(3)

@@ -1,5 +1,5 @@
-"""The read-out kernels of an accumulation on designed imported states (tests/designed_states.py): k_finalize(_counts), k_sem(_counts),
-k_noise_partials / k_noise_final and their _counts forms, k_adaptive_decide and k_adaptive_info, k_denoise_inputs(_counts),
+"""The read-out kernels of an accumulation on designed imported states (tests/designed_states.py): k_finalize<COUNTS>, k_sem<COUNTS>,
+k_noise_partials<COUNTS> / k_noise_final<COUNTS>, k_adaptive_decide and k_adaptive_info, k_denoise_inputs<COUNTS>,
 k_denoise_inputs_channels, k_channel_sem and, behind them, the two filters.  A state is built in numpy, imported right after
 rt_accum_begin and read; nothing is traced except in the decision test (one sample on 24 x 16).  The scene, test_sphere, is uploaded only
 so that rt_accum_begin succeeds.
@@ -179,7 +179,7 @@ def _finite_figures_are_the_tree(rt, r, cam, prm, fid, st, loc, what):
         assert abs(noise.rms_sem - rms) <= bound * rms, (what, limit, noise.rms_sem, rms)
 
 
-# ---- 1. a uniform state: k_finalize, k_sem, k_noise_partials, k_noise_final, k_denoise_inputs, k_channel_sem<false>, ... ------------------
+# ---- 1. a uniform state: the <false> forms of k_finalize, k_sem, k_noise_partials, k_noise_final, k_denoise_inputs, k_channel_sem, ... ----
 @pytest.mark.parametrize("channels", [False, True])
 @pytest.mark.parametrize("done", ds.UNIFORM_DONE)
 @pytest.mark.parametrize("nx,rows", SMALL_FRAMES)
@@ -194,7 +194,7 @@ def test_read_out_of_a_uniform_state(rt, ctx, nx, rows, done, channels):
     ctx.accum_end()
 
 
-# ---- 2. the same with counts: k_finalize_counts, k_sem_counts, k_noise_*_counts, k_denoise_inputs_counts, k_adaptive_decide<false> ------
+# ---- 2. the same with counts: the <true> forms of k_finalize, k_sem, k_noise_*, k_denoise_inputs, and k_adaptive_decide<false> ------------
 @pytest.mark.parametrize("channels", [False, True])
 @pytest.mark.parametrize("done", ds.COUNTS_DONE)
 @pytest.mark.parametrize("nx,rows", SMALL_FRAMES)
@@ -231,7 +231,7 @@ def test_noise_is_inf_exactly_when_a_pixel_holds_fewer_than_two_samples(rt, ctx,
     ctx.accum_end()
 
 
-# ---- 3. more than 256 partial sums: the second trip of k_noise_final, k_noise_final_counts and k_adaptive_info ----------------------------
+# ---- 3. more than 256 partial sums: the second trip of k_noise_final<false>, k_noise_final<true> and k_adaptive_info -----------------------
 @pytest.mark.parametrize("po", [1, 2])
 @pytest.mark.parametrize("nx,rows", BIG_FRAMES)
 def test_more_than_256_partial_sums(rt, ctx, nx, rows, po):
@@ -321,7 +321,7 @@ def test_the_decision_on_the_thresholds(rt, ctx, tolerance, min_samples):
 def test_a_pixel_that_stopped_on_fewer_than_two_samples_spreads_to_no_other(rt, ctx):
     """rt_accum_state_check accepts a converged pixel with counts 0 or 1 beside done = 8.  The header: rt_accum_read divides it by
     max(n_p, 1); rt_accum_denoise gives it that colour and a NaN guide, so it stays what it is and every other pixel stays finite.
-    (k_denoise_inputs_counts once formed sum / (float)0 beside the finite guide (0, 0): in this neighbourhood the reference with those
+    (k_denoise_inputs<true> once formed sum / (float)0 beside the finite guide (0, 0): in this neighbourhood the reference with those
     inputs returns inf in the 121 pixels of the search window — tests/test_designed_states_host.py.)"""
     nx, rows = SMALL_FRAMES[0]
     cam, prm, fid, loc = _begin(rt, ctx, nx, rows)
@@ -348,3 +348,56 @@ def test_a_pixel_that_stopped_on_fewer_than_two_samples_spreads_to_no_other(rt, 
     assert np.isfinite(got[~w["count 0"]]).all(), "a pixel without a sample spread through the colour-guided filter"
     _exports_what_was_imported(ctx, s, "stopped early")
     ctx.accum_end()
+
+
+# ---- 6. a uniform accumulation behind an adaptive one on the same context -----------------------------------------------------------------
+def _every_read_out(r):
+    """Every read-out of the open accumulation (channels and halves tracked, done >= 4), by name; arrays, and ctypes figures as their bytes."""
+    out = {}
+    out["read f32"], out["read rgb8"], out["read sem"], noise = r.accum_read(want_rgb8=True, want_sem=True)
+    out["counts"], info = r.accum_counts()
+    out["denoise f32"], out["denoise rgb8"] = r.accum_denoise(want_rgb8=True)
+    out["channel sem"] = r.accum_channel_sem()
+    out["denoise channels f32"], out["denoise channels rgb8"] = r.accum_denoise_channels(want_rgb8=True)
+    for h in (0, 1):
+        out[f"half {h} f32"], out[f"half {h} sem"] = r.accum_half(h, want_sem=True)
+    out["denoise halves f32"], out["denoise halves rgb8"], out["denoise halves err"], res = r.accum_denoise_halves(want_rgb8=True, want_err=True)
+    e = r.accum_export()
+    for name in ("sum", "moments", "counts", "converged", "channel_moments"):
+        out["export " + name] = getattr(e, name)
+    out["export scalars"] = np.array([e.nx, e.rows, e.first_sample, e.done, e.planes, e.frame_id], np.uint64)
+    for name, figures in (("noise", noise), ("info", info), ("residual", res)):
+        out[name] = np.frombuffer(bytes(figures), np.uint8)
+    return out
+
+
+def test_a_uniform_accumulation_never_reads_a_stale_count_plane(rt, ctx):
+    """The readers of a uniform accumulation are handed the context's count plane whatever it holds (K<false> does not read it).  Here it
+    holds the n_p of an ended adaptive accumulation of the same size, which differ from pixel to pixel; a fresh context has none at all.
+    Every read-out of the two is the same, byte for byte."""
+    nx, rows = SMALL_FRAMES[0]
+    cam, prm, fid, _ = _begin(rt, ctx, nx, rows)
+    st = ds.state(nx, rows, 24, counts=True, channels=True)
+    assert len(np.unique(st["counts"])) > 2
+    _import(rt, ctx, cam, prm, fid, st)
+    assert np.array_equal(ctx.accum_counts()[0], st["counts"])
+    ctx.accum_end()
+    fresh = rt.Renderer(0)
+    try:
+        fresh.upload(_scenes[nx, rows])
+        outs = []
+        for r in (ctx, fresh):
+            r.accum_begin(cam, prm)
+            r.accum_track_channels()
+            r.accum_track_halves()
+            r.accum_add(3)
+            r.accum_add(2)
+            outs.append(_every_read_out(r))
+            r.accum_end()
+    finally:
+        fresh.close()
+    stale, clean = outs
+    assert stale["export scalars"][3] == 5 and (stale["counts"] == 5).all() and not stale["export converged"].any()
+    assert stale.keys() == clean.keys()
+    for name in stale:
+        _same(stale[name], clean[name], name)

@@ -232,7 +232,7 @@ def test_the_finite_copies_have_figures_that_are_numbers(nx, rows, counts):
 
 
 def test_the_stopped_early_state_tells_a_finite_guide_from_a_nan_guide():
-    """With the inputs k_denoise_inputs_counts once formed — c = sum / (float)n_p, the guide of pixel_noise — the reference filter returns
+    """With the inputs k_denoise_inputs<true> once formed — c = sum / (float)n_p, the guide of pixel_noise — the reference filter returns
     a non-finite colour in the whole search window of the pixel without a sample; with the header's inputs every pixel is finite."""
     import denoise_ref
     st = ds.stopped_early_state(40, 20)
