@@ -735,7 +735,8 @@ int rt_accum_merge(RtCtx* ctx, const RtAccumState* st);
  *     1.0           0.1245                  0.0980                      0.031            0.121
  * A NON-FINITE SAMPLE lands in one half.  The other half's guide is finite there, so — unlike in "Denoising" — the half that holds it is
  * filtered with finite weights and carries the value to the pixels within R of it; out, e_p and the frame figures follow (NaN).  The
- * half guided by the bad one keeps it out.  A host that must contain such pixels reads the halves and masks them.
+ * half guided by the bad one keeps it out.  A host that must contain such pixels reads the halves and masks them, or tracks "Sample
+ * buckets" below, whose read-out keeps a non-finite sample inside its bucket.
  * Half guides are noisier than the whole pixel's, so the best strength is not that of "Denoising": RT_DENOISE_HALVES_DEFAULT_STRENGTH
  * is chosen by measurement on rendered frames (DESIGN.md "Half buffers").
  * State.  RtAccumHalves carries the four planes in the row order of out_rgb_f32, as RtAccumState carries the accumulation's.  Resume is
@@ -787,6 +788,111 @@ int rt_accum_export_halves(RtCtx* ctx, RtAccumHalves* hs);
  * Values are copied as bits.  RT_ERR_INVALID: rt_accum_halves_check fails, or nx, rows, frame_id, first_sample or done differ from the
  * accumulation's.  A failed call leaves the accumulation as it was.  Synchronises once. */
 int rt_accum_import_halves(RtCtx* ctx, const RtAccumHalves* hs);
+
+/* -- sample buckets: M sums per pixel by sample index, and the median-of-means read-out that tames a firefly --------------------------------
+ * Every read-out above is the plain mean sum / n, so one sample a thousand times brighter than its neighbours — a caustic path, a small
+ * emitter found by chance, a NaN out of a degenerate bounce — owns its pixel for thousands of further samples, and the variance-guided
+ * filters carry its colour to every pixel inside their window.  The standard remedy is the MEDIAN OF MEANS, here in the Gini-adaptive form
+ * of Buisine et al. 2021 (G-MoN): the samples of every pixel are kept in M buckets by sample index, the frame is read out as a trimmed mean
+ * of the sorted bucket means, and the trim follows from how unequal the bucket means are.
+ * Tracking.  An accumulation that TRACKS BUCKETS also keeps, per pixel and bucket b in [0, M), an f32 x 3 sum (no moments): 12 * M bytes
+ * per pixel more, in the local pixel order of the sums, allocated by rt_accum_track_buckets (or rt_accum_import_buckets) and kept for the
+ * next accumulation like the other accumulation buffers.  The sample with the ABSOLUTE index i = first_sample + k goes to bucket i % M,
+ * in sample order, with one IEEE f32 addition per channel (no FMA), across slices and adds, uniform or adaptive.  Of the n samples a pixel
+ * holds (n_p after adaptive adds), n_b = the number of i in [first_sample, first_sample + n) with i % M == b belong to bucket b, evaluated
+ * without wrap up to 2^32 - 1; n_b follows from (first_sample, n, M) and is stored nowhere.
+ * Defining property: bucket b of pixel p is, bit for bit, the in-order f32 sum of the pixel's samples with i % M == b, however adds and
+ * slices are cut, under every pixel order, on shards, and after adaptive adds with n = n_p.
+ * Everything an accumulation returned before — the images, sem, the frame figures, the counts, all three filters, the exported states,
+ * the launch ledger of an add — is unchanged in every bit with tracking on or off: the resolve kernels are the same ones, a kernel of its
+ * own reads the radiance of a slice once more for the buckets.
+ * The robust read-out.  Per pixel and per channel, every operation one IEEE f32 operation in this order:
+ *   1. For b = 0 .. M - 1 with n_b > 0:  m_b = sum_b / (float)n_b.  The finite ones (m_b - m_b == 0) are kept; K is their number,
+ *      x_0 <= .. <= x_{K-1} their ascending order.  Ties and +-0 may sort in any order: every sum below starts from +0, so no output bit
+ *      depends on it.  K == 0: out = NaN, t = 0.
+ *   2. s = 0; w = 0; for i = 0 .. K - 1:  s = s + x_i;  w = w + (float)(i + 1) * x_i.
+ *   3. The trim t per side.  RT_ROBUST_MEDIAN: t = (K - 1) / 2.  RT_ROBUST_TRIM: t = min(RtRobust.trim, (K - 1) / 2).  RT_ROBUST_GINI:
+ *      t = 0 when K < 2 or !(s > 0); else  G = (2.0f * w) / ((float)K * s) - ((float)(K + 1) / (float)K);
+ *      Gn = G * ((float)K / (float)(K - 1));  t = Gn > 0 ? min((uint32_t)((Gn * (float)K) * 0.5f), (K - 1) / 2) : 0.
+ *   4. a = 0; for i = t .. K - 1 - t:  a = a + x_i;  out = a / (float)(K - 2 * t);  out_trim = t.
+ * So bucket means that agree give the mean of means (Gn = 0), and bucket means dominated by one or two buckets give their median.  A NaN
+ * or inf sample stays inside its bucket and never reaches `out` while another bucket of the pixel is finite: the containment that "Half
+ * buffers" left to the host.  out_rgb8 is the quantisation of rt_accum_read applied to `out`.
+ * WHAT THE ESTIMATOR IS.  It is BIASED.  A trimmed mean removes energy that belongs to the integral — the bright tail of an honest
+ * pixel as well as a firefly — and RtRobustInfo.energy_removed says how much of the frame's luminance went.  It is not a denoiser: where
+ * EVERY pixel is heavy-tailed at a low sample count it loses against the plain mean.  Numpy restatement on a 37 x 21 frame, RMSE against
+ * the truth:
+ *                                                              n     M    plain mean    GINI    MEDIAN
+ *   samples U(0.5, 1.5), one in 500 brighter by 200            64    5      0.545       0.296    0.194
+ *   the same                                                  1024   9      0.130       0.120    0.201    (MEDIAN now loses: its bias stays)
+ *   every sample heavy-tailed (the frame of "Half buffers")     16   5      0.216       0.306    0.338    (both lose)
+ * with the frame's mean value at n = 64: 0.583 plain, 0.439 GINI, truth 0.586.  Rendered frames: DESIGN.md "Sample buckets".
+ * Frame figures (RtRobustInfo), in f64 over the pixels in image order, on the fixed tree of "Moments" (per workgroup of 256 pixels, then
+ * one workgroup over the partial sums in index order; no floating-point atomics), l the f32 luminance of "Half buffers":
+ *   mean_luminance_plain = sum_p (double)l(c_p) / npix with c_p = sum_p / (float)max(n_p, 1);  mean_luminance_robust likewise over out_p;
+ *   energy_removed = 1 - mean_luminance_robust / mean_luminance_plain, 0 where both are 0; a NaN propagates;
+ *   trimmed_fraction = (pixel-channels with t > 0) / (3 npix);  nonfinite_dropped = the bucket means dropped in step 1, an exact count.
+ * The filter on robust colours is "Denoising" word for word with the colours c replaced by `out`; the guide (y, v) comes unchanged from the
+ * luminance moments.  A firefly pixel's large v still makes its neighbours accept it, but what they now accept is the tamed colour.
+ * State.  RtAccumBuckets carries the M planes in the row order of out_rgb_f32.  Resume is rt_accum_begin, rt_accum_import, optionally
+ * rt_accum_import_halves, then rt_accum_import_buckets: from then on everything, the calls of this section included, is bit for bit what
+ * the uninterrupted accumulation returns.  rt_accum_import and rt_accum_merge on an accumulation that already tracks buckets are
+ * RT_ERR_UNSUPPORTED and change nothing.  Tracking can only be turned on while the accumulation holds no sample or — through
+ * rt_accum_import_buckets — together with the buckets that belong to its samples.
+ * Not covered: a merge of buckets; rt_multi_*; rt_render_to_noise and rt_render_adaptive, which open their own accumulation; a robust form
+ * of the channel-guided and the cross filter; an adaptive criterion on the robust estimate; sharded frames for the filter
+ * (RT_ERR_UNSUPPORTED, as rt_accum_denoise; the read-out works on shards).  DESIGN.md "Sample buckets". */
+#define RT_BUCKETS_MAX 16u
+#define RT_ROBUST_GINI 0u
+#define RT_ROBUST_MEDIAN 1u
+#define RT_ROBUST_TRIM 2u
+typedef struct RtRobust {
+    uint32_t mode;         /* RT_ROBUST_* */
+    uint32_t trim;         /* RT_ROBUST_TRIM: bucket means dropped per side, clamped to (K - 1) / 2; not looked at otherwise */
+    uint32_t reserved[2];  /* 0 */
+} RtRobust;
+typedef struct RtRobustInfo {
+    double mean_luminance_plain;   /* (sum_p l(c_p)) / npix of the plain mean */
+    double mean_luminance_robust;  /* (sum_p l(out_p)) / npix of the robust read-out */
+    double energy_removed;         /* 1 - robust / plain: the share of the frame's luminance the trim took away (the bias, and the fireflies) */
+    double trimmed_fraction;       /* pixel-channels with t > 0, over 3 npix */
+    uint64_t nonfinite_dropped;    /* bucket means dropped as NaN or inf */
+} RtRobustInfo;
+typedef struct RtAccumBuckets {
+    uint32_t nx, rows;             /* the shard: rows = rows_local */
+    uint32_t first_sample, done;   /* those of the accumulation the buckets belong to */
+    uint32_t M, reserved;          /* 3 .. RT_BUCKETS_MAX; 0 */
+    uint64_t frame_id;             /* rt_accum_frame_id of the frame */
+    float* sum[16];                /* RT_BUCKETS_MAX of them; [rows*nx*3] per bucket b < M: the running f32 sums, NOT divided; the pointers past M are not looked at */
+} RtAccumBuckets;
+/* Makes the open accumulation track M buckets, 3 <= M <= RT_BUCKETS_MAX, and clears them.  The rules of rt_accum_track_halves: after
+ * rt_accum_begin and before the first add, uniform or adaptive, else RT_ERR_STATE (also after an rt_accum_import that brought samples:
+ * their buckets come through rt_accum_import_buckets).  A second call with the same M is RT_OK and changes nothing; with another M it is
+ * RT_ERR_STATE.  RT_ERR_INVALID: M outside the range.  RT_ERR_NOMEM leaves the accumulation untracked.  Tracking ends with the
+ * accumulation.  Combines freely with rt_accum_track_channels and rt_accum_track_halves. */
+int rt_accum_track_buckets(RtCtx* ctx, uint32_t M);
+/* The robust read-out above.  `rb` NULL: RT_ROBUST_GINI.  out_rgb_f32 and out_rgb8 in the layouts of rt_accum_read; out_trim
+ * [rows_local*nx*3] = t per pixel and channel in the row order of out_rgb_f32; every output may be NULL.  The accumulation is read and not
+ * changed.  Works on shards.  Synchronises the context's stream once.  RT_ERR_INVALID: a mode above RT_ROBUST_TRIM or a reserved word
+ * that is not 0.  RT_ERR_STATE: no open accumulation, it does not track buckets, or fewer than 1 sample is done. */
+int rt_accum_read_robust(RtCtx* ctx, const RtRobust* rb, float* out_rgb_f32, uint8_t* out_rgb8, uint8_t* out_trim, RtRobustInfo* info);
+/* The filter on robust colours above.  `rb` and `dn` NULL: RT_ROBUST_GINI; radius 5, patch 1, strength RT_DENOISE_DEFAULT_STRENGTH.
+ * out_rgb_f32 and out_rgb8 as rt_accum_denoise writes them; either may be NULL.  The errors of rt_accum_denoise and of
+ * rt_accum_read_robust. */
+int rt_accum_denoise_robust(RtCtx* ctx, const RtRobust* rb, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8);
+/* GPU-free.  RT_OK, or RT_ERR_INVALID unless: `bs` non-NULL, reserved 0, 3 <= M <= RT_BUCKETS_MAX, sum[0] .. sum[M - 1] non-NULL,
+ * first_sample + done <= 2^32 - 1.  Values are not judged. */
+int rt_accum_buckets_check(const RtAccumBuckets* bs);
+/* Fills the scalar fields of `bs` and writes every plane b < M whose pointer is non-NULL; a NULL pointer skips that plane (all NULL: the
+ * scalar fields alone, without any device work).  Reads, and changes nothing.  Synchronises the context's stream once.  RT_ERR_STATE: no
+ * open accumulation, or it does not track buckets. */
+int rt_accum_export_buckets(RtCtx* ctx, RtAccumBuckets* bs);
+/* Puts `bs` into the open accumulation and turns tracking on, with the allocation of rt_accum_track_buckets.  Allowed while the
+ * accumulation has had no add (and no merge) since rt_accum_begin — fresh with done 0, or after rt_accum_import — else RT_ERR_STATE.
+ * Values are copied as bits.  RT_ERR_INVALID: rt_accum_buckets_check fails, or nx, rows, frame_id, first_sample or done differ from the
+ * accumulation's, or M from that of an accumulation that tracks already.  A failed call leaves the accumulation as it was.  Synchronises
+ * once. */
+int rt_accum_import_buckets(RtCtx* ctx, const RtAccumBuckets* bs);
 
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the

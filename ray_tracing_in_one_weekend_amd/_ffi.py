@@ -170,6 +170,29 @@ class RtAccumHalves(C.Structure):
                 ("frame_id", C.c_uint64), ("sum", _f * 2), ("moments", C.POINTER(C.c_double) * 2)]
 
 
+BUCKETS_MAX = 16  # RT_BUCKETS_MAX
+ROBUST_GINI, ROBUST_MEDIAN, ROBUST_TRIM = 0, 1, 2  # RT_ROBUST_*
+
+
+class RtRobust(C.Structure):
+    """rt_accum_read_robust / rt_accum_denoise_robust: how the trim of the sorted bucket means is chosen (rtow_mi355x.h "sample buckets")."""
+    _fields_ = [("mode", C.c_uint32), ("trim", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class RtRobustInfo(C.Structure):
+    """rt_accum_read_robust: the frame figures of the robust read-out; energy_removed is the share of the frame's luminance the trim took
+    away — the estimator is biased."""
+    _fields_ = [("mean_luminance_plain", C.c_double), ("mean_luminance_robust", C.c_double), ("energy_removed", C.c_double),
+                ("trimmed_fraction", C.c_double), ("nonfinite_dropped", C.c_uint64)]
+
+
+class RtAccumBuckets(C.Structure):
+    """rt_accum_export_buckets / rt_accum_import_buckets: the M bucket sums of an accumulation, as host arrays in the row order of the f32
+    image (rtow_mi355x.h "sample buckets")."""
+    _fields_ = [("nx", C.c_uint32), ("rows", C.c_uint32), ("first_sample", C.c_uint32), ("done", C.c_uint32), ("M", C.c_uint32),
+                ("reserved", C.c_uint32), ("frame_id", C.c_uint64), ("sum", _f * BUCKETS_MAX)]
+
+
 class RtBounceIO(C.Structure):
     _fields_ = [("n", C.c_uint32), ("depth", C.c_uint32), ("in_o", _f), ("in_d", _f), ("in_key", _u32),
                 ("out_hit", C.POINTER(C.c_int32)), ("out_t", _f), ("out_radiance", _f), ("out_attenuation", _f),
@@ -228,6 +251,8 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_accum_frame_id", "rt_accum_state_check", "rt_accum_export", "rt_accum_import", "rt_accum_merge",
                "rt_accum_track_halves", "rt_accum_read_halves", "rt_accum_denoise_halves", "rt_accum_halves_check", "rt_accum_export_halves",
                "rt_accum_import_halves",
+               "rt_accum_track_buckets", "rt_accum_read_robust", "rt_accum_denoise_robust", "rt_accum_buckets_check", "rt_accum_export_buckets",
+               "rt_accum_import_buckets",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
@@ -364,6 +389,18 @@ def load_gpu_library():
     lib.rt_accum_export_halves.restype = C.c_int
     lib.rt_accum_import_halves.argtypes = [vp, C.POINTER(RtAccumHalves)]
     lib.rt_accum_import_halves.restype = C.c_int
+    lib.rt_accum_track_buckets.argtypes = [vp, C.c_uint32]
+    lib.rt_accum_track_buckets.restype = C.c_int
+    lib.rt_accum_read_robust.argtypes = [vp, C.POINTER(RtRobust), _f, _u8, _u8, C.POINTER(RtRobustInfo)]
+    lib.rt_accum_read_robust.restype = C.c_int
+    lib.rt_accum_denoise_robust.argtypes = [vp, C.POINTER(RtRobust), C.POINTER(RtDenoise), _f, _u8]
+    lib.rt_accum_denoise_robust.restype = C.c_int
+    lib.rt_accum_buckets_check.argtypes = [C.POINTER(RtAccumBuckets)]
+    lib.rt_accum_buckets_check.restype = C.c_int
+    lib.rt_accum_export_buckets.argtypes = [vp, C.POINTER(RtAccumBuckets)]
+    lib.rt_accum_export_buckets.restype = C.c_int
+    lib.rt_accum_import_buckets.argtypes = [vp, C.POINTER(RtAccumBuckets)]
+    lib.rt_accum_import_buckets.restype = C.c_int
     lib.rt_debug_planar_info.argtypes =[vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.rt_debug_planar_info.restype = C.c_int
     lib.rt_debug_planar_bounds.argtypes = [C.POINTER(RtQuads), C.c_float, vp, vp]

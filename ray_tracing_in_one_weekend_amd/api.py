@@ -482,6 +482,66 @@ class AccumHalves:
             return cls(sum=z["sum"], moments=z["moments"], **kw)
 
 
+class AccumBuckets:
+    """The M sample buckets of an accumulation (rtow_mi355x.h "sample buckets"), as a numpy array in the row order of the f32 image plus the
+    scalar fields of RtAccumBuckets: sum [M, rows, nx, 3] f32 (not divided), bucket b holding the samples with absolute index i % M == b.
+    It goes with the AccumState of the same accumulation: first_sample and done are that state's."""
+    _SCALARS = ("nx", "rows", "first_sample", "done", "M", "frame_id")
+
+    def __init__(self, nx, rows, M, first_sample=0, done=0, frame_id=0, sum=None):
+        self.nx, self.rows, self.M = int(nx), int(rows), int(M)
+        self.first_sample, self.done, self.frame_id = int(first_sample), int(done), int(frame_id)
+        planes = min(max(self.M, 0), _ffi.BUCKETS_MAX)  # (an M the library refuses still makes a struct: check() says so)
+        arr = np.zeros((planes, self.rows, self.nx, 3), np.float32) if sum is None else np.ascontiguousarray(sum, dtype=np.float32)
+        if arr.shape != (planes, self.rows, self.nx, 3):
+            raise ValueError(f"AccumBuckets.sum: shape {arr.shape}, expected {(planes, self.rows, self.nx, 3)}")
+        self.sum = arr
+
+    def as_struct(self):
+        """The RtAccumBuckets over this array (which must stay alive while it is used)."""
+        bs = _ffi.RtAccumBuckets(self.nx, self.rows, self.first_sample, self.done, self.M, 0)
+        bs.frame_id = self.frame_id
+        for b in range(self.sum.shape[0]):
+            bs.sum[b] = self.sum[b].ctypes.data_as(C.POINTER(C.c_float))
+        return bs
+
+    def check(self):
+        """rt_accum_buckets_check (no GPU): True when the library would accept the buckets before comparing them with an accumulation."""
+        bs = self.as_struct()
+        return _ffi.load_gpu_library().rt_accum_buckets_check(C.byref(bs)) == 0
+
+    def counts(self, n=None):
+        """[M, ...]: how many of the `n` samples of a pixel (default: done; an array of per-pixel counts after adaptive adds) each bucket holds."""
+        n = np.asarray(self.done if n is None else n, dtype=np.uint64)
+        M, f = np.uint64(self.M), np.uint64(self.first_sample % self.M)
+        q, r = n // M, n % M
+        return np.stack([q + (((np.uint64(b) + M - f) % M) < r).astype(np.uint64) for b in range(self.M)])
+
+    def save(self, path):
+        """Writes the buckets as an .npz at exactly `path`, through a temporary file beside it and os.replace, as AccumState.save does."""
+        import os
+        import tempfile
+        data = {k: np.asarray(getattr(self, k), dtype=np.uint64) for k in self._SCALARS}
+        data.update(sum=self.sum)
+        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(path)))
+        try:
+            with os.fdopen(fd, "wb") as f:
+                np.savez(f, **data)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            kw = {k: int(z[k]) for k in cls._SCALARS}
+            return cls(sum=z["sum"], **kw)
+
+
 def make_params(nx, ny, spp, max_depth=50, seed=95, shard_band=0, shard_count=1, shard_id=0, spp_slice=0, flags=0):
     p = RtParams()
     p.flags = flags
@@ -944,6 +1004,68 @@ class Renderer:
         rc = self._lib.rt_accum_import_halves(self._ctx, C.byref(hs))
         if rc != 0:
             self._raise("rt_accum_import_halves", rc)
+
+    def accum_track_buckets(self, M):
+        """rt_accum_track_buckets: the open accumulation also keeps the samples of every pixel in M buckets by sample index (12 M bytes per
+        pixel, 3 <= M <= 16); right after accum_begin, before the first add.  Everything else the accumulation returns stays bit for bit."""
+        rc = self._lib.rt_accum_track_buckets(self._ctx, int(M))
+        if rc != 0:
+            self._raise("rt_accum_track_buckets", rc)
+
+    @staticmethod
+    def _robust(mode, trim):
+        modes = {"gini": _ffi.ROBUST_GINI, "median": _ffi.ROBUST_MEDIAN, "trim": _ffi.ROBUST_TRIM}
+        if isinstance(mode, str) and mode not in modes:
+            raise ValueError(f"robust mode {mode!r}: expected one of {sorted(modes)} (or an RT_ROBUST_* value)")
+        return _ffi.RtRobust(modes[mode] if isinstance(mode, str) else int(mode), int(trim))
+
+    def accum_robust(self, mode="gini", trim=0, want_trim=False, want_rgb8=False):
+        """rt_accum_read_robust: the frame as the trimmed mean of its sorted bucket means — mode "gini" (the trim follows the Gini
+        coefficient of the means), "median", or "trim" with `trim` means dropped per side.  Returns (img [rows, nx, 3] f32, RtRobustInfo
+        [, trim [rows, nx, 3] u8][, rgb8]).  The estimator is biased: RtRobustInfo.energy_removed is the share of luminance it took away."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        img = np.zeros((rows, nx, 3), dtype=np.float32)
+        t = np.zeros((rows, nx, 3), dtype=np.uint8) if want_trim else None
+        rgb8 = np.zeros((rows, nx, 3), dtype=np.uint8) if want_rgb8 else None
+        u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None
+        rb, info = self._robust(mode, trim), _ffi.RtRobustInfo()
+        rc = self._lib.rt_accum_read_robust(self._ctx, C.byref(rb), img.ctypes.data_as(C.POINTER(C.c_float)), u8(rgb8), u8(t), C.byref(info))
+        if rc != 0:
+            self._raise("rt_accum_read_robust", rc)
+        return (img, info) + ((t,) if want_trim else ()) + ((rgb8,) if want_rgb8 else ())
+
+    def accum_denoise_robust(self, mode="gini", trim=0, radius=5, patch=1, strength=None, want_rgb8=False):
+        """rt_accum_denoise_robust: accum_denoise with the colours replaced by the robust read-out; the guide stays the luminance moments'.
+        Returns (img [rows, nx, 3] f32, rgb8 or None)."""
+        img, rgb8, _, ptrs = self._accum_outputs(want_rgb8, False)
+        rb = self._robust(mode, trim)
+        rc = self._lib.rt_accum_denoise_robust(self._ctx, C.byref(rb), self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
+        if rc != 0:
+            self._raise("rt_accum_denoise_robust", rc)
+        return img, rgb8
+
+    def accum_export_buckets(self):
+        """rt_accum_export_buckets: the sample buckets of the open accumulation as an AccumBuckets.  Read, not changed."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        probe = _ffi.RtAccumBuckets()
+        rc = self._lib.rt_accum_export_buckets(self._ctx, C.byref(probe))  # the scalar fields only: M
+        if rc != 0:
+            self._raise("rt_accum_export_buckets", rc)
+        buckets = AccumBuckets(nx, rows, probe.M)
+        bs = buckets.as_struct()
+        rc = self._lib.rt_accum_export_buckets(self._ctx, C.byref(bs))
+        if rc != 0:
+            self._raise("rt_accum_export_buckets", rc)
+        buckets.first_sample, buckets.done, buckets.frame_id = bs.first_sample, bs.done, bs.frame_id
+        return buckets
+
+    def accum_import_buckets(self, buckets):
+        """rt_accum_import_buckets: puts an AccumBuckets into the accumulation just begun — fresh, or right after accum_import (and
+        accum_import_halves) of the state it belongs to — and turns tracking on."""
+        bs = buckets.as_struct()
+        rc = self._lib.rt_accum_import_buckets(self._ctx, C.byref(bs))
+        if rc != 0:
+            self._raise("rt_accum_import_buckets", rc)
 
     def render_to_residual(self, camera, params, target, step, radius=5, patch=1, strength=None, want_rgb8=False, want_err=False):
         """Renders until the DENOISED frame is clean: an accumulation that tracks halves gets adds of `step` samples (the first one at least

@@ -9,6 +9,7 @@
 #include "rt_accum_state.h"
 #include "rt_accum_state_kernels.h"
 #include "rt_halves.h"
+#include "rt_buckets.h"
 #include "rt_bvh.h"
 #include "rt_grid.h"
 #include "rt_pool.h"
@@ -138,6 +139,7 @@ struct RtCtx {
         bool channels = false; // rt_accum_track_channels: accum_chm holds the channel moments and every add keeps them
         bool halves = false;   // rt_accum_track_halves / rt_accum_import_halves: accum_halves holds the half sums and moments and every add keeps them
         bool added = false;    // an add of either kind or a merge has happened since rt_accum_begin (rt_accum_import_halves comes before)
+        uint32_t buckets = 0;  // rt_accum_track_buckets / rt_accum_import_buckets: M, accum_buckets holds the bucket sums and every add keeps them; 0: not tracked
     } accum;
     DevBuf accum_sum, accum_mom, accum_sem, accum_partials; // (accum_sem: staging of out_sem; accum_partials: one f64 pair per workgroup + the 3 frame figures)
     double* h_noise = nullptr;   // page-locked: mean_luminance, rms_sem, noise as k_noise_final wrote them
@@ -154,6 +156,11 @@ struct RtCtx {
     // output, out, e: 48 B per pixel, the partial sums and the three frame figures)
     DevBuf accum_halves, halves_stage, dn_halves;
     double* h_resid = nullptr;   // page-locked: mean_luminance, residual_rms, residual_noise as k_halves_final wrote them
+    // rt_accum_track_buckets (rt_buckets.h): M planes of f32 x 3 sums, 12 M B per pixel, each in the order of accum_sum (rt_buckets_plan.h);
+    // buckets_stage: the same planes in image order (a state of buckets); robust_out: what a robust read-out writes — out (12 B) and the
+    // trims (3 B) per pixel in image order, the partial sums and the frame figures
+    DevBuf accum_buckets, buckets_stage, robust_out;
+    RtRobustInfo* h_robust = nullptr; // page-locked: the figures as k_robust_final wrote them
     DevBuf accum_stage;          // rt_accum_export / _import / _merge: the planes of a state in image order (rt_accum_state.h: accum_state_staging), at most 81 B per pixel
     DevBuf dn_c, dn_yv, dn_out;  // rt_accum_denoise: the filter's inputs (c 12 B, (y, v) 8 B) and its output (12 B) per pixel, in image order
     // Host-side timeline of the last trace_samples and what its caller enqueued behind it (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
@@ -749,7 +756,9 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->accum_cnt), free_buf(ctx->accum_flag), free_buf(ctx->accum_info), free_buf(ctx->accum_cnt_out);
     free_buf(ctx->accum_stage);
     free_buf(ctx->accum_halves), free_buf(ctx->halves_stage), free_buf(ctx->dn_halves);
+    free_buf(ctx->accum_buckets), free_buf(ctx->buckets_stage), free_buf(ctx->robust_out);
     if (ctx->h_resid) (void)hipHostFree(ctx->h_resid);
+    if (ctx->h_robust) (void)hipHostFree(ctx->h_robust);
     if (ctx->h_info) (void)hipHostFree(ctx->h_info);
     free_buf(ctx->dn_c), free_buf(ctx->dn_yv), free_buf(ctx->dn_out);
     if (ctx->h_noise) (void)hipHostFree(ctx->h_noise);
@@ -894,6 +903,9 @@ struct SampleSink {
     // rt_accum_track_halves (rt_halves.h): the half sums and moments, kept by a kernel of their own in front of the resolve
     bool halves = false;
     HalfPlanes hp{};
+    // rt_accum_track_buckets (rt_buckets.h): the M planes of bucket sums, kept by a kernel of their own in front of the resolve
+    float* buckets = nullptr;
+    uint32_t n_buckets = 0;
 };
 // What trace_samples enqueued, for the finalize, the copies and the statistics of its caller.
 struct Traced {
@@ -1111,6 +1123,11 @@ static int resolve_and_preview(RtCtx* ctx, const Frame& f, const SampleSink& sin
         const uint32_t i0 = sink.first_sample + (done - sc);
         if (sink.converged) hipLaunchKernelGGL(k_resolve_halves<true>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, sink.hp, sink.converged, npix, i0, sc);
         else hipLaunchKernelGGL(k_resolve_halves<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, sink.hp, (const uint8_t*)nullptr, npix, i0, sc);
+    }
+    if (sink.buckets) {
+        const uint32_t i0 = sink.first_sample + (done - sc);
+        if (sink.converged) hipLaunchKernelGGL(k_resolve_buckets<true>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, sink.buckets, sink.converged, npix, sink.n_buckets, i0, sc);
+        else hipLaunchKernelGGL(k_resolve_buckets<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, sink.buckets, (const uint8_t*)nullptr, npix, sink.n_buckets, i0, sc);
     }
     if (sink.chm && sink.converged)
         hipLaunchKernelGGL(k_resolve_moments_channels<true>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.chm, sink.converged, sink.cnt, npix, sc);
@@ -1460,6 +1477,7 @@ static int accum_add(RtCtx* ctx, uint32_t n_samples, bool adaptive, const RtAdap
     if (adaptive) sink.converged = ctx->accum_flag.as<const uint8_t>(), sink.cnt = ctx->accum_cnt.as<uint32_t>();
     if (a.channels) sink.chm = ctx->accum_chm.as<double2>();
     if (a.halves) sink.halves = true, sink.hp = half_planes(ctx->accum_halves, a.npix);
+    if (a.buckets) sink.buckets = ctx->accum_buckets.as<float>(), sink.n_buckets = a.buckets;
     if ((rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr))) return rc;
     if (tr.npix == 0u) return nothing_traced();
     if (tr.npix != a.npix || tr.tiles_per_row != a.tiles_per_row || tr.tile_pixels != a.tile_pixels) {
@@ -1903,6 +1921,7 @@ int rt_accum_import(RtCtx* ctx, const RtAccumState* st) {
     RtCtx::Accum& a = ctx->accum;
     if (const int rc = require_open(ctx, "rt_accum_import")) return rc;
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks halves already (import the state first, then rt_accum_import_halves)");
+    if (a.buckets) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks buckets already (import the state first, then rt_accum_import_buckets)");
     if (a.done != 0u || a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_import: samples were added already (call it right after rt_accum_begin)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import: ") + why);
     if (const char* why = state_mismatch(a, *st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import: ") + why);
@@ -1941,6 +1960,7 @@ int rt_accum_merge(RtCtx* ctx, const RtAccumState* st) {
     RtCtx::Accum& a = ctx->accum;
     if (const int rc = require_open(ctx, "rt_accum_merge")) return rc;
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks halves: a merge of halves is not covered (rtow_mi355x.h)");
+    if (a.buckets) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks buckets: a merge of buckets is not covered (rtow_mi355x.h)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_merge: ") + why);
     if (a.adaptive || (st->planes & RT_ACCUM_STATE_COUNTS))
         return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: an adaptive accumulation or state: windows of pixels with different sample counts are not contiguous");
@@ -2114,6 +2134,169 @@ int rt_accum_import_halves(RtCtx* ctx, const RtAccumHalves* hs) {
         RT_HIP(ctx, hipStreamSynchronize(s_)); // (the caller's arrays are free again)
     }
     a.halves = true;
+    return RT_OK;
+}
+
+// ---- sample buckets (rtow_mi355x.h "Sample buckets", csrc/rt_buckets.h, csrc/rt_buckets_plan.h) --------------------------------------------
+int rt_accum_buckets_check(const RtAccumBuckets* bs) { return accum_buckets_invalid(bs) ? RT_ERR_INVALID : RT_OK; }
+
+// The accumulation's buffer of M buckets for npix pixels (kept for the next accumulation).
+static int ensure_buckets(RtCtx* ctx, uint32_t npix, uint32_t M) { return ensure(ctx, ctx->accum_buckets, buckets_total(npix, M)); }
+
+int rt_accum_track_buckets(RtCtx* ctx, uint32_t M) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    if (const int rc = require_open(ctx, "rt_accum_track_buckets")) return rc;
+    if (M < RT_BUCKETS_MIN || M > RT_BUCKETS_MAX) return fail(ctx, RT_ERR_INVALID, "rt_accum_track_buckets: M must be 3 .. RT_BUCKETS_MAX");
+    if (a.buckets == M) return RT_OK;
+    if (a.buckets) return fail(ctx, RT_ERR_STATE, "rt_accum_track_buckets: the accumulation tracks " + std::to_string(a.buckets) + " buckets already");
+    if (a.done != 0u || a.adaptive || a.added)
+        return fail(ctx, RT_ERR_STATE, "rt_accum_track_buckets: the accumulation holds samples already (call it right after rt_accum_begin; after rt_accum_import "
+                                       "the buckets come through rt_accum_import_buckets)");
+    if (a.npix) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        if (const int rc = ensure_buckets(ctx, a.npix, M)) return rc;
+        RT_HIP(ctx, hipMemsetAsync(ctx->accum_buckets.p, 0, buckets_total(a.npix, M), ctx->stream));
+    }
+    a.buckets = M;
+    return RT_OK;
+}
+
+// What both robust calls refuse beyond their own checks.
+static int robust_begin(RtCtx* ctx, const char* who, const RtRobust* rb, RtRobust& r) {
+    const RtCtx::Accum& a = ctx->accum;
+    if (!a.buckets) return fail(ctx, RT_ERR_STATE, std::string(who) + ": the accumulation does not track buckets (rt_accum_track_buckets)");
+    if (const char* why = robust_invalid(rb)) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": " + why);
+    if (a.done < 1u) return fail(ctx, RT_ERR_STATE, std::string(who) + ": no sample accumulated yet");
+    r = rb ? *rb : RtRobust{RT_ROBUST_GINI, 0u, {0u, 0u}};
+    return RT_OK;
+}
+// k_robust_read over the open accumulation on `st`: out (image order, 12 B per pixel) and trims (3 B per pixel), either may be NULL;
+// with `figures` the partial sums, k_robust_final and the copy into ctx->h_robust, valid after the next wait for `st`.  The partials
+// and the figures live at the head of ctx->robust_out, which the caller has ensured.
+static size_t robust_head_bytes(uint32_t npix) { return (((size_t)((npix + 255u) / 256u) * sizeof(RobustPartial) + sizeof(RobustFigures)) + 15u) & ~(size_t)15u; }
+static int enqueue_robust(RtCtx* ctx, hipStream_t st, const RtRobust& rb, float* out, uint8_t* trims, bool figures) {
+    const RtCtx::Accum& a = ctx->accum;
+    const AccumReader r = accum_reader(ctx, st);
+    const uint32_t nb = r.grid.x;
+    RobustPartial* partials = ctx->robust_out.as<RobustPartial>();
+    RobustFigures* fig = (RobustFigures*)(partials + nb);
+    ACCUM_READER(k_robust_read, r, ctx->accum_buckets.as<const float>(), ctx->accum_sum.as<const float>(), r.cnt, out, trims, figures ? partials : (RobustPartial*)nullptr,
+                 a.buckets, rb.mode, rb.trim, r.nx, r.rows, a.first, r.n, r.tiles_per_row, r.tile_pixels);
+    if (figures) {
+        hipLaunchKernelGGL(k_robust_final, dim3(1), dim3(256), 0, st, (const RobustPartial*)partials, nb, a.npix, fig);
+        RT_HIP(ctx, hipMemcpyAsync(ctx->h_robust, fig, sizeof(RtRobustInfo), hipMemcpyDeviceToHost, st));
+    }
+    return RT_OK;
+}
+
+int rt_accum_read_robust(RtCtx* ctx, const RtRobust* rb, float* out_rgb_f32, uint8_t* out_rgb8, uint8_t* out_trim, RtRobustInfo* info) {
+    if (!ctx) return RT_ERR_INVALID;
+    int rc = require_open(ctx, "rt_accum_read_robust");
+    if (rc) return rc;
+    const RtCtx::Accum& a = ctx->accum;
+    RtRobust r;
+    if ((rc = robust_begin(ctx, "rt_accum_read_robust", rb, r))) return rc;
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (a.npix == 0u || (!out_rgb_f32 && !out_rgb8 && !out_trim && !info)) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const uint32_t npix = a.npix;
+    const size_t n = (size_t)npix * 3, head = robust_head_bytes(npix);
+    if ((rc = ensure(ctx, ctx->robust_out, head + n * sizeof(float) + n))) return rc;
+    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
+    if (info && !ctx->h_robust) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_robust, sizeof(RtRobustInfo), hipHostMallocDefault));
+    float* d_out = (float*)(ctx->robust_out.as<char>() + head);
+    uint8_t* d_trim = (uint8_t*)(d_out + n);
+    if ((rc = enqueue_robust(ctx, st, r, d_out, out_trim ? d_trim : nullptr, info != nullptr))) return rc;
+    if ((rc = denoise_finish(ctx, d_out, out_rgb_f32, out_rgb8))) return rc; // (k_finalize's quantisation of `out`, and the copies)
+    if (out_trim) RT_HIP(ctx, hipMemcpyAsync(out_trim, d_trim, n, hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    if (info) *info = *ctx->h_robust;
+    return RT_OK;
+}
+
+int rt_accum_denoise_robust(RtCtx* ctx, const RtRobust* rb, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    RtDenoise d;
+    RtRobust r;
+    int rc = denoise_begin(ctx, "rt_accum_denoise_robust", dn, d, RT_DENOISE_DEFAULT_STRENGTH,
+                           a.buckets ? nullptr : "the accumulation does not track buckets (rt_accum_track_buckets)", 2u, "there is no variance yet");
+    if (rc) return rc;
+    if ((rc = robust_begin(ctx, "rt_accum_denoise_robust", rb, r))) return rc;
+    if (a.npix == 0u) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    if ((rc = ensure_denoise(ctx, a.npix))) return rc;
+    if ((rc = ensure(ctx, ctx->robust_out, robust_head_bytes(a.npix)))) return rc;
+    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, (size_t)a.npix * 3))) return rc;
+    const AccumReader rd = accum_reader(ctx, st);
+    // the inputs of rt_accum_denoise, then the robust colours over c: the guide stays the luminance moments'.  Deliberately so:
+    // k_denoise_inputs stays the kernel it was, at the price of 12 B per pixel of plain colours written and then overwritten
+    ACCUM_READER(k_denoise_inputs, rd, ctx->accum_sum.as<const float>(), ctx->accum_mom.as<const double2>(), rd.cnt, ctx->dn_c.as<float>(), ctx->dn_yv.as<float2>(), rd.nx,
+                 rd.rows, rd.n, rd.tiles_per_row, rd.tile_pixels);
+    if ((rc = enqueue_robust(ctx, st, r, ctx->dn_c.as<float>(), nullptr, false))) return rc;
+    launch_denoise(st, ctx->dn_c.as<const float>(), ctx->dn_yv.as<const float2>(), ctx->dn_out.as<float>(), a.nx, a.rows, d);
+    if ((rc = denoise_finish(ctx, ctx->dn_out.as<const float>(), out_rgb_f32, out_rgb8))) return rc;
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+int rt_accum_export_buckets(RtCtx* ctx, RtAccumBuckets* bs) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!bs) return fail(ctx, RT_ERR_INVALID, "rt_accum_export_buckets: the RtAccumBuckets is NULL");
+    if (const int rc = require_open(ctx, "rt_accum_export_buckets")) return rc;
+    if (!a.buckets) return fail(ctx, RT_ERR_STATE, "rt_accum_export_buckets: the accumulation does not track buckets (rt_accum_track_buckets)");
+    const uint32_t npix = a.npix, M = a.buckets;
+    bool any = false;
+    for (uint32_t b = 0; b < M; ++b) any = any || bs->sum[b];
+    if (npix && any) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        const hipStream_t s_ = ctx->stream;
+        if (const int rc = ensure(ctx, ctx->buckets_stage, buckets_total(npix, M))) return rc;
+        hipLaunchKernelGGL(k_buckets_export, dim3((npix + 255u) / 256u), dim3(256), 0, s_, ctx->accum_buckets.as<const float>(), ctx->buckets_stage.as<float>(), M, a.nx, a.rows,
+                           a.tiles_per_row, a.tile_pixels);
+        RT_HIP(ctx, hipGetLastError());
+        for (uint32_t b = 0; b < M; ++b)
+            if (bs->sum[b])
+                RT_HIP(ctx, hipMemcpyAsync(bs->sum[b], ctx->buckets_stage.as<char>() + buckets_plane(npix, b), (size_t)npix * RT_BUCKETS_SUM_BYTES, hipMemcpyDeviceToHost, s_));
+        RT_HIP(ctx, hipStreamSynchronize(s_));
+    }
+    bs->nx = a.nx, bs->rows = a.rows, bs->first_sample = a.first, bs->done = a.done;
+    bs->M = M, bs->reserved = 0u;
+    bs->frame_id = accum_frame_id(a.cam, a.prm);
+    return RT_OK;
+}
+
+int rt_accum_import_buckets(RtCtx* ctx, const RtAccumBuckets* bs) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    if (const int rc = require_open(ctx, "rt_accum_import_buckets")) return rc;
+    if (a.added) return fail(ctx, RT_ERR_STATE, "rt_accum_import_buckets: samples were added since rt_accum_begin (call it right after rt_accum_begin or rt_accum_import)");
+    if (const char* why = accum_buckets_invalid(bs)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import_buckets: ") + why);
+    if (bs->nx != a.nx || bs->rows != a.rows) return fail(ctx, RT_ERR_INVALID, "rt_accum_import_buckets: nx and rows of the buckets are not the accumulation's");
+    if (bs->frame_id != accum_frame_id(a.cam, a.prm))
+        return fail(ctx, RT_ERR_INVALID, "rt_accum_import_buckets: frame_id of the buckets is not rt_accum_frame_id of the accumulation's camera and params");
+    if (bs->first_sample != a.first || bs->done != a.done)
+        return fail(ctx, RT_ERR_INVALID, "rt_accum_import_buckets: first_sample and done of the buckets are not the accumulation's (rt_accum_import comes first)");
+    if (a.buckets && a.buckets != bs->M) return fail(ctx, RT_ERR_INVALID, "rt_accum_import_buckets: M of the buckets is not that of the accumulation, which tracks already");
+    const uint32_t npix = a.npix, M = bs->M;
+    if (npix) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        const hipStream_t s_ = ctx->stream;
+        int rc;
+        if ((rc = ensure_buckets(ctx, npix, M))) return rc; // every allocation first: a failure cannot leave the accumulation half imported
+        if ((rc = ensure(ctx, ctx->buckets_stage, buckets_total(npix, M)))) return rc;
+        for (uint32_t b = 0; b < M; ++b)
+            RT_HIP(ctx, hipMemcpyAsync(ctx->buckets_stage.as<char>() + buckets_plane(npix, b), bs->sum[b], (size_t)npix * RT_BUCKETS_SUM_BYTES, hipMemcpyHostToDevice, s_));
+        hipLaunchKernelGGL(k_buckets_import, dim3((npix + 255u) / 256u), dim3(256), 0, s_, ctx->accum_buckets.as<float>(), ctx->buckets_stage.as<const float>(), M, a.nx, a.rows,
+                           a.tiles_per_row, a.tile_pixels);
+        RT_HIP(ctx, hipGetLastError());
+        RT_HIP(ctx, hipStreamSynchronize(s_)); // (the caller's arrays are free again)
+    }
+    a.buckets = M;
     return RT_OK;
 }
 

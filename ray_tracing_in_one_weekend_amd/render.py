@@ -7,13 +7,17 @@ images while rendering and the final PNG under the reference's time-stamped name
 main.rs: 800x400, aspect nx/ny, 128 spp, MAX_DEPTH 50, seed base 95, test_sphere.
 There is no CPU fallback: without librtow_mi355x.so and a GPU this exits with the library's error."""
 import argparse
+import os
 import sys
 import time
 
 import numpy as np
 
-from . import AccumState, Renderer, RtError, Scene, make_params, output_file_name, register_default_images, save_png
+from . import AccumBuckets, AccumState, Renderer, RtError, Scene, make_params, output_file_name, register_default_images, save_png
 from . import _ffi
+
+# --robust without --buckets: of 5, 9 and 15 by the rule of RT_DENOISE_DEFAULT_STRENGTH on rendered frames (DESIGN.md "Sample buckets")
+DEFAULT_BUCKETS = 5
 
 SCENES = ("test_sphere", "sphere_scene", "moving_sphere_scene", "quads_scene", "mesh_scene", "simple_light_scene", "cornell_box", "final_scene", "earth_env_scene",
           "pbr_sweep_scene")
@@ -84,6 +88,17 @@ def main(argv=None):
     ap.add_argument("--merge", nargs="+", default=None, metavar="FILE",
                     help="states of further sample windows, merged in the order given behind what was rendered or resumed, before the image is "
                          "written; each must begin where the samples so far end (uniform states only)")
+    ap.add_argument("--buckets", type=int, default=None, metavar="M",
+                    help="keep the samples of every pixel in M buckets by sample index (3..%d, 12 M bytes per pixel more; default %d with "
+                         "--robust): what --robust and --firefly-map read, carried by --checkpoint in FILE.buckets.npz, which --resume picks up with its own M" % (_ffi.BUCKETS_MAX, DEFAULT_BUCKETS))
+    ap.add_argument("--robust", default=None, metavar="{gini,median,trim:N}",
+                    help="write the robust read-out instead of the plain mean (rt_accum_read_robust): the trimmed mean of the sorted bucket means, "
+                         "the trim chosen by their Gini coefficient (gini), the median (median) or N per side (trim:N).  It tames fireflies and "
+                         "keeps a NaN sample out; it is BIASED — the line printed with the image says how much energy it removed.  With "
+                         "--denoise: the luminance-guided filter on the robust colours (rt_accum_denoise_robust)")
+    ap.add_argument("--firefly-map", default=None, metavar="PATH",
+                    help="with --robust: the number of bucket means trimmed per side, per pixel the largest of its three channels, as a grey PNG "
+                         "(white = the most possible, (M - 1) / 2)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     ny = a.ny
@@ -109,6 +124,22 @@ def main(argv=None):
         rend.set_lights(scene.lights)  # (a moving scene refuses it: RT_ERR_UNSUPPORTED)
     flags = _ffi.FLAG_RUSSIAN_ROULETTE if a.russian_roulette else 0
     halves = a.residual_target is not None or (a.denoise and a.denoise_guide == "halves")
+    a.robust_mode = None
+    if a.robust is not None:
+        kind, _, n = a.robust.partition(":")
+        if kind not in ("gini", "median", "trim") or (kind == "trim") != bool(n) or (n and not n.isdigit()):
+            ap.error("--robust takes gini, median or trim:N")
+        a.robust_mode = (kind, int(n or 0))
+    a.want_buckets = a.buckets is not None or a.robust_mode is not None  # (--buckets None with --robust: the resumed file's M, else the default)
+    if a.want_buckets:
+        if a.buckets is not None and not 3 <= a.buckets <= _ffi.BUCKETS_MAX:
+            ap.error("--buckets takes 3..%d" % _ffi.BUCKETS_MAX)
+        if halves or a.merge or a.preview_every:
+            ap.error("--buckets and --robust do not combine with --denoise-guide halves, --residual-target, --merge or --preview-every")
+        if a.robust_mode and a.denoise and a.denoise_guide != "luminance":
+            ap.error("--denoise --robust filters with the luminance guide only")
+    if a.firefly_map and not a.robust_mode:
+        ap.error("--firefly-map needs --robust")
     if halves:
         if a.checkpoint or a.resume or a.merge:
             ap.error("--denoise-guide halves and --residual-target do not combine with --checkpoint, --resume or --merge")
@@ -119,7 +150,7 @@ def main(argv=None):
         if a.spp < 4:
             ap.error("the cross filter needs --spp >= 4: two samples per half")
         return render_halves(a, rend, scene, flags, file_name, t0)
-    if a.checkpoint or a.resume or a.merge or a.first_sample is not None:
+    if a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets:
         if a.preview_every:
             ap.error("--checkpoint, --resume, --first-sample and --merge do not combine with --preview-every")
         if a.adaptive_tolerance is not None and (a.noise_target is not None or a.denoise):
@@ -208,9 +239,28 @@ def render_with_state(a, rend, scene, flags, file_name, t0):
     rend.accum_begin(scene.camera, make_params(a.nx, a.ny, min(a.spp_step, a.spp), max_depth=a.max_depth, seed=a.seed, flags=flags), first_sample=first)
     if a.denoise and a.denoise_guide == "channels":
         rend.accum_track_channels()
+    n_buckets = 0  # M of the buckets the accumulation tracks, 0: none
     try:
         if state:
             rend.accum_import(state)
+            # the buckets that were checkpointed beside the state go on with it, asked for or not; their M is the file's
+            if os.path.exists(a.resume + ".buckets.npz"):
+                try:
+                    buckets = AccumBuckets.load(a.resume + ".buckets.npz")
+                except (OSError, ValueError, KeyError) as e:
+                    print(f"error: {a.resume}.buckets.npz: {e}", file=sys.stderr)
+                    return 2
+                if a.buckets is not None and a.buckets != buckets.M:
+                    print(f"error: --buckets {a.buckets}, but {a.resume}.buckets.npz holds {buckets.M} buckets", file=sys.stderr)
+                    return 2
+                rend.accum_import_buckets(buckets)
+                n_buckets = buckets.M
+            elif a.want_buckets:
+                print(f"error: --buckets / --robust with --resume need {a.resume}.buckets.npz, the buckets checkpointed beside the state", file=sys.stderr)
+                return 2
+        elif a.want_buckets:
+            n_buckets = a.buckets if a.buckets is not None else DEFAULT_BUCKETS
+            rend.accum_track_buckets(n_buckets)
         done, steps, n_rays, seconds = (state.done if state else 0), 0, 0, 0.0
 
         def finished():
@@ -222,27 +272,44 @@ def render_with_state(a, rend, scene, flags, file_name, t0):
                 return rend.accum_counts()[1].n_active == 0
             return a.noise_target is not None and rend.accum_read()[3].noise <= a.noise_target
 
+        def save_state():
+            if n_buckets:  # the buckets first: a state without its buckets resumes nowhere, buckets without a state are ignored
+                rend.accum_export_buckets().save(a.checkpoint + ".buckets.npz")
+            rend.accum_export().save(a.checkpoint)
+
         while not finished():
             n = min(a.spp_step, a.spp - done)
             st = rend.accum_add_adaptive(n, a.adaptive_tolerance, a.luminance_floor, a.min_spp) if adaptive else rend.accum_add(n)
             done, steps, n_rays, seconds = done + n, steps + 1, n_rays + st.n_rays, seconds + st.seconds_device
             if a.checkpoint and steps % a.checkpoint_every == 0:
-                rend.accum_export().save(a.checkpoint)
+                save_state()
             print(f"{done}/{a.spp}", file=sys.stderr)
         for path in a.merge or ():
             rend.accum_merge(AccumState.load(path))
         if a.checkpoint and (a.merge or steps % a.checkpoint_every != 0 or steps == 0):
-            rend.accum_export().save(a.checkpoint)  # (what was merged is part of it)
+            save_state()  # (what was merged is part of it)
     except RtError as e:
         print(f"error: {e}", file=sys.stderr)
         return 2
     _, rgb8, _, noise = rend.accum_read(want_rgb8=True)
     counts, info = rend.accum_counts()
+    robust_line = ""
+    if a.robust_mode:
+        _, rinfo, trim, rgb8 = rend.accum_robust(*a.robust_mode, want_trim=True, want_rgb8=True)
+        robust_line = (f"{file_name}: robust read-out ({a.robust}, {n_buckets} buckets): energy_removed {rinfo.energy_removed:.4g}, trimmed_fraction "
+                       f"{rinfo.trimmed_fraction:.4g}, {rinfo.nonfinite_dropped} non-finite bucket means dropped (a biased estimate: the trim takes "
+                       f"energy that belongs to the frame)")
+        if a.firefly_map:
+            worst = trim.max(axis=2).astype(np.uint32)  # the largest trim of the three channels; at most (M - 1) / 2
+            grey = (worst * 255 // max((n_buckets - 1) // 2, 1)).astype(np.uint8)[::-1]  # (row 0 of the trims is the bottom row)
+            save_png(a.firefly_map, np.ascontiguousarray(np.repeat(grey[..., None], 3, axis=2)))
     if a.denoise:
         rgb8 = _denoised(a, rend)
     rend.accum_end()
     print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
     save_png(file_name, rgb8)
+    if robust_line:
+        print(robust_line, file=sys.stderr)
     if a.counts_out:
         grey = np.minimum(counts.astype(np.float64) * (255.0 / max(a.spp, 1)), 255.0).astype(np.uint8)[::-1]  # (row 0 of the counts is the bottom row)
         save_png(a.counts_out, np.ascontiguousarray(np.repeat(grey[..., None], 3, axis=2)))
@@ -253,6 +320,8 @@ def render_with_state(a, rend, scene, flags, file_name, t0):
 
 
 def _denoised(a, rend):
+    if a.robust_mode:
+        return rend.accum_denoise_robust(*a.robust_mode, a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
     if a.denoise_guide == "channels":
         return rend.accum_denoise_channels(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
     return rend.accum_denoise(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
