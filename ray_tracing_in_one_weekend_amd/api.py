@@ -423,19 +423,70 @@ def variant_tables():
     return _ledger_sets(led)
 
 
-class AccumHalves:
+class _Snapshot:
+    """What AccumState, AccumHalves and AccumBuckets share: scalar fields, per-pixel arrays in the row order of the f32 image, the library's
+    check of the struct over them, and an .npz file.  A subclass declares _SCALARS (the scalar fields, in the file's order), _ARRAYS (name,
+    dtype, trailing shape, leading shape — a leading entry may name an attribute) and _CHECK (the library's check function), and supplies
+    as_struct().  _OPTIONAL: an array that is not given stays None and is left out of the file; else it is zeros."""
+    _SCALARS, _ARRAYS, _CHECK, _OPTIONAL = (), (), None, False
+
+    def _init(self, scalars, arrays):
+        for k in self._SCALARS:
+            setattr(self, k, int(scalars[k]))
+        for name, dt, trailing, leading in self._ARRAYS:
+            shape = tuple(getattr(self, d) if isinstance(d, str) else d for d in leading) + (self.rows, self.nx) + trailing
+            arr = arrays[name]
+            if arr is None and not self._OPTIONAL:
+                arr = np.zeros(shape, dt)
+            elif arr is not None:
+                arr = np.ascontiguousarray(arr, dtype=dt)
+                if arr.shape != shape:
+                    raise ValueError(f"{type(self).__name__}.{name}: shape {arr.shape}, expected {shape}")
+            setattr(self, name, arr)
+
+    def check(self):
+        """The library's check of the struct (rt_accum_state_check, rt_accum_halves_check, rt_accum_buckets_check; no GPU): True when the
+        library would accept it before comparing it with an accumulation."""
+        st = self.as_struct()
+        return getattr(_ffi.load_gpu_library(), self._CHECK)(C.byref(st)) == 0
+
+    def save(self, path):
+        """Writes the snapshot as an .npz at exactly `path`, through a temporary file beside it and os.replace: a process killed while
+        saving leaves the previous checkpoint or none, never half of one."""
+        import os
+        import tempfile
+        data = {k: np.asarray(getattr(self, k), dtype=np.uint64) for k in self._SCALARS}
+        data.update({name: getattr(self, name) for name, *_ in self._ARRAYS if getattr(self, name) is not None})
+        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(path)))
+        try:
+            with os.fdopen(fd, "wb") as f:
+                np.savez(f, **data)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            kw = {k: int(z[k]) for k in cls._SCALARS}
+            kw.update({name: z[name] for name, *_ in cls._ARRAYS if name in z.files or not cls._OPTIONAL})
+        return cls(**kw)
+
+
+class AccumHalves(_Snapshot):
     """The two half buffers of an accumulation (rtow_mi355x.h "half buffers"), as numpy arrays in the row order of the f32 image plus the
     scalar fields of RtAccumHalves: sum [2, rows, nx, 3] f32 (not divided) and moments [2, rows, nx, 2] f64, half 0 (the samples with an
     even absolute index) first.  It goes with the AccumState of the same accumulation: first_sample and done are that state's."""
     _SCALARS = ("nx", "rows", "first_sample", "done", "frame_id")
+    _ARRAYS = (("sum", np.float32, (3,), (2,)), ("moments", np.float64, (2,), (2,)))
+    _CHECK = "rt_accum_halves_check"
 
     def __init__(self, nx, rows, first_sample=0, done=0, frame_id=0, sum=None, moments=None):
-        self.nx, self.rows, self.first_sample, self.done, self.frame_id = int(nx), int(rows), int(first_sample), int(done), int(frame_id)
-        for name, arr, dt, k in (("sum", sum, np.float32, 3), ("moments", moments, np.float64, 2)):
-            arr = np.zeros((2, self.rows, self.nx, k), dt) if arr is None else np.ascontiguousarray(arr, dtype=dt)
-            if arr.shape != (2, self.rows, self.nx, k):
-                raise ValueError(f"AccumHalves.{name}: shape {arr.shape}, expected {(2, self.rows, self.nx, k)}")
-            setattr(self, name, arr)
+        self._init(dict(nx=nx, rows=rows, first_sample=first_sample, done=done, frame_id=frame_id), dict(sum=sum, moments=moments))
 
     def as_struct(self):
         """The RtAccumHalves over these arrays (which must stay alive while it is used)."""
@@ -446,56 +497,24 @@ class AccumHalves:
             hs.moments[h] = self.moments[h].ctypes.data_as(C.POINTER(C.c_double))
         return hs
 
-    def check(self):
-        """rt_accum_halves_check (no GPU): True when the library would accept the halves before comparing them with an accumulation."""
-        hs = self.as_struct()
-        return _ffi.load_gpu_library().rt_accum_halves_check(C.byref(hs)) == 0
-
     def counts(self, n=None):
         """(n_0, n_1): how many of the `n` samples of a pixel (default: done; an array of per-pixel counts after adaptive adds) each half holds."""
         n = np.asarray(self.done if n is None else n, dtype=np.uint64)
         n0 = n // 2 + (n & 1 & ~np.uint64(self.first_sample))
         return n0, n - n0
 
-    def save(self, path):
-        """Writes the halves as an .npz at exactly `path`, through a temporary file beside it and os.replace, as AccumState.save does."""
-        import os
-        import tempfile
-        data = {k: np.asarray(getattr(self, k), dtype=np.uint64) for k in self._SCALARS}
-        data.update(sum=self.sum, moments=self.moments)
-        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(path)))
-        try:
-            with os.fdopen(fd, "wb") as f:
-                np.savez(f, **data)
-                f.flush()
-                os.fsync(f.fileno())
-            os.replace(tmp, path)
-        except BaseException:
-            if os.path.exists(tmp):
-                os.unlink(tmp)
-            raise
 
-    @classmethod
-    def load(cls, path):
-        with np.load(path) as z:
-            kw = {k: int(z[k]) for k in cls._SCALARS}
-            return cls(sum=z["sum"], moments=z["moments"], **kw)
-
-
-class AccumBuckets:
+class AccumBuckets(_Snapshot):
     """The M sample buckets of an accumulation (rtow_mi355x.h "sample buckets"), as a numpy array in the row order of the f32 image plus the
     scalar fields of RtAccumBuckets: sum [M, rows, nx, 3] f32 (not divided), bucket b holding the samples with absolute index i % M == b.
     It goes with the AccumState of the same accumulation: first_sample and done are that state's."""
     _SCALARS = ("nx", "rows", "first_sample", "done", "M", "frame_id")
+    _ARRAYS = (("sum", np.float32, (3,), ("_planes",)),)
+    _CHECK = "rt_accum_buckets_check"
 
     def __init__(self, nx, rows, M, first_sample=0, done=0, frame_id=0, sum=None):
-        self.nx, self.rows, self.M = int(nx), int(rows), int(M)
-        self.first_sample, self.done, self.frame_id = int(first_sample), int(done), int(frame_id)
-        planes = min(max(self.M, 0), _ffi.BUCKETS_MAX)  # (an M the library refuses still makes a struct: check() says so)
-        arr = np.zeros((planes, self.rows, self.nx, 3), np.float32) if sum is None else np.ascontiguousarray(sum, dtype=np.float32)
-        if arr.shape != (planes, self.rows, self.nx, 3):
-            raise ValueError(f"AccumBuckets.sum: shape {arr.shape}, expected {(planes, self.rows, self.nx, 3)}")
-        self.sum = arr
+        self._planes = min(max(int(M), 0), _ffi.BUCKETS_MAX)  # (an M the library refuses still makes a struct: check() says so)
+        self._init(dict(nx=nx, rows=rows, first_sample=first_sample, done=done, M=M, frame_id=frame_id), dict(sum=sum))
 
     def as_struct(self):
         """The RtAccumBuckets over this array (which must stay alive while it is used)."""
@@ -505,41 +524,12 @@ class AccumBuckets:
             bs.sum[b] = self.sum[b].ctypes.data_as(C.POINTER(C.c_float))
         return bs
 
-    def check(self):
-        """rt_accum_buckets_check (no GPU): True when the library would accept the buckets before comparing them with an accumulation."""
-        bs = self.as_struct()
-        return _ffi.load_gpu_library().rt_accum_buckets_check(C.byref(bs)) == 0
-
     def counts(self, n=None):
         """[M, ...]: how many of the `n` samples of a pixel (default: done; an array of per-pixel counts after adaptive adds) each bucket holds."""
         n = np.asarray(self.done if n is None else n, dtype=np.uint64)
         M, f = np.uint64(self.M), np.uint64(self.first_sample % self.M)
         q, r = n // M, n % M
         return np.stack([q + (((np.uint64(b) + M - f) % M) < r).astype(np.uint64) for b in range(self.M)])
-
-    def save(self, path):
-        """Writes the buckets as an .npz at exactly `path`, through a temporary file beside it and os.replace, as AccumState.save does."""
-        import os
-        import tempfile
-        data = {k: np.asarray(getattr(self, k), dtype=np.uint64) for k in self._SCALARS}
-        data.update(sum=self.sum)
-        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(path)))
-        try:
-            with os.fdopen(fd, "wb") as f:
-                np.savez(f, **data)
-                f.flush()
-                os.fsync(f.fileno())
-            os.replace(tmp, path)
-        except BaseException:
-            if os.path.exists(tmp):
-                os.unlink(tmp)
-            raise
-
-    @classmethod
-    def load(cls, path):
-        with np.load(path) as z:
-            kw = {k: int(z[k]) for k in cls._SCALARS}
-            return cls(sum=z["sum"], **kw)
 
 
 def make_params(nx, ny, spp, max_depth=50, seed=95, shard_band=0, shard_count=1, shard_id=0, spp_slice=0, flags=0):
@@ -574,28 +564,21 @@ def accum_frame_id(camera, params):
     return int(_ffi.load_gpu_library().rt_accum_frame_id(C.byref(camera), C.byref(params)))
 
 
-class AccumState:
+class AccumState(_Snapshot):
     """What an accumulation owns (rtow_mi355x.h "accumulation state"), as numpy arrays in the row order of the f32 image plus the scalar
     fields of RtAccumState: sum [rows, nx, 3] f32 (not divided), moments [rows, nx, 2] f64, counts [rows, nx] u32, converged [rows, nx] u8,
     channel_moments [rows, nx, 6] f64 or None.  `planes` says which of counts / converged and channel_moments belong to the state
     (_ffi.ACCUM_STATE_*); on a uniform state counts and converged are informative (done and 0) and are not handed to the library."""
     _SCALARS = ("nx", "rows", "first_sample", "done", "planes", "frame_id")
-    _ARRAYS = (("sum", np.float32, 3), ("moments", np.float64, 2), ("counts", np.uint32, 0), ("converged", np.uint8, 0),
-               ("channel_moments", np.float64, 6))
+    _ARRAYS = (("sum", np.float32, (3,), ()), ("moments", np.float64, (2,), ()), ("counts", np.uint32, (), ()), ("converged", np.uint8, (), ()),
+               ("channel_moments", np.float64, (6,), ()))
+    _CHECK = "rt_accum_state_check"
+    _OPTIONAL = True
 
     def __init__(self, nx, rows, first_sample=0, done=0, planes=0, frame_id=0, sum=None, moments=None, counts=None, converged=None,
                  channel_moments=None):
-        self.nx, self.rows, self.first_sample, self.done = int(nx), int(rows), int(first_sample), int(done)
-        self.planes, self.frame_id = int(planes), int(frame_id)
-        given = dict(sum=sum, moments=moments, counts=counts, converged=converged, channel_moments=channel_moments)
-        for name, dt, k in self._ARRAYS:
-            arr = given[name]
-            if arr is not None:
-                shape = (self.rows, self.nx, k) if k else (self.rows, self.nx)
-                arr = np.ascontiguousarray(arr, dtype=dt)
-                if arr.shape != shape:
-                    raise ValueError(f"AccumState.{name}: shape {arr.shape}, expected {shape}")
-            setattr(self, name, arr)
+        self._init(dict(nx=nx, rows=rows, first_sample=first_sample, done=done, planes=planes, frame_id=frame_id),
+                   dict(sum=sum, moments=moments, counts=counts, converged=converged, channel_moments=channel_moments))
 
     @property
     def adaptive(self):
@@ -617,37 +600,6 @@ class AccumState:
             st.channel_moments = ptr(self.channel_moments, C.c_double)
         return st
 
-    def check(self):
-        """rt_accum_state_check (no GPU): True when the library would accept the state before comparing it with an accumulation."""
-        st = self.as_struct()
-        return _ffi.load_gpu_library().rt_accum_state_check(C.byref(st)) == 0
-
-    def save(self, path):
-        """Writes the state as an .npz at exactly `path`, through a temporary file beside it and os.replace: a process killed while
-        saving leaves the previous checkpoint or none, never half of one."""
-        import os
-        import tempfile
-        data = {k: np.asarray(getattr(self, k), dtype=np.uint64) for k in self._SCALARS}
-        data.update({name: getattr(self, name) for name, _, _ in self._ARRAYS if getattr(self, name) is not None})
-        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(path)))
-        try:
-            with os.fdopen(fd, "wb") as f:
-                np.savez(f, **data)
-                f.flush()
-                os.fsync(f.fileno())
-            os.replace(tmp, path)
-        except BaseException:
-            if os.path.exists(tmp):
-                os.unlink(tmp)
-            raise
-
-    @classmethod
-    def load(cls, path):
-        with np.load(path) as z:
-            kw = {k: int(z[k]) for k in cls._SCALARS}
-            kw.update({name: z[name] for name, _, _ in cls._ARRAYS if name in z.files})
-        return cls(**kw)
-
 
 class Renderer:
     """One GPU context (rt_ctx_create).  Replaces the render half of main.rs:62-129."""
@@ -663,6 +615,12 @@ class Renderer:
     def _raise(self, what, rc):
         raise RtError(f"{what} failed ({rc}): {self._lib.rt_last_error(self._ctx).decode()}")
 
+    def _call(self, what, *args):
+        """The library's function `what` on this context; anything but RT_OK raises with the context's last error."""
+        rc = getattr(self._lib, what)(self._ctx, *args)
+        if rc != 0:
+            self._raise(what, rc)
+
     @property
     def build_id(self):
         """rt_build_id(): hash of the device sources + compiler flags the loaded library was built from."""
@@ -670,45 +628,33 @@ class Renderer:
 
     def upload(self, scene):
         ptr = scene.flat_ptr if isinstance(scene, Scene) else C.pointer(scene)
-        rc = self._lib.rt_scene_upload(self._ctx, ptr)
-        if rc != 0:
-            self._raise("rt_scene_upload", rc)
+        self._call("rt_scene_upload", ptr)
 
     def prepare(self, params):
         """rt_prepare: start requesting the work buffers of the frame `params` describes (a helper thread inside the library);
         call it before building the scene, as a host that knows its frame size up front would (main.rs:64-67)."""
-        rc = self._lib.rt_prepare(self._ctx, C.byref(params))
-        if rc != 0:
-            self._raise("rt_prepare", rc)
+        self._call("rt_prepare", C.byref(params))
 
     def set_option(self, option, value):
         """rt_debug_set_option: `option` an _ffi.OPT_* number or its lower-case name.  Per context; every setting renders the
         same bits (they select between equivalent search structures / placements / orders).  Upload-time options
         (tree_placement, texel_pool, grid_cell, general_lds) take effect at the next upload()."""
         opt = _ffi.OPT_NAMES[option] if isinstance(option, str) else int(option)
-        rc = self._lib.rt_debug_set_option(self._ctx, opt, int(value))
-        if rc != 0:
-            self._raise("rt_debug_set_option", rc)
+        self._call("rt_debug_set_option", opt, int(value))
 
     def get_option(self, option):
         opt = _ffi.OPT_NAMES[option] if isinstance(option, str) else int(option)
         v = C.c_uint32()
-        rc = self._lib.rt_debug_get_option(self._ctx, opt, C.byref(v))
-        if rc != 0:
-            self._raise("rt_debug_get_option", rc)
+        self._call("rt_debug_get_option", opt, C.byref(v))
         return v.value
 
     def scene_info(self):
         """rt_debug_scene_info as a dict: what upload() built for the closest-hit search (tree placement, grid or not)."""
         info = _ffi.RtSceneInfo()
-        rc = self._lib.rt_debug_scene_info(self._ctx, C.byref(info))
-        if rc != 0:
-            self._raise("rt_debug_scene_info", rc)
+        self._call("rt_debug_scene_info", C.byref(info))
         d = info.as_dict()
         n, lds = C.c_uint32(0), C.c_uint32(0)
-        rc = self._lib.rt_debug_planar_info(self._ctx, C.byref(n), C.byref(lds))
-        if rc != 0:
-            self._raise("rt_debug_planar_info", rc)
+        self._call("rt_debug_planar_info", C.byref(n), C.byref(lds))
         d["n_planar"], d["plane_data_in_lds"] = n.value, lds.value  # (rt_set_quads: the count, and LDS or L2 for the plane data)
         return d
 
@@ -716,9 +662,7 @@ class Renderer:
         """rt_debug_launched_variants: the kernel instantiations this context has launched since the last reset, in the form of
         variant_tables()."""
         led = _ffi.RtVariantLedger()
-        rc = self._lib.rt_debug_launched_variants(self._ctx, C.byref(led), 1 if reset else 0)
-        if rc != 0:
-            self._raise("rt_debug_launched_variants", rc)
+        self._call("rt_debug_launched_variants", C.byref(led), 1 if reset else 0)
         return _ledger_sets(led)
 
     def shard_rows(self, params):
@@ -754,27 +698,20 @@ class Renderer:
             img = np.zeros((rows, params.nx, 3), dtype=np.float32)
             rgb8 = np.zeros((rows, params.nx, 3), dtype=np.uint8) if want_rgb8 else None
         stats = RtStats()
-        rc = self._lib.rt_render(self._ctx, C.byref(camera), C.byref(params),
-                                 img.ctypes.data_as(C.POINTER(C.c_float)),
-                                 rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgb8 else None, C.byref(stats))
-        if rc != 0:
-            self._raise("rt_render", rc)
+        self._call("rt_render", C.byref(camera), C.byref(params), img.ctypes.data_as(C.POINTER(C.c_float)),
+                   rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgb8 else None, C.byref(stats))
         return img, rgb8, stats
 
     def accum_begin(self, camera, params, first_sample=0):
         """rt_accum_begin: opens the accumulation of this context for the frame of `params` (params.spp: the expected size of one add)
         and clears its sums; the first added sample gets the index first_sample."""
-        rc = self._lib.rt_accum_begin(self._ctx, C.byref(camera), C.byref(params), int(first_sample))
-        if rc != 0:
-            self._raise("rt_accum_begin", rc)
+        self._call("rt_accum_begin", C.byref(camera), C.byref(params), int(first_sample))
         self._accum_shape = (self.shard_rows(params), params.nx)
 
     def accum_add(self, n):
         """rt_accum_add: n more samples per pixel onto the running sums; returns the RtStats of these samples."""
         stats = RtStats()
-        rc = self._lib.rt_accum_add(self._ctx, int(n), C.byref(stats))
-        if rc != 0:
-            self._raise("rt_accum_add", rc)
+        self._call("rt_accum_add", int(n), C.byref(stats))
         return stats
 
     def _accum_outputs(self, want_rgb8, want_sem):
@@ -790,16 +727,12 @@ class Renderer:
         of each pixel's mean luminance —, RtNoise) of the samples accumulated so far."""
         img, rgb8, sem, ptrs = self._accum_outputs(want_rgb8, want_sem)
         noise = RtNoise()
-        rc = self._lib.rt_accum_read(self._ctx, *ptrs, C.byref(noise))
-        if rc != 0:
-            self._raise("rt_accum_read", rc)
+        self._call("rt_accum_read", *ptrs, C.byref(noise))
         return img, rgb8, sem, noise
 
     def accum_end(self):
         """rt_accum_end: ends the accumulation (no error when none is open)."""
-        rc = self._lib.rt_accum_end(self._ctx)
-        if rc != 0:
-            self._raise("rt_accum_end", rc)
+        self._call("rt_accum_end")
 
     def render_to_noise(self, camera, params, target, step, want_rgb8=False, want_sem=False):
         """rt_render_to_noise: samples in steps of `step` until RtNoise.noise <= target or params.spp, the maximum, are done.  Returns
@@ -807,10 +740,7 @@ class Renderer:
         self._accum_shape = (self.shard_rows(params), params.nx)
         img, rgb8, sem, ptrs = self._accum_outputs(want_rgb8, want_sem)
         noise, stats = RtNoise(), RtStats()
-        rc = self._lib.rt_render_to_noise(self._ctx, C.byref(camera), C.byref(params), float(target), int(step), *ptrs, C.byref(noise),
-                                          C.byref(stats))
-        if rc != 0:
-            self._raise("rt_render_to_noise", rc)
+        self._call("rt_render_to_noise", C.byref(camera), C.byref(params), float(target), int(step), *ptrs, C.byref(noise), C.byref(stats))
         return img, rgb8, sem, noise, stats
 
     def accum_add_adaptive(self, n, tolerance, luminance_floor=0.01, min_samples=16):
@@ -818,18 +748,14 @@ class Renderer:
         (tolerance * max(mean, luminance_floor))^2 stop for good; every other pixel gets n more samples.  Returns the RtStats of the rays
         traced (n_paths = active pixels x n)."""
         ad, stats = make_adaptive(tolerance, luminance_floor, min_samples), RtStats()
-        rc = self._lib.rt_accum_add_adaptive(self._ctx, int(n), C.byref(ad), C.byref(stats))
-        if rc != 0:
-            self._raise("rt_accum_add_adaptive", rc)
+        self._call("rt_accum_add_adaptive", int(n), C.byref(ad), C.byref(stats))
         return stats
 
     def accum_counts(self):
         """rt_accum_read_counts: (sample counts [rows, nx] u32 laid out as accum_read's sem, RtAdaptiveInfo)."""
         rows, nx = getattr(self, "_accum_shape", (0, 0))
         counts, info = np.zeros((rows, nx), dtype=np.uint32), RtAdaptiveInfo()
-        rc = self._lib.rt_accum_read_counts(self._ctx, counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(info))
-        if rc != 0:
-            self._raise("rt_accum_read_counts", rc)
+        self._call("rt_accum_read_counts", counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(info))
         return counts, info
 
     def render_adaptive(self, camera, params, tolerance, step, luminance_floor=0.01, min_samples=16, want_rgb8=False, want_sem=False):
@@ -840,17 +766,13 @@ class Renderer:
         img, rgb8, sem, ptrs = self._accum_outputs(want_rgb8, want_sem)
         counts = np.zeros(self._accum_shape, dtype=np.uint32)
         ad, noise, info, stats = make_adaptive(tolerance, luminance_floor, min_samples), RtNoise(), RtAdaptiveInfo(), RtStats()
-        rc = self._lib.rt_render_adaptive(self._ctx, C.byref(camera), C.byref(params), C.byref(ad), int(step), *ptrs,
-                                          counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(noise), C.byref(info), C.byref(stats))
-        if rc != 0:
-            self._raise("rt_render_adaptive", rc)
+        self._call("rt_render_adaptive", C.byref(camera), C.byref(params), C.byref(ad), int(step), *ptrs,
+                   counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(noise), C.byref(info), C.byref(stats))
         return img, rgb8, sem, counts, noise, info, stats
 
     def debug_accum_set_moments(self, pixel, s1, s2):
         """rt_debug_accum_set_moments: overwrites (S1, S2) of pixel `pixel` (an index into accum_read's sem, flattened) of the open accumulation."""
-        rc = self._lib.rt_debug_accum_set_moments(self._ctx, int(pixel), float(s1), float(s2))
-        if rc != 0:
-            self._raise("rt_debug_accum_set_moments", rc)
+        self._call("rt_debug_accum_set_moments", int(pixel), float(s1), float(s2))
 
     @staticmethod
     def _denoise_ptr(radius, patch, strength):
@@ -862,9 +784,7 @@ class Renderer:
         radius, strength; None: RT_DENOISE_DEFAULT_STRENGTH).  Returns (img [rows, nx, 3] f32, rgb8 or None) laid out as accum_read's; the
         accumulation itself is not changed."""
         img, rgb8, _, ptrs = self._accum_outputs(want_rgb8, False)
-        rc = self._lib.rt_accum_denoise(self._ctx, self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
-        if rc != 0:
-            self._raise("rt_accum_denoise", rc)
+        self._call("rt_accum_denoise", self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
         return img, rgb8
 
     def debug_denoise(self, rgb, y, v, radius=5, patch=1, strength=None):
@@ -876,34 +796,26 @@ class Renderer:
         assert rgb.shape == (rows, nx, 3) and v.shape == (rows, nx)
         out = np.zeros_like(rgb)
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-        rc = self._lib.rt_debug_denoise(self._ctx, nx, rows, fp(rgb), fp(y), fp(v), self._denoise_ptr(radius, patch, strength), fp(out))
-        if rc != 0:
-            self._raise("rt_debug_denoise", rc)
+        self._call("rt_debug_denoise", nx, rows, fp(rgb), fp(y), fp(v), self._denoise_ptr(radius, patch, strength), fp(out))
         return out
 
     def accum_track_channels(self):
         """rt_accum_track_channels: the open accumulation also keeps two f64 moments per pixel and channel (48 B per pixel); right after
         accum_begin, before the first add.  Everything else the accumulation returns stays bit for bit."""
-        rc = self._lib.rt_accum_track_channels(self._ctx)
-        if rc != 0:
-            self._raise("rt_accum_track_channels", rc)
+        self._call("rt_accum_track_channels")
 
     def accum_channel_sem(self):
         """rt_accum_read_channel_sem: [rows, nx, 3] f32, the standard error of each pixel's mean per channel, laid out as accum_read's image."""
         rows, nx = getattr(self, "_accum_shape", (0, 0))
         sem = np.zeros((rows, nx, 3), dtype=np.float32)
-        rc = self._lib.rt_accum_read_channel_sem(self._ctx, sem.ctypes.data_as(C.POINTER(C.c_float)))
-        if rc != 0:
-            self._raise("rt_accum_read_channel_sem", rc)
+        self._call("rt_accum_read_channel_sem", sem.ctypes.data_as(C.POINTER(C.c_float)))
         return sem
 
     def accum_denoise_channels(self, radius=5, patch=1, strength=None, want_rgb8=False):
         """rt_accum_denoise_channels: accum_denoise with the distance on the three channels and their own variances, so that edges between
         colours of equal luminance stay; the accumulation must track channels (accum_track_channels).  Returns (img, rgb8 or None)."""
         img, rgb8, _, ptrs = self._accum_outputs(want_rgb8, False)
-        rc = self._lib.rt_accum_denoise_channels(self._ctx, self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
-        if rc != 0:
-            self._raise("rt_accum_denoise_channels", rc)
+        self._call("rt_accum_denoise_channels", self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
         return img, rgb8
 
     def debug_denoise_channels(self, rgb, var_rgb, radius=5, patch=1, strength=None):
@@ -914,9 +826,7 @@ class Renderer:
         assert rgb.shape == (rows, nx, 3) == var_rgb.shape
         out = np.zeros_like(rgb)
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-        rc = self._lib.rt_debug_denoise_channels(self._ctx, nx, rows, fp(rgb), fp(var_rgb), self._denoise_ptr(radius, patch, strength), fp(out))
-        if rc != 0:
-            self._raise("rt_debug_denoise_channels", rc)
+        self._call("rt_debug_denoise_channels", nx, rows, fp(rgb), fp(var_rgb), self._denoise_ptr(radius, patch, strength), fp(out))
         return out
 
     def accum_export(self):
@@ -924,18 +834,14 @@ class Renderer:
         are `done` and 0.  The accumulation is read and not changed."""
         rows, nx = getattr(self, "_accum_shape", (0, 0))
         probe = _ffi.RtAccumState()
-        rc = self._lib.rt_accum_export(self._ctx, C.byref(probe))  # the scalar fields only: which planes are there to ask for
-        if rc != 0:
-            self._raise("rt_accum_export", rc)
+        self._call("rt_accum_export", C.byref(probe))  # the scalar fields only: which planes are there to ask for
         channels = bool(probe.planes & _ffi.ACCUM_STATE_CHANNELS)
         state = AccumState(probe.nx, probe.rows, sum=np.zeros((rows, nx, 3), np.float32), moments=np.zeros((rows, nx, 2), np.float64),
                            counts=np.zeros((rows, nx), np.uint32), converged=np.zeros((rows, nx), np.uint8),
                            channel_moments=np.zeros((rows, nx, 6), np.float64) if channels else None)
         state.planes = _ffi.ACCUM_STATE_COUNTS | (_ffi.ACCUM_STATE_CHANNELS if channels else 0)  # (every array below gets a pointer)
         st = state.as_struct()
-        rc = self._lib.rt_accum_export(self._ctx, C.byref(st))
-        if rc != 0:
-            self._raise("rt_accum_export", rc)
+        self._call("rt_accum_export", C.byref(st))
         state.first_sample, state.done, state.planes, state.frame_id = st.first_sample, st.done, st.planes, st.frame_id
         return state
 
@@ -943,23 +849,17 @@ class Renderer:
         """rt_accum_import: puts an AccumState into the accumulation just begun (before its first add); it then goes on, bit for bit, as
         the exported one would have."""
         st = state.as_struct()
-        rc = self._lib.rt_accum_import(self._ctx, C.byref(st))
-        if rc != 0:
-            self._raise("rt_accum_import", rc)
+        self._call("rt_accum_import", C.byref(st))
 
     def accum_merge(self, state):
         """rt_accum_merge: adds the AccumState of the sample window that follows the open accumulation's onto it (both uniform)."""
         st = state.as_struct()
-        rc = self._lib.rt_accum_merge(self._ctx, C.byref(st))
-        if rc != 0:
-            self._raise("rt_accum_merge", rc)
+        self._call("rt_accum_merge", C.byref(st))
 
     def accum_track_halves(self):
         """rt_accum_track_halves: the open accumulation also keeps the even and the odd samples of every pixel apart (56 B per pixel); right
         after accum_begin, before the first add.  Everything else the accumulation returns stays bit for bit."""
-        rc = self._lib.rt_accum_track_halves(self._ctx)
-        if rc != 0:
-            self._raise("rt_accum_track_halves", rc)
+        self._call("rt_accum_track_halves")
 
     def accum_half(self, h, want_sem=False):
         """rt_accum_read_halves: (img [rows, nx, 3] f32 of half h — 0: the samples with an even absolute index —, sem [rows, nx] f32 or None),
@@ -967,10 +867,7 @@ class Renderer:
         rows, nx = getattr(self, "_accum_shape", (0, 0))
         img = np.zeros((rows, nx, 3), dtype=np.float32)
         sem = np.zeros((rows, nx), dtype=np.float32) if want_sem else None
-        rc = self._lib.rt_accum_read_halves(self._ctx, int(h), img.ctypes.data_as(C.POINTER(C.c_float)),
-                                            sem.ctypes.data_as(C.POINTER(C.c_float)) if want_sem else None)
-        if rc != 0:
-            self._raise("rt_accum_read_halves", rc)
+        self._call("rt_accum_read_halves", int(h), img.ctypes.data_as(C.POINTER(C.c_float)), sem.ctypes.data_as(C.POINTER(C.c_float)) if want_sem else None)
         return img, sem
 
     def accum_denoise_halves(self, radius=5, patch=1, strength=None, want_rgb8=False, want_err=False):
@@ -981,9 +878,7 @@ class Renderer:
         img, rgb8, err, ptrs = self._accum_outputs(want_rgb8, want_err)
         res = RtResidual()
         dn = RtDenoise(int(radius), int(patch), float(_ffi.DENOISE_HALVES_DEFAULT_STRENGTH if strength is None else strength), 0)
-        rc = self._lib.rt_accum_denoise_halves(self._ctx, C.byref(dn), ptrs[0], ptrs[1], ptrs[2], C.byref(res))
-        if rc != 0:
-            self._raise("rt_accum_denoise_halves", rc)
+        self._call("rt_accum_denoise_halves", C.byref(dn), ptrs[0], ptrs[1], ptrs[2], C.byref(res))
         return img, rgb8, err, res
 
     def accum_export_halves(self):
@@ -991,9 +886,7 @@ class Renderer:
         rows, nx = getattr(self, "_accum_shape", (0, 0))
         halves = AccumHalves(nx, rows)
         hs = halves.as_struct()
-        rc = self._lib.rt_accum_export_halves(self._ctx, C.byref(hs))
-        if rc != 0:
-            self._raise("rt_accum_export_halves", rc)
+        self._call("rt_accum_export_halves", C.byref(hs))
         halves.first_sample, halves.done, halves.frame_id = hs.first_sample, hs.done, hs.frame_id
         return halves
 
@@ -1001,16 +894,12 @@ class Renderer:
         """rt_accum_import_halves: puts an AccumHalves into the accumulation just begun — fresh, or right after accum_import of the state it
         belongs to — and turns tracking on."""
         hs = halves.as_struct()
-        rc = self._lib.rt_accum_import_halves(self._ctx, C.byref(hs))
-        if rc != 0:
-            self._raise("rt_accum_import_halves", rc)
+        self._call("rt_accum_import_halves", C.byref(hs))
 
     def accum_track_buckets(self, M):
         """rt_accum_track_buckets: the open accumulation also keeps the samples of every pixel in M buckets by sample index (12 M bytes per
         pixel, 3 <= M <= 16); right after accum_begin, before the first add.  Everything else the accumulation returns stays bit for bit."""
-        rc = self._lib.rt_accum_track_buckets(self._ctx, int(M))
-        if rc != 0:
-            self._raise("rt_accum_track_buckets", rc)
+        self._call("rt_accum_track_buckets", int(M))
 
     @staticmethod
     def _robust(mode, trim):
@@ -1029,9 +918,7 @@ class Renderer:
         rgb8 = np.zeros((rows, nx, 3), dtype=np.uint8) if want_rgb8 else None
         u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None
         rb, info = self._robust(mode, trim), _ffi.RtRobustInfo()
-        rc = self._lib.rt_accum_read_robust(self._ctx, C.byref(rb), img.ctypes.data_as(C.POINTER(C.c_float)), u8(rgb8), u8(t), C.byref(info))
-        if rc != 0:
-            self._raise("rt_accum_read_robust", rc)
+        self._call("rt_accum_read_robust", C.byref(rb), img.ctypes.data_as(C.POINTER(C.c_float)), u8(rgb8), u8(t), C.byref(info))
         return (img, info) + ((t,) if want_trim else ()) + ((rgb8,) if want_rgb8 else ())
 
     def accum_denoise_robust(self, mode="gini", trim=0, radius=5, patch=1, strength=None, want_rgb8=False):
@@ -1039,23 +926,17 @@ class Renderer:
         Returns (img [rows, nx, 3] f32, rgb8 or None)."""
         img, rgb8, _, ptrs = self._accum_outputs(want_rgb8, False)
         rb = self._robust(mode, trim)
-        rc = self._lib.rt_accum_denoise_robust(self._ctx, C.byref(rb), self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
-        if rc != 0:
-            self._raise("rt_accum_denoise_robust", rc)
+        self._call("rt_accum_denoise_robust", C.byref(rb), self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
         return img, rgb8
 
     def accum_export_buckets(self):
         """rt_accum_export_buckets: the sample buckets of the open accumulation as an AccumBuckets.  Read, not changed."""
         rows, nx = getattr(self, "_accum_shape", (0, 0))
         probe = _ffi.RtAccumBuckets()
-        rc = self._lib.rt_accum_export_buckets(self._ctx, C.byref(probe))  # the scalar fields only: M
-        if rc != 0:
-            self._raise("rt_accum_export_buckets", rc)
+        self._call("rt_accum_export_buckets", C.byref(probe))  # the scalar fields only: M
         buckets = AccumBuckets(nx, rows, probe.M)
         bs = buckets.as_struct()
-        rc = self._lib.rt_accum_export_buckets(self._ctx, C.byref(bs))
-        if rc != 0:
-            self._raise("rt_accum_export_buckets", rc)
+        self._call("rt_accum_export_buckets", C.byref(bs))
         buckets.first_sample, buckets.done, buckets.frame_id = bs.first_sample, bs.done, bs.frame_id
         return buckets
 
@@ -1063,9 +944,7 @@ class Renderer:
         """rt_accum_import_buckets: puts an AccumBuckets into the accumulation just begun — fresh, or right after accum_import (and
         accum_import_halves) of the state it belongs to — and turns tracking on."""
         bs = buckets.as_struct()
-        rc = self._lib.rt_accum_import_buckets(self._ctx, C.byref(bs))
-        if rc != 0:
-            self._raise("rt_accum_import_buckets", rc)
+        self._call("rt_accum_import_buckets", C.byref(bs))
 
     def render_to_residual(self, camera, params, target, step, radius=5, patch=1, strength=None, want_rgb8=False, want_err=False):
         """Renders until the DENOISED frame is clean: an accumulation that tracks halves gets adds of `step` samples (the first one at least
@@ -1108,34 +987,26 @@ class Renderer:
         """rt_set_lens: the thin lens of the following renders — an RtLens, a (lens_radius, focus_dist) pair or Scene.lens;
         lens_radius = aperture / 2 of the book's Camera::new.  None or lens_radius 0: the pinhole.  Per context, and like the
         camera it is passed, not taken from the uploaded scene."""
-        rc = self._lib.rt_set_lens(self._ctx, _lens_ptr(lens))
-        if rc != 0:
-            self._raise("rt_set_lens", rc)
+        self._call("rt_set_lens", _lens_ptr(lens))
 
     def set_motion(self, motion):
         """rt_set_motion: the moving spheres of the following renders — Scene.motion, make_motion(..) or a (spheres, center1[, shutter])
         tuple; None: the static renderer.  After upload(); upload() clears it."""
         if motion is not None and not isinstance(motion, RtMotion):
             motion = make_motion(*motion)
-        rc = self._lib.rt_set_motion(self._ctx, _motion_ptr(motion))
-        if rc != 0:
-            self._raise("rt_set_motion", rc)
+        self._call("rt_set_motion", _motion_ptr(motion))
         self._n_moving = motion.n_moving if motion is not None else 0  # (motion_bounds sizes its cell table by it)
 
     def set_quads(self, quads):
         """rt_set_quads: the planar primitives (quads, triangles) of the following renders — Scene.quads, make_quads(..) or a
         (q, u, v, kind, mat) tuple; None: none.  After upload(); upload() clears them.  Not together with set_motion."""
-        rc = self._lib.rt_set_quads(self._ctx, _quads_ptr(quads))
-        if rc != 0:
-            self._raise("rt_set_quads", rc)
+        self._call("rt_set_quads", _quads_ptr(quads))
 
     def set_lights(self, lights):
         """rt_set_lights: light importance sampling for the following renders — Scene.lights, make_lights(..) or a (q, u, v) tuple of
         world-space parallelograms; None: none.  After upload(); upload() clears it.  The lights are sampling targets only: any set gives
         the same mean, the one that covers the emitters gives less noise.  Not together with set_motion."""
-        rc = self._lib.rt_set_lights(self._ctx, _lights_ptr(lights))
-        if rc != 0:
-            self._raise("rt_set_lights", rc)
+        self._call("rt_set_lights", _lights_ptr(lights))
 
     def motion_bounds(self):
         """rt_debug_motion_bounds as a dict: the bounds set_motion built (padded entry boxes, candidate-list spheres, entry ids, the
@@ -1151,21 +1022,16 @@ class Renderer:
         ids = np.zeros(n.value, np.uint32)
         cells = np.zeros(max(nc.value, 1), np.uint32)
         begin = np.zeros(getattr(self, "_n_moving", 0) + 1, np.uint32)  # the call writes n_moving + 1 entries
-        rc = self._lib.rt_debug_motion_bounds(self._ctx, boxes.ctypes.data, bs.ctypes.data, ids.ctypes.data, n.value, C.byref(n), grid, dims,
-                                              begin.ctypes.data, cells.ctypes.data, cells.size, C.byref(nc))
-        if rc != 0:
-            self._raise("rt_debug_motion_bounds", rc)
+        self._call("rt_debug_motion_bounds", boxes.ctypes.data, bs.ctypes.data, ids.ctypes.data, n.value, C.byref(n), grid, dims,
+                   begin.ctypes.data, cells.ctypes.data, cells.size, C.byref(nc))
         return {"entry_box_padded": boxes, "entry_sphere": bs, "entry_id": ids, "grid_min": np.array(grid[0:3], np.float32),
                 "grid_cell": np.array(grid[3:6], np.float32), "grid_dims": tuple(dims), "cell_begin": begin, "cell_id": cells[:nc.value]}
 
     def render_device(self, camera, params, device_ptr, stream=None, want_stats=True):
         """Renders into HBM at `device_ptr` (e.g. torch_tensor.data_ptr()); nothing crosses PCIe."""
         stats = RtStats()
-        rc = self._lib.rt_render_device(self._ctx, C.byref(camera), C.byref(params), C.c_void_p(device_ptr),
-                                        C.c_void_p(stream) if stream else None,
-                                        C.byref(stats) if want_stats else None)
-        if rc != 0:
-            self._raise("rt_render_device", rc)
+        self._call("rt_render_device", C.byref(camera), C.byref(params), C.c_void_p(device_ptr), C.c_void_p(stream) if stream else None,
+                   C.byref(stats) if want_stats else None)
         return stats
 
     def render_parts(self):
@@ -1207,9 +1073,7 @@ class Renderer:
         io.out_t, io.out_radiance, io.out_attenuation = fp(out["t"]), fp(out["radiance"]), fp(out["attenuation"])
         io.out_o, io.out_d = fp(out["o"]), fp(out["d"])
         io.out_alive = out["alive"].ctypes.data_as(C.POINTER(C.c_uint8))
-        rc = self._lib.rt_debug_bounce(self._ctx, C.byref(io))
-        if rc != 0:
-            self._raise("rt_debug_bounce", rc)
+        self._call("rt_debug_bounce", C.byref(io))
         return out
 
     def debug_shared_division(self, x, a):
@@ -1254,18 +1118,13 @@ class Renderer:
         assert x.shape == a.shape
         out = np.zeros_like(x)
         fp = lambda v: v.ctypes.data_as(C.POINTER(C.c_float))
-        rc = self._lib.rt_debug_arithmetic(self._ctx, op, len(x), fp(x), fp(a), fp(out))
-        if rc != 0:
-            self._raise("rt_debug_arithmetic", rc)
+        self._call("rt_debug_arithmetic", op, len(x), fp(x), fp(a), fp(out))
         return out
 
     def deinterleave_bands(self, d_gathered, nx, ny, band, n_shards, d_out_f32=None, d_out_u8=None, stream=None):
         """rt_deinterleave_bands on device pointers (ints): gathered band buffers -> frame in image row order."""
-        rc = self._lib.rt_deinterleave_bands(self._ctx, C.c_void_p(d_gathered), nx, ny, band, n_shards,
-                                             C.c_void_p(d_out_f32) if d_out_f32 else None, C.c_void_p(d_out_u8) if d_out_u8 else None,
-                                             C.c_void_p(stream) if stream else None)
-        if rc != 0:
-            self._raise("rt_deinterleave_bands", rc)
+        self._call("rt_deinterleave_bands", C.c_void_p(d_gathered), nx, ny, band, n_shards, C.c_void_p(d_out_f32) if d_out_f32 else None,
+                   C.c_void_p(d_out_u8) if d_out_u8 else None, C.c_void_p(stream) if stream else None)
 
     def close(self):
         if self._ctx:

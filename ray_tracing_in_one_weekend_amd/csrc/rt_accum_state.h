@@ -82,21 +82,4 @@ inline size_t accum_state_pixel_bytes(uint32_t planes) {
 }
 inline uint64_t accum_state_bytes(uint64_t npix, uint32_t planes) { return npix * accum_state_pixel_bytes(planes); }
 
-// Where the planes of npix pixels lie in one staging buffer in image order: the 16 B aligned ones first, so that every plane keeps the
-// alignment of its element behind a base aligned to 16 B (moments and channel moments 16, sum and counts 4).
-struct StateStaging {
-    size_t moments, channels, sum, counts, flags, total;
-};
-inline StateStaging accum_state_staging(uint64_t npix, uint32_t planes) {
-    StateStaging s{};
-    size_t off = 0;
-    s.moments = off, off += (size_t)npix * RT_STATE_MOMENT_BYTES;
-    s.channels = off, off += (planes & RT_ACCUM_STATE_CHANNELS) ? (size_t)npix * RT_STATE_CHANNEL_BYTES : 0u;
-    s.sum = off, off += (size_t)npix * RT_STATE_SUM_BYTES;
-    s.counts = off, off += (planes & RT_ACCUM_STATE_COUNTS) ? (size_t)npix * RT_STATE_COUNT_BYTES : 0u;
-    s.flags = off, off += (planes & RT_ACCUM_STATE_COUNTS) ? (size_t)npix * RT_STATE_FLAG_BYTES : 0u;
-    s.total = off;
-    return s;
-}
-
 } // namespace rt

@@ -151,17 +151,17 @@ struct RtCtx {
     // accum_chsem: staging of out_sem_rgb; dn_cv: the inputs of rt_accum_denoise_channels, (c, v) x 3 per pixel in image order, 24 B
     DevBuf accum_chm, accum_chsem, dn_cv;
     // rt_accum_track_halves (rt_halves.h): per half a plane of f32 x 3 sums and one of f64 x 2 moments, 56 B per pixel, each in the order of
-    // accum_sum (rt_halves_plan.h: halves_layout); halves_stage: the same planes in image order (a state of halves) and the staging of
-    // rt_accum_read_halves; dn_halves: what rt_accum_denoise_halves needs beside dn_c, dn_yv and dn_out (the second half's inputs and filter
-    // output, out, e: 48 B per pixel, the partial sums and the three frame figures)
-    DevBuf accum_halves, halves_stage, dn_halves;
+    // accum_sum (rt_halves_plan.h: halves_layout); dn_halves: what rt_accum_denoise_halves needs beside dn_c, dn_yv and dn_out (the second
+    // half's inputs and filter output, out, e: 48 B per pixel, the partial sums and the three frame figures)
+    DevBuf accum_halves, dn_halves;
     double* h_resid = nullptr;   // page-locked: mean_luminance, residual_rms, residual_noise as k_halves_final wrote them
     // rt_accum_track_buckets (rt_buckets.h): M planes of f32 x 3 sums, 12 M B per pixel, each in the order of accum_sum (rt_buckets_plan.h);
-    // buckets_stage: the same planes in image order (a state of buckets); robust_out: what a robust read-out writes — out (12 B) and the
-    // trims (3 B) per pixel in image order, the partial sums and the frame figures
-    DevBuf accum_buckets, buckets_stage, robust_out;
+    // robust_out: what a robust read-out writes — out (12 B) and the trims (3 B) per pixel in image order, the partial sums and the frame figures
+    DevBuf accum_buckets, robust_out;
     RtRobustInfo* h_robust = nullptr; // page-locked: the figures as k_robust_final wrote them
-    DevBuf accum_stage;          // rt_accum_export / _import / _merge: the planes of a state in image order (rt_accum_state.h: accum_state_staging), at most 81 B per pixel
+    // The one staging buffer of every export, import and merge: the planes of a state, of the halves or of the buckets in image order
+    // (rt_accum_planes.h: planes_place), at most 192 B per pixel; rt_accum_read_halves borrows it for its two outputs
+    DevBuf accum_stage;
     DevBuf dn_c, dn_yv, dn_out;  // rt_accum_denoise: the filter's inputs (c 12 B, (y, v) 8 B) and its output (12 B) per pixel, in image order
     // Host-side timeline of the last trace_samples and what its caller enqueued behind it (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
     // render of a process is where allocations, code-object loads and the queue probe happen; this says which.
@@ -755,8 +755,8 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->accum_sum), free_buf(ctx->accum_mom), free_buf(ctx->accum_sem), free_buf(ctx->accum_partials);
     free_buf(ctx->accum_cnt), free_buf(ctx->accum_flag), free_buf(ctx->accum_info), free_buf(ctx->accum_cnt_out);
     free_buf(ctx->accum_stage);
-    free_buf(ctx->accum_halves), free_buf(ctx->halves_stage), free_buf(ctx->dn_halves);
-    free_buf(ctx->accum_buckets), free_buf(ctx->buckets_stage), free_buf(ctx->robust_out);
+    free_buf(ctx->accum_halves), free_buf(ctx->dn_halves);
+    free_buf(ctx->accum_buckets), free_buf(ctx->robust_out);
     if (ctx->h_resid) (void)hipHostFree(ctx->h_resid);
     if (ctx->h_robust) (void)hipHostFree(ctx->h_robust);
     if (ctx->h_info) (void)hipHostFree(ctx->h_info);
@@ -1843,37 +1843,56 @@ int rt_debug_denoise_channels(RtCtx* ctx, uint32_t nx, uint32_t rows, const floa
 uint64_t rt_accum_frame_id(const RtCamera* cam, const RtParams* prm) { return cam && prm ? accum_frame_id(*cam, *prm) : 0ull; }
 int rt_accum_state_check(const RtAccumState* st) { return accum_state_invalid(st) ? RT_ERR_INVALID : RT_OK; }
 
-// The accumulation's planes and the staging planes of a state with `planes`, carved from ctx->accum_stage (grown on demand, kept).
+// ---- snapshots as plane tables (csrc/rt_accum_planes.h): what the three exports, the three imports and the merge share ---------------------
+static SnapshotHeader accum_header(const RtCtx::Accum& a) { return SnapshotHeader{a.nx, a.rows, a.first, a.done, accum_frame_id(a.cam, a.prm)}; }
 static AccumPlanes accum_planes(RtCtx* ctx) {
     return AccumPlanes{(float*)ctx->accum_sum.p, (double2*)ctx->accum_mom.p, (uint32_t*)ctx->accum_cnt.p, (uint8_t*)ctx->accum_flag.p,
                        (double2*)ctx->accum_chm.p};
 }
-static int stage_planes(RtCtx* ctx, uint32_t npix, uint32_t planes, StagedPlanes& s) {
-    const StateStaging lay = accum_state_staging(npix, planes);
-    if (const int rc = ensure(ctx, ctx->accum_stage, lay.total)) return rc;
-    char* base = (char*)ctx->accum_stage.p;
-    s = StagedPlanes{(float*)(base + lay.sum), (double2*)(base + lay.moments), (uint32_t*)(base + lay.counts), (uint8_t*)(base + lay.flags),
-                     (double2*)(base + lay.channels)};
+// The table of a state over the open accumulation's planes.  (A table holds device pointers: it is built behind every ensure_*.)
+static PlaneTable state_table(RtCtx* ctx, const RtAccumState& st, bool counts, bool channels) {
+    const AccumPlanes ap = accum_planes(ctx);
+    return state_planes(st, counts, channels, ap.sum, ap.mom, ap.cnt, ap.flag, ap.chm);
+}
+// Places the table of the open accumulation (npix >= 1) in ctx->accum_stage, grown on demand and kept.
+static int planes_stage(RtCtx* ctx, PlaneTable& t) {
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return ensure(ctx, ctx->accum_stage, planes_place(t, ctx->accum.npix));
+}
+static void launch_planes_move(RtCtx* ctx, const PlaneTable& t, bool to_staging) {
+    const RtCtx::Accum& a = ctx->accum;
+    const dim3 grid((a.npix + 255u) / 256u), block(256);
+    char* stage = ctx->accum_stage.as<char>();
+    if (to_staging) hipLaunchKernelGGL(k_planes_move<true>, grid, block, 0, ctx->stream, t, stage, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+    else hipLaunchKernelGGL(k_planes_move<false>, grid, block, 0, ctx->stream, t, stage, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+}
+// The accumulation's planes -> the caller's arrays, the rows without one left out; complete on return.
+static int planes_to_host(RtCtx* ctx, PlaneTable& t) {
+    if (const int rc = planes_stage(ctx, t)) return rc;
+    launch_planes_move(ctx, t, true);
+    RT_HIP(ctx, hipGetLastError());
+    for (uint32_t k = 0; k < t.n; ++k)
+        if (const Plane& p = t.row[k]; p.host)
+            RT_HIP(ctx, hipMemcpyAsync(p.host, ctx->accum_stage.as<char>() + p.stage, plane_bytes(p, ctx->accum.npix), hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
-// What rt_accum_import and rt_accum_merge both ask of a state against the open accumulation `a`, beyond accum_state_invalid: NULL or the
-// mismatch.  (Which first_sample fits is each caller's own question.)
-static const char* state_mismatch(const RtCtx::Accum& a, const RtAccumState& st) {
-    if (st.nx != a.nx || st.rows != a.rows) return "nx and rows of the state are not the accumulation's";
-    if (st.frame_id != accum_frame_id(a.cam, a.prm)) return "frame_id of the state is not rt_accum_frame_id of the accumulation's camera and params";
-    return nullptr;
-}
-// state -> staging planes, enqueued on `st_` in front of the kernel that reads them
-static int upload_state(RtCtx* ctx, const RtAccumState& st, const StagedPlanes& s, uint32_t npix, hipStream_t st_) {
-    RT_HIP(ctx, hipMemcpyAsync(s.sum, st.sum, (size_t)npix * RT_STATE_SUM_BYTES, hipMemcpyHostToDevice, st_));
-    RT_HIP(ctx, hipMemcpyAsync(s.mom, st.moments, (size_t)npix * RT_STATE_MOMENT_BYTES, hipMemcpyHostToDevice, st_));
-    if (st.planes & RT_ACCUM_STATE_COUNTS) {
-        RT_HIP(ctx, hipMemcpyAsync(s.cnt, st.counts, (size_t)npix * RT_STATE_COUNT_BYTES, hipMemcpyHostToDevice, st_));
-        RT_HIP(ctx, hipMemcpyAsync(s.flag, st.converged, (size_t)npix * RT_STATE_FLAG_BYTES, hipMemcpyHostToDevice, st_));
-    }
-    if (st.planes & RT_ACCUM_STATE_CHANNELS)
-        RT_HIP(ctx, hipMemcpyAsync(s.chm, st.channel_moments, (size_t)npix * RT_STATE_CHANNEL_BYTES, hipMemcpyHostToDevice, st_));
+// The caller's arrays -> the accumulation's planes, complete on return (the caller's arrays are free again).  move = false: into the
+// staging buffer only, enqueued; the caller launches what reads it behind that and waits.
+static int planes_from_host(RtCtx* ctx, PlaneTable& t, bool move) {
+    if (const int rc = planes_stage(ctx, t)) return rc;
+    for (uint32_t k = 0; k < t.n; ++k)
+        RT_HIP(ctx, hipMemcpyAsync(ctx->accum_stage.as<char>() + t.row[k].stage, t.row[k].host, plane_bytes(t.row[k], ctx->accum.npix), hipMemcpyHostToDevice, ctx->stream));
+    if (!move) return RT_OK;
+    launch_planes_move(ctx, t, false);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
+}
+// What every import and the merge refuse of a well-formed snapshot that does not fit the open accumulation.
+static int require_match(RtCtx* ctx, const char* who, const SnapshotHeader& s, const char* noun, SnapshotWindow window) {
+    const std::string why = snapshot_mismatch(accum_header(ctx->accum), s, noun, window);
+    return why.empty() ? RT_OK : fail(ctx, RT_ERR_INVALID, std::string(who) + ": " + why);
 }
 
 int rt_accum_export(RtCtx* ctx, RtAccumState* st) {
@@ -1883,71 +1902,40 @@ int rt_accum_export(RtCtx* ctx, RtAccumState* st) {
     if (const int rc = require_open(ctx, "rt_accum_export")) return rc;
     if (st->channel_moments && !a.channels)
         return fail(ctx, RT_ERR_STATE, "rt_accum_export: channel_moments asked of an accumulation that does not track channels (rt_accum_track_channels)");
-    const uint32_t npix = a.npix;
     const bool want_counts = st->counts || st->converged;
-    if (npix && (st->sum || st->moments || want_counts || st->channel_moments)) { // (no pointer at all: the scalar fields only, no device work)
-        RT_HIP(ctx, hipSetDevice(ctx->device));
-        const hipStream_t s_ = ctx->stream;
-        const bool counts = a.adaptive && want_counts, channels = st->channel_moments != nullptr;
-        StagedPlanes s;
-        if (const int rc = stage_planes(ctx, npix, (counts ? RT_ACCUM_STATE_COUNTS : 0u) | (channels ? RT_ACCUM_STATE_CHANNELS : 0u), s)) return rc;
-        const AccumPlanes ap = accum_planes(ctx);
-        const dim3 grid((npix + 255u) / 256u), block(256);
-        if (counts && channels) hipLaunchKernelGGL((k_accum_export<true, true>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-        else if (counts) hipLaunchKernelGGL((k_accum_export<true, false>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-        else if (channels) hipLaunchKernelGGL((k_accum_export<false, true>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-        else hipLaunchKernelGGL((k_accum_export<false, false>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-        RT_HIP(ctx, hipGetLastError());
-        if (st->sum) RT_HIP(ctx, hipMemcpyAsync(st->sum, s.sum, (size_t)npix * RT_STATE_SUM_BYTES, hipMemcpyDeviceToHost, s_));
-        if (st->moments) RT_HIP(ctx, hipMemcpyAsync(st->moments, s.mom, (size_t)npix * RT_STATE_MOMENT_BYTES, hipMemcpyDeviceToHost, s_));
-        if (counts && st->counts) RT_HIP(ctx, hipMemcpyAsync(st->counts, s.cnt, (size_t)npix * RT_STATE_COUNT_BYTES, hipMemcpyDeviceToHost, s_));
-        if (counts && st->converged) RT_HIP(ctx, hipMemcpyAsync(st->converged, s.flag, (size_t)npix * RT_STATE_FLAG_BYTES, hipMemcpyDeviceToHost, s_));
-        if (channels) RT_HIP(ctx, hipMemcpyAsync(st->channel_moments, s.chm, (size_t)npix * RT_STATE_CHANNEL_BYTES, hipMemcpyDeviceToHost, s_));
-        RT_HIP(ctx, hipStreamSynchronize(s_));
+    if (a.npix && (st->sum || st->moments || want_counts || st->channel_moments)) { // (no pointer at all: the scalar fields only, no device work)
+        PlaneTable t = state_table(ctx, *st, a.adaptive && want_counts, st->channel_moments != nullptr);
+        if (const int rc = planes_to_host(ctx, t)) return rc;
         if (!a.adaptive) { // uniform: every pixel holds `done` samples and is active (rt_accum_read_counts)
-            if (st->counts) std::fill(st->counts, st->counts + npix, a.done);
-            if (st->converged) std::fill(st->converged, st->converged + npix, (uint8_t)0u);
+            if (st->counts) std::fill(st->counts, st->counts + a.npix, a.done);
+            if (st->converged) std::fill(st->converged, st->converged + a.npix, (uint8_t)0u);
         }
     }
-    st->nx = a.nx, st->rows = a.rows, st->first_sample = a.first, st->done = a.done;
+    snapshot_header_put(*st, accum_header(a));
     st->planes = (a.adaptive ? RT_ACCUM_STATE_COUNTS : 0u) | (a.channels ? RT_ACCUM_STATE_CHANNELS : 0u);
     st->reserved = 0u;
-    st->frame_id = accum_frame_id(a.cam, a.prm);
     return RT_OK;
 }
 
 int rt_accum_import(RtCtx* ctx, const RtAccumState* st) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
-    if (const int rc = require_open(ctx, "rt_accum_import")) return rc;
+    int rc;
+    if ((rc = require_open(ctx, "rt_accum_import"))) return rc;
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks halves already (import the state first, then rt_accum_import_halves)");
     if (a.buckets) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks buckets already (import the state first, then rt_accum_import_buckets)");
     if (a.done != 0u || a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_import: samples were added already (call it right after rt_accum_begin)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import: ") + why);
-    if (const char* why = state_mismatch(a, *st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import: ") + why);
-    if (st->first_sample != a.first) return fail(ctx, RT_ERR_INVALID, "rt_accum_import: first_sample of the state is not the accumulation's");
+    if ((rc = require_match(ctx, "rt_accum_import", snapshot_header(*st), "state", SNAPSHOT_FIRST_SAMPLE))) return rc;
     const bool counts = (st->planes & RT_ACCUM_STATE_COUNTS) != 0u, channels = (st->planes & RT_ACCUM_STATE_CHANNELS) != 0u;
     if (a.channels && !channels) return fail(ctx, RT_ERR_INVALID, "rt_accum_import: the accumulation tracks channels and the state holds no channel moments");
-    const uint32_t npix = a.npix;
-    if (npix) {
+    if (a.npix) {
         RT_HIP(ctx, hipSetDevice(ctx->device));
-        const hipStream_t s_ = ctx->stream;
-        const uint32_t nb = (npix + 255u) / 256u;
-        int rc;
         // every allocation first: a failure below this block cannot leave the accumulation half imported
-        if (channels && (rc = ensure_channels(ctx, npix))) return rc;
-        if (counts && (rc = ensure_adaptive(ctx, npix))) return rc;
-        StagedPlanes s;
-        if ((rc = stage_planes(ctx, npix, st->planes, s))) return rc;
-        if ((rc = upload_state(ctx, *st, s, npix, s_))) return rc;
-        const AccumPlanes ap = accum_planes(ctx);
-        const dim3 grid(nb), block(256);
-        if (counts && channels) hipLaunchKernelGGL((k_accum_import<true, true>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-        else if (counts) hipLaunchKernelGGL((k_accum_import<true, false>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-        else if (channels) hipLaunchKernelGGL((k_accum_import<false, true>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-        else hipLaunchKernelGGL((k_accum_import<false, false>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-        RT_HIP(ctx, hipGetLastError());
-        RT_HIP(ctx, hipStreamSynchronize(s_)); // (the caller's arrays are free again)
+        if (channels && (rc = ensure_channels(ctx, a.npix))) return rc;
+        if (counts && (rc = ensure_adaptive(ctx, a.npix))) return rc;
+        PlaneTable t = state_table(ctx, *st, counts, channels);
+        if ((rc = planes_from_host(ctx, t, true))) return rc;
     }
     a.channels = a.channels || channels;
     a.adaptive = counts;
@@ -1958,13 +1946,14 @@ int rt_accum_import(RtCtx* ctx, const RtAccumState* st) {
 int rt_accum_merge(RtCtx* ctx, const RtAccumState* st) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
-    if (const int rc = require_open(ctx, "rt_accum_merge")) return rc;
+    int rc;
+    if ((rc = require_open(ctx, "rt_accum_merge"))) return rc;
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks halves: a merge of halves is not covered (rtow_mi355x.h)");
     if (a.buckets) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks buckets: a merge of buckets is not covered (rtow_mi355x.h)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_merge: ") + why);
     if (a.adaptive || (st->planes & RT_ACCUM_STATE_COUNTS))
         return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: an adaptive accumulation or state: windows of pixels with different sample counts are not contiguous");
-    if (const char* why = state_mismatch(a, *st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_merge: ") + why);
+    if ((rc = require_match(ctx, "rt_accum_merge", snapshot_header(*st), "state", SNAPSHOT_ANY_WINDOW))) return rc;
     if ((uint64_t)st->first_sample != (uint64_t)a.first + a.done)
         return fail(ctx, RT_ERR_INVALID, "rt_accum_merge: the state's window is not adjacent: its first_sample (" + std::to_string(st->first_sample) +
                                              ") must be the accumulation's first_sample + done (" + std::to_string((uint64_t)a.first + a.done) + ")");
@@ -1972,20 +1961,17 @@ int rt_accum_merge(RtCtx* ctx, const RtAccumState* st) {
     if (channels != a.channels) return fail(ctx, RT_ERR_INVALID, "rt_accum_merge: channel moments must be in both the accumulation and the state, or in neither");
     if ((uint64_t)a.first + a.done + st->done > 0xFFFFFFFFull)
         return fail(ctx, RT_ERR_INVALID, "rt_accum_merge: first_sample + the samples merged must stay below 2^32, as RtParams.spp does");
-    const uint32_t npix = a.npix;
-    if (npix) {
-        RT_HIP(ctx, hipSetDevice(ctx->device));
-        const hipStream_t s_ = ctx->stream;
-        StagedPlanes s;
-        int rc;
-        if ((rc = stage_planes(ctx, npix, st->planes, s))) return rc;
-        if ((rc = upload_state(ctx, *st, s, npix, s_))) return rc;
+    if (a.npix) {
+        PlaneTable t = state_table(ctx, *st, false, channels); // rows: sum, moments[, channel_moments]
+        if ((rc = planes_from_host(ctx, t, false))) return rc;
+        char* base = ctx->accum_stage.as<char>();
+        const StagedPlanes s{(float*)(base + t.row[0].stage), (double2*)(base + t.row[1].stage), nullptr, nullptr, channels ? (double2*)(base + t.row[2].stage) : nullptr};
         const AccumPlanes ap = accum_planes(ctx);
-        const dim3 grid((npix + 255u) / 256u), block(256);
-        if (channels) hipLaunchKernelGGL((k_accum_merge<true>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
-        else hipLaunchKernelGGL((k_accum_merge<false>), grid, block, 0, s_, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        const dim3 grid((a.npix + 255u) / 256u), block(256);
+        if (channels) hipLaunchKernelGGL((k_accum_merge<true>), grid, block, 0, ctx->stream, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+        else hipLaunchKernelGGL((k_accum_merge<false>), grid, block, 0, ctx->stream, ap, s, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
         RT_HIP(ctx, hipGetLastError());
-        RT_HIP(ctx, hipStreamSynchronize(s_));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     a.done += st->done, a.added = true;
     return RT_OK;
@@ -2024,8 +2010,8 @@ int rt_accum_read_halves(RtCtx* ctx, uint32_t h, float* out_rgb_f32, float* out_
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
     const uint32_t npix = a.npix;
-    if (const int rc = ensure(ctx, ctx->halves_stage, halves_layout(npix).total)) return rc;
-    float* d_rgb = ctx->halves_stage.as<float>(); // (staging: 12 B + 4 B of the 56 B per pixel a state of halves takes there)
+    if (const int rc = ensure(ctx, ctx->accum_stage, (size_t)npix * 4 * sizeof(float))) return rc;
+    float* d_rgb = ctx->accum_stage.as<float>(); // (borrowed: 12 B + 4 B per pixel of the buffer the exports and imports stage in)
     float* d_sem = d_rgb + 3 * (size_t)npix;
     const HalfPlanes hp = half_planes(ctx->accum_halves, npix);
     const AccumReader r = accum_reader(ctx, st);
@@ -2084,58 +2070,33 @@ int rt_accum_export_halves(RtCtx* ctx, RtAccumHalves* hs) {
     if (!hs) return fail(ctx, RT_ERR_INVALID, "rt_accum_export_halves: the RtAccumHalves is NULL");
     if (const int rc = require_open(ctx, "rt_accum_export_halves")) return rc;
     if (!a.halves) return fail(ctx, RT_ERR_STATE, "rt_accum_export_halves: the accumulation does not track halves (rt_accum_track_halves)");
-    const uint32_t npix = a.npix;
-    if (npix && (hs->sum[0] || hs->sum[1] || hs->moments[0] || hs->moments[1])) {
-        RT_HIP(ctx, hipSetDevice(ctx->device));
-        const hipStream_t s_ = ctx->stream;
-        if (const int rc = ensure(ctx, ctx->halves_stage, halves_layout(npix).total)) return rc;
-        const HalfPlanes s = half_planes(ctx->halves_stage, npix);
-        hipLaunchKernelGGL(k_halves_export, dim3((npix + 255u) / 256u), dim3(256), 0, s_, half_planes(ctx->accum_halves, npix), s, a.nx, a.rows, a.tiles_per_row,
-                           a.tile_pixels);
-        RT_HIP(ctx, hipGetLastError());
-        for (int h = 0; h < 2; ++h) {
-            if (hs->sum[h]) RT_HIP(ctx, hipMemcpyAsync(hs->sum[h], s.sum[h], (size_t)npix * RT_HALVES_SUM_BYTES, hipMemcpyDeviceToHost, s_));
-            if (hs->moments[h]) RT_HIP(ctx, hipMemcpyAsync(hs->moments[h], s.mom[h], (size_t)npix * RT_HALVES_MOMENT_BYTES, hipMemcpyDeviceToHost, s_));
-        }
-        RT_HIP(ctx, hipStreamSynchronize(s_));
+    if (a.npix && (hs->sum[0] || hs->sum[1] || hs->moments[0] || hs->moments[1])) {
+        PlaneTable t = halves_planes(*hs, ctx->accum_halves.p, a.npix);
+        if (const int rc = planes_to_host(ctx, t)) return rc;
     }
-    hs->nx = a.nx, hs->rows = a.rows, hs->first_sample = a.first, hs->done = a.done;
+    snapshot_header_put(*hs, accum_header(a));
     hs->reserved[0] = hs->reserved[1] = 0u;
-    hs->frame_id = accum_frame_id(a.cam, a.prm);
     return RT_OK;
 }
 
 int rt_accum_import_halves(RtCtx* ctx, const RtAccumHalves* hs) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
-    if (const int rc = require_open(ctx, "rt_accum_import_halves")) return rc;
+    int rc;
+    if ((rc = require_open(ctx, "rt_accum_import_halves"))) return rc;
     if (a.added) return fail(ctx, RT_ERR_STATE, "rt_accum_import_halves: samples were added since rt_accum_begin (call it right after rt_accum_begin or rt_accum_import)");
     if (const char* why = accum_halves_invalid(hs)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import_halves: ") + why);
-    if (hs->nx != a.nx || hs->rows != a.rows) return fail(ctx, RT_ERR_INVALID, "rt_accum_import_halves: nx and rows of the halves are not the accumulation's");
-    if (hs->frame_id != accum_frame_id(a.cam, a.prm))
-        return fail(ctx, RT_ERR_INVALID, "rt_accum_import_halves: frame_id of the halves is not rt_accum_frame_id of the accumulation's camera and params");
-    if (hs->first_sample != a.first || hs->done != a.done)
-        return fail(ctx, RT_ERR_INVALID, "rt_accum_import_halves: first_sample and done of the halves are not the accumulation's (rt_accum_import comes first)");
-    const uint32_t npix = a.npix;
-    if (npix) {
+    if ((rc = require_match(ctx, "rt_accum_import_halves", snapshot_header(*hs), "halves", SNAPSHOT_FIRST_AND_DONE))) return rc;
+    if (a.npix) {
         RT_HIP(ctx, hipSetDevice(ctx->device));
-        const hipStream_t s_ = ctx->stream;
-        int rc;
-        if ((rc = ensure_halves(ctx, npix))) return rc; // every allocation first: a failure cannot leave the accumulation half imported
-        if ((rc = ensure(ctx, ctx->halves_stage, halves_layout(npix).total))) return rc;
-        const HalfPlanes s = half_planes(ctx->halves_stage, npix);
-        for (int h = 0; h < 2; ++h) {
-            RT_HIP(ctx, hipMemcpyAsync(s.sum[h], hs->sum[h], (size_t)npix * RT_HALVES_SUM_BYTES, hipMemcpyHostToDevice, s_));
-            RT_HIP(ctx, hipMemcpyAsync(s.mom[h], hs->moments[h], (size_t)npix * RT_HALVES_MOMENT_BYTES, hipMemcpyHostToDevice, s_));
-        }
-        hipLaunchKernelGGL(k_halves_import, dim3((npix + 255u) / 256u), dim3(256), 0, s_, half_planes(ctx->accum_halves, npix), s, a.nx, a.rows, a.tiles_per_row,
-                           a.tile_pixels);
-        RT_HIP(ctx, hipGetLastError());
-        RT_HIP(ctx, hipStreamSynchronize(s_)); // (the caller's arrays are free again)
+        if ((rc = ensure_halves(ctx, a.npix))) return rc; // every allocation first: a failure cannot leave the accumulation half imported
+        PlaneTable t = halves_planes(*hs, ctx->accum_halves.p, a.npix);
+        if ((rc = planes_from_host(ctx, t, true))) return rc;
     }
     a.halves = true;
     return RT_OK;
 }
+
 
 // ---- sample buckets (rtow_mi355x.h "Sample buckets", csrc/rt_buckets.h, csrc/rt_buckets_plan.h) --------------------------------------------
 int rt_accum_buckets_check(const RtAccumBuckets* bs) { return accum_buckets_invalid(bs) ? RT_ERR_INVALID : RT_OK; }
@@ -2249,56 +2210,34 @@ int rt_accum_export_buckets(RtCtx* ctx, RtAccumBuckets* bs) {
     if (!bs) return fail(ctx, RT_ERR_INVALID, "rt_accum_export_buckets: the RtAccumBuckets is NULL");
     if (const int rc = require_open(ctx, "rt_accum_export_buckets")) return rc;
     if (!a.buckets) return fail(ctx, RT_ERR_STATE, "rt_accum_export_buckets: the accumulation does not track buckets (rt_accum_track_buckets)");
-    const uint32_t npix = a.npix, M = a.buckets;
-    bool any = false;
-    for (uint32_t b = 0; b < M; ++b) any = any || bs->sum[b];
-    if (npix && any) {
-        RT_HIP(ctx, hipSetDevice(ctx->device));
-        const hipStream_t s_ = ctx->stream;
-        if (const int rc = ensure(ctx, ctx->buckets_stage, buckets_total(npix, M))) return rc;
-        hipLaunchKernelGGL(k_buckets_export, dim3((npix + 255u) / 256u), dim3(256), 0, s_, ctx->accum_buckets.as<const float>(), ctx->buckets_stage.as<float>(), M, a.nx, a.rows,
-                           a.tiles_per_row, a.tile_pixels);
-        RT_HIP(ctx, hipGetLastError());
-        for (uint32_t b = 0; b < M; ++b)
-            if (bs->sum[b])
-                RT_HIP(ctx, hipMemcpyAsync(bs->sum[b], ctx->buckets_stage.as<char>() + buckets_plane(npix, b), (size_t)npix * RT_BUCKETS_SUM_BYTES, hipMemcpyDeviceToHost, s_));
-        RT_HIP(ctx, hipStreamSynchronize(s_));
+    if (a.npix && std::any_of(bs->sum, bs->sum + a.buckets, [](const float* s) { return s != nullptr; })) {
+        PlaneTable t = buckets_planes(*bs, a.buckets, ctx->accum_buckets.p, a.npix);
+        if (const int rc = planes_to_host(ctx, t)) return rc;
     }
-    bs->nx = a.nx, bs->rows = a.rows, bs->first_sample = a.first, bs->done = a.done;
-    bs->M = M, bs->reserved = 0u;
-    bs->frame_id = accum_frame_id(a.cam, a.prm);
+    snapshot_header_put(*bs, accum_header(a));
+    bs->M = a.buckets, bs->reserved = 0u;
     return RT_OK;
 }
 
 int rt_accum_import_buckets(RtCtx* ctx, const RtAccumBuckets* bs) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
-    if (const int rc = require_open(ctx, "rt_accum_import_buckets")) return rc;
+    int rc;
+    if ((rc = require_open(ctx, "rt_accum_import_buckets"))) return rc;
     if (a.added) return fail(ctx, RT_ERR_STATE, "rt_accum_import_buckets: samples were added since rt_accum_begin (call it right after rt_accum_begin or rt_accum_import)");
     if (const char* why = accum_buckets_invalid(bs)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import_buckets: ") + why);
-    if (bs->nx != a.nx || bs->rows != a.rows) return fail(ctx, RT_ERR_INVALID, "rt_accum_import_buckets: nx and rows of the buckets are not the accumulation's");
-    if (bs->frame_id != accum_frame_id(a.cam, a.prm))
-        return fail(ctx, RT_ERR_INVALID, "rt_accum_import_buckets: frame_id of the buckets is not rt_accum_frame_id of the accumulation's camera and params");
-    if (bs->first_sample != a.first || bs->done != a.done)
-        return fail(ctx, RT_ERR_INVALID, "rt_accum_import_buckets: first_sample and done of the buckets are not the accumulation's (rt_accum_import comes first)");
+    if ((rc = require_match(ctx, "rt_accum_import_buckets", snapshot_header(*bs), "buckets", SNAPSHOT_FIRST_AND_DONE))) return rc;
     if (a.buckets && a.buckets != bs->M) return fail(ctx, RT_ERR_INVALID, "rt_accum_import_buckets: M of the buckets is not that of the accumulation, which tracks already");
-    const uint32_t npix = a.npix, M = bs->M;
-    if (npix) {
+    if (a.npix) {
         RT_HIP(ctx, hipSetDevice(ctx->device));
-        const hipStream_t s_ = ctx->stream;
-        int rc;
-        if ((rc = ensure_buckets(ctx, npix, M))) return rc; // every allocation first: a failure cannot leave the accumulation half imported
-        if ((rc = ensure(ctx, ctx->buckets_stage, buckets_total(npix, M)))) return rc;
-        for (uint32_t b = 0; b < M; ++b)
-            RT_HIP(ctx, hipMemcpyAsync(ctx->buckets_stage.as<char>() + buckets_plane(npix, b), bs->sum[b], (size_t)npix * RT_BUCKETS_SUM_BYTES, hipMemcpyHostToDevice, s_));
-        hipLaunchKernelGGL(k_buckets_import, dim3((npix + 255u) / 256u), dim3(256), 0, s_, ctx->accum_buckets.as<float>(), ctx->buckets_stage.as<const float>(), M, a.nx, a.rows,
-                           a.tiles_per_row, a.tile_pixels);
-        RT_HIP(ctx, hipGetLastError());
-        RT_HIP(ctx, hipStreamSynchronize(s_)); // (the caller's arrays are free again)
+        if ((rc = ensure_buckets(ctx, a.npix, bs->M))) return rc; // every allocation first: a failure cannot leave the accumulation half imported
+        PlaneTable t = buckets_planes(*bs, bs->M, ctx->accum_buckets.p, a.npix);
+        if ((rc = planes_from_host(ctx, t, true))) return rc;
     }
-    a.buckets = M;
+    a.buckets = bs->M;
     return RT_OK;
 }
+
 
 void* rt_host_alloc(size_t bytes) {
     void* p = nullptr;

@@ -6,7 +6,7 @@
 //   k_robust_read<COUNTS>              : the trimmed mean of the sorted bucket means per pixel and channel, its trim, and the per-workgroup
 //                                        partial sums of the frame figures, in image order
 //   k_robust_final                     : one workgroup over the partials -> RtRobustInfo
-//   k_buckets_export, k_buckets_import : the M planes between the local pixel order and a state's image order, bit for bit
+// (rt_accum_export_buckets and _import_buckets move the M planes as a PlaneTable through k_planes_move, rt_accum_state_kernels.h.)
 //
 // The planes lie one behind the other in one buffer (rt_buckets_plan.h), each npix RGB triples in the accumulation's local pixel order: a
 // lane reads and writes 12 B at stride 12 B per plane, as k_resolve_moments does on the whole-pixel sums.  M is a run-time value
@@ -175,23 +175,6 @@ __global__ __launch_bounds__(256) void k_robust_final(const RobustPartial* __res
     double removed = 1.0 - robust / plain;
     if (plain == 0.0 && robust == 0.0) removed = 0.0;
     *out = RobustFigures{plain, robust, removed, (double)trimmed / (3.0 * (double)npix), dropped};
-}
-
-// The M planes of the accumulation (local pixel order) -> staging planes in image order, and back; one thread per pixel in image order,
-// as k_halves_export / k_halves_import.
-__global__ __launch_bounds__(256) void k_buckets_export(const float* __restrict__ a, float* __restrict__ s, uint32_t M, uint32_t nx, uint32_t rows,
-                                                        uint32_t tiles_per_row, uint32_t tile_pixels) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= nx * rows) return;
-    const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx), plane = (size_t)3u * nx * rows;
-    for (uint32_t b = 0; b < M; ++b) reinterpret_cast<StateRgb*>(s + b * plane)[p] = reinterpret_cast<const StateRgb*>(a + b * plane)[ap];
-}
-__global__ __launch_bounds__(256) void k_buckets_import(float* __restrict__ a, const float* __restrict__ s, uint32_t M, uint32_t nx, uint32_t rows,
-                                                        uint32_t tiles_per_row, uint32_t tile_pixels) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= nx * rows) return;
-    const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx), plane = (size_t)3u * nx * rows;
-    for (uint32_t b = 0; b < M; ++b) reinterpret_cast<StateRgb*>(a + b * plane)[ap] = reinterpret_cast<const StateRgb*>(s + b * plane)[p];
 }
 
 } // namespace rt

@@ -7,7 +7,7 @@
 //   k_denoise_inputs_halves<COUNTS> : c_0, c_1, (y, v)_0, (y, v)_1 in image order — what the two launches of k_denoise<F> read
 //   k_halves_combine<COUNTS>        : out and e per pixel from f_0 and f_1, and the per-workgroup partial sums of the frame figures
 //   k_halves_final                  : one workgroup over the partials -> mean_luminance, residual_rms, residual_noise
-//   k_halves_export, k_halves_import: the four planes between the local pixel order and a state's image order, bit for bit
+// (rt_accum_export_halves and _import_halves move the four planes as a PlaneTable through k_planes_move, rt_accum_state_kernels.h.)
 //
 // HalfPlanes in the accumulation's local pixel order: per half a plane of RGB triples and a plane of double2 (S1, S2).  A lane reads and
 // writes 12 B at stride 12 B and 16 B at stride 16 B per plane, as k_resolve_moments does on the whole-pixel sums.  COUNTS: the pixel's own
@@ -166,27 +166,6 @@ __global__ __launch_bounds__(256) void k_halves_final(const double2* __restrict_
     double noise = rms / mean;
     if (mean == 0.0) noise = rms == 0.0 ? 0.0 : (double)INFINITY;
     out[0] = mean, out[1] = rms, out[2] = noise;
-}
-
-// The four planes of the accumulation (local pixel order) -> staging planes in image order, and back; one thread per pixel in image order,
-// as k_accum_export / k_accum_import.
-__global__ __launch_bounds__(256) void k_halves_export(HalfPlanes a, HalfPlanes s, uint32_t nx, uint32_t rows, uint32_t tiles_per_row, uint32_t tile_pixels) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= nx * rows) return;
-    const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx);
-    for (int h = 0; h < 2; ++h) {
-        reinterpret_cast<StateRgb*>(s.sum[h])[p] = reinterpret_cast<const StateRgb*>(a.sum[h])[ap];
-        s.mom[h][p] = a.mom[h][ap];
-    }
-}
-__global__ __launch_bounds__(256) void k_halves_import(HalfPlanes a, HalfPlanes s, uint32_t nx, uint32_t rows, uint32_t tiles_per_row, uint32_t tile_pixels) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= nx * rows) return;
-    const size_t ap = local_of_pixel(nx, tiles_per_row, tile_pixels, p % nx, p / nx);
-    for (int h = 0; h < 2; ++h) {
-        reinterpret_cast<StateRgb*>(a.sum[h])[ap] = reinterpret_cast<const StateRgb*>(s.sum[h])[p];
-        a.mom[h][ap] = s.mom[h][p];
-    }
 }
 
 } // namespace rt

@@ -1,8 +1,8 @@
-// The GPU-free part of the accumulation state (csrc/rt_accum_state.h) as a stand-alone program: built with AddressSanitizer + UBSan by
+// The GPU-free part of the accumulation state and of its snapshots' plane tables (csrc/rt_accum_state.h, rt_accum_planes.h) as a stand-alone program: built with AddressSanitizer + UBSan by
 // tests/test_accum_state_host.py and run without a GPU.  It prints one line per section — its name and the number of checks made — and
 // "ok"; a failed check prints what failed and ends the program with status 1.  The arrays of every state are exactly as long as the
 // scalar fields say, so a check that reads one element too many is an AddressSanitizer report.
-#include "rt_accum_state.h"
+#include "rt_accum_planes.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -58,6 +58,17 @@ struct Owned {
     }
 };
 
+// A placed table: every plane aligned to its element behind a 16 B base, no two planes overlapping, none beyond `total`.
+static void check_placed(const rt::PlaneTable& t, uint64_t npix, size_t total) {
+    for (uint32_t k = 0; k < t.n; ++k) {
+        const rt::Plane& p = t.row[k];
+        CHECK(p.elem_bytes == 1u || p.elem_bytes == 4u || p.elem_bytes == 12u || p.elem_bytes == 16u);
+        CHECK(p.stage % (p.elem_bytes == 16u ? 16u : p.elem_bytes == 1u ? 1u : 4u) == 0u && p.stage + rt::plane_bytes(p, npix) <= total);
+        for (uint32_t j = 0; j < k; ++j)
+            CHECK(npix == 0u || p.stage + rt::plane_bytes(p, npix) <= t.row[j].stage || t.row[j].stage + rt::plane_bytes(t.row[j], npix) <= p.stage);
+    }
+}
+
 int main() {
     using namespace rt;
     const uint32_t ALL = RT_ACCUM_STATE_COUNTS | RT_ACCUM_STATE_CHANNELS;
@@ -73,12 +84,52 @@ int main() {
             CHECK(accum_state_pixel_bytes(planes) == per && accum_state_bytes(npix, planes) == npix * per);
             CHECK(o.sum.size() * sizeof(float) == npix * RT_STATE_SUM_BYTES && o.mom.size() * sizeof(double) == npix * RT_STATE_MOMENT_BYTES);
             CHECK(o.chm.size() * sizeof(double) == ((planes & RT_ACCUM_STATE_CHANNELS) ? npix * RT_STATE_CHANNEL_BYTES : 0u));
-            const StateStaging lay = accum_state_staging(npix, planes);
-            CHECK(lay.total == npix * per && lay.moments == 0u && lay.moments % 16u == 0u && lay.channels % 16u == 0u && lay.sum % 4u == 0u &&
-                  lay.counts % 4u == 0u);
-            CHECK(lay.channels == npix * 16u && lay.sum >= lay.channels && lay.counts == lay.sum + npix * 12u && lay.flags >= lay.counts &&
-                  lay.total >= lay.flags);
+            // the staging layout of the state's table (rt_accum_planes.h): rows sum, moments[, counts, converged][, channel_moments]
+            const bool counts = (planes & RT_ACCUM_STATE_COUNTS) != 0u, channels = (planes & RT_ACCUM_STATE_CHANNELS) != 0u;
+            PlaneTable t = state_planes(o.st, counts, channels, nullptr, nullptr, nullptr, nullptr, nullptr);
+            CHECK(t.n == 2u + (counts ? 2u : 0u) + (channels ? 1u : 0u) && t.row[0].host == o.st.sum && t.row[1].host == o.st.moments);
+            CHECK(planes_place(t, npix) == npix * per);
+            check_placed(t, npix, npix * per);
+            const size_t sum = t.row[0].stage, moments = t.row[1].stage, after16 = npix * (channels ? 64u : 16u);
+            CHECK(moments == 0u && sum == after16);
+            if (channels) CHECK(t.row[t.n - 1u].stage == npix * 16u && t.row[t.n - 1u].parts == 3u && t.row[t.n - 1u].elem_bytes == 16u);
+            if (counts) CHECK(t.row[2].stage == sum + npix * 12u && t.row[3].stage == t.row[2].stage + npix * 4u && t.row[3].host == o.st.converged);
         }
+    { // the halves' and the buckets' tables: the accumulation's own layouts on the local side, placed without a gap in staging
+        char* const local = reinterpret_cast<char*>(static_cast<uintptr_t>(1) << 32); // (an address to offset from; nothing is read there)
+        for (uint64_t npix : {0ull, 1ull, 255ull, 257ull, 1920ull * 1080ull}) {
+            RtAccumHalves hs{};
+            PlaneTable t = halves_planes(hs, local, npix);
+            const HalvesLayout l = halves_layout(npix);
+            CHECK(t.n == 4u && t.row[1].local == local + l.moments[1] && t.row[3].local == local + l.sum[1] && t.row[3].elem_bytes == 12u);
+            CHECK(planes_place(t, npix) == l.total);
+            check_placed(t, npix, l.total);
+            for (uint32_t M : {3u, 16u}) {
+                RtAccumBuckets bs{};
+                PlaneTable b = buckets_planes(bs, M, local, npix);
+                CHECK(b.n == M && b.row[M - 1u].local == local + buckets_plane(npix, M - 1u) && b.row[M - 1u].host == nullptr);
+                CHECK(planes_place(b, npix) == buckets_total(npix, M));
+                check_placed(b, npix, buckets_total(npix, M));
+            }
+        }
+    }
+    { // one mismatch text per field, with the snapshot's noun; what of the window is compared is the caller's choice
+        const SnapshotHeader a{8u, 4u, 3u, 7u, 99u};
+        CHECK(snapshot_mismatch(a, a, "state", SNAPSHOT_FIRST_AND_DONE).empty());
+        SnapshotHeader s = a;
+        s.rows = 5u;
+        CHECK(snapshot_mismatch(a, s, "halves", SNAPSHOT_ANY_WINDOW) == "nx and rows of the halves are not the accumulation's");
+        s = a, s.frame_id = 98u;
+        CHECK(snapshot_mismatch(a, s, "state", SNAPSHOT_ANY_WINDOW) == "frame_id of the state is not rt_accum_frame_id of the accumulation's camera and params");
+        s = a, s.done = 6u;
+        CHECK(snapshot_mismatch(a, s, "state", SNAPSHOT_ANY_WINDOW).empty() && snapshot_mismatch(a, s, "state", SNAPSHOT_FIRST_SAMPLE).empty());
+        CHECK(snapshot_mismatch(a, s, "buckets", SNAPSHOT_FIRST_AND_DONE) == "first_sample and done of the buckets are not the accumulation's (rt_accum_import comes first)");
+        s = a, s.first_sample = 4u;
+        CHECK(snapshot_mismatch(a, s, "state", SNAPSHOT_FIRST_SAMPLE) == "first_sample of the state is not the accumulation's");
+        RtAccumBuckets bs{};
+        snapshot_header_put(bs, a);
+        CHECK(bs.nx == 8u && bs.rows == 4u && bs.first_sample == 3u && bs.done == 7u && bs.frame_id == 99u && snapshot_header(bs).frame_id == 99u);
+    }
     CHECK(accum_state_pixel_bytes(ALL) == 81u);
     {
         Owned o(65535u, 0u, 0u, 0u); // a shard without rows

@@ -705,3 +705,116 @@ def test_render_py_windows_and_merge(rt, tmp_path):
     # a window that is not adjacent is an error with the library's text
     p = _render_py(tmp_path, "--first-sample", 0, "--spp", 4, "--spp-step", 4, "--merge", w1, "--out", tmp_path / "bad.png")
     assert p.returncode != 0 and "not adjacent" in p.stderr and not (tmp_path / "bad.png").exists(), p.stderr[-2000:]
+
+
+# ---- 11. the one kernel behind the three exports and the three imports (k_planes_move) ----------------------------------------------------
+MOVER_DONE = 16  # every bucket of M = 16 holds a sample, each half 8
+
+
+def _coded(shape, dtype, plane):
+    """Every element a value of its own: its flat index in the image-order array (so part and pixel) + 1 + plane * 2^20.  Exact in f32."""
+    n = int(np.prod(shape))
+    assert n < 2 ** 20 and plane < 15
+    return (np.arange(n, dtype=np.int64) + 1 + (plane << 20)).astype(dtype).reshape(shape)
+
+
+@pytest.mark.parametrize("nx,rows,po", [(24, 19, 1), (24, 19, 2), (21, 13, 2)])
+def test_every_plane_of_every_snapshot_moves_to_its_pixel(rt, ctx, nx, rows, po):
+    """24 x 19 under RT_OPT_PIXEL_ORDER 2: two rows of 8 x 8 tiles and three rows row-major, 456 pixels — one full and one partial workgroup;
+    under 1, and 21 x 13 whatever the option, row-major.  Imports of coded planes come back from the export bit for bit; and since that alone
+    would hold under any permutation the two directions share, the readers, which compute the local index on their own, see every value at
+    its pixel."""
+    import ctypes
+    import robust_ref
+    r, f32 = ctx, np.float32
+    if ("test_sphere", nx, rows) not in _scenes:
+        _scenes["test_sphere", nx, rows] = rt.Scene.build("test_sphere", nx / rows)
+    scene = _scenes["test_sphere", nx, rows]
+    r.set_option("pixel_order", po)
+    try:
+        r.upload(scene)
+        r.set_lens(None)
+        prm = rt.make_params(nx, rows, 1, max_depth=8, seed=SEED)
+        fid = rt.accum_frame_id(scene.camera, prm)
+        sentinel = lambda shape, dt: np.full(shape, -1 if np.dtype(dt).kind == "f" else 0xFF, dt)
+        # ---- a state with counts and channels: every third pixel converged on fewer samples
+        p = np.arange(nx * rows).reshape(rows, nx)
+        conv = (p % 3 == 0).astype(np.uint8)
+        cnt = np.where(conv, p % (MOVER_DONE + 1), MOVER_DONE).astype(np.uint32)
+        full = rt.AccumState(nx, rows, 0, MOVER_DONE, ref.COUNTS | ref.CHANNELS, fid, sum=_coded((rows, nx, 3), f32, 0), moments=_coded((rows, nx, 2), np.float64, 1),
+                             counts=cnt, converged=conv, channel_moments=_coded((rows, nx, 6), np.float64, 2))
+        assert full.check()
+        r.accum_begin(scene.camera, prm)
+        r.accum_import(full)
+        _states_equal(r.accum_export(), full, "a state with counts and channels")
+        _same(r.accum_read()[0], (full.sum / np.maximum(cnt, 1).astype(f32)[..., None]).astype(f32), "accum_read of the state with counts")
+        assert np.array_equal(r.accum_counts()[0], cnt)
+        names = ["sum", "moments", "counts", "converged", "channel_moments"]
+        for skip in names:
+            out = rt.AccumState(nx, rows, planes=full.planes, **{n: sentinel(getattr(full, n).shape, getattr(full, n).dtype) for n in names})
+            st = out.as_struct()
+            setattr(st, skip, None)
+            r._call("rt_accum_export", ctypes.byref(st))
+            for n in names:
+                _same(getattr(out, n), getattr(full, n) if n != skip else sentinel(getattr(full, n).shape, getattr(full, n).dtype), ("export without", skip, n))
+        # ---- a state with neither, then the halves and M = 3 buckets behind it
+        plain = rt.AccumState(nx, rows, 0, MOVER_DONE, 0, fid, sum=_coded((rows, nx, 3), f32, 3), moments=_coded((rows, nx, 2), np.float64, 4))
+        halves = rt.AccumHalves(nx, rows, 0, MOVER_DONE, fid, sum=_coded((2, rows, nx, 3), f32, 5), moments=_coded((2, rows, nx, 2), np.float64, 6))
+        for M in (3, 16):
+            buckets = rt.AccumBuckets(nx, rows, M, 0, MOVER_DONE, fid, sum=_coded((M, rows, nx, 3), f32, 7))
+            assert plain.check() and halves.check() and buckets.check()
+            r.accum_begin(scene.camera, prm)
+            r.accum_import(plain)
+            r.accum_import_halves(halves)
+            r.accum_import_buckets(buckets)
+            e = r.accum_export()
+            assert (e.planes, e.done, e.frame_id) == (0, MOVER_DONE, fid) and e.channel_moments is None
+            _same(e.sum, plain.sum, "a plain state, sum")
+            _same(e.moments, plain.moments, "a plain state, moments")
+            _same(r.accum_read()[0], (plain.sum / f32(MOVER_DONE)).astype(f32), "accum_read of the plain state")
+            eh = r.accum_export_halves()
+            assert (eh.first_sample, eh.done, eh.frame_id) == (0, MOVER_DONE, fid)
+            _same(eh.sum, halves.sum, "the halves, sum")
+            _same(eh.moments, halves.moments, "the halves, moments")
+            for h in range(2):
+                _same(r.accum_half(h)[0], (halves.sum[h] / f32(MOVER_DONE // 2)).astype(f32), ("accum_half", h))
+            eb = r.accum_export_buckets()
+            assert (eb.M, eb.done, eb.frame_id) == (M, MOVER_DONE, fid)
+            _same(eb.sum, buckets.sum, ("the buckets", M))
+            _same(r.accum_robust(mode="trim", trim=0)[0], robust_ref.robust(buckets.sum, 0, MOVER_DONE, robust_ref.TRIM, 0)[0], ("accum_robust", M))
+            # a NULL pointer: that plane is not asked for
+            out = rt.AccumHalves(nx, rows, sum=sentinel(halves.sum.shape, f32), moments=sentinel(halves.moments.shape, np.float64))
+            hs = out.as_struct()
+            hs.sum[1], hs.moments[0] = ctypes.POINTER(ctypes.c_float)(), ctypes.POINTER(ctypes.c_double)()
+            r._call("rt_accum_export_halves", ctypes.byref(hs))
+            _same(out.sum[0], halves.sum[0], "halves without sum[1] and moments[0]: sum[0]")
+            _same(out.moments[1], halves.moments[1], "halves without sum[1] and moments[0]: moments[1]")
+            _same(out.sum[1], sentinel(halves.sum[1].shape, f32), "halves: sum[1] was not asked for")
+            _same(out.moments[0], sentinel(halves.moments[0].shape, np.float64), "halves: moments[0] was not asked for")
+            out = rt.AccumBuckets(nx, rows, M, sum=sentinel(buckets.sum.shape, f32))
+            bs = out.as_struct()
+            bs.sum[1] = ctypes.POINTER(ctypes.c_float)()
+            r._call("rt_accum_export_buckets", ctypes.byref(bs))
+            for b in range(M):
+                _same(out.sum[b], buckets.sum[b] if b != 1 else sentinel(buckets.sum[1].shape, f32), ("buckets without sum[1]", M, b))
+        r.accum_end()
+    finally:
+        r.set_option("pixel_order", 0)
+
+
+def test_the_snapshots_of_a_shard_without_rows_move_nothing(rt, ctx):
+    r = ctx
+    scene, prm = _setup(rt, r, "A")
+    p = prm(3, shard_count=8, shard_band=4, shard_id=7)  # 20 rows in bands of 4: shards 5, 6 and 7 own none
+    fid = rt.accum_frame_id(scene.camera, p)
+    state, halves, buckets = rt.AccumState(40, 0, 0, 5, 0, fid, sum=np.zeros((0, 40, 3), np.float32), moments=np.zeros((0, 40, 2))), \
+        rt.AccumHalves(40, 0, 0, 5, fid), rt.AccumBuckets(40, 0, 16, 0, 5, fid)
+    r.accum_begin(scene.camera, p)
+    r.accum_import(state)
+    r.accum_import_halves(halves)
+    r.accum_import_buckets(buckets)
+    e, eh, eb = r.accum_export(), r.accum_export_halves(), r.accum_export_buckets()
+    assert (e.rows, e.done, e.sum.size, e.frame_id) == (0, 5, 0, fid) and e.check()
+    assert (eh.rows, eh.done, eh.sum.size, eh.frame_id) == (0, 5, 0, fid) and eh.check()
+    assert (eb.rows, eb.done, eb.M, eb.sum.size, eb.frame_id) == (0, 5, 16, 0, fid) and eb.check()
+    r.accum_end()

@@ -265,3 +265,55 @@ def test_accum_state_header_under_asan_ubsan(tmp_path):
     lines = [l.split() for l in r.stdout.splitlines()]
     assert [l[0] for l in lines] == ["sizes", "check", "identity", "ok"]
     assert all(int(l[1]) > 0 for l in lines[:-1])
+
+
+# What each class's file holds, key by key, as the first version of each class wrote it: the scalars as 0-d uint64 in this order, then the
+# arrays; an AccumState leaves out the planes it does not hold.
+NPZ_SCALARS = {"AccumState": ["nx", "rows", "first_sample", "done", "planes", "frame_id"],
+               "AccumHalves": ["nx", "rows", "first_sample", "done", "frame_id"],
+               "AccumBuckets": ["nx", "rows", "first_sample", "done", "M", "frame_id"]}
+NPZ_ARRAYS = {"AccumState": [("sum", "<f4", (2, 3, 3)), ("moments", "<f8", (2, 3, 2)), ("counts", "<u4", (2, 3)), ("converged", "|u1", (2, 3)),
+                             ("channel_moments", "<f8", (2, 3, 6))],
+              "AccumHalves": [("sum", "<f4", (2, 2, 3, 3)), ("moments", "<f8", (2, 2, 3, 2))],
+              "AccumBuckets": [("sum", "<f4", (5, 2, 3, 3))]}
+
+
+@pytest.mark.parametrize("cls,absent", [("AccumState", ()), ("AccumState", ("counts", "converged", "channel_moments")), ("AccumState", ("channel_moments",)),
+                                        ("AccumHalves", ()), ("AccumBuckets", ())])
+def test_npz_keys_and_dtypes_are_the_first_version_s(rt, tmp_path, cls, absent):
+    """save writes exactly the listed keys with the listed dtypes, and a file written with plain np.savez from that list loads back."""
+    rng = np.random.default_rng(5)
+    scalars = dict(nx=3, rows=2, first_sample=2 ** 32 - 9, done=8, frame_id=2 ** 64 - 3)
+    planes = (0 if "counts" in absent else ref.COUNTS) | (0 if "channel_moments" in absent else ref.CHANNELS)
+    scalars.update({"AccumState": dict(planes=planes), "AccumBuckets": dict(M=5)}.get(cls, {}))
+    assert sorted(scalars) == sorted(NPZ_SCALARS[cls])
+    arrays = {}
+    for name, dt, shape in NPZ_ARRAYS[cls]:
+        if name not in absent:
+            bits = rng.integers(0, 256, size=int(np.prod(shape)) * np.dtype(dt).itemsize, dtype=np.uint8)
+            arrays[name] = bits.view(dt).reshape(shape) if name not in ("counts", "converged") else np.full(shape, 8 * (name == "counts"), dt)
+    Class = getattr(rt, cls)
+    # 1. what save writes
+    path = tmp_path / "saved.npz"
+    Class(**scalars, **arrays).save(str(path))
+    assert sorted(os.listdir(tmp_path)) == ["saved.npz"]  # (the temporary file is gone)
+    with np.load(path) as z:
+        assert z.files == NPZ_SCALARS[cls] + [n for n, _, _ in NPZ_ARRAYS[cls] if n not in absent]
+        for k in NPZ_SCALARS[cls]:
+            assert z[k].dtype == np.uint64 and z[k].shape == () and int(z[k]) == scalars[k], k
+        for name, dt, shape in NPZ_ARRAYS[cls]:
+            if name not in absent:
+                assert z[name].dtype.str == dt and z[name].shape == shape and z[name].tobytes() == arrays[name].tobytes(), name
+    # 2. a file made without the class
+    plain = tmp_path / "plain.npz"
+    np.savez(plain, **{k: np.asarray(scalars[k], dtype=np.uint64) for k in NPZ_SCALARS[cls]}, **arrays)
+    for back in (Class.load(str(plain)), Class.load(str(path))):
+        for k in NPZ_SCALARS[cls]:
+            assert getattr(back, k) == scalars[k], k
+        for name, dt, shape in NPZ_ARRAYS[cls]:
+            got = getattr(back, name)
+            if name in absent:
+                assert got is None, name
+            else:
+                assert got.dtype.str == dt and got.tobytes() == arrays[name].tobytes(), name
+        assert back.check()
