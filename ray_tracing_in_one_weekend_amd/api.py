@@ -775,17 +775,21 @@ class Renderer:
         self._call("rt_debug_accum_set_moments", int(pixel), float(s1), float(s2))
 
     @staticmethod
-    def _denoise_ptr(radius, patch, strength):
-        dn = RtDenoise(int(radius), int(patch), float(_ffi.DENOISE_DEFAULT_STRENGTH if strength is None else strength), 0)
+    def _denoise_ptr(radius, patch, strength, default_strength=_ffi.DENOISE_DEFAULT_STRENGTH):
+        dn = RtDenoise(int(radius), int(patch), float(default_strength if strength is None else strength), 0)
         return C.byref(dn)
+
+    def _accum_filter(self, name, *lead, dn, want_rgb8):
+        """An rt_accum_denoise* call with the arguments (`lead`, RtDenoise, out_rgb_f32, out_rgb8).  Returns (img, rgb8 or None)."""
+        img, rgb8, _, ptrs = self._accum_outputs(want_rgb8, False)
+        self._call(name, *lead, dn, ptrs[0], ptrs[1])
+        return img, rgb8
 
     def accum_denoise(self, radius=5, patch=1, strength=None, want_rgb8=False):
         """rt_accum_denoise: the frame of the open accumulation through the variance-guided non-local-means filter (window radius, patch
         radius, strength; None: RT_DENOISE_DEFAULT_STRENGTH).  Returns (img [rows, nx, 3] f32, rgb8 or None) laid out as accum_read's; the
         accumulation itself is not changed."""
-        img, rgb8, _, ptrs = self._accum_outputs(want_rgb8, False)
-        self._call("rt_accum_denoise", self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
-        return img, rgb8
+        return self._accum_filter("rt_accum_denoise", dn=self._denoise_ptr(radius, patch, strength), want_rgb8=want_rgb8)
 
     def debug_denoise(self, rgb, y, v, radius=5, patch=1, strength=None):
         """rt_debug_denoise: the filter kernel of accum_denoise over host arrays in image order — rgb [rows, nx, 3], y and v [rows, nx]
@@ -814,9 +818,7 @@ class Renderer:
     def accum_denoise_channels(self, radius=5, patch=1, strength=None, want_rgb8=False):
         """rt_accum_denoise_channels: accum_denoise with the distance on the three channels and their own variances, so that edges between
         colours of equal luminance stay; the accumulation must track channels (accum_track_channels).  Returns (img, rgb8 or None)."""
-        img, rgb8, _, ptrs = self._accum_outputs(want_rgb8, False)
-        self._call("rt_accum_denoise_channels", self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
-        return img, rgb8
+        return self._accum_filter("rt_accum_denoise_channels", dn=self._denoise_ptr(radius, patch, strength), want_rgb8=want_rgb8)
 
     def debug_denoise_channels(self, rgb, var_rgb, radius=5, patch=1, strength=None):
         """rt_debug_denoise_channels: the filter kernel of accum_denoise_channels over host arrays in image order — rgb and var_rgb
@@ -877,8 +879,7 @@ class Renderer:
         RT_DENOISE_HALVES_DEFAULT_STRENGTH."""
         img, rgb8, err, ptrs = self._accum_outputs(want_rgb8, want_err)
         res = RtResidual()
-        dn = RtDenoise(int(radius), int(patch), float(_ffi.DENOISE_HALVES_DEFAULT_STRENGTH if strength is None else strength), 0)
-        self._call("rt_accum_denoise_halves", C.byref(dn), ptrs[0], ptrs[1], ptrs[2], C.byref(res))
+        self._call("rt_accum_denoise_halves", self._denoise_ptr(radius, patch, strength, _ffi.DENOISE_HALVES_DEFAULT_STRENGTH), *ptrs, C.byref(res))
         return img, rgb8, err, res
 
     def accum_export_halves(self):
@@ -924,10 +925,8 @@ class Renderer:
     def accum_denoise_robust(self, mode="gini", trim=0, radius=5, patch=1, strength=None, want_rgb8=False):
         """rt_accum_denoise_robust: accum_denoise with the colours replaced by the robust read-out; the guide stays the luminance moments'.
         Returns (img [rows, nx, 3] f32, rgb8 or None)."""
-        img, rgb8, _, ptrs = self._accum_outputs(want_rgb8, False)
         rb = self._robust(mode, trim)
-        self._call("rt_accum_denoise_robust", C.byref(rb), self._denoise_ptr(radius, patch, strength), ptrs[0], ptrs[1])
-        return img, rgb8
+        return self._accum_filter("rt_accum_denoise_robust", C.byref(rb), dn=self._denoise_ptr(radius, patch, strength), want_rgb8=want_rgb8)
 
     def accum_export_buckets(self):
         """rt_accum_export_buckets: the sample buckets of the open accumulation as an AccumBuckets.  Read, not changed."""

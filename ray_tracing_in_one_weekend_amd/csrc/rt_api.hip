@@ -1114,30 +1114,27 @@ static int enqueue_slice(RtCtx* ctx, Frame& f, const WorkView& wv, uint32_t sl) 
     return RT_OK;
 }
 
+// A kernel with one bool template parameter: K<true> where `flag` holds and K<false> otherwise, in workgroups of 256 on `st`, both with
+// the same arguments: what only one instantiation needs, the other does not read (stated at each such kernel).
+#define KERNEL_PAIR(K, flag, grid, st, ...)                                                \
+    do {                                                                                   \
+        if (flag) hipLaunchKernelGGL(K<true>, (grid), dim3(256), 0, (st), __VA_ARGS__);    \
+        else hipLaunchKernelGGL(K<false>, (grid), dim3(256), 0, (st), __VA_ARGS__);        \
+    } while (0)
+
 // Resolves the slice's `sc` samples per pixel onto the running sum, in sample order, and shows the `done` of `spp` samples so far to
 // the progress callback.
 static int resolve_and_preview(RtCtx* ctx, const Frame& f, const SampleSink& sink, const float* rad, uint32_t sc, uint32_t done, uint32_t rows) {
     const hipStream_t st = f.st;
     const uint32_t npix = f.npix, spp = f.prm->spp, nx = f.prm->nx;
-    if (sink.halves) { // the slice's first sample has the absolute index first_sample + (done - sc)
-        const uint32_t i0 = sink.first_sample + (done - sc);
-        if (sink.converged) hipLaunchKernelGGL(k_resolve_halves<true>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, sink.hp, sink.converged, npix, i0, sc);
-        else hipLaunchKernelGGL(k_resolve_halves<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, sink.hp, (const uint8_t*)nullptr, npix, i0, sc);
-    }
-    if (sink.buckets) {
-        const uint32_t i0 = sink.first_sample + (done - sc);
-        if (sink.converged) hipLaunchKernelGGL(k_resolve_buckets<true>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, sink.buckets, sink.converged, npix, sink.n_buckets, i0, sc);
-        else hipLaunchKernelGGL(k_resolve_buckets<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, sink.buckets, (const uint8_t*)nullptr, npix, sink.n_buckets, i0, sc);
-    }
-    if (sink.chm && sink.converged)
-        hipLaunchKernelGGL(k_resolve_moments_channels<true>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.chm, sink.converged, sink.cnt, npix, sc);
-    else if (sink.chm)
-        hipLaunchKernelGGL(k_resolve_moments_channels<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.chm, (const uint8_t*)nullptr,
-                           (uint32_t*)nullptr, npix, sc);
-    else if (sink.converged) hipLaunchKernelGGL(k_resolve_moments<true>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, sink.converged, sink.cnt, npix, sc);
-    else if (sink.mom)
-        hipLaunchKernelGGL(k_resolve_moments<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, sink.mom, (const uint8_t*)nullptr, (uint32_t*)nullptr, npix, sc);
-    else hipLaunchKernelGGL(k_resolve, dim3((npix + 255u) / 256u), dim3(256), 0, st, rad, f.acc, npix, sc);
+    const dim3 grid((npix + 255u) / 256u);
+    const bool active = sink.converged != nullptr; // (an adaptive add; otherwise `converged` and `cnt` are not read)
+    const uint32_t i0 = sink.first_sample + (done - sc); // the absolute index of the slice's first sample
+    if (sink.halves) KERNEL_PAIR(k_resolve_halves, active, grid, st, rad, sink.hp, sink.converged, npix, i0, sc);
+    if (sink.buckets) KERNEL_PAIR(k_resolve_buckets, active, grid, st, rad, sink.buckets, sink.converged, npix, sink.n_buckets, i0, sc);
+    if (sink.chm) KERNEL_PAIR(k_resolve_moments_channels, active, grid, st, rad, f.acc, sink.mom, sink.chm, sink.converged, sink.cnt, npix, sc);
+    else if (sink.mom || active) KERNEL_PAIR(k_resolve_moments, active, grid, st, rad, f.acc, sink.mom, sink.converged, sink.cnt, npix, sc);
+    else hipLaunchKernelGGL(k_resolve, grid, dim3(256), 0, st, rad, f.acc, npix, sc);
     hipLaunchKernelGGL(k_accum_counts, dim3((unsigned)f.n_depths), dim3(256), 0, st, f.counts, f.d.nq, (uint32_t)f.n_depths, f.totals + 2);
     if (ctx->progress_armed && ctx->progress_fn && done < spp) { // the last slice is the final image itself
         hipLaunchKernelGGL(k_finalize<false>, dim3((npix + 255u) / 256u), dim3(256), 0, st, f.acc, (const uint32_t*)nullptr, (float*)nullptr,
@@ -1327,9 +1324,9 @@ int rt_render(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, float* out_r
 static int require_open(RtCtx* ctx, const char* who) {
     return ctx->accum.open ? RT_OK : fail(ctx, RT_ERR_STATE, std::string(who) + ": no accumulation begun (or it was ended: rtow_mi355x.h)");
 }
-// What every reader of the open accumulation is launched with: one lane per pixel in workgroups of 256 on `st`.  ACCUM_READER launches
-// K<true> on an adaptive accumulation and K<false> on a uniform one, with the same arguments: among them `cnt` (NULL or a finished
-// accumulation's on a uniform one) and `n` = done, of which each instantiation ignores the other's (rt_kernels.h).
+// What every reader of the open accumulation is launched with: one lane per pixel in workgroups of 256 on `st`.  ACCUM_READER is
+// KERNEL_PAIR by the accumulation's kind: K<true> on an adaptive one and K<false> on a uniform one; among the arguments `cnt` (NULL or a
+// finished accumulation's on a uniform one) and `n` = done, of which each instantiation ignores the other's (rt_kernels.h).
 struct AccumReader {
     hipStream_t st;
     dim3 grid;
@@ -1342,11 +1339,7 @@ static AccumReader accum_reader(const RtCtx* ctx, hipStream_t st) {
     const RtCtx::Accum& a = ctx->accum;
     return AccumReader{st, dim3((a.npix + 255u) / 256u), a.nx, a.rows, a.tiles_per_row, a.tile_pixels, ctx->accum_cnt.as<const uint32_t>(), a.done, a.adaptive};
 }
-#define ACCUM_READER(K, r, ...)                                                                       \
-    do {                                                                                              \
-        if ((r).counts) hipLaunchKernelGGL(K<true>, (r).grid, dim3(256), 0, (r).st, __VA_ARGS__);     \
-        else hipLaunchKernelGGL(K<false>, (r).grid, dim3(256), 0, (r).st, __VA_ARGS__);               \
-    } while (0)
+#define ACCUM_READER(K, r, ...) KERNEL_PAIR(K, (r).counts, (r).grid, (r).st, __VA_ARGS__)
 
 // The buffers of an adaptive accumulation of npix pixels (kept for the next one): n_p, the flags, the integer sums and their host copy.
 static int ensure_adaptive(RtCtx* ctx, uint32_t npix) {
@@ -1370,8 +1363,8 @@ static int enqueue_adaptive_info(RtCtx* ctx, hipStream_t st, const RtAdaptive* d
     const double2* mom = ctx->accum_mom.as<const double2>();
     const uint32_t* cnt = ctx->accum_cnt.as<const uint32_t>();
     uint8_t* flag = ctx->accum_flag.as<uint8_t>();
-    if (decide) hipLaunchKernelGGL(k_adaptive_decide<true>, dim3(nb), dim3(256), 0, st, mom, cnt, flag, partials, a.npix, decide->tolerance, decide->luminance_floor, decide->min_samples);
-    else hipLaunchKernelGGL(k_adaptive_decide<false>, dim3(nb), dim3(256), 0, st, mom, cnt, flag, partials, a.npix, 0.0, 0.0, 0u);
+    const RtAdaptive crit = decide ? *decide : RtAdaptive{}; // (k_adaptive_decide<false> reads no criterion: zeros)
+    KERNEL_PAIR(k_adaptive_decide, decide != nullptr, dim3(nb), st, mom, cnt, flag, partials, a.npix, crit.tolerance, crit.luminance_floor, crit.min_samples);
     hipLaunchKernelGGL(k_adaptive_info, dim3(1), dim3(256), 0, st, (const AdaptiveSums*)partials, nb, partials + nb);
     RT_HIP(ctx, hipMemcpyAsync(ctx->h_info, partials + nb, sizeof(RtAdaptiveInfo), hipMemcpyDeviceToHost, st));
     return RT_OK;
@@ -1389,8 +1382,7 @@ static int enqueue_noise(RtCtx* ctx, hipStream_t st) {
     }
     ACCUM_READER(k_noise_partials, r, ctx->accum_mom.as<const double2>(), r.cnt, partials, a.npix, r.n);
     // (ONE workgroup over the partials, not a lane per pixel)
-    if (a.adaptive) hipLaunchKernelGGL(k_noise_final<true>, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, a.npix, info, r.n, figures);
-    else hipLaunchKernelGGL(k_noise_final<false>, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, a.npix, info, r.n, figures);
+    KERNEL_PAIR(k_noise_final, a.adaptive, dim3(1), st, (const double2*)partials, nb, a.npix, info, r.n, figures);
     RT_HIP(ctx, hipMemcpyAsync(ctx->h_noise, figures, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     return RT_OK;
 }
@@ -1652,40 +1644,37 @@ static int denoise_params(RtCtx* ctx, const RtDenoise* dn, RtDenoise& d, const c
     d = *dn;
     return RT_OK;
 }
-// k_denoise over an image in image order: c, yv -> out (device pointers), nx, rows >= 1
-static void launch_denoise(hipStream_t st, const float* c, const float2* yv, float* out, uint32_t nx, uint32_t rows, const RtDenoise& d) {
+// The filter over an image in image order (device pointers; nx, rows >= 1) -> out.  planes 1: k_denoise with the colours `c` and the guide
+// g = (y, v) per pixel; planes 3: k_denoise_channels with g = (c_ch, v_ch) x 3 per pixel (`c` is not used).
+static void launch_nlm(hipStream_t st, uint32_t planes, const float* c, const float2* g, float* out, uint32_t nx, uint32_t rows, const RtDenoise& d) {
     const dim3 grid((nx + RT_DN_TILE - 1u) / RT_DN_TILE, (rows + RT_DN_TILE - 1u) / RT_DN_TILE), block(RT_DN_TILE, RT_DN_TILE);
     const int R = (int)d.radius;
     const float k2 = d.strength * d.strength;
-    const size_t lds = denoise_lds_bytes(d.radius, d.patch);
+    const size_t lds = nlm_lds_bytes(planes, d.radius, d.patch);
+#define NLM_PATCH(F)                                                                                            \
+    do {                                                                                                        \
+        if (planes == 1u) {                                                                                     \
+            hipLaunchKernelGGL(k_denoise<F>, grid, block, lds, st, c, g, out, nx, rows, R, k2);                 \
+        } else {                                                                                                \
+            hipLaunchKernelGGL(k_denoise_channels<F>, grid, block, lds, st, g, out, nx, rows, R, k2);           \
+        }                                                                                                       \
+    } while (0)
     switch (d.patch) {
-    case 0u: hipLaunchKernelGGL(k_denoise<0>, grid, block, lds, st, c, yv, out, nx, rows, R, k2); break;
-    case 1u: hipLaunchKernelGGL(k_denoise<1>, grid, block, lds, st, c, yv, out, nx, rows, R, k2); break;
-    case 2u: hipLaunchKernelGGL(k_denoise<2>, grid, block, lds, st, c, yv, out, nx, rows, R, k2); break;
-    default: hipLaunchKernelGGL(k_denoise<3>, grid, block, lds, st, c, yv, out, nx, rows, R, k2); break;
+    case 0u: NLM_PATCH(0); break;
+    case 1u: NLM_PATCH(1); break;
+    case 2u: NLM_PATCH(2); break;
+    default: NLM_PATCH(3); break;
     }
+#undef NLM_PATCH
 }
-static int ensure_denoise(RtCtx* ctx, size_t npix) {
+// The filter's buffers for npix pixels: its output and, by the guide's planes, (c, (y, v)) or (c, v) x 3
+static int ensure_nlm(RtCtx* ctx, size_t npix, uint32_t planes) {
     int rc;
-    if ((rc = ensure(ctx, ctx->dn_c, npix * 3 * sizeof(float)))) return rc;
-    if ((rc = ensure(ctx, ctx->dn_yv, npix * sizeof(float2)))) return rc;
+    if (planes == 1u && (rc = ensure(ctx, ctx->dn_c, npix * 3 * sizeof(float)))) return rc;
+    if ((rc = ensure(ctx, planes == 1u ? ctx->dn_yv : ctx->dn_cv, npix * planes * sizeof(float2)))) return rc;
     return ensure(ctx, ctx->dn_out, npix * 3 * sizeof(float));
 }
 
-// What the three rt_accum_denoise* calls refuse, in this order, and the parameters of the call.  `untracked`: NULL, or what the accumulation
-// lacks for this filter; `min_done`: the samples below which there is no variance, and `no_variance` says whose.
-static int denoise_begin(RtCtx* ctx, const char* who, const RtDenoise* dn, RtDenoise& d, float default_strength, const char* untracked, uint32_t min_done,
-                         const char* no_variance) {
-    int rc = require_open(ctx, who);
-    if (rc) return rc;
-    const RtCtx::Accum& a = ctx->accum;
-    if (untracked) return fail(ctx, RT_ERR_STATE, std::string(who) + ": " + untracked);
-    if ((rc = denoise_params(ctx, dn, d, who, default_strength))) return rc;
-    if (a.prm.shard_count > 1u)
-        return fail(ctx, RT_ERR_UNSUPPORTED, std::string(who) + ": a sharded frame (shard_count > 1): the local rows of a shard are not neighbours in the image");
-    if (a.done < min_done) return fail(ctx, RT_ERR_STATE, std::string(who) + ": fewer than " + std::to_string(min_done) + " samples accumulated: " + no_variance);
-    return RT_OK;
-}
 // Their shared end: the filtered image `img` (device, image order) through k_finalize's quantisation and flip into ctx->out_u8 where rgb8 is
 // asked — row-major (no tiles), and / (float)1 changes no bit — and the copies to the host, enqueued on the context's stream.
 static int denoise_finish(RtCtx* ctx, const float* img, float* out_rgb_f32, uint8_t* out_rgb8) {
@@ -1701,47 +1690,91 @@ static int denoise_finish(RtCtx* ctx, const float* img, float* out_rgb_f32, uint
     return RT_OK;
 }
 
-int rt_accum_denoise(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8) {
-    if (!ctx) return RT_ERR_INVALID;
-    RtDenoise d;
-    int rc = denoise_begin(ctx, "rt_accum_denoise", dn, d, RT_DENOISE_DEFAULT_STRENGTH, nullptr, 2u, "there is no variance yet");
+// What a rt_accum_denoise* call is beside its middle.  `untracked`: NULL, or what the accumulation lacks for this filter; `min_done`: the
+// samples below which there is no variance, and `no_variance` says whose.
+struct DenoiseCall {
+    const char* who;
+    float default_strength;
+    const char* untracked;
+    uint32_t min_done;
+    const char* no_variance;
+};
+// The frame of the four rt_accum_denoise* calls.  What they refuse, in this order: no accumulation, `untracked`, the parameters, a sharded
+// frame, too few samples, then whatever `more` refuses (the call's own checks: RT_OK or its code).  On an accumulation without pixels
+// that is all.  Otherwise `middle(r, d, img)` ensures its buffers and enqueues its kernels on the reader's stream — the parameters `d`
+// checked, ctx->out_u8 ensured where rgb8 is asked — and names the filtered image `img` (device, image order), which goes through
+// denoise_finish; one wait for the stream ends the call.
+extern "C++" template <class More, class Middle>
+static int denoise_run(RtCtx* ctx, const DenoiseCall& call, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8, More more, Middle middle) {
+    const std::string who = call.who;
+    int rc = require_open(ctx, call.who);
     if (rc) return rc;
     const RtCtx::Accum& a = ctx->accum;
+    if (call.untracked) return fail(ctx, RT_ERR_STATE, who + ": " + call.untracked);
+    RtDenoise d;
+    if ((rc = denoise_params(ctx, dn, d, call.who, call.default_strength))) return rc;
+    if (a.prm.shard_count > 1u)
+        return fail(ctx, RT_ERR_UNSUPPORTED, who + ": a sharded frame (shard_count > 1): the local rows of a shard are not neighbours in the image");
+    if (a.done < call.min_done) return fail(ctx, RT_ERR_STATE, who + ": fewer than " + std::to_string(call.min_done) + " samples accumulated: " + call.no_variance);
+    if ((rc = more())) return rc;
     if (a.npix == 0u) return RT_OK;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
-    if ((rc = ensure_denoise(ctx, a.npix))) return rc;
     if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, (size_t)a.npix * 3))) return rc;
-    const AccumReader r = accum_reader(ctx, st);
-    // (adaptive: every n_p >= 2 unless a state was imported: a pixel stops on min_samples >= 2 at the earliest, and done >= 2 was checked)
-    ACCUM_READER(k_denoise_inputs, r, ctx->accum_sum.as<const float>(), ctx->accum_mom.as<const double2>(), r.cnt, ctx->dn_c.as<float>(), ctx->dn_yv.as<float2>(), r.nx,
-                 r.rows, r.n, r.tiles_per_row, r.tile_pixels);
-    launch_denoise(st, ctx->dn_c.as<const float>(), ctx->dn_yv.as<const float2>(), ctx->dn_out.as<float>(), a.nx, a.rows, d);
-    if ((rc = denoise_finish(ctx, ctx->dn_out.as<const float>(), out_rgb_f32, out_rgb8))) return rc;
+    const float* img = nullptr;
+    if ((rc = middle(accum_reader(ctx, st), d, img))) return rc;
+    if ((rc = denoise_finish(ctx, img, out_rgb_f32, out_rgb8))) return rc;
     RT_HIP(ctx, hipStreamSynchronize(st));
     return RT_OK;
 }
+static int no_more_checks() { return RT_OK; } // (`more` of a call without checks of its own)
+// The inputs of rt_accum_denoise, (c, (y, v)) into ctx->dn_c and ctx->dn_yv.  (Adaptive: every n_p >= 2 unless a state was imported: a
+// pixel stops on min_samples >= 2 at the earliest, and done >= 2 was checked.)
+static void enqueue_denoise_inputs(RtCtx* ctx, const AccumReader& r) {
+    ACCUM_READER(k_denoise_inputs, r, ctx->accum_sum.as<const float>(), ctx->accum_mom.as<const double2>(), r.cnt, ctx->dn_c.as<float>(), ctx->dn_yv.as<float2>(), r.nx,
+                 r.rows, r.n, r.tiles_per_row, r.tile_pixels);
+}
 
-int rt_debug_denoise(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* y, const float* v, const RtDenoise* dn, float* out_rgb_f32) {
+int rt_accum_denoise(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8) {
     if (!ctx) return RT_ERR_INVALID;
-    if (!rgb || !y || !v || !out_rgb_f32) return fail(ctx, RT_ERR_INVALID, "rt_debug_denoise: NULL array");
-    if (nx == 0u || rows == 0u || (uint64_t)nx * rows > (1ull << 28)) return fail(ctx, RT_ERR_INVALID, "rt_debug_denoise: nx * rows must be 1 .. 2^28");
+    const DenoiseCall call{"rt_accum_denoise", RT_DENOISE_DEFAULT_STRENGTH, nullptr, 2u, "there is no variance yet"};
+    return denoise_run(ctx, call, dn, out_rgb_f32, out_rgb8, no_more_checks, [&](const AccumReader& r, const RtDenoise& d, const float*& img) -> int {
+        if (const int rc = ensure_nlm(ctx, ctx->accum.npix, 1u)) return rc;
+        enqueue_denoise_inputs(ctx, r);
+        launch_nlm(r.st, 1u, ctx->dn_c.as<const float>(), ctx->dn_yv.as<const float2>(), ctx->dn_out.as<float>(), r.nx, r.rows, d);
+        img = ctx->dn_out.as<const float>();
+        return RT_OK;
+    });
+}
+
+// rt_debug_denoise (planes 1: mean = y, var = v) and rt_debug_denoise_channels (planes 3: mean = rgb, var = var_rgb) under the caller's
+// name: the host's arrays interleaved into the guide's float2, uploaded, filtered and downloaded.
+static int debug_nlm(RtCtx* ctx, const char* who, uint32_t planes, uint32_t nx, uint32_t rows, const float* rgb, const float* mean, const float* var,
+                     const RtDenoise* dn, float* out_rgb_f32) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!rgb || !mean || !var || !out_rgb_f32) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": NULL array");
+    if (nx == 0u || rows == 0u || (uint64_t)nx * rows > (1ull << 28)) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": nx * rows must be 1 .. 2^28");
     RtDenoise d;
-    int rc = denoise_params(ctx, dn, d, "rt_debug_denoise");
+    int rc = denoise_params(ctx, dn, d, who);
     if (rc) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)nx * rows;
-    if ((rc = ensure_denoise(ctx, npix))) return rc;
-    std::vector<float2> yv(npix);
-    for (size_t p = 0; p < npix; ++p) yv[p] = make_float2(y[p], v[p]);
+    if ((rc = ensure_nlm(ctx, npix, planes))) return rc;
+    std::vector<float2> g(planes * npix);
+    for (size_t k = 0; k < g.size(); ++k) g[k] = make_float2(mean[k], var[k]);
     const hipStream_t st = ctx->stream;
-    RT_HIP(ctx, hipMemcpyAsync(ctx->dn_c.p, rgb, npix * 3 * sizeof(float), hipMemcpyHostToDevice, st));
-    RT_HIP(ctx, hipMemcpyAsync(ctx->dn_yv.p, yv.data(), npix * sizeof(float2), hipMemcpyHostToDevice, st));
-    launch_denoise(st, (const float*)ctx->dn_c.p, (const float2*)ctx->dn_yv.p, (float*)ctx->dn_out.p, nx, rows, d);
+    const float* c = planes == 1u ? ctx->dn_c.as<const float>() : nullptr;
+    float2* guide = planes == 1u ? ctx->dn_yv.as<float2>() : ctx->dn_cv.as<float2>();
+    if (c) RT_HIP(ctx, hipMemcpyAsync(ctx->dn_c.p, rgb, npix * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    RT_HIP(ctx, hipMemcpyAsync(guide, g.data(), g.size() * sizeof(float2), hipMemcpyHostToDevice, st));
+    launch_nlm(st, planes, c, guide, ctx->dn_out.as<float>(), nx, rows, d);
     RT_HIP(ctx, hipGetLastError());
     RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->dn_out.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
     RT_HIP(ctx, hipStreamSynchronize(st));
     return RT_OK;
+}
+int rt_debug_denoise(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* y, const float* v, const RtDenoise* dn, float* out_rgb_f32) {
+    return debug_nlm(ctx, "rt_debug_denoise", 1u, nx, rows, rgb, y, v, dn, out_rgb_f32);
 }
 
 // ---- channel moments and the colour-guided filter (rtow_mi355x.h "Channel moments and the colour-guided filter", csrc/rt_channels.h) ------
@@ -1779,64 +1812,22 @@ int rt_accum_read_channel_sem(RtCtx* ctx, float* out_sem_rgb) {
     return RT_OK;
 }
 
-// k_denoise_channels over an image in image order: cv -> out (device pointers), nx, rows >= 1
-static void launch_denoise_channels(hipStream_t st, const float2* cv, float* out, uint32_t nx, uint32_t rows, const RtDenoise& d) {
-    const dim3 grid((nx + RT_DN_TILE - 1u) / RT_DN_TILE, (rows + RT_DN_TILE - 1u) / RT_DN_TILE), block(RT_DN_TILE, RT_DN_TILE);
-    const int R = (int)d.radius;
-    const float k2 = d.strength * d.strength;
-    const size_t lds = denoise_channels_lds_bytes(d.radius, d.patch);
-    switch (d.patch) {
-    case 0u: hipLaunchKernelGGL(k_denoise_channels<0>, grid, block, lds, st, cv, out, nx, rows, R, k2); break;
-    case 1u: hipLaunchKernelGGL(k_denoise_channels<1>, grid, block, lds, st, cv, out, nx, rows, R, k2); break;
-    case 2u: hipLaunchKernelGGL(k_denoise_channels<2>, grid, block, lds, st, cv, out, nx, rows, R, k2); break;
-    default: hipLaunchKernelGGL(k_denoise_channels<3>, grid, block, lds, st, cv, out, nx, rows, R, k2); break;
-    }
-}
-static int ensure_denoise_channels(RtCtx* ctx, size_t npix) {
-    if (const int rc = ensure(ctx, ctx->dn_cv, npix * 3 * sizeof(float2))) return rc;
-    return ensure(ctx, ctx->dn_out, npix * 3 * sizeof(float));
-}
-
 int rt_accum_denoise_channels(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8) {
     if (!ctx) return RT_ERR_INVALID;
-    const RtCtx::Accum& a = ctx->accum;
-    RtDenoise d;
-    int rc = denoise_begin(ctx, "rt_accum_denoise_channels", dn, d, RT_DENOISE_DEFAULT_STRENGTH,
-                           a.channels ? nullptr : "the accumulation does not track channels (rt_accum_track_channels)", 2u, "there is no variance yet");
-    if (rc) return rc;
-    if (a.npix == 0u) return RT_OK;
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    const hipStream_t st = ctx->stream;
-    if ((rc = ensure_denoise_channels(ctx, a.npix))) return rc;
-    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, (size_t)a.npix * 3))) return rc;
-    const AccumReader r = accum_reader(ctx, st);
-    ACCUM_READER(k_denoise_inputs_channels, r, ctx->accum_sum.as<const float>(), ctx->accum_chm.as<const double2>(), r.cnt, ctx->dn_cv.as<float2>(), r.nx, r.rows, r.n,
-                 r.tiles_per_row, r.tile_pixels);
-    launch_denoise_channels(st, ctx->dn_cv.as<const float2>(), ctx->dn_out.as<float>(), a.nx, a.rows, d);
-    if ((rc = denoise_finish(ctx, ctx->dn_out.as<const float>(), out_rgb_f32, out_rgb8))) return rc;
-    RT_HIP(ctx, hipStreamSynchronize(st));
-    return RT_OK;
+    const DenoiseCall call{"rt_accum_denoise_channels", RT_DENOISE_DEFAULT_STRENGTH,
+                           ctx->accum.channels ? nullptr : "the accumulation does not track channels (rt_accum_track_channels)", 2u, "there is no variance yet"};
+    return denoise_run(ctx, call, dn, out_rgb_f32, out_rgb8, no_more_checks, [&](const AccumReader& r, const RtDenoise& d, const float*& img) -> int {
+        if (const int rc = ensure_nlm(ctx, ctx->accum.npix, 3u)) return rc;
+        ACCUM_READER(k_denoise_inputs_channels, r, ctx->accum_sum.as<const float>(), ctx->accum_chm.as<const double2>(), r.cnt, ctx->dn_cv.as<float2>(), r.nx, r.rows, r.n,
+                     r.tiles_per_row, r.tile_pixels);
+        launch_nlm(r.st, 3u, nullptr, ctx->dn_cv.as<const float2>(), ctx->dn_out.as<float>(), r.nx, r.rows, d);
+        img = ctx->dn_out.as<const float>();
+        return RT_OK;
+    });
 }
 
 int rt_debug_denoise_channels(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* var_rgb, const RtDenoise* dn, float* out_rgb_f32) {
-    if (!ctx) return RT_ERR_INVALID;
-    if (!rgb || !var_rgb || !out_rgb_f32) return fail(ctx, RT_ERR_INVALID, "rt_debug_denoise_channels: NULL array");
-    if (nx == 0u || rows == 0u || (uint64_t)nx * rows > (1ull << 28)) return fail(ctx, RT_ERR_INVALID, "rt_debug_denoise_channels: nx * rows must be 1 .. 2^28");
-    RtDenoise d;
-    int rc = denoise_params(ctx, dn, d, "rt_debug_denoise_channels");
-    if (rc) return rc;
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t npix = (size_t)nx * rows;
-    if ((rc = ensure_denoise_channels(ctx, npix))) return rc;
-    std::vector<float2> cv(3 * npix);
-    for (size_t k = 0; k < 3 * npix; ++k) cv[k] = make_float2(rgb[k], var_rgb[k]);
-    const hipStream_t st = ctx->stream;
-    RT_HIP(ctx, hipMemcpyAsync(ctx->dn_cv.p, cv.data(), 3 * npix * sizeof(float2), hipMemcpyHostToDevice, st));
-    launch_denoise_channels(st, (const float2*)ctx->dn_cv.p, (float*)ctx->dn_out.p, nx, rows, d);
-    RT_HIP(ctx, hipGetLastError());
-    RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->dn_out.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-    RT_HIP(ctx, hipStreamSynchronize(st));
-    return RT_OK;
+    return debug_nlm(ctx, "rt_debug_denoise_channels", 3u, nx, rows, rgb, rgb, var_rgb, dn, out_rgb_f32);
 }
 
 // ---- accumulation state (rtow_mi355x.h "Accumulation state", csrc/rt_accum_state.h, csrc/rt_accum_state_kernels.h) -------------------------
@@ -2026,42 +2017,42 @@ int rt_accum_read_halves(RtCtx* ctx, uint32_t h, float* out_rgb_f32, float* out_
 int rt_accum_denoise_halves(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8, float* out_err, RtResidual* res) {
     if (!ctx) return RT_ERR_INVALID;
     const RtCtx::Accum& a = ctx->accum;
-    RtDenoise d;
-    int rc = denoise_begin(ctx, "rt_accum_denoise_halves", dn, d, RT_DENOISE_HALVES_DEFAULT_STRENGTH,
-                           a.halves ? nullptr : "the accumulation does not track halves (rt_accum_track_halves)", 4u, "a half has no variance yet");
-    if (rc) return rc;
-    if (res) std::memset(res, 0, sizeof(*res));
-    if (a.npix == 0u) return RT_OK;
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    const hipStream_t st = ctx->stream;
-    const uint32_t npix = a.npix, nb = (npix + 255u) / 256u;
-    const size_t n = (size_t)npix * 3;
-    if ((rc = ensure_denoise(ctx, npix))) return rc;
-    // dn_halves: the partial sums and the figures, (y, v)_1, then c_1, f_1, out (12 B each) and e (4 B) per pixel
-    const size_t part_bytes = ((size_t)nb * sizeof(double2) + 3 * sizeof(double) + 15u) & ~(size_t)15u;
-    if ((rc = ensure(ctx, ctx->dn_halves, part_bytes + (size_t)npix * (sizeof(float2) + 10 * sizeof(float))))) return rc;
-    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
-    if (!ctx->h_resid) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_resid, 3 * sizeof(double), hipHostMallocDefault));
-    double2* partials = ctx->dn_halves.as<double2>();
-    double* figures = (double*)(partials + nb);
-    float2* yv1 = (float2*)(ctx->dn_halves.as<char>() + part_bytes);
-    float* c1 = (float*)(yv1 + npix);
-    float *f1 = c1 + n, *out = f1 + n, *err = out + n;
-    float *c0 = ctx->dn_c.as<float>(), *f0 = ctx->dn_out.as<float>();
-    float2* yv0 = ctx->dn_yv.as<float2>();
-    const HalfPlanes hp = half_planes(ctx->accum_halves, npix);
-    const AccumReader r = accum_reader(ctx, st);
-    ACCUM_READER(k_denoise_inputs_halves, r, hp, r.cnt, c0, c1, yv0, yv1, r.nx, r.rows, a.first, r.n, r.tiles_per_row, r.tile_pixels);
-    launch_denoise(st, c0, yv1, f0, a.nx, a.rows, d); // each half by the other's guide
-    launch_denoise(st, c1, yv0, f1, a.nx, a.rows, d);
-    ACCUM_READER(k_halves_combine, r, (const float*)f0, (const float*)f1, r.cnt, out, err, partials, r.nx, r.rows, a.first, r.n, r.tiles_per_row, r.tile_pixels);
-    hipLaunchKernelGGL(k_halves_final, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, npix, figures);
-    if ((rc = denoise_finish(ctx, out, out_rgb_f32, out_rgb8))) return rc;
-    if (out_err) RT_HIP(ctx, hipMemcpyAsync(out_err, err, (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, st));
-    RT_HIP(ctx, hipMemcpyAsync(ctx->h_resid, figures, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    RT_HIP(ctx, hipStreamSynchronize(st));
-    if (res) res->mean_luminance = ctx->h_resid[0], res->residual_rms = ctx->h_resid[1], res->residual_noise = ctx->h_resid[2];
-    return RT_OK;
+    const DenoiseCall call{"rt_accum_denoise_halves", RT_DENOISE_HALVES_DEFAULT_STRENGTH,
+                           a.halves ? nullptr : "the accumulation does not track halves (rt_accum_track_halves)", 4u, "a half has no variance yet"};
+    const auto clear = [&]() -> int {
+        if (res) std::memset(res, 0, sizeof(*res));
+        return RT_OK;
+    };
+    const int rc = denoise_run(ctx, call, dn, out_rgb_f32, out_rgb8, clear, [&](const AccumReader& r, const RtDenoise& d, const float*& img) -> int {
+        const hipStream_t st = r.st;
+        const uint32_t npix = a.npix, nb = r.grid.x;
+        const size_t n = (size_t)npix * 3;
+        int rc;
+        if ((rc = ensure_nlm(ctx, npix, 1u))) return rc;
+        // dn_halves: the partial sums and the figures, (y, v)_1, then c_1, f_1, out (12 B each) and e (4 B) per pixel
+        const size_t part_bytes = ((size_t)nb * sizeof(double2) + 3 * sizeof(double) + 15u) & ~(size_t)15u;
+        if ((rc = ensure(ctx, ctx->dn_halves, part_bytes + (size_t)npix * (sizeof(float2) + 10 * sizeof(float))))) return rc;
+        if (!ctx->h_resid) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_resid, 3 * sizeof(double), hipHostMallocDefault));
+        double2* partials = ctx->dn_halves.as<double2>();
+        double* figures = (double*)(partials + nb);
+        float2* yv1 = (float2*)(ctx->dn_halves.as<char>() + part_bytes);
+        float* c1 = (float*)(yv1 + npix);
+        float *f1 = c1 + n, *out = f1 + n, *err = out + n;
+        float *c0 = ctx->dn_c.as<float>(), *f0 = ctx->dn_out.as<float>();
+        float2* yv0 = ctx->dn_yv.as<float2>();
+        const HalfPlanes hp = half_planes(ctx->accum_halves, npix);
+        ACCUM_READER(k_denoise_inputs_halves, r, hp, r.cnt, c0, c1, yv0, yv1, r.nx, r.rows, a.first, r.n, r.tiles_per_row, r.tile_pixels);
+        launch_nlm(st, 1u, c0, yv1, f0, r.nx, r.rows, d); // each half by the other's guide
+        launch_nlm(st, 1u, c1, yv0, f1, r.nx, r.rows, d);
+        ACCUM_READER(k_halves_combine, r, (const float*)f0, (const float*)f1, r.cnt, out, err, partials, r.nx, r.rows, a.first, r.n, r.tiles_per_row, r.tile_pixels);
+        hipLaunchKernelGGL(k_halves_final, dim3(1), dim3(256), 0, st, (const double2*)partials, nb, npix, figures);
+        if (out_err) RT_HIP(ctx, hipMemcpyAsync(out_err, err, (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, st));
+        RT_HIP(ctx, hipMemcpyAsync(ctx->h_resid, figures, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        img = out;
+        return RT_OK;
+    });
+    if (rc == RT_OK && res && a.npix) res->mean_luminance = ctx->h_resid[0], res->residual_rms = ctx->h_resid[1], res->residual_noise = ctx->h_resid[2];
+    return rc;
 }
 
 int rt_accum_export_halves(RtCtx* ctx, RtAccumHalves* hs) {
@@ -2179,29 +2170,22 @@ int rt_accum_read_robust(RtCtx* ctx, const RtRobust* rb, float* out_rgb_f32, uin
 
 int rt_accum_denoise_robust(RtCtx* ctx, const RtRobust* rb, const RtDenoise* dn, float* out_rgb_f32, uint8_t* out_rgb8) {
     if (!ctx) return RT_ERR_INVALID;
-    const RtCtx::Accum& a = ctx->accum;
-    RtDenoise d;
+    const DenoiseCall call{"rt_accum_denoise_robust", RT_DENOISE_DEFAULT_STRENGTH,
+                           ctx->accum.buckets ? nullptr : "the accumulation does not track buckets (rt_accum_track_buckets)", 2u, "there is no variance yet"};
     RtRobust r;
-    int rc = denoise_begin(ctx, "rt_accum_denoise_robust", dn, d, RT_DENOISE_DEFAULT_STRENGTH,
-                           a.buckets ? nullptr : "the accumulation does not track buckets (rt_accum_track_buckets)", 2u, "there is no variance yet");
-    if (rc) return rc;
-    if ((rc = robust_begin(ctx, "rt_accum_denoise_robust", rb, r))) return rc;
-    if (a.npix == 0u) return RT_OK;
-    RT_HIP(ctx, hipSetDevice(ctx->device));
-    const hipStream_t st = ctx->stream;
-    if ((rc = ensure_denoise(ctx, a.npix))) return rc;
-    if ((rc = ensure(ctx, ctx->robust_out, robust_head_bytes(a.npix)))) return rc;
-    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, (size_t)a.npix * 3))) return rc;
-    const AccumReader rd = accum_reader(ctx, st);
-    // the inputs of rt_accum_denoise, then the robust colours over c: the guide stays the luminance moments'.  Deliberately so:
-    // k_denoise_inputs stays the kernel it was, at the price of 12 B per pixel of plain colours written and then overwritten
-    ACCUM_READER(k_denoise_inputs, rd, ctx->accum_sum.as<const float>(), ctx->accum_mom.as<const double2>(), rd.cnt, ctx->dn_c.as<float>(), ctx->dn_yv.as<float2>(), rd.nx,
-                 rd.rows, rd.n, rd.tiles_per_row, rd.tile_pixels);
-    if ((rc = enqueue_robust(ctx, st, r, ctx->dn_c.as<float>(), nullptr, false))) return rc;
-    launch_denoise(st, ctx->dn_c.as<const float>(), ctx->dn_yv.as<const float2>(), ctx->dn_out.as<float>(), a.nx, a.rows, d);
-    if ((rc = denoise_finish(ctx, ctx->dn_out.as<const float>(), out_rgb_f32, out_rgb8))) return rc;
-    RT_HIP(ctx, hipStreamSynchronize(st));
-    return RT_OK;
+    return denoise_run(ctx, call, dn, out_rgb_f32, out_rgb8, [&]() { return robust_begin(ctx, call.who, rb, r); },
+                       [&](const AccumReader& rd, const RtDenoise& d, const float*& img) -> int {
+        int rc;
+        if ((rc = ensure_nlm(ctx, ctx->accum.npix, 1u))) return rc;
+        if ((rc = ensure(ctx, ctx->robust_out, robust_head_bytes(ctx->accum.npix)))) return rc;
+        // the inputs of rt_accum_denoise, then the robust colours over c: the guide stays the luminance moments'.  Deliberately so:
+        // k_denoise_inputs stays the kernel it was, at the price of 12 B per pixel of plain colours written and then overwritten
+        enqueue_denoise_inputs(ctx, rd);
+        if ((rc = enqueue_robust(ctx, rd.st, r, ctx->dn_c.as<float>(), nullptr, false))) return rc;
+        launch_nlm(rd.st, 1u, ctx->dn_c.as<const float>(), ctx->dn_yv.as<const float2>(), ctx->dn_out.as<float>(), rd.nx, rd.rows, d);
+        img = ctx->dn_out.as<const float>();
+        return RT_OK;
+    });
 }
 
 int rt_accum_export_buckets(RtCtx* ctx, RtAccumBuckets* bs) {

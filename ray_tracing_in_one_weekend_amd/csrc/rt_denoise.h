@@ -2,8 +2,9 @@
 // only, fed by what an accumulation already owns (the running f32 sum and the two f64 luminance moments per pixel).
 //
 //   k_denoise_inputs<COUNTS> : c = sum / (float)n, y = (float)Ybar, v = (float)V per pixel, in image order (COUNTS: n = the pixel's n_p)
-//   k_denoise<F>     : the filter; one thread per pixel, the (y, v) tile of a workgroup and its halo in LDS, the distance terms that the
-//                      patches of neighbouring pixels share evaluated once per workgroup
+//   nlm_filter<F, G> : the filter's body; one thread per pixel, the guide tile of a workgroup and its halo in LDS, the distance terms
+//                      that the patches of neighbouring pixels share evaluated once per workgroup; G: the guide policy
+//   k_denoise<F>     : nlm_filter<F, GuideLuminance>: one plane of (y, v), colours read from global memory
 //
 // Every operation of the filter is one IEEE f32 operation in the header's order (-ffp-contract=off, the compiler's correctly rounded
 // `/`): tests/denoise_ref.py restates it in numpy and the kernel is held to it bit for bit.
@@ -49,35 +50,52 @@ __device__ __forceinline__ float denoise_distance(float2 a, float2 b, float k2) 
 // puts them on the two halves of the banks; a map row is at most 16 + 2 * 3 = 22 wide.
 constexpr uint32_t RT_DN_MAP_PITCH = 48u;
 
+// What guides the filter, a compile-time policy of constants that answers the three things in which the two filters differ and nothing
+// else.  PLANES: how many float2 planes (mean, variance) the tile holds, 1 or 3; plane ch of a tile entry lies ch * plane entries behind
+// plane 0.  With it what a map entry is: d of the one plane, or (d_0 + d_1) + d_2, and the divisor PLANES times the patch's pixels.
+// COLOUR_IN_TILE: channel ch of a pixel's colour is the .x of plane ch of its tile entry; otherwise c[3 * pixel + ch] in global memory.
+// (Constants, not functions: the compiler simplifies a policy's function on its own before it inlines it, without the body around it,
+// and the kernels then come out as other, if equivalent, code than the text written out in one piece gives.)
+// GuideLuminance: one plane of (y, v); colours from global memory.  (GuideChannels: rt_channels.h.)
+struct GuideLuminance {
+    static constexpr int PLANES = 1;
+    static constexpr bool COLOUR_IN_TILE = false;
+};
+
+// The non-local-means body of k_denoise<F> and k_denoise_channels<F>.  g: G::PLANES entries (mean, variance) per pixel in image order.
 // F: the patch radius (0 .. RT_DENOISE_MAX_PATCH), a template parameter so that the patch loops unroll.  R: 1 .. RT_DENOISE_MAX_RADIUS.
-// Grid: ceil(nx / 16) x ceil(rows / 16) workgroups of 16 x 16 threads; dynamic LDS: denoise_lds_bytes(R, F).
+// Grid: ceil(nx / 16) x ceil(rows / 16) workgroups of 16 x 16 threads; dynamic LDS: nlm_lds_bytes(G::PLANES, R, F).
 //
-// The tile.  LDS entry (lx, ly) holds (y, v) of the pixel clamp(x0 - H + lx), clamp(y0 - H + ly), H = R + F, each axis clamped on its
-// own: the clamped patch coordinates of the header ARE the entries at p + o and q + o, since q itself lies in the image.
+// The tile.  LDS entry (lx, ly) of a plane holds (mean, v) of the pixel clamp(x0 - H + lx), clamp(y0 - H + ly), H = R + F, each axis
+// clamped on its own: the clamped patch coordinates of the header ARE the entries at p + o and q + o, since q itself lies in the image
+// (so its entry is unclamped).  Every plane has the pitch RT_DN_PITCH, so its bank argument holds per plane.
 //
 // Shared terms.  The term of offset o in the patch distance of (p, q = p + delta) is e(x, delta) = d(clamp(x), clamp(x + delta)) with
-// x = p + o: a function of x and delta alone, and the same term for the (2F + 1)^2 pixels p = x - o.  So per delta the workgroup
-// evaluates e ONCE for every x of its tile grown by F — (16 + 2F)^2 terms, each with its division, instead of 256 (2F + 1)^2 — into a
-// map in LDS, and a pixel sums its (2F + 1)^2 entries in the header's order (rows first): the same operands in the same order, the
-// same bits.  The map is double-buffered, so one barrier per delta is enough: a thread that runs ahead writes the other buffer, and
-// reaches the buffer being read only behind the next barrier, which every reader has then passed.  Every thread of the workgroup walks all
-// deltas (the barriers), whether its pixel or its q lies in the image or not; only the accumulation is guarded.
-template <int F>
-__global__ __launch_bounds__(256) void k_denoise(const float* __restrict__ c, const float2* __restrict__ yv, float* __restrict__ out,
-                                                 uint32_t nx, uint32_t rows, int R, float k2) {
+// x = p + o, summed over the planes: a function of x and delta alone, and the same term for the (2F + 1)^2 pixels p = x - o.  So per
+// delta the workgroup evaluates e ONCE for every x of its tile grown by F — (16 + 2F)^2 terms, each with its division per plane, instead
+// of 256 (2F + 1)^2 — into a map in LDS, and a pixel sums its (2F + 1)^2 entries in the header's order (rows first): the same operands in
+// the same order, the same bits.  The map is double-buffered, so one barrier per delta is enough: a thread that runs ahead writes the
+// other buffer, and reaches the buffer being read only behind the next barrier, which every reader has then passed.  Every thread of the
+// workgroup walks all deltas (the barriers), whether its pixel or its q lies in the image or not; only the accumulation is guarded.
+template <int F, class G>
+__device__ __forceinline__ void nlm_filter(const float* c, const float2* g, float* out, uint32_t nx, uint32_t rows, int R, float k2) {
     extern __shared__ float2 dn_tile[];
-    constexpr int T = (int)RT_DN_TILE, TP = (int)RT_DN_PITCH, MP = (int)RT_DN_MAP_PITCH;
+    constexpr int T = (int)RT_DN_TILE, TP = (int)RT_DN_PITCH, MP = (int)RT_DN_MAP_PITCH, P = G::PLANES;
+    static_assert(P == 1 || P == 3, "the map entry is written out for one plane and for three");
     constexpr int E = T + 2 * F; // side of the distance map
     const int H = R + F;
     const int side = T + 2 * H;
-    float* const dmap = reinterpret_cast<float*>(dn_tile + TP * side); // 2 buffers of MP * E floats
+    const int plane = TP * side;
+    float* const dmap = reinterpret_cast<float*>(dn_tile + P * plane); // 2 buffers of MP * E floats
     const int x0 = (int)(blockIdx.x * RT_DN_TILE) - H, y0 = (int)(blockIdx.y * RT_DN_TILE) - H;
     const int tx = (int)threadIdx.x, ty = (int)threadIdx.y;
     const int tid = ty * T + tx;
     for (int e = tid; e < side * side; e += 256) {
         const int ly = e / side, lx = e - ly * side;
         const int gx = min(max(x0 + lx, 0), (int)nx - 1), gy = min(max(y0 + ly, 0), (int)rows - 1);
-        dn_tile[ly * TP + lx] = yv[(size_t)gy * nx + gx];
+        const float2* src = g + P * ((size_t)gy * nx + gx);
+        float2* dst = dn_tile + ly * TP + lx;
+        for (int ch = 0; ch < P; ++ch) dst[ch * plane] = src[ch];
     }
     __syncthreads();
     const int px = (int)(blockIdx.x * RT_DN_TILE) + tx, py = (int)(blockIdx.y * RT_DN_TILE) + ty;
@@ -89,8 +107,10 @@ __global__ __launch_bounds__(256) void k_denoise(const float* __restrict__ c, co
     const int m1y = two ? e1 / E : 0, m1x = two ? e1 - m1y * E : 0;
     const float2* const a0p = dn_tile + (m0y + R) * TP + m0x + R; // map entry (mx, my) is x = tile origin - F + (mx, my): tile entry + R
     const float2* const a1p = dn_tile + (m1y + R) * TP + m1x + R;
-    const float2 a0 = *a0p, a1 = *a1p;
-    constexpr float cnt = (float)((2 * F + 1) * (2 * F + 1));
+    const float2 a0 = a0p[0], a0g = a0p[P == 3 ? plane : 0], a0b = a0p[P == 3 ? 2 * plane : 0]; // (one plane: a0g, a0b are not used)
+    const float2 a1 = a1p[0], a1g = a1p[P == 3 ? plane : 0], a1b = a1p[P == 3 ? 2 * plane : 0];
+    const float2* const me = dn_tile + (ty + H) * TP + tx + H; // the tile entry of p
+    constexpr float cnt = (float)(P * (2 * F + 1) * (2 * F + 1));
     float den = 0.0f, nr = 0.0f, ng = 0.0f, nb = 0.0f;
     int buf = 0;
     for (int dy = -R; dy <= R; ++dy) {
@@ -98,8 +118,16 @@ __global__ __launch_bounds__(256) void k_denoise(const float* __restrict__ c, co
         for (int dx = -R; dx <= R; ++dx, buf ^= 1) {
             float* const map = dmap + buf * (MP * E);
             const int off = dy * TP + dx;
-            map[m0y * MP + m0x] = denoise_distance(a0, a0p[off], k2);
-            if (two) map[m1y * MP + m1x] = denoise_distance(a1, a1p[off], k2);
+            if constexpr (P == 1) {
+                map[m0y * MP + m0x] = denoise_distance(a0, a0p[off], k2);
+                if (two) map[m1y * MP + m1x] = denoise_distance(a1, a1p[off], k2);
+            } else {
+                map[m0y * MP + m0x] = (denoise_distance(a0, a0p[off], k2) + denoise_distance(a0g, a0p[plane + off], k2)) +
+                                      denoise_distance(a0b, a0p[2 * plane + off], k2);
+                if (two)
+                    map[m1y * MP + m1x] = (denoise_distance(a1, a1p[off], k2) + denoise_distance(a1g, a1p[plane + off], k2)) +
+                                          denoise_distance(a1b, a1p[2 * plane + off], k2);
+            }
             __syncthreads();
             const int qx = px + dx;
             if (!live || qy < 0 || qy >= (int)rows || qx < 0 || qx >= (int)nx) continue;
@@ -116,21 +144,34 @@ __global__ __launch_bounds__(256) void k_denoise(const float* __restrict__ c, co
             u = u > 0.0f ? u : 0.0f;             // (a NaN becomes 0)
             if (u != 0.0f) {
                 const float w = (u * u) * (u * u);
-                const float* cq = c + 3 * ((size_t)qy * nx + qx);
                 den = den + w;
-                nr = nr + w * cq[0], ng = ng + w * cq[1], nb = nb + w * cq[2];
+                if constexpr (G::COLOUR_IN_TILE) {
+                    nr = nr + w * me[off].x, ng = ng + w * me[plane + off].x, nb = nb + w * me[2 * plane + off].x;
+                } else {
+                    const float* cq = c + 3 * ((size_t)qy * nx + qx);
+                    nr = nr + w * cq[0], ng = ng + w * cq[1], nb = nb + w * cq[2];
+                }
             }
         }
     }
     if (!live) return;
     const size_t p = (size_t)py * nx + px;
-    float r = c[3 * p], g = c[3 * p + 1], b = c[3 * p + 2]; // den == 0: p itself is not finite and stays what it is
-    if (den != 0.0f) r = nr / den, g = ng / den, b = nb / den;
-    out[3 * p] = r, out[3 * p + 1] = g, out[3 * p + 2] = b;
+    float r, gr, b; // den == 0: p itself is not finite and stays what it is
+    if constexpr (G::COLOUR_IN_TILE) r = me[0].x, gr = me[plane].x, b = me[2 * plane].x;
+    else r = c[3 * p], gr = c[3 * p + 1], b = c[3 * p + 2];
+    if (den != 0.0f) r = nr / den, gr = ng / den, b = nb / den;
+    out[3 * p] = r, out[3 * p + 1] = gr, out[3 * p + 2] = b;
 }
-// dynamic LDS of k_denoise<F>: the (y, v) tile and the two distance maps
-__host__ inline size_t denoise_lds_bytes(uint32_t R, uint32_t F) {
-    return (size_t)RT_DN_PITCH * (RT_DN_TILE + 2u * (R + F)) * sizeof(float2) + 2u * RT_DN_MAP_PITCH * (RT_DN_TILE + 2u * F) * sizeof(float);
+// dynamic LDS of the filter: `planes` tiles and the two distance maps.  R 5, F 1: 17 664 B with one plane, 39 168 B with three; R 10, F 3, the
+// maximum: 24 576 B and 56 832 B
+__host__ inline size_t nlm_lds_bytes(uint32_t planes, uint32_t R, uint32_t F) {
+    return planes * (size_t)RT_DN_PITCH * (RT_DN_TILE + 2u * (R + F)) * sizeof(float2) + 2u * RT_DN_MAP_PITCH * (RT_DN_TILE + 2u * F) * sizeof(float);
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void k_denoise(const float* __restrict__ c, const float2* __restrict__ yv, float* __restrict__ out,
+                                                 uint32_t nx, uint32_t rows, int R, float k2) {
+    nlm_filter<F, GuideLuminance>(c, yv, out, nx, rows, R, k2);
 }
 
 } // namespace rt

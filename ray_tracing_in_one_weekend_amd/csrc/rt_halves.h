@@ -4,7 +4,8 @@
 //
 //   k_resolve_halves<ACTIVE>        : the slice's samples onto the half sums and moments by the parity of their absolute index
 //   k_halves_read<COUNTS>           : one half as an image and its standard error, in image order
-//   k_denoise_inputs_halves<COUNTS> : c_0, c_1, (y, v)_0, (y, v)_1 in image order — what the two launches of k_denoise<F> read
+//   k_denoise_inputs_halves<COUNTS> : c_0, c_1, (y, v)_0, (y, v)_1 in image order — what the two launches of k_denoise<F> read (rt_denoise.h:
+//                                     nlm_filter with one guide plane), each half by the other's (y, v)
 //   k_halves_combine<COUNTS>        : out and e per pixel from f_0 and f_1, and the per-workgroup partial sums of the frame figures
 //   k_halves_final                  : one workgroup over the partials -> mean_luminance, residual_rms, residual_noise
 // (rt_accum_export_halves and _import_halves move the four planes as a PlaneTable through k_planes_move, rt_accum_state_kernels.h.)

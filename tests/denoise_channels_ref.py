@@ -8,7 +8,6 @@ import denoise_ref
 import noise_ref
 
 F32 = np.float32
-EPS = denoise_ref.EPS
 KERNEL_CASE_STRENGTH = denoise_ref.KERNEL_CASE_STRENGTH
 
 
@@ -51,55 +50,10 @@ def channel_sem(s1, s2, n):
 
 # ---- the filter -----------------------------------------------------------------------------------------------------------------------
 def denoise(c, var, radius, patch, strength):
-    """c, var [rows, nx, 3] in image order -> (out [rows, nx, 3] f32, shares) as denoise_ref.denoise returns them."""
+    """c, var [rows, nx, 3] in image order -> (out [rows, nx, 3] f32, shares) as denoise_ref.denoise returns them: denoise_ref.nlm with
+    the three guide planes (c_ch, var_ch), so a term is (d_r + d_g) + d_b and the divisor 3 (2F + 1)^2."""
     c, var = np.asarray(c, F32), np.asarray(var, F32)
-    rows, nx, _ = c.shape
-    R, F = int(radius), int(patch)
-    k = F32(strength)
-    k2 = F32(k * k)
-    cnt3 = F32(3 * (2 * F + 1) * (2 * F + 1))
-    ys, xs = np.mgrid[0:rows, 0:nx]
-
-    def at(a, yy, xx):
-        return a[np.clip(yy, 0, rows - 1), np.clip(xx, 0, nx - 1)]
-
-    def d(ca, va, cb, vb):
-        diff = ca - cb
-        vmin = np.where(vb < va, vb, va)
-        return (diff * diff - (va + vmin)) / (EPS + k2 * (va + vb))
-
-    den = np.zeros((rows, nx), F32)
-    num = np.zeros((rows, nx, 3), F32)
-    n_zero = n_mid = n_one = 0
-    with np.errstate(all="ignore"):
-        for dy in range(-R, R + 1):
-            for dx in range(-R, R + 1):
-                qy, qx = ys + dy, xs + dx
-                inside = (qy >= 0) & (qy < rows) & (qx >= 0) & (qx < nx)
-                S = np.zeros((rows, nx), F32)
-                for oy in range(-F, F + 1):
-                    row = np.zeros((rows, nx), F32)
-                    for ox in range(-F, F + 1):
-                        ca, va = at(c, ys + oy, xs + ox), at(var, ys + oy, xs + ox)
-                        cb, vb = at(c, qy + oy, qx + ox), at(var, qy + oy, qx + ox)  # (q outside the image: masked out below)
-                        dr, dg, db = (d(ca[..., ch], va[..., ch], cb[..., ch], vb[..., ch]) for ch in range(3))
-                        row = row + ((dr + dg) + db)
-                    S = S + row
-                D = S / cnt3
-                m = np.where(D < 0, F32(0), D)  # a NaN stays
-                u = F32(1) - F32(0.25) * m
-                u = np.where(u > 0, u, F32(0))  # a NaN becomes 0
-                w = (u * u) * (u * u)
-                use = inside & (u != 0)
-                den = np.where(use, den + w, den)
-                num = np.where(use[..., None], num + w[..., None] * at(c, qy, qx), num)
-                n_zero += int((inside & (w == 0)).sum())
-                n_one += int((inside & (w == 1)).sum())
-                n_mid += int((inside & (w > 0) & (w < 1)).sum())
-        out = np.where((den == 0)[..., None], c, num / den[..., None])
-    assert out.dtype == F32 and den.dtype == F32 and num.dtype == F32
-    total = max(n_zero + n_mid + n_one, 1)
-    return out, (n_zero / total, n_mid / total, n_one / total)
+    return denoise_ref.nlm(c, [(c[..., ch], var[..., ch]) for ch in range(3)], radius, patch, strength)
 
 
 # ---- frames ---------------------------------------------------------------------------------------------------------------------------

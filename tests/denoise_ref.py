@@ -10,53 +10,52 @@ EPS = F32(1e-10)
 KERNEL_CASE_STRENGTH = 0.45  # at which kernel_case(37, 21) with (R 5, F 1) has >= 10 % of its pairs in each weight class (test_denoise_host.py)
 
 
-def denoise(c, y, v, radius, patch, strength):
-    """c [rows, nx, 3], y, v [rows, nx] in image order -> (out [rows, nx, 3] f32, shares), shares = the fractions of the in-image (p, q)
-    pairs with w == 0, 0 < w < 1 and w == 1."""
-    c, y, v = np.asarray(c, F32), np.asarray(y, F32), np.asarray(v, F32)
-    rows, nx = y.shape
-    R, F = int(radius), int(patch)
-    k = F32(strength)
-    k2 = F32(k * k)
-    cnt = F32((2 * F + 1) * (2 * F + 1))
-    ys, xs = np.mgrid[0:rows, 0:nx]
+def nlm(colours, guides, radius, patch, strength):
+    """The body both filters share.  colours [rows, nx, 3]; guides: a list of (mean, variance) planes [rows, nx], all in image order.  A
+    term of the patch distance is the left-to-right sum of the planes' d, the divisor len(guides) (2F + 1)^2.  Returns (out [rows, nx, 3]
+    f32, shares), shares = the fractions of the in-image (p, q) pairs with w == 0, 0 < w < 1 and w == 1."""
+    c, guides = np.asarray(colours, F32), [(np.asarray(g, F32), np.asarray(v, F32)) for g, v in guides]
+    (rows, nx), R, F, k = c.shape[:2], int(radius), int(patch), F32(strength)
+    k2, cnt = F32(k * k), F32(len(guides) * (2 * F + 1) * (2 * F + 1))
+    (ys, xs), (ye, xe) = np.mgrid[0:rows, 0:nx], np.mgrid[-F:rows + F, -F:nx + F]
 
     def at(a, yy, xx):
         return a[np.clip(yy, 0, rows - 1), np.clip(xx, 0, nx - 1)]
 
-    den = np.zeros((rows, nx), F32)
-    num = np.zeros((rows, nx, 3), F32)
-    n_zero = n_mid = n_one = 0
+    def d(g, v, ay, ax, by, bx):  # one plane's d between the pixels a and b, each clamped on its own
+        diff, va, vb = at(g, ay, ax) - at(g, by, bx), at(v, ay, ax), at(v, by, bx)
+        return (diff * diff - (va + np.where(vb < va, vb, va))) / (EPS + k2 * (va + vb))
+
+    den, num, n = np.zeros((rows, nx), F32), np.zeros((rows, nx, 3), F32), [0, 0, 0]
     with np.errstate(all="ignore"):
         for dy in range(-R, R + 1):
             for dx in range(-R, R + 1):
                 qy, qx = ys + dy, xs + dx
                 inside = (qy >= 0) & (qy < rows) & (qx >= 0) & (qx < nx)
+                terms = [d(g, v, ye, xe, ye + dy, xe + dx) for g, v in guides]  # at every x = p + o, once: all (p, o) with this x share it
+                e = sum(terms[1:], terms[0])  # (left to right; one plane: d itself.  q outside the image: masked out below)
                 S = np.zeros((rows, nx), F32)
-                for oy in range(-F, F + 1):
+                for oy in range(F + F + 1):
                     row = np.zeros((rows, nx), F32)
-                    for ox in range(-F, F + 1):
-                        ya, va = at(y, ys + oy, xs + ox), at(v, ys + oy, xs + ox)
-                        yb, vb = at(y, qy + oy, qx + ox), at(v, qy + oy, qx + ox)  # (q outside the image: masked out below)
-                        diff = ya - yb
-                        vmin = np.where(vb < va, vb, va)
-                        row = row + (diff * diff - (va + vmin)) / (EPS + k2 * (va + vb))
+                    for ox in range(F + F + 1):
+                        row = row + e[oy:oy + rows, ox:ox + nx]
                     S = S + row
                 D = S / cnt
-                m = np.where(D < 0, F32(0), D)  # a NaN stays
-                u = F32(1) - F32(0.25) * m
+                u = F32(1) - F32(0.25) * np.where(D < 0, F32(0), D)  # max(D, 0), but a NaN stays
                 u = np.where(u > 0, u, F32(0))  # a NaN becomes 0
                 w = (u * u) * (u * u)
                 use = inside & (u != 0)
                 den = np.where(use, den + w, den)
                 num = np.where(use[..., None], num + w[..., None] * at(c, qy, qx), num)
-                n_zero += int((inside & (w == 0)).sum())
-                n_one += int((inside & (w == 1)).sum())
-                n_mid += int((inside & (w > 0) & (w < 1)).sum())
+                n = [a + int((inside & cls).sum()) for a, cls in zip(n, (w == 0, (w > 0) & (w < 1), w == 1))]
         out = np.where((den == 0)[..., None], c, num / den[..., None])
     assert out.dtype == F32 and den.dtype == F32 and num.dtype == F32
-    total = max(n_zero + n_mid + n_one, 1)
-    return out, (n_zero / total, n_mid / total, n_one / total)
+    return out, tuple(x / max(sum(n), 1) for x in n)
+
+
+def denoise(c, y, v, radius, patch, strength):
+    """c [rows, nx, 3], y, v [rows, nx] in image order -> (out, shares) of nlm with the one guide plane (y, v)."""
+    return nlm(c, [(y, v)], radius, patch, strength)
 
 
 def truth_image(nx, rows):

@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import denoise_channels_ref
 import denoise_ref
 import noise_ref
 
@@ -52,8 +53,9 @@ def _setup(rt, r, case):
 
 # ---- 1. the filter kernel against denoise_ref -----------------------------------------------------------------------------------------
 # 37 x 21: three workgroup tiles of 16 across and two up, the last of each partial; 13 x 9 with the largest window and patch: both exceed
-# the frame, every clamp is in play; 1 x 1: one pixel, one workgroup.
-KERNEL_CASES = [(37, 21, 5, 1), (37, 21, 1, 0), (13, 9, 10, 3), (1, 1, 5, 1), (37, 21, 3, 2)]
+# the frame, every clamp is in play; 1 x 1: one pixel, one workgroup; 17 x 33 and 33 x 17 with F = 3: one pixel column or row spills
+# into a second or third tile, and with R 10 the halo is larger than the image.
+KERNEL_CASES = [(37, 21, 5, 1), (37, 21, 1, 0), (13, 9, 10, 3), (1, 1, 5, 1), (37, 21, 3, 2), (17, 33, 2, 3), (33, 17, 10, 3)]
 
 
 @pytest.mark.parametrize("nx,rows,radius,patch", KERNEL_CASES)
@@ -67,6 +69,18 @@ def test_kernel_matches_the_reference_bit_for_bit(ctx, nx, rows, radius, patch):
         assert (~np.isfinite(y)).sum() == 2 and (v == 0).sum() >= 8 and (want != c).any()
     got = ctx.debug_denoise(c, y, v, radius, patch, k)
     _same(got, want, (nx, rows, radius, patch))
+
+
+def test_the_debug_path_keeps_nothing_from_the_other_filter(ctx):
+    """rt_debug_denoise and rt_debug_denoise_channels share one host path and the filter's scratch buffers: a call of the other filter at
+    another size in between changes no bit of what the first inputs give."""
+    c, y, v = denoise_ref.kernel_case(37, 21)
+    c3, var3 = denoise_channels_ref.kernel_case(13, 9)
+    k = denoise_ref.KERNEL_CASE_STRENGTH
+    first = ctx.debug_denoise(c, y, v, 5, 1, k)
+    between = ctx.debug_denoise_channels(c3, var3, 5, 1, k)
+    assert between.shape == c3.shape and (first != c).any() and (between != c3).any()
+    _same(ctx.debug_denoise(c, y, v, 5, 1, k), first, "the first inputs again")
 
 
 # ---- 2. the accumulation against denoise_ref ------------------------------------------------------------------------------------------

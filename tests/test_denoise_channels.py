@@ -73,8 +73,9 @@ def _variances(x, n):
 
 # ---- 1. the filter kernel against the reference ---------------------------------------------------------------------------------------
 # 37 x 21: three workgroup tiles of 16 across and two up, the last of each partial; 13 x 9 with the largest window and patch: both exceed
-# the frame, every clamp is in play; 1 x 1: one pixel, one workgroup; F = 0, 1, 2, 3: every instantiation.
-KERNEL_CASES = [(37, 21, 5, 1), (37, 21, 1, 0), (37, 21, 3, 2), (13, 9, 10, 3), (1, 1, 5, 1)]
+# the frame, every clamp is in play; 1 x 1: one pixel, one workgroup; F = 0, 1, 2, 3: every instantiation; 17 x 33 and 33 x 17 with
+# F = 3: one pixel column or row spills into a second or third tile, and with R 10 the halo is larger than the image.
+KERNEL_CASES = [(37, 21, 5, 1), (37, 21, 1, 0), (37, 21, 3, 2), (13, 9, 10, 3), (1, 1, 5, 1), (17, 33, 2, 3), (33, 17, 10, 3)]
 
 
 @pytest.mark.parametrize("nx,rows,radius,patch", KERNEL_CASES)
@@ -90,6 +91,18 @@ def test_kernel_matches_the_reference_bit_for_bit(ctx, nx, rows, radius, patch):
         assert (want != c).any()
     got = ctx.debug_denoise_channels(c, var, radius, patch, k)
     _same(got, want, (nx, rows, radius, patch))
+
+
+def test_the_debug_path_keeps_nothing_from_the_other_filter(ctx):
+    """test_denoise.py's test of the same name, mirrored: the channels filter, the luminance filter at another size, the channels filter
+    again with the first inputs."""
+    c, var = ch_ref.kernel_case(37, 21)
+    c1, y1, v1 = denoise_ref.kernel_case(13, 9)
+    k = ch_ref.KERNEL_CASE_STRENGTH
+    first = ctx.debug_denoise_channels(c, var, 5, 1, k)
+    between = ctx.debug_denoise(c1, y1, v1, 5, 1, k)
+    assert between.shape == c1.shape and (first != c).any() and (between != c1).any()
+    _same(ctx.debug_denoise_channels(c, var, 5, 1, k), first, "the first inputs again")
 
 
 # ---- 2. the moments, and everything else unchanged ------------------------------------------------------------------------------------

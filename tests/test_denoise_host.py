@@ -1,12 +1,17 @@
 """The denoising filter (rt_accum_denoise) without a GPU: the struct layout, the bindings, and properties of tests/denoise_ref.py, the numpy
 restatement of the header's definition that the GPU tests hold the kernel to bit for bit."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
 import numpy as np
+import pytest
 
+import denoise_channels_ref
 import denoise_ref
+import test_denoise
+import test_denoise_channels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
@@ -102,3 +107,50 @@ def test_the_kernel_case_covers_every_weight_class():
     c, y, v = denoise_ref.kernel_case(37, 21)
     _, shares = denoise_ref.denoise(c, y, v, 5, 1, denoise_ref.KERNEL_CASE_STRENGTH)
     assert min(shares) >= 0.10, shares
+
+
+# sha256 of out.tobytes() of (denoise_ref.denoise, denoise_channels_ref.denoise) on their kernel_case inputs at KERNEL_CASE_STRENGTH, for
+# every entry of both KERNEL_CASES lists: computed with the two references as they were before they became wrappers of denoise_ref.nlm.
+REFERENCE_DIGESTS = {
+    (37, 21, 5, 1): ("be60f98af4410093fde2750072c6b3355fc8d3e8c4568bf65a15553863e5e783",
+                     "48e970e4168dc77c97c8e0b505ce2b4ae358d5bb7a33335d009978ede8385dab"),
+    (37, 21, 1, 0): ("4c01bbb29fa665650b84db9360b476789c3dd2587300668e920c64784a73ee0b",
+                     "955ee1b02b2c07d68692be3e198bf93fa108fb46df073ea19ca4ae684d854997"),
+    (13, 9, 10, 3): ("de7828c204373310e71ad40e2259295d379a53e6a3ee6d55fd542d6bde6cc00d",
+                     "aa72f68bde8253be8aeba9ff5fd3603116afdbb6e0604e4b45a12b2c78b48ba1"),
+    (1, 1, 5, 1): ("6b730b5f0d00d88b2f0abf3cb425f6a98644b3074a13e4b3507268eb6ef07d63",
+                   "6b730b5f0d00d88b2f0abf3cb425f6a98644b3074a13e4b3507268eb6ef07d63"),
+    (37, 21, 3, 2): ("e657eb97da4a1141e5df9a7feb67b71220764e1cf64630ef991ef0947cbc004a",
+                     "90fe5e3d213c9b6244399ba4bdf1d93f34509aab3d34796517586dd5949a6014"),
+    (17, 33, 2, 3): ("533ad64658cdf4eb1744ceeaf31e03d9327bb0a2a2025ee817a34aafaee4306f",
+                     "8a6d016f39ac70490806a6aba60f4327e436016f8e551c4851ec105470bc824d"),
+    (33, 17, 10, 3): ("ef4f664e2fca4fa027398c3e390df824a8a58f7792d695f464fd60b079e108e5",
+                      "1da98278a9524a358b92739cab9622a1a9f20753e38ea4357eae591d464164be"),
+}
+
+
+def test_the_digests_cover_every_kernel_case():
+    assert set(REFERENCE_DIGESTS) == set(test_denoise.KERNEL_CASES) == set(test_denoise_channels.KERNEL_CASES)
+
+
+@pytest.mark.parametrize("case", list(REFERENCE_DIGESTS))
+def test_the_folded_references_reproduce_the_digests_of_the_separate_ones(case):
+    nx, rows, radius, patch = case
+    k = denoise_ref.KERNEL_CASE_STRENGTH
+    c, y, v = denoise_ref.kernel_case(nx, rows)
+    c3, var3 = denoise_channels_ref.kernel_case(nx, rows)
+    got = (hashlib.sha256(denoise_ref.denoise(c, y, v, radius, patch, k)[0].tobytes()).hexdigest(),
+           hashlib.sha256(denoise_channels_ref.denoise(c3, var3, radius, patch, k)[0].tobytes()).hexdigest())
+    assert got == REFERENCE_DIGESTS[case]
+
+
+def test_the_plane_count_is_part_of_the_filter():
+    """nlm with one guide plane is denoise_ref.denoise in bits; the same plane given three times is another filter (the term is the sum
+    of three equal d, (d + d) + d, over three times the divisor: not d again in f32), so a fold that ignored the planes would show."""
+    c, y, v = denoise_ref.kernel_case(37, 21)
+    k = denoise_ref.KERNEL_CASE_STRENGTH
+    one, shares = denoise_ref.nlm(c, [(y, v)], 5, 1, k)
+    want, want_shares = denoise_ref.denoise(c, y, v, 5, 1, k)
+    assert np.array_equal(_bits(one), _bits(want)) and shares == want_shares
+    three, _ = denoise_ref.nlm(c, [(y, v)] * 3, 5, 1, k)
+    assert three.shape == one.shape and not np.array_equal(_bits(three), _bits(one))
