@@ -894,6 +894,57 @@ int rt_accum_export_buckets(RtCtx* ctx, RtAccumBuckets* bs);
  * once. */
 int rt_accum_import_buckets(RtCtx* ctx, const RtAccumBuckets* bs);
 
+/* -- multi-scale denoising: the filter on a 2x pyramid ---------------------------------------------------------------------------------------
+ * The window of "Denoising" is at most 21 x 21 pixels; noise of a longer wavelength passes it and shows as low-frequency blotches.  The
+ * standard cure filters a 2x image pyramid and lets every coarser level replace the low frequencies of the finer one (Rousselle et al.
+ * 2012; Delbracio et al. 2014: "Boosting Monte Carlo rendering by ray histogram fusion"; Boughida, Boubekeur 2017), for about
+ * 1/4 + 1/16 + .. of the single-scale filter on top of it.  New kernels only, around the unchanged filter of the chosen guide.
+ * Every operation is one IEEE f32 operation in the order written, no FMA.
+ * Levels.  L = levels, 1 .. RT_DENOISE_MAX_LEVELS.  Level 0 is the frame: nx_0 = nx, rows_0 = rows;  nx_{s+1} = (nx_s + 1) / 2 and
+ *   rows_{s+1} = (rows_s + 1) / 2, integer division (rt_denoise_level_size).  There are always exactly L levels; a side of 1 stays 1.
+ * Inputs of level 0.  Exactly what the single-scale filter of the guide reads, for uniform and adaptive accumulations alike, the NaN
+ *   guide of a pixel with n_p < 2 included.  RT_DENOISE_GUIDE_LUMINANCE: c (3 floats), y, v of "Denoising".  RT_DENOISE_GUIDE_CHANNELS: c
+ *   and the three channel variances of "Channel moments and the colour-guided filter"; the guide means are c.
+ * Downsample D (level s -> s + 1).  For the coarse pixel (X, Y) and a plane a of level s:
+ *   t00 = a(2X, 2Y), t10 = a(2X+1, 2Y), t01 = a(2X, 2Y+1), t11 = a(2X+1, 2Y+1), a tap outside the level-s image +0.0f;
+ *   sum = (t00 + t10) + (t01 + t11);   kx = 1 + (2X+1 < nx_s), ky = 1 + (2Y+1 < rows_s), k = kx * ky in {1, 2, 4};
+ *   a mean plane — the colour channels, y, the channel means — is sum * (1/k);  a variance plane is sum * (1/(k*k)), the variance of a
+ *   mean of k independent pixel means.  The four multipliers 1, 0.5, 0.25, 0.0625 are powers of two: the scale is exact.
+ * Filter.  F_s = the filter of the guide over the inputs of level s, with the caller's R, F and strength on every level.
+ * Combine, from coarse to fine.  o_{L-1} = F_{L-1}.  For s = L-2 .. 0:
+ *   at level s+1, per channel:  e = o_{s+1} - D(F_s), D in the mean form;  an e that is not finite is replaced by +0.0f;
+ *   at level s, per pixel (x, y) and channel:
+ *     o_s = F_s + ((0.5625f * e(X, Y) + 0.1875f * e(X', Y)) + (0.1875f * e(X, Y') + 0.0625f * e(X', Y'))),
+ *     X = x >> 1,  X' = clamp(X + ((x & 1) ? 1 : -1), 0, nx_{s+1} - 1);  Y and Y' likewise from y and rows_{s+1}:
+ *   the 2x bilinear interpolation at pixel centres, clamped at the border.
+ * Output.  o_0; out_rgb8 is o_0 through the quantisation and flip of rt_render.
+ * Properties (tests/denoise_multiscale_ref.py restates all of it in numpy, and the kernels are held to it bit for bit):
+ *   L = 1 is the single-scale filter of the same guide, bit for bit.
+ *   A non-finite pixel stays itself and spreads to no other: its coarse pixel is non-finite, which the filter leaves alone while it skips
+ *   every patch that holds it; the e of that coarse pixel become 0, so its three finite siblings get their level-0 result.
+ *   A constant dyadic image without variance comes back bit for bit.
+ *   The accumulation is read and not changed.
+ * Cost: the levels above 0 take about a third of level 0 in time and memory (DESIGN.md "Multi-scale denoising").
+ * Not covered: the cross-filtered halves of "Half buffers" and the robust read-out of "Sample buckets" (both stay single-scale); sharded
+ * frames (RT_ERR_UNSUPPORTED, as rt_accum_denoise); rt_multi_*. */
+typedef struct RtMultiscale {
+    uint32_t levels, guide; /* 1 .. RT_DENOISE_MAX_LEVELS; RT_DENOISE_GUIDE_* */
+    uint32_t reserved[2];   /* 0 */
+} RtMultiscale;
+#define RT_DENOISE_MAX_LEVELS 4u
+#define RT_DENOISE_GUIDE_LUMINANCE 0u
+#define RT_DENOISE_GUIDE_CHANNELS 1u
+#define RT_DENOISE_DEFAULT_LEVELS 2u /* 2 unless 3 is more than 5 % better on both cornell frames (DESIGN.md "Multi-scale denoising") */
+/* GPU-free, no context.  The size of level `level` (0 .. RT_DENOISE_MAX_LEVELS - 1) of a frame of nx x rows pixels into *nx_l and
+ * *rows_l (each may be NULL).  RT_ERR_INVALID: nx or rows 0, or a level outside the range. */
+int rt_denoise_level_size(uint32_t nx, uint32_t rows, uint32_t level, uint32_t* nx_l, uint32_t* rows_l);
+/* The multi-scale filter above over the frame of the open accumulation.  `dn` as rt_accum_denoise reads it; `ms` NULL:
+ * RT_DENOISE_DEFAULT_LEVELS levels with the luminance guide.  Outputs, the untouched accumulation, the one synchronisation and every
+ * error are those of the single-scale call of the same guide — rt_accum_denoise, or rt_accum_denoise_channels with its RT_ERR_STATE where
+ * the accumulation does not track channels.  In addition RT_ERR_INVALID: levels 0 or above RT_DENOISE_MAX_LEVELS, an unknown guide,
+ * reserved != 0. */
+int rt_accum_denoise_multiscale(RtCtx* ctx, const RtDenoise* dn, const RtMultiscale* ms, float* out_rgb_f32, uint8_t* out_rgb8);
+
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the
  * world shared read-only (main.rs:72-108); here the scene is replicated on every device, device r renders the image

@@ -246,6 +246,16 @@ int rt_debug_denoise(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, c
  * rgb [3 * nx * rows] = c and var_rgb [3 * nx * rows] = the three channel variances, both in image order; errors as rt_debug_denoise. */
 int rt_debug_denoise_channels(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* var_rgb, const RtDenoise* dn,
                               float* out_rgb_f32);
+/* Test hook for rt_accum_denoise_multiscale (rtow_mi355x.h "multi-scale denoising"): the same kernels over host arrays in image order, as
+ * the two hooks above take them.  guide RT_DENOISE_GUIDE_LUMINANCE: rgb [3 * nx * rows] = c, mean and var [nx * rows] = y and v;
+ * RT_DENOISE_GUIDE_CHANNELS: `mean` is not read (may be NULL) and var [3 * nx * rows] holds the three channel variances.  out_rgb_f32
+ * [3 * nx * rows] = o_0.  The probe arrays that are not NULL receive the filter's INPUTS of level probe_level < levels, sized by
+ * rt_denoise_level_size: probe_rgb [3 * n] = c, probe_mean and probe_var [n] = y and v, or with the channels guide probe_mean = c again
+ * and probe_var [3 * n] — so that a wrong downsample shows apart from a wrong combine.  RT_ERR_INVALID: a NULL array, nx * rows outside
+ * 1 .. 2^28, parameters rt_accum_denoise_multiscale would refuse, a probe array with probe_level >= levels. */
+int rt_debug_denoise_multiscale(RtCtx* ctx, uint32_t nx, uint32_t rows, uint32_t guide, const float* rgb, const float* mean, const float* var,
+                                const RtDenoise* dn, uint32_t levels, float* out_rgb_f32, uint32_t probe_level, float* probe_rgb,
+                                float* probe_mean, float* probe_var);
 
 /* Test hook for adaptive sampling (rtow_mi355x.h "adaptive sampling"): overwrites the two luminance moments (S1, S2) of pixel `pixel` of
  * the open accumulation, `pixel` an index into out_sem (row order of out_rgb_f32).  The tests plant a NaN with it: such a pixel never

@@ -157,6 +157,16 @@ DENOISE_DEFAULT_STRENGTH = 1.0  # RT_DENOISE_DEFAULT_STRENGTH
 DENOISE_HALVES_DEFAULT_STRENGTH = 0.7  # RT_DENOISE_HALVES_DEFAULT_STRENGTH
 
 
+DENOISE_MAX_LEVELS, DENOISE_DEFAULT_LEVELS = 4, 2  # RT_DENOISE_MAX_LEVELS, RT_DENOISE_DEFAULT_LEVELS
+DENOISE_GUIDE_LUMINANCE, DENOISE_GUIDE_CHANNELS = 0, 1  # RT_DENOISE_GUIDE_*
+
+
+class RtMultiscale(C.Structure):
+    """rt_accum_denoise_multiscale: the levels of the 2x pyramid (1..MAX) and which filter runs on them (rtow_mi355x.h "multi-scale
+    denoising")."""
+    _fields_ = [("levels", C.c_uint32), ("guide", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class RtResidual(C.Structure):
     """rt_accum_denoise_halves: the frame figures of the cross-filtered frame (rtow_mi355x.h "half buffers"); residual_rms is the variance
     half of the filtered frame's error, a lower bound."""
@@ -246,6 +256,7 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_accum_begin", "rt_accum_add", "rt_accum_read", "rt_accum_end", "rt_render_to_noise",
                "rt_accum_denoise", "rt_debug_denoise",
                "rt_accum_track_channels", "rt_accum_read_channel_sem", "rt_accum_denoise_channels", "rt_debug_denoise_channels",
+               "rt_denoise_level_size", "rt_accum_denoise_multiscale", "rt_debug_denoise_multiscale",
                "rt_accum_add_adaptive", "rt_accum_read_counts", "rt_render_adaptive", "rt_adaptive_check", "rt_adaptive_converged",
                "rt_debug_accum_set_moments",
                "rt_accum_frame_id", "rt_accum_state_check", "rt_accum_export", "rt_accum_import", "rt_accum_merge",
@@ -354,6 +365,12 @@ def load_gpu_library():
     lib.rt_accum_denoise_channels.restype = C.c_int
     lib.rt_debug_denoise_channels.argtypes = [vp, C.c_uint32, C.c_uint32, _f, _f, C.POINTER(RtDenoise), _f]
     lib.rt_debug_denoise_channels.restype = C.c_int
+    lib.rt_denoise_level_size.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, _u32, _u32]
+    lib.rt_denoise_level_size.restype = C.c_int
+    lib.rt_accum_denoise_multiscale.argtypes = [vp, C.POINTER(RtDenoise), C.POINTER(RtMultiscale), _f, _u8]
+    lib.rt_accum_denoise_multiscale.restype = C.c_int
+    lib.rt_debug_denoise_multiscale.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, _f, _f, _f, C.POINTER(RtDenoise), C.c_uint32, _f, C.c_uint32, _f, _f, _f]
+    lib.rt_debug_denoise_multiscale.restype = C.c_int
     lib.rt_accum_add_adaptive.argtypes = [vp, C.c_uint32, C.POINTER(RtAdaptive), C.POINTER(RtStats)]
     lib.rt_accum_add_adaptive.restype = C.c_int
     lib.rt_accum_read_counts.argtypes = [vp, _u32, C.POINTER(RtAdaptiveInfo)]

@@ -558,6 +558,15 @@ def adaptive_converged(ad, s1, s2, n):
     return rc == 1
 
 
+def denoise_level_size(nx, rows, level):
+    """rt_denoise_level_size (no GPU): (nx_l, rows_l) of level `level` of the pyramid accum_denoise_multiscale filters."""
+    nx_l, rows_l = C.c_uint32(), C.c_uint32()
+    rc = _ffi.load_gpu_library().rt_denoise_level_size(int(nx), int(rows), int(level), C.byref(nx_l), C.byref(rows_l))
+    if rc < 0:
+        raise RtError(f"rt_denoise_level_size failed ({rc}): nx or rows 0, or a level outside 0 .. RT_DENOISE_MAX_LEVELS - 1")
+    return nx_l.value, rows_l.value
+
+
 def accum_frame_id(camera, params):
     """rt_accum_frame_id (no GPU): the 64-bit identity of the frame a camera and an RtParams describe — what an AccumState carries so that
     it is only imported into, or merged with, an accumulation of the same samples.  The scene and the sets are not part of it."""
@@ -830,6 +839,41 @@ class Renderer:
         fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
         self._call("rt_debug_denoise_channels", nx, rows, fp(rgb), fp(var_rgb), self._denoise_ptr(radius, patch, strength), fp(out))
         return out
+
+    _GUIDES = {"luminance": _ffi.DENOISE_GUIDE_LUMINANCE, "channels": _ffi.DENOISE_GUIDE_CHANNELS}
+
+    def accum_denoise_multiscale(self, levels=None, guide="luminance", radius=5, patch=1, strength=None, want_rgb8=False):
+        """rt_accum_denoise_multiscale: accum_denoise (guide "luminance") or accum_denoise_channels (guide "channels") on a 2x pyramid of
+        `levels` levels (1 .. DENOISE_MAX_LEVELS; None: RT_DENOISE_DEFAULT_LEVELS), each coarser level replacing the low frequencies of
+        the finer one; levels=1 is the single-scale filter bit for bit.  Returns (img [rows, nx, 3] f32, rgb8 or None)."""
+        ms = _ffi.RtMultiscale(_ffi.DENOISE_DEFAULT_LEVELS if levels is None else int(levels), self._GUIDES[guide] if isinstance(guide, str) else int(guide))
+        img, rgb8, _, ptrs = self._accum_outputs(want_rgb8, False)
+        self._call("rt_accum_denoise_multiscale", self._denoise_ptr(radius, patch, strength), C.byref(ms), ptrs[0], ptrs[1])
+        return img, rgb8
+
+    def debug_denoise_multiscale(self, rgb, mean, var, levels, guide="luminance", radius=5, patch=1, strength=None, probe_level=None):
+        """rt_debug_denoise_multiscale: the kernels of accum_denoise_multiscale over host arrays in image order.  guide "luminance": rgb
+        [rows, nx, 3], mean and var [rows, nx] as debug_denoise takes them; guide "channels": rgb and var [rows, nx, 3] as
+        debug_denoise_channels takes them, `mean` is not read (None).  Returns the filtered [rows, nx, 3] f32 image, or with probe_level
+        (img, (c, mean, var)): the filter's inputs of that level, shaped as the arguments are at the level's size."""
+        g = self._GUIDES[guide] if isinstance(guide, str) else int(guide)
+        channels = g == _ffi.DENOISE_GUIDE_CHANNELS
+        rgb, var = np.ascontiguousarray(rgb, dtype=np.float32), np.ascontiguousarray(var, dtype=np.float32)
+        rows, nx, _ = rgb.shape
+        assert var.shape == ((rows, nx, 3) if channels else (rows, nx))
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None
+        if not channels:
+            mean = np.ascontiguousarray(mean, dtype=np.float32)
+            assert mean.shape == (rows, nx)
+        out = np.zeros_like(rgb)
+        probes = [None, None, None]
+        if probe_level is not None:
+            nx_l, rows_l = denoise_level_size(nx, rows, probe_level)
+            tail = (3,) if channels else ()
+            probes = [np.zeros((rows_l, nx_l, 3), np.float32), np.zeros((rows_l, nx_l) + tail, np.float32), np.zeros((rows_l, nx_l) + tail, np.float32)]
+        self._call("rt_debug_denoise_multiscale", nx, rows, g, fp(rgb), None if channels else fp(mean), fp(var), self._denoise_ptr(radius, patch, strength),
+                   int(levels), fp(out), int(probe_level or 0), *[fp(a) for a in probes])
+        return out if probe_level is None else (out, tuple(probes))
 
     def accum_export(self):
         """rt_accum_export: the open accumulation as an AccumState — every plane it holds; on a uniform accumulation counts and converged

@@ -5,6 +5,8 @@
 #include "rt_kernels.h"
 #include "rt_denoise.h"
 #include "rt_channels.h"
+#include "rt_multiscale.h"
+#include "rt_multiscale_plan.h"
 #include "rt_adaptive.h"
 #include "rt_accum_state.h"
 #include "rt_accum_state_kernels.h"
@@ -163,6 +165,7 @@ struct RtCtx {
     // (rt_accum_planes.h: planes_place), at most 192 B per pixel; rt_accum_read_halves borrows it for its two outputs
     DevBuf accum_stage;
     DevBuf dn_c, dn_yv, dn_out;  // rt_accum_denoise: the filter's inputs (c 12 B, (y, v) 8 B) and its output (12 B) per pixel, in image order
+    DevBuf dn_ms;                // rt_accum_denoise_multiscale: the regions of every level of the pyramid (rt_multiscale_plan.h: multiscale_plan)
     // Host-side timeline of the last trace_samples and what its caller enqueued behind it (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
     // render of a process is where allocations, code-object loads and the queue probe happen; this says which.
     std::vector<std::pair<const char*, double>> parts;
@@ -760,7 +763,7 @@ void rt_ctx_destroy(RtCtx* ctx) {
     if (ctx->h_resid) (void)hipHostFree(ctx->h_resid);
     if (ctx->h_robust) (void)hipHostFree(ctx->h_robust);
     if (ctx->h_info) (void)hipHostFree(ctx->h_info);
-    free_buf(ctx->dn_c), free_buf(ctx->dn_yv), free_buf(ctx->dn_out);
+    free_buf(ctx->dn_c), free_buf(ctx->dn_yv), free_buf(ctx->dn_out), free_buf(ctx->dn_ms);
     if (ctx->h_noise) (void)hipHostFree(ctx->h_noise);
     free_buf(ctx->motion_region), free_buf(ctx->quads_region), free_buf(ctx->lights_buf);
     for (auto ev : ctx->events) (void)hipEventDestroy(ev);
@@ -1828,6 +1831,121 @@ int rt_accum_denoise_channels(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f3
 
 int rt_debug_denoise_channels(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* var_rgb, const RtDenoise* dn, float* out_rgb_f32) {
     return debug_nlm(ctx, "rt_debug_denoise_channels", 3u, nx, rows, rgb, rgb, var_rgb, dn, out_rgb_f32);
+}
+
+// ---- multi-scale denoising (rtow_mi355x.h "Multi-scale denoising", csrc/rt_multiscale.h, csrc/rt_multiscale_plan.h) ----------------------
+int rt_denoise_level_size(uint32_t nx, uint32_t rows, uint32_t level, uint32_t* nx_l, uint32_t* rows_l) {
+    if (nx == 0u || rows == 0u || level >= RT_DENOISE_MAX_LEVELS) return RT_ERR_INVALID;
+    for (uint32_t s = 0; s < level; ++s) nx = multiscale_half(nx), rows = multiscale_half(rows);
+    if (nx_l) *nx_l = nx;
+    if (rows_l) *rows_l = rows;
+    return RT_OK;
+}
+// The regions of a plan in ctx->dn_ms (ensured by the caller) as pointers
+struct MultiscaleRegions {
+    char* base;
+    const MultiscalePlan& pl;
+    float* c(uint32_t s) const { return pl.planes == 1u ? (float*)(base + pl.lv[s].c) : nullptr; }
+    float2* guide(uint32_t s) const { return (float2*)(base + pl.lv[s].guide); }
+    float* f(uint32_t s) const { return (float*)(base + pl.lv[s].f); }
+    float* e(uint32_t s) const { return (float*)(base + pl.lv[s].e); }
+    float* o(uint32_t s) const { return (float*)(base + pl.lv[s].o); }
+};
+// Everything behind the inputs of level 0, which the caller has enqueued into c(0) and guide(0) on `st`: the inputs of the coarser levels,
+// the filter on every level, and the combination from coarse to fine.  The result is o(0).
+static void enqueue_multiscale(hipStream_t st, const MultiscaleRegions& m, const RtDenoise& d) {
+    const MultiscalePlan& pl = m.pl;
+    const auto blocks = [](uint64_t npix) { return dim3((uint32_t)((npix + 255u) / 256u)); };
+    for (uint32_t s = 0; s < pl.levels; ++s) {
+        const MultiscaleLevel& l = pl.lv[s];
+        if (s) {
+            const MultiscaleLevel& fine = pl.lv[s - 1u];
+            if (pl.planes == 1u)
+                hipLaunchKernelGGL(k_ms_down<1>, blocks(l.npix), dim3(256), 0, st, m.c(s - 1u), m.guide(s - 1u), m.c(s), m.guide(s), fine.nx, fine.rows, l.nx, l.rows);
+            else
+                hipLaunchKernelGGL(k_ms_down<3>, blocks(l.npix), dim3(256), 0, st, (const float*)nullptr, m.guide(s - 1u), (float*)nullptr, m.guide(s), fine.nx, fine.rows,
+                                   l.nx, l.rows);
+        }
+        launch_nlm(st, pl.planes, m.c(s), m.guide(s), m.f(s), l.nx, l.rows, d);
+    }
+    for (uint32_t s = pl.levels - 1u; s-- > 0u;) {
+        const MultiscaleLevel &l = pl.lv[s], &coarse = pl.lv[s + 1u];
+        hipLaunchKernelGGL(k_ms_residual, blocks(coarse.npix), dim3(256), 0, st, m.o(s + 1u), m.f(s), m.e(s + 1u), l.nx, l.rows, coarse.nx, coarse.rows);
+        hipLaunchKernelGGL(k_ms_up_add, blocks(l.npix), dim3(256), 0, st, m.f(s), m.e(s + 1u), m.o(s), l.nx, l.rows, coarse.nx, coarse.rows);
+    }
+}
+
+int rt_accum_denoise_multiscale(RtCtx* ctx, const RtDenoise* dn, const RtMultiscale* ms, float* out_rgb_f32, uint8_t* out_rgb8) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtMultiscale m = ms ? *ms : RtMultiscale{RT_DENOISE_DEFAULT_LEVELS, RT_DENOISE_GUIDE_LUMINANCE, {0u, 0u}};
+    const bool channels = m.guide == RT_DENOISE_GUIDE_CHANNELS;
+    const DenoiseCall call{"rt_accum_denoise_multiscale", RT_DENOISE_DEFAULT_STRENGTH,
+                           channels && !ctx->accum.channels ? "the accumulation does not track channels (rt_accum_track_channels)" : nullptr, 2u,
+                           "there is no variance yet"};
+    const auto more = [&]() -> int {
+        const char* why = multiscale_invalid(&m);
+        return why ? fail(ctx, RT_ERR_INVALID, std::string(call.who) + ": " + why) : RT_OK;
+    };
+    return denoise_run(ctx, call, dn, out_rgb_f32, out_rgb8, more, [&](const AccumReader& r, const RtDenoise& d, const float*& img) -> int {
+        const MultiscalePlan pl = multiscale_plan(r.nx, r.rows, m.levels, channels ? 3u : 1u);
+        if (const int rc = ensure(ctx, ctx->dn_ms, pl.total)) return rc;
+        const MultiscaleRegions reg{ctx->dn_ms.as<char>(), pl};
+        if (channels)
+            ACCUM_READER(k_denoise_inputs_channels, r, ctx->accum_sum.as<const float>(), ctx->accum_chm.as<const double2>(), r.cnt, reg.guide(0u), r.nx, r.rows, r.n,
+                         r.tiles_per_row, r.tile_pixels);
+        else
+            ACCUM_READER(k_denoise_inputs, r, ctx->accum_sum.as<const float>(), ctx->accum_mom.as<const double2>(), r.cnt, reg.c(0u), reg.guide(0u), r.nx, r.rows, r.n,
+                         r.tiles_per_row, r.tile_pixels);
+        enqueue_multiscale(r.st, reg, d);
+        img = reg.o(0u);
+        return RT_OK;
+    });
+}
+
+// debug_nlm's pattern with the pyramid behind the upload, and the inputs of one level read back where asked
+int rt_debug_denoise_multiscale(RtCtx* ctx, uint32_t nx, uint32_t rows, uint32_t guide, const float* rgb, const float* mean, const float* var, const RtDenoise* dn,
+                                uint32_t levels, float* out_rgb_f32, uint32_t probe_level, float* probe_rgb, float* probe_mean, float* probe_var) {
+    if (!ctx) return RT_ERR_INVALID;
+    const std::string who = "rt_debug_denoise_multiscale";
+    const RtMultiscale m{levels, guide, {0u, 0u}};
+    if (const char* why = multiscale_invalid(&m)) return fail(ctx, RT_ERR_INVALID, who + ": " + why);
+    const bool channels = guide == RT_DENOISE_GUIDE_CHANNELS;
+    if (!rgb || (!channels && !mean) || !var || !out_rgb_f32) return fail(ctx, RT_ERR_INVALID, who + ": NULL array");
+    if (nx == 0u || rows == 0u || (uint64_t)nx * rows > (1ull << 28)) return fail(ctx, RT_ERR_INVALID, who + ": nx * rows must be 1 .. 2^28");
+    const bool probe = probe_rgb || probe_mean || probe_var;
+    if (probe && probe_level >= levels) return fail(ctx, RT_ERR_INVALID, who + ": probe_level must be below levels");
+    RtDenoise d;
+    int rc = denoise_params(ctx, dn, d, who.c_str());
+    if (rc) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t planes = channels ? 3u : 1u;
+    const MultiscalePlan pl = multiscale_plan(nx, rows, levels, planes);
+    if ((rc = ensure(ctx, ctx->dn_ms, pl.total))) return rc;
+    const MultiscaleRegions reg{ctx->dn_ms.as<char>(), pl};
+    const size_t npix = (size_t)nx * rows;
+    const float* const gmean = channels ? rgb : mean;
+    std::vector<float2> g(planes * npix);
+    for (size_t k = 0; k < g.size(); ++k) g[k] = make_float2(gmean[k], var[k]);
+    const hipStream_t st = ctx->stream;
+    if (!channels) RT_HIP(ctx, hipMemcpyAsync(reg.c(0u), rgb, npix * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    RT_HIP(ctx, hipMemcpyAsync(reg.guide(0u), g.data(), g.size() * sizeof(float2), hipMemcpyHostToDevice, st));
+    enqueue_multiscale(st, reg, d);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, reg.o(0u), npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    std::vector<float2> pg;
+    const size_t pn = probe ? (size_t)pl.lv[probe_level].npix : 0u;
+    if (probe) {
+        pg.resize(planes * pn);
+        RT_HIP(ctx, hipMemcpyAsync(pg.data(), reg.guide(probe_level), pg.size() * sizeof(float2), hipMemcpyDeviceToHost, st));
+        if (probe_rgb && !channels) RT_HIP(ctx, hipMemcpyAsync(probe_rgb, reg.c(probe_level), pn * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    for (size_t k = 0; k < pg.size(); ++k) {
+        if (probe_rgb && channels) probe_rgb[k] = pg[k].x;
+        if (probe_mean) probe_mean[k] = pg[k].x;
+        if (probe_var) probe_var[k] = pg[k].y;
+    }
+    return RT_OK;
 }
 
 // ---- accumulation state (rtow_mi355x.h "Accumulation state", csrc/rt_accum_state.h, csrc/rt_accum_state_kernels.h) -------------------------

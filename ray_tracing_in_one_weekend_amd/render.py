@@ -68,6 +68,10 @@ def main(argv=None):
                          "theirs (rt_accum_denoise_channels: 48 B per pixel more, keeps edges between colours of equal luminance), or, per half "
                          "of the samples, the luminance of the OTHER half (rt_accum_denoise_halves: 56 B per pixel more, default strength %g, "
                          "reports the variance left in the filtered frame)" % _ffi.DENOISE_HALVES_DEFAULT_STRENGTH)
+    ap.add_argument("--denoise-levels", type=int, default=None, metavar="L",
+                    help="with --denoise and --denoise-guide luminance or channels: filter a 2x pyramid of L levels, 1..%d, each coarser level "
+                         "replacing the low frequencies of the finer one (rt_accum_denoise_multiscale); 1 is the single-scale filter"
+                         % _ffi.DENOISE_MAX_LEVELS)
     ap.add_argument("--residual-target", type=float, default=None, metavar="X",
                     help="render until the DENOISED frame is clean: samples in steps of --spp-step, the cross filter of --denoise-guide halves "
                          "after each, until its residual_noise <= X or --spp are done.  The figure is the variance half of the filtered "
@@ -124,6 +128,13 @@ def main(argv=None):
         rend.set_lights(scene.lights)  # (a moving scene refuses it: RT_ERR_UNSUPPORTED)
     flags = _ffi.FLAG_RUSSIAN_ROULETTE if a.russian_roulette else 0
     halves = a.residual_target is not None or (a.denoise and a.denoise_guide == "halves")
+    if a.denoise_levels is not None:
+        if not a.denoise or a.denoise_guide == "halves" or a.residual_target is not None:
+            ap.error("--denoise-levels needs --denoise with --denoise-guide luminance or channels")
+        if not 1 <= a.denoise_levels <= _ffi.DENOISE_MAX_LEVELS:
+            ap.error("--denoise-levels takes 1..%d" % _ffi.DENOISE_MAX_LEVELS)
+        if a.robust is not None:
+            ap.error("--denoise-levels does not combine with --robust")
     a.robust_mode = None
     if a.robust is not None:
         kind, _, n = a.robust.partition(":")
@@ -322,6 +333,8 @@ def render_with_state(a, rend, scene, flags, file_name, t0):
 def _denoised(a, rend):
     if a.robust_mode:
         return rend.accum_denoise_robust(*a.robust_mode, a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
+    if a.denoise_levels is not None:
+        return rend.accum_denoise_multiscale(a.denoise_levels, a.denoise_guide, a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
     if a.denoise_guide == "channels":
         return rend.accum_denoise_channels(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
     return rend.accum_denoise(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
