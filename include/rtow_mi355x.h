@@ -460,7 +460,8 @@ int rt_set_lights(RtCtx* ctx, const RtLights* lights);
  * Cost: 28 B per pixel that the accumulation owns (an f32 x 3 sum, an f64 x 2 moment), apart from the frame renderer's buffers —
  * rt_render and rt_render_device may be called in between and neither disturbs the other.  The first rt_accum_denoise of a context adds
  * 20 B + 12 B per pixel (the filter's inputs c, y, v in image order and its output), kept for the next like the accumulation's buffers.
- * Not covered: rt_multi_* (the noise of a frame split over devices needs a reduction across them); the rt_set_progress callback (a
+ * Across devices: rt_multi_accum_* (the noise of a frame split over devices needs the frame in one piece: the joined context of
+ * rt_multi_accum_join delivers it).  Not covered: rt_render_to_noise over an RtMulti (the caller loops add / join / read); the rt_set_progress callback (a
  * host that accumulates has its preview in rt_accum_read).  rt_accum_add gives every pixel the same number of samples; "Adaptive
  * sampling" below gives them to the pixels that still need them. */
 typedef struct RtNoise {
@@ -527,7 +528,8 @@ int rt_render_to_noise(RtCtx* ctx, const RtCamera* cam, const RtParams* params, 
  * is sum / (float)max(n_p, 1) as rt_accum_read writes it, its y and v are NaN, so it stays what it is and spreads to no other pixel.
  * Depth 0 of an adaptive add runs on the materialised ray queue (the fused depth-0 kernels and the candidate lists invert a queue position
  * into a pixel, which a compacted queue does not allow): per traced sample it costs what RT_OPT_MATERIALISE_PRIMARIES costs (DESIGN.md
- * "Adaptive sampling").  Not covered: rt_multi_*; un-sticking a pixel; per-channel criteria. */
+ * "Adaptive sampling").  Across devices: rt_multi_accum_add_adaptive (the decision is per pixel, so shards need no exchange).  Not covered:
+ * rt_render_adaptive over an RtMulti; un-sticking a pixel; per-channel criteria. */
 typedef struct RtAdaptive {
     double tolerance;        /* finite, >= 0: relative standard error of the mean luminance at which a pixel stops */
     double luminance_floor;  /* finite, > 0: the mean luminance below which the error is measured against this floor */
@@ -588,7 +590,7 @@ int rt_adaptive_converged(const RtAdaptive* ad, double s1, double s2, uint32_t n
  * equal luminance blur; "Channel moments and the colour-guided filter" below keeps a variance per channel (48 B per pixel more, opt-in)
  * and filters on it; the weights are chosen from the
  * image they filter — "Half buffers" below keeps the even and the odd samples apart (56 B per pixel more, opt-in), filters each half with
- * the other's weights and reports the variance that is left; rt_multi_* is not supported.
+ * the other's weights and reports the variance that is left; on an RtMulti the filter runs on the joined context (rt_multi_accum_join), not on a shard.
  * DESIGN.md "Denoising". */
 typedef struct RtDenoise { uint32_t radius, patch; float strength; uint32_t reserved; } RtDenoise;
 #define RT_DENOISE_MAX_RADIUS 10u
@@ -622,7 +624,8 @@ int rt_accum_denoise(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f32, uint8_
  *     D = S / cnt3,  cnt3 = (float)(3*(2F+1)*(2F+1)).
  * The clamp per axis, the weight with its NaN rules, "accumulate only where u != 0", out = num / den, out = c_p where den == 0 and the
  * visiting order of delta are those of "Denoising"; a non-finite pixel spreads to no other, for the same reason.
- * Not covered: rt_multi_*; sharded frames for the filter (RT_ERR_UNSUPPORTED, as rt_accum_denoise); a per-channel adaptive criterion
+ * Across devices: RT_MULTI_TRACK_CHANNELS and the joined context of rt_multi_accum_join.  Not covered: sharded frames for the filter
+ * (RT_ERR_UNSUPPORTED, as rt_accum_denoise); a per-channel adaptive criterion
  * (rt_accum_add_adaptive decides on luminance); rt_render_to_noise and rt_render_adaptive, which open and end their own accumulation — a
  * host that wants the filter drives the adds itself.  DESIGN.md "Channel moments and the colour-guided filter". */
 /* Makes the open accumulation track channels and clears the channel moments.  After rt_accum_begin and before the first add, uniform or
@@ -656,7 +659,8 @@ int rt_accum_denoise_channels(RtCtx* ctx, const RtDenoise* dn, float* out_rgb_f3
  * channel moments likewise.  The merged image is therefore NOT rt_render(spp = n1 + n2) in every bit — an f32 sum of n1 + n2 terms was cut
  * in two: ((x0 + .. + x_{n1-1}) + (x_{n1} + .. + x_{n1+n2-1})) — it is the arithmetic above exactly; per channel of non-negative radiance
  * the two differ by at most (2 n + 2) 2^-24 of the larger, n = n1 + n2.  Moments, out_sem and the figures follow from the merged sums.
- * Failed calls leave the accumulation as it was.  A shard without pixels: RT_OK.  Not covered: rt_multi_*; planes in device memory.
+ * Failed calls leave the accumulation as it was.  A shard without pixels: RT_OK.  Across devices: rt_multi_accum_import splits a whole-frame
+ * state over the shards and the joined context exports one; rt_accum_merge stays a single-context call.  Not covered: planes in device memory.
  * DESIGN.md "Accumulation state". */
 #define RT_ACCUM_STATE_COUNTS   1u  /* adaptive: counts and converged are part of the state */
 #define RT_ACCUM_STATE_CHANNELS 2u  /* channel moments are part of the state */
@@ -745,7 +749,8 @@ int rt_accum_merge(RtCtx* ctx, const RtAccumState* st);
  * RT_ERR_UNSUPPORTED and change nothing (the halves would no longer belong to the sums; a merge of halves is not covered).
  * Tracking can only be turned on while the accumulation holds no sample or — through rt_accum_import_halves — together with the halves
  * that belong to its samples, so a tracking accumulation's halves are always those of its samples.
- * Not covered: the colour-guided cross filter (channel moments per half); a merge of halves; rt_multi_*; sharded frames for the filter
+ * Across devices: RT_MULTI_TRACK_HALVES and the joined context of rt_multi_accum_join.  Not covered: the colour-guided cross filter (channel
+ * moments per half); a merge of halves; sharded frames for the filter
  * (RT_ERR_UNSUPPORTED, as rt_accum_denoise; the half images read on shards).  DESIGN.md "Half buffers". */
 #define RT_DENOISE_HALVES_DEFAULT_STRENGTH 0.7f /* of 0.45, 0.7 and 1.0 by the rule of RT_DENOISE_DEFAULT_STRENGTH (DESIGN.md "Half buffers") */
 typedef struct RtResidual {
@@ -839,7 +844,8 @@ int rt_accum_import_halves(RtCtx* ctx, const RtAccumHalves* hs);
  * the uninterrupted accumulation returns.  rt_accum_import and rt_accum_merge on an accumulation that already tracks buckets are
  * RT_ERR_UNSUPPORTED and change nothing.  Tracking can only be turned on while the accumulation holds no sample or — through
  * rt_accum_import_buckets — together with the buckets that belong to its samples.
- * Not covered: a merge of buckets; rt_multi_*; rt_render_to_noise and rt_render_adaptive, which open their own accumulation; a robust form
+ * Across devices: RT_MULTI_TRACK_BUCKETS and the joined context of rt_multi_accum_join.  Not covered: a merge of buckets; rt_render_to_noise
+ * and rt_render_adaptive, which open their own accumulation; a robust form
  * of the channel-guided and the cross filter; an adaptive criterion on the robust estimate; sharded frames for the filter
  * (RT_ERR_UNSUPPORTED, as rt_accum_denoise; the read-out works on shards).  DESIGN.md "Sample buckets". */
 #define RT_BUCKETS_MAX 16u
@@ -926,7 +932,7 @@ int rt_accum_import_buckets(RtCtx* ctx, const RtAccumBuckets* bs);
  *   The accumulation is read and not changed.
  * Cost: the levels above 0 take about a third of level 0 in time and memory (DESIGN.md "Multi-scale denoising").
  * Not covered: the cross-filtered halves of "Half buffers" and the robust read-out of "Sample buckets" (both stay single-scale); sharded
- * frames (RT_ERR_UNSUPPORTED, as rt_accum_denoise); rt_multi_*. */
+ * frames (RT_ERR_UNSUPPORTED, as rt_accum_denoise: on an RtMulti the filter runs on the joined context of rt_multi_accum_join). */
 typedef struct RtMultiscale {
     uint32_t levels, guide; /* 1 .. RT_DENOISE_MAX_LEVELS; RT_DENOISE_GUIDE_* */
     uint32_t reserved[2];   /* 0 */
@@ -974,6 +980,62 @@ int rt_multi_scene_upload(RtMulti* m, const RtFlatScene* scene);
  * either may be NULL.  `stats` sums the counters of the devices and takes the maximum of their times. */
 int rt_multi_render(RtMulti* m, const RtCamera* cam, const RtParams* params, float* out_rgb_f32, uint8_t* out_rgb8,
                     RtStats* stats);
+
+/* -- progressive accumulation across devices ------------------------------------------------------------------------
+ * The accumulation line ("Progressive accumulation" .. "Multi-scale denoising") on the devices of an RtMulti.  Device i holds an ordinary
+ * accumulation over shard (band, n, i) of the frame; an add is the same rt_accum_add / rt_accum_add_adaptive on every device, one host
+ * thread each, so the shards stay in lock-step with one `done` for all.  The adaptive decision is per pixel, so — unlike the sample
+ * windows of rt_accum_merge — row-interleaved shards combine with adaptive sampling.  A shard's rows are not neighbours in the image, so
+ * no filter runs on one and its frame figures are not the frame's: rt_multi_accum_join is the spatial join.  It brings every plane of
+ * every shard to the first device, device to device (the two gather mechanisms of rt_multi_render; no host staging), and installs them in
+ * a whole-frame accumulation there, on which every reading call of this header runs unchanged.
+ *
+ * The joined context.  rt_multi_accum_join hands out an RtCtx that the RtMulti owns: created by the first rt_multi_accum_begin (users of
+ * rt_multi_render pay nothing), the same pointer for the life of `m`, destroyed by rt_multi_destroy — never by the caller.  It holds the
+ * accumulation of the frame with shard_count 1, the same camera, first_sample and done, adaptive / channels / halves / buckets as the
+ * shards have them, in the local pixel order that one context with this scene and default options picks, so that every read-out is what
+ * ONE context returns after the same adds, bit for bit: rt_accum_read, _read_counts, _read_channel_sem, _denoise, _denoise_channels,
+ * _denoise_halves, _denoise_robust, _denoise_multiscale, _read_halves, _read_robust, _export, _export_halves, _export_buckets.  It is a
+ * MIRROR: rt_accum_begin, _add, _add_adaptive, _import, _import_halves, _import_buckets, _merge, _track_channels, _track_halves,
+ * _track_buckets and _end on it are RT_ERR_STATE and change nothing (so are rt_render_to_noise and rt_render_adaptive, which begin an
+ * accumulation).  It has no scene and no work buffers.  A join may follow every add; each rewrites every pixel, since every pixel
+ * belongs to exactly one shard.  Between rt_multi_accum_begin (or _end) and the next join it holds no accumulation: reading calls are
+ * RT_ERR_STATE.
+ *
+ * Errors.  Arguments are checked before any device is touched where this header says so; otherwise an invalid argument or a call out of
+ * order is refused by every device alike, the code and text are the first device's and nothing has changed.  A device-side failure
+ * (RT_ERR_NOMEM, RT_ERR_DEVICE) on any device ENDS the accumulation on all of them — the shards no longer belong together —, every later
+ * call but rt_multi_accum_begin and rt_multi_accum_end is RT_ERR_STATE, and rt_multi_last_error names the device.  rt_multi_render may
+ * run between two adds; rt_multi_scene_upload and rt_multi_set_* end the accumulation as their single-context forms do.
+ * RCCL: as rt_multi_create says, every step over RCCL with n > 1 — here the one group of byte-counted ncclSend / ncclRecv of the join —
+ * is UNVERIFIED ON HARDWARE; RT_MULTI_COPY_GATHER runs everything else for n = 2, 3 on one GPU.
+ * Not covered: a sample-window split inside rt_multi_*; driver loops (the caller loops add / join / read); rt_debug_set_option on the
+ * contexts of an RtMulti; denoising without a join (a halo exchange between shards).  DESIGN.md "Accumulation across devices". */
+#define RT_MULTI_TRACK_CHANNELS 1u /* rt_accum_track_channels on every shard */
+#define RT_MULTI_TRACK_HALVES   2u /* rt_accum_track_halves */
+#define RT_MULTI_TRACK_BUCKETS  4u /* rt_accum_track_buckets(M) */
+/* rt_accum_begin on every device: device i on shard (band, n, i) of the frame of `params` — band = shard_band, 0 = 8; shard_count and
+ * shard_id are ignored, as in rt_multi_render —, then the tracking that `track` names.  RT_ERR_INVALID before any device is touched: cam or
+ * params NULL, a bit in `track` that is no RT_MULTI_TRACK_*, M outside 3 .. RT_BUCKETS_MAX with RT_MULTI_TRACK_BUCKETS (M is not looked
+ * at without it).  Everything else as rt_accum_begin refuses it.  A failure leaves no accumulation open anywhere.  An open one is replaced. */
+int rt_multi_accum_begin(RtMulti* m, const RtCamera* cam, const RtParams* params, uint32_t first_sample, uint32_t track, uint32_t M);
+/* rt_accum_add / rt_accum_add_adaptive on every device.  `stats` (may be NULL) sums the devices' as rt_multi_render does.  Complete on return. */
+int rt_multi_accum_add(RtMulti* m, uint32_t n_samples, RtStats* stats);
+int rt_multi_accum_add_adaptive(RtMulti* m, uint32_t n_samples, const RtAdaptive* ad, RtStats* stats);
+/* Joins the shards into the joined context (above) and stores it in *joined (also on failure, once it exists).  Complete on return.
+ * RT_ERR_STATE: no accumulation begun, or a context of `m` was ended or changed behind its back. */
+int rt_multi_accum_join(RtMulti* m, RtCtx** joined);
+/* The resume of a multi-device render: a WHOLE-FRAME snapshot — what the joined context, or one context over the frame, exported — is
+ * split on the host by rows into the n shard snapshots (frame_id of each: rt_accum_frame_id with that shard's params) and each is imported
+ * on its device with rt_accum_import [, _import_halves][, _import_buckets].  `st` required; `hs`, `bs` may be NULL.  Right after
+ * rt_multi_accum_begin, under the rules of those three calls (so: begun without halves and buckets tracking, which the import turns on).
+ * RT_ERR_INVALID before any device is touched: a snapshot that its _check refuses, or whose nx, rows (= ny), frame_id (of the frame with
+ * shard_count 1) or first_sample are not the frame's, or halves / buckets whose first_sample and done are not the state's.  A snapshot
+ * written on n devices resumes on any other number, and on one context through rt_accum_import. */
+int rt_multi_accum_import(RtMulti* m, const RtAccumState* st, const RtAccumHalves* hs, const RtAccumBuckets* bs);
+/* rt_accum_end on every device; the joined context holds no accumulation afterwards.  RT_OK also where none is open. */
+int rt_multi_accum_end(RtMulti* m);
+
 /* rt_set_lens on every device (all or none: the values are checked by the first). */
 int rt_multi_set_lens(RtMulti* m, const RtLens* lens);
 /* rt_set_motion on every device.  An invalid motion is refused by the first device and none has changed; a device-side failure

@@ -213,6 +213,7 @@ class RtBounceIO(C.Structure):
 RtProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32)
 
 MULTI_COPY_GATHER = 1  # RT_MULTI_COPY_GATHER (rt_multi_create_ex)
+MULTI_TRACK_CHANNELS, MULTI_TRACK_HALVES, MULTI_TRACK_BUCKETS = 1, 2, 4  # RT_MULTI_TRACK_* (rt_multi_accum_begin)
 # enum RtDebugOption (rt_debug_set_option): per context, every setting renders the same bits
 (OPT_TREE_PLACEMENT, OPT_PRIMARY_LISTS, OPT_PIXEL_ORDER, OPT_TEXEL_POOL, OPT_GRID, OPT_GRID_CELL, OPT_CHAINS,
  OPT_GENERAL_KERNELS, OPT_GENERAL_LDS, OPT_QUEUE_SHARDS, OPT_ISECT_WORKGROUPS, OPT_MATERIALISE_PRIMARIES, OPT_MEDIUM_SEARCH, OPT_POOL_CHUNK_DELAY_US) = range(14)
@@ -264,6 +265,7 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_accum_import_halves",
                "rt_accum_track_buckets", "rt_accum_read_robust", "rt_accum_denoise_robust", "rt_accum_buckets_check", "rt_accum_export_buckets",
                "rt_accum_import_buckets",
+               "rt_multi_accum_begin", "rt_multi_accum_add", "rt_multi_accum_add_adaptive", "rt_multi_accum_join", "rt_multi_accum_import", "rt_multi_accum_end",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
@@ -459,6 +461,18 @@ def load_gpu_library():
     lib.rt_multi_scene_upload.restype = C.c_int
     lib.rt_multi_render.argtypes = [vp, C.POINTER(RtCamera), C.POINTER(RtParams), _f, _u8, C.POINTER(RtStats)]
     lib.rt_multi_render.restype = C.c_int
+    lib.rt_multi_accum_begin.argtypes = [vp, C.POINTER(RtCamera), C.POINTER(RtParams), C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.rt_multi_accum_begin.restype = C.c_int
+    lib.rt_multi_accum_add.argtypes = [vp, C.c_uint32, C.POINTER(RtStats)]
+    lib.rt_multi_accum_add.restype = C.c_int
+    lib.rt_multi_accum_add_adaptive.argtypes = [vp, C.c_uint32, C.POINTER(RtAdaptive), C.POINTER(RtStats)]
+    lib.rt_multi_accum_add_adaptive.restype = C.c_int
+    lib.rt_multi_accum_join.argtypes = [vp, C.POINTER(vp)]
+    lib.rt_multi_accum_join.restype = C.c_int
+    lib.rt_multi_accum_import.argtypes = [vp, C.POINTER(RtAccumState), C.POINTER(RtAccumHalves), C.POINTER(RtAccumBuckets)]
+    lib.rt_multi_accum_import.restype = C.c_int
+    lib.rt_multi_accum_end.argtypes = [vp]
+    lib.rt_multi_accum_end.restype = C.c_int
     lib.rt_deinterleave_bands.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]
     lib.rt_deinterleave_bands.restype = C.c_int
     _gpu_lib = lib

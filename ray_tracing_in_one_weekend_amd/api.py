@@ -1169,9 +1169,17 @@ class Renderer:
         self._call("rt_deinterleave_bands", C.c_void_p(d_gathered), nx, ny, band, n_shards, C.c_void_p(d_out_f32) if d_out_f32 else None,
                    C.c_void_p(d_out_u8) if d_out_u8 else None, C.c_void_p(stream) if stream else None)
 
+    @classmethod
+    def _borrowed(cls, lib, ctx, device, accum_shape):
+        """A Renderer over a context somebody else owns (MultiRenderer.accum_join): close() leaves the context alone."""
+        r = cls.__new__(cls)
+        r._lib, r._ctx, r.device, r._owned, r._accum_shape = lib, C.c_void_p(ctx), device, False, accum_shape
+        return r
+
     def close(self):
         if self._ctx:
-            self._lib.rt_ctx_destroy(self._ctx)
+            if getattr(self, "_owned", True):
+                self._lib.rt_ctx_destroy(self._ctx)
             self._ctx = C.c_void_p()
         for ptr in [q for q, _ in getattr(self, "_pin", {}).values()] + getattr(self, "_pin_retired", []):
             if ptr:
@@ -1219,6 +1227,7 @@ class MultiRenderer:
         rc = self._lib.rt_multi_create_ex(ids, len(devices), _ffi.MULTI_COPY_GATHER if copy_gather else 0, C.byref(self._m))
         if rc != 0:
             raise RtError(f"rt_multi_create({list(devices)}) failed ({rc}): {self._lib.rt_multi_last_error(None).decode()}")
+        self._devices = list(devices)
 
     def _raise(self, what, rc):
         raise RtError(f"{what} failed ({rc}): {self._lib.rt_multi_last_error(self._m).decode()}")
@@ -1267,6 +1276,51 @@ class MultiRenderer:
         if rc != 0:
             self._raise("rt_multi_render", rc)
         return img, rgb8, st
+
+    def _call(self, what, *args):
+        rc = getattr(self._lib, what)(self._m, *args)
+        if rc != 0:
+            self._raise(what, rc)
+
+    def accum_begin(self, camera, params, first_sample=0, channels=False, halves=False, buckets=0):
+        """rt_multi_accum_begin: Renderer.accum_begin on every device, device i on shard i of the frame of `params` (shard_band rows per
+        band, 0 = 8), then the tracking asked for: channels, halves, buckets = M (0: none)."""
+        track = ((_ffi.MULTI_TRACK_CHANNELS if channels else 0) | (_ffi.MULTI_TRACK_HALVES if halves else 0) |
+                 (_ffi.MULTI_TRACK_BUCKETS if buckets else 0))
+        self._call("rt_multi_accum_begin", C.byref(camera), C.byref(params), int(first_sample), track, int(buckets))
+        self._accum_shape = (params.ny, params.nx)
+
+    def accum_add(self, n):
+        """rt_multi_accum_add: n more samples per pixel on every shard; returns the RtStats summed over the devices."""
+        stats = RtStats()
+        self._call("rt_multi_accum_add", int(n), C.byref(stats))
+        return stats
+
+    def accum_add_adaptive(self, n, tolerance, luminance_floor=0.01, min_samples=16):
+        """rt_multi_accum_add_adaptive: Renderer.accum_add_adaptive on every shard (the decision is per pixel); the summed RtStats."""
+        ad, stats = make_adaptive(tolerance, luminance_floor, min_samples), RtStats()
+        self._call("rt_multi_accum_add_adaptive", int(n), C.byref(ad), C.byref(stats))
+        return stats
+
+    def accum_join(self):
+        """rt_multi_accum_join: every plane of every shard into the whole-frame accumulation on the first device.  Returns a Renderer over
+        that context, which this MultiRenderer owns (closing the Renderer destroys nothing): every reading accum_* call works on it and
+        returns what one Renderer over the frame returns, bit for bit; every writing one raises (RT_ERR_STATE)."""
+        ctx = C.c_void_p()
+        self._call("rt_multi_accum_join", C.byref(ctx))
+        return Renderer._borrowed(self._lib, ctx.value, self._devices[0], getattr(self, "_accum_shape", (0, 0)))
+
+    def accum_import(self, state, halves=None, buckets=None):
+        """rt_multi_accum_import: a whole-frame AccumState (and its AccumHalves / AccumBuckets) — what accum_join().accum_export*() or one
+        Renderer over the frame exported — split by rows over the devices; right after accum_begin (begun without halves and buckets)."""
+        st = state.as_struct()
+        hs = halves.as_struct() if halves is not None else None
+        bs = buckets.as_struct() if buckets is not None else None
+        self._call("rt_multi_accum_import", C.byref(st), C.byref(hs) if hs is not None else None, C.byref(bs) if bs is not None else None)
+
+    def accum_end(self):
+        """rt_multi_accum_end: ends the accumulation on every device; the joined context holds nothing afterwards."""
+        self._call("rt_multi_accum_end")
 
     def close(self):
         if self._m:

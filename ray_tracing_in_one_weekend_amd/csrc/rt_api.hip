@@ -142,6 +142,7 @@ struct RtCtx {
         bool halves = false;   // rt_accum_track_halves / rt_accum_import_halves: accum_halves holds the half sums and moments and every add keeps them
         bool added = false;    // an add of either kind or a merge has happened since rt_accum_begin (rt_accum_import_halves comes before)
         uint32_t buckets = 0;  // rt_accum_track_buckets / rt_accum_import_buckets: M, accum_buckets holds the bucket sums and every add keeps them; 0: not tracked
+        bool mirror = false;   // the context an RtMulti joins its shards into (rt_multi_accum.h): only rt_multi_accum_join writes the accumulation, for good
     } accum;
     DevBuf accum_sum, accum_mom, accum_sem, accum_partials; // (accum_sem: staging of out_sem; accum_partials: one f64 pair per workgroup + the 3 frame figures)
     double* h_noise = nullptr;   // page-locked: mean_luminance, rms_sem, noise as k_noise_final wrote them
@@ -1342,6 +1343,11 @@ static AccumReader accum_reader(const RtCtx* ctx, hipStream_t st) {
     const RtCtx::Accum& a = ctx->accum;
     return AccumReader{st, dim3((a.npix + 255u) / 256u), a.nx, a.rows, a.tiles_per_row, a.tile_pixels, ctx->accum_cnt.as<const uint32_t>(), a.done, a.adaptive};
 }
+// Every call that writes an accumulation refuses first on the mirror of an RtMulti (rt_multi_accum_join alone writes that one).
+static int refuse_mirror(RtCtx* ctx, const char* who) {
+    return ctx->accum.mirror ? fail(ctx, RT_ERR_STATE, std::string(who) + ": the context is the joined mirror of an RtMulti, which rt_multi_accum_join alone writes (rtow_mi355x.h)")
+                             : RT_OK;
+}
 #define ACCUM_READER(K, r, ...) KERNEL_PAIR(K, (r).counts, (r).grid, (r).st, __VA_ARGS__)
 
 // The buffers of an adaptive accumulation of npix pixels (kept for the next one): n_p, the flags, the integer sums and their host copy.
@@ -1401,8 +1407,8 @@ static void fill_noise(const RtCtx* ctx, RtNoise* noise) {
 }
 
 int rt_accum_begin(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, uint32_t first_sample) {
-    int rc = check_params(ctx, cam, prm);
-    if (rc) return rc;
+    int rc = ctx ? refuse_mirror(ctx, "rt_accum_begin") : RT_OK; // (before the scene is asked for: the mirror has none)
+    if (rc || (rc = check_params(ctx, cam, prm))) return rc;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     ctx->accum.open = false;
     RtCtx::Accum a{};
@@ -1435,8 +1441,8 @@ int rt_accum_begin(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, uint32_
 static int accum_add(RtCtx* ctx, uint32_t n_samples, bool adaptive, const RtAdaptive* ad, RtStats* stats, bool figures) {
     if (!ctx) return RT_ERR_INVALID;
     const char* name = adaptive ? "rt_accum_add_adaptive" : "rt_accum_add";
-    int rc = require_open(ctx, name);
-    if (rc) return rc;
+    int rc = refuse_mirror(ctx, name);
+    if (rc || (rc = require_open(ctx, name))) return rc;
     const std::string who = std::string(name) + ": ";
     RtCtx::Accum& a = ctx->accum;
     const bool too_many = (uint64_t)a.first + a.done + n_samples > 0xFFFFFFFFull;
@@ -1526,6 +1532,7 @@ int rt_accum_read(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_
 
 int rt_accum_end(RtCtx* ctx) {
     if (!ctx) return RT_ERR_INVALID;
+    if (const int rc = refuse_mirror(ctx, "rt_accum_end")) return rc;
     ctx->accum.open = false;
     return RT_OK;
 }
@@ -1783,6 +1790,7 @@ int rt_debug_denoise(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, c
 // ---- channel moments and the colour-guided filter (rtow_mi355x.h "Channel moments and the colour-guided filter", csrc/rt_channels.h) ------
 int rt_accum_track_channels(RtCtx* ctx) {
     if (!ctx) return RT_ERR_INVALID;
+    if (const int rc = refuse_mirror(ctx, "rt_accum_track_channels")) return rc;
     if (const int rc = require_open(ctx, "rt_accum_track_channels")) return rc;
     RtCtx::Accum& a = ctx->accum;
     if (a.channels) return RT_OK;
@@ -1968,17 +1976,18 @@ static int planes_stage(RtCtx* ctx, PlaneTable& t) {
     RT_HIP(ctx, hipSetDevice(ctx->device));
     return ensure(ctx, ctx->accum_stage, planes_place(t, ctx->accum.npix));
 }
-static void launch_planes_move(RtCtx* ctx, const PlaneTable& t, bool to_staging) {
+// k_planes_move over the open accumulation (npix >= 1) on the context's stream; `stage`: the image-order buffer the rows' offsets count in
+// (ctx->accum_stage, or a buffer of the caller's: rt_multi_accum.h)
+static void launch_planes_move(RtCtx* ctx, const PlaneTable& t, char* stage, bool to_staging) {
     const RtCtx::Accum& a = ctx->accum;
     const dim3 grid((a.npix + 255u) / 256u), block(256);
-    char* stage = ctx->accum_stage.as<char>();
     if (to_staging) hipLaunchKernelGGL(k_planes_move<true>, grid, block, 0, ctx->stream, t, stage, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
     else hipLaunchKernelGGL(k_planes_move<false>, grid, block, 0, ctx->stream, t, stage, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
 }
 // The accumulation's planes -> the caller's arrays, the rows without one left out; complete on return.
 static int planes_to_host(RtCtx* ctx, PlaneTable& t) {
     if (const int rc = planes_stage(ctx, t)) return rc;
-    launch_planes_move(ctx, t, true);
+    launch_planes_move(ctx, t, ctx->accum_stage.as<char>(), true);
     RT_HIP(ctx, hipGetLastError());
     for (uint32_t k = 0; k < t.n; ++k)
         if (const Plane& p = t.row[k]; p.host)
@@ -1993,7 +2002,7 @@ static int planes_from_host(RtCtx* ctx, PlaneTable& t, bool move) {
     for (uint32_t k = 0; k < t.n; ++k)
         RT_HIP(ctx, hipMemcpyAsync(ctx->accum_stage.as<char>() + t.row[k].stage, t.row[k].host, plane_bytes(t.row[k], ctx->accum.npix), hipMemcpyHostToDevice, ctx->stream));
     if (!move) return RT_OK;
-    launch_planes_move(ctx, t, false);
+    launch_planes_move(ctx, t, ctx->accum_stage.as<char>(), false);
     RT_HIP(ctx, hipGetLastError());
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
@@ -2030,7 +2039,7 @@ int rt_accum_import(RtCtx* ctx, const RtAccumState* st) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
     int rc;
-    if ((rc = require_open(ctx, "rt_accum_import"))) return rc;
+    if ((rc = refuse_mirror(ctx, "rt_accum_import")) || (rc = require_open(ctx, "rt_accum_import"))) return rc;
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks halves already (import the state first, then rt_accum_import_halves)");
     if (a.buckets) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks buckets already (import the state first, then rt_accum_import_buckets)");
     if (a.done != 0u || a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_import: samples were added already (call it right after rt_accum_begin)");
@@ -2056,7 +2065,7 @@ int rt_accum_merge(RtCtx* ctx, const RtAccumState* st) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
     int rc;
-    if ((rc = require_open(ctx, "rt_accum_merge"))) return rc;
+    if ((rc = refuse_mirror(ctx, "rt_accum_merge")) || (rc = require_open(ctx, "rt_accum_merge"))) return rc;
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks halves: a merge of halves is not covered (rtow_mi355x.h)");
     if (a.buckets) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks buckets: a merge of buckets is not covered (rtow_mi355x.h)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_merge: ") + why);
@@ -2095,6 +2104,7 @@ static int ensure_halves(RtCtx* ctx, uint32_t npix) { return ensure(ctx, ctx->ac
 int rt_accum_track_halves(RtCtx* ctx) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
+    if (const int rc = refuse_mirror(ctx, "rt_accum_track_halves")) return rc;
     if (const int rc = require_open(ctx, "rt_accum_track_halves")) return rc;
     if (a.halves) return RT_OK;
     if (a.done != 0u || a.adaptive || a.added)
@@ -2192,7 +2202,7 @@ int rt_accum_import_halves(RtCtx* ctx, const RtAccumHalves* hs) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
     int rc;
-    if ((rc = require_open(ctx, "rt_accum_import_halves"))) return rc;
+    if ((rc = refuse_mirror(ctx, "rt_accum_import_halves")) || (rc = require_open(ctx, "rt_accum_import_halves"))) return rc;
     if (a.added) return fail(ctx, RT_ERR_STATE, "rt_accum_import_halves: samples were added since rt_accum_begin (call it right after rt_accum_begin or rt_accum_import)");
     if (const char* why = accum_halves_invalid(hs)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import_halves: ") + why);
     if ((rc = require_match(ctx, "rt_accum_import_halves", snapshot_header(*hs), "halves", SNAPSHOT_FIRST_AND_DONE))) return rc;
@@ -2216,6 +2226,7 @@ static int ensure_buckets(RtCtx* ctx, uint32_t npix, uint32_t M) { return ensure
 int rt_accum_track_buckets(RtCtx* ctx, uint32_t M) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
+    if (const int rc = refuse_mirror(ctx, "rt_accum_track_buckets")) return rc;
     if (const int rc = require_open(ctx, "rt_accum_track_buckets")) return rc;
     if (M < RT_BUCKETS_MIN || M > RT_BUCKETS_MAX) return fail(ctx, RT_ERR_INVALID, "rt_accum_track_buckets: M must be 3 .. RT_BUCKETS_MAX");
     if (a.buckets == M) return RT_OK;
@@ -2325,7 +2336,7 @@ int rt_accum_import_buckets(RtCtx* ctx, const RtAccumBuckets* bs) {
     if (!ctx) return RT_ERR_INVALID;
     RtCtx::Accum& a = ctx->accum;
     int rc;
-    if ((rc = require_open(ctx, "rt_accum_import_buckets"))) return rc;
+    if ((rc = refuse_mirror(ctx, "rt_accum_import_buckets")) || (rc = require_open(ctx, "rt_accum_import_buckets"))) return rc;
     if (a.added) return fail(ctx, RT_ERR_STATE, "rt_accum_import_buckets: samples were added since rt_accum_begin (call it right after rt_accum_begin or rt_accum_import)");
     if (const char* why = accum_buckets_invalid(bs)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import_buckets: ") + why);
     if ((rc = require_match(ctx, "rt_accum_import_buckets", snapshot_header(*bs), "buckets", SNAPSHOT_FIRST_AND_DONE))) return rc;
@@ -2942,3 +2953,4 @@ extern "C" int rt_debug_phase_stats(unsigned long long* out16, int reset) {
 #endif
 
 #include "rt_multi.h"
+#include "rt_multi_accum.h"

@@ -65,6 +65,18 @@ struct RtMulti {
     // per device: band buffer; first device: the gathered band buffers and the full frame
     std::vector<DevBuf> local;
     DevBuf gathered, full_f32, full_u8;
+    // rt_multi_accum_* (rt_multi_accum.h): one accumulation over the shards of every context, joined into `mirror` on the first device
+    struct Accum {
+        bool open = false;
+        bool broken = false; // a device-side failure ended it on every device: every call but rt_multi_accum_begin refuses (`why` names the device)
+        std::string why;
+        RtCamera cam{};
+        RtParams prm{};      // the whole frame's: shard (0, 1, 0)
+        uint32_t first = 0, band = 0;
+    } accum;
+    RtCtx* mirror = nullptr;      // created by the first rt_multi_accum_begin: users of rt_multi_render pay nothing
+    std::vector<DevBuf> send;     // per device: the planes of its shard in image order (plain hipMalloc, as `local`)
+    DevBuf slots;                 // first device: n slots of equal stride, slot i = device i's send buffer
 };
 
 namespace {
@@ -78,6 +90,22 @@ int multi_fail(RtMulti* m, int code, const std::string& msg) {
 
 // rt_set_motion / rt_set_quads / rt_set_lights on every context.  Every context holds the same scene: the first refuses what all would,
 // then none has changed.  After a device-side failure behind the first context, the ones already changed get the set cleared (nullptr).
+// What the devices of one call counted, as one RtStats: the counters summed, the times the maximum (the devices run side by side).
+void multi_sum_stats(const std::vector<RtStats>& sts, RtStats* stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    for (const RtStats& s : sts) {
+        stats->n_paths += s.n_paths, stats->n_rays += s.n_rays, stats->n_rays_secondary += s.n_rays_secondary;
+        stats->n_texture_fetches += s.n_texture_fetches, stats->n_bad_dir += s.n_bad_dir;
+        stats->bytes_algorithmic += s.bytes_algorithmic, stats->bytes_trace_algorithmic += s.bytes_trace_algorithmic;
+        stats->n_trace_launches += s.n_trace_launches;
+        stats->n_slices = std::max(stats->n_slices, s.n_slices);
+        stats->seconds_total = std::max(stats->seconds_total, s.seconds_total);
+        stats->seconds_trace = std::max(stats->seconds_trace, s.seconds_trace);
+        stats->seconds_device = std::max(stats->seconds_device, s.seconds_device);
+        for (int d = 0; d < 64; ++d) stats->rays_per_depth[d] += s.rays_per_depth[d];
+    }
+}
+
 template <class Set>
 int multi_set(RtMulti* m, int (*set)(RtCtx*, const Set*), const Set* value) {
     if (!m) return RT_ERR_INVALID;
@@ -103,10 +131,15 @@ void rt_multi_destroy(RtMulti* m) {
         (void)hipSetDevice(m->devices[i]);
         if (i < m->local.size()) free_buf(m->local[i]);
     }
+    for (size_t i = 0; i < m->send.size(); ++i) {
+        (void)hipSetDevice(m->devices[i]);
+        free_buf(m->send[i]);
+    }
     if (!m->ctx.empty()) {
         (void)hipSetDevice(m->devices[0]);
-        free_buf(m->gathered), free_buf(m->full_f32), free_buf(m->full_u8);
+        free_buf(m->gathered), free_buf(m->full_f32), free_buf(m->full_u8), free_buf(m->slots);
     }
+    if (m->mirror) rt_ctx_destroy(m->mirror);
     for (ncclComm_t c : m->comms)
         if (c && m->CommDestroy) (void)m->CommDestroy(c);
     for (size_t i = 0; i < m->gather_done.size(); ++i) {
@@ -313,21 +346,7 @@ int rt_multi_render(RtMulti* m, const RtCamera* cam, const RtParams* params, flo
         if ((e = hipSetDevice(m->devices[i])) == hipSuccess) e = hipStreamSynchronize(m->ctx[i]->stream);
     }
     if (e != hipSuccess) return multi_fail(m, RT_ERR_DEVICE, std::string("rt_multi_render: ") + hipGetErrorString(e));
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        for (uint32_t i = 0; i < n; ++i) {
-            const RtStats& s = sts[i];
-            stats->n_paths += s.n_paths, stats->n_rays += s.n_rays, stats->n_rays_secondary += s.n_rays_secondary;
-            stats->n_texture_fetches += s.n_texture_fetches, stats->n_bad_dir += s.n_bad_dir;
-            stats->bytes_algorithmic += s.bytes_algorithmic, stats->bytes_trace_algorithmic += s.bytes_trace_algorithmic;
-            stats->n_trace_launches += s.n_trace_launches;
-            stats->n_slices = std::max(stats->n_slices, s.n_slices);
-            stats->seconds_total = std::max(stats->seconds_total, s.seconds_total); // devices run side by side
-            stats->seconds_trace = std::max(stats->seconds_trace, s.seconds_trace);
-            stats->seconds_device = std::max(stats->seconds_device, s.seconds_device);
-            for (int d = 0; d < 64; ++d) stats->rays_per_depth[d] += s.rays_per_depth[d];
-        }
-    }
+    if (stats) multi_sum_stats(sts, stats);
     return RT_OK;
 }
 

@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from . import AccumBuckets, AccumState, Renderer, RtError, Scene, make_params, output_file_name, register_default_images, save_png
+from . import AccumBuckets, AccumState, MultiRenderer, Renderer, RtError, Scene, make_params, output_file_name, register_default_images, save_png
 from . import _ffi
 
 # --robust without --buckets: of 5, 9 and 15 by the rule of RT_DENOISE_DEFAULT_STRENGTH on rendered frames (DESIGN.md "Sample buckets")
@@ -21,6 +21,69 @@ DEFAULT_BUCKETS = 5
 
 SCENES = ("test_sphere", "sphere_scene", "moving_sphere_scene", "quads_scene", "mesh_scene", "simple_light_scene", "cornell_box", "final_scene", "earth_env_scene",
           "pbr_sweep_scene")
+
+
+class _MultiAccum:
+    """--devices: a MultiRenderer behind the Renderer calls the functions below make.  What builds the accumulation goes to every device
+    (rt_multi_accum_*: tracking is asked for at begin and an import takes the state and its buckets in one call, so a later accum_track_*
+    or accum_import_buckets begins again with what is known by then; nothing has been sampled at that point).  Everything that reads goes
+    to the joined context, joined again after every add."""
+
+    def __init__(self, devices, copy_gather):
+        self._mr = MultiRenderer(devices, copy_gather=copy_gather)
+        self._begin = self._state = self._joined = None
+        self._track = dict(channels=False, halves=False, buckets=0)
+        for name in ("upload", "set_lens", "set_motion", "set_quads", "set_lights", "render"):
+            setattr(self, name, getattr(self._mr, name))
+
+    def _rebegin(self):
+        self._mr.accum_begin(*self._begin, **self._track)
+        self._joined = None
+
+    def accum_begin(self, camera, params, first_sample=0):
+        self._begin, self._state = (camera, params, first_sample), None
+        self._track = dict(channels=False, halves=False, buckets=0)
+        self._rebegin()
+
+    def accum_track_channels(self):
+        self._track["channels"] = True
+        self._rebegin()
+
+    def accum_track_halves(self):
+        self._track["halves"] = True
+        self._rebegin()
+
+    def accum_track_buckets(self, M):
+        self._track["buckets"] = int(M)
+        self._rebegin()
+
+    def accum_import(self, state):
+        self._state = state
+        self._mr.accum_import(state)
+        self._joined = None
+
+    def accum_import_buckets(self, buckets):
+        self._rebegin()
+        self._mr.accum_import(self._state, buckets=buckets)
+
+    def accum_add(self, n):
+        self._joined = None
+        return self._mr.accum_add(n)
+
+    def accum_add_adaptive(self, n, tolerance, luminance_floor=0.01, min_samples=16):
+        self._joined = None
+        return self._mr.accum_add_adaptive(n, tolerance, luminance_floor, min_samples)
+
+    def accum_end(self):
+        self._joined = None
+        self._mr.accum_end()
+
+    def __getattr__(self, name):  # every reading call: accum_read, accum_counts, accum_denoise*, accum_robust, accum_export*
+        if not name.startswith("accum_"):
+            raise AttributeError(name)
+        if self._joined is None:
+            self._joined = self._mr.accum_join()
+        return getattr(self._joined, name)
 
 
 def main(argv=None):
@@ -104,7 +167,25 @@ def main(argv=None):
                     help="with --robust: the number of bucket means trimmed per side, per pixel the largest of its three channels, as a grey PNG "
                          "(white = the most possible, (M - 1) / 2)")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--devices", default=None, metavar="ID,ID,...",
+                    help="render on these devices of the node at once (rt_multi_*): every device takes row-interleaved bands of the frame; the "
+                         "progressive options (--noise-target, --adaptive-tolerance, --denoise, --buckets, --robust, --checkpoint, --resume) add "
+                         "on every device and read the frame out of the joined accumulation on the first (rt_multi_accum_join), bit for bit "
+                         "what --device renders.  A checkpoint is a whole-frame state: it resumes on any number of devices, or on one with --device")
+    ap.add_argument("--copy-gather", action="store_true",
+                    help="with --devices: device-to-device copies instead of RCCL (RT_MULTI_COPY_GATHER); an id may then be listed several times, "
+                         "so --devices 0,0 runs two contexts on one GPU")
     a = ap.parse_args(argv)
+    multi = a.devices is not None
+    if multi:
+        try:
+            a.devices = [int(d) for d in a.devices.split(",")]
+        except ValueError:
+            ap.error("--devices takes a comma-separated list of device ids")
+        if a.preview_every or a.merge or a.residual_target is not None:
+            ap.error("--devices does not combine with --preview-every, --merge or --residual-target")
+    elif a.copy_gather:
+        ap.error("--copy-gather needs --devices")
     ny = a.ny
     aspect = a.nx / ny                                                        # main.rs:68
     file_name = a.out or output_file_name()
@@ -112,7 +193,7 @@ def main(argv=None):
     t0 = time.perf_counter()                                                  # EZTimer, main.rs:70
     register_default_images()
     scene = Scene.build(a.scene, aspect)
-    rend = Renderer(a.device)
+    rend = _MultiAccum(a.devices, a.copy_gather) if multi else Renderer(a.device)
     rend.upload(scene)
     if a.aperture:
         rend.set_lens((a.aperture / 2.0, a.focus_dist))
@@ -161,11 +242,12 @@ def main(argv=None):
         if a.spp < 4:
             ap.error("the cross filter needs --spp >= 4: two samples per half")
         return render_halves(a, rend, scene, flags, file_name, t0)
-    if a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets:
+    progressive = a.adaptive_tolerance is not None or a.noise_target is not None or a.denoise
+    if a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets or (multi and progressive):
         if a.preview_every:
             ap.error("--checkpoint, --resume, --first-sample and --merge do not combine with --preview-every")
-        if a.adaptive_tolerance is not None and (a.noise_target is not None or a.denoise):
-            ap.error("--adaptive-tolerance does not combine with --noise-target or --denoise")
+        if a.adaptive_tolerance is not None and a.noise_target is not None:
+            ap.error("--adaptive-tolerance does not combine with --noise-target")
         if a.checkpoint_every < 1 or a.spp_step < 1:
             ap.error("--checkpoint-every and --spp-step must be >= 1")
         return render_with_state(a, rend, scene, flags, file_name, t0)
