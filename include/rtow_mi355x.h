@@ -951,6 +951,83 @@ int rt_denoise_level_size(uint32_t nx, uint32_t rows, uint32_t level, uint32_t* 
  * reserved != 0. */
 int rt_accum_denoise_multiscale(RtCtx* ctx, const RtDenoise* dn, const RtMultiscale* ms, float* out_rgb_f32, uint8_t* out_rgb8);
 
+/* -- display transform: exposure, tone curve, transfer function and dither behind every 8-bit read-out of an accumulation -----------------
+ * Every out_rgb8 above is the reference driver's quantisation, sqrt(c) * 255.99 saturating: radiance above 1 clips (emitters, their
+ * surround, fireflies), a dark frame has no exposure, a denoised gradient shows the bands its noise used to dither away, and gamma 2 is
+ * not the sRGB a PNG viewer assumes.  A DISPLAY set on a context replaces that one step — on the device, behind the same single wait —
+ * for the out_rgb8 of rt_accum_read, rt_accum_denoise, rt_accum_denoise_channels, rt_accum_denoise_halves, rt_accum_denoise_robust,
+ * rt_accum_denoise_multiscale and rt_accum_read_robust (and of rt_render_to_noise and rt_render_adaptive, which end in rt_accum_read):
+ * out_rgb8 is the transform below of the f32 image the same call returns.  Nothing else changes in any bit: out_rgb_f32, out_sem, every
+ * figure, state and export; no sample, sum or moment is touched, and no existing kernel.  It works on a shard; the statistics are then
+ * those of the shard's pixels, as the noise figures are.
+ * Every f32 operation is one IEEE operation in the order written, no FMA; `/` and sqrtf are correctly rounded.
+ * Input.  Pixel c = (r, g, b) of the f32 image in the call's row order; e = the exposure.
+ * Statistics (only where exposure_mode is not RT_EXPOSURE_MANUAL, whose e = exposure_value):
+ *   Y = (0.2126f * r + 0.7152f * g) + 0.0722f * b in f32.  A pixel is LIT iff Y is finite and Y > 0; n_lit counts them.
+ *   RT_EXPOSURE_KEY: S = the sum of log((double)Y) over the lit pixels, in f64 on the fixed tree of the frame figures ("Frame figures":
+ *     per 256 consecutive pixels of the image lanes then waves, then one workgroup over those partial sums in index order; a pixel that
+ *     is not lit adds 0.0).  Lavg = exp(S / (double)n_lit);  e = (float)((double)exposure_value / Lavg).
+ *   RT_EXPOSURE_PERCENTILE: a histogram of the lit pixels over bin = bits(Y) >> 20 — 2048 bins, 8 per octave, integer arithmetic only,
+ *     u32 counts.  rank = max(1, ceil((double)percentile * (double)n_lit));  b = the first bin whose cumulative count reaches rank;
+ *     L_q = the f32 with the bits (b << 20) | 0x80000, the middle of the bin;  e = (float)((double)exposure_value / (double)L_q).
+ *   n_lit == 0, or an e that is zero or not finite: e = 1.
+ * Per pixel.  If any channel of c is not finite the pixel counts in n_non_finite and each channel is written as: NaN 0, -inf 0, +inf 255,
+ *   a finite one as under RT_TONE_CLAMP below (with the display's transfer and dither).  Otherwise, per channel, x = e * c, then
+ *   x = x > 0 ? x : 0.
+ * Curve.  RT_TONE_CLAMP: t = x.
+ *   RT_TONE_REINHARD: L = the luminance of x by the formula of Y;  s = (1 + L / (white * white)) / (1 + L);  t = x * s per channel
+ *     (white = +inf: s = 1 / (1 + L)).
+ *   RT_TONE_ACES (Narkowicz 2015, "ACES filmic tone mapping curve"), per channel:  x = x < 65536.0f ? x : 65536.0f;
+ *     t = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f).
+ * Transfer.  RT_TRANSFER_GAMMA2: y = sqrtf(t).
+ *   RT_TRANSFER_SRGB: y = t <= 0.0031308f ? 12.92f * t : 1.055f * p - 0.055f,  p = (float)pow((double)t, 1.0 / 2.4): the power in f64,
+ *     rounded to f32 once, the product and the difference in f32.  The f64 pow of a conforming library is within 16 ulp (the device's and
+ *     glibc's are within 1), so two implementations agree on p except within 2^-48 of a rounding boundary, where they differ by one ulp
+ *     of p; through 1.055f * p - 0.055f, which amplifies a relative error by 1.055 p / y <= 2.36, two y differ by less than 3 ulp of the
+ *     product: RT_DISPLAY_SRGB_EPS = 2^-20 relative (14.2 * 2^-24, rounded up) bounds the difference of any two implementations.
+ * Quantisation, with k_finalize's row flip: i = the column and r = the row of out_rgb8, 0 at the top.
+ *   RT_DITHER_NONE: g = y * 255.99f.
+ *   RT_DITHER_BAYER8: g = y * 255.0f + ((float)B(i & 7, r & 7) + 0.5f) / 64.0f,  B(x, y) = the OR over k = 0 .. 2 of
+ *     (((x ^ y) >> k) & 1) << (2 * (2 - k) + 1)  |  ((y >> k) & 1) << (2 * (2 - k)):  the standard 8 x 8 Bayer index, a permutation of
+ *     0 .. 63 with the first row 0 32 8 40 2 34 10 42.  The offsets are 1/128 .. 127/128: an ordered dither of one level's width.
+ *   In both: u = (g == g && g > 0) ? (g >= 255 ? 255 : (uint32_t)g) : 0, the rule of rt_render's quantisation.
+ * Properties (tests/display_ref.py restates all of it in numpy; the kernels are held to it bit for bit, under RT_TRANSFER_SRGB outside
+ * the values whose level differs between y (1 - eps) and y (1 + eps)):
+ *   {RT_EXPOSURE_MANUAL, 1.0f, .., RT_TONE_CLAMP, .., RT_TRANSFER_GAMMA2, RT_DITHER_NONE} gives the out_rgb8 of no display, bit for bit.
+ *   The same image gives the same e and the same figures on every run: no floating-point atomic takes part.
+ * Not covered: rt_render, rt_render_device, the preview of rt_set_progress and rt_multi_render keep the reference quantisation, and so do
+ * the contexts of an RtMulti (the joined context of rt_multi_accum_join included).  DESIGN.md "Display transform". */
+enum RtExposureMode { RT_EXPOSURE_MANUAL = 0, RT_EXPOSURE_KEY = 1, RT_EXPOSURE_PERCENTILE = 2 };
+enum RtToneCurve { RT_TONE_CLAMP = 0, RT_TONE_REINHARD = 1, RT_TONE_ACES = 2 };
+enum RtTransfer { RT_TRANSFER_GAMMA2 = 0, RT_TRANSFER_SRGB = 1 };
+enum RtDither { RT_DITHER_NONE = 0, RT_DITHER_BAYER8 = 1 };
+#define RT_DISPLAY_SRGB_EPS 9.5367431640625e-07 /* 2^-20 */
+typedef struct RtDisplay {
+    uint32_t exposure_mode; /* RtExposureMode */
+    float exposure_value;   /* MANUAL: the multiplier e; KEY: the key (0.18); PERCENTILE: the linear level the percentile maps to; finite, > 0 */
+    float percentile;       /* PERCENTILE: q in (0, 1]; else ignored */
+    uint32_t curve;         /* RtToneCurve */
+    float white;            /* REINHARD: the white point, > 0, +inf allowed; else ignored */
+    uint32_t transfer, dither, reserved; /* RtTransfer, RtDither, 0 */
+} RtDisplay;
+typedef struct RtDisplayInfo {
+    float exposure;             /* the e that was applied */
+    float percentile_luminance; /* PERCENTILE: L_q (0 where nothing is lit), else 0 */
+    double log_average;         /* KEY: exp(S / n_lit) (0 where nothing is lit), else 0 */
+    uint64_t n_lit;             /* pixels with finite Y > 0; MANUAL: 0, no statistics run */
+    uint64_t n_non_finite;      /* pixels with a non-finite channel */
+    uint64_t n_saturated;       /* channel values written as 255 */
+} RtDisplayInfo;
+/* A per-context setting, as rt_set_lens and rt_set_progress are, but one that changes no sample: it does NOT end an open accumulation,
+ * and rt_scene_upload leaves it.  `display` NULL: no display, the reference quantisation, bit for bit.  RT_ERR_INVALID: what
+ * rt_display_check refuses; the display set before stays in force. */
+int rt_set_display(RtCtx* ctx, const RtDisplay* display);
+/* The figures of the last out_rgb8 this context wrote under a display.  RT_ERR_STATE: there was none. */
+int rt_display_info(RtCtx* ctx, RtDisplayInfo* info);
+/* GPU-free, no context.  RT_OK, or RT_ERR_INVALID: `display` NULL, an enum out of range, exposure_value not finite or <= 0, percentile
+ * outside (0, 1] under RT_EXPOSURE_PERCENTILE, white NaN or <= 0 under RT_TONE_REINHARD, reserved != 0. */
+int rt_display_check(const RtDisplay* display);
+
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the
  * world shared read-only (main.rs:72-108); here the scene is replicated on every device, device r renders the image

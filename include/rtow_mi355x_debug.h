@@ -256,6 +256,12 @@ int rt_debug_denoise_channels(RtCtx* ctx, uint32_t nx, uint32_t rows, const floa
 int rt_debug_denoise_multiscale(RtCtx* ctx, uint32_t nx, uint32_t rows, uint32_t guide, const float* rgb, const float* mean, const float* var,
                                 const RtDenoise* dn, uint32_t levels, float* out_rgb_f32, uint32_t probe_level, float* probe_rgb,
                                 float* probe_mean, float* probe_var);
+/* Test hook for the display transform (rtow_mi355x.h "display transform"): the same kernels over a host image in the row order of an
+ * out_rgb_f32 — rgb [3 * nx * rows] — under `display` (not the context's, which it neither reads nor changes; nor does it touch what
+ * rt_display_info returns); out_rgb8 [3 * nx * rows], rows flipped as every out_rgb8, and `info` (may be NULL) the figures of this run.
+ * No scene and no accumulation is needed.  RT_ERR_INVALID: a NULL array or display, nx * rows outside 1 .. 2^28, or a display
+ * rt_display_check refuses. */
+int rt_debug_display(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const RtDisplay* display, uint8_t* out_rgb8, RtDisplayInfo* info);
 
 /* Test hook for adaptive sampling (rtow_mi355x.h "adaptive sampling"): overwrites the two luminance moments (S1, S2) of pixel `pixel` of
  * the open accumulation, `pixel` an index into out_sem (row order of out_rgb_f32).  The tests plant a NaN with it: such a pixel never

@@ -203,6 +203,30 @@ class RtAccumBuckets(C.Structure):
                 ("reserved", C.c_uint32), ("frame_id", C.c_uint64), ("sum", _f * BUCKETS_MAX)]
 
 
+# enum RtExposureMode, RtToneCurve, RtTransfer, RtDither (rt_set_display)
+EXPOSURE_MANUAL, EXPOSURE_KEY, EXPOSURE_PERCENTILE = range(3)
+TONE_CLAMP, TONE_REINHARD, TONE_ACES = range(3)
+TRANSFER_GAMMA2, TRANSFER_SRGB = range(2)
+DITHER_NONE, DITHER_BAYER8 = range(2)
+DISPLAY_SRGB_EPS = 2.0 ** -20  # RT_DISPLAY_SRGB_EPS
+
+
+class RtDisplay(C.Structure):
+    """rt_set_display: exposure (manual, or measured from the frame), tone curve, transfer function and dither behind every out_rgb8 of
+    the accumulation family (rtow_mi355x.h "display transform")."""
+    _fields_ = [("exposure_mode", C.c_uint32), ("exposure_value", C.c_float), ("percentile", C.c_float), ("curve", C.c_uint32),
+                ("white", C.c_float), ("transfer", C.c_uint32), ("dither", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RtDisplayInfo(C.Structure):
+    """rt_display_info: the exposure that was applied and the figures of the last out_rgb8 written under a display."""
+    _fields_ = [("exposure", C.c_float), ("percentile_luminance", C.c_float), ("log_average", C.c_double), ("n_lit", C.c_uint64),
+                ("n_non_finite", C.c_uint64), ("n_saturated", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RtBounceIO(C.Structure):
     _fields_ = [("n", C.c_uint32), ("depth", C.c_uint32), ("in_o", _f), ("in_d", _f), ("in_key", _u32),
                 ("out_hit", C.POINTER(C.c_int32)), ("out_t", _f), ("out_radiance", _f), ("out_attenuation", _f),
@@ -266,6 +290,7 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_accum_track_buckets", "rt_accum_read_robust", "rt_accum_denoise_robust", "rt_accum_buckets_check", "rt_accum_export_buckets",
                "rt_accum_import_buckets",
                "rt_multi_accum_begin", "rt_multi_accum_add", "rt_multi_accum_add_adaptive", "rt_multi_accum_join", "rt_multi_accum_import", "rt_multi_accum_end",
+               "rt_set_display", "rt_display_info", "rt_display_check", "rt_debug_display",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
@@ -420,6 +445,14 @@ def load_gpu_library():
     lib.rt_accum_export_buckets.restype = C.c_int
     lib.rt_accum_import_buckets.argtypes = [vp, C.POINTER(RtAccumBuckets)]
     lib.rt_accum_import_buckets.restype = C.c_int
+    lib.rt_set_display.argtypes = [vp, C.POINTER(RtDisplay)]
+    lib.rt_set_display.restype = C.c_int
+    lib.rt_display_info.argtypes = [vp, C.POINTER(RtDisplayInfo)]
+    lib.rt_display_info.restype = C.c_int
+    lib.rt_display_check.argtypes = [C.POINTER(RtDisplay)]
+    lib.rt_display_check.restype = C.c_int
+    lib.rt_debug_display.argtypes = [vp, C.c_uint32, C.c_uint32, _f, C.POINTER(RtDisplay), _u8, C.POINTER(RtDisplayInfo)]
+    lib.rt_debug_display.restype = C.c_int
     lib.rt_debug_planar_info.argtypes =[vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.rt_debug_planar_info.restype = C.c_int
     lib.rt_debug_planar_bounds.argtypes = [C.POINTER(RtQuads), C.c_float, vp, vp]

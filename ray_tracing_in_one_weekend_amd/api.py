@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import RtAdaptive, RtAdaptiveInfo, RtBounceIO, RtCamera, RtDenoise, RtFlatScene, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtResidual, RtStats
+from ._ffi import RtAdaptive, RtAdaptiveInfo, RtBounceIO, RtCamera, RtDenoise, RtDisplay, RtDisplayInfo, RtFlatScene, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtResidual, RtStats
 
 
 class RtError(RuntimeError):
@@ -558,6 +558,27 @@ def adaptive_converged(ad, s1, s2, n):
     return rc == 1
 
 
+_EXPOSURE_MODES = {"manual": _ffi.EXPOSURE_MANUAL, "key": _ffi.EXPOSURE_KEY, "percentile": _ffi.EXPOSURE_PERCENTILE}
+_TONE_CURVES = {"clamp": _ffi.TONE_CLAMP, "reinhard": _ffi.TONE_REINHARD, "aces": _ffi.TONE_ACES}
+_TRANSFERS = {"gamma2": _ffi.TRANSFER_GAMMA2, "srgb": _ffi.TRANSFER_SRGB}
+_DITHERS = {"none": _ffi.DITHER_NONE, "bayer8": _ffi.DITHER_BAYER8}
+
+
+def make_display(exposure=1.0, auto=None, percentile=0.99, curve="clamp", white=float("inf"), transfer="gamma2", dither="none"):
+    """An RtDisplay for Renderer.set_display.  auto None: `exposure` is the multiplier e; "key": `exposure` is the key the frame's log-average
+    luminance maps to (0.18 is customary); "percentile": the linear level the `percentile` quantile of the lit luminances maps to.  curve
+    "clamp" | "reinhard" (with `white`, inf: none) | "aces"; transfer "gamma2" | "srgb"; dither "none" | "bayer8".  Names or the
+    _ffi numbers; the defaults are the reference quantisation."""
+    pick = lambda table, v: table[v] if isinstance(v, str) else int(v)
+    return RtDisplay(pick(_EXPOSURE_MODES, auto or "manual"), float(exposure), float(percentile), pick(_TONE_CURVES, curve), float(white),
+                     pick(_TRANSFERS, transfer), pick(_DITHERS, dither), 0)
+
+
+def display_check(display):
+    """rt_display_check (no GPU): True when rt_set_display would accept the RtDisplay."""
+    return _ffi.load_gpu_library().rt_display_check(C.byref(display) if display is not None else None) == 0
+
+
 def denoise_level_size(nx, rows, level):
     """rt_denoise_level_size (no GPU): (nx_l, rows_l) of level `level` of the pyramid accum_denoise_multiscale filters."""
     nx_l, rows_l = C.c_uint32(), C.c_uint32()
@@ -1011,6 +1032,30 @@ class Renderer:
                     return out + (done,)
         finally:
             self.accum_end()
+
+    def set_display(self, display):
+        """rt_set_display: every rgb8 of accum_read, the accum_denoise* calls and accum_robust becomes the display transform (make_display)
+        of the f32 image the same call returns; None: the reference quantisation again.  Does not end an open accumulation; upload()
+        keeps it.  render() and the progress preview are not covered."""
+        self._call("rt_set_display", C.byref(display) if display is not None else None)
+
+    def display_info(self):
+        """rt_display_info: the RtDisplayInfo (exposure applied, L_q or the log average, lit / non-finite pixels, saturated values) of the
+        last rgb8 this Renderer wrote under a display."""
+        info = RtDisplayInfo()
+        self._call("rt_display_info", C.byref(info))
+        return info
+
+    def debug_display(self, rgb, display):
+        """rt_debug_display: the display kernels over a host image [rows, nx, 3] f32 in the row order of accum_read's img; returns
+        (rgb8 [rows, nx, 3] with row 0 on top, RtDisplayInfo).  Neither reads nor changes the display set on this Renderer."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        rows, nx = rgb.shape[:2]
+        assert rgb.shape == (rows, nx, 3)
+        out, info = np.zeros((rows, nx, 3), np.uint8), RtDisplayInfo()
+        self._call("rt_debug_display", nx, rows, rgb.ctypes.data_as(C.POINTER(C.c_float)), C.byref(display), out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                   C.byref(info))
+        return out, info
 
     def set_progress(self, fn):
         """fn(spp_done, spp_total, rgb8[rows, nx, 3]) after every slice but the last of a following render()

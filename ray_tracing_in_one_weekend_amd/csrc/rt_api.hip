@@ -12,6 +12,7 @@
 #include "rt_accum_state_kernels.h"
 #include "rt_halves.h"
 #include "rt_buckets.h"
+#include "rt_display.h"
 #include "rt_bvh.h"
 #include "rt_grid.h"
 #include "rt_pool.h"
@@ -167,6 +168,16 @@ struct RtCtx {
     DevBuf accum_stage;
     DevBuf dn_c, dn_yv, dn_out;  // rt_accum_denoise: the filter's inputs (c 12 B, (y, v) 8 B) and its output (12 B) per pixel, in image order
     DevBuf dn_ms;                // rt_accum_denoise_multiscale: the regions of every level of the pyramid (rt_multiscale_plan.h: multiscale_plan)
+    // rt_set_display (rt_display.h): the transform behind every out_rgb8 of the accumulation family.  display_buf: the RtDisplayInfo record
+    // k_display_exposure writes (64 B), 256 counter slots, the 2048-bin histogram and one f64 partial sum per 256 pixels
+    bool has_display = false;
+    RtDisplay display{};
+    DevBuf display_buf;
+    RtDisplayInfo* h_display = nullptr; // page-locked: the record and the slots as the kernels left them
+    bool display_pending = false;       // a display run is enqueued: the wait that ends the call makes h_display the last figures
+    RtDisplay display_ran{};            // (the display of that run)
+    bool has_display_info = false;
+    RtDisplayInfo display_info{};       // rt_display_info: the figures of the last out_rgb8 written under a display
     // Host-side timeline of the last trace_samples and what its caller enqueued behind it (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
     // render of a process is where allocations, code-object loads and the queue probe happen; this says which.
     std::vector<std::pair<const char*, double>> parts;
@@ -763,6 +774,8 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->accum_buckets), free_buf(ctx->robust_out);
     if (ctx->h_resid) (void)hipHostFree(ctx->h_resid);
     if (ctx->h_robust) (void)hipHostFree(ctx->h_robust);
+    free_buf(ctx->display_buf);
+    if (ctx->h_display) (void)hipHostFree(ctx->h_display);
     if (ctx->h_info) (void)hipHostFree(ctx->h_info);
     free_buf(ctx->dn_c), free_buf(ctx->dn_yv), free_buf(ctx->dn_out), free_buf(ctx->dn_ms);
     if (ctx->h_noise) (void)hipHostFree(ctx->h_noise);
@@ -1406,6 +1419,90 @@ static void fill_noise(const RtCtx* ctx, RtNoise* noise) {
     noise->mean_luminance = ctx->h_noise[0], noise->rms_sem = ctx->h_noise[1], noise->noise = ctx->h_noise[2];
 }
 
+// ---- display transform (rtow_mi355x.h "Display transform", csrc/rt_display.h, csrc/rt_display_plan.h) ---------------------------------------
+// `img` (device, f32 x 3 per pixel in the call's row order, nx x rows >= 1 pixels) through the display `d` into ctx->out_u8, which the
+// caller has ensured, on `st`: the record, the counter slots and the histogram zeroed, the statistics and the exposure where it is not
+// manual, the transform, and a copy of the record and the slots (8 KB) into ctx->h_display, valid after the next wait for `st`
+// (display_commit).  The buffer: record (64 B), slots, histogram, one f64 partial sum per 256 pixels.
+constexpr size_t RT_DISPLAY_RECORD_BYTES = 64u, RT_DISPLAY_COUNT_BYTES = RT_DISPLAY_RECORD_BYTES + RT_DISPLAY_SLOTS * sizeof(DisplayCounters),
+                 RT_DISPLAY_HEAD_BYTES = RT_DISPLAY_COUNT_BYTES + RT_DISPLAY_BINS * sizeof(uint32_t);
+static int enqueue_display(RtCtx* ctx, hipStream_t st, const float* img, uint32_t nx, uint32_t rows, const RtDisplay& d) {
+    const uint32_t npix = nx * rows, n_groups = (npix + 255u) / 256u;
+    const bool manual = d.exposure_mode == RT_EXPOSURE_MANUAL;
+    if (const int rc = ensure(ctx, ctx->display_buf, RT_DISPLAY_HEAD_BYTES + (size_t)n_groups * sizeof(double))) return rc;
+    if (!ctx->h_display) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_display, RT_DISPLAY_COUNT_BYTES, hipHostMallocDefault));
+    char* base = ctx->display_buf.as<char>();
+    RtDisplayInfo* rec = (RtDisplayInfo*)base;
+    DisplayCounters* slots = (DisplayCounters*)(base + RT_DISPLAY_RECORD_BYTES);
+    uint32_t* hist = (uint32_t*)(base + RT_DISPLAY_COUNT_BYTES);
+    double* partials = (double*)(base + RT_DISPLAY_HEAD_BYTES);
+    RT_HIP(ctx, hipMemsetAsync(base, 0, manual ? RT_DISPLAY_COUNT_BYTES : RT_DISPLAY_HEAD_BYTES, st));
+    if (!manual) {
+        const bool key = d.exposure_mode == RT_EXPOSURE_KEY;
+        hipLaunchKernelGGL(k_display_stats, dim3((n_groups + RT_DISPLAY_GROUPS - 1u) / RT_DISPLAY_GROUPS), dim3(256), 0, st, img, npix, n_groups, key ? 0u : 1u,
+                           key ? 1u : 0u, hist, partials, slots);
+        hipLaunchKernelGGL(k_display_exposure, dim3(1), dim3(256), 0, st, (const double*)partials, n_groups, (const uint32_t*)hist, (const DisplayCounters*)slots, d,
+                           rec);
+    }
+    hipLaunchKernelGGL(k_display, dim3(n_groups), dim3(256), 0, st, img, ctx->out_u8.as<uint8_t>(), nx, rows, d, manual ? (const RtDisplayInfo*)nullptr : rec, slots);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(ctx->h_display, rec, RT_DISPLAY_COUNT_BYTES, hipMemcpyDeviceToHost, st));
+    ctx->display_pending = true, ctx->display_ran = d;
+    return RT_OK;
+}
+// After the wait that ends a call: what enqueue_display left in ctx->h_display — the record, the slots' counts added up — with the e of a
+// manual exposure, which no kernel writes.
+static RtDisplayInfo display_figures(const RtCtx* ctx) {
+    RtDisplayInfo info = *ctx->h_display;
+    const DisplayCounters* slots = (const DisplayCounters*)((const char*)ctx->h_display + RT_DISPLAY_RECORD_BYTES);
+    for (uint32_t k = 0; k < RT_DISPLAY_SLOTS; ++k) info.n_non_finite += slots[k].n_non_finite, info.n_saturated += slots[k].n_saturated;
+    if (ctx->display_ran.exposure_mode == RT_EXPOSURE_MANUAL) info.exposure = ctx->display_ran.exposure_value;
+    return info;
+}
+static void display_commit(RtCtx* ctx) {
+    if (!ctx->display_pending) return;
+    ctx->display_pending = false;
+    ctx->display_info = display_figures(ctx), ctx->has_display_info = true;
+}
+
+int rt_display_check(const RtDisplay* display) { return display_invalid(display) ? RT_ERR_INVALID : RT_OK; }
+int rt_set_display(RtCtx* ctx, const RtDisplay* display) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!display) {
+        ctx->has_display = false;
+        return RT_OK;
+    }
+    if (const char* why = display_invalid(display)) return fail(ctx, RT_ERR_INVALID, std::string("rt_set_display: ") + why);
+    ctx->display = *display, ctx->has_display = true;
+    return RT_OK;
+}
+int rt_display_info(RtCtx* ctx, RtDisplayInfo* info) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!info) return fail(ctx, RT_ERR_INVALID, "rt_display_info: info is NULL");
+    if (!ctx->has_display_info) return fail(ctx, RT_ERR_STATE, "rt_display_info: no out_rgb8 was written under a display yet (rt_set_display)");
+    *info = ctx->display_info;
+    return RT_OK;
+}
+int rt_debug_display(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const RtDisplay* display, uint8_t* out_rgb8, RtDisplayInfo* info) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!rgb || !out_rgb8) return fail(ctx, RT_ERR_INVALID, "rt_debug_display: NULL array");
+    if (nx == 0u || rows == 0u || (uint64_t)nx * rows > (1ull << 28)) return fail(ctx, RT_ERR_INVALID, "rt_debug_display: nx * rows must be 1 .. 2^28");
+    if (const char* why = display_invalid(display)) return fail(ctx, RT_ERR_INVALID, std::string("rt_debug_display: ") + why);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)nx * rows * 3;
+    int rc;
+    if ((rc = ensure(ctx, ctx->out_f32, n * sizeof(float))) || (rc = ensure(ctx, ctx->out_u8, n))) return rc;
+    const hipStream_t st = ctx->stream;
+    RT_HIP(ctx, hipMemcpyAsync(ctx->out_f32.p, rgb, n * sizeof(float), hipMemcpyHostToDevice, st));
+    const bool was_pending = ctx->display_pending; // (false: every call that enqueues a display waits and commits before it returns)
+    if ((rc = enqueue_display(ctx, st, ctx->out_f32.as<const float>(), nx, rows, *display))) return rc;
+    RT_HIP(ctx, hipMemcpyAsync(out_rgb8, ctx->out_u8.p, n, hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    ctx->display_pending = was_pending;
+    if (info) *info = display_figures(ctx);
+    return RT_OK;
+}
+
 int rt_accum_begin(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, uint32_t first_sample) {
     int rc = ctx ? refuse_mirror(ctx, "rt_accum_begin") : RT_OK; // (before the scene is asked for: the mirror has none)
     if (rc || (rc = check_params(ctx, cam, prm))) return rc;
@@ -1510,13 +1607,15 @@ int rt_accum_read(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_
     const hipStream_t st = ctx->stream;
     const uint32_t npix = a.npix;
     const size_t n = (size_t)npix * 3;
-    if (out_rgb_f32 && (rc = ensure(ctx, ctx->out_f32, n * sizeof(float)))) return rc;
+    const bool displayed = out_rgb8 && ctx->has_display; // the f32 image is then written whoever asks for it: the display kernels read it
+    if ((out_rgb_f32 || displayed) && (rc = ensure(ctx, ctx->out_f32, n * sizeof(float)))) return rc;
     if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
     if (out_sem && (rc = ensure(ctx, ctx->accum_sem, (size_t)npix * sizeof(float)))) return rc;
     const AccumReader r = accum_reader(ctx, st);
     if (out_rgb_f32 || out_rgb8) // (a uniform accumulation before the first add: the sums are zeros, divided by 1, not by 0)
-        ACCUM_READER(k_finalize, r, ctx->accum_sum.as<const float>(), r.cnt, out_rgb_f32 ? ctx->out_f32.as<float>() : nullptr,
-                     out_rgb8 ? ctx->out_u8.as<uint8_t>() : nullptr, r.nx, r.rows, std::max(r.n, 1u), r.tiles_per_row, r.tile_pixels);
+        ACCUM_READER(k_finalize, r, ctx->accum_sum.as<const float>(), r.cnt, out_rgb_f32 || displayed ? ctx->out_f32.as<float>() : nullptr,
+                     out_rgb8 && !displayed ? ctx->out_u8.as<uint8_t>() : nullptr, r.nx, r.rows, std::max(r.n, 1u), r.tiles_per_row, r.tile_pixels);
+    if (displayed && (rc = enqueue_display(ctx, st, ctx->out_f32.as<const float>(), a.nx, a.rows, ctx->display))) return rc;
     if (out_sem)
         ACCUM_READER(k_sem, r, ctx->accum_mom.as<const double2>(), r.cnt, ctx->accum_sem.as<float>(), (uint32_t*)nullptr, r.nx, r.rows, r.n, r.tiles_per_row,
                      r.tile_pixels);
@@ -1526,6 +1625,7 @@ int rt_accum_read(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_
     if (out_rgb8) RT_HIP(ctx, hipMemcpyAsync(out_rgb8, ctx->out_u8.p, n, hipMemcpyDeviceToHost, st));
     if (out_sem) RT_HIP(ctx, hipMemcpyAsync(out_sem, ctx->accum_sem.p, (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, st));
     RT_HIP(ctx, hipStreamSynchronize(st));
+    display_commit(ctx);
     if (noise) fill_noise(ctx, noise);
     return RT_OK;
 }
@@ -1686,12 +1786,15 @@ static int ensure_nlm(RtCtx* ctx, size_t npix, uint32_t planes) {
 }
 
 // Their shared end: the filtered image `img` (device, image order) through k_finalize's quantisation and flip into ctx->out_u8 where rgb8 is
-// asked — row-major (no tiles), and / (float)1 changes no bit — and the copies to the host, enqueued on the context's stream.
+// asked — row-major (no tiles), and / (float)1 changes no bit — or through the context's display (rt_set_display) in its place, and the
+// copies to the host, enqueued on the context's stream.  The caller's wait for the stream is followed by display_commit.
 static int denoise_finish(RtCtx* ctx, const float* img, float* out_rgb_f32, uint8_t* out_rgb8) {
     const RtCtx::Accum& a = ctx->accum;
     const hipStream_t st = ctx->stream;
     const size_t n = (size_t)a.npix * 3;
-    if (out_rgb8)
+    if (out_rgb8 && ctx->has_display) {
+        if (const int rc = enqueue_display(ctx, st, img, a.nx, a.rows, ctx->display)) return rc;
+    } else if (out_rgb8)
         hipLaunchKernelGGL(k_finalize<false>, dim3((a.npix + 255u) / 256u), dim3(256), 0, st, img, (const uint32_t*)nullptr, (float*)nullptr, ctx->out_u8.as<uint8_t>(), a.nx,
                            a.rows, 1u, 0u, 0u);
     RT_HIP(ctx, hipGetLastError());
@@ -1735,6 +1838,7 @@ static int denoise_run(RtCtx* ctx, const DenoiseCall& call, const RtDenoise* dn,
     if ((rc = middle(accum_reader(ctx, st), d, img))) return rc;
     if ((rc = denoise_finish(ctx, img, out_rgb_f32, out_rgb8))) return rc;
     RT_HIP(ctx, hipStreamSynchronize(st));
+    display_commit(ctx);
     return RT_OK;
 }
 static int no_more_checks() { return RT_OK; } // (`more` of a call without checks of its own)
@@ -2293,6 +2397,7 @@ int rt_accum_read_robust(RtCtx* ctx, const RtRobust* rb, float* out_rgb_f32, uin
     if ((rc = denoise_finish(ctx, d_out, out_rgb_f32, out_rgb8))) return rc; // (k_finalize's quantisation of `out`, and the copies)
     if (out_trim) RT_HIP(ctx, hipMemcpyAsync(out_trim, d_trim, n, hipMemcpyDeviceToHost, st));
     RT_HIP(ctx, hipStreamSynchronize(st));
+    display_commit(ctx);
     if (info) *info = *ctx->h_robust;
     return RT_OK;
 }

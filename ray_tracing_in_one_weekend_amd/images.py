@@ -24,6 +24,30 @@ def decode_rgb32f(path):
     return (a.astype(np.float32) / np.float32(255.0)).astype(np.float32)
 
 
+def write_pfm(path, img):
+    """Writes the linear f32 image [rows, nx, 3] with row 0 at the BOTTOM — what Renderer.render and accum_read return — as a colour PFM
+    (Portable FloatMap: "PF", width and height, a negative scale for little-endian, then the rows from the bottom one up, f32 x 3 per
+    pixel): the one format here that keeps an HDR frame, every bit of it, NaNs and infinities included."""
+    a = np.ascontiguousarray(img, dtype="<f4")
+    assert a.ndim == 3 and a.shape[2] == 3, a.shape
+    with open(path, "wb") as f:
+        f.write(b"PF\n%d %d\n-1.0\n" % (a.shape[1], a.shape[0]))
+        f.write(a.tobytes())
+
+
+def read_pfm(path):
+    """The [rows, nx, 3] f32 image, row 0 at the bottom, of a colour PFM of either byte order."""
+    with open(path, "rb") as f:
+        magic, size, scale = f.readline().strip(), f.readline().split(), float(f.readline())
+        if magic != b"PF" or len(size) != 2:
+            raise ValueError(f"{path}: not a colour PFM")
+        nx, rows = int(size[0]), int(size[1])
+        a = np.frombuffer(f.read(rows * nx * 12), dtype="<f4" if scale < 0 else ">f4")
+    if a.size != rows * nx * 3:
+        raise ValueError(f"{path}: truncated")
+    return a.reshape(rows, nx, 3).astype(np.float32)
+
+
 def register_image(ref_path, pixels):
     """Registers decoded pixels under the path string the scene code uses."""
     lib = _ffi.load_host_library()

@@ -13,8 +13,9 @@ import time
 
 import numpy as np
 
-from . import AccumBuckets, AccumState, MultiRenderer, Renderer, RtError, Scene, make_params, output_file_name, register_default_images, save_png
+from . import AccumBuckets, AccumState, MultiRenderer, Renderer, RtError, Scene, display_check, make_display, make_params, output_file_name, register_default_images, save_png
 from . import _ffi
+from .images import write_pfm
 
 # --robust without --buckets: of 5, 9 and 15 by the rule of RT_DENOISE_DEFAULT_STRENGTH on rendered frames (DESIGN.md "Sample buckets")
 DEFAULT_BUCKETS = 5
@@ -166,6 +167,23 @@ def main(argv=None):
     ap.add_argument("--firefly-map", default=None, metavar="PATH",
                     help="with --robust: the number of bucket means trimmed per side, per pixel the largest of its three channels, as a grey PNG "
                          "(white = the most possible, (M - 1) / 2)")
+    ap.add_argument("--exposure", type=float, default=None, metavar="E",
+                    help="display transform (rt_set_display): multiply the linear image by E before the 8-bit step; with --auto-exposure the "
+                         "level the measured luminance maps to instead (default 0.18 for key, 0.8 for percentile)")
+    ap.add_argument("--auto-exposure", choices=("key", "percentile"), default=None,
+                    help="measure the exposure from the frame on the device: key maps the log-average luminance of the lit pixels onto "
+                         "--exposure, percentile the --percentile quantile of their luminance histogram")
+    ap.add_argument("--percentile", type=float, default=0.99, metavar="Q", help="with --auto-exposure percentile: the quantile, in (0, 1]")
+    ap.add_argument("--tone", choices=("clamp", "reinhard", "aces"), default=None,
+                    help="tone curve: clamp (the reference's: radiance above 1 saturates), extended Reinhard on the luminance (--white), or the "
+                         "ACES filmic fit per channel")
+    ap.add_argument("--white", type=float, default=float("inf"), metavar="W", help="with --tone reinhard: the luminance that maps to 1 (default: none)")
+    ap.add_argument("--srgb", action="store_true", help="the sRGB transfer function instead of the reference's gamma 2: what a PNG viewer assumes")
+    ap.add_argument("--dither", action="store_true",
+                    help="8 x 8 ordered dither of the 8-bit step: a denoised gradient keeps no bands")
+    ap.add_argument("--hdr-out", default=None, metavar="FILE.pfm",
+                    help="also write the linear f32 image as a PFM (a plain render only: not with --noise-target, --adaptive-tolerance, "
+                         "--denoise, --checkpoint and their kin)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--devices", default=None, metavar="ID,ID,...",
                     help="render on these devices of the node at once (rt_multi_*): every device takes row-interleaved bands of the frame; the "
@@ -208,6 +226,18 @@ def main(argv=None):
     if a.light_sampling:
         rend.set_lights(scene.lights)  # (a moving scene refuses it: RT_ERR_UNSUPPORTED)
     flags = _ffi.FLAG_RUSSIAN_ROULETTE if a.russian_roulette else 0
+    # the display transform: set once on the context, it stands behind every 8-bit read-out of an accumulation below
+    display = None
+    if a.exposure is not None or a.auto_exposure or a.tone or a.srgb or a.dither:
+        exposure = a.exposure if a.exposure is not None else {None: 1.0, "key": 0.18, "percentile": 0.8}[a.auto_exposure]
+        display = make_display(exposure, auto=a.auto_exposure, percentile=a.percentile, curve=a.tone or "clamp", white=a.white,
+                               transfer="srgb" if a.srgb else "gamma2", dither="bayer8" if a.dither else "none")
+        if not display_check(display):
+            ap.error("--exposure must be finite and > 0, --percentile in (0, 1], --white > 0")
+        if multi or a.preview_every:
+            ap.error("--exposure, --auto-exposure, --tone, --srgb and --dither do not combine with --devices or --preview-every "
+                     "(rt_multi_* and the progress preview keep the reference quantisation)")
+        rend.set_display(display)
     halves = a.residual_target is not None or (a.denoise and a.denoise_guide == "halves")
     if a.denoise_levels is not None:
         if not a.denoise or a.denoise_guide == "halves" or a.residual_target is not None:
@@ -233,6 +263,8 @@ def main(argv=None):
     if a.firefly_map and not a.robust_mode:
         ap.error("--firefly-map needs --robust")
     if halves:
+        if a.hdr_out:
+            ap.error("--hdr-out writes the image of a plain render: it does not combine with the progressive options")
         if a.checkpoint or a.resume or a.merge:
             ap.error("--denoise-guide halves and --residual-target do not combine with --checkpoint, --resume or --merge")
         if a.first_sample is not None or a.adaptive_tolerance is not None or a.noise_target is not None or a.preview_every:
@@ -243,6 +275,8 @@ def main(argv=None):
             ap.error("the cross filter needs --spp >= 4: two samples per half")
         return render_halves(a, rend, scene, flags, file_name, t0)
     progressive = a.adaptive_tolerance is not None or a.noise_target is not None or a.denoise
+    if a.hdr_out and (progressive or halves or a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets):
+        ap.error("--hdr-out writes the image of a plain render: it does not combine with the progressive options")
     if a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets or (multi and progressive):
         if a.preview_every:
             ap.error("--checkpoint, --resume, --first-sample and --merge do not combine with --preview-every")
@@ -260,14 +294,29 @@ def main(argv=None):
     if a.denoise:
         return render_denoised(a, rend, scene, flags, file_name, t0)
     params = make_params(a.nx, ny, a.spp, max_depth=a.max_depth, seed=a.seed, spp_slice=a.preview_every, flags=flags)
+    if display is not None:  # through an accumulation: begin / add / read; its f32 image is rt_render's, bit for bit
+        rend.accum_begin(scene.camera, params)
+        st = rend.accum_add(a.spp)
+        img, rgb8, _, _ = rend.accum_read(want_rgb8=True)
+        rend.accum_end()
+        info = rend.display_info()
+        print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
+        save_png(file_name, rgb8)
+        if a.hdr_out:
+            write_pfm(a.hdr_out, img)
+        print(f"{file_name}: {a.nx}x{ny}, {a.spp} spp, {st.n_rays} rays, {st.n_rays / st.seconds_device / 1e6:.0f} Mray/s on the device; display: exposure "
+              f"{info.exposure:.4g}, {info.n_saturated} of {rgb8.size} values at 255, {info.n_non_finite} non-finite pixels", file=sys.stderr)
+        return 0
     if a.preview_every:
         def progress(done, total, rgb8):
             print(f"{done}/{total}", file=sys.stderr)                          # main.rs:116-118
             save_png(file_name, rgb8)                                          # main.rs:119-123
         rend.set_progress(progress)
-    _, rgb8, st = rend.render(scene.camera, params, want_rgb8=True)
+    img, rgb8, st = rend.render(scene.camera, params, want_rgb8=True)
     print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)        # drop(t), main.rs:126
     save_png(file_name, rgb8)                                                  # main.rs:127-128
+    if a.hdr_out:
+        write_pfm(a.hdr_out, img)
     print(f"{file_name}: {a.nx}x{ny}, {a.spp} spp, {st.n_rays} rays, {st.n_rays / st.seconds_device / 1e6:.0f} Mray/s on the device",
           file=sys.stderr)
     return 0
