@@ -1028,6 +1028,73 @@ int rt_display_info(RtCtx* ctx, RtDisplayInfo* info);
  * outside (0, 1] under RT_EXPOSURE_PERCENTILE, white NaN or <= 0 under RT_TONE_REINHARD, reserved != 0. */
 int rt_display_check(const RtDisplay* display);
 
+/* -- Glare: an energy-conserving bloom in front of the display stage ------------------------------------------------------------------------
+ * Every stage of the display transform works on one pixel: a light a thousand times brighter than its surround still ends as a hard-edged
+ * white disc.  A GLARE set on a context carries a share of every pixel's energy into its neighbourhood — what an eye or a lens does —
+ * before the display stage of every out_rgb8 a display can stand behind: rt_accum_read, rt_accum_denoise, rt_accum_denoise_channels,
+ * rt_accum_denoise_halves, rt_accum_denoise_robust, rt_accum_denoise_multiscale and rt_accum_read_robust (and rt_render_to_noise and
+ * rt_render_adaptive, which end in rt_accum_read).  `out` below replaces "the f32 image" as the display stage's input, for its statistics
+ * and for its per-pixel transform; with no display set, `out` goes through the reference quantisation, which is the display of the
+ * identity configuration.  Nothing else changes in any bit: out_rgb_f32, out_sem, every figure, state and export, and no existing kernel.
+ * Every f32 operation is one IEEE operation in the order written, no FMA.
+ * Input.  Pixel c of the f32 image in the call's row order, nx x rows; a = amount; L = levels.
+ * 1. Sanitise, per channel: s = (c is finite && c > 0) ? min(c, 0x1p64f) : +0.0f.
+ *    No sum below can overflow: s <= 2^64; k <= 1, so b <= s; a mean of up to four such values, their sum at most 2^66 before the scale,
+ *    is <= 2^64 (1 + 2^-22) per level; the weights are positive and sum to 1 within Le ulp, and U's weights sum to 1, so every u_l and B
+ *    stay below 2^65; a <= 1: (s - a b) + a B < 2^66, far from 2^128.
+ * 2. Bright pass.  threshold == 0: b = s.  Otherwise Y = (0.2126f * s_r + 0.7152f * s_g) + 0.0722f * s_b (the display's luminance),
+ *    k = Y > threshold ? (Y - threshold) / Y : 0, b = s * k per channel.
+ * 3. Down.  d_0 = b, d_l = D(d_{l-1}) for l = 1 .. Le.  D is the mean form of "multi-scale denoising": the four taps of a coarse pixel,
+ *    those outside the image +0, summed as (t00 + t10) + (t01 + t11) and scaled by 1 / k for k taps inside.  Level sizes:
+ *    rt_denoise_level_size.  Le = min(L, the first level whose larger side is 1); Le = 0 for a 1 x 1 image: out = s where c is finite.
+ * 4. Weights (host, f32).  w_1 = 1, w_{l+1} = w_l * spread; W = ((w_1 + w_2) + ..) over l = 1 .. Le in index order; ŵ_l = w_l / W.
+ * 5. Up.  u_Le = ŵ_Le * d_Le; u_l = ŵ_l * d_l + U(u_{l+1}) for l = Le - 1 .. 1; B = U(u_1).  U is the clamped 2x bilinear interpolation
+ *    of "multi-scale denoising": (0.5625f e(X, Y) + 0.1875f e(X', Y)) + (0.1875f e(X, Y') + 0.0625f e(X', Y')).
+ * 6. Combine, per channel.  Every channel of c finite: out = (s - a * b) + a * B.  Otherwise out = c, all three channels unchanged, so
+ *    that the display's non-finite rule and count still see the pixel (its finite, positive channels still glow into its neighbours).
+ * Properties (tests/glare_ref.py restates all of it in numpy; the kernels are held to it bit for bit, and the host tests prove these on
+ * the reference alone):
+ *   A constant image stays that constant, within the 9 Le + 4 f32 roundings on the longest path to `out` (tests/glare_ref.py counts them).
+ *   With threshold 0 the frame's energy is conserved for light that lies at least 2^(Le+1) pixels from every edge of a frame whose
+ *   sides are multiples of 2^Le: D's weights sum to 1 per fine pixel there, U's per coarse pixel.
+ *   At the edges the frame continues with its edge values: U clamps, D averages the taps it has.  An emitter on the edge glows as though
+ *   it went on beyond it, and a pixel in the last row or column of an odd-sized level counts for more than its neighbours — under the
+ *   default glare an impulse in the odd corner (52, 36) of a 53 x 37 frame comes out with 70 % more energy, one in the even corner (0, 0)
+ *   with 0.4 % less (with amount 1 ten times that).  That is a consequence of the border rule and is left as it is.
+ *   out >= 0 wherever c is finite: a b <= b <= s by the monotonicity of rounding.
+ *   amount == 0 gives the out_rgb8 of no glare bit for bit; the f32 `out` differs from c only where c < 0 or c > 2^64 (and in the sign of
+ *   a -0), which the quantisation maps to the same level.
+ *   The point spread of a pixel depends on where it sits in its 2^l blocks: a property of the pyramid, which is not shift invariant.
+ * A shard (shard_count > 1) has no neighbourhoods — its rows are interleaved with other devices': a call that asks for out_rgb8 under a
+ * glare is RT_ERR_STATE there; calls that ask for no out_rgb8 are unaffected.
+ * Not covered, as for the display: rt_render, rt_render_device, the preview of rt_set_progress, and every context of an RtMulti.
+ * Cost: 12 B per pixel for `out` and 8 B for the pyramid; DESIGN.md "Glare". */
+#define RT_GLARE_MAX_LEVELS 8u
+#define RT_GLARE_DEFAULT_LEVELS 6u
+#define RT_GLARE_DEFAULT_AMOUNT 0.1f
+#define RT_GLARE_DEFAULT_SPREAD 0.7f
+typedef struct RtGlare {
+    float amount;    /* a in [0, 1]: the share of the bright pass that leaves its pixel */
+    float spread;    /* in (0, 1]: the weight of a level relative to the next finer one; 1: all levels alike, the widest glow */
+    float threshold; /* finite, >= 0: the luminance below which a pixel does not glow; 0: every pixel does, and energy is conserved */
+    uint32_t levels; /* L in 1 .. RT_GLARE_MAX_LEVELS: the coarsest level's pixels are 2^L wide */
+} RtGlare;
+typedef struct RtGlareInfo {
+    uint32_t levels;                  /* Le */
+    uint32_t coarse_nx, coarse_rows;  /* the size of level Le */
+    uint32_t reserved;                /* 0 */
+} RtGlareInfo;
+/* A per-context setting under the rules of rt_set_display: it does NOT end an open accumulation, and rt_scene_upload leaves it.  `glare`
+ * NULL: no glare.  RT_ERR_INVALID: what rt_glare_check refuses; the glare set before stays in force. */
+int rt_set_glare(RtCtx* ctx, const RtGlare* glare);
+/* GPU-free, no context.  RT_OK, or RT_ERR_INVALID: `glare` NULL, a NaN in any field, amount outside [0, 1], spread outside (0, 1],
+ * threshold negative or not finite, levels 0 or above RT_GLARE_MAX_LEVELS. */
+int rt_glare_check(const RtGlare* glare);
+/* Le and the size of the coarsest level of the last out_rgb8 this context wrote under a glare.  RT_ERR_STATE: there was none. */
+int rt_glare_info(RtCtx* ctx, RtGlareInfo* info);
+/* `out` of that last call: out_rgb_f32 [3 * nx * rows] in the call's row order.  RT_ERR_STATE: there was none. */
+int rt_glare_image(RtCtx* ctx, float* out_rgb_f32);
+
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the
  * world shared read-only (main.rs:72-108); here the scene is replicated on every device, device r renders the image

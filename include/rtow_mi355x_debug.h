@@ -262,6 +262,21 @@ int rt_debug_denoise_multiscale(RtCtx* ctx, uint32_t nx, uint32_t rows, uint32_t
  * No scene and no accumulation is needed.  RT_ERR_INVALID: a NULL array or display, nx * rows outside 1 .. 2^28, or a display
  * rt_display_check refuses. */
 int rt_debug_display(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const RtDisplay* display, uint8_t* out_rgb8, RtDisplayInfo* info);
+/* Test hook for the glare (rtow_mi355x.h "Glare"): the same kernels over a host image in the row order of an out_rgb_f32 — rgb
+ * [3 * nx * rows] — under `glare` and, behind it, `display` (NULL: the reference quantisation); neither is the context's, which the hook
+ * neither reads nor changes, nor does it touch what rt_glare_info, rt_glare_image and rt_display_info return.  out_rgb_f32 [3 * nx * rows]
+ * (may be NULL): `out`; out_rgb8 [3 * nx * rows] (may be NULL), rows flipped as every out_rgb8; `info` (may be NULL): Le and the coarsest
+ * level of this run.  No scene and no accumulation is needed.  RT_ERR_INVALID: a NULL rgb or glare, nx * rows outside 1 .. 2^28, a glare
+ * rt_glare_check refuses or a display rt_display_check refuses. */
+int rt_debug_glare(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const RtGlare* glare, const RtDisplay* display, float* out_rgb_f32,
+                   uint8_t* out_rgb8, RtGlareInfo* info);
+/* Which down chain the glare of this context runs, the hook above and the product calls alike; both give the same bits.
+ * RT_GLARE_CHAIN_AUTO: the library's choice; _PLAIN: one launch per level; _FUSED: levels 1 .. 3 in one launch wherever Le >= 3.
+ * A per-context setting that changes no sample: it does not end an open accumulation.  RT_ERR_INVALID: another value. */
+#define RT_GLARE_CHAIN_AUTO 0u
+#define RT_GLARE_CHAIN_PLAIN 1u
+#define RT_GLARE_CHAIN_FUSED 2u
+int rt_debug_glare_chain(RtCtx* ctx, uint32_t chain);
 
 /* Test hook for adaptive sampling (rtow_mi355x.h "adaptive sampling"): overwrites the two luminance moments (S1, S2) of pixel `pixel` of
  * the open accumulation, `pixel` an index into out_sem (row order of out_rgb_f32).  The tests plant a NaN with it: such a pixel never

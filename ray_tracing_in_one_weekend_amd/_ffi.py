@@ -227,6 +227,26 @@ class RtDisplayInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# rt_set_glare
+GLARE_MAX_LEVELS, GLARE_DEFAULT_LEVELS = 8, 6
+GLARE_DEFAULT_AMOUNT, GLARE_DEFAULT_SPREAD = 0.1, 0.7
+GLARE_CHAIN_AUTO, GLARE_CHAIN_PLAIN, GLARE_CHAIN_FUSED = range(3)  # rt_debug_glare_chain
+
+
+class RtGlare(C.Structure):
+    """rt_set_glare: the share of every pixel's bright pass that a 2x pyramid spreads over its neighbourhood, in front of the display
+    stage of every out_rgb8 of the accumulation family (rtow_mi355x.h "Glare")."""
+    _fields_ = [("amount", C.c_float), ("spread", C.c_float), ("threshold", C.c_float), ("levels", C.c_uint32)]
+
+
+class RtGlareInfo(C.Structure):
+    """rt_glare_info: the effective levels Le and the size of the coarsest level of the last out_rgb8 written under a glare."""
+    _fields_ = [("levels", C.c_uint32), ("coarse_nx", C.c_uint32), ("coarse_rows", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RtBounceIO(C.Structure):
     _fields_ = [("n", C.c_uint32), ("depth", C.c_uint32), ("in_o", _f), ("in_d", _f), ("in_key", _u32),
                 ("out_hit", C.POINTER(C.c_int32)), ("out_t", _f), ("out_radiance", _f), ("out_attenuation", _f),
@@ -291,6 +311,7 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_accum_import_buckets",
                "rt_multi_accum_begin", "rt_multi_accum_add", "rt_multi_accum_add_adaptive", "rt_multi_accum_join", "rt_multi_accum_import", "rt_multi_accum_end",
                "rt_set_display", "rt_display_info", "rt_display_check", "rt_debug_display",
+               "rt_set_glare", "rt_glare_check", "rt_glare_info", "rt_glare_image", "rt_debug_glare", "rt_debug_glare_chain",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
@@ -453,6 +474,18 @@ def load_gpu_library():
     lib.rt_display_check.restype = C.c_int
     lib.rt_debug_display.argtypes = [vp, C.c_uint32, C.c_uint32, _f, C.POINTER(RtDisplay), _u8, C.POINTER(RtDisplayInfo)]
     lib.rt_debug_display.restype = C.c_int
+    lib.rt_set_glare.argtypes = [vp, C.POINTER(RtGlare)]
+    lib.rt_set_glare.restype = C.c_int
+    lib.rt_glare_check.argtypes = [C.POINTER(RtGlare)]
+    lib.rt_glare_check.restype = C.c_int
+    lib.rt_glare_info.argtypes = [vp, C.POINTER(RtGlareInfo)]
+    lib.rt_glare_info.restype = C.c_int
+    lib.rt_glare_image.argtypes = [vp, _f]
+    lib.rt_glare_image.restype = C.c_int
+    lib.rt_debug_glare.argtypes = [vp, C.c_uint32, C.c_uint32, _f, C.POINTER(RtGlare), C.POINTER(RtDisplay), _f, _u8, C.POINTER(RtGlareInfo)]
+    lib.rt_debug_glare.restype = C.c_int
+    lib.rt_debug_glare_chain.argtypes = [vp, C.c_uint32]
+    lib.rt_debug_glare_chain.restype = C.c_int
     lib.rt_debug_planar_info.argtypes =[vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.rt_debug_planar_info.restype = C.c_int
     lib.rt_debug_planar_bounds.argtypes = [C.POINTER(RtQuads), C.c_float, vp, vp]

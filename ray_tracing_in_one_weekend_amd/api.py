@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import RtAdaptive, RtAdaptiveInfo, RtBounceIO, RtCamera, RtDenoise, RtDisplay, RtDisplayInfo, RtFlatScene, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtResidual, RtStats
+from ._ffi import RtAdaptive, RtAdaptiveInfo, RtBounceIO, RtCamera, RtDenoise, RtDisplay, RtDisplayInfo, RtFlatScene, RtGlare, RtGlareInfo, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtResidual, RtStats
 
 
 class RtError(RuntimeError):
@@ -579,6 +579,18 @@ def display_check(display):
     return _ffi.load_gpu_library().rt_display_check(C.byref(display) if display is not None else None) == 0
 
 
+def make_glare(amount=_ffi.GLARE_DEFAULT_AMOUNT, spread=_ffi.GLARE_DEFAULT_SPREAD, threshold=0.0, levels=_ffi.GLARE_DEFAULT_LEVELS):
+    """An RtGlare for Renderer.set_glare: `amount` in [0, 1] of every pixel's bright pass leaves the pixel and is spread by a 2x pyramid of
+    `levels` levels (1 .. 8), each coarser level weighted `spread` (in (0, 1]) times the one below; `threshold` >= 0: the luminance below
+    which a pixel does not glow (0: every pixel does and the frame's energy is conserved)."""
+    return RtGlare(float(amount), float(spread), float(threshold), int(levels))
+
+
+def glare_check(glare):
+    """rt_glare_check (no GPU): True when rt_set_glare would accept the RtGlare."""
+    return _ffi.load_gpu_library().rt_glare_check(C.byref(glare) if glare is not None else None) == 0
+
+
 def denoise_level_size(nx, rows, level):
     """rt_denoise_level_size (no GPU): (nx_l, rows_l) of level `level` of the pyramid accum_denoise_multiscale filters."""
     nx_l, rows_l = C.c_uint32(), C.c_uint32()
@@ -1056,6 +1068,44 @@ class Renderer:
         self._call("rt_debug_display", nx, rows, rgb.ctypes.data_as(C.POINTER(C.c_float)), C.byref(display), out.ctypes.data_as(C.POINTER(C.c_uint8)),
                    C.byref(info))
         return out, info
+
+    def set_glare(self, glare):
+        """rt_set_glare: every rgb8 of accum_read, the accum_denoise* calls and accum_robust is made from the glared image (make_glare) of
+        the f32 image the same call returns — through the display where one is set, else through the reference quantisation; None: no
+        glare.  Does not end an open accumulation; upload() keeps it.  render() and the progress preview are not covered."""
+        self._call("rt_set_glare", C.byref(glare) if glare is not None else None)
+
+    def glare_info(self):
+        """rt_glare_info: the RtGlareInfo (effective levels, size of the coarsest level) of the last rgb8 written under a glare."""
+        info = RtGlareInfo()
+        self._call("rt_glare_info", C.byref(info))
+        return info
+
+    def glare_image(self, nx, rows):
+        """rt_glare_image: the glared linear image [rows, nx, 3] f32 (row 0 at the bottom, as accum_read's img) behind the last rgb8
+        written under a glare; nx and rows are that call's."""
+        out = np.zeros((rows, nx, 3), np.float32)
+        self._call("rt_glare_image", out.ctypes.data_as(C.POINTER(C.c_float)))
+        return out
+
+    def debug_glare(self, rgb, glare, display=None, want_rgb8=True):
+        """rt_debug_glare: the glare kernels over a host image [rows, nx, 3] f32 in the row order of accum_read's img, then `display` (None:
+        the reference quantisation); returns (out [rows, nx, 3] f32, rgb8 [rows, nx, 3] with row 0 on top or None, RtGlareInfo).  Neither
+        reads nor changes the glare and the display set on this Renderer."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        rows, nx = rgb.shape[:2]
+        assert rgb.shape == (rows, nx, 3)
+        out, info = np.zeros((rows, nx, 3), np.float32), RtGlareInfo()
+        u8 = np.zeros((rows, nx, 3), np.uint8) if want_rgb8 else None
+        self._call("rt_debug_glare", nx, rows, rgb.ctypes.data_as(C.POINTER(C.c_float)), C.byref(glare), C.byref(display) if display is not None else None,
+                   out.ctypes.data_as(C.POINTER(C.c_float)), u8.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgb8 else None, C.byref(info))
+        return out, u8, info
+
+    def debug_glare_chain(self, chain):
+        """rt_debug_glare_chain: "auto" | "plain" | "fused" (or the _ffi number): which down chain the glare of this Renderer runs; the
+        same bits either way."""
+        table = {"auto": _ffi.GLARE_CHAIN_AUTO, "plain": _ffi.GLARE_CHAIN_PLAIN, "fused": _ffi.GLARE_CHAIN_FUSED}
+        self._call("rt_debug_glare_chain", table[chain] if isinstance(chain, str) else int(chain))
 
     def set_progress(self, fn):
         """fn(spp_done, spp_total, rgb8[rows, nx, 3]) after every slice but the last of a following render()

@@ -13,6 +13,7 @@
 #include "rt_halves.h"
 #include "rt_buckets.h"
 #include "rt_display.h"
+#include "rt_glare.h"
 #include "rt_bvh.h"
 #include "rt_grid.h"
 #include "rt_pool.h"
@@ -178,6 +179,16 @@ struct RtCtx {
     RtDisplay display_ran{};            // (the display of that run)
     bool has_display_info = false;
     RtDisplayInfo display_info{};       // rt_display_info: the figures of the last out_rgb8 written under a display
+    // rt_set_glare (rt_glare.h): the bloom in front of that transform.  glare_buf: `out` and the d and u levels of the pyramid
+    // (rt_glare_plan.h: glare_plan); glare_debug_buf: the same for rt_debug_glare, which leaves the product's last run alone
+    bool has_glare = false;
+    RtGlare glare{};
+    uint32_t glare_chain = RT_GLARE_CHAIN_AUTO; // rt_debug_glare_chain
+    DevBuf glare_buf, glare_debug_buf;
+    bool has_glare_info = false;
+    RtGlareInfo glare_info{};           // rt_glare_info: Le and the coarsest level of the last out_rgb8 written under a glare
+    const float* glare_out = nullptr;   // rt_glare_image: `out` of that call, in glare_buf, glare_nx x glare_rows
+    uint32_t glare_nx = 0, glare_rows = 0;
     // Host-side timeline of the last trace_samples and what its caller enqueued behind it (rt_debug_render_parts): wall-clock milliseconds between marks.  The first
     // render of a process is where allocations, code-object loads and the queue probe happen; this says which.
     std::vector<std::pair<const char*, double>> parts;
@@ -775,6 +786,7 @@ void rt_ctx_destroy(RtCtx* ctx) {
     if (ctx->h_resid) (void)hipHostFree(ctx->h_resid);
     if (ctx->h_robust) (void)hipHostFree(ctx->h_robust);
     free_buf(ctx->display_buf);
+    free_buf(ctx->glare_buf), free_buf(ctx->glare_debug_buf);
     if (ctx->h_display) (void)hipHostFree(ctx->h_display);
     if (ctx->h_info) (void)hipHostFree(ctx->h_info);
     free_buf(ctx->dn_c), free_buf(ctx->dn_yv), free_buf(ctx->dn_out), free_buf(ctx->dn_ms);
@@ -1503,6 +1515,139 @@ int rt_debug_display(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, c
     return RT_OK;
 }
 
+// ---- glare (rtow_mi355x.h "Glare", csrc/rt_glare.h, csrc/rt_glare_plan.h) --------------------------------------------------------------------
+// `img` (device, f32 x 3 per pixel in the call's row order, nx x rows >= 1 pixels) under the glare `g` into the region `out` of `buf`, on
+// `st`: the down chain — fused (levels 1 .. 3 in one launch) or plain —, the plain kernels for the levels beyond, the up chain from the
+// coarsest level, the combine.  No host wait in between; `info` is host-known.
+// The fused chain where the context's choice is RT_GLARE_CHAIN_AUTO: frames of RT_GLARE_FUSED_MIN_PIXELS and more (DESIGN.md "Glare").
+constexpr uint64_t RT_GLARE_FUSED_MIN_PIXELS = 1ull << 18;
+static int enqueue_glare(RtCtx* ctx, hipStream_t st, const float* img, uint32_t nx, uint32_t rows, const RtGlare& g, DevBuf& buf, const float*& out,
+                         RtGlareInfo& info) {
+    const GlarePlan pl = glare_plan(nx, rows, g);
+    if (const int rc = ensure(ctx, buf, pl.total)) return rc;
+    char* base = buf.as<char>();
+    const auto D = [&](uint32_t l) { return (float*)(base + pl.lv[l].d); };
+    const auto U = [&](uint32_t l) { return (float*)(base + pl.lv[l].u); };
+    const auto grid = [](uint64_t npix) { return dim3((uint32_t)((npix + 255u) / 256u)); };
+    const GlareLevel* lv = pl.lv;
+    const uint32_t le = pl.levels;
+    if (le >= 1u) {
+        const bool fused = le >= 3u && (ctx->glare_chain == RT_GLARE_CHAIN_FUSED || (ctx->glare_chain == RT_GLARE_CHAIN_AUTO && lv[0].npix >= RT_GLARE_FUSED_MIN_PIXELS));
+        uint32_t l;
+        if (fused) {
+            const uint32_t tiles_x = (nx + RT_GLARE_TILE_X - 1u) / RT_GLARE_TILE_X, tiles_y = (rows + RT_GLARE_TILE_Y - 1u) / RT_GLARE_TILE_Y;
+            hipLaunchKernelGGL(k_glare_down3, dim3(tiles_x * tiles_y), dim3(256), 0, st, img, D(1), D(2), D(3), nx, rows, lv[1].nx, lv[1].rows, lv[2].nx, lv[2].rows,
+                               lv[3].nx, lv[3].rows, tiles_x, g.threshold);
+            l = 3u;
+        } else {
+            hipLaunchKernelGGL(k_glare_bright_down, grid(lv[1].npix), dim3(256), 0, st, img, D(1), nx, rows, lv[1].nx, lv[1].rows, g.threshold);
+            l = 1u;
+        }
+        for (; l < le; ++l)
+            hipLaunchKernelGGL(k_glare_down, grid(lv[l + 1u].npix), dim3(256), 0, st, (const float*)D(l), D(l + 1u), lv[l].nx, lv[l].rows, lv[l + 1u].nx, lv[l + 1u].rows);
+        for (l = le; l >= 1u; --l) {
+            const bool top = l == le;
+            hipLaunchKernelGGL(k_glare_up, grid(lv[l].npix), dim3(256), 0, st, (const float*)D(l), top ? (const float*)nullptr : (const float*)U(l + 1u), U(l), lv[l].w,
+                               lv[l].nx, lv[l].rows, top ? 0u : lv[l + 1u].nx, top ? 0u : lv[l + 1u].rows);
+        }
+    }
+    float* o = (float*)(base + pl.out);
+    hipLaunchKernelGGL(k_glare_combine, grid(lv[0].npix), dim3(256), 0, st, img, le ? (const float*)U(1) : (const float*)nullptr, o, nx, rows, le ? lv[1].nx : 0u,
+                       le ? lv[1].rows : 0u, g.amount, g.threshold);
+    RT_HIP(ctx, hipGetLastError());
+    info = RtGlareInfo{le, lv[le].nx, lv[le].rows, 0u};
+    out = o;
+    return RT_OK;
+}
+// `out` into ctx->out_u8, which the caller has ensured: through `display` where there is one, else through k_finalize's quantisation and
+// flip — row-major, / (float)1 changes no bit —, which is the display of the identity configuration.
+static int enqueue_glare_display(RtCtx* ctx, hipStream_t st, const float* out, uint32_t nx, uint32_t rows, const RtDisplay* display) {
+    if (display) return enqueue_display(ctx, st, out, nx, rows, *display);
+    hipLaunchKernelGGL(k_finalize<false>, dim3((nx * rows + 255u) / 256u), dim3(256), 0, st, out, (const uint32_t*)nullptr, (float*)nullptr, ctx->out_u8.as<uint8_t>(), nx, rows,
+                       1u, 0u, 0u);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+// What stands behind an out_rgb8 of the accumulation family where a glare or a display is set: `img` through the context's glare, then the
+// context's display or the reference quantisation, into ctx->out_u8.  The caller's wait for `st` is followed by display_commit.
+static int enqueue_presentation(RtCtx* ctx, hipStream_t st, const float* img, uint32_t nx, uint32_t rows) {
+    if (!ctx->has_glare) return enqueue_display(ctx, st, img, nx, rows, ctx->display);
+    const float* out = nullptr;
+    RtGlareInfo info{};
+    if (const int rc = enqueue_glare(ctx, st, img, nx, rows, ctx->glare, ctx->glare_buf, out, info)) return rc;
+    ctx->glare_info = info, ctx->has_glare_info = true, ctx->glare_out = out, ctx->glare_nx = nx, ctx->glare_rows = rows;
+    return enqueue_glare_display(ctx, st, out, nx, rows, ctx->has_display ? &ctx->display : nullptr);
+}
+// A shard has no neighbourhoods: RT_ERR_STATE for a call `who` that asks for out_rgb8 under a glare on one.
+static int refuse_glare_on_shard(RtCtx* ctx, const char* who, const uint8_t* out_rgb8) {
+    if (out_rgb8 && ctx->has_glare && ctx->accum.prm.shard_count > 1u)
+        return fail(ctx, RT_ERR_STATE, std::string(who) + ": out_rgb8 under a glare (rt_set_glare) on a sharded accumulation (shard_count > 1): a row-interleaved shard has "
+                                                          "no neighbourhoods");
+    return RT_OK;
+}
+
+int rt_glare_check(const RtGlare* glare) { return glare_invalid(glare) ? RT_ERR_INVALID : RT_OK; }
+int rt_set_glare(RtCtx* ctx, const RtGlare* glare) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!glare) {
+        ctx->has_glare = false;
+        return RT_OK;
+    }
+    if (const char* why = glare_invalid(glare)) return fail(ctx, RT_ERR_INVALID, std::string("rt_set_glare: ") + why);
+    ctx->glare = *glare, ctx->has_glare = true;
+    return RT_OK;
+}
+int rt_glare_info(RtCtx* ctx, RtGlareInfo* info) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!info) return fail(ctx, RT_ERR_INVALID, "rt_glare_info: info is NULL");
+    if (!ctx->has_glare_info) return fail(ctx, RT_ERR_STATE, "rt_glare_info: no out_rgb8 was written under a glare yet (rt_set_glare)");
+    *info = ctx->glare_info;
+    return RT_OK;
+}
+int rt_glare_image(RtCtx* ctx, float* out_rgb_f32) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!out_rgb_f32) return fail(ctx, RT_ERR_INVALID, "rt_glare_image: out_rgb_f32 is NULL");
+    if (!ctx->has_glare_info) return fail(ctx, RT_ERR_STATE, "rt_glare_image: no out_rgb8 was written under a glare yet (rt_set_glare)");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->glare_out, (size_t)ctx->glare_nx * ctx->glare_rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+int rt_debug_glare_chain(RtCtx* ctx, uint32_t chain) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (chain > RT_GLARE_CHAIN_FUSED) return fail(ctx, RT_ERR_INVALID, "rt_debug_glare_chain: chain must be RT_GLARE_CHAIN_AUTO, _PLAIN or _FUSED");
+    ctx->glare_chain = chain;
+    return RT_OK;
+}
+int rt_debug_glare(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const RtGlare* glare, const RtDisplay* display, float* out_rgb_f32, uint8_t* out_rgb8,
+                   RtGlareInfo* info) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (!rgb) return fail(ctx, RT_ERR_INVALID, "rt_debug_glare: rgb is NULL");
+    if (nx == 0u || rows == 0u || (uint64_t)nx * rows > (1ull << 28)) return fail(ctx, RT_ERR_INVALID, "rt_debug_glare: nx * rows must be 1 .. 2^28");
+    if (const char* why = glare_invalid(glare)) return fail(ctx, RT_ERR_INVALID, std::string("rt_debug_glare: ") + why);
+    if (display)
+        if (const char* why = display_invalid(display)) return fail(ctx, RT_ERR_INVALID, std::string("rt_debug_glare: ") + why);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)nx * rows * 3;
+    int rc;
+    if ((rc = ensure(ctx, ctx->out_f32, n * sizeof(float))) || (rc = ensure(ctx, ctx->out_u8, n))) return rc;
+    const hipStream_t st = ctx->stream;
+    RT_HIP(ctx, hipMemcpyAsync(ctx->out_f32.p, rgb, n * sizeof(float), hipMemcpyHostToDevice, st));
+    const float* out = nullptr;
+    RtGlareInfo ran{};
+    if ((rc = enqueue_glare(ctx, st, ctx->out_f32.as<const float>(), nx, rows, *glare, ctx->glare_debug_buf, out, ran))) return rc;
+    if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, out, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    const bool was_pending = ctx->display_pending; // (false, as in rt_debug_display)
+    if (out_rgb8) {
+        if ((rc = enqueue_glare_display(ctx, st, out, nx, rows, display))) return rc;
+        RT_HIP(ctx, hipMemcpyAsync(out_rgb8, ctx->out_u8.p, n, hipMemcpyDeviceToHost, st));
+    }
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    ctx->display_pending = was_pending;
+    if (info) *info = ran;
+    return RT_OK;
+}
+
 int rt_accum_begin(RtCtx* ctx, const RtCamera* cam, const RtParams* prm, uint32_t first_sample) {
     int rc = ctx ? refuse_mirror(ctx, "rt_accum_begin") : RT_OK; // (before the scene is asked for: the mirror has none)
     if (rc || (rc = check_params(ctx, cam, prm))) return rc;
@@ -1599,6 +1744,7 @@ int rt_accum_read(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_
     int rc = require_open(ctx, "rt_accum_read");
     if (rc) return rc;
     const RtCtx::Accum& a = ctx->accum;
+    if ((rc = refuse_glare_on_shard(ctx, "rt_accum_read", out_rgb8))) return rc;
     if (a.npix == 0u) {
         if (noise) fill_noise(ctx, noise);
         return RT_OK;
@@ -1607,7 +1753,7 @@ int rt_accum_read(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_
     const hipStream_t st = ctx->stream;
     const uint32_t npix = a.npix;
     const size_t n = (size_t)npix * 3;
-    const bool displayed = out_rgb8 && ctx->has_display; // the f32 image is then written whoever asks for it: the display kernels read it
+    const bool displayed = out_rgb8 && (ctx->has_display || ctx->has_glare); // the f32 image is then written whoever asks for it: the glare and display kernels read it
     if ((out_rgb_f32 || displayed) && (rc = ensure(ctx, ctx->out_f32, n * sizeof(float)))) return rc;
     if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, n))) return rc;
     if (out_sem && (rc = ensure(ctx, ctx->accum_sem, (size_t)npix * sizeof(float)))) return rc;
@@ -1615,7 +1761,7 @@ int rt_accum_read(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_
     if (out_rgb_f32 || out_rgb8) // (a uniform accumulation before the first add: the sums are zeros, divided by 1, not by 0)
         ACCUM_READER(k_finalize, r, ctx->accum_sum.as<const float>(), r.cnt, out_rgb_f32 || displayed ? ctx->out_f32.as<float>() : nullptr,
                      out_rgb8 && !displayed ? ctx->out_u8.as<uint8_t>() : nullptr, r.nx, r.rows, std::max(r.n, 1u), r.tiles_per_row, r.tile_pixels);
-    if (displayed && (rc = enqueue_display(ctx, st, ctx->out_f32.as<const float>(), a.nx, a.rows, ctx->display))) return rc;
+    if (displayed && (rc = enqueue_presentation(ctx, st, ctx->out_f32.as<const float>(), a.nx, a.rows))) return rc;
     if (out_sem)
         ACCUM_READER(k_sem, r, ctx->accum_mom.as<const double2>(), r.cnt, ctx->accum_sem.as<float>(), (uint32_t*)nullptr, r.nx, r.rows, r.n, r.tiles_per_row,
                      r.tile_pixels);
@@ -1786,14 +1932,14 @@ static int ensure_nlm(RtCtx* ctx, size_t npix, uint32_t planes) {
 }
 
 // Their shared end: the filtered image `img` (device, image order) through k_finalize's quantisation and flip into ctx->out_u8 where rgb8 is
-// asked — row-major (no tiles), and / (float)1 changes no bit — or through the context's display (rt_set_display) in its place, and the
+// asked — row-major (no tiles), and / (float)1 changes no bit — or through the context's glare and display (enqueue_presentation), and the
 // copies to the host, enqueued on the context's stream.  The caller's wait for the stream is followed by display_commit.
 static int denoise_finish(RtCtx* ctx, const float* img, float* out_rgb_f32, uint8_t* out_rgb8) {
     const RtCtx::Accum& a = ctx->accum;
     const hipStream_t st = ctx->stream;
     const size_t n = (size_t)a.npix * 3;
-    if (out_rgb8 && ctx->has_display) {
-        if (const int rc = enqueue_display(ctx, st, img, a.nx, a.rows, ctx->display)) return rc;
+    if (out_rgb8 && (ctx->has_display || ctx->has_glare)) {
+        if (const int rc = enqueue_presentation(ctx, st, img, a.nx, a.rows)) return rc;
     } else if (out_rgb8)
         hipLaunchKernelGGL(k_finalize<false>, dim3((a.npix + 255u) / 256u), dim3(256), 0, st, img, (const uint32_t*)nullptr, (float*)nullptr, ctx->out_u8.as<uint8_t>(), a.nx,
                            a.rows, 1u, 0u, 0u);
@@ -2382,6 +2528,7 @@ int rt_accum_read_robust(RtCtx* ctx, const RtRobust* rb, float* out_rgb_f32, uin
     const RtCtx::Accum& a = ctx->accum;
     RtRobust r;
     if ((rc = robust_begin(ctx, "rt_accum_read_robust", rb, r))) return rc;
+    if ((rc = refuse_glare_on_shard(ctx, "rt_accum_read_robust", out_rgb8))) return rc;
     if (info) std::memset(info, 0, sizeof(*info));
     if (a.npix == 0u || (!out_rgb_f32 && !out_rgb8 && !out_trim && !info)) return RT_OK;
     RT_HIP(ctx, hipSetDevice(ctx->device));

@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from . import AccumBuckets, AccumState, MultiRenderer, Renderer, RtError, Scene, display_check, make_display, make_params, output_file_name, register_default_images, save_png
+from . import AccumBuckets, AccumState, MultiRenderer, Renderer, RtError, Scene, display_check, glare_check, make_display, make_glare, make_params, output_file_name, register_default_images, save_png
 from . import _ffi
 from .images import write_pfm
 
@@ -184,6 +184,15 @@ def main(argv=None):
     ap.add_argument("--hdr-out", default=None, metavar="FILE.pfm",
                     help="also write the linear f32 image as a PFM (a plain render only: not with --noise-target, --adaptive-tolerance, "
                          "--denoise, --checkpoint and their kin)")
+    ap.add_argument("--glare", type=float, default=None, metavar="A",
+                    help="glare (rt_set_glare): the share A in [0, 1] of every pixel's light that a 2x image pyramid spreads over its "
+                         "neighbourhood before the 8-bit step, so that a bright light looks bright; the frame's energy is kept")
+    ap.add_argument("--glare-levels", type=int, default=_ffi.GLARE_DEFAULT_LEVELS, metavar="L", help="with --glare: levels of the pyramid, 1..8; the glow is about 2^L pixels wide")
+    ap.add_argument("--glare-spread", type=float, default=_ffi.GLARE_DEFAULT_SPREAD, metavar="S",
+                    help="with --glare: the weight of each coarser level relative to the one below, in (0, 1]; 1 is the widest glow")
+    ap.add_argument("--glare-threshold", type=float, default=0.0, metavar="T", help="with --glare: only the luminance above T glows (0: all of it)")
+    ap.add_argument("--glare-out", default=None, metavar="FILE.pfm",
+                    help="with --glare: also write the glared linear f32 image as a PFM (a plain render only, as --hdr-out, which stays the un-glared frame)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--devices", default=None, metavar="ID,ID,...",
                     help="render on these devices of the node at once (rt_multi_*): every device takes row-interleaved bands of the frame; the "
@@ -238,6 +247,17 @@ def main(argv=None):
             ap.error("--exposure, --auto-exposure, --tone, --srgb and --dither do not combine with --devices or --preview-every "
                      "(rt_multi_* and the progress preview keep the reference quantisation)")
         rend.set_display(display)
+    # the glare: set once on the context as well, in front of that display (or of the reference quantisation)
+    glare = None
+    if a.glare is not None:
+        glare = make_glare(a.glare, a.glare_spread, a.glare_threshold, a.glare_levels if 0 <= a.glare_levels < 2 ** 32 else 0)
+        if not glare_check(glare):
+            ap.error("--glare takes 0..1, --glare-levels 1..%d, --glare-spread a value in (0, 1], --glare-threshold a finite value >= 0" % _ffi.GLARE_MAX_LEVELS)
+        if multi or a.preview_every:
+            ap.error("--glare does not combine with --devices or --preview-every (rt_multi_* and the progress preview keep the reference quantisation)")
+        rend.set_glare(glare)
+    elif a.glare_out:
+        ap.error("--glare-out needs --glare")
     halves = a.residual_target is not None or (a.denoise and a.denoise_guide == "halves")
     if a.denoise_levels is not None:
         if not a.denoise or a.denoise_guide == "halves" or a.residual_target is not None:
@@ -263,8 +283,8 @@ def main(argv=None):
     if a.firefly_map and not a.robust_mode:
         ap.error("--firefly-map needs --robust")
     if halves:
-        if a.hdr_out:
-            ap.error("--hdr-out writes the image of a plain render: it does not combine with the progressive options")
+        if a.hdr_out or a.glare_out:
+            ap.error("--hdr-out and --glare-out write the image of a plain render: they do not combine with the progressive options")
         if a.checkpoint or a.resume or a.merge:
             ap.error("--denoise-guide halves and --residual-target do not combine with --checkpoint, --resume or --merge")
         if a.first_sample is not None or a.adaptive_tolerance is not None or a.noise_target is not None or a.preview_every:
@@ -275,8 +295,8 @@ def main(argv=None):
             ap.error("the cross filter needs --spp >= 4: two samples per half")
         return render_halves(a, rend, scene, flags, file_name, t0)
     progressive = a.adaptive_tolerance is not None or a.noise_target is not None or a.denoise
-    if a.hdr_out and (progressive or halves or a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets):
-        ap.error("--hdr-out writes the image of a plain render: it does not combine with the progressive options")
+    if (a.hdr_out or a.glare_out) and (progressive or halves or a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets):
+        ap.error("--hdr-out and --glare-out write the image of a plain render: they do not combine with the progressive options")
     if a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets or (multi and progressive):
         if a.preview_every:
             ap.error("--checkpoint, --resume, --first-sample and --merge do not combine with --preview-every")
@@ -294,18 +314,26 @@ def main(argv=None):
     if a.denoise:
         return render_denoised(a, rend, scene, flags, file_name, t0)
     params = make_params(a.nx, ny, a.spp, max_depth=a.max_depth, seed=a.seed, spp_slice=a.preview_every, flags=flags)
-    if display is not None:  # through an accumulation: begin / add / read; its f32 image is rt_render's, bit for bit
+    if display is not None or glare is not None:  # through an accumulation: begin / add / read; its f32 image is rt_render's, bit for bit
         rend.accum_begin(scene.camera, params)
         st = rend.accum_add(a.spp)
         img, rgb8, _, _ = rend.accum_read(want_rgb8=True)
         rend.accum_end()
-        info = rend.display_info()
         print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
         save_png(file_name, rgb8)
         if a.hdr_out:
             write_pfm(a.hdr_out, img)
-        print(f"{file_name}: {a.nx}x{ny}, {a.spp} spp, {st.n_rays} rays, {st.n_rays / st.seconds_device / 1e6:.0f} Mray/s on the device; display: exposure "
-              f"{info.exposure:.4g}, {info.n_saturated} of {rgb8.size} values at 255, {info.n_non_finite} non-finite pixels", file=sys.stderr)
+        if a.glare_out:
+            write_pfm(a.glare_out, rend.glare_image(a.nx, ny))
+        notes = ""
+        if glare is not None:
+            g = rend.glare_info()
+            notes += f"; glare: {g.levels} levels, the coarsest {g.coarse_nx}x{g.coarse_rows}"
+        if display is not None:
+            info = rend.display_info()
+            notes += (f"; display: exposure {info.exposure:.4g}, {info.n_saturated} of {rgb8.size} values at 255, "
+                      f"{info.n_non_finite} non-finite pixels")
+        print(f"{file_name}: {a.nx}x{ny}, {a.spp} spp, {st.n_rays} rays, {st.n_rays / st.seconds_device / 1e6:.0f} Mray/s on the device{notes}", file=sys.stderr)
         return 0
     if a.preview_every:
         def progress(done, total, rgb8):
