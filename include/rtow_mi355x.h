@@ -794,6 +794,85 @@ int rt_accum_export_halves(RtCtx* ctx, RtAccumHalves* hs);
  * accumulation's.  A failed call leaves the accumulation as it was.  Synchronises once. */
 int rt_accum_import_halves(RtCtx* ctx, const RtAccumHalves* hs);
 
+/* -- selected strength: the strength of the cross filter chosen per pixel from the half buffers --------------------------------------------
+ * The best strength of "Half buffers" differs from frame to frame and, within a frame, from a flat wall to a contact shadow; and
+ * residual_rms there "does not see the blur both halves share".  Both gaps close with what a tracking accumulation already owns: half
+ * 1 - h is an independent, unbiased, noisy picture of the truth, so (l(f_h) - y_{1-h})^2 - v_{1-h} estimates the squared error of half h's
+ * filtered value, BIAS INCLUDED — the dual-buffer cross-validation of Rousselle, Knaus, Zwicker 2012 / Rousselle, Manzi, Zwicker 2013.
+ * It is evaluated for K candidate strengths, smoothed, the smallest picked per pixel, and the candidates blended.  New kernels only,
+ * around the unchanged filter.  Every operation is one IEEE f32 operation in the order written, no FMA; f64 only in the frame figures.
+ * Parameters (RtSelect).  K = n_strengths, 2 .. RT_SELECT_MAX; k_0 < k_1 < .. < k_{K-1} = strength[0 .. K-1], finite and > 0 (the
+ *   entries past K are not looked at);  R = radius and F = patch as in RtDenoise;  S = error_radius and T = blend_radius, 0 .. 4 each;
+ *   reserved 0.
+ * With c_h, y_h, v_h, n_h, a_h, l() and "combine" exactly as "Half buffers" defines them:
+ *   1. Candidates.  For j = 0 .. K-1:  f_{j,h} = the cross filter of "Half buffers" word for word with the strength k_j;
+ *      out_j = combine(f_{j,0}, f_{j,1}).  out_j is, bit for bit, what rt_accum_denoise_halves returns at the strength k_j.
+ *   2. Error.  r = l(f_{j,h}) - y_{1-h};  E_{j,h} = r * r - v_{1-h};  E_j = 0.5f * (E_{j,0} + E_{j,1}).  Pixel q is USABLE when E_j(q) is
+ *      finite for every j (a pixel with an n_h < 2 has a NaN guide and is not).
+ *   3. Smoothing.  B_j(p) = sum_{oy = -S..S} ( sum_{ox = -S..S} E_j(clamp(p + o)) ), row sums first, each sum from +0.0f, coordinates
+ *      clamped to the image per axis.  The terms of pixels that are not usable are skipped, not added as 0 * x.  U(p) = the number of
+ *      usable terms.
+ *   4. Choice.  s = K-1, best = B_{K-1};  for j = K-2 down to 0: if (B_j < best) { s = j; best = B_j; }.  Ties go to the stronger filter,
+ *      and a window without a usable pixel gives K-1.
+ *   5. Blend.  W_j(p) = the number of o in [-T, T]^2 with s(clamp(p + o)) = j, an integer.  Per channel
+ *      out(p) = ( sum over j in increasing order, W_j != 0 only, of (float)W_j * out_j(p) ) / (float)((2T+1)*(2T+1)); the sum starts with
+ *      its first term (not with 0), so that with T = 0 out(p) = out_{s(p)}(p) in every bit.
+ * Outputs.  out_index[p] = s(p);  out_est[p] = B_{s(p)}(p) / (float)U(p), NaN where U(p) = 0.
+ * Frame figures (RtSelectInfo), in f64 over the pixels in image order, on the fixed tree of "Moments" (per workgroup of 256 pixels, then
+ * one workgroup over the partial sums in index order; no floating-point atomics; a pixel that is not usable adds 0.0):
+ *   est_mse[j] = sum_usable (double)E_j / usable;   est_mse_selected = sum_usable (double)E_{s(p)}(p) / usable;
+ *   chosen[j] = the number of pixels with s(p) = j;   usable = the number of usable pixels;
+ *   best = the argmin of est_mse, by the rule of step 4 (ties to the larger j): the frame-wide choice a host can hand to
+ *   rt_accum_denoise_halves.  Entries j >= K are 0.  usable = 0: the figures are NaN and best = K-1.
+ * WHAT THE FIGURE IS.  E estimates the LUMINANCE error of a HALF filter (n/2 samples) against the truth, blur included; the combined
+ * frame is better by the variance the halves do not share.  It is unbiased only as far as the weights of f_{j,h} are independent of
+ * half 1 - h's noise — and they are chosen from that half's guide, so the term -v under-corrects where the filter follows the guide's
+ * noise.  est_mse_selected is biased low by the minimum taken in step 4.  DIFFERENCES between candidates are far better determined than
+ * the values themselves, because the noise of y_{1-h} is common to all of them and cancels; on small frames with heavy-tailed samples
+ * the values scatter by an order of magnitude around the truth while the order of the candidates holds.
+ * A NON-FINITE SAMPLE: the half that holds it carries it to the pixels within R, as "Half buffers" says; every such pixel has a
+ * non-finite E_j, is not usable, is left out of the windows of step 3 and of the frame figures, and takes the choice of its usable
+ * neighbours; out is non-finite there, as every out_j is.
+ * MEASURED on two rendered frames (cornell_box 64 x 64, 16 spp, with and without a light set; DESIGN.md "Selected strength"), RMSE of
+ * rt_accum_denoise_halves at each strength, of the selection from all four with S 2, T 1, and of the selection with the defaults:
+ *                      0.45      0.7       1.0       1.4     four, S 2, T 1   (0.7, 1.0, 1.4), S 0, T 1
+ *   with the lights  0.09132   0.07848   0.07084   0.07490      0.07703              0.07078
+ *   without          0.10343   0.09295   0.09252   0.09701      0.09476              0.08995
+ * THE SELECTION FROM THE FOUR IS NOT BETTER THAN THE BEST SINGLE CANDIDATE: 8.7 % and 2.4 % worse than it, though never as bad as a wrong
+ * strength.  The weakest candidate is chosen by 30 % and 55 % of the pixels: where a filter follows its own half's noise the -v term
+ * under-corrects in its favour.  est_mse is within 3 to 31 % of the true luminance MSE of the half filters; `best` names the truly best
+ * candidate with the lights and the second best (0.5 % behind in RMSE) without.  The defaults of a NULL `sel` are the one choice among
+ * the candidate sets and windows measured that is more than 5 % better than (four, S 2, T 1) on both frames (8.1 % and 5.1 %); it is 0.1 %
+ * and 2.8 % better than the best single candidate.  Two small frames decide this: a host that knows its frames passes its own RtSelect.
+ * Across devices: the joined context of rt_multi_accum_join.  Not covered: selection for the luminance-, channel- or robust-guided
+ * filters or on the pyramid; candidates that differ in radius or patch; sharded frames (RT_ERR_UNSUPPORTED, as rt_accum_denoise). */
+#define RT_SELECT_MAX 4u
+#define RT_SELECT_MAX_WINDOW 4u /* error_radius and blend_radius at the most */
+typedef struct RtSelect {
+    uint32_t n_strengths;  /* K: 2 .. RT_SELECT_MAX */
+    float strength[4];     /* RT_SELECT_MAX of them; strictly increasing over the first K */
+    uint32_t radius, patch;               /* as RtDenoise */
+    uint32_t error_radius, blend_radius;  /* S, T: 0 .. RT_SELECT_MAX_WINDOW */
+    uint32_t reserved;     /* 0 */
+} RtSelect;
+typedef struct RtSelectInfo {
+    double est_mse[4];        /* per candidate: the mean of E_j over the usable pixels */
+    double est_mse_selected;  /* the mean of E_{s(p)}(p): biased low by the minimum */
+    uint32_t chosen[4];       /* pixels with s(p) = j */
+    uint32_t usable, best;    /* usable pixels; the argmin of est_mse, ties to the larger j */
+    uint32_t reserved[2];
+} RtSelectInfo;
+/* GPU-free.  RT_OK, or RT_ERR_INVALID unless `sel` is NULL (the defaults) or within the ranges above. */
+int rt_select_check(const RtSelect* sel);
+/* The selection above on the open accumulation.  `sel` NULL: strengths 0.7, 1.0, 1.4, radius 5, patch 1, error_radius 0,
+ * blend_radius 1 (chosen by measurement on rendered frames: DESIGN.md "Selected strength").  out_rgb_f32 and out_rgb8 as rt_accum_denoise writes them (out_rgb8 through the context's glare and display where
+ * set); out_index [rows_local*nx] = s(p) and out_est [rows_local*nx] in the row order of out_rgb_f32; every output may be NULL.  The
+ * accumulation is read and not changed.  Synchronises the context's stream once.  The errors of rt_accum_denoise_halves: RT_ERR_STATE
+ * without an open accumulation that tracks halves or below 4 samples; RT_ERR_UNSUPPORTED on shard_count > 1; RT_ERR_INVALID where
+ * rt_select_check refuses `sel`; a failed call writes nothing.  A shard without pixels: RT_OK, nothing is written. */
+int rt_accum_denoise_select(RtCtx* ctx, const RtSelect* sel, float* out_rgb_f32, uint8_t* out_rgb8, uint8_t* out_index, float* out_est,
+                            RtSelectInfo* info);
+
 /* -- sample buckets: M sums per pixel by sample index, and the median-of-means read-out that tames a firefly --------------------------------
  * Every read-out above is the plain mean sum / n, so one sample a thousand times brighter than its neighbours — a caustic path, a small
  * emitter found by chance, a NaN out of a degenerate bounce — owns its pixel for thousands of further samples, and the variance-guided

@@ -256,6 +256,24 @@ int rt_debug_denoise_channels(RtCtx* ctx, uint32_t nx, uint32_t rows, const floa
 int rt_debug_denoise_multiscale(RtCtx* ctx, uint32_t nx, uint32_t rows, uint32_t guide, const float* rgb, const float* mean, const float* var,
                                 const RtDenoise* dn, uint32_t levels, float* out_rgb_f32, uint32_t probe_level, float* probe_rgb,
                                 float* probe_mean, float* probe_var);
+/* Test hook for rt_accum_denoise_select (rtow_mi355x.h "selected strength"): the same kernels over host arrays in image order.  c0 and
+ * c1 [3 * nx * rows] = c_0 and c_1; yv0 and yv1 [2 * nx * rows] = (y_h, v_h) per pixel, interleaved, NaN where the half has no variance.
+ * The sample counts n_h follow from (first_sample, n) as in "Half buffers", with n = counts[p] per pixel where `counts` [nx * rows] is not
+ * NULL.  `sel` as rt_accum_denoise_select reads it (NULL: the defaults).  out_rgb_f32 [3 * nx * rows], out_index and out_est [nx * rows]
+ * and `info` as that call writes them, each may be NULL.  The probe arrays that are not NULL receive out_j [3 * nx * rows] and E_j
+ * [nx * rows] of the candidate j = probe_candidate < K — so that a wrong candidate shows apart from a wrong choice or blend.  No scene and
+ * no accumulation is needed.  RT_ERR_INVALID: a NULL input array, nx * rows outside 1 .. 2^28, an RtSelect rt_select_check refuses, a probe
+ * array with probe_candidate >= K. */
+int rt_debug_denoise_select(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* c0, const float* c1, const float* yv0, const float* yv1,
+                            const uint32_t* counts, uint32_t first_sample, uint32_t n, const RtSelect* sel, float* out_rgb_f32,
+                            uint8_t* out_index, float* out_est, RtSelectInfo* info, uint32_t probe_candidate, float* probe_out, float* probe_err);
+/* Which filter chain the selection of this context runs, the hook above and the product call alike; both give the same bits.
+ * RT_SELECT_CHAIN_AUTO: the library's choice; _PLAIN: 2 K launches of the filter of "Denoising"; _FUSED: one launch per half that filters
+ * with all K strengths.  A per-context setting that changes no sample: it does not end an open accumulation.  RT_ERR_INVALID: another value. */
+#define RT_SELECT_CHAIN_AUTO 0u
+#define RT_SELECT_CHAIN_PLAIN 1u
+#define RT_SELECT_CHAIN_FUSED 2u
+int rt_debug_select_chain(RtCtx* ctx, uint32_t chain);
 /* Test hook for the display transform (rtow_mi355x.h "display transform"): the same kernels over a host image in the row order of an
  * out_rgb_f32 — rgb [3 * nx * rows] — under `display` (not the context's, which it neither reads nor changes; nor does it touch what
  * rt_display_info returns); out_rgb8 [3 * nx * rows], rows flipped as every out_rgb8, and `info` (may be NULL) the figures of this run.

@@ -180,6 +180,29 @@ class RtAccumHalves(C.Structure):
                 ("frame_id", C.c_uint64), ("sum", _f * 2), ("moments", C.POINTER(C.c_double) * 2)]
 
 
+SELECT_MAX, SELECT_MAX_WINDOW = 4, 4  # RT_SELECT_MAX, RT_SELECT_MAX_WINDOW
+SELECT_CHAIN_AUTO, SELECT_CHAIN_PLAIN, SELECT_CHAIN_FUSED = range(3)  # rt_debug_select_chain
+SELECT_DEFAULT_STRENGTHS = (0.7, 1.0, 1.4)  # `sel` NULL of rt_accum_denoise_select, with radius 5, patch 1, error_radius 0, blend_radius 1
+
+
+class RtSelect(C.Structure):
+    """rt_accum_denoise_select: the candidate strengths of the cross filter, its window and patch, and the radii of the window the error
+    estimate is smoothed over and of the one the choice is blended over (rtow_mi355x.h "selected strength")."""
+    _fields_ = [("n_strengths", C.c_uint32), ("strength", C.c_float * 4), ("radius", C.c_uint32), ("patch", C.c_uint32),
+                ("error_radius", C.c_uint32), ("blend_radius", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RtSelectInfo(C.Structure):
+    """rt_accum_denoise_select: per candidate the estimated luminance MSE of a half filter over the usable pixels, that of the selection
+    (biased low by the minimum), how many pixels chose each candidate, and `best`, the frame-wide choice."""
+    _fields_ = [("est_mse", C.c_double * 4), ("est_mse_selected", C.c_double), ("chosen", C.c_uint32 * 4), ("usable", C.c_uint32),
+                ("best", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {"est_mse": list(self.est_mse), "est_mse_selected": self.est_mse_selected, "chosen": list(self.chosen), "usable": self.usable,
+                "best": self.best}
+
+
 BUCKETS_MAX = 16  # RT_BUCKETS_MAX
 ROBUST_GINI, ROBUST_MEDIAN, ROBUST_TRIM = 0, 1, 2  # RT_ROBUST_*
 
@@ -307,6 +330,7 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_accum_frame_id", "rt_accum_state_check", "rt_accum_export", "rt_accum_import", "rt_accum_merge",
                "rt_accum_track_halves", "rt_accum_read_halves", "rt_accum_denoise_halves", "rt_accum_halves_check", "rt_accum_export_halves",
                "rt_accum_import_halves",
+               "rt_select_check", "rt_accum_denoise_select", "rt_debug_denoise_select", "rt_debug_select_chain",
                "rt_accum_track_buckets", "rt_accum_read_robust", "rt_accum_denoise_robust", "rt_accum_buckets_check", "rt_accum_export_buckets",
                "rt_accum_import_buckets",
                "rt_multi_accum_begin", "rt_multi_accum_add", "rt_multi_accum_add_adaptive", "rt_multi_accum_join", "rt_multi_accum_import", "rt_multi_accum_end",
@@ -454,6 +478,15 @@ def load_gpu_library():
     lib.rt_accum_export_halves.restype = C.c_int
     lib.rt_accum_import_halves.argtypes = [vp, C.POINTER(RtAccumHalves)]
     lib.rt_accum_import_halves.restype = C.c_int
+    lib.rt_select_check.argtypes = [C.POINTER(RtSelect)]
+    lib.rt_select_check.restype = C.c_int
+    lib.rt_accum_denoise_select.argtypes = [vp, C.POINTER(RtSelect), _f, _u8, _u8, _f, C.POINTER(RtSelectInfo)]
+    lib.rt_accum_denoise_select.restype = C.c_int
+    lib.rt_debug_denoise_select.argtypes = [vp, C.c_uint32, C.c_uint32, _f, _f, _f, _f, _u32, C.c_uint32, C.c_uint32, C.POINTER(RtSelect), _f, _u8, _f,
+                                            C.POINTER(RtSelectInfo), C.c_uint32, _f, _f]
+    lib.rt_debug_denoise_select.restype = C.c_int
+    lib.rt_debug_select_chain.argtypes = [vp, C.c_uint32]
+    lib.rt_debug_select_chain.restype = C.c_int
     lib.rt_accum_track_buckets.argtypes = [vp, C.c_uint32]
     lib.rt_accum_track_buckets.restype = C.c_int
     lib.rt_accum_read_robust.argtypes = [vp, C.POINTER(RtRobust), _f, _u8, _u8, C.POINTER(RtRobustInfo)]

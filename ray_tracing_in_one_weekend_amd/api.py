@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import RtAdaptive, RtAdaptiveInfo, RtBounceIO, RtCamera, RtDenoise, RtDisplay, RtDisplayInfo, RtFlatScene, RtGlare, RtGlareInfo, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtResidual, RtStats
+from ._ffi import RtAdaptive, RtAdaptiveInfo, RtBounceIO, RtCamera, RtDenoise, RtDisplay, RtDisplayInfo, RtFlatScene, RtGlare, RtGlareInfo, RtLens, RtLights, RtMotion, RtNoise, RtParams, RtQuads, RtResidual, RtSelect, RtSelectInfo, RtStats
 
 
 class RtError(RuntimeError):
@@ -591,6 +591,21 @@ def glare_check(glare):
     return _ffi.load_gpu_library().rt_glare_check(C.byref(glare) if glare is not None else None) == 0
 
 
+def make_select(strengths=_ffi.SELECT_DEFAULT_STRENGTHS, radius=5, patch=1, error_radius=0, blend_radius=1):
+    """An RtSelect for Renderer.accum_denoise_select: 2 .. 4 strictly increasing candidate strengths of the cross filter, its window radius
+    and patch radius, the radius of the window the per-pixel error estimate is summed over and that of the window the choice is blended
+    over (0 .. 4 each).  The defaults are those of a NULL `sel`."""
+    ks = [float(k) for k in strengths]
+    if len(ks) > _ffi.SELECT_MAX:
+        raise ValueError(f"at most {_ffi.SELECT_MAX} strengths, got {len(ks)}")
+    return RtSelect(len(ks), (C.c_float * 4)(*ks), int(radius), int(patch), int(error_radius), int(blend_radius), 0)
+
+
+def select_check(sel):
+    """rt_select_check (no GPU): True when rt_accum_denoise_select would accept the RtSelect (None: the defaults)."""
+    return _ffi.load_gpu_library().rt_select_check(C.byref(sel) if sel is not None else None) == 0
+
+
 def denoise_level_size(nx, rows, level):
     """rt_denoise_level_size (no GPU): (nx_l, rows_l) of level `level` of the pyramid accum_denoise_multiscale filters."""
     nx_l, rows_l = C.c_uint32(), C.c_uint32()
@@ -958,6 +973,46 @@ class Renderer:
         res = RtResidual()
         self._call("rt_accum_denoise_halves", self._denoise_ptr(radius, patch, strength, _ffi.DENOISE_HALVES_DEFAULT_STRENGTH), *ptrs, C.byref(res))
         return img, rgb8, err, res
+
+    def accum_denoise_select(self, select=None, want_rgb8=False):
+        """rt_accum_denoise_select: the cross filter of accum_denoise_halves at every candidate strength of `select` (make_select; None: the
+        defaults), the luminance error of each estimated per pixel against the other half, the smallest chosen and the candidates blended;
+        the accumulation must track halves.  Returns (img [rows, nx, 3] f32, rgb8 or None, index [rows, nx] u8 — the candidate each pixel
+        chose —, est [rows, nx] f32 — the estimated squared luminance error of a half filter there —, RtSelectInfo).  RtSelectInfo.best is
+        the frame-wide choice: select.strength[best] is what to hand to accum_denoise_halves."""
+        img, rgb8, est, ptrs = self._accum_outputs(want_rgb8, True)
+        index = np.zeros(est.shape, dtype=np.uint8)
+        info = RtSelectInfo()
+        self._call("rt_accum_denoise_select", C.byref(select) if select is not None else None, ptrs[0], ptrs[1], index.ctypes.data_as(C.POINTER(C.c_uint8)), ptrs[2],
+                   C.byref(info))
+        return img, rgb8, index, est, info
+
+    def debug_denoise_select(self, c, yv, select=None, first_sample=0, n=16, counts=None, probe=None):
+        """rt_debug_denoise_select: the kernels of accum_denoise_select over host arrays in image order — c = (c_0, c_1), [rows, nx, 3] each;
+        yv = ((y_0, v_0), (y_1, v_1)), [rows, nx] each; the halves hold the samples [first_sample, first_sample + n), with n = counts[p]
+        per pixel where counts [rows, nx] u32 is given.  Returns (img, index, est, RtSelectInfo), and with probe = j also (out_j, E_j)."""
+        c = [np.ascontiguousarray(x, dtype=np.float32) for x in c]
+        rows, nx, _ = c[0].shape
+        g = [np.ascontiguousarray(np.stack([np.asarray(y, np.float32), np.asarray(v, np.float32)], -1)) for y, v in yv]
+        assert c[1].shape == (rows, nx, 3) and all(x.shape == (rows, nx, 2) for x in g)
+        cnt = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+        assert cnt is None or cnt.shape == (rows, nx)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None
+        out, est, index = np.zeros((rows, nx, 3), np.float32), np.zeros((rows, nx), np.float32), np.zeros((rows, nx), np.uint8)
+        p_out = np.zeros((rows, nx, 3), np.float32) if probe is not None else None
+        p_err = np.zeros((rows, nx), np.float32) if probe is not None else None
+        info = RtSelectInfo()
+        self._call("rt_debug_denoise_select", nx, rows, fp(c[0]), fp(c[1]), fp(g[0]), fp(g[1]), cnt.ctypes.data_as(C.POINTER(C.c_uint32)) if cnt is not None else None,
+                   int(first_sample), int(n), C.byref(select) if select is not None else None, fp(out), index.ctypes.data_as(C.POINTER(C.c_uint8)), fp(est),
+                   C.byref(info), int(probe or 0), fp(p_out), fp(p_err))
+        return (out, index, est, info) if probe is None else (out, index, est, info, p_out, p_err)
+
+    def debug_select_chain(self, chain):
+        """rt_debug_select_chain: which filter chain accum_denoise_select and debug_denoise_select run on this Renderer — "auto", "plain"
+        (2 K launches of the filter) or "fused" (one launch per half for all K strengths), or the _ffi.SELECT_CHAIN_* number.  Every chain
+        gives the same bits."""
+        names = {"auto": _ffi.SELECT_CHAIN_AUTO, "plain": _ffi.SELECT_CHAIN_PLAIN, "fused": _ffi.SELECT_CHAIN_FUSED}
+        self._call("rt_debug_select_chain", names[chain] if isinstance(chain, str) else int(chain))
 
     def accum_export_halves(self):
         """rt_accum_export_halves: the half buffers of the open accumulation as an AccumHalves.  Read, not changed."""

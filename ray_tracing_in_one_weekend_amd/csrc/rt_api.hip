@@ -11,6 +11,7 @@
 #include "rt_accum_state.h"
 #include "rt_accum_state_kernels.h"
 #include "rt_halves.h"
+#include "rt_select.h"
 #include "rt_buckets.h"
 #include "rt_display.h"
 #include "rt_glare.h"
@@ -160,6 +161,10 @@ struct RtCtx {
     // half's inputs and filter output, out, e: 48 B per pixel, the partial sums and the three frame figures)
     DevBuf accum_halves, dn_halves;
     double* h_resid = nullptr;   // page-locked: mean_luminance, residual_rms, residual_noise as k_halves_final wrote them
+    // rt_accum_denoise_select and rt_debug_denoise_select (rt_select.h): every region of a run (rt_select_plan.h: select_layout)
+    DevBuf dn_select;
+    RtSelectInfo* h_select = nullptr; // page-locked: the figures as k_select_final wrote them
+    uint32_t select_chain = RT_SELECT_CHAIN_AUTO; // rt_debug_select_chain
     // rt_accum_track_buckets (rt_buckets.h): M planes of f32 x 3 sums, 12 M B per pixel, each in the order of accum_sum (rt_buckets_plan.h);
     // robust_out: what a robust read-out writes — out (12 B) and the trims (3 B) per pixel in image order, the partial sums and the frame figures
     DevBuf accum_buckets, robust_out;
@@ -784,6 +789,8 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->accum_halves), free_buf(ctx->dn_halves);
     free_buf(ctx->accum_buckets), free_buf(ctx->robust_out);
     if (ctx->h_resid) (void)hipHostFree(ctx->h_resid);
+    free_buf(ctx->dn_select);
+    if (ctx->h_select) (void)hipHostFree(ctx->h_select);
     if (ctx->h_robust) (void)hipHostFree(ctx->h_robust);
     free_buf(ctx->display_buf);
     free_buf(ctx->glare_buf), free_buf(ctx->glare_debug_buf);
@@ -2466,6 +2473,158 @@ int rt_accum_import_halves(RtCtx* ctx, const RtAccumHalves* hs) {
     return RT_OK;
 }
 
+// ---- selected strength (rtow_mi355x.h "Selected strength", csrc/rt_select.h, csrc/rt_select_plan.h) ----------------------------------------
+int rt_select_check(const RtSelect* sel) { return select_invalid(sel) ? RT_ERR_INVALID : RT_OK; }
+
+// The regions of a layout in ctx->dn_select (ensured by the caller) as pointers
+struct SelectRegions {
+    char* base;
+    SelectLayout l;
+    float* c(int h) const { return (float*)(base + l.c[h]); }
+    float2* yv(int h) const { return (float2*)(base + l.yv[h]); }
+    uint32_t* cnt() const { return (uint32_t*)(base + l.cnt); }
+    float* f(int h, uint32_t j) const { return (float*)(base + l.f[h][j]); }
+    float* est() const { return (float*)(base + l.est); }
+    float* out() const { return (float*)(base + l.out); }
+    uint8_t* index() const { return (uint8_t*)(base + l.index); }
+    SelectPartial* partials() const { return (SelectPartial*)(base + l.partials); }
+    RtSelectInfo* info() const { return (RtSelectInfo*)(base + l.info); }
+    SelectPlanes planes() const {
+        SelectPlanes p{};
+        for (uint32_t j = 0; j < RT_SELECT_MAX; ++j) p.out_j[j] = (float*)(base + l.out_j[j]), p.e_j[j] = (float*)(base + l.e_j[j]);
+        return p;
+    }
+};
+constexpr bool RT_SELECT_AUTO_FUSED = true; // (by the measurement of DESIGN.md "Selected strength")
+// Which chain a run takes: rt_debug_select_chain, or the library's choice (the one measured faster: DESIGN.md "Selected strength")
+static bool select_fused(const RtCtx* ctx) { return ctx->select_chain == RT_SELECT_CHAIN_AUTO ? RT_SELECT_AUTO_FUSED : ctx->select_chain == RT_SELECT_CHAIN_FUSED; }
+int rt_debug_select_chain(RtCtx* ctx, uint32_t chain) {
+    if (!ctx) return RT_ERR_INVALID;
+    if (chain > RT_SELECT_CHAIN_FUSED) return fail(ctx, RT_ERR_INVALID, "rt_debug_select_chain: chain must be RT_SELECT_CHAIN_AUTO, _PLAIN or _FUSED");
+    ctx->select_chain = chain;
+    return RT_OK;
+}
+static int ensure_select(RtCtx* ctx, uint64_t npix, uint32_t K, SelectRegions& m) {
+    const SelectLayout l = select_layout(npix, K);
+    if (const int rc = ensure(ctx, ctx->dn_select, l.total)) return rc;
+    if (!ctx->h_select) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_select, sizeof(RtSelectInfo), hipHostMallocDefault));
+    m = SelectRegions{ctx->dn_select.as<char>(), l};
+    return RT_OK;
+}
+// One launch of k_denoise_multi<F, K>: the colours `c` of one half by the guide `g` of the other -> f(h, j) for every j
+static void launch_nlm_multi(hipStream_t st, const float* c, const float2* g, const SelectRegions& m, int h, uint32_t nx, uint32_t rows, const RtSelect& s) {
+    const dim3 grid((nx + RT_DN_TILE - 1u) / RT_DN_TILE, (rows + RT_DN_TILE - 1u) / RT_DN_TILE), block(RT_DN_TILE, RT_DN_TILE);
+    const int R = (int)s.radius;
+    const size_t lds = select_multi_lds_bytes(s.n_strengths, s.radius, s.patch);
+    SelectMulti sm{};
+    for (uint32_t j = 0; j < s.n_strengths; ++j) sm.out[j] = m.f(h, j), sm.k2[j] = s.strength[j] * s.strength[j];
+#define NLM_MULTI(F, K) hipLaunchKernelGGL((k_denoise_multi<F, K>), grid, block, lds, st, c, g, sm, nx, rows, R)
+#define NLM_MULTI_K(F)                        \
+    do {                                      \
+        switch (s.n_strengths) {              \
+        case 2u: NLM_MULTI(F, 2); break;      \
+        case 3u: NLM_MULTI(F, 3); break;      \
+        default: NLM_MULTI(F, 4); break;      \
+        }                                     \
+    } while (0)
+    switch (s.patch) {
+    case 0u: NLM_MULTI_K(0); break;
+    case 1u: NLM_MULTI_K(1); break;
+    case 2u: NLM_MULTI_K(2); break;
+    default: NLM_MULTI_K(3); break;
+    }
+#undef NLM_MULTI_K
+#undef NLM_MULTI
+}
+// Everything behind the inputs c_h and (y, v)_h, which the caller has enqueued into the regions on `st`: the filter of every candidate on
+// both halves — `fused`: two launches of k_denoise_multi, else 2 K of the unchanged k_denoise — and its error, then the choice, the partial
+// sums, the blend and the figures.  `r`: the image and where the counts of its pixels are (r.cnt in the order local_of_pixel gives with
+// r.tiles_per_row and r.tile_pixels; r.n where r.counts is false).
+static void enqueue_select(const AccumReader& r, uint32_t first, const SelectRegions& m, const RtSelect& s, bool fused) {
+    const hipStream_t st = r.st;
+    const SelectPlanes pl = m.planes();
+    const uint32_t K = s.n_strengths, npix = r.nx * r.rows;
+    if (fused) {
+        launch_nlm_multi(st, m.c(0), m.yv(1), m, 0, r.nx, r.rows, s); // each half by the other's guide
+        launch_nlm_multi(st, m.c(1), m.yv(0), m, 1, r.nx, r.rows, s);
+    }
+    for (uint32_t j = 0; j < K; ++j) {
+        if (!fused) {
+            const RtDenoise d{s.radius, s.patch, s.strength[j], 0u};
+            launch_nlm(st, 1u, m.c(0), m.yv(1), m.f(0, j), r.nx, r.rows, d);
+            launch_nlm(st, 1u, m.c(1), m.yv(0), m.f(1, j), r.nx, r.rows, d);
+        }
+        ACCUM_READER(k_select_error, r, (const float*)m.f(0, j), (const float*)m.f(1, j), (const float2*)m.yv(0), (const float2*)m.yv(1), r.cnt, pl.out_j[j], pl.e_j[j],
+                     r.nx, r.rows, first, r.n, r.tiles_per_row, r.tile_pixels);
+    }
+    const dim3 tiles((r.nx + RT_SEL_TILE - 1u) / RT_SEL_TILE, (r.rows + RT_SEL_TILE - 1u) / RT_SEL_TILE), block(RT_SEL_TILE, RT_SEL_TILE);
+    hipLaunchKernelGGL(k_select_choose, tiles, block, 0, st, pl, K, (int)s.error_radius, m.index(), m.est(), r.nx, r.rows);
+    hipLaunchKernelGGL(k_select_partials, dim3(m.l.n_partials), dim3(256), 0, st, pl, K, (const uint8_t*)m.index(), m.partials(), npix);
+    hipLaunchKernelGGL(k_select_blend, tiles, block, 0, st, pl, K, (int)s.blend_radius, (const uint8_t*)m.index(), m.out(), r.nx, r.rows);
+    hipLaunchKernelGGL(k_select_final, dim3(1), dim3(256), 0, st, (const SelectPartial*)m.partials(), m.l.n_partials, K, m.info());
+}
+
+int rt_accum_denoise_select(RtCtx* ctx, const RtSelect* sel, float* out_rgb_f32, uint8_t* out_rgb8, uint8_t* out_index, float* out_est, RtSelectInfo* info) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    const DenoiseCall call{"rt_accum_denoise_select", RT_DENOISE_HALVES_DEFAULT_STRENGTH,
+                           a.halves ? nullptr : "the accumulation does not track halves (rt_accum_track_halves)", 4u, "a half has no variance yet"};
+    const char* const why = select_invalid(sel);
+    const RtSelect s = sel && !why ? *sel : select_defaults();
+    const auto more = [&]() -> int { return why ? fail(ctx, RT_ERR_INVALID, std::string(call.who) + ": " + why) : RT_OK; };
+    // (denoise_run judges an RtDenoise of its own: NULL, the defaults, since `more` judges the whole RtSelect in the same place of the order)
+    const int rc = denoise_run(ctx, call, nullptr, out_rgb_f32, out_rgb8, more, [&](const AccumReader& r, const RtDenoise&, const float*& img) -> int {
+        SelectRegions m{};
+        if (const int rc = ensure_select(ctx, a.npix, s.n_strengths, m)) return rc;
+        const HalfPlanes hp = half_planes(ctx->accum_halves, a.npix);
+        ACCUM_READER(k_denoise_inputs_halves, r, hp, r.cnt, m.c(0), m.c(1), m.yv(0), m.yv(1), r.nx, r.rows, a.first, r.n, r.tiles_per_row, r.tile_pixels);
+        enqueue_select(r, a.first, m, s, select_fused(ctx));
+        if (out_index) RT_HIP(ctx, hipMemcpyAsync(out_index, m.index(), (size_t)a.npix, hipMemcpyDeviceToHost, r.st));
+        if (out_est) RT_HIP(ctx, hipMemcpyAsync(out_est, m.est(), (size_t)a.npix * sizeof(float), hipMemcpyDeviceToHost, r.st));
+        RT_HIP(ctx, hipMemcpyAsync(ctx->h_select, m.info(), sizeof(RtSelectInfo), hipMemcpyDeviceToHost, r.st));
+        img = m.out();
+        return RT_OK;
+    });
+    if (rc == RT_OK && info && a.npix) *info = *ctx->h_select;
+    return rc;
+}
+
+// debug_nlm's pattern with the selection behind the upload, and out_j and E_j of one candidate read back where asked
+int rt_debug_denoise_select(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* c0, const float* c1, const float* yv0, const float* yv1, const uint32_t* counts,
+                            uint32_t first_sample, uint32_t n, const RtSelect* sel, float* out_rgb_f32, uint8_t* out_index, float* out_est, RtSelectInfo* info,
+                            uint32_t probe_candidate, float* probe_out, float* probe_err) {
+    if (!ctx) return RT_ERR_INVALID;
+    const std::string who = "rt_debug_denoise_select";
+    if (!c0 || !c1 || !yv0 || !yv1) return fail(ctx, RT_ERR_INVALID, who + ": NULL array");
+    if (nx == 0u || rows == 0u || (uint64_t)nx * rows > (1ull << 28)) return fail(ctx, RT_ERR_INVALID, who + ": nx * rows must be 1 .. 2^28");
+    if (const char* why = select_invalid(sel)) return fail(ctx, RT_ERR_INVALID, who + ": " + why);
+    const RtSelect s = sel ? *sel : select_defaults();
+    if ((probe_out || probe_err) && probe_candidate >= s.n_strengths) return fail(ctx, RT_ERR_INVALID, who + ": probe_candidate must be below n_strengths");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t npix = (size_t)nx * rows;
+    SelectRegions m{};
+    if (const int rc = ensure_select(ctx, npix, s.n_strengths, m)) return rc;
+    const hipStream_t st = ctx->stream;
+    RT_HIP(ctx, hipMemcpyAsync(m.c(0), c0, npix * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    RT_HIP(ctx, hipMemcpyAsync(m.c(1), c1, npix * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    RT_HIP(ctx, hipMemcpyAsync(m.yv(0), yv0, npix * sizeof(float2), hipMemcpyHostToDevice, st));
+    RT_HIP(ctx, hipMemcpyAsync(m.yv(1), yv1, npix * sizeof(float2), hipMemcpyHostToDevice, st));
+    if (counts) RT_HIP(ctx, hipMemcpyAsync(m.cnt(), counts, npix * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    // (tiles_per_row 0: local_of_pixel is the image order the host's counts are in)
+    const AccumReader r{st, dim3((uint32_t)((npix + 255u) / 256u)), nx, rows, 0u, 0u, m.cnt(), n, counts != nullptr};
+    enqueue_select(r, first_sample, m, s, select_fused(ctx));
+    RT_HIP(ctx, hipGetLastError());
+    const SelectPlanes pl = m.planes();
+    if (out_rgb_f32) RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, m.out(), npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (out_index) RT_HIP(ctx, hipMemcpyAsync(out_index, m.index(), npix, hipMemcpyDeviceToHost, st));
+    if (out_est) RT_HIP(ctx, hipMemcpyAsync(out_est, m.est(), npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (probe_out) RT_HIP(ctx, hipMemcpyAsync(probe_out, pl.out_j[probe_candidate], npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (probe_err) RT_HIP(ctx, hipMemcpyAsync(probe_err, pl.e_j[probe_candidate], npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipMemcpyAsync(ctx->h_select, m.info(), sizeof(RtSelectInfo), hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    if (info) *info = *ctx->h_select;
+    return RT_OK;
+}
 
 // ---- sample buckets (rtow_mi355x.h "Sample buckets", csrc/rt_buckets.h, csrc/rt_buckets_plan.h) --------------------------------------------
 int rt_accum_buckets_check(const RtAccumBuckets* bs) { return accum_buckets_invalid(bs) ? RT_ERR_INVALID : RT_OK; }

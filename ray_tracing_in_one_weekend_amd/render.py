@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from . import AccumBuckets, AccumState, MultiRenderer, Renderer, RtError, Scene, display_check, glare_check, make_display, make_glare, make_params, output_file_name, register_default_images, save_png
+from . import AccumBuckets, AccumState, MultiRenderer, Renderer, RtError, Scene, display_check, glare_check, make_display, make_glare, make_params, make_select, select_check, output_file_name, register_default_images, save_png
 from . import _ffi
 from .images import write_pfm
 
@@ -136,6 +136,16 @@ def main(argv=None):
                     help="with --denoise and --denoise-guide luminance or channels: filter a 2x pyramid of L levels, 1..%d, each coarser level "
                          "replacing the low frequencies of the finer one (rt_accum_denoise_multiscale); 1 is the single-scale filter"
                          % _ffi.DENOISE_MAX_LEVELS)
+    ap.add_argument("--denoise-select", default=None, metavar="K0,K1[,K2[,K3]]",
+                    help="with --denoise --denoise-guide halves: 2..%d strictly increasing candidate strengths; the cross filter runs at each, its "
+                         "error is estimated per pixel against the other half, and every pixel takes the candidate with the smallest "
+                         "(rt_accum_denoise_select; the library's candidates are %s).  Prints the frame-wide best candidate and the estimated "
+                         "error of each" % (_ffi.SELECT_MAX, ",".join("%g" % k for k in _ffi.SELECT_DEFAULT_STRENGTHS)))
+    ap.add_argument("--select-error-radius", type=int, default=0, metavar="S", help="radius of the window the error estimate is summed over, 0..%d" % _ffi.SELECT_MAX_WINDOW)
+    ap.add_argument("--select-blend-radius", type=int, default=1, metavar="T", help="radius of the window the choice is blended over, 0..%d" % _ffi.SELECT_MAX_WINDOW)
+    ap.add_argument("--select-map-out", default=None, metavar="FILE",
+                    help="with --denoise-select: write the index map (the candidate every pixel chose, u8) and the error map (est, f32) to FILE, an "
+                         ".npz with `index`, `est` and `strengths`, rows as the saved image has them (row 0 on top)")
     ap.add_argument("--residual-target", type=float, default=None, metavar="X",
                     help="render until the DENOISED frame is clean: samples in steps of --spp-step, the cross filter of --denoise-guide halves "
                          "after each, until its residual_noise <= X or --spp are done.  The figure is the variance half of the filtered "
@@ -282,6 +292,18 @@ def main(argv=None):
             ap.error("--denoise --robust filters with the luminance guide only")
     if a.firefly_map and not a.robust_mode:
         ap.error("--firefly-map needs --robust")
+    if a.denoise_select is not None or a.select_map_out:
+        if not (a.denoise and a.denoise_guide == "halves") or a.residual_target is not None or a.denoise_strength is not None:
+            ap.error("--denoise-select needs --denoise --denoise-guide halves, without --residual-target and --denoise-strength")
+        if a.denoise_select is None:
+            ap.error("--select-map-out needs --denoise-select")
+        try:
+            a.select = make_select([float(k) for k in a.denoise_select.split(",")], a.denoise_radius, a.denoise_patch, a.select_error_radius, a.select_blend_radius)
+        except ValueError as e:
+            ap.error("--denoise-select: %s" % e)
+        if not select_check(a.select):
+            ap.error("--denoise-select takes 2..%d finite strengths > 0 in strictly increasing order, --select-error-radius and --select-blend-radius 0..%d"
+                     % (_ffi.SELECT_MAX, _ffi.SELECT_MAX_WINDOW))
     if halves:
         if a.hdr_out or a.glare_out:
             ap.error("--hdr-out and --glare-out write the image of a plain render: they do not combine with the progressive options")
@@ -509,6 +531,19 @@ def render_halves(a, rend, scene, flags, file_name, t0):
         rend.accum_begin(scene.camera, params)
         rend.accum_track_halves()
         rend.accum_add(a.spp)
+        if a.denoise_select is not None:
+            _, rgb8, index, est, info = rend.accum_denoise_select(a.select, want_rgb8=True)
+            rend.accum_end()
+            print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
+            save_png(file_name, rgb8)
+            ks = list(a.select.strength)[:a.select.n_strengths]
+            if a.select_map_out:
+                with open(a.select_map_out, "wb") as f:  # (np.savez would append .npz to a name)
+                    np.savez(f, index=index[::-1], est=est[::-1], strengths=np.asarray(ks, np.float32))
+            print(f"{file_name}: {a.nx}x{a.ny}, {a.spp} spp, cross-filtered at the strength chosen per pixel from " + ", ".join("%g" % k for k in ks) +
+                  f": frame-wide best {ks[info.best]:g}; estimated luminance MSE of a half filter " + ", ".join("%.4g" % e for e in list(info.est_mse)[:len(ks)]) +
+                  "; pixels per candidate " + ", ".join(str(n) for n in list(info.chosen)[:len(ks)]) + f"; {info.usable} usable pixels", file=sys.stderr)
+            return 0
         _, rgb8, _, res = rend.accum_denoise_halves(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)
         rend.accum_end()
         done = a.spp
