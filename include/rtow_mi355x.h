@@ -1174,6 +1174,90 @@ int rt_glare_info(RtCtx* ctx, RtGlareInfo* info);
 /* `out` of that last call: out_rgb_f32 [3 * nx * rows] in the call's row order.  RT_ERR_STATE: there was none. */
 int rt_glare_image(RtCtx* ctx, float* out_rgb_f32);
 
+/* -- pixel reconstruction filters: tent, Gaussian, Mitchell-Netravali and Blackman-Harris instead of the box ---------------------------------
+ * The running sum of an accumulation is the reference's: sample s of pixel p counts for p alone with weight 1 wherever inside the pixel it
+ * fell (main.rs:95-97), a box of radius 0.5.  An accumulation that TRACKS A FILTER also keeps, per pixel, (sum w r, sum w g, sum w b,
+ * sum w) in f32 — 16 B per pixel more, in the local pixel order of the sums — over the samples of the pixel AND of its neighbours, each
+ * weighted by a separable filter of one radius R, in pixels, at its distance from the pixel's centre.  The sub-pixel position of a sample
+ * is not stored: it is the first two draws of the path's key (DESIGN.md "RNG", counters 0 and 1), recomputed from (seed, pixel, sample).
+ * The filter.  f(|x|) for |x| <= R, RT_FILTER_MIN_RADIUS <= R <= RT_FILTER_MAX_RADIUS:
+ *   RT_FILTER_BOX             1
+ *   RT_FILTER_TENT            1 - x / R
+ *   RT_FILTER_GAUSSIAN        exp(-x^2 / (2 sigma^2)) - exp(-R^2 / (2 sigma^2)),  sigma = p0 > 0
+ *   RT_FILTER_MITCHELL        with B = p0, C = p1 and t = 2 x / R:  ((12 - 9B - 6C) t^3 + (-18 + 12B + 6C) t^2 + (6 - 2B)) / 6 for t < 1,
+ *                             ((-B - 6C) t^3 + (6B + 30C) t^2 + (-12B - 48C) t + (8B + 24C)) / 6 else (negative lobes where C > 0)
+ *   RT_FILTER_BLACKMAN_HARRIS 0.35875 + 0.48829 cos(a) + 0.14128 cos(2a) + 0.01168 cos(3a),  a = pi x / R
+ * The TABLE.  The host evaluates f in f64 at the midpoints x_k = (k + 0.5) R / RT_FILTER_TABLE, k = 0 .. RT_FILTER_TABLE - 1, and rounds each
+ * value once to f32 (rt_pixel_filter_table returns exactly what the device uses).  The device evaluates no profile: it looks the table up.
+ * The REACH.  D = ceil(R + 0.5) - 1 pixels: R 0.5 -> 0, (0.5, 1.5] -> 1, (1.5, 2.5] -> 2, (2.5, 3] -> 3.
+ * Defining property.  With (jx, jy) = the draws 0 and 1 of path_key(seed, q, i) as f32 in [0, 1), every operation below one IEEE f32
+ * operation without contraction, for the samples i of the accumulation in ascending order:
+ *   for dy = -D .. D ascending, for dx = -D .. D ascending, q = (i_p + dx, j_p + dy) inside the frame (and, in an adaptive add, active):
+ *     ox = ((float)dx + jx) - 0.5f;  ax = |ox|;  skip where ax > R;  kx = min((uint32_t)(ax * (256.0f / R)), 255);   likewise oy, ay, ky
+ *     w = table[kx] * table[ky];   sum.rgb += w * radiance(q, i).rgb;   sum.w += w
+ * The plane is that, bit for bit, however adds and slices are cut and for either pixel order: a gather, no atomics.  A pixel that has
+ * converged in an adaptive accumulation gets no samples of its own and keeps receiving those of its active neighbours.
+ * Read-out.  c = sum.rgb / sum.w and W = sum.w; where !(W > 0) — no sample yet, or a negative-lobe filter whose weights cancel — the pixel
+ * is the box mean of rt_accum_read.  out_rgb8 goes where the denoisers' goes: the reference quantisation, or the context's glare and
+ * display.  With RT_FILTER_BOX at R 0.5 the plane's rgb is the accumulation's sum, W is (float)n and the read-out is rt_accum_read's, bit
+ * for bit.
+ * Everything an accumulation returned before is unchanged in every bit with tracking on or off: a kernel of its own reads the radiance of a
+ * slice a second time.
+ * State.  RtAccumFilter carries the filter and the plane in the row order of out_rgb_f32.  Resume is rt_accum_begin, rt_accum_import,
+ * rt_accum_import_filter: from then on the plane and the read-out are bit for bit those of the uninterrupted accumulation.
+ * rt_accum_import and rt_accum_merge on an accumulation that tracks a filter are RT_ERR_UNSUPPORTED and change nothing.
+ * Not covered: sharded frames and rt_multi_accum_* (a row-interleaved shard has no neighbourhoods: RT_ERR_STATE); a merge of filter planes;
+ * a denoiser on the filtered image (its pixels are correlated, and the variance guides do not describe it); anisotropic radii.
+ * DESIGN.md "Pixel reconstruction filters". */
+#define RT_FILTER_BOX             0u
+#define RT_FILTER_TENT            1u
+#define RT_FILTER_GAUSSIAN        2u /* p0 = sigma */
+#define RT_FILTER_MITCHELL        3u /* p0 = B, p1 = C */
+#define RT_FILTER_BLACKMAN_HARRIS 4u
+#define RT_FILTER_TABLE 256u
+#define RT_FILTER_MIN_RADIUS 0.5f
+#define RT_FILTER_MAX_RADIUS 3.0f
+typedef struct RtPixelFilter {
+    uint32_t kind;   /* RT_FILTER_* */
+    float radius;    /* R, in pixels */
+    float p0, p1;    /* the kind's parameters; finite, 0 where the kind has none */
+} RtPixelFilter;
+typedef struct RtAccumFilter {
+    uint32_t nx, rows;           /* the frame: rows = ny (no shards) */
+    uint32_t first_sample, done; /* those of the accumulation the plane belongs to */
+    uint32_t reserved[2];        /* 0 */
+    uint64_t frame_id;           /* rt_accum_frame_id of the frame */
+    RtPixelFilter filter;        /* the filter the plane was summed under */
+    float* plane;                /* [rows*nx*4]: sum w r, sum w g, sum w b, sum w — NOT divided */
+} RtAccumFilter;
+/* GPU-free, no context.  RT_OK, or RT_ERR_INVALID: `filter` NULL, a kind outside the enum, a non-finite field, a radius outside
+ * [RT_FILTER_MIN_RADIUS, RT_FILTER_MAX_RADIUS], a Gaussian with sigma <= 0. */
+int rt_pixel_filter_check(const RtPixelFilter* filter);
+/* GPU-free, no context.  table [RT_FILTER_TABLE] and *reach = D as defined above; either may be NULL.  RT_ERR_INVALID: what
+ * rt_pixel_filter_check refuses. */
+int rt_pixel_filter_table(const RtPixelFilter* filter, float* table, uint32_t* reach);
+/* Makes the open accumulation track `filter` and clears the plane.  The rules of rt_accum_track_halves: after rt_accum_begin and before
+ * the first add, else RT_ERR_STATE; a second call with the same filter is RT_OK and changes nothing, with another one RT_ERR_STATE.
+ * RT_ERR_STATE on a sharded accumulation (shard_count > 1).  RT_ERR_INVALID: what rt_pixel_filter_check refuses.  Tracking ends with the
+ * accumulation.  Combines freely with the other rt_accum_track_* calls and with adaptive adds. */
+int rt_accum_track_filter(RtCtx* ctx, const RtPixelFilter* filter);
+/* The read-out above: out_rgb_f32 [ny*nx*3] and out_rgb8 as rt_accum_denoise writes them, out_weight [ny*nx] = W in the row order of
+ * out_rgb_f32; each may be NULL.  The accumulation is read and not changed.  Synchronises the context's stream once.  RT_ERR_STATE: no open
+ * accumulation, or it does not track a filter. */
+int rt_accum_read_filtered(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_weight);
+/* GPU-free.  RT_OK, or RT_ERR_INVALID unless: `fs` non-NULL, both reserved words 0, the plane non-NULL, first_sample + done <= 2^32 - 1,
+ * a filter rt_pixel_filter_check accepts.  Values are not judged. */
+int rt_accum_filter_check(const RtAccumFilter* fs);
+/* Fills the scalar fields and the filter of `fs` and writes the plane where its pointer is non-NULL.  Reads, and changes nothing.
+ * Synchronises the context's stream once.  RT_ERR_STATE: no open accumulation, or it does not track a filter. */
+int rt_accum_export_filter(RtCtx* ctx, RtAccumFilter* fs);
+/* Puts `fs` into the open accumulation and turns tracking on under its filter.  Allowed while the accumulation has had no add (and no
+ * merge) since rt_accum_begin — fresh with done 0, or after rt_accum_import — else RT_ERR_STATE; RT_ERR_STATE on a sharded accumulation.
+ * Values are copied as bits.  RT_ERR_INVALID: rt_accum_filter_check fails, nx, rows, frame_id, first_sample or done differ from the
+ * accumulation's, or the accumulation tracks a filter already and the snapshot's is another one.  A failed call leaves the accumulation
+ * as it was.  Synchronises once. */
+int rt_accum_import_filter(RtCtx* ctx, const RtAccumFilter* fs);
+
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the
  * world shared read-only (main.rs:72-108); here the scene is replicated on every device, device r renders the image

@@ -300,6 +300,12 @@ int rt_debug_glare_chain(RtCtx* ctx, uint32_t chain);
  * the open accumulation, `pixel` an index into out_sem (row order of out_rgb_f32).  The tests plant a NaN with it: such a pixel never
  * converges and spreads to no other.  The f32 sum and n_p stay.  RT_ERR_STATE: no open accumulation; RT_ERR_INVALID: pixel outside the shard. */
 int rt_debug_accum_set_moments(RtCtx* ctx, uint32_t pixel, double s1, double s2);
+/* Test hook for the pixel filters (rtow_mi355x.h "pixel reconstruction filters"): the production kernel k_resolve_filter<false> over a host
+ * array of radiance, rad [n_samples][rows][nx][3] in the row order of out_rgb_f32, as the samples with the absolute indices i0 .. i0 +
+ * n_samples - 1, onto the filter plane of the open accumulation ONLY: its sums, moments, counts and `done` are untouched.  Designed radiance
+ * (an impulse, a NaN, 1e30) reaches the kernel without a trace.  RT_ERR_STATE: no open accumulation, or it does not track a filter;
+ * RT_ERR_INVALID: rad NULL, n_samples 0 or above 4096, i0 + n_samples above 2^32. */
+int rt_debug_filter_add(RtCtx* ctx, uint32_t i0, uint32_t n_samples, const float* rad);
 
 #ifdef __cplusplus
 }

@@ -250,6 +250,24 @@ class RtDisplayInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# rt_accum_track_filter
+FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN, FILTER_MITCHELL, FILTER_BLACKMAN_HARRIS = range(5)  # RT_FILTER_*
+FILTER_TABLE, FILTER_MIN_RADIUS, FILTER_MAX_RADIUS = 256, 0.5, 3.0  # RT_FILTER_TABLE, RT_FILTER_MIN_RADIUS, RT_FILTER_MAX_RADIUS
+
+
+class RtPixelFilter(C.Structure):
+    """rt_accum_track_filter: the separable reconstruction filter of an accumulation, its radius in pixels and the parameters of its kind
+    (rtow_mi355x.h "pixel reconstruction filters")."""
+    _fields_ = [("kind", C.c_uint32), ("radius", C.c_float), ("p0", C.c_float), ("p1", C.c_float)]
+
+
+class RtAccumFilter(C.Structure):
+    """rt_accum_export_filter / rt_accum_import_filter: the filter and the plane (sum w rgb, sum w) of an accumulation, as a host array in the
+    row order of the f32 image."""
+    _fields_ = [("nx", C.c_uint32), ("rows", C.c_uint32), ("first_sample", C.c_uint32), ("done", C.c_uint32), ("reserved", C.c_uint32 * 2),
+                ("frame_id", C.c_uint64), ("filter", RtPixelFilter), ("plane", _f)]
+
+
 # rt_set_glare
 GLARE_MAX_LEVELS, GLARE_DEFAULT_LEVELS = 8, 6
 GLARE_DEFAULT_AMOUNT, GLARE_DEFAULT_SPREAD = 0.1, 0.7
@@ -336,6 +354,8 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_multi_accum_begin", "rt_multi_accum_add", "rt_multi_accum_add_adaptive", "rt_multi_accum_join", "rt_multi_accum_import", "rt_multi_accum_end",
                "rt_set_display", "rt_display_info", "rt_display_check", "rt_debug_display",
                "rt_set_glare", "rt_glare_check", "rt_glare_info", "rt_glare_image", "rt_debug_glare", "rt_debug_glare_chain",
+               "rt_pixel_filter_check", "rt_pixel_filter_table", "rt_accum_track_filter", "rt_accum_read_filtered", "rt_accum_filter_check",
+               "rt_accum_export_filter", "rt_accum_import_filter", "rt_debug_filter_add",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
@@ -478,6 +498,22 @@ def load_gpu_library():
     lib.rt_accum_export_halves.restype = C.c_int
     lib.rt_accum_import_halves.argtypes = [vp, C.POINTER(RtAccumHalves)]
     lib.rt_accum_import_halves.restype = C.c_int
+    lib.rt_pixel_filter_check.argtypes = [C.POINTER(RtPixelFilter)]
+    lib.rt_pixel_filter_check.restype = C.c_int
+    lib.rt_pixel_filter_table.argtypes = [C.POINTER(RtPixelFilter), _f, _u32]
+    lib.rt_pixel_filter_table.restype = C.c_int
+    lib.rt_accum_track_filter.argtypes = [vp, C.POINTER(RtPixelFilter)]
+    lib.rt_accum_track_filter.restype = C.c_int
+    lib.rt_accum_read_filtered.argtypes = [vp, _f, _u8, _f]
+    lib.rt_accum_read_filtered.restype = C.c_int
+    lib.rt_accum_filter_check.argtypes = [C.POINTER(RtAccumFilter)]
+    lib.rt_accum_filter_check.restype = C.c_int
+    lib.rt_accum_export_filter.argtypes = [vp, C.POINTER(RtAccumFilter)]
+    lib.rt_accum_export_filter.restype = C.c_int
+    lib.rt_accum_import_filter.argtypes = [vp, C.POINTER(RtAccumFilter)]
+    lib.rt_accum_import_filter.restype = C.c_int
+    lib.rt_debug_filter_add.argtypes = [vp, C.c_uint32, C.c_uint32, _f]
+    lib.rt_debug_filter_add.restype = C.c_int
     lib.rt_select_check.argtypes = [C.POINTER(RtSelect)]
     lib.rt_select_check.restype = C.c_int
     lib.rt_accum_denoise_select.argtypes = [vp, C.POINTER(RtSelect), _f, _u8, _u8, _f, C.POINTER(RtSelectInfo)]

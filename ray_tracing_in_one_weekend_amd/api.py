@@ -591,6 +591,73 @@ def glare_check(glare):
     return _ffi.load_gpu_library().rt_glare_check(C.byref(glare) if glare is not None else None) == 0
 
 
+_FILTER_KINDS = {"box": _ffi.FILTER_BOX, "tent": _ffi.FILTER_TENT, "gaussian": _ffi.FILTER_GAUSSIAN, "mitchell": _ffi.FILTER_MITCHELL,
+                 "blackman-harris": _ffi.FILTER_BLACKMAN_HARRIS}
+# kind: (radius, p0, p1) where the caller gives none
+_FILTER_DEFAULTS = {_ffi.FILTER_BOX: (0.5, 0.0, 0.0), _ffi.FILTER_TENT: (1.0, 0.0, 0.0), _ffi.FILTER_GAUSSIAN: (1.5, 0.5, 0.0),
+                    _ffi.FILTER_MITCHELL: (2.0, 1.0 / 3.0, 1.0 / 3.0), _ffi.FILTER_BLACKMAN_HARRIS: (1.5, 0.0, 0.0)}
+
+
+def make_pixel_filter(kind, radius=None, sigma=None, B=None, C=None):
+    """An RtPixelFilter for Renderer.accum_track_filter: kind "box", "tent", "gaussian", "mitchell" or "blackman-harris" (or an
+    _ffi.FILTER_* value) and its radius in pixels, 0.5 .. 3.  Defaults: box 0.5; tent 1.0; Gaussian 1.5 with sigma 0.5; Mitchell 2.0
+    with B = C = 1/3; Blackman-Harris 1.5."""
+    if isinstance(kind, str) and kind not in _FILTER_KINDS:
+        raise ValueError(f"pixel filter {kind!r}: expected one of {sorted(_FILTER_KINDS)} (or an RT_FILTER_* value)")
+    k = _FILTER_KINDS[kind] if isinstance(kind, str) else int(kind)
+    r, p0, p1 = _FILTER_DEFAULTS.get(k, (0.5, 0.0, 0.0))
+    if k == _ffi.FILTER_GAUSSIAN and sigma is not None:
+        p0 = sigma
+    if k == _ffi.FILTER_MITCHELL:
+        p0, p1 = (p0 if B is None else B), (p1 if C is None else C)
+    return _ffi.RtPixelFilter(k, float(r if radius is None else radius), float(p0), float(p1))
+
+
+def pixel_filter_check(flt):
+    """rt_pixel_filter_check (no GPU): True when rt_accum_track_filter would accept the RtPixelFilter."""
+    return _ffi.load_gpu_library().rt_pixel_filter_check(C.byref(flt) if flt is not None else None) == 0
+
+
+def pixel_filter_table(flt):
+    """rt_pixel_filter_table (no GPU): (table [256] f32 — the filter's 1-D profile at the midpoints (k + 0.5) R / 256, exactly what the
+    device looks up —, reach D in pixels)."""
+    table = np.zeros(_ffi.FILTER_TABLE, dtype=np.float32)
+    reach = C.c_uint32(0)
+    rc = _ffi.load_gpu_library().rt_pixel_filter_table(C.byref(flt), table.ctypes.data_as(C.POINTER(C.c_float)), C.byref(reach))
+    if rc != 0:
+        raise RtError(f"rt_pixel_filter_table failed ({rc}): the RtPixelFilter is outside its ranges")
+    return table, int(reach.value)
+
+
+class AccumFilter(_Snapshot):
+    """The filter plane of an accumulation (rtow_mi355x.h "pixel reconstruction filters"), as a numpy array in the row order of the f32 image
+    plus the scalar fields of RtAccumFilter and the filter it was summed under: plane [rows, nx, 4] f32 = (sum w r, sum w g, sum w b,
+    sum w), not divided.  It goes with the AccumState of the same accumulation: first_sample and done are that state's."""
+    _SCALARS = ("nx", "rows", "first_sample", "done", "frame_id", "kind", "radius_bits", "p0_bits", "p1_bits")  # (the f32 fields as their bits)
+    _ARRAYS = (("plane", np.float32, (4,), ()),)
+    _CHECK = "rt_accum_filter_check"
+
+    def __init__(self, nx, rows, first_sample=0, done=0, frame_id=0, kind=0, radius_bits=0x3F000000, p0_bits=0, p1_bits=0, plane=None, filter=None):
+        if filter is not None:
+            kind = filter.kind
+            radius_bits, p0_bits, p1_bits = (int(np.float32(x).view(np.uint32)) for x in (filter.radius, filter.p0, filter.p1))
+        self._init(dict(nx=nx, rows=rows, first_sample=first_sample, done=done, frame_id=frame_id, kind=kind, radius_bits=radius_bits, p0_bits=p0_bits,
+                        p1_bits=p1_bits), dict(plane=plane))
+
+    @property
+    def filter(self):
+        """The RtPixelFilter the plane was summed under."""
+        r, p0, p1 = (float(np.uint32(b).view(np.float32)) for b in (self.radius_bits, self.p0_bits, self.p1_bits))
+        return _ffi.RtPixelFilter(self.kind, r, p0, p1)
+
+    def as_struct(self):
+        """The RtAccumFilter over this array (which must stay alive while it is used)."""
+        fs = _ffi.RtAccumFilter(self.nx, self.rows, self.first_sample, self.done)
+        fs.frame_id, fs.filter = self.frame_id, self.filter
+        fs.plane = self.plane.ctypes.data_as(C.POINTER(C.c_float))
+        return fs
+
+
 def make_select(strengths=_ffi.SELECT_DEFAULT_STRENGTHS, radius=5, patch=1, error_radius=0, blend_radius=1):
     """An RtSelect for Renderer.accum_denoise_select: 2 .. 4 strictly increasing candidate strengths of the cross filter, its window radius
     and patch radius, the radius of the window the per-pixel error estimate is summed over and that of the window the choice is blended
@@ -1028,6 +1095,41 @@ class Renderer:
         belongs to — and turns tracking on."""
         hs = halves.as_struct()
         self._call("rt_accum_import_halves", C.byref(hs))
+
+    def accum_track_filter(self, flt):
+        """rt_accum_track_filter: the open accumulation also keeps, per pixel, the samples of the pixel and of its neighbours weighted by the
+        reconstruction filter `flt` (make_pixel_filter; 16 B per pixel); right after accum_begin, before the first add.  Everything else the
+        accumulation returns stays bit for bit.  Not on a sharded accumulation."""
+        self._call("rt_accum_track_filter", C.byref(flt) if flt is not None else None)
+
+    def accum_filtered(self, want_rgb8=False, want_weight=False):
+        """rt_accum_read_filtered: (img [rows, nx, 3] f32 = sum w rgb / sum w — the box mean of accum_read where the weight sum is not
+        positive —, rgb8 or None, made as the denoisers' is, weight [rows, nx] f32 = sum w or None)."""
+        img, rgb8, w, ptrs = self._accum_outputs(want_rgb8, want_weight)
+        self._call("rt_accum_read_filtered", *ptrs)
+        return img, rgb8, w
+
+    def accum_export_filter(self):
+        """rt_accum_export_filter: the filter and its plane of the open accumulation as an AccumFilter.  Read, not changed."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        snap = AccumFilter(nx, rows)
+        fs = snap.as_struct()
+        self._call("rt_accum_export_filter", C.byref(fs))
+        return AccumFilter(nx, rows, fs.first_sample, fs.done, fs.frame_id, plane=snap.plane, filter=fs.filter)
+
+    def accum_import_filter(self, snap):
+        """rt_accum_import_filter: puts an AccumFilter into the accumulation just begun — fresh, or right after accum_import of the state it
+        belongs to — and turns tracking on under its filter."""
+        fs = snap.as_struct()
+        self._call("rt_accum_import_filter", C.byref(fs))
+
+    def debug_filter_add(self, i0, rad):
+        """rt_debug_filter_add: the production resolve kernel over rad [n, rows, nx, 3] f32 — designed radiance in image order, as the samples
+        with the absolute indices i0 .. i0 + n - 1 — onto the filter plane of the open accumulation only."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        rad = np.ascontiguousarray(rad, dtype=np.float32)
+        assert rad.ndim == 4 and rad.shape[1:] == (rows, nx, 3), rad.shape
+        self._call("rt_debug_filter_add", int(i0), rad.shape[0], rad.ctypes.data_as(C.POINTER(C.c_float)))
 
     def accum_track_buckets(self, M):
         """rt_accum_track_buckets: the open accumulation also keeps the samples of every pixel in M buckets by sample index (12 M bytes per

@@ -7,6 +7,7 @@
 #pragma once
 #include "rt_accum_state.h"
 #include "rt_buckets_plan.h"
+#include "rt_filter_plan.h"
 #include "rt_halves_plan.h"
 
 #include <string>
@@ -69,6 +70,13 @@ inline PlaneTable halves_planes(const RtAccumHalves& hs, void* local, uint64_t n
 inline PlaneTable buckets_planes(const RtAccumBuckets& bs, uint32_t M, void* local, uint64_t npix) {
     PlaneTable t{};
     for (uint32_t b = 0; b < M; ++b) planes_push(t, bs.sum[b], (char*)local + buckets_plane(npix, b), RT_BUCKETS_SUM_BYTES);
+    return t;
+}
+
+// `local`: the accumulation's filter plane (behind the table in its buffer: rt_filter_plan.h)
+inline PlaneTable filter_planes(const RtAccumFilter& fs, void* local) {
+    PlaneTable t{};
+    planes_push(t, fs.plane, local, RT_FILTER_PIXEL_BYTES);
     return t;
 }
 

@@ -13,6 +13,7 @@
 #include "rt_halves.h"
 #include "rt_select.h"
 #include "rt_buckets.h"
+#include "rt_filter.h"
 #include "rt_display.h"
 #include "rt_glare.h"
 #include "rt_bvh.h"
@@ -145,6 +146,8 @@ struct RtCtx {
         bool halves = false;   // rt_accum_track_halves / rt_accum_import_halves: accum_halves holds the half sums and moments and every add keeps them
         bool added = false;    // an add of either kind or a merge has happened since rt_accum_begin (rt_accum_import_halves comes before)
         uint32_t buckets = 0;  // rt_accum_track_buckets / rt_accum_import_buckets: M, accum_buckets holds the bucket sums and every add keeps them; 0: not tracked
+        bool filter = false;   // rt_accum_track_filter / rt_accum_import_filter: accum_filter holds the table of `pf` and the plane, and every add keeps it
+        RtPixelFilter pf{};
         bool mirror = false;   // the context an RtMulti joins its shards into (rt_multi_accum.h): only rt_multi_accum_join writes the accumulation, for good
     } accum;
     DevBuf accum_sum, accum_mom, accum_sem, accum_partials; // (accum_sem: staging of out_sem; accum_partials: one f64 pair per workgroup + the 3 frame figures)
@@ -169,6 +172,10 @@ struct RtCtx {
     // robust_out: what a robust read-out writes — out (12 B) and the trims (3 B) per pixel in image order, the partial sums and the frame figures
     DevBuf accum_buckets, robust_out;
     RtRobustInfo* h_robust = nullptr; // page-locked: the figures as k_robust_final wrote them
+    // rt_accum_track_filter (rt_filter.h): the 256-entry table of the tracked filter, then the plane (sum w rgb, sum w), 16 B per pixel in the
+    // order of accum_sum (rt_filter_plan.h: filter_buffer_bytes); filter_out: what rt_accum_read_filtered writes — c (12 B) and W (4 B) per
+    // pixel in image order; filter_rad: the radiance slots rt_debug_filter_add uploads
+    DevBuf accum_filter, filter_out, filter_rad;
     // The one staging buffer of every export, import and merge: the planes of a state, of the halves or of the buckets in image order
     // (rt_accum_planes.h: planes_place), at most 192 B per pixel; rt_accum_read_halves borrows it for its two outputs
     DevBuf accum_stage;
@@ -263,6 +270,18 @@ HalfPlanes half_planes(const DevBuf& b, uint32_t npix) {
     const HalvesLayout l = halves_layout(npix);
     char* base = (char*)b.p;
     return HalfPlanes{{(float*)(base + l.sum[0]), (float*)(base + l.sum[1])}, {(double2*)(base + l.moments[0]), (double2*)(base + l.moments[1])}};
+}
+
+// What k_resolve_filter needs of the open accumulation, which tracks a filter (the slice's i0, s_count and flags are the caller's)
+FilterArgs filter_args(const RtCtx* ctx) {
+    const RtCtx::Accum& a = ctx->accum;
+    FilterArgs fa{};
+    fa.table = ctx->accum_filter.as<const float>();
+    fa.plane = (float4*)(ctx->accum_filter.as<char>() + RT_FILTER_TABLE_BYTES);
+    fa.nx = a.nx, fa.rows = a.rows, fa.npix = a.npix, fa.tiles_per_row = a.tiles_per_row, fa.tile_pixels = a.tile_pixels;
+    fa.seed_lo = (uint32_t)a.prm.seed, fa.seed_hi = (uint32_t)(a.prm.seed >> 32);
+    fa.radius = a.pf.radius, fa.scale = pixel_filter_scale(a.pf.radius);
+    return fa;
 }
 
 void free_scene(RtCtx* ctx) { // (the region stays: the next upload carves it again)
@@ -787,6 +806,7 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->accum_cnt), free_buf(ctx->accum_flag), free_buf(ctx->accum_info), free_buf(ctx->accum_cnt_out);
     free_buf(ctx->accum_stage);
     free_buf(ctx->accum_halves), free_buf(ctx->dn_halves);
+    free_buf(ctx->accum_filter), free_buf(ctx->filter_out), free_buf(ctx->filter_rad);
     free_buf(ctx->accum_buckets), free_buf(ctx->robust_out);
     if (ctx->h_resid) (void)hipHostFree(ctx->h_resid);
     free_buf(ctx->dn_select);
@@ -942,6 +962,11 @@ struct SampleSink {
     // rt_accum_track_buckets (rt_buckets.h): the M planes of bucket sums, kept by a kernel of their own in front of the resolve
     float* buckets = nullptr;
     uint32_t n_buckets = 0;
+    // rt_accum_track_filter (rt_filter.h): the table, the plane and the filter's figures, kept by a kernel of its own in front of the resolve
+    // (i0, s_count and the flags are the slice's: resolve_and_preview fills them in)
+    bool filter = false;
+    FilterArgs fa{};
+    uint32_t filter_reach = 0;
 };
 // What trace_samples enqueued, for the finalize, the copies and the statistics of its caller.
 struct Traced {
@@ -1158,6 +1183,23 @@ static int enqueue_slice(RtCtx* ctx, Frame& f, const WorkView& wv, uint32_t sl) 
         else hipLaunchKernelGGL(K<false>, (grid), dim3(256), 0, (st), __VA_ARGS__);        \
     } while (0)
 
+// k_resolve_filter<active, reach> over the 32 x 8 blocks of the frame on `st` (reach <= 3: pixel_filter_reach of a valid radius).
+static void launch_resolve_filter(hipStream_t st, bool active, uint32_t reach, const float* rad, const FilterArgs& fa) {
+    const dim3 grid((fa.nx + RT_FILTER_BLOCK_X - 1u) / RT_FILTER_BLOCK_X, (fa.rows + RT_FILTER_BLOCK_Y - 1u) / RT_FILTER_BLOCK_Y);
+#define FILTER_REACH(D)                                                                                  \
+    do {                                                                                                 \
+        if (active) hipLaunchKernelGGL((k_resolve_filter<true, D>), grid, dim3(256), 0, st, rad, fa);    \
+        else hipLaunchKernelGGL((k_resolve_filter<false, D>), grid, dim3(256), 0, st, rad, fa);          \
+    } while (0)
+    switch (reach) {
+    case 0u: FILTER_REACH(0); break;
+    case 1u: FILTER_REACH(1); break;
+    case 2u: FILTER_REACH(2); break;
+    default: FILTER_REACH(3); break;
+    }
+#undef FILTER_REACH
+}
+
 // Resolves the slice's `sc` samples per pixel onto the running sum, in sample order, and shows the `done` of `spp` samples so far to
 // the progress callback.
 static int resolve_and_preview(RtCtx* ctx, const Frame& f, const SampleSink& sink, const float* rad, uint32_t sc, uint32_t done, uint32_t rows) {
@@ -1168,6 +1210,11 @@ static int resolve_and_preview(RtCtx* ctx, const Frame& f, const SampleSink& sin
     const uint32_t i0 = sink.first_sample + (done - sc); // the absolute index of the slice's first sample
     if (sink.halves) KERNEL_PAIR(k_resolve_halves, active, grid, st, rad, sink.hp, sink.converged, npix, i0, sc);
     if (sink.buckets) KERNEL_PAIR(k_resolve_buckets, active, grid, st, rad, sink.buckets, sink.converged, npix, sink.n_buckets, i0, sc);
+    if (sink.filter) {
+        FilterArgs fa = sink.fa;
+        fa.flag = sink.converged, fa.i0 = i0, fa.s_count = sc;
+        launch_resolve_filter(st, active, sink.filter_reach, rad, fa);
+    }
     if (sink.chm) KERNEL_PAIR(k_resolve_moments_channels, active, grid, st, rad, f.acc, sink.mom, sink.chm, sink.converged, sink.cnt, npix, sc);
     else if (sink.mom || active) KERNEL_PAIR(k_resolve_moments, active, grid, st, rad, f.acc, sink.mom, sink.converged, sink.cnt, npix, sc);
     else hipLaunchKernelGGL(k_resolve, grid, dim3(256), 0, st, rad, f.acc, npix, sc);
@@ -1728,6 +1775,7 @@ static int accum_add(RtCtx* ctx, uint32_t n_samples, bool adaptive, const RtAdap
     if (a.channels) sink.chm = ctx->accum_chm.as<double2>();
     if (a.halves) sink.halves = true, sink.hp = half_planes(ctx->accum_halves, a.npix);
     if (a.buckets) sink.buckets = ctx->accum_buckets.as<float>(), sink.n_buckets = a.buckets;
+    if (a.filter) sink.filter = true, sink.fa = filter_args(ctx), sink.filter_reach = pixel_filter_reach(a.pf.radius);
     if ((rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr))) return rc;
     if (tr.npix == 0u) return nothing_traced();
     if (tr.npix != a.npix || tr.tiles_per_row != a.tiles_per_row || tr.tile_pixels != a.tile_pixels) {
@@ -2299,6 +2347,7 @@ int rt_accum_import(RtCtx* ctx, const RtAccumState* st) {
     if ((rc = refuse_mirror(ctx, "rt_accum_import")) || (rc = require_open(ctx, "rt_accum_import"))) return rc;
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks halves already (import the state first, then rt_accum_import_halves)");
     if (a.buckets) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks buckets already (import the state first, then rt_accum_import_buckets)");
+    if (a.filter) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks a filter already (import the state first, then rt_accum_import_filter)");
     if (a.done != 0u || a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_import: samples were added already (call it right after rt_accum_begin)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import: ") + why);
     if ((rc = require_match(ctx, "rt_accum_import", snapshot_header(*st), "state", SNAPSHOT_FIRST_SAMPLE))) return rc;
@@ -2325,6 +2374,7 @@ int rt_accum_merge(RtCtx* ctx, const RtAccumState* st) {
     if ((rc = refuse_mirror(ctx, "rt_accum_merge")) || (rc = require_open(ctx, "rt_accum_merge"))) return rc;
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks halves: a merge of halves is not covered (rtow_mi355x.h)");
     if (a.buckets) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks buckets: a merge of buckets is not covered (rtow_mi355x.h)");
+    if (a.filter) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks a filter: a merge of filter planes is not covered (rtow_mi355x.h)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_merge: ") + why);
     if (a.adaptive || (st->planes & RT_ACCUM_STATE_COUNTS))
         return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: an adaptive accumulation or state: windows of pixels with different sample counts are not contiguous");
@@ -2470,6 +2520,132 @@ int rt_accum_import_halves(RtCtx* ctx, const RtAccumHalves* hs) {
         if ((rc = planes_from_host(ctx, t, true))) return rc;
     }
     a.halves = true;
+    return RT_OK;
+}
+
+// ---- pixel reconstruction filters (rtow_mi355x.h "Pixel reconstruction filters", csrc/rt_filter.h, csrc/rt_filter_plan.h) -------------------
+int rt_pixel_filter_check(const RtPixelFilter* filter) { return pixel_filter_invalid(filter) ? RT_ERR_INVALID : RT_OK; }
+int rt_pixel_filter_table(const RtPixelFilter* filter, float* table, uint32_t* reach) { return pixel_filter_table(filter, table, reach) ? RT_ERR_INVALID : RT_OK; }
+int rt_accum_filter_check(const RtAccumFilter* fs) { return accum_filter_invalid(fs) ? RT_ERR_INVALID : RT_OK; }
+
+static int refuse_filter_on_shard(RtCtx* ctx, const char* who) {
+    return ctx->accum.prm.shard_count > 1u
+               ? fail(ctx, RT_ERR_STATE, std::string(who) + ": a sharded accumulation (shard_count > 1): a row-interleaved shard has no neighbourhoods")
+               : RT_OK;
+}
+// The accumulation's filter buffer for npix pixels (kept for the next accumulation) with the table of `pf`, a valid filter, uploaded.
+static int ensure_filter(RtCtx* ctx, uint32_t npix, const RtPixelFilter& pf) {
+    if (const int rc = ensure(ctx, ctx->accum_filter, filter_buffer_bytes(npix))) return rc;
+    float table[RT_FILTER_TABLE];
+    (void)pixel_filter_table(&pf, table, nullptr);
+    return copy_to_device(ctx, ctx->accum_filter.p, table, sizeof(table));
+}
+
+int rt_accum_track_filter(RtCtx* ctx, const RtPixelFilter* filter) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    int rc;
+    if ((rc = refuse_mirror(ctx, "rt_accum_track_filter")) || (rc = require_open(ctx, "rt_accum_track_filter"))) return rc;
+    if (const char* why = pixel_filter_invalid(filter)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_track_filter: ") + why);
+    if ((rc = refuse_filter_on_shard(ctx, "rt_accum_track_filter"))) return rc;
+    if (a.filter)
+        return pixel_filter_same(a.pf, *filter) ? RT_OK : fail(ctx, RT_ERR_STATE, "rt_accum_track_filter: the accumulation tracks another filter already");
+    if (a.done != 0u || a.adaptive || a.added)
+        return fail(ctx, RT_ERR_STATE, "rt_accum_track_filter: the accumulation holds samples already (call it right after rt_accum_begin; after rt_accum_import "
+                                       "the plane comes through rt_accum_import_filter)");
+    if (a.npix) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        if ((rc = ensure_filter(ctx, a.npix, *filter))) return rc;
+        RT_HIP(ctx, hipMemsetAsync(ctx->accum_filter.as<char>() + RT_FILTER_TABLE_BYTES, 0, (size_t)a.npix * RT_FILTER_PIXEL_BYTES, ctx->stream));
+    }
+    a.filter = true, a.pf = *filter;
+    return RT_OK;
+}
+
+int rt_accum_read_filtered(RtCtx* ctx, float* out_rgb_f32, uint8_t* out_rgb8, float* out_weight) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    int rc;
+    if ((rc = require_open(ctx, "rt_accum_read_filtered"))) return rc;
+    if (!a.filter) return fail(ctx, RT_ERR_STATE, "rt_accum_read_filtered: the accumulation does not track a filter (rt_accum_track_filter)");
+    if (a.npix == 0u || (!out_rgb_f32 && !out_rgb8 && !out_weight)) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const uint32_t npix = a.npix;
+    if ((rc = ensure(ctx, ctx->filter_out, (size_t)npix * 4 * sizeof(float)))) return rc;
+    if (out_rgb8 && (rc = ensure(ctx, ctx->out_u8, (size_t)npix * 3))) return rc;
+    float* d_rgb = ctx->filter_out.as<float>();
+    float* d_w = d_rgb + 3 * (size_t)npix;
+    const AccumReader r = accum_reader(ctx, st);
+    ACCUM_READER(k_filter_read, r, (const float4*)filter_args(ctx).plane, ctx->accum_sum.as<const float>(), r.cnt, d_rgb, out_weight ? d_w : nullptr, r.nx, r.rows, r.n,
+                 r.tiles_per_row, r.tile_pixels);
+    if ((rc = denoise_finish(ctx, d_rgb, out_rgb_f32, out_rgb8))) return rc; // (the quantisation or the presentation of the filtered image, and the copies)
+    if (out_weight) RT_HIP(ctx, hipMemcpyAsync(out_weight, d_w, (size_t)npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    display_commit(ctx);
+    return RT_OK;
+}
+
+int rt_accum_export_filter(RtCtx* ctx, RtAccumFilter* fs) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!fs) return fail(ctx, RT_ERR_INVALID, "rt_accum_export_filter: the RtAccumFilter is NULL");
+    if (const int rc = require_open(ctx, "rt_accum_export_filter")) return rc;
+    if (!a.filter) return fail(ctx, RT_ERR_STATE, "rt_accum_export_filter: the accumulation does not track a filter (rt_accum_track_filter)");
+    if (a.npix && fs->plane) {
+        PlaneTable t = filter_planes(*fs, filter_args(ctx).plane);
+        if (const int rc = planes_to_host(ctx, t)) return rc;
+    }
+    snapshot_header_put(*fs, accum_header(a));
+    fs->reserved[0] = fs->reserved[1] = 0u;
+    fs->filter = a.pf;
+    return RT_OK;
+}
+
+int rt_accum_import_filter(RtCtx* ctx, const RtAccumFilter* fs) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    int rc;
+    if ((rc = refuse_mirror(ctx, "rt_accum_import_filter")) || (rc = require_open(ctx, "rt_accum_import_filter"))) return rc;
+    if (a.added) return fail(ctx, RT_ERR_STATE, "rt_accum_import_filter: samples were added since rt_accum_begin (call it right after rt_accum_begin or rt_accum_import)");
+    if ((rc = refuse_filter_on_shard(ctx, "rt_accum_import_filter"))) return rc;
+    if (const char* why = accum_filter_invalid(fs)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import_filter: ") + why);
+    if ((rc = require_match(ctx, "rt_accum_import_filter", snapshot_header(*fs), "filter plane", SNAPSHOT_FIRST_AND_DONE))) return rc;
+    if (a.filter && !pixel_filter_same(a.pf, fs->filter))
+        return fail(ctx, RT_ERR_INVALID, "rt_accum_import_filter: the filter of the snapshot is not the one the accumulation tracks");
+    if (a.npix) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        if (!a.filter && (rc = ensure_filter(ctx, a.npix, fs->filter))) return rc; // every allocation first: a failure cannot leave the accumulation half imported
+        PlaneTable t = filter_planes(*fs, ctx->accum_filter.as<char>() + RT_FILTER_TABLE_BYTES);
+        if ((rc = planes_from_host(ctx, t, true))) return rc;
+    }
+    a.filter = true, a.pf = fs->filter;
+    return RT_OK;
+}
+
+int rt_debug_filter_add(RtCtx* ctx, uint32_t i0, uint32_t n_samples, const float* rad) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (const int rc = require_open(ctx, "rt_debug_filter_add")) return rc;
+    if (!a.filter) return fail(ctx, RT_ERR_STATE, "rt_debug_filter_add: the accumulation does not track a filter (rt_accum_track_filter)");
+    if (!rad || n_samples == 0u || n_samples > 4096u || (uint64_t)i0 + n_samples > (1ull << 32))
+        return fail(ctx, RT_ERR_INVALID, "rt_debug_filter_add: rad NULL, n_samples outside 1 .. 4096, or i0 + n_samples above 2^32");
+    if (a.npix == 0u) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    // image order -> the radiance slots of a slice: slot = s * npix + local pixel, RT_RAD_FLOATS floats each
+    std::vector<float> slots((size_t)n_samples * a.npix * RT_RAD_FLOATS, 0.0f);
+    for (uint32_t s = 0; s < n_samples; ++s)
+        for (uint32_t p = 0; p < a.npix; ++p) {
+            const size_t lp = local_of_pixel(a.nx, a.tiles_per_row, a.tile_pixels, p % a.nx, p / a.nx);
+            for (int c = 0; c < 3; ++c) slots[RT_RAD_FLOATS * ((size_t)s * a.npix + lp) + c] = rad[3 * ((size_t)s * a.npix + p) + c];
+        }
+    if (const int rc = ensure(ctx, ctx->filter_rad, slots.size() * sizeof(float))) return rc;
+    if (const int rc = copy_to_device(ctx, ctx->filter_rad.p, slots.data(), slots.size() * sizeof(float))) return rc;
+    FilterArgs fa = filter_args(ctx);
+    fa.flag = nullptr, fa.i0 = i0, fa.s_count = n_samples;
+    launch_resolve_filter(ctx->stream, false, pixel_filter_reach(a.pf.radius), ctx->filter_rad.as<const float>(), fa);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 

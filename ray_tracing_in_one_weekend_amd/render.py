@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from . import AccumBuckets, AccumState, MultiRenderer, Renderer, RtError, Scene, display_check, glare_check, make_display, make_glare, make_params, make_select, select_check, output_file_name, register_default_images, save_png
+from . import AccumBuckets, AccumFilter, AccumState, make_pixel_filter, pixel_filter_check, MultiRenderer, Renderer, RtError, Scene, display_check, glare_check, make_display, make_glare, make_params, make_select, select_check, output_file_name, register_default_images, save_png
 from . import _ffi
 from .images import write_pfm
 
@@ -203,6 +203,16 @@ def main(argv=None):
     ap.add_argument("--glare-threshold", type=float, default=0.0, metavar="T", help="with --glare: only the luminance above T glows (0: all of it)")
     ap.add_argument("--glare-out", default=None, metavar="FILE.pfm",
                     help="with --glare: also write the glared linear f32 image as a PFM (a plain render only, as --hdr-out, which stays the un-glared frame)")
+    ap.add_argument("--pixel-filter", choices=("box", "tent", "gaussian", "mitchell", "blackman-harris"), default=None,
+                    help="reconstruct every pixel from its own samples AND its neighbours', weighted by this filter at their sub-pixel distance "
+                         "(rt_accum_track_filter: 16 B per pixel more), instead of the reference's box over the pixel; the image written is the "
+                         "filtered one, and --checkpoint carries the plane in FILE.filter.npz, which --resume picks up.  Does not combine with "
+                         "--denoise, --devices or --merge")
+    ap.add_argument("--filter-radius", type=float, default=None, metavar="R",
+                    help="with --pixel-filter: the radius in pixels, %g..%g (default: box 0.5, tent 1, gaussian 1.5, mitchell 2, blackman-harris 1.5)"
+                         % (_ffi.FILTER_MIN_RADIUS, _ffi.FILTER_MAX_RADIUS))
+    ap.add_argument("--filter-param", type=float, nargs="+", default=None, metavar="P",
+                    help="with --pixel-filter gaussian: sigma (default 0.5); with mitchell: B C (default 1/3 1/3)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--devices", default=None, metavar="ID,ID,...",
                     help="render on these devices of the node at once (rt_multi_*): every device takes row-interleaved bands of the frame; the "
@@ -269,6 +279,27 @@ def main(argv=None):
     elif a.glare_out:
         ap.error("--glare-out needs --glare")
     halves = a.residual_target is not None or (a.denoise and a.denoise_guide == "halves")
+    a.filter = None
+    if a.pixel_filter is None and (a.filter_radius is not None or a.filter_param is not None):
+        ap.error("--filter-radius and --filter-param need --pixel-filter")
+    if a.pixel_filter is not None:
+        if a.denoise:
+            ap.error("--pixel-filter does not combine with --denoise: the pixels of a filtered image are correlated, and the variance guides of "
+                     "the denoisers do not describe it")
+        if multi:
+            ap.error("--pixel-filter does not combine with --devices: a row-interleaved shard has no neighbourhoods (rt_accum_track_filter)")
+        if a.merge:
+            ap.error("--pixel-filter does not combine with --merge: a merge of filter planes is not covered (rt_accum_merge)")
+        if a.preview_every or a.robust is not None or a.residual_target is not None or a.hdr_out or a.glare_out:
+            ap.error("--pixel-filter does not combine with --preview-every, --robust, --residual-target, --hdr-out or --glare-out")
+        p = a.filter_param or []
+        want = {"gaussian": 1, "mitchell": 2}.get(a.pixel_filter, 0)
+        if p and len(p) != want:
+            ap.error("--filter-param takes sigma with --pixel-filter gaussian, B C with mitchell, and nothing with the other filters")
+        a.filter = make_pixel_filter(a.pixel_filter, a.filter_radius, sigma=p[0] if want == 1 and p else None, B=p[0] if want == 2 and p else None,
+                                     C=p[1] if want == 2 and p else None)
+        if not pixel_filter_check(a.filter):
+            ap.error("--pixel-filter: --filter-radius takes %g..%g, sigma must be > 0, every value finite" % (_ffi.FILTER_MIN_RADIUS, _ffi.FILTER_MAX_RADIUS))
     if a.denoise_levels is not None:
         if not a.denoise or a.denoise_guide == "halves" or a.residual_target is not None:
             ap.error("--denoise-levels needs --denoise with --denoise-guide luminance or channels")
@@ -319,7 +350,7 @@ def main(argv=None):
     progressive = a.adaptive_tolerance is not None or a.noise_target is not None or a.denoise
     if (a.hdr_out or a.glare_out) and (progressive or halves or a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets):
         ap.error("--hdr-out and --glare-out write the image of a plain render: they do not combine with the progressive options")
-    if a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets or (multi and progressive):
+    if a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets or a.filter is not None or (multi and progressive):
         if a.preview_every:
             ap.error("--checkpoint, --resume, --first-sample and --merge do not combine with --preview-every")
         if a.adaptive_tolerance is not None and a.noise_target is not None:
@@ -453,6 +484,18 @@ def render_with_state(a, rend, scene, flags, file_name, t0):
         elif a.want_buckets:
             n_buckets = a.buckets if a.buckets is not None else DEFAULT_BUCKETS
             rend.accum_track_buckets(n_buckets)
+        if state and a.filter is not None:  # the plane that was checkpointed beside the state goes on with it, under the same filter
+            try:
+                plane = AccumFilter.load(a.resume + ".filter.npz")
+            except (OSError, ValueError, KeyError) as e:
+                print(f"error: --pixel-filter with --resume needs {a.resume}.filter.npz, the plane checkpointed beside the state: {e}", file=sys.stderr)
+                return 2
+            if bytes(plane.filter) != bytes(a.filter):
+                print(f"error: {a.resume}.filter.npz was summed under another filter than --pixel-filter, --filter-radius and --filter-param name", file=sys.stderr)
+                return 2
+            rend.accum_import_filter(plane)
+        elif a.filter is not None:
+            rend.accum_track_filter(a.filter)
         done, steps, n_rays, seconds = (state.done if state else 0), 0, 0, 0.0
 
         def finished():
@@ -467,6 +510,8 @@ def render_with_state(a, rend, scene, flags, file_name, t0):
         def save_state():
             if n_buckets:  # the buckets first: a state without its buckets resumes nowhere, buckets without a state are ignored
                 rend.accum_export_buckets().save(a.checkpoint + ".buckets.npz")
+            if a.filter is not None:  # likewise the filter plane
+                rend.accum_export_filter().save(a.checkpoint + ".filter.npz")
             rend.accum_export().save(a.checkpoint)
 
         while not finished():
@@ -497,6 +542,8 @@ def render_with_state(a, rend, scene, flags, file_name, t0):
             save_png(a.firefly_map, np.ascontiguousarray(np.repeat(grey[..., None], 3, axis=2)))
     if a.denoise:
         rgb8 = _denoised(a, rend)
+    if a.filter is not None:
+        rgb8 = rend.accum_filtered(want_rgb8=True)[1]
     rend.accum_end()
     print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
     save_png(file_name, rgb8)
