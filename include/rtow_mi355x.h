@@ -1258,6 +1258,127 @@ int rt_accum_export_filter(RtCtx* ctx, RtAccumFilter* fs);
  * as it was.  Synchronises once. */
 int rt_accum_import_filter(RtCtx* ctx, const RtAccumFilter* fs);
 
+/* -- First-hit features: albedo, normal and depth of the primary hit, with their second moments -------------------------------------------
+ * What a feature-guided denoiser (Rousselle, Manzi, Zwicker 2013) or a compositor asks a renderer for.  An accumulation that TRACKS
+ * FEATURES also keeps one RtFeaturePixel per pixel, 64 B more.  Nothing is taken from the paths that are traced: the first hit of sample s
+ * of pixel p is a function of the frame, the scene and (p, s), and a kernel of its own (csrc/rt_features.h) recomputes it — the primary ray
+ * exactly as the render makes it (the pixel jitter, the thin lens of rt_set_lens), its time under rt_set_motion, the closest hit as the
+ * context's search finds it (the tree, or every primitive under RT_FLAG_BRUTE_FORCE; quads and triangles of rt_set_quads included; a light
+ * set changes nothing), and a constant medium's scatter decision at depth 0 with the draws the render uses.
+ * Which samples.  Sample s, by its absolute index (first_sample + the samples before it), contributes iff s % stride == 0.  So the planes
+ * after the samples [a, b) are the same bits however [a, b) is cut into adds and slices.  In an adaptive add a converged pixel takes none.
+ * What sample s contributes, as (a, n, hit, z):
+ *   miss                       a = (1, 1, 1), n = 0, no hit
+ *   surface                    hit, z = t of the hit; n = the world-space, face-forwarded unit normal the shading uses (spheres, rectangles,
+ *                              planar primitives, unwound through Translate / RotateY wrappers, chains of any length); a by material tag:
+ *                              0, 1, 2, 5 .. 11 the material's first texture at the hit, at the (uv, p) the shading evaluates it at;
+ *                              3 (Metal) the material's colour; 4 (Dielectric) and 12 (DisneyClearcoat) (1, 1, 1); any other tag 0;
+ *                              then per channel a NaN becomes 0 and the value is clamped to [0, 1]
+ *   medium scatter at depth 0  hit, z = t of the scatter; n = 0; a = the medium's Isotropic texture, NaN -> 0, clamped likewise
+ * and what the record does with it, every operation one IEEE operation without contraction, in ascending order of s:
+ *   albedo[c] += a[c], normal[c] += n[c] (f32);   n_f += 1;
+ *   a2 += ((double)a[0] * (double)a[0] + (double)a[1] * (double)a[1]) + (double)a[2] * (double)a[2];   n2 likewise over n;
+ *   hit:  n_h += 1;  z1 += (double)z;  z2 += (double)z * (double)z.
+ * Read-out (rt_accum_read_features), per pixel, with N = (float)n_f:  albedo / N and normal / N per component (0 where n_f == 0);
+ * depth = (float)(z1 / (double)n_h) (0 where n_h == 0);  hit = (float)n_h / N (0 where n_f == 0);  var = the variance of the MEAN of
+ * albedo, normal and depth: for the vectors, with S = ((double)sum[0]^2 + (double)sum[1]^2) + (double)sum[2]^2 and n = (double)n_f,
+ * q = (a2 - S / n) / (n - 1), clamped below at 0, then (float)(q / n); for the depth the same on (z2, z1 * z1, n_h).  0 where the count
+ * is below 2.
+ * Everything an accumulation returned before is unchanged in every bit with tracking on or off, and an accumulation that does not track
+ * features launches no kernel it did not launch before.
+ * State.  RtAccumFeatures carries the stride and the records in the row order of out_rgb_f32.  Resume is rt_accum_begin, rt_accum_import,
+ * rt_accum_import_features: from then on the records are bit for bit those of the uninterrupted accumulation.
+ * Not covered, refused with RT_ERR_UNSUPPORTED and a message: a sharded accumulation (shard_count > 1), hence rt_multi_accum_begin with
+ * RT_MULTI_UNSUPPORTED_FEATURES (the joined context of an RtMulti refuses the call as it refuses every rt_accum_track_*: RT_ERR_STATE);
+ * rt_accum_merge and rt_accum_import on an accumulation that tracks features.  The denoisers stay colour-guided.  DESIGN.md "First-hit
+ * features". */
+#define RT_FEATURES_MIN_STRIDE 1u
+#define RT_FEATURES_MAX_STRIDE 64u
+typedef struct RtFeatures {
+    uint32_t stride;   /* RT_FEATURES_MIN_STRIDE .. RT_FEATURES_MAX_STRIDE: every stride-th sample, by absolute index */
+    uint32_t reserved; /* 0 */
+} RtFeatures;
+typedef struct RtFeaturePixel {
+    float albedo[3]; /* sum of a */
+    uint32_t n_f;    /* feature samples taken */
+    float normal[3]; /* sum of n */
+    uint32_t n_h;    /* of which hit a surface or scattered in a medium */
+    double a2, n2, z1, z2; /* sum |a|^2, sum |n|^2, sum z, sum z^2 */
+} RtFeaturePixel;
+typedef struct RtAccumFeatures {
+    uint32_t nx, rows;           /* the frame: rows = ny (no shards) */
+    uint32_t first_sample, done; /* those of the accumulation the records belong to */
+    uint32_t reserved[2];        /* 0 */
+    uint64_t frame_id;           /* rt_accum_frame_id of the frame */
+    RtFeatures features;         /* the stride the records were summed under */
+    RtFeaturePixel* plane;       /* [rows*nx] */
+} RtAccumFeatures;
+/* GPU-free, no context.  RT_OK, or RT_ERR_INVALID: `features` NULL, a stride outside its range, reserved not 0. */
+int rt_features_check(const RtFeatures* features);
+/* Makes the open accumulation track features and clears the records.  The rules of rt_accum_track_filter: after rt_accum_begin and before
+ * the first add, else RT_ERR_STATE; a second call with the same stride is RT_OK and changes nothing, with another one RT_ERR_STATE;
+ * RT_ERR_STATE on the joined context of an RtMulti.  RT_ERR_UNSUPPORTED on a sharded accumulation.  RT_ERR_INVALID: what rt_features_check
+ * refuses.  Tracking ends with the accumulation.  Combines freely with the other rt_accum_track_* calls and with adaptive adds. */
+int rt_accum_track_features(RtCtx* ctx, const RtFeatures* features);
+/* The read-out above, in image order as rt_accum_read lays its outputs out: out_albedo [ny*nx*3], out_normal [ny*nx*3], out_depth [ny*nx],
+ * out_hit [ny*nx], out_var [ny*nx*3] (albedo, normal, depth); each may be NULL.  The accumulation is read and not changed.  Synchronises the
+ * context's stream once.  RT_ERR_STATE: no open accumulation, or it does not track features. */
+int rt_accum_read_features(RtCtx* ctx, float* out_albedo, float* out_normal, float* out_depth, float* out_hit, float* out_var);
+/* GPU-free.  RT_OK, or RT_ERR_INVALID unless: `fs` non-NULL, both reserved words 0, the plane non-NULL, first_sample + done <= 2^32 - 1,
+ * features that rt_features_check accepts.  Values are not judged. */
+int rt_accum_features_check(const RtAccumFeatures* fs);
+/* Fills the scalar fields and the stride of `fs` and writes the records where its pointer is non-NULL.  Reads, and changes nothing.
+ * Synchronises the context's stream once.  RT_ERR_STATE: no open accumulation, or it does not track features. */
+int rt_accum_export_features(RtCtx* ctx, RtAccumFeatures* fs);
+/* Puts `fs` into the open accumulation and turns tracking on under its stride.  Allowed while the accumulation has had no add (and no
+ * merge) since rt_accum_begin — fresh with done 0, or after rt_accum_import — else RT_ERR_STATE; RT_ERR_UNSUPPORTED on a sharded
+ * accumulation.  Values are copied as bits.  RT_ERR_INVALID: rt_accum_features_check fails, nx, rows, frame_id, first_sample or done differ
+ * from the accumulation's, or the accumulation tracks features already and the snapshot's stride is another one.  A failed call leaves the
+ * accumulation as it was.  Synchronises once. */
+int rt_accum_import_features(RtCtx* ctx, const RtAccumFeatures* fs);
+
+/* -- The feature-guided filter: rt_accum_denoise with the first-hit features beside the colour guide (Rousselle, Manzi, Zwicker 2013) -------
+ * Inputs per pixel, in image order: c, y, v as in "Denoising"; from the pixel's RtFeaturePixel the means abar = albedo / (float)n_f and
+ * nbar = normal / (float)n_f per component, zbar = (float)(z1 / (double)n_h) (0 where n_h == 0), and the variances of the mean va, vn, vz
+ * exactly as rt_accum_read_features returns them (vz 0 where n_h < 2).  A pixel with n_f < 2 has NaN for all ten: it stays what it is and
+ * spreads to no other pixel.
+ * Demodulation (demodulate != 0), before anything else, per pixel: a'[ch] = abar[ch] > 1/64 ? abar[ch] : 1/64;
+ * Ya = (0.2126f a'[0] + 0.7152f a'[1]) + 0.0722f a'[2];  c[ch] = c[ch] / a'[ch];  y = y / Ya;  v = v / (Ya * Ya).
+ * Per pair (p, q), q in the window of radius R inside the image, in the order of "Denoising":
+ *   D_c = the patch distance of "Denoising" on (y, v): the same operands in the same order.
+ *   for each feature f in `use` (= use_mask), in the order albedo, normal, depth, with f_p, f_q the means and vf_p, vf_q the variances:
+ *     s2 = (dx dx + dy dy) + dz dz over the components of f_p - f_q (depth: dz dz alone);  vmin = vf_q < vf_p ? vf_q : vf_p;
+ *     floor = tau_albedo, tau_normal, or tau_depth * (zbar_p * zbar_p);  vs = vf_p + vf_q;  vmax = vs > floor ? vs : floor;
+ *     d_f = (s2 - (vf_p + vmin)) / (1e-10f + (k_f * k_f) * vmax)
+ *   m = D_c < 0 ? 0 : D_c;  then for each used f in that order: m = d_f > m ? d_f : m.   (The min-of-weights rule of the 2013 paper: the
+ *   weight falls monotonically in m, so one weight is evaluated.)
+ *   u = 1 - 0.25f m;  u = u > 0 ? u : 0;  where D_c or a used d_f is NaN: u = 0.   Then w, den and num as in "Denoising".
+ * Output per channel: den != 0 ? num / den : c (the possibly demodulated c of p), times a'[ch] of p where demodulate != 0.
+ * With use == 0 and demodulate == 0 the output is rt_accum_denoise's, bit for bit.  out_rgb8 goes where rt_accum_denoise's goes.
+ * Defaults (RT_FEATURE_GUIDE_DEFAULT_*): k 0.6 for each feature and tau 1e-3, the paper's values; no error figure of this filter on this
+ * renderer's frames exists yet (DESIGN.md "First-hit features").  The half, select, multi-scale and robust filters stay colour-guided. */
+#define RT_FEATURE_USE_ALBEDO 1u
+#define RT_FEATURE_USE_NORMAL 2u
+#define RT_FEATURE_USE_DEPTH  4u
+#define RT_FEATURE_GUIDE_DEFAULT_K 0.6f
+#define RT_FEATURE_GUIDE_DEFAULT_TAU 1e-3f
+typedef struct RtFeatureGuide {
+    float k_albedo, k_normal, k_depth;       /* strengths: finite, > 0 */
+    float tau_albedo, tau_normal, tau_depth; /* variance floors: finite, >= 0; tau_depth is relative to zbar_p^2 */
+    uint32_t use_mask;                       /* `use`: RT_FEATURE_USE_* (the field is not named `use`, a keyword of Rust) */
+    uint32_t demodulate;                     /* 0, or anything else: filter c / albedo and multiply the albedo back */
+    uint32_t reserved[2];                    /* 0 */
+} RtFeatureGuide;
+/* GPU-free, no context.  RT_OK, or RT_ERR_INVALID: `guide` NULL, a strength not finite or <= 0, a floor not finite or < 0, a bit of `use`
+ * above RT_FEATURE_USE_DEPTH, a reserved word not 0. */
+int rt_feature_guide_check(const RtFeatureGuide* guide);
+/* The filter above over the open accumulation; `dn` as for rt_accum_denoise (NULL: its defaults), `guide` must not be NULL.  Outputs as
+ * rt_accum_denoise's.  The accumulation is read and not changed.  Synchronises the context's stream once.  RT_ERR_STATE: no accumulation
+ * is open, it does not track features, fewer than 2 samples are done, or fewer than 2 feature samples were taken (the samples done hold
+ * fewer than 2 multiples of the stride).  RT_ERR_UNSUPPORTED: a shard.  RT_ERR_INVALID: what rt_feature_guide_check or rt_accum_denoise
+ * refuses of its parameters. */
+int rt_accum_denoise_features(RtCtx* ctx, const RtDenoise* dn, const RtFeatureGuide* guide, float* out_rgb_f32, uint8_t* out_rgb8);
+
 /* -- multi-GPU: one process, the GPUs of one node, the framebuffer gather inside the library ---------------------
  * SURVEY.md 8(b)/(e).  The reference's only parallelism is the per-column fan-out over a thread pool with the
  * world shared read-only (main.rs:72-108); here the scene is replicated on every device, device r renders the image
@@ -1321,10 +1442,13 @@ int rt_multi_render(RtMulti* m, const RtCamera* cam, const RtParams* params, flo
 #define RT_MULTI_TRACK_CHANNELS 1u /* rt_accum_track_channels on every shard */
 #define RT_MULTI_TRACK_HALVES   2u /* rt_accum_track_halves */
 #define RT_MULTI_TRACK_BUCKETS  4u /* rt_accum_track_buckets(M) */
+/* No track flag: the bit that would ask for rt_accum_track_features on every shard, which is not covered.  rt_multi_accum_begin knows it
+ * in order to answer RT_ERR_UNSUPPORTED with a message, and begins nothing. */
+#define RT_MULTI_UNSUPPORTED_FEATURES 32u
 /* rt_accum_begin on every device: device i on shard (band, n, i) of the frame of `params` — band = shard_band, 0 = 8; shard_count and
  * shard_id are ignored, as in rt_multi_render —, then the tracking that `track` names.  RT_ERR_INVALID before any device is touched: cam or
  * params NULL, a bit in `track` that is no RT_MULTI_TRACK_*, M outside 3 .. RT_BUCKETS_MAX with RT_MULTI_TRACK_BUCKETS (M is not looked
- * at without it).  Everything else as rt_accum_begin refuses it.  A failure leaves no accumulation open anywhere.  An open one is replaced. */
+ * at without it).  RT_ERR_UNSUPPORTED, likewise before any device is touched: RT_MULTI_UNSUPPORTED_FEATURES.  Everything else as rt_accum_begin refuses it.  A failure leaves no accumulation open anywhere.  An open one is replaced. */
 int rt_multi_accum_begin(RtMulti* m, const RtCamera* cam, const RtParams* params, uint32_t first_sample, uint32_t track, uint32_t M);
 /* rt_accum_add / rt_accum_add_adaptive on every device.  `stats` (may be NULL) sums the devices' as rt_multi_render does.  Complete on return. */
 int rt_multi_accum_add(RtMulti* m, uint32_t n_samples, RtStats* stats);

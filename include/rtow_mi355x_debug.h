@@ -306,6 +306,18 @@ int rt_debug_accum_set_moments(RtCtx* ctx, uint32_t pixel, double s1, double s2)
  * (an impulse, a NaN, 1e30) reaches the kernel without a trace.  RT_ERR_STATE: no open accumulation, or it does not track a filter;
  * RT_ERR_INVALID: rad NULL, n_samples 0 or above 4096, i0 + n_samples above 2^32. */
 int rt_debug_filter_add(RtCtx* ctx, uint32_t i0, uint32_t n_samples, const float* rad);
+/* Test hook for the first-hit features (rtow_mi355x.h "First-hit features"): the production kernel k_features over the samples with the
+ * absolute indices i0 .. i0 + n_samples - 1 of every pixel, onto the feature records of the open accumulation ONLY: nothing is traced, and
+ * its sums, moments, counts and `done` are untouched.  The search form is the one an add would use: the tree as the scene upload placed it,
+ * or every primitive where the context has no tree or the accumulation's RtParams hold RT_FLAG_BRUTE_FORCE.  RT_ERR_STATE: no open
+ * accumulation, or it does not track features; RT_ERR_INVALID: n_samples 0 or above 4096, i0 + n_samples above 2^32. */
+int rt_debug_features_add(RtCtx* ctx, uint32_t i0, uint32_t n_samples);
+/* Test hook for the feature-guided filter (rtow_mi355x.h "The feature-guided filter"): the kernels of rt_accum_denoise_features — the
+ * demodulation, then k_denoise_features — over host arrays in image order: rgb [rows*nx*3], y and v [rows*nx], feat_mean [rows*nx*7]
+ * (abar 3, nbar 3, zbar) and feat_var [rows*nx*3] (va, vn, vz) -> out_rgb_f32 [rows*nx*3].  No accumulation is needed.  RT_ERR_INVALID: a
+ * NULL array, nx * rows outside 1 .. 2^28, what rt_accum_denoise refuses of `dn`, what rt_feature_guide_check refuses of `guide`. */
+int rt_debug_denoise_features(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* y, const float* v, const float* feat_mean, const float* feat_var,
+                              const RtDenoise* dn, const RtFeatureGuide* guide, float* out_rgb_f32);
 
 #ifdef __cplusplus
 }

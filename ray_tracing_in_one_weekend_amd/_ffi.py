@@ -268,6 +268,40 @@ class RtAccumFilter(C.Structure):
                 ("frame_id", C.c_uint64), ("filter", RtPixelFilter), ("plane", _f)]
 
 
+# rt_accum_track_features
+FEATURES_MIN_STRIDE, FEATURES_MAX_STRIDE = 1, 64  # RT_FEATURES_MIN_STRIDE, RT_FEATURES_MAX_STRIDE
+
+
+class RtFeatures(C.Structure):
+    """rt_accum_track_features: every stride-th sample, by absolute index, takes a first-hit feature sample (rtow_mi355x.h "First-hit
+    features")."""
+    _fields_ = [("stride", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RtFeaturePixel(C.Structure):
+    """The feature record of one pixel: the f32 sums of albedo and normal with their counts, and the f64 moments."""
+    _fields_ = [("albedo", C.c_float * 3), ("n_f", C.c_uint32), ("normal", C.c_float * 3), ("n_h", C.c_uint32),
+                ("a2", C.c_double), ("n2", C.c_double), ("z1", C.c_double), ("z2", C.c_double)]
+
+
+FEATURE_USE_ALBEDO, FEATURE_USE_NORMAL, FEATURE_USE_DEPTH = 1, 2, 4  # RT_FEATURE_USE_*
+FEATURE_GUIDE_DEFAULT_K, FEATURE_GUIDE_DEFAULT_TAU = 0.6, 1e-3  # RT_FEATURE_GUIDE_DEFAULT_*
+
+
+class RtFeatureGuide(C.Structure):
+    """rt_accum_denoise_features: the strengths and variance floors of the three feature distances, which of them are used, and whether
+    the colour is filtered demodulated by the albedo (rtow_mi355x.h "The feature-guided filter")."""
+    _fields_ = [("k_albedo", C.c_float), ("k_normal", C.c_float), ("k_depth", C.c_float), ("tau_albedo", C.c_float), ("tau_normal", C.c_float),
+                ("tau_depth", C.c_float), ("use_mask", C.c_uint32), ("demodulate", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class RtAccumFeatures(C.Structure):
+    """rt_accum_export_features / rt_accum_import_features: the stride and the records of an accumulation, as a host array in the row order
+    of the f32 image."""
+    _fields_ = [("nx", C.c_uint32), ("rows", C.c_uint32), ("first_sample", C.c_uint32), ("done", C.c_uint32), ("reserved", C.c_uint32 * 2),
+                ("frame_id", C.c_uint64), ("features", RtFeatures), ("plane", C.POINTER(RtFeaturePixel))]
+
+
 # rt_set_glare
 GLARE_MAX_LEVELS, GLARE_DEFAULT_LEVELS = 8, 6
 GLARE_DEFAULT_AMOUNT, GLARE_DEFAULT_SPREAD = 0.1, 0.7
@@ -299,6 +333,7 @@ RtProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C
 
 MULTI_COPY_GATHER = 1  # RT_MULTI_COPY_GATHER (rt_multi_create_ex)
 MULTI_TRACK_CHANNELS, MULTI_TRACK_HALVES, MULTI_TRACK_BUCKETS = 1, 2, 4  # RT_MULTI_TRACK_* (rt_multi_accum_begin)
+MULTI_UNSUPPORTED_FEATURES = 32  # RT_MULTI_UNSUPPORTED_FEATURES: declared so that it can be refused (RT_ERR_UNSUPPORTED); 8 and 16 are no track bits
 # enum RtDebugOption (rt_debug_set_option): per context, every setting renders the same bits
 (OPT_TREE_PLACEMENT, OPT_PRIMARY_LISTS, OPT_PIXEL_ORDER, OPT_TEXEL_POOL, OPT_GRID, OPT_GRID_CELL, OPT_CHAINS,
  OPT_GENERAL_KERNELS, OPT_GENERAL_LDS, OPT_QUEUE_SHARDS, OPT_ISECT_WORKGROUPS, OPT_MATERIALISE_PRIMARIES, OPT_MEDIUM_SEARCH, OPT_POOL_CHUNK_DELAY_US) = range(14)
@@ -356,6 +391,8 @@ GPU_SYMBOLS = ["rt_abi_version", "rt_build_id", "rt_ctx_create", "rt_ctx_destroy
                "rt_set_glare", "rt_glare_check", "rt_glare_info", "rt_glare_image", "rt_debug_glare", "rt_debug_glare_chain",
                "rt_pixel_filter_check", "rt_pixel_filter_table", "rt_accum_track_filter", "rt_accum_read_filtered", "rt_accum_filter_check",
                "rt_accum_export_filter", "rt_accum_import_filter", "rt_debug_filter_add",
+               "rt_features_check", "rt_accum_track_features", "rt_accum_read_features", "rt_accum_features_check", "rt_accum_export_features",
+               "rt_accum_import_features", "rt_debug_features_add", "rt_feature_guide_check", "rt_accum_denoise_features", "rt_debug_denoise_features",
                "rt_debug_variant_tables", "rt_debug_variant_flag_names", "rt_debug_launched_variants"]
 HOST_SYMBOLS = ["rth_last_error", "rth_register_image", "rth_rng_reseed", "rth_scene_build", "rth_scene_new",
                 "rth_tex_constant", "rth_tex_checker", "rth_tex_perlin", "rth_tex_image", "rth_material",
@@ -514,6 +551,26 @@ def load_gpu_library():
     lib.rt_accum_import_filter.restype = C.c_int
     lib.rt_debug_filter_add.argtypes = [vp, C.c_uint32, C.c_uint32, _f]
     lib.rt_debug_filter_add.restype = C.c_int
+    lib.rt_features_check.argtypes = [C.POINTER(RtFeatures)]
+    lib.rt_features_check.restype = C.c_int
+    lib.rt_accum_track_features.argtypes = [vp, C.POINTER(RtFeatures)]
+    lib.rt_accum_track_features.restype = C.c_int
+    lib.rt_accum_read_features.argtypes = [vp, _f, _f, _f, _f, _f]
+    lib.rt_accum_read_features.restype = C.c_int
+    lib.rt_accum_features_check.argtypes = [C.POINTER(RtAccumFeatures)]
+    lib.rt_accum_features_check.restype = C.c_int
+    lib.rt_accum_export_features.argtypes = [vp, C.POINTER(RtAccumFeatures)]
+    lib.rt_accum_export_features.restype = C.c_int
+    lib.rt_accum_import_features.argtypes = [vp, C.POINTER(RtAccumFeatures)]
+    lib.rt_accum_import_features.restype = C.c_int
+    lib.rt_debug_features_add.argtypes = [vp, C.c_uint32, C.c_uint32]
+    lib.rt_debug_features_add.restype = C.c_int
+    lib.rt_feature_guide_check.argtypes = [C.POINTER(RtFeatureGuide)]
+    lib.rt_feature_guide_check.restype = C.c_int
+    lib.rt_accum_denoise_features.argtypes = [vp, C.POINTER(RtDenoise), C.POINTER(RtFeatureGuide), _f, _u8]
+    lib.rt_accum_denoise_features.restype = C.c_int
+    lib.rt_debug_denoise_features.argtypes = [vp, C.c_uint32, C.c_uint32, _f, _f, _f, _f, _f, C.POINTER(RtDenoise), C.POINTER(RtFeatureGuide), _f]
+    lib.rt_debug_denoise_features.restype = C.c_int
     lib.rt_select_check.argtypes = [C.POINTER(RtSelect)]
     lib.rt_select_check.restype = C.c_int
     lib.rt_accum_denoise_select.argtypes = [vp, C.POINTER(RtSelect), _f, _u8, _u8, _f, C.POINTER(RtSelectInfo)]

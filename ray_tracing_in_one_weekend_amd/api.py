@@ -658,6 +658,58 @@ class AccumFilter(_Snapshot):
         return fs
 
 
+FEATURE_PIXEL = np.dtype([("albedo", "<f4", (3,)), ("n_f", "<u4"), ("normal", "<f4", (3,)), ("n_h", "<u4"), ("a2", "<f8"), ("n2", "<f8"),
+                          ("z1", "<f8"), ("z2", "<f8")])  # RtFeaturePixel, 64 B
+
+
+def features_check(stride):
+    """rt_features_check (no GPU): True when rt_accum_track_features would accept the stride."""
+    return _ffi.load_gpu_library().rt_features_check(C.byref(_ffi.RtFeatures(int(stride), 0))) == 0
+
+
+def make_feature_guide(use=("albedo", "normal", "depth"), k=_ffi.FEATURE_GUIDE_DEFAULT_K, tau=_ffi.FEATURE_GUIDE_DEFAULT_TAU, demodulate=False):
+    """An RtFeatureGuide for Renderer.accum_denoise_features: `use` names the features that guide ("albedo", "normal", "depth"; or the
+    RT_FEATURE_USE_* mask), `k` and `tau` are one value for all three or a triple (albedo, normal, depth); the defaults are the 2013
+    paper's, 0.6 and 1e-3."""
+    names = {"albedo": _ffi.FEATURE_USE_ALBEDO, "normal": _ffi.FEATURE_USE_NORMAL, "depth": _ffi.FEATURE_USE_DEPTH}
+    if isinstance(use, int):
+        mask = use
+    else:
+        for u in use:
+            if u not in names:
+                raise ValueError(f"feature {u!r}: expected one of {sorted(names)}")
+        mask = sum({names[u] for u in use})
+    k3 = tuple(float(x) for x in k) if np.ndim(k) else (float(k),) * 3
+    t3 = tuple(float(x) for x in tau) if np.ndim(tau) else (float(tau),) * 3
+    if len(k3) != 3 or len(t3) != 3:
+        raise ValueError("k and tau take one value or three (albedo, normal, depth)")
+    return _ffi.RtFeatureGuide(*k3, *t3, int(mask), 1 if demodulate else 0)
+
+
+def feature_guide_check(guide):
+    """rt_feature_guide_check (no GPU): True when rt_accum_denoise_features would accept the RtFeatureGuide."""
+    return _ffi.load_gpu_library().rt_feature_guide_check(C.byref(guide) if guide is not None else None) == 0
+
+
+class AccumFeatures(_Snapshot):
+    """The first-hit feature records of an accumulation (rtow_mi355x.h "First-hit features"), as a numpy array in the row order of the f32
+    image plus the scalar fields of RtAccumFeatures and the stride: plane [rows, nx] of FEATURE_PIXEL (sums, not divided).  It goes with the
+    AccumState of the same accumulation: first_sample and done are that state's."""
+    _SCALARS = ("nx", "rows", "first_sample", "done", "frame_id", "stride")
+    _ARRAYS = (("plane", FEATURE_PIXEL, (), ()),)
+    _CHECK = "rt_accum_features_check"
+
+    def __init__(self, nx, rows, first_sample=0, done=0, frame_id=0, stride=1, plane=None):
+        self._init(dict(nx=nx, rows=rows, first_sample=first_sample, done=done, frame_id=frame_id, stride=stride), dict(plane=plane))
+
+    def as_struct(self):
+        """The RtAccumFeatures over this array (which must stay alive while it is used)."""
+        fs = _ffi.RtAccumFeatures(self.nx, self.rows, self.first_sample, self.done)
+        fs.frame_id, fs.features = self.frame_id, _ffi.RtFeatures(self.stride, 0)
+        fs.plane = self.plane.ctypes.data_as(C.POINTER(_ffi.RtFeaturePixel))
+        return fs
+
+
 def make_select(strengths=_ffi.SELECT_DEFAULT_STRENGTHS, radius=5, patch=1, error_radius=0, blend_radius=1):
     """An RtSelect for Renderer.accum_denoise_select: 2 .. 4 strictly increasing candidate strengths of the cross filter, its window radius
     and patch radius, the radius of the window the per-pixel error estimate is summed over and that of the window the choice is blended
@@ -1130,6 +1182,66 @@ class Renderer:
         rad = np.ascontiguousarray(rad, dtype=np.float32)
         assert rad.ndim == 4 and rad.shape[1:] == (rows, nx, 3), rad.shape
         self._call("rt_debug_filter_add", int(i0), rad.shape[0], rad.ctypes.data_as(C.POINTER(C.c_float)))
+
+    def accum_track_features(self, stride=1):
+        """rt_accum_track_features: the open accumulation also keeps, per pixel, the albedo, normal and depth of the first hit of every
+        stride-th sample (by absolute index) with their second moments (64 B per pixel); right after accum_begin, before the first add.
+        A kernel of its own recomputes the first hits; everything else the accumulation returns stays bit for bit.  Not on a sharded
+        accumulation."""
+        self._call("rt_accum_track_features", C.byref(_ffi.RtFeatures(int(stride), 0)))
+
+    def accum_features(self):
+        """rt_accum_read_features: a dict of f32 arrays in image order — albedo [rows, nx, 3], normal [rows, nx, 3], depth [rows, nx],
+        hit [rows, nx] (the fraction of feature samples that hit) and var [rows, nx, 3] (the variance of the mean of albedo, normal,
+        depth)."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        out = {"albedo": np.zeros((rows, nx, 3), np.float32), "normal": np.zeros((rows, nx, 3), np.float32), "depth": np.zeros((rows, nx), np.float32),
+               "hit": np.zeros((rows, nx), np.float32), "var": np.zeros((rows, nx, 3), np.float32)}
+        self._call("rt_accum_read_features", *(out[k].ctypes.data_as(C.POINTER(C.c_float)) for k in ("albedo", "normal", "depth", "hit", "var")))
+        return out
+
+    def accum_export_features(self):
+        """rt_accum_export_features: the stride and the records of the open accumulation as an AccumFeatures.  Read, not changed."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        snap = AccumFeatures(nx, rows)
+        fs = snap.as_struct()
+        self._call("rt_accum_export_features", C.byref(fs))
+        return AccumFeatures(nx, rows, fs.first_sample, fs.done, fs.frame_id, fs.features.stride, plane=snap.plane)
+
+    def accum_import_features(self, snap):
+        """rt_accum_import_features: puts an AccumFeatures into the accumulation just begun — fresh, or right after accum_import of the state
+        it belongs to — and turns tracking on under its stride."""
+        fs = snap.as_struct()
+        self._call("rt_accum_import_features", C.byref(fs))
+
+    def accum_denoise_features(self, guide, radius=5, patch=1, strength=None, want_rgb8=False):
+        """rt_accum_denoise_features: accum_denoise with the first-hit features of the accumulation beside the colour guide (`guide`:
+        make_feature_guide).  Returns (img [rows, nx, 3] f32, rgb8 or None) laid out as accum_read's; the accumulation is not changed."""
+        rows, nx = getattr(self, "_accum_shape", (0, 0))
+        img = np.zeros((rows, nx, 3), dtype=np.float32)
+        rgb8 = np.zeros((rows, nx, 3), dtype=np.uint8) if want_rgb8 else None
+        self._call("rt_accum_denoise_features", self._denoise_ptr(radius, patch, strength), C.byref(guide) if guide is not None else None,
+                   img.ctypes.data_as(C.POINTER(C.c_float)), rgb8.ctypes.data_as(C.POINTER(C.c_uint8)) if want_rgb8 else None)
+        return img, rgb8
+
+    def debug_denoise_features(self, rgb, y, v, feat_mean, feat_var, guide, radius=5, patch=1, strength=None):
+        """rt_debug_denoise_features: the kernels of accum_denoise_features over host arrays in image order — rgb [rows, nx, 3], y and v
+        [rows, nx], feat_mean [rows, nx, 7] (albedo 3, normal 3, depth) and feat_var [rows, nx, 3]; returns the filtered [rows, nx, 3]."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        y, v = np.ascontiguousarray(y, dtype=np.float32), np.ascontiguousarray(v, dtype=np.float32)
+        fm, fv = np.ascontiguousarray(feat_mean, dtype=np.float32), np.ascontiguousarray(feat_var, dtype=np.float32)
+        rows, nx = y.shape
+        assert rgb.shape == (rows, nx, 3) and v.shape == (rows, nx) and fm.shape == (rows, nx, 7) and fv.shape == (rows, nx, 3)
+        out = np.zeros_like(rgb)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        self._call("rt_debug_denoise_features", nx, rows, fp(rgb), fp(y), fp(v), fp(fm), fp(fv), self._denoise_ptr(radius, patch, strength),
+                   C.byref(guide) if guide is not None else None, fp(out))
+        return out
+
+    def debug_features_add(self, i0, n_samples):
+        """rt_debug_features_add: the production kernel k_features over the samples i0 .. i0 + n_samples - 1 of every pixel, onto the
+        feature records of the open accumulation only; nothing is traced."""
+        self._call("rt_debug_features_add", int(i0), int(n_samples))
 
     def accum_track_buckets(self, M):
         """rt_accum_track_buckets: the open accumulation also keeps the samples of every pixel in M buckets by sample index (12 M bytes per

@@ -43,7 +43,7 @@ def build_gpu_debug_library(out=None):
 
 def gpu_sources():
     csrc = os.path.join(PKG_DIR, "csrc")
-    return [os.path.join(csrc, f) for f in ("rt_api.hip", "rt_kernels.h", "rt_denoise.h", "rt_channels.h", "rt_adaptive.h", "rt_adaptive_plan.h", "rt_accum_state.h", "rt_accum_planes.h", "rt_accum_state_kernels.h", "rt_halves.h", "rt_halves_plan.h", "rt_select.h", "rt_select_plan.h", "rt_buckets.h", "rt_buckets_plan.h", "rt_filter.h", "rt_filter_plan.h", "rt_display.h", "rt_display_plan.h", "rt_glare.h", "rt_glare_plan.h", "rt_device.h", "rt_bvh.h", "rt_grid.h", "rt_multi.h", "rt_multi_accum.h", "rt_multi_accum_plan.h", "rt_pool.h", "rt_scene_prep.h", "rt_frame_plan.h")] + \
+    return [os.path.join(csrc, f) for f in ("rt_api.hip", "rt_kernels.h", "rt_denoise.h", "rt_channels.h", "rt_adaptive.h", "rt_adaptive_plan.h", "rt_accum_state.h", "rt_accum_planes.h", "rt_accum_state_kernels.h", "rt_halves.h", "rt_halves_plan.h", "rt_select.h", "rt_select_plan.h", "rt_buckets.h", "rt_buckets_plan.h", "rt_filter.h", "rt_filter_plan.h", "rt_features.h", "rt_features_plan.h", "rt_display.h", "rt_display_plan.h", "rt_glare.h", "rt_glare_plan.h", "rt_device.h", "rt_bvh.h", "rt_grid.h", "rt_multi.h", "rt_multi_accum.h", "rt_multi_accum_plan.h", "rt_pool.h", "rt_scene_prep.h", "rt_frame_plan.h")] + \
            [os.path.join(ROOT, "include", "rtow_mi355x.h")]
 
 

@@ -7,6 +7,7 @@
 #pragma once
 #include "rt_accum_state.h"
 #include "rt_buckets_plan.h"
+#include "rt_features_plan.h"
 #include "rt_filter_plan.h"
 #include "rt_halves_plan.h"
 
@@ -77,6 +78,14 @@ inline PlaneTable buckets_planes(const RtAccumBuckets& bs, uint32_t M, void* loc
 inline PlaneTable filter_planes(const RtAccumFilter& fs, void* local) {
     PlaneTable t{};
     planes_push(t, fs.plane, local, RT_FILTER_PIXEL_BYTES);
+    return t;
+}
+
+// `local`: the accumulation's feature records, four quarter planes of 16 B (rt_features_plan.h); in image order a pixel's quarters lie side
+// by side: the 64 B RtFeaturePixel
+inline PlaneTable features_planes(const RtAccumFeatures& fs, void* local) {
+    PlaneTable t{};
+    planes_push(t, fs.plane, local, RT_FEATURES_QUARTER_BYTES, RT_FEATURES_QUARTERS);
     return t;
 }
 

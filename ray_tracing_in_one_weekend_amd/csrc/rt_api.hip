@@ -14,6 +14,7 @@
 #include "rt_select.h"
 #include "rt_buckets.h"
 #include "rt_filter.h"
+#include "rt_features.h"
 #include "rt_display.h"
 #include "rt_glare.h"
 #include "rt_bvh.h"
@@ -148,6 +149,7 @@ struct RtCtx {
         uint32_t buckets = 0;  // rt_accum_track_buckets / rt_accum_import_buckets: M, accum_buckets holds the bucket sums and every add keeps them; 0: not tracked
         bool filter = false;   // rt_accum_track_filter / rt_accum_import_filter: accum_filter holds the table of `pf` and the plane, and every add keeps it
         RtPixelFilter pf{};
+        uint32_t features = 0; // rt_accum_track_features / rt_accum_import_features: the stride, accum_features holds the records and every add keeps them; 0: not tracked
         bool mirror = false;   // the context an RtMulti joins its shards into (rt_multi_accum.h): only rt_multi_accum_join writes the accumulation, for good
     } accum;
     DevBuf accum_sum, accum_mom, accum_sem, accum_partials; // (accum_sem: staging of out_sem; accum_partials: one f64 pair per workgroup + the 3 frame figures)
@@ -176,6 +178,10 @@ struct RtCtx {
     // order of accum_sum (rt_filter_plan.h: filter_buffer_bytes); filter_out: what rt_accum_read_filtered writes — c (12 B) and W (4 B) per
     // pixel in image order; filter_rad: the radiance slots rt_debug_filter_add uploads
     DevBuf accum_filter, filter_out, filter_rad;
+    // rt_accum_track_features (rt_features.h): the four quarter planes of the records, 64 B per pixel in the order of accum_sum
+    // (rt_features_plan.h); features_out: what rt_accum_read_features writes, 11 floats per pixel in image order
+    DevBuf accum_features, features_out;
+    DevBuf dn_feat; // rt_accum_denoise_features: the 7 means, then the 3 variances of the mean per pixel, in image order (rt_features_plan.h)
     // The one staging buffer of every export, import and merge: the planes of a state, of the halves or of the buckets in image order
     // (rt_accum_planes.h: planes_place), at most 192 B per pixel; rt_accum_read_halves borrows it for its two outputs
     DevBuf accum_stage;
@@ -775,6 +781,11 @@ int rt_ctx_create(int device_id, RtCtx** out_ctx) {
         for (auto fn : DEBUG_KERNELS_TREE_LDS) raise_lds(fn); // (DEBUG_KERNELS_BRUTE stage one tile of spheres: below the default)
         raise_lds(&k_intersect_grid<true>), raise_lds(&k_intersect_grid<false>);
         raise_lds(&k_intersect_grid_motion<true>), raise_lds(&k_intersect_grid_motion<false>);
+        // the tree forms of k_features stage what k_intersect stages (the list-walk form one tile of spheres: below the default)
+#define FEATURES_RAISE(N, M, P) raise_lds(&k_features<true, N, M, P, false>), raise_lds(&k_features<true, N, M, P, true>)
+        FEATURES_RAISE(true, false, false), FEATURES_RAISE(true, true, false), FEATURES_RAISE(true, false, true);
+        FEATURES_RAISE(false, false, false), FEATURES_RAISE(false, true, false), FEATURES_RAISE(false, false, true);
+#undef FEATURES_RAISE
         if (e != hipSuccess) return bail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
     }
     if ((e = hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
@@ -807,6 +818,7 @@ void rt_ctx_destroy(RtCtx* ctx) {
     free_buf(ctx->accum_stage);
     free_buf(ctx->accum_halves), free_buf(ctx->dn_halves);
     free_buf(ctx->accum_filter), free_buf(ctx->filter_out), free_buf(ctx->filter_rad);
+    free_buf(ctx->accum_features), free_buf(ctx->features_out), free_buf(ctx->dn_feat);
     free_buf(ctx->accum_buckets), free_buf(ctx->robust_out);
     if (ctx->h_resid) (void)hipHostFree(ctx->h_resid);
     free_buf(ctx->dn_select);
@@ -967,6 +979,9 @@ struct SampleSink {
     bool filter = false;
     FilterArgs fa{};
     uint32_t filter_reach = 0;
+    // rt_accum_track_features (rt_features.h): the records and the stride, kept by a kernel of its own that reads no radiance
+    uint4* features = nullptr;
+    uint32_t features_stride = 0;
 };
 // What trace_samples enqueued, for the finalize, the copies and the statistics of its caller.
 struct Traced {
@@ -1200,6 +1215,30 @@ static void launch_resolve_filter(hipStream_t st, bool active, uint32_t reach, c
 #undef FILTER_REACH
 }
 
+// k_features over the samples i0 .. i0 + n - 1 of every pixel of the frame `gp` on `st`: the search form an add with `use_bvh` uses, the
+// sets of the context, the lens of the frame.  Nothing is launched where the window holds no contributing sample.
+using FeaturesKernel = void (*)(DevScene, GenParams, GenLens, FeatureArgs);
+// (MOTION excludes PLANAR, as for k_shade)
+#define FEATURES_SET(U, N, M, P) (lens ? &k_features<U, N, M, P, true> : &k_features<U, N, M, P, false>)
+#define FEATURES_FORM(U, N) (ctx->motion ? FEATURES_SET(U, N, true, false) : ctx->planar ? FEATURES_SET(U, N, false, true) : FEATURES_SET(U, N, false, false))
+static void launch_features(RtCtx* ctx, hipStream_t st, const GenParams& gp, const GenLens& gl, bool lens, bool use_bvh, uint4* plane, const uint8_t* flag,
+                            uint32_t stride, uint32_t i0, uint32_t n) {
+    FeatureArgs fa{};
+    fa.plane = plane, fa.flag = flag, fa.stride = stride;
+    fa.n_feat = features_in_window(i0, n, stride);
+    if (fa.n_feat == 0u) return;
+    fa.s_first = (uint32_t)features_first(i0, stride); // (below i0 + n <= 2^32)
+    fa.motion = ctx->gmotion, fa.planar = ctx->gplanar;
+    const bool lds_nodes = ctx->search.bvh_in_lds;
+    const FeaturesKernel fn = !use_bvh ? FEATURES_FORM(false, true) : lds_nodes ? FEATURES_FORM(true, true) : FEATURES_FORM(true, false);
+    // what stage_bvh carves, and no more: the general tables and the displacements that k_intersect stages beside it are read from memory here
+    const size_t lds_bytes = use_bvh ? bvh_lds_bytes(ctx->search.ds, RT_BVH_BLOCK, lds_nodes)
+                                     : (size_t)std::min<uint32_t>(std::max<uint32_t>(ctx->search.ds.n_spheres, 1u), RT_SPHERE_TILE) * sizeof(float4);
+    const uint32_t rows = gp.npix / gp.nx;
+    const dim3 grid((gp.nx + RT_FEATURES_BLOCK_X - 1u) / RT_FEATURES_BLOCK_X, (rows + RT_FEATURES_BLOCK_Y - 1u) / RT_FEATURES_BLOCK_Y);
+    hipLaunchKernelGGL(fn, grid, dim3(RT_BVH_BLOCK), lds_bytes, st, ctx->search.ds, gp, gl, fa);
+}
+
 // Resolves the slice's `sc` samples per pixel onto the running sum, in sample order, and shows the `done` of `spp` samples so far to
 // the progress callback.
 static int resolve_and_preview(RtCtx* ctx, const Frame& f, const SampleSink& sink, const float* rad, uint32_t sc, uint32_t done, uint32_t rows) {
@@ -1214,6 +1253,10 @@ static int resolve_and_preview(RtCtx* ctx, const Frame& f, const SampleSink& sin
         FilterArgs fa = sink.fa;
         fa.flag = sink.converged, fa.i0 = i0, fa.s_count = sc;
         launch_resolve_filter(st, active, sink.filter_reach, rad, fa);
+    }
+    if (sink.features) {
+        launch_features(ctx, st, f.gp, f.glens, f.d.lens, f.d.use_bvh, sink.features, sink.converged, sink.features_stride, i0, sc);
+        RT_HIP(ctx, hipGetLastError()); // (a launch refused for its dynamic LDS or its registers is reported by this add, not by a later call)
     }
     if (sink.chm) KERNEL_PAIR(k_resolve_moments_channels, active, grid, st, rad, f.acc, sink.mom, sink.chm, sink.converged, sink.cnt, npix, sc);
     else if (sink.mom || active) KERNEL_PAIR(k_resolve_moments, active, grid, st, rad, f.acc, sink.mom, sink.converged, sink.cnt, npix, sc);
@@ -1776,6 +1819,7 @@ static int accum_add(RtCtx* ctx, uint32_t n_samples, bool adaptive, const RtAdap
     if (a.halves) sink.halves = true, sink.hp = half_planes(ctx->accum_halves, a.npix);
     if (a.buckets) sink.buckets = ctx->accum_buckets.as<float>(), sink.n_buckets = a.buckets;
     if (a.filter) sink.filter = true, sink.fa = filter_args(ctx), sink.filter_reach = pixel_filter_reach(a.pf.radius);
+    if (a.features) sink.features = ctx->accum_features.as<uint4>(), sink.features_stride = a.features;
     if ((rc = trace_samples(ctx, &a.cam, &p, nullptr, sink, tr))) return rc;
     if (tr.npix == 0u) return nothing_traced();
     if (tr.npix != a.npix || tr.tiles_per_row != a.tiles_per_row || tr.tile_pixels != a.tile_pixels) {
@@ -2348,6 +2392,7 @@ int rt_accum_import(RtCtx* ctx, const RtAccumState* st) {
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks halves already (import the state first, then rt_accum_import_halves)");
     if (a.buckets) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks buckets already (import the state first, then rt_accum_import_buckets)");
     if (a.filter) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks a filter already (import the state first, then rt_accum_import_filter)");
+    if (a.features) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_import: the accumulation tracks features already (import the state first, then rt_accum_import_features)");
     if (a.done != 0u || a.adaptive) return fail(ctx, RT_ERR_STATE, "rt_accum_import: samples were added already (call it right after rt_accum_begin)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import: ") + why);
     if ((rc = require_match(ctx, "rt_accum_import", snapshot_header(*st), "state", SNAPSHOT_FIRST_SAMPLE))) return rc;
@@ -2375,6 +2420,7 @@ int rt_accum_merge(RtCtx* ctx, const RtAccumState* st) {
     if (a.halves) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks halves: a merge of halves is not covered (rtow_mi355x.h)");
     if (a.buckets) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks buckets: a merge of buckets is not covered (rtow_mi355x.h)");
     if (a.filter) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks a filter: a merge of filter planes is not covered (rtow_mi355x.h)");
+    if (a.features) return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: the accumulation tracks features: a merge of feature records is not covered (rtow_mi355x.h)");
     if (const char* why = accum_state_invalid(st)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_merge: ") + why);
     if (a.adaptive || (st->planes & RT_ACCUM_STATE_COUNTS))
         return fail(ctx, RT_ERR_UNSUPPORTED, "rt_accum_merge: an adaptive accumulation or state: windows of pixels with different sample counts are not contiguous");
@@ -2646,6 +2692,199 @@ int rt_debug_filter_add(RtCtx* ctx, uint32_t i0, uint32_t n_samples, const float
     launch_resolve_filter(ctx->stream, false, pixel_filter_reach(a.pf.radius), ctx->filter_rad.as<const float>(), fa);
     RT_HIP(ctx, hipGetLastError());
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+// ---- first-hit features (rtow_mi355x.h "First-hit features", csrc/rt_features.h, csrc/rt_features_plan.h) ----------------------------------
+int rt_features_check(const RtFeatures* features) { return features_invalid(features) ? RT_ERR_INVALID : RT_OK; }
+int rt_accum_features_check(const RtAccumFeatures* fs) { return accum_features_invalid(fs) ? RT_ERR_INVALID : RT_OK; }
+
+static int refuse_features_on_shard(RtCtx* ctx, const char* who) {
+    return ctx->accum.prm.shard_count > 1u
+               ? fail(ctx, RT_ERR_UNSUPPORTED, std::string(who) + ": a sharded accumulation (shard_count > 1): first-hit features of shards, and so of rt_multi_accum_*, are not covered (rtow_mi355x.h)")
+               : RT_OK;
+}
+
+int rt_accum_track_features(RtCtx* ctx, const RtFeatures* features) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    int rc;
+    if ((rc = refuse_mirror(ctx, "rt_accum_track_features")) || (rc = require_open(ctx, "rt_accum_track_features"))) return rc;
+    if (const char* why = features_invalid(features)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_track_features: ") + why);
+    if ((rc = refuse_features_on_shard(ctx, "rt_accum_track_features"))) return rc;
+    if (a.features)
+        return a.features == features->stride ? RT_OK : fail(ctx, RT_ERR_STATE, "rt_accum_track_features: the accumulation tracks features under another stride already");
+    if (a.done != 0u || a.adaptive || a.added)
+        return fail(ctx, RT_ERR_STATE, "rt_accum_track_features: the accumulation holds samples already (call it right after rt_accum_begin; after rt_accum_import "
+                                       "the records come through rt_accum_import_features)");
+    if (a.npix) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        if ((rc = ensure(ctx, ctx->accum_features, features_buffer_bytes(a.npix)))) return rc;
+        RT_HIP(ctx, hipMemsetAsync(ctx->accum_features.p, 0, features_buffer_bytes(a.npix), ctx->stream));
+    }
+    a.features = features->stride;
+    return RT_OK;
+}
+
+int rt_accum_read_features(RtCtx* ctx, float* out_albedo, float* out_normal, float* out_depth, float* out_hit, float* out_var) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    int rc;
+    if ((rc = require_open(ctx, "rt_accum_read_features"))) return rc;
+    if (!a.features) return fail(ctx, RT_ERR_STATE, "rt_accum_read_features: the accumulation does not track features (rt_accum_track_features)");
+    if (a.npix == 0u || (!out_albedo && !out_normal && !out_depth && !out_hit && !out_var)) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const size_t npix = a.npix;
+    if ((rc = ensure(ctx, ctx->features_out, features_read_bytes(npix)))) return rc;
+    float* d = ctx->features_out.as<float>();
+    hipLaunchKernelGGL(k_features_read, dim3((a.npix + 255u) / 256u), dim3(256), 0, st, ctx->accum_features.as<const uint4>(), d, a.nx, a.rows, a.tiles_per_row, a.tile_pixels);
+    RT_HIP(ctx, hipGetLastError());
+    const struct {
+        float* host;
+        size_t first, floats; // in pixels' worth of floats: where the output starts and how many it holds per pixel
+    } outs[] = {{out_albedo, 0u, 3u}, {out_normal, 3u, 3u}, {out_depth, 6u, 1u}, {out_hit, 7u, 1u}, {out_var, 8u, 3u}};
+    for (const auto& o : outs)
+        if (o.host) RT_HIP(ctx, hipMemcpyAsync(o.host, d + o.first * npix, o.floats * npix * sizeof(float), hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+int rt_accum_export_features(RtCtx* ctx, RtAccumFeatures* fs) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (!fs) return fail(ctx, RT_ERR_INVALID, "rt_accum_export_features: the RtAccumFeatures is NULL");
+    if (const int rc = require_open(ctx, "rt_accum_export_features")) return rc;
+    if (!a.features) return fail(ctx, RT_ERR_STATE, "rt_accum_export_features: the accumulation does not track features (rt_accum_track_features)");
+    if (a.npix && fs->plane) {
+        PlaneTable t = features_planes(*fs, ctx->accum_features.p);
+        if (const int rc = planes_to_host(ctx, t)) return rc;
+    }
+    snapshot_header_put(*fs, accum_header(a));
+    fs->reserved[0] = fs->reserved[1] = 0u;
+    fs->features = RtFeatures{a.features, 0u};
+    return RT_OK;
+}
+
+int rt_accum_import_features(RtCtx* ctx, const RtAccumFeatures* fs) {
+    if (!ctx) return RT_ERR_INVALID;
+    RtCtx::Accum& a = ctx->accum;
+    int rc;
+    if ((rc = refuse_mirror(ctx, "rt_accum_import_features")) || (rc = require_open(ctx, "rt_accum_import_features"))) return rc;
+    if (a.added) return fail(ctx, RT_ERR_STATE, "rt_accum_import_features: samples were added since rt_accum_begin (call it right after rt_accum_begin or rt_accum_import)");
+    if ((rc = refuse_features_on_shard(ctx, "rt_accum_import_features"))) return rc;
+    if (const char* why = accum_features_invalid(fs)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_import_features: ") + why);
+    if ((rc = require_match(ctx, "rt_accum_import_features", snapshot_header(*fs), "features", SNAPSHOT_FIRST_AND_DONE))) return rc;
+    if (a.features && a.features != fs->features.stride)
+        return fail(ctx, RT_ERR_INVALID, "rt_accum_import_features: the stride of the snapshot is not the one the accumulation tracks");
+    if (a.npix) {
+        RT_HIP(ctx, hipSetDevice(ctx->device));
+        if ((rc = ensure(ctx, ctx->accum_features, features_buffer_bytes(a.npix)))) return rc; // every allocation first: a failure cannot leave the accumulation half imported
+        PlaneTable t = features_planes(*fs, ctx->accum_features.p);
+        if ((rc = planes_from_host(ctx, t, true))) return rc;
+    }
+    a.features = fs->features.stride;
+    return RT_OK;
+}
+
+int rt_debug_features_add(RtCtx* ctx, uint32_t i0, uint32_t n_samples) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& a = ctx->accum;
+    if (const int rc = require_open(ctx, "rt_debug_features_add")) return rc;
+    if (!a.features) return fail(ctx, RT_ERR_STATE, "rt_debug_features_add: the accumulation does not track features (rt_accum_track_features)");
+    if (n_samples == 0u || n_samples > 4096u || (uint64_t)i0 + n_samples > (1ull << 32))
+        return fail(ctx, RT_ERR_INVALID, "rt_debug_features_add: n_samples outside 1 .. 4096, or i0 + n_samples above 2^32");
+    if (a.npix == 0u) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    // the frame as an add of the accumulation sees it: its GenParams, its lens and its search form
+    const FrameDecisions d = frame_decisions(ctx, &a.prm);
+    const GenParams gp = frame_gen_params(a.cam, a.prm, shard_geom(a.prm), d.nq, PixelOrder{a.tiles_per_row, a.tile_pixels});
+    const GenLens gl = d.lens ? host_gen_lens(&a.cam, ctx->lens) : GenLens{};
+    launch_features(ctx, ctx->stream, gp, gl, d.lens, d.use_bvh, ctx->accum_features.as<uint4>(), nullptr, a.features, i0, n_samples);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+// ---- the feature-guided filter (rtow_mi355x.h "The feature-guided filter", csrc/rt_features.h) -------------------------------------------
+int rt_feature_guide_check(const RtFeatureGuide* guide) { return feature_guide_invalid(guide) ? RT_ERR_INVALID : RT_OK; }
+
+// The demodulation where the guide asks for it, then k_denoise_features over an image in image order (device pointers) -> out.
+static void launch_denoise_features(hipStream_t st, float* c, float2* yv, const float* fmean, const float* fvar, float* out, uint32_t nx, uint32_t rows,
+                                    const RtDenoise& d, const RtFeatureGuide& fg) {
+    const uint32_t npix = nx * rows;
+    if (fg.demodulate) hipLaunchKernelGGL(k_features_demodulate, dim3((npix + 255u) / 256u), dim3(256), 0, st, c, yv, fmean, npix);
+    FeatureGuideArgs a{};
+    a.k2[0] = fg.k_albedo * fg.k_albedo, a.k2[1] = fg.k_normal * fg.k_normal, a.k2[2] = fg.k_depth * fg.k_depth;
+    a.tau[0] = fg.tau_albedo, a.tau[1] = fg.tau_normal, a.tau[2] = fg.tau_depth;
+    a.use = fg.use_mask, a.demodulate = fg.demodulate;
+    const dim3 grid((nx + RT_DN_TILE - 1u) / RT_DN_TILE, (rows + RT_DN_TILE - 1u) / RT_DN_TILE), block(RT_DN_TILE, RT_DN_TILE);
+    const int R = (int)d.radius;
+    const float k2 = d.strength * d.strength;
+    const size_t lds = nlm_lds_bytes(1u, d.radius, d.patch);
+#define FEATURES_PATCH(F) hipLaunchKernelGGL(k_denoise_features<F>, grid, block, lds, st, (const float*)c, (const float2*)yv, fmean, fvar, out, nx, rows, R, k2, a)
+    switch (d.patch) {
+    case 0u: FEATURES_PATCH(0); break;
+    case 1u: FEATURES_PATCH(1); break;
+    case 2u: FEATURES_PATCH(2); break;
+    default: FEATURES_PATCH(3); break;
+    }
+#undef FEATURES_PATCH
+}
+
+int rt_accum_denoise_features(RtCtx* ctx, const RtDenoise* dn, const RtFeatureGuide* guide, float* out_rgb_f32, uint8_t* out_rgb8) {
+    if (!ctx) return RT_ERR_INVALID;
+    const RtCtx::Accum& acc = ctx->accum;
+    const DenoiseCall call{"rt_accum_denoise_features", RT_DENOISE_DEFAULT_STRENGTH,
+                           acc.open && !acc.features ? "the accumulation does not track features (rt_accum_track_features)" : nullptr, 2u, "there is no variance yet"};
+    return denoise_run(
+        ctx, call, dn, out_rgb_f32, out_rgb8,
+        [&]() -> int {
+            if (const char* why = feature_guide_invalid(guide)) return fail(ctx, RT_ERR_INVALID, std::string("rt_accum_denoise_features: ") + why);
+            if (features_in_window(acc.first, acc.done, acc.features) < 2u)
+                return fail(ctx, RT_ERR_STATE, "rt_accum_denoise_features: fewer than 2 feature samples were taken: the features have no variance yet");
+            return RT_OK;
+        },
+        [&](const AccumReader& r, const RtDenoise& d, const float*& img) -> int {
+            const size_t npix = acc.npix;
+            int rc;
+            if ((rc = ensure_nlm(ctx, npix, 1u)) || (rc = ensure(ctx, ctx->dn_feat, features_guide_bytes(npix)))) return rc;
+            float* fmean = ctx->dn_feat.as<float>();
+            float* fvar = fmean + RT_FEATURES_MEAN_FLOATS * npix;
+            enqueue_denoise_inputs(ctx, r);
+            hipLaunchKernelGGL(k_features_inputs, r.grid, dim3(256), 0, r.st, ctx->accum_features.as<const uint4>(), fmean, fvar, r.nx, r.rows, r.tiles_per_row, r.tile_pixels);
+            launch_denoise_features(r.st, ctx->dn_c.as<float>(), ctx->dn_yv.as<float2>(), fmean, fvar, ctx->dn_out.as<float>(), r.nx, r.rows, d, *guide);
+            img = ctx->dn_out.as<const float>();
+            return RT_OK;
+        });
+}
+
+int rt_debug_denoise_features(RtCtx* ctx, uint32_t nx, uint32_t rows, const float* rgb, const float* y, const float* v, const float* feat_mean, const float* feat_var,
+                              const RtDenoise* dn, const RtFeatureGuide* guide, float* out_rgb_f32) {
+    if (!ctx) return RT_ERR_INVALID;
+    const char* who = "rt_debug_denoise_features";
+    if (!rgb || !y || !v || !feat_mean || !feat_var || !out_rgb_f32) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": NULL array");
+    if (nx == 0u || rows == 0u || (uint64_t)nx * rows > (1ull << 28)) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": nx * rows must be 1 .. 2^28");
+    RtDenoise d;
+    int rc = denoise_params(ctx, dn, d, who);
+    if (rc) return rc;
+    if (const char* why = feature_guide_invalid(guide)) return fail(ctx, RT_ERR_INVALID, std::string(who) + ": " + why);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t npix = (size_t)nx * rows;
+    if ((rc = ensure_nlm(ctx, npix, 1u)) || (rc = ensure(ctx, ctx->dn_feat, features_guide_bytes(npix)))) return rc;
+    std::vector<float2> g(npix);
+    for (size_t k = 0; k < npix; ++k) g[k] = make_float2(y[k], v[k]);
+    const hipStream_t st = ctx->stream;
+    float* fmean = ctx->dn_feat.as<float>();
+    float* fvar = fmean + RT_FEATURES_MEAN_FLOATS * npix;
+    RT_HIP(ctx, hipMemcpyAsync(ctx->dn_c.p, rgb, npix * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    RT_HIP(ctx, hipMemcpyAsync(ctx->dn_yv.p, g.data(), npix * sizeof(float2), hipMemcpyHostToDevice, st));
+    RT_HIP(ctx, hipMemcpyAsync(fmean, feat_mean, npix * RT_FEATURES_MEAN_FLOATS * sizeof(float), hipMemcpyHostToDevice, st));
+    RT_HIP(ctx, hipMemcpyAsync(fvar, feat_var, npix * RT_FEATURES_VAR_FLOATS * sizeof(float), hipMemcpyHostToDevice, st));
+    launch_denoise_features(st, ctx->dn_c.as<float>(), ctx->dn_yv.as<float2>(), fmean, fvar, ctx->dn_out.as<float>(), nx, rows, d, *guide);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(out_rgb_f32, ctx->dn_out.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
     return RT_OK;
 }
 

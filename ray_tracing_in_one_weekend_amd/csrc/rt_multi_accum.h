@@ -117,6 +117,8 @@ extern "C" {
 int rt_multi_accum_begin(RtMulti* m, const RtCamera* cam, const RtParams* params, uint32_t first_sample, uint32_t track, uint32_t M) {
     if (!m) return RT_ERR_INVALID;
     if (!cam || !params) return multi_fail(m, RT_ERR_INVALID, "rt_multi_accum_begin: camera/params NULL");
+    if (track & RT_MULTI_UNSUPPORTED_FEATURES)
+        return multi_fail(m, RT_ERR_UNSUPPORTED, "rt_multi_accum_begin: RT_MULTI_UNSUPPORTED_FEATURES: first-hit features of shards are not covered (rtow_mi355x.h \"First-hit features\")");
     if (track & ~(RT_MULTI_TRACK_CHANNELS | RT_MULTI_TRACK_HALVES | RT_MULTI_TRACK_BUCKETS))
         return multi_fail(m, RT_ERR_INVALID, "rt_multi_accum_begin: track holds a bit that is no RT_MULTI_TRACK_*");
     if ((track & RT_MULTI_TRACK_BUCKETS) && (M < RT_BUCKETS_MIN || M > RT_BUCKETS_MAX))

@@ -13,12 +13,13 @@ import time
 
 import numpy as np
 
-from . import AccumBuckets, AccumFilter, AccumState, make_pixel_filter, pixel_filter_check, MultiRenderer, Renderer, RtError, Scene, display_check, glare_check, make_display, make_glare, make_params, make_select, select_check, output_file_name, register_default_images, save_png
+from . import make_feature_guide, feature_guide_check, AccumBuckets, AccumFeatures, AccumFilter, AccumState, features_check, make_pixel_filter, pixel_filter_check, MultiRenderer, Renderer, RtError, Scene, display_check, glare_check, make_display, make_glare, make_params, make_select, select_check, output_file_name, register_default_images, save_png
 from . import _ffi
 from .images import write_pfm
 
 # --robust without --buckets: of 5, 9 and 15 by the rule of RT_DENOISE_DEFAULT_STRENGTH on rendered frames (DESIGN.md "Sample buckets")
 DEFAULT_BUCKETS = 5
+DEFAULT_FEATURE_STRIDE = 4  # (11 % of a 64-sample add of sphere_scene at 1920 x 1080, 2.7 % of cornell_box: DESIGN.md 4.18)
 
 SCENES = ("test_sphere", "sphere_scene", "moving_sphere_scene", "quads_scene", "mesh_scene", "simple_light_scene", "cornell_box", "final_scene", "earth_env_scene",
           "pbr_sweep_scene")
@@ -127,7 +128,7 @@ def main(argv=None):
     ap.add_argument("--denoise-patch", type=int, default=1, metavar="F", help="patch radius, 0..%d" % _ffi.DENOISE_MAX_PATCH)
     ap.add_argument("--denoise-strength", type=float, default=None, metavar="K",
                     help="how many standard errors two pixels may differ and still be averaged (default %g)" % _ffi.DENOISE_DEFAULT_STRENGTH)
-    ap.add_argument("--denoise-guide", choices=("luminance", "channels", "halves"), default="luminance",
+    ap.add_argument("--denoise-guide", choices=("luminance", "channels", "halves", "features"), default="luminance",
                     help="what the filter measures distance on: the mean luminance and its variance (rt_accum_denoise), the three channels and "
                          "theirs (rt_accum_denoise_channels: 48 B per pixel more, keeps edges between colours of equal luminance), or, per half "
                          "of the samples, the luminance of the OTHER half (rt_accum_denoise_halves: 56 B per pixel more, default strength %g, "
@@ -213,6 +214,24 @@ def main(argv=None):
                          % (_ffi.FILTER_MIN_RADIUS, _ffi.FILTER_MAX_RADIUS))
     ap.add_argument("--filter-param", type=float, nargs="+", default=None, metavar="P",
                     help="with --pixel-filter gaussian: sigma (default 0.5); with mitchell: B C (default 1/3 1/3)")
+    ap.add_argument("--features", action="store_true",
+                    help="also keep the first-hit features of the accumulation — albedo, shading normal and depth of the primary hit, with their "
+                         "second moments (rt_accum_track_features: 64 B per pixel more) —, recomputed by a kernel of its own; the image is "
+                         "unchanged, and --checkpoint carries the records in FILE.features.npz, which --resume picks up.  Does not combine with "
+                         "--devices and --merge (the library refuses features on shards and in a merge), nor with --denoise-guide halves, "
+                         "--residual-target and --preview-every: the library would track both, but those three render through loops of "
+                         "this program that read no records and write no FILE.features.npz, so the option would cost time for nothing")
+    ap.add_argument("--feature-stride", type=int, default=None, metavar="K",
+                    help="with --features: every K-th sample, by absolute index, takes a feature sample, %d..%d (default %d)"
+                         % (_ffi.FEATURES_MIN_STRIDE, _ffi.FEATURES_MAX_STRIDE, DEFAULT_FEATURE_STRIDE))
+    ap.add_argument("--feature-k", type=float, default=None, metavar="K",
+                    help="with --denoise --denoise-guide features (which needs --features): the strength of the three feature distances of "
+                         "rt_accum_denoise_features (default %g, the 2013 paper's; smaller keeps more feature edges)" % _ffi.FEATURE_GUIDE_DEFAULT_K)
+    ap.add_argument("--demodulate", action="store_true",
+                    help="with --denoise-guide features: filter the colour divided by the albedo and multiply the albedo back (keeps texture detail)")
+    ap.add_argument("--albedo-out", default=None, metavar="FILE.pfm", help="with --features: write the mean albedo as a PFM")
+    ap.add_argument("--normal-out", default=None, metavar="FILE.pfm", help="with --features: write the mean shading normal as a PFM")
+    ap.add_argument("--depth-out", default=None, metavar="FILE.pfm", help="with --features: write the mean depth of the hits, in all three channels, as a PFM")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--devices", default=None, metavar="ID,ID,...",
                     help="render on these devices of the node at once (rt_multi_*): every device takes row-interleaved bands of the frame; the "
@@ -300,6 +319,24 @@ def main(argv=None):
                                      C=p[1] if want == 2 and p else None)
         if not pixel_filter_check(a.filter):
             ap.error("--pixel-filter: --filter-radius takes %g..%g, sigma must be > 0, every value finite" % (_ffi.FILTER_MIN_RADIUS, _ffi.FILTER_MAX_RADIUS))
+    if not a.features and (a.feature_stride is not None or a.albedo_out or a.normal_out or a.depth_out):
+        ap.error("--feature-stride, --albedo-out, --normal-out and --depth-out need --features")
+    if a.features:
+        if multi or a.merge or halves or a.preview_every:
+            ap.error("--features does not combine with --devices and --merge (rt_accum_track_features refuses shards, rt_accum_merge tracked "
+                     "features), nor with --denoise-guide halves, --residual-target and --preview-every (their loops here read no records)")
+        a.feature_stride = DEFAULT_FEATURE_STRIDE if a.feature_stride is None else a.feature_stride
+        if not features_check(a.feature_stride):
+            ap.error("--feature-stride takes %d..%d" % (_ffi.FEATURES_MIN_STRIDE, _ffi.FEATURES_MAX_STRIDE))
+    a.feature_guide = None
+    if a.denoise_guide == "features":
+        if not (a.denoise and a.features) or a.robust is not None or a.denoise_levels is not None:
+            ap.error("--denoise-guide features needs --denoise and --features, without --robust and --denoise-levels")
+        a.feature_guide = make_feature_guide(k=_ffi.FEATURE_GUIDE_DEFAULT_K if a.feature_k is None else a.feature_k, demodulate=a.demodulate)
+        if not feature_guide_check(a.feature_guide):
+            ap.error("--feature-k must be finite and > 0")
+    elif a.feature_k is not None or a.demodulate:
+        ap.error("--feature-k and --demodulate need --denoise-guide features")
     if a.denoise_levels is not None:
         if not a.denoise or a.denoise_guide == "halves" or a.residual_target is not None:
             ap.error("--denoise-levels needs --denoise with --denoise-guide luminance or channels")
@@ -350,7 +387,7 @@ def main(argv=None):
     progressive = a.adaptive_tolerance is not None or a.noise_target is not None or a.denoise
     if (a.hdr_out or a.glare_out) and (progressive or halves or a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets):
         ap.error("--hdr-out and --glare-out write the image of a plain render: they do not combine with the progressive options")
-    if a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets or a.filter is not None or (multi and progressive):
+    if a.checkpoint or a.resume or a.merge or a.first_sample is not None or a.want_buckets or a.filter is not None or a.features or (multi and progressive):
         if a.preview_every:
             ap.error("--checkpoint, --resume, --first-sample and --merge do not combine with --preview-every")
         if a.adaptive_tolerance is not None and a.noise_target is not None:
@@ -496,6 +533,18 @@ def render_with_state(a, rend, scene, flags, file_name, t0):
             rend.accum_import_filter(plane)
         elif a.filter is not None:
             rend.accum_track_filter(a.filter)
+        if state and a.features:  # likewise the feature records, under the same stride
+            try:
+                records = AccumFeatures.load(a.resume + ".features.npz")
+            except (OSError, ValueError, KeyError) as e:
+                print(f"error: --features with --resume needs {a.resume}.features.npz, the records checkpointed beside the state: {e}", file=sys.stderr)
+                return 2
+            if records.stride != a.feature_stride:
+                print(f"error: {a.resume}.features.npz was summed under stride {records.stride}, not --feature-stride {a.feature_stride}", file=sys.stderr)
+                return 2
+            rend.accum_import_features(records)
+        elif a.features:
+            rend.accum_track_features(a.feature_stride)
         done, steps, n_rays, seconds = (state.done if state else 0), 0, 0, 0.0
 
         def finished():
@@ -512,6 +561,8 @@ def render_with_state(a, rend, scene, flags, file_name, t0):
                 rend.accum_export_buckets().save(a.checkpoint + ".buckets.npz")
             if a.filter is not None:  # likewise the filter plane
                 rend.accum_export_filter().save(a.checkpoint + ".filter.npz")
+            if a.features:  # and the feature records
+                rend.accum_export_features().save(a.checkpoint + ".features.npz")
             rend.accum_export().save(a.checkpoint)
 
         while not finished():
@@ -544,6 +595,14 @@ def render_with_state(a, rend, scene, flags, file_name, t0):
         rgb8 = _denoised(a, rend)
     if a.filter is not None:
         rgb8 = rend.accum_filtered(want_rgb8=True)[1]
+    if a.features and (a.albedo_out or a.normal_out or a.depth_out):
+        feat = rend.accum_features()
+        if a.albedo_out:
+            write_pfm(a.albedo_out, feat["albedo"])
+        if a.normal_out:
+            write_pfm(a.normal_out, feat["normal"])
+        if a.depth_out:
+            write_pfm(a.depth_out, np.repeat(feat["depth"][..., None], 3, axis=2))
     rend.accum_end()
     print(f"elapsed {time.perf_counter() - t0:.3f} s", file=sys.stderr)
     save_png(file_name, rgb8)
@@ -563,6 +622,8 @@ def _denoised(a, rend):
         return rend.accum_denoise_robust(*a.robust_mode, a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
     if a.denoise_levels is not None:
         return rend.accum_denoise_multiscale(a.denoise_levels, a.denoise_guide, a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
+    if a.denoise_guide == "features":
+        return rend.accum_denoise_features(a.feature_guide, a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
     if a.denoise_guide == "channels":
         return rend.accum_denoise_channels(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
     return rend.accum_denoise(a.denoise_radius, a.denoise_patch, a.denoise_strength, want_rgb8=True)[1]
